@@ -16,6 +16,7 @@ committed N = 1 value), and the packed sufficient statistics are all-reduced ove
 
     python bench.py --gpus 1 --steps 200 --warmup 50    # the defaults
     python bench.py --gpus N ...        # WORLD_SIZE unset: starts N ranks itself (torchrun)
+    python bench.py ... --dump-outputs DIR   # + the statistics of the last timed step as DIR/<field>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -333,6 +334,19 @@ def workload_configs1(K, T):
 KERNEL_NAMES = ["prescan", "stitch", "fwdbwd", "finalize", "estep_total"]
 
 
+def dump_outputs(d, res):
+    """--dump-outputs: the reduced statistics of the last timed E-step, one float64 .npy per field (a few
+    KB in all).  The workload is seeded, so two builds run with the same arguments can be compared field
+    by field."""
+    os.makedirs(d, exist_ok=True)
+    fields = {"loglik": np.array([res.loglik]), "gamma0_sum": res.gamma0_sum, "transition_counts": res.C,
+              "state_counts": res.state_counts, "sum_gd": res.sum_gd, "sum_gdd": res.sum_gdd,
+              "symbol_counts": res.symbol_counts}
+    for name, a in fields.items():
+        if a is not None:
+            np.save(os.path.join(d, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 class Series(object):
     """This rank's share of a workload on its GPU and the timing protocol of the contract on it."""
 
@@ -394,6 +408,7 @@ class Series(object):
             kern_ms += eng.kernel_ms_all()
         rk.fence()
         self.elapsed = rk.max_over_ranks(time.perf_counter() - t0)
+        self.last_timed = self.host_np.copy()       # what the last timed step handed its caller
         self.allreduces_per_step = (self.allreduces - n0) / float(max(steps, 1))
         self.kern_ms = kern_ms / max(steps, 1)
         # a second window right behind the requested steps, untimed by the contract: what an EM loop of
@@ -1003,7 +1018,12 @@ def main():
     ap.add_argument("--oversubscribe", action="store_true",
                     help="TEST AID for boxes with fewer GPUs than ranks: ranks share GPUs "
                          "(local rank modulo device count) and the all-reduce runs over gloo")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the reduced statistics of the last one (configs[2]) as "
+                         "DIR/<field>.npy, float64 (rank 0; not with --only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if args.gpus > 1 and not launched:
@@ -1060,6 +1080,8 @@ def main():
     wl = workload_configs2(K, T)
     ser = Series(rk, wl, Kloc, rank * Kloc, chunk=args.chunk)
     ser.run(args.warmup, args.steps, 0 if args.no_steady else 40)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ser.eng.unpack(ser.last_timed))
     elapsed = ser.elapsed
     res = ser.res
     want = C2_LOGLIK_N1.get((K, T))

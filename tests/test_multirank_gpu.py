@@ -129,6 +129,24 @@ def test_bench_starts_its_own_ranks(launcher):
 
 
 @pytest.mark.gpu
+def test_bench_dumps_the_last_timed_step(launcher, tmp_path):
+    """`--dump-outputs DIR` writes the reduced statistics of the last timed configs[2] E-step as float64
+    .npy files: the log-likelihood of the line, unit gamma mass per time step, M = 64 symbol counts."""
+    K, T = 16, 30000
+    line = _bench_line(launcher, 1, ["--steps", "3", "--warmup", "1", "--ntraj", str(K), "--length", str(T),
+                                     "--no-cpu", "--no-secondary", "--dump-outputs", str(tmp_path)])
+    got = {f[:-4]: np.load(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))}
+    assert sorted(got) == ["gamma0_sum", "loglik", "state_counts", "symbol_counts", "transition_counts"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["loglik"].shape == (1,) and got["loglik"][0] == line["loglik"]
+    assert got["transition_counts"].shape == (8, 8) and got["symbol_counts"].shape == (8, 64)
+    np.testing.assert_allclose(got["gamma0_sum"].sum(), K, rtol=1e-9)
+    np.testing.assert_allclose(got["state_counts"].sum(), K * T, rtol=1e-9)
+    np.testing.assert_allclose(got["symbol_counts"].sum(axis=1), got["state_counts"], rtol=1e-9)
+    np.testing.assert_allclose(got["transition_counts"].sum(), K * (T - 1), rtol=1e-9)
+
+
+@pytest.mark.gpu
 def test_bench_collective_path_on_rccl_with_one_rank(launcher):
     """The driver launches `bench.py --gpus N` under torch.distributed.run with backend nccl (= RCCL).  A
     one-GPU box can run that code path with ONE rank: RANK / WORLD_SIZE in the environment make the bench take
@@ -155,24 +173,25 @@ def test_bench_collective_path_on_rccl_with_one_rank(launcher):
 
 
 @pytest.mark.gpu
-def test_bench_eight_rank_dry_run(launcher):
-    """The 8-GPU job of BASELINE configs[2] before an 8-GPU node exists: `bench.py --gpus 8
-    --oversubscribe` (eight ranks sharing this box's GPU, the sum over gloo -- everything else is the
-    production path): 1024 trajectories in 128-trajectory shards, rank r drawing trajectories
-    r*128 .. by global index, ONE all-reduce per step, identical reduced statistics on every rank,
-    and the log-likelihood of the one-rank run on the same (short) trajectories.  No scaling number
-    is expected from it."""
+def test_bench_four_rank_dry_run(launcher):
+    """A multi-GPU job of BASELINE configs[2] on one GPU: `bench.py --gpus 4 --oversubscribe` (four ranks
+    sharing this box's GPU, the sum over gloo -- everything else is the production path): 1024
+    trajectories in 256-trajectory shards, rank r drawing trajectories r*256 .. by global index, ONE
+    all-reduce per step, identical reduced statistics on every rank, and the log-likelihood of the
+    one-rank run on the same (short) trajectories.  Four ranks rather than the eight of a full node: with
+    this pytest process five processes hold the one device, eight ranks would make it nine.  No scaling
+    number is expected from it."""
     small = ["--steps", "2", "--warmup", "1", "--ntraj", "1024", "--length", "3000", "--no-cpu",
              "--no-secondary", "--no-steady"]
     one = _bench_line(launcher, 1, small)
-    eight = _bench_line(launcher, 8, small, timeout=1500)
-    assert eight["n_gpus"] == 8 and eight["scaling"] == "strong"
-    assert eight["config"]["trajectories_per_gpu"] == 128 and eight["config"]["trajectories_total"] == 1024
-    assert eight["config"]["allreduces_per_step"] == 1.0
-    assert eight["statistics_identical_on_all_ranks"] is True
-    assert abs(eight["loglik"] - one["loglik"]) <= 1e-12 * abs(one["loglik"])
-    assert eight["roofline"]["alg_bytes_per_launch"] == 136 * 128 * 3000
-    assert abs(eight["value"] - 1024 * 3000 * 2 / (eight["ms_per_step"] * 2e-3)) < 1e-6 * eight["value"]
+    four = _bench_line(launcher, 4, small, timeout=1500)
+    assert four["n_gpus"] == 4 and four["scaling"] == "strong"
+    assert four["config"]["trajectories_per_gpu"] == 256 and four["config"]["trajectories_total"] == 1024
+    assert four["config"]["allreduces_per_step"] == 1.0
+    assert four["statistics_identical_on_all_ranks"] is True
+    assert abs(four["loglik"] - one["loglik"]) <= 1e-12 * abs(one["loglik"])
+    assert four["roofline"]["alg_bytes_per_launch"] == 136 * 256 * 3000
+    assert abs(four["value"] - 1024 * 3000 * 2 / (four["ms_per_step"] * 2e-3)) < 1e-6 * four["value"]
 
 
 @pytest.mark.gpu

@@ -1,9 +1,10 @@
 """Pins the CPU oracle (oracle/bhmm_oracle.c) to the reference.
 
 Two anchors: (1) the golden fixtures captured from the reference's own C and Python
-kernels (tests/golden/gen_golden.py); (2) oracle/_ref -- the reference C sources compiled
-in place -- on fresh random inputs, where the restatement must be BIT-identical
-(same operation order, no contraction).  Mirrors bhmm/tests/test_hidden.py:265-335.
+kernels (tests/golden/gen_golden.py); (2) the outputs of oracle/_ref -- the reference C
+sources compiled in place -- on seeded random inputs (tests/golden/gen_golden_bitident.py),
+which the restatement must reproduce BIT-identically (same operation order, no contraction).
+Mirrors bhmm/tests/test_hidden.py:265-335.
 """
 import hashlib
 
@@ -179,33 +180,25 @@ def test_path_counts():
     assert np.array_equal(n0, [1, 1, 1])
 
 
-@pytest.mark.skipif(not orc.ref_available(), reason="oracle/_ref not built")
 @pytest.mark.parametrize("N,T,seed", [(2, 50, 1), (3, 1000, 2), (8, 5000, 3), (17, 300, 4)])
-def test_bit_identical_to_compiled_reference(N, T, seed):
-    rng = np.random.default_rng(seed)
-    A = rng.random((N, N))
-    A /= A.sum(axis=1)[:, None]
-    pi = rng.dirichlet(np.ones(N))
-    mu = np.linspace(-3, 3, N)
-    sig = rng.uniform(0.3, 1.5, N)
-    obs = rng.normal(0, 3, T)
+def test_bit_identical_to_compiled_reference(golden, N, T, seed):
+    """Against the outputs of oracle/_ref on seeded random inputs, stored by
+    tests/golden/gen_golden_bitident.py (p_obs, alpha, beta as digests of their bytes)."""
+    g = golden("ref_bitident")
+    p = "N%d_T%d_s%d_" % (N, T, seed)
+    A, pi, mu, sig, obs = g[p + "A"], g[p + "pi"], g[p + "mu"], g[p + "sigma"], g[p + "obs"]
     pobs = orc.pobs_gaussian(obs, mu, sig, ignore_outliers=False)
-    assert np.array_equal(pobs, orc.ref_pobs_gaussian(obs, mu, sig))
+    assert sha1(pobs) == str(g[p + "pobs_sha1"])
     logL, alpha = orc.forward(A, pobs, pi)
-    rl, ra = orc.ref_forward(A, pobs, pi)
-    assert logL == rl and np.array_equal(alpha, ra)
+    assert logL == float(g[p + "logL"]) and sha1(alpha) == str(g[p + "alpha_sha1"])
     beta = orc.backward(A, pobs)
-    assert np.array_equal(beta, orc.ref_backward(A, pobs))
-    assert np.array_equal(orc.transition_counts(alpha, beta, A, pobs),
-                          orc.ref_transition_counts(alpha, beta, A, pobs))
-    assert np.array_equal(orc.viterbi(A, pobs, pi), orc.ref_viterbi(A, pobs, pi))
-    assert np.array_equal(orc.sample_path(alpha, A, seed=11),
-                          orc.ref_sample_path(alpha, A, pobs, seed=11))
+    assert sha1(beta) == str(g[p + "beta_sha1"])
+    assert np.array_equal(orc.transition_counts(alpha, beta, A, pobs), g[p + "C"])
+    assert np.array_equal(orc.viterbi(A, pobs, pi), g[p + "viterbi"])
+    assert np.array_equal(orc.sample_path(alpha, A, seed=11), g[p + "sample_path_seed11"])
     np.testing.assert_allclose(orc.gamma(alpha, beta), orc.ref_gamma(alpha, beta), rtol=1e-14)
     w = orc.gamma(alpha, beta)
-    o_int = rng.integers(0, 5, T).astype(np.int32)
-    assert np.array_equal(orc.update_pout(o_int, w, np.zeros((N, 5))),
-                          orc.ref_update_pout(o_int, w, np.zeros((N, 5))))
+    assert np.array_equal(orc.update_pout(g[p + "o_int"], w, np.zeros((N, 5))), g[p + "pout"])
 
 
 def test_longdouble_recursions_agree_with_the_oracle_in_the_normal_range():
