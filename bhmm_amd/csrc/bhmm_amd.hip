@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "host_common.hpp"
+#include "host_internal.hpp"
 #include "plan.hpp"
 #include "estep_sweep.hpp"
 
@@ -25,16 +26,13 @@ int hip_fail(hipError_t e, const char *what)
     return e == hipErrorOutOfMemory ? BHMM_ERR_NO_MEM : BHMM_ERR_HIP;
 }
 
-static int invalid(const std::string &msg)
+int invalid_arg(const std::string &msg)
 {
     g_err = msg;
     return BHMM_ERR_INVALID;
 }
-int invalid_arg(const std::string &msg) { return invalid(msg); }
 
-Chunks chunks_pub(const bhmm_ctx *c);
-static Chunks chunks_of(const bhmm_ctx *c) { return chunks_pub(c); }
-Chunks chunks_pub(const bhmm_ctx *c)
+Chunks chunks_of(const bhmm_ctx *c)
 {
     Chunks ch;
     ch.traj = c->d_ctraj.p;
@@ -77,7 +75,7 @@ int replan_for_warmup(bhmm_ctx *c);
 
 // componentwise relative tolerance of the boundary check (k_spec_check / k_tail)
 // boundary tolerance of the time-split E-step, N <= 8: the context's spec_tol (option, default 1e-11)
-#define SPEC_TOL (c->spec_tol)
+#define SPEC_TOL (c->opt.spec_tol)
 
 // One E-step launch sequence for a fixed padded N.
 template <int N>
@@ -152,7 +150,7 @@ struct Runner {
                                    (const void *)c->d_obs_ci.p, (const void *)c->d_obs_rm.p,
                                    (const int64_t *)c->d_offsets.p, (const double *)c->d_Bt.p,
                                    c->d_aentry.p, c->d_bexit.p, c->d_aexit.p, c->d_bentry.p,
-                                   c->spec_W, c->d_ws.p,
+                                   c->ds.spec_W, c->d_ws.p,
                                    store_gamma ? c->d_gamma_ci.p : (double *)nullptr, c->d_logLc.p,
                                    c->d_gamma0.p, c->d_partials.p, c->d_dpartials.p, flag_words,
                                    c->d_ea.p, Carry());
@@ -162,7 +160,7 @@ struct Runner {
             // path to report zero / denormal vectors; everything else runs the careful one
             // (it rescales only every few steps: emission values must stay far from the
             // exponent range -- caller-supplied pobs and very narrow gaussians do not qualify)
-            bool fast = SPEC && !store_gamma && !c->careful && KIND != EMIT_EXPL;
+            bool fast = SPEC && !store_gamma && !c->ds.careful && KIND != EMIT_EXPL;
             if (KIND == EMIT_GAUSS)
                 for (int i = 0; i < c->n; ++i)
                     fast = fast && m.e2[i] < 1048576.0;
@@ -187,7 +185,7 @@ struct Runner {
                                            (const void *)c->d_obs_ci.p, (const void *)c->d_obs_rm.p,
                                            (const int64_t *)c->d_offsets.p,
                                            (const double *)c->d_Bt.p, c->d_aentry.p, c->d_bexit.p,
-                                           c->d_aexit.p, c->d_bentry.p, c->spec_W, c->d_ws.p,
+                                           c->d_aexit.p, c->d_bentry.p, c->ds.spec_W, c->d_ws.p,
                                            (double *)nullptr, c->d_logLc.p, c->d_gamma0.p,
                                            c->d_partials.p, c->d_dpartials.p, flag_words, c->d_ea.p,
                                            cy);
@@ -196,7 +194,7 @@ struct Runner {
                     // boundary vectors carried between E-steps (decided by estep_kind): P1 starts its
                     // warm-ups from them, P2 captures beta for the next E-step
                     Carry c1, c2;
-                    if (c->carry_use > 0) {
+                    if (c->ds.carry_use > 0) {
                         c1.a_in = c->d_carry_a.p;
                         c1.b_in = c->d_carry_b.p;
                         c1.da = c->d_carry_da.p;
@@ -206,8 +204,8 @@ struct Runner {
                                       sm1, c1)))
                         return rc;
                     BHMM_HIP(hipGetLastError());
-                    c2.cap = c->carry_cap;
-                    if (c->carry_cap > 0 && c->carry_store) {
+                    c2.cap = c->ds.carry_cap;
+                    if (c->ds.carry_cap > 0 && c->carry_store) {
                         // (P1 has consumed the old vectors: the same buffers take the new ones)
                         BHMM_HIP(hipMemsetAsync(c->d_carry_db.p, 0, (size_t)c->Gp * sizeof(int32_t),
                                                 c->stream));
@@ -215,18 +213,18 @@ struct Runner {
                         c2.db_out = c->d_carry_db.p;
                     }
                     rc = launch2(k_estep<N, KIND, SPEC, false, false, PH_P2>, nblk, m, sm, c2);
-                    if (rc == BHMM_OK && c->carry_cap > 0 && c->carry_store) {
+                    if (rc == BHMM_OK && c->ds.carry_cap > 0 && c->carry_store) {
                         BHMM_HIP(hipGetLastError());
                         hipLaunchKernelGGL((k_carry_alpha<N>), dim3((c->G + 255) / 256), dim3(256), 0,
                                            c->stream, ch, c->G, (const double *)c->d_ws.p,
                                            c->carry_Wout, c->d_carry_a.p, c->d_carry_da.p);
                     }
                 } else {
-                    c->carry_cap = 0;
+                    c->ds.carry_cap = 0;
                     rc = launch(k_estep<N, KIND, SPEC, false, false>);
                 }
             } else {
-                c->carry_cap = 0; // (no capture outside the split launches)
+                c->ds.carry_cap = 0; // (no capture outside the split launches)
                 rc = launch(k_estep<N, KIND, SPEC, true, true>);
             }
             if (rc)
@@ -417,7 +415,7 @@ struct Runner {
         BHMM_HIP(hipStreamSynchronize(c->stream)); // starts / curve are temporaries
         int last = -1;
         for (int w = 0; w < Wmax; ++w)
-            if (std::max(curve[w], curve[Wmax + w]) >= (float)(0.01 * c->spec_tol)) // (default: 1e-13)
+            if (std::max(curve[w], curve[Wmax + w]) >= (float)(0.01 * c->opt.spec_tol)) // (default: 1e-13)
                 last = w;
         int W = last + 2; // steps needed to get below the target and stay there
         W = (int)std::ceil(1.15 * W);
@@ -430,57 +428,57 @@ struct Runner {
     static int estep_kind(bhmm_ctx *c, const Model<N> &m, double *stats_dev, int flags)
     {
         int rc;
-        if (c->spec_enabled && !c->spec_calibrated) {
+        if (c->opt.spec_enabled && !c->ds.spec_calibrated) {
             // first E-step on these observations: measure how fast this model forgets
-            c->spec_calibrated = true;
+            c->ds.spec_calibrated = true;
             c->spec_probes_left = 2;
             int W = 0;
             if ((rc = probe_warmup<KIND>(c, m, &W)))
                 return rc;
             if (W > 0)
-                c->spec_W = W;
-            if (c->chunk_mult > 1 && (int64_t)c->spec_W * 16 > c->L && (rc = replan_coarse(c)))
+                c->ds.spec_W = W;
+            if (c->chunk_mult > 1 && (int64_t)c->ds.spec_W * 16 > c->L && (rc = replan_coarse(c)))
                 return rc;
             if ((rc = replan_for_warmup(c)))
                 return rc;
         }
-        if (c->spec_enabled) {
+        if (c->opt.spec_enabled) {
             // ---- boundary vectors carried from the previous E-step (estep_sweep.hpp: Carry) ----
             // decades of forgetting per step, from the calibrated warm-up (1e-13 after W / 1.15 steps)
             // (the calibration is conservative -- 1e-13 on 256 sampled stretches plus 15 % --; what the
             // boundary check of a full warm-up actually measured is the better estimate, when known)
-            double rdec = -log10(0.01 * c->spec_tol) * 1.15 / std::max(c->spec_W, 16);
-            if (c->carry_rdec > 0.0)
-                rdec = std::min(rdec, c->carry_rdec);
-            bool eligible = c->carry_enabled && ESTEP_SPLIT && KIND != EMIT_EXPL && !c->careful &&
+            double rdec = -log10(0.01 * c->opt.spec_tol) * 1.15 / std::max(c->ds.spec_W, 16);
+            if (c->ds.carry_rdec > 0.0)
+                rdec = std::min(rdec, c->ds.carry_rdec);
+            bool eligible = c->opt.carry_enabled && ESTEP_SPLIT && KIND != EMIT_EXPL && !c->ds.careful &&
                             !(flags & BHMM_FLAG_STORE_GAMMA) && c->G > c->K;
             if (KIND == EMIT_GAUSS) // (the branch-free split launches only, see fwdbwd)
                 for (int i = 0; i < c->n; ++i)
                     eligible = eligible && m.e2[i] < 1048576.0;
             const double delta = c->carry_delta;
-            c->carry_use = 0;
-            if (eligible && c->carry_valid && delta > 0.0 && delta <= 0.05) {
+            c->ds.carry_use = 0;
+            if (eligible && c->ds.carry_valid && delta > 0.0 && delta <= 0.05) {
                 // predicted boundary deviation of a warm-up of carry_Wc steps from vectors that are
                 // off by kappa * delta
-                const double pred = c->carry_kappa * delta * pow(10.0, -rdec * c->carry_Wc);
+                const double pred = c->ds.carry_kappa * delta * pow(10.0, -rdec * c->carry_Wc);
                 if (pred <= 0.3 * SPEC_TOL)
-                    c->carry_use = c->carry_Wc;
+                    c->ds.carry_use = c->carry_Wc;
             }
             auto plan_capture = [&]() {
                 // capture for the NEXT E-step, sized for twice this step's model change
-                c->carry_cap = c->carry_Wout = 0;
+                c->ds.carry_cap = c->carry_Wout = 0;
                 c->carry_store = false;
                 if (!eligible || (c->d_carry_a.ensure((size_t)c->Gp * N)) ||
                     (c->d_carry_b.ensure((size_t)c->Gp * N)) || (c->d_carry_da.ensure(c->Gp)) ||
                     (c->d_carry_db.ensure(c->Gp)))
                     return;
                 const double dn = delta > 0.0 ? 2.0 * delta : 1e-3;
-                const double need = (log10(c->carry_kappa * dn) - log10(0.1 * SPEC_TOL)) / rdec;
+                const double need = (log10(c->ds.carry_kappa * dn) - log10(0.1 * SPEC_TOL)) / rdec;
                 int Wc = ((int)ceil(std::max(need, 16.0)) + 7) / 8 * 8;
-                if (Wc > (int)(0.85 * c->spec_W) || Wc + 16 > c->L)
+                if (Wc > (int)(0.85 * c->ds.spec_W) || Wc + 16 > c->L)
                     return; // not worth it / chunks too short
                 c->carry_Wout = Wc;
-                c->carry_cap = Wc; // beta at local step Wc: Wc + 1 warm-up steps
+                c->ds.carry_cap = Wc; // beta at local step Wc: Wc + 1 warm-up steps
                 // a model identical to the previous call's: the sweep is split at the same place (it
                 // must round like the call before, see Carry::cap) but nothing is stored -- carried
                 // starts are only used after a change, and a caller that repeats E-steps on a fixed
@@ -489,53 +487,53 @@ struct Runner {
             };
             for (int attempt = 0; attempt < 3; ++attempt) {
                 bool ok = false;
-                const int W_tried = c->spec_W;
-                const int carried = c->carry_use;
+                const int W_tried = c->ds.spec_W;
+                const int carried = c->ds.carry_use;
                 plan_capture();
                 if ((rc = estep_spec<KIND>(c, m, stats_dev, flags, &ok)))
                     return rc;
                 if (ok) {
                     if (carried > 0) {
                         // what the check measured bounds the sensitivity for the next prediction
-                        const double keff = (double)c->spec_last_dev /
+                        const double keff = (double)c->last.spec_last_dev /
                                             (delta * pow(10.0, -rdec * carried));
-                        c->carry_kappa = std::min(std::max(std::max(0.5 * c->carry_kappa, 8.0 * keff), 1.0), 1e8);
-                        c->carry_ok++;
+                        c->ds.carry_kappa = std::min(std::max(std::max(0.5 * c->ds.carry_kappa, 8.0 * keff), 1.0), 1e8);
+                        c->last.carry_ok++;
                     }
-                    if (carried == 0 && c->spec_last_dev > 0.f && c->spec_last_dev < 1e-6f) {
+                    if (carried == 0 && c->last.spec_last_dev > 0.f && c->last.spec_last_dev < 1e-6f) {
                         // a full warm-up of spec_W steps from the uniform vector (start error O(1))
                         // left this deviation at the worst boundary
-                        const double rr = -log10((double)c->spec_last_dev) / std::max(c->spec_W, 16);
-                        c->carry_rdec = c->carry_rdec > 0.0 ? std::min(c->carry_rdec, rr) : rr;
+                        const double rr = -log10((double)c->last.spec_last_dev) / std::max(c->ds.spec_W, 16);
+                        c->ds.carry_rdec = c->ds.carry_rdec > 0.0 ? std::min(c->ds.carry_rdec, rr) : rr;
                     }
-                    c->carry_last_W = carried;
-                    c->carry_valid = c->carry_cap > 0 && c->carry_store;
+                    c->last.carry_last_W = carried;
+                    c->ds.carry_valid = c->ds.carry_cap > 0 && c->carry_store;
                     c->carry_Wc = c->carry_Wout;
-                    c->carry_use = 0;
+                    c->ds.carry_use = 0;
                     return BHMM_OK;
                 }
-                c->carry_valid = false;
-                if (carried > 0 && !c->careful_retry) {
+                c->ds.carry_valid = false;
+                if (carried > 0 && !c->ds.careful_retry) {
                     // shortened warm-ups did not verify: same call again with full ones
-                    c->carry_kappa = std::min(c->carry_kappa * 30.0, 1e8);
-                    c->carry_use = 0;
+                    c->ds.carry_kappa = std::min(c->ds.carry_kappa * 30.0, 1e8);
+                    c->ds.carry_use = 0;
                     continue;
                 }
-                c->carry_use = 0;
-                if (!c->careful_retry) {
+                c->ds.carry_use = 0;
+                if (!c->ds.careful_retry) {
                     // boundaries did not verify: exact pipeline now; for the next call measure
                     // the curve again (the model has moved), never below +25 %
-                    if (c->spec_enabled && !c->spec_W_fixed && c->spec_probes_left > 0) {
+                    if (c->opt.spec_enabled && !c->opt.spec_W_fixed && c->spec_probes_left > 0) {
                         --c->spec_probes_left;
                         int W = 0;
                         if ((rc = probe_warmup<KIND>(c, m, &W)))
                             return rc;
                         if (W > 0)
-                            c->spec_W = std::max(W, (W_tried * 5 / 4 + 3) / 4 * 4);
+                            c->ds.spec_W = std::max(W, (W_tried * 5 / 4 + 3) / 4 * 4);
                     }
                     break;
                 }
-                c->careful_retry = false; // zero / denormal vectors: same path, careful kernel
+                c->ds.careful_retry = false; // zero / denormal vectors: same path, careful kernel
             }
         }
         rc = prescan_stitch<KIND>(c, m);
@@ -665,36 +663,36 @@ struct Runner {
     {
         float dev;
         memcpy(&dev, &words[1], sizeof(float));
-        c->spec_last_dev = dev;
+        c->last.spec_last_dev = dev;
         *verified = words[0] == 0;
         if (words[2] != 0) {
             // the branch-free sweep met a zero / denormal vector (an all-zero emission row,
             // outputmodel.py:126-130): its statistics are void, repeat with the careful kernel
             // and keep using that one for this set of observations
             *verified = false;
-            c->careful = true;
-            c->careful_retry = true;
+            c->ds.careful = true;
+            c->ds.careful_retry = true;
             return BHMM_OK;
         }
         if (*verified) {
             c->prefetched = results_on_host;
-            c->spec_ok++;
-        } else if (c->carry_use > 0) {
+            c->last.spec_ok++;
+        } else if (c->ds.carry_use > 0) {
             // the shortened warm-ups from carried vectors did not verify: the caller repeats with
             // full warm-ups; this says nothing about the warm-up length itself
-            c->carry_fail++;
+            c->last.carry_fail++;
         } else {
             // lengthen the warm-up for the next call; give up once it would cost more than the
             // prescan (slowly mixing model / uninformative data)
-            c->spec_fail++;
-            if (c->spec_W >= 8192 || c->spec_W >= 2 * c->Lmax) {
-                c->spec_enabled = false;
+            c->last.spec_fail++;
+            if (c->ds.spec_W >= 8192 || c->ds.spec_W >= 2 * c->Lmax) {
+                c->opt.spec_enabled = false;
             } else {
                 // the deviation decays geometrically with the warm-up length: extrapolate to a
                 // tenth of the tolerance (at least +25 %, at most x8 per failure)
-                const double d = std::min(std::max((double)c->spec_last_dev, 1e-300), 0.5);
+                const double d = std::min(std::max((double)c->last.spec_last_dev, 1e-300), 0.5);
                 const double f = std::min(std::max(log(0.1 * SPEC_TOL) / log(d), 1.25), 8.0);
-                c->spec_W = std::max(c->spec_W + 4, ((int)ceil(c->spec_W * f) + 3) / 4 * 4);
+                c->ds.spec_W = std::max(c->ds.spec_W + 4, ((int)ceil(c->ds.spec_W * f) + 3) / 4 * 4);
             }
         }
         return BHMM_OK;
@@ -737,7 +735,7 @@ struct Runner {
         hipLaunchKernelGGL(kern, dim3(c->Gp / 64), dim3(32 * N), sm, c->stream, m, ch,
                            (const void *)c->d_obs_ci.p, (const void *)c->d_obs_rm.p,
                            (const int64_t *)c->d_offsets.p, (const double *)c->d_Bt.p, c->d_aentry.p,
-                           c->d_bexit.p, c->d_aexit.p, c->d_bentry.p, c->spec_W, c->d_ws.p,
+                           c->d_bexit.p, c->d_aexit.p, c->d_bentry.p, c->ds.spec_W, c->d_ws.p,
                            reinterpret_cast<double *>(c->d_ws32.p), c->d_logLc.p, c->d_gamma0.p,
                            c->d_partials.p, c->d_dpartials.p, c->d_specres.p, c->d_ea.p, Carry());
         BHMM_HIP(hipGetLastError());
@@ -749,23 +747,23 @@ struct Runner {
     static int forward_kind(bhmm_ctx *c, const Model<N> &m)
     {
         int rc;
-        if (c->spec_enabled && !c->spec_calibrated) {
-            c->spec_calibrated = true;
+        if (c->opt.spec_enabled && !c->ds.spec_calibrated) {
+            c->ds.spec_calibrated = true;
             c->spec_probes_left = 2;
             int W = 0;
             if ((rc = probe_warmup<KIND>(c, m, &W)))
                 return rc;
             if (W > 0)
-                c->spec_W = W;
-            if (c->chunk_mult > 1 && (int64_t)c->spec_W * 16 > c->L && (rc = replan_coarse(c)))
+                c->ds.spec_W = W;
+            if (c->chunk_mult > 1 && (int64_t)c->ds.spec_W * 16 > c->L && (rc = replan_coarse(c)))
                 return rc;
             if ((rc = replan_for_warmup(c)))
                 return rc;
         }
-        if (c->spec_enabled) {
+        if (c->opt.spec_enabled) {
             for (int attempt = 0; attempt < 2; ++attempt) {
                 bool ok = false;
-                bool fast = !c->careful && KIND != EMIT_EXPL;
+                bool fast = !c->ds.careful && KIND != EMIT_EXPL;
                 if (KIND == EMIT_GAUSS)
                     for (int i = 0; i < c->n; ++i)
                         fast = fast && m.e2[i] < 1048576.0;
@@ -792,9 +790,9 @@ struct Runner {
                     return rc;
                 if (ok)
                     return BHMM_OK;
-                if (!c->careful_retry)
+                if (!c->ds.careful_retry)
                     break;
-                c->careful_retry = false;
+                c->ds.careful_retry = false;
             }
         }
         if ((rc = prescan_stitch<KIND>(c, m)))
@@ -861,7 +859,7 @@ static int plan_chunks(bhmm_ctx *c, int chunk, bool allow_mult = true, bool half
     const int K = c->K;
     plan::ChunkPlan p;
     if (!plan::plan_chunks(c->offsets, K, c->N, c->total, chunk, allow_mult, BLOCK, p, half))
-        return invalid("too many chunks");
+        return invalid_arg("too many chunks");
     c->chunk_mult = p.chunk_mult;
     c->L = p.L;
     c->traj_c0 = p.traj_c0;
@@ -899,26 +897,6 @@ static int plan_chunks(bhmm_ctx *c, int chunk, bool allow_mult = true, bool half
     }
     return BHMM_OK;
 }
-
-int forward_ci(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
-               const double *par1);
-int forward_ci_verdict(bhmm_ctx *c, bool *ok);
-int unpack_ws_rows(bhmm_ctx *c, double *dst_dev);
-// wide_api.hip (9..64 states)
-int wide_alloc(bhmm_ctx *c);
-int wide_forward(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
-                 const double *par1);
-int wide_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
-               const double *par1, double *stats_dev, int flags);
-int wide_backward(bhmm_ctx *c, const double *A);
-// gen_api.hip (more than 64 states)
-int gen_alloc(bhmm_ctx *c);
-int gen_forward(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
-                const double *par1);
-int gen_backward(bhmm_ctx *c, const double *A);
-int gen_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
-              double *stats_dev, int flags);
-
 
 static int stats_size(const bhmm_ctx *c)
 {
@@ -1012,21 +990,21 @@ static void collect_timing(bhmm_ctx *c)
     c->ev_pending = false;
     float ms = 0.f;
     if (c->ev_lean) { // sweep kernel, tail kernel; no prescan / stitch
-        c->last_ms[0] = c->last_ms[1] = 0.0;
+        c->last.ms[0] = c->last.ms[1] = 0.0;
         if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess)
-            c->last_ms[2] = ms;
+            c->last.ms[2] = ms;
         if (hipEventElapsedTime(&ms, c->ev[3], c->ev[4]) == hipSuccess)
-            c->last_ms[3] = ms;
+            c->last.ms[3] = ms;
         if (hipEventElapsedTime(&ms, c->ev[2], c->ev[4]) == hipSuccess)
-            c->last_ms[4] = ms;
+            c->last.ms[4] = ms;
         (void)hipGetLastError();
         return;
     }
     for (int i = 0; i < 4; ++i)
         if (hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]) == hipSuccess)
-            c->last_ms[i] = ms;
+            c->last.ms[i] = ms;
     if (hipEventElapsedTime(&ms, c->ev[0], c->ev[4]) == hipSuccess)
-        c->last_ms[4] = ms;
+        c->last.ms[4] = ms;
     (void)hipGetLastError();
 }
 
@@ -1056,7 +1034,7 @@ int bhmm_device_count(void)
 int bhmm_ctx_create(bhmm_ctx **out, int device, void *stream)
 {
     if (!out)
-        return invalid("out == NULL");
+        return invalid_arg("out == NULL");
     *out = nullptr;
     int ndev = bhmm_device_count();
     if (ndev <= 0) {
@@ -1064,7 +1042,7 @@ int bhmm_ctx_create(bhmm_ctx **out, int device, void *stream)
         return BHMM_ERR_NO_DEVICE;
     }
     if (device < 0 || device >= ndev)
-        return invalid("device ordinal out of range");
+        return invalid_arg("device ordinal out of range");
     BHMM_HIP(hipSetDevice(device));
     bhmm_ctx *c = new (std::nothrow) bhmm_ctx();
     if (!c)
@@ -1077,22 +1055,22 @@ int bhmm_ctx_create(bhmm_ctx **out, int device, void *stream)
         (void)hipGetLastError();
     }
     if (const char *e = getenv("BHMM_AMD_CARRY"))
-        c->carry_enabled = atoi(e) != 0;
+        c->opt.carry_enabled = atoi(e) != 0;
     if (const char *e = getenv("BHMM_AMD_SPEC"))
-        c->spec_enabled = atoi(e) != 0;
+        c->opt.spec_enabled = atoi(e) != 0;
     if (const char *e = getenv("BHMM_AMD_TILE"))
-        c->tile_enabled = atoi(e) != 0;
+        c->opt.tile_enabled = atoi(e) != 0;
     if (const char *e = getenv("BHMM_AMD_TILE_PER_CU"))
-        c->tile_per_cu = std::max(1, std::min(4, atoi(e)));
+        c->opt.tile_per_cu = std::max(1, std::min(4, atoi(e)));
     // (sweeps: the watched-draw machinery of draw_verify.hpp with a wide watch / with every watched draw treated as
     // a decision that did not stand, on whatever problems the sweep draws)
     if (const char *e = getenv("BHMM_AMD_DRAW_WATCH_TOL"))
-        c->draw_watch_tol = std::min(0.5, std::max(0.0, atof(e)));
+        c->opt.draw_watch_tol = std::min(0.5, std::max(0.0, atof(e)));
     if (const char *e = getenv("BHMM_AMD_DRAW_TEST_REDO"))
-        c->draw_test_redo = atoi(e) != 0;
+        c->opt.draw_test_redo = atoi(e) != 0;
     if (const char *e = getenv("BHMM_AMD_SPEC_W")) {
-        c->spec_W = std::max(1, atoi(e));
-        c->spec_W_fixed = true;
+        c->ds.spec_W = std::max(1, atoi(e));
+        c->opt.spec_W_fixed = true;
     }
     if (stream) {
         c->stream = static_cast<hipStream_t>(stream);
@@ -1235,11 +1213,11 @@ static int pack_observations(bhmm_ctx *c, const char *src_dev)
 // and more chunks mean more parallelism -- and only once per set of observations.
 int bhmm::replan_for_warmup(bhmm_ctx *c)
 {
-    if (!c->chunk_auto || c->replanned_half || c->chunk_mult > 1 || c->wide || c->gen)
+    if (!c->ds.chunk_auto || c->ds.replanned_half || c->chunk_mult > 1 || c->wide || c->gen)
         return BHMM_OK;
-    if ((int64_t)c->G * 10 < plan::default_chunk_count(c->N) * 9 || (double)c->L >= 1.6 * c->spec_W)
+    if ((int64_t)c->G * 10 < plan::default_chunk_count(c->N) * 9 || (double)c->L >= 1.6 * c->ds.spec_W)
         return BHMM_OK;
-    c->replanned_half = true;
+    c->ds.replanned_half = true;
     return replan_coarse(c, true);
 }
 
@@ -1256,26 +1234,44 @@ int bhmm::replan_coarse(bhmm_ctx *c, bool half, int chunk)
     // rows stored under the old plan are gone; an E-step in flight that stores gamma (this runs
     // inside its first call) gets rows of the new plan's size -- bhmm_estep sets gamma_valid
     // when that E-step has been enqueued
-    c->gamma_valid = false;
+    c->ds.gamma_valid = false;
     if (c->gamma_wanted && (rc = c->d_gamma_ci.ensure((size_t)ci_records(c) * c->N * 64)))
         return rc;
-    c->carry_valid = false; // (vectors of the old plan's chunks)
+    c->ds.carry_valid = false; // (vectors of the old plan's chunks)
     c->rows32_valid = false;
     return BHMM_OK;
 }
 } // extern "C++"
 
+// The adaptive state of a new observation set (ctx.hpp, bhmm_ctx::ObservationSet): the defaults, except
+// for what follows from the options and from the number of states.
+static void new_observation_set(bhmm_ctx *c)
+{
+    const int spec_W = c->ds.spec_W;
+    c->ds = {};
+    if (c->opt.spec_W_fixed)
+        c->ds.spec_W = spec_W; // (the caller's choice: no probe)
+    c->ds.spec_calibrated = c->opt.spec_W_fixed;
+    c->ds.tile_latched = c->opt.tile_enabled; // (ctx.hpp: one decision per set of observations)
+    // 33..64 states: the margin rule from the first call on (round 6).  On observations that follow the model --
+    // what a Viterbi pass after EM sees -- most boundaries of the first pass carry rounding noise and a fix-up round
+    // runs for half a pass (6.7 ms at configs[3]) where margins + mending take 2.6; on white-noise data the round is
+    // 0.5 ms cheaper.  Below 33 states a round is short either way: there the rule waits for a call that needed it.
+    // (BHMM_AMD_VIT_MARGIN_FORCE: the rule at every state count, for the sweeps)
+    c->ds.vit_margin_want = getenv("BHMM_AMD_VIT_MARGIN_FORCE") != nullptr || (c->n > 32 && c->n <= 64);
+}
+
 int bhmm_ctx_set_observations(bhmm_ctx *c, int kind, const void *obs, const int64_t *offsets, int K,
                               int nstates, int nsymbols, int chunk, int obs_on_device)
 {
     if (!c || !offsets || K < 1)
-        return invalid("bad context / offsets / K");
+        return invalid_arg("bad context / offsets / K");
     if (kind < 0 || kind > 2)
-        return invalid("unknown emission kind");
+        return invalid_arg("unknown emission kind");
     if (nstates < 1 || nstates > 4096)
-        return invalid("1..4096 hidden states are supported");
+        return invalid_arg("1..4096 hidden states are supported");
     if (kind == BHMM_EMIT_DISCRETE && nsymbols < 1)
-        return invalid("nsymbols must be >= 1 for discrete emissions");
+        return invalid_arg("nsymbols must be >= 1 for discrete emissions");
     BHMM_HIP(hipSetDevice(c->device));
     BHMM_HIP(hipStreamSynchronize(c->stream));
     c->d_soff.release(); // random-stream positions belong to the previous trajectories
@@ -1289,44 +1285,16 @@ int bhmm_ctx_set_observations(bhmm_ctx *c, int kind, const void *obs, const int6
     c->K = K;
     for (int k = 0; k < K; ++k)
         if (offsets[k + 1] < offsets[k])
-            return invalid("offsets must be non-decreasing");
+            return invalid_arg("offsets must be non-decreasing");
     c->offsets.resize(K + 1);
     for (int k = 0; k <= K; ++k) // positions relative to the first element handed over
         c->offsets[k] = offsets[k] - offsets[0];
     c->total = c->offsets[K];
     if (c->total <= 0)
-        return invalid("no observations");
+        return invalid_arg("no observations");
     if (obs == nullptr)
-        return invalid("obs == NULL");
-    c->gamma_valid = false;
-    c->careful = c->careful_retry = false;
-    c->carry_valid = false;
-    c->carry_use = c->carry_cap = 0;
-    c->carry_kappa = 100.0;
-    c->carry_rdec = 0.0;
-    c->prev_model.clear();
-    c->spec_calibrated = c->spec_W_fixed;
-    if (!c->spec_W_fixed)
-        c->spec_W = 288;
-    c->vit_W = 0;
-    c->pplan[0].nseg = c->pplan[1].nseg = c->pplan[2].nseg = 0;
-    c->smp_W = 0;
-    c->tile_latched = c->tile_enabled; // (ctx.hpp: one decision per set of observations)
-    c->vit_seg_given_up = false;
-    c->vit_rows_fail = 0;
-    // 33..64 states: the margin rule from the first call on (round 6).  On observations that follow the model --
-    // what a Viterbi pass after EM sees -- most boundaries of the first pass carry rounding noise and a fix-up round
-    // runs for half a pass (6.7 ms at configs[3]) where margins + mending take 2.6; on white-noise data the round is
-    // 0.5 ms cheaper.  Below 33 states a round is short either way: there the rule waits for a call that needed it.
-    // (BHMM_AMD_VIT_MARGIN_FORCE: the rule at every state count, for the sweeps)
-    c->vit_margin_want = getenv("BHMM_AMD_VIT_MARGIN_FORCE") != nullptr || (c->n > 32 && c->n <= 64);
-    c->vit_bad = 0;
-    c->vit_explore = true;
-    c->wide_replans = 0;
-    c->tile_settle = 0;
-    c->tile_W_good = 0;
-    c->wseg_given_up = false;
-    c->wide_careful = false;
+        return invalid_arg("obs == NULL");
+    new_observation_set(c);
     // discrete alphabets whose emission / count tables do not fit the LDS of the sweep kernels
     // (M above ~1200 at 8 states) keep them in global memory instead (estep_sweep.hpp, BtSrc)
     c->bt_global = kind == BHMM_EMIT_DISCRETE && !c->wide && !c->gen &&
@@ -1355,9 +1323,7 @@ int bhmm_ctx_set_observations(bhmm_ctx *c, int kind, const void *obs, const int6
         BHMM_HIP(hipStreamSynchronize(c->stream));
         return BHMM_OK;
     }
-    c->chunk_auto = chunk <= 0;
-    c->replanned_half = false;
-    c->serial_retry_done = false;
+    c->ds.chunk_auto = chunk <= 0;
     rc = plan_chunks(c, chunk);
     if (rc)
         return rc;
@@ -1393,7 +1359,7 @@ int bhmm_ctx_set_observations(bhmm_ctx *c, int kind, const void *obs, const int6
                             c->stream));
     BHMM_HIP(hipStreamSynchronize(c->stream));
     if (kind == BHMM_EMIT_GAUSSIAN && has_nan)
-        c->careful = true; // gauss_pdf(): the branch-free kernels take NaN for a perfect hit
+        c->ds.careful = true; // gauss_pdf(): the branch-free kernels take NaN for a perfect hit
     return BHMM_OK;
 }
 
@@ -1424,11 +1390,11 @@ int bhmm_ctx_set_observations_lagged(bhmm_ctx *c, int kind, const void *obs, con
                                      int chunk, int obs_on_device)
 {
     if (!c || !obs || !offsets || K < 1 || !view_traj || !view_shift || V < 1)
-        return invalid("bad context / observations / views");
+        return invalid_arg("bad context / observations / views");
     if (lag < 1)
-        return invalid("lag must be >= 1");
+        return invalid_arg("lag must be >= 1");
     if (kind < 0 || kind > 2 || nstates < 1)
-        return invalid("unknown emission kind / nstates");
+        return invalid_arg("unknown emission kind / nstates");
     BHMM_HIP(hipSetDevice(c->device));
     const size_t esz = kind == BHMM_EMIT_GAUSSIAN ? sizeof(double)
                        : kind == BHMM_EMIT_DISCRETE ? sizeof(int32_t)
@@ -1437,7 +1403,7 @@ int bhmm_ctx_set_observations_lagged(bhmm_ctx *c, int kind, const void *obs, con
     for (int v = 0; v < V; ++v) {
         const int k = view_traj[v], sh = view_shift[v];
         if (k < 0 || k >= K || sh < 0)
-            return invalid("view refers to a trajectory / shift that does not exist");
+            return invalid_arg("view refers to a trajectory / shift that does not exist");
         const int64_t T = offsets[k + 1] - offsets[k];
         const int64_t len = T > sh ? (T - sh + lag - 1) / lag : 0; // len(obs[sh::lag])
         src_start[v] = offsets[k] - offsets[0] + sh;
@@ -1445,7 +1411,7 @@ int bhmm_ctx_set_observations_lagged(bhmm_ctx *c, int kind, const void *obs, con
     }
     const int64_t total_src = offsets[K] - offsets[0], total_dst = dst_off[V];
     if (total_dst <= 0)
-        return invalid("the views are empty");
+        return invalid_arg("the views are empty");
     // ONE upload of the original observations; the views are cut on the device
     DevBuf<char> d_src, d_dst;
     DevBuf<int64_t> d_tab;
@@ -1489,7 +1455,7 @@ int bhmm_diag_gauss_pdf(double *y, const double *o, int64_t n, double mu, double
                         int nansafe)
 {
     if (!y || !o || n < 0)
-        return invalid("bhmm_diag_gauss_pdf: bad arguments");
+        return invalid_arg("bhmm_diag_gauss_pdf: bad arguments");
     Model<2> m;
     const double A[1] = {1.0}, pi[1] = {1.0};
     fill_model<2>(m, 1, EMIT_GAUSS, 0, A, pi, &mu, &sigma);
@@ -1514,7 +1480,7 @@ int bhmm_diag_gauss_pdf(double *y, const double *o, int64_t n, double mu, double
 int bhmm_diag_exp_nonpos(double *y, const double *x, int64_t n)
 {
     if (!y || !x || n < 1)
-        return invalid("NULL argument or empty problem");
+        return invalid_arg("NULL argument or empty problem");
     double *dx = nullptr, *dy = nullptr;
     BHMM_HIP(hipMalloc(reinterpret_cast<void **>(&dx), (size_t)n * sizeof(double)));
     if (hipMalloc(reinterpret_cast<void **>(&dy), (size_t)n * sizeof(double)) != hipSuccess) {
@@ -1537,168 +1503,168 @@ int bhmm_diag_exp_nonpos(double *y, const double *x, int64_t n)
 int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
 {
     if (!c || !name)
-        return invalid("NULL argument");
+        return invalid_arg("NULL argument");
     const std::string n(name);
     if (n == "spec_enabled") {
-        c->spec_enabled = value != 0.0;
-        c->carry_valid = false; // (an E-step outside the verified split path leaves no vectors to carry)
+        c->opt.spec_enabled = value != 0.0;
+        c->ds.carry_valid = false; // (an E-step outside the verified split path leaves no vectors to carry)
     } else if (n == "carry") { // warm-ups from the previous E-step's boundary vectors (EM sequences)
-        c->carry_enabled = value != 0.0;
-        c->carry_valid = false;
+        c->opt.carry_enabled = value != 0.0;
+        c->ds.carry_valid = false;
     } else if (n == "carry_kappa") { // (tests: the sensitivity bound that sizes the carried warm-ups)
-        c->carry_kappa = value;
+        c->ds.carry_kappa = value;
     } else if (n == "spec_tol") {
         // N <= 8: componentwise relative tolerance of the boundary check of the time-split E-step (and
         // what the warm-up is calibrated for, a hundred times inside it).  Default 1e-11; the parity
         // contract is 1e-6, so 1e-9 still leaves three decades -- and shortens the warm-ups by a sixth.
         if (!(value >= 1e-13 && value <= 1e-7))
-            return invalid("spec_tol outside [1e-13, 1e-7]");
-        c->spec_tol = value;
-        c->spec_calibrated = c->spec_W_fixed; // (the next E-step measures the warm-up for it)
-        c->carry_valid = false;
+            return invalid_arg("spec_tol outside [1e-13, 1e-7]");
+        c->opt.spec_tol = value;
+        c->ds.spec_calibrated = c->opt.spec_W_fixed; // (the next E-step measures the warm-up for it)
+        c->ds.carry_valid = false;
     } else if (n == "sample_seg_per_simd") { // 9..64 states: segments per SIMD of the backward draw
         if (value < 1 || value > 64)
             return BHMM_ERR_INVALID;
-        c->smp_seg_per_simd = (int)value;
-        c->pplan[1].nseg = 0;
+        c->opt.smp_seg_per_simd = (int)value;
+        c->ds.pplan[1].nseg = 0;
     } else if (n == "viterbi_seg_warmups") { // 9..64 states: a Viterbi segment is at least this many warm-ups long
         if (value < 1 || value > 64)
             return BHMM_ERR_INVALID;
-        c->vit_seg_warmups = (int)value;
-        c->pplan[0].nseg = 0;
+        c->opt.vit_seg_warmups = (int)value;
+        c->ds.pplan[0].nseg = 0;
     } else if (n == "viterbi_W") { // warm-up of the next segment-parallel Viterbi pass (0: from the E-step's)
         if (value < 0 || value > (1 << 20))
             return BHMM_ERR_INVALID;
-        c->vit_W = (int)value;
+        c->ds.vit_W = (int)value;
     } else if (n == "viterbi_margin") { // 9..128 states: the path-margin acceptance of the segment-parallel first pass
-        c->vit_margin = value != 0.0;
+        c->opt.vit_margin = value != 0.0;
         if (value == 2.0) // (up to 64 states: from the next call on, not only after a call with two or more rounds)
-            c->vit_margin_want = true;
+            c->ds.vit_margin_want = true;
     } else if (n == "viterbi_mend") { // 9..64 states: segments further than 1e-12 from their predecessors run again alone
-        c->vit_mend = value != 0.0;
+        c->opt.vit_mend = value != 0.0;
     } else if (n == "viterbi_seg_per_simd") { // 9..64 states: segments per SIMD of the Viterbi pass
         if (value < 1 || value > 64)
             return BHMM_ERR_INVALID;
-        c->vit_seg_per_simd = (int)value;
-        c->pplan[0].nseg = 0;
-        c->vit_seg_given_up = false;
+        c->opt.vit_seg_per_simd = (int)value;
+        c->ds.pplan[0].nseg = 0;
+        c->ds.vit_seg_given_up = false;
     } else if (n == "spec_W") {
-        c->carry_valid = false;
-        c->spec_W = std::max(1, (int)value);
-        c->vit_W = 0;
-        c->spec_W_fixed = c->spec_calibrated = true; // the caller's choice: no probe
+        c->ds.carry_valid = false;
+        c->ds.spec_W = std::max(1, (int)value);
+        c->ds.vit_W = 0;
+        c->opt.spec_W_fixed = c->ds.spec_calibrated = true; // the caller's choice: no probe
     }
     else if (n == "draw_watch") // draws inside the reach of the alpha rows' verified deviation are decided again (draw_verify.hpp)
-        c->draw_watch = value != 0.0;
+        c->opt.draw_watch = value != 0.0;
     else if (n == "draw_watch_tol") { // (tests) watch tolerance instead of 64 x the measured deviation; 0: automatic
         if (!(value >= 0.0 && value <= 0.5))
-            return invalid("draw_watch_tol outside [0, 0.5]");
-        c->draw_watch_tol = value;
+            return invalid_arg("draw_watch_tol outside [0, 0.5]");
+        c->opt.draw_watch_tol = value;
     } else if (n == "draw_test_redo") // (tests) every watched draw counts as a decision that did not stand
-        c->draw_test_redo = value != 0.0;
+        c->opt.draw_test_redo = value != 0.0;
     else if (n == "wide_segments")
-        c->wseg_enabled = value != 0.0;
+        c->opt.wseg_enabled = value != 0.0;
     else if (n == "wide_segment_len")
-        c->wseg_len = std::max(0, (int)value); // takes effect at the next set_observations
+        c->opt.wseg_len = std::max(0, (int)value); // takes effect at the next set_observations
     else if (n == "wide_split")
-        c->wseg_split = value != 0.0; // 64 states: own, finer segment plan for the forward pass
+        c->opt.wseg_split = value != 0.0; // 64 states: own, finer segment plan for the forward pass
     else if (n == "tile")
-        c->tile_enabled = value != 0.0; // row-batched matrix-core recursions (next set_observations)
+        c->opt.tile_enabled = value != 0.0; // row-batched matrix-core recursions (next set_observations)
     else if (n == "tile_per_cu")
-        c->tile_per_cu = std::max(1, std::min(4, (int)value)); // (next set_observations)
+        c->opt.tile_per_cu = std::max(1, std::min(4, (int)value)); // (next set_observations)
     else
-        return invalid("unknown or read-only option: " + n);
+        return invalid_arg("unknown or read-only option: " + n);
     return BHMM_OK;
 }
 
 int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
 {
     if (!c || !name || !value)
-        return invalid("NULL argument");
+        return invalid_arg("NULL argument");
     const std::string n(name);
     if (n == "spec_enabled")
-        *value = c->spec_enabled ? 1.0 : 0.0;
+        *value = c->opt.spec_enabled ? 1.0 : 0.0;
     else if (n == "spec_W")
-        *value = c->spec_W;
+        *value = c->ds.spec_W;
     else if (n == "spec_tol")
-        *value = c->spec_tol;
+        *value = c->opt.spec_tol;
     else if (n == "spec_ok")
-        *value = c->spec_ok;
+        *value = c->last.spec_ok;
     else if (n == "spec_fail")
-        *value = c->spec_fail;
+        *value = c->last.spec_fail;
     else if (n == "spec_last_dev")
-        *value = c->spec_last_dev;
+        *value = c->last.spec_last_dev;
     else if (n == "careful")
-        *value = (c->careful || c->wide_careful) ? 1.0 : 0.0;
+        *value = (c->ds.careful || c->ds.wide_careful) ? 1.0 : 0.0;
     else if (n == "viterbi_chunked")
-        *value = c->viterbi_chunked ? 1.0 : 0.0;
+        *value = c->last.viterbi_chunked ? 1.0 : 0.0;
     else if (n == "viterbi_close")
-        *value = c->viterbi_close;
+        *value = c->last.viterbi_close;
     else if (n == "viterbi_W") // warm-up the chunk-parallel Viterbi last verified with
-        *value = c->vit_W;
+        *value = c->ds.vit_W;
     else if (n == "viterbi_segments") // 9..64 states: time segments of the last Viterbi pass's plan
-        *value = c->pplan[0].nseg;
+        *value = c->ds.pplan[0].nseg;
     else if (n == "sample_segmented") // 9..64 states: the last path sampling ran over time segments
-        *value = c->smp_segmented ? 1.0 : 0.0;
+        *value = c->last.smp_segmented ? 1.0 : 0.0;
     else if (n == "sample_forward_segmented")
-        *value = c->draw_fwd_segmented ? 1.0 : 0.0;
+        *value = c->last.draw_fwd_segmented ? 1.0 : 0.0;
     else if (n == "sample_segments")
-        *value = c->pplan[1].nseg;
+        *value = c->ds.pplan[1].nseg;
     else if (n == "sample_W")
-        *value = c->smp_W;
+        *value = c->ds.smp_W;
     else if (n == "sample_mismatch") // ... segments its first pass left to the fix-up rounds
-        *value = c->smp_seg_mismatch;
+        *value = c->last.smp_seg_mismatch;
     else if (n == "sample_rounds")
-        *value = c->smp_seg_rounds;
+        *value = c->last.smp_seg_rounds;
     else if (n == "viterbi_rounds") // ... fix-up rounds its last pass needed
-        *value = c->vit_seg_rounds;
+        *value = c->last.vit_seg_rounds;
     else if (n == "viterbi_mismatch") // ... boundaries of its last attempt that were not bit-identical
-        *value = c->vit_seg_mismatch;
+        *value = c->last.vit_seg_mismatch;
     else if (n == "viterbi_margin")
-        *value = c->vit_margin ? 1.0 : 0.0;
+        *value = c->opt.vit_margin ? 1.0 : 0.0;
     else if (n == "viterbi_mended") // ... segments its last call ran again up to a kept vector of the first pass
-        *value = c->vit_mended;
+        *value = c->last.vit_mended;
     else if (n == "viterbi_far") // ... boundaries of its first pass that were not equal to 1e-12
-        *value = c->vit_far;
+        *value = c->last.vit_far;
     else if (n == "viterbi_margin_used") // ... accepted by the margins of the decisions on its path (no fix-up rounds)
-        *value = c->vit_margin_used;
+        *value = c->last.vit_margin_used;
     else if (n == "viterbi_margin_close") // ... segments with a close decision on the path (the rounds ran instead)
-        *value = c->vit_margin_close;
+        *value = c->last.vit_margin_close;
     else if (n == "draw_watch")
-        *value = c->draw_watch ? 1.0 : 0.0;
+        *value = c->opt.draw_watch ? 1.0 : 0.0;
     else if (n == "draw_events") // last path sampling: draws inside the watch tolerance
-        *value = c->draw_events;
+        *value = c->last.draw_events;
     else if (n == "draw_checked") // ... of them decided again on the windowed serial recursion
-        *value = c->draw_checked;
+        *value = c->last.draw_checked;
     else if (n == "draw_redone") // ... the call was repeated on the exact alpha rows
-        *value = c->draw_redone;
+        *value = c->last.draw_redone;
     else if (n == "draw_alpha_dev") // ... largest boundary deviation of the forward pass the draws read
-        *value = c->draw_alpha_dev;
+        *value = c->last.draw_alpha_dev;
     else if (n == "carry")
-        *value = c->carry_enabled ? 1.0 : 0.0;
+        *value = c->opt.carry_enabled ? 1.0 : 0.0;
     else if (n == "carry_W") // warm-up steps of the last E-step's carried starts (0: full warm-ups)
-        *value = c->carry_last_W;
+        *value = c->last.carry_last_W;
     else if (n == "carry_ok")
-        *value = c->carry_ok;
+        *value = c->last.carry_ok;
     else if (n == "carry_fail")
-        *value = c->carry_fail;
+        *value = c->last.carry_fail;
     else if (n == "carry_kappa")
-        *value = c->carry_kappa;
+        *value = c->ds.carry_kappa;
     else if (n == "wide_segments")
-        *value = (c->wseg_enabled && !c->wseg_given_up && c->w_nseg[1] > c->w_nseg[0]) ? c->w_nseg[1] : 0;
+        *value = (c->opt.wseg_enabled && !c->ds.wseg_given_up && c->w_nseg[1] > c->w_nseg[0]) ? c->w_nseg[1] : 0;
     else if (n == "wide_segment_len") // segment length of the current time-segmented plan (0: none)
-        *value = (c->wseg_enabled && !c->wseg_given_up && c->w_nseg[1] > c->w_nseg[0]) ? (double)c->wseg_cur_len : 0.0;
+        *value = (c->opt.wseg_enabled && !c->ds.wseg_given_up && c->w_nseg[1] > c->w_nseg[0]) ? (double)c->wseg_cur_len : 0.0;
     else if (n == "wide_trouble") // which self-check of the lazily scaled kernels fired last (bit mask)
-        *value = c->wide_trouble;
+        *value = c->last.wide_trouble;
     else if (n == "tile_reason") // more than 64 states: why the tile kernels were left (ctx.hpp), 0: they were not
         *value = c->tile_reason;
     else if (n == "tile") // 1: the last E-step ran on the row-batched matrix-core kernels
-        *value = c->tile_used ? 1.0 : 0.0;
+        *value = c->last.tile_used ? 1.0 : 0.0;
     else if (n == "wide_fwd_segments") // the forward pass's own, finer plan (64 states), 0 if none
-        *value = (c->wseg_enabled && !c->wseg_given_up && c->w_nseg[1] > c->w_nseg[0] &&
+        *value = (c->opt.wseg_enabled && !c->ds.wseg_given_up && c->w_nseg[1] > c->w_nseg[0] &&
                   c->w_nseg[2] > c->w_nseg[1]) ? c->w_nseg[2] : 0;
     else
-        return invalid("unknown option: " + n);
+        return invalid_arg("unknown option: " + n);
     return BHMM_OK;
 }
 
@@ -1711,7 +1677,7 @@ void *bhmm_ctx_stream(bhmm_ctx *c) { return c ? (void *)c->stream : nullptr; }
 int bhmm_ctx_sync(bhmm_ctx *c)
 {
     if (!c)
-        return invalid("ctx == NULL");
+        return invalid_arg("ctx == NULL");
     BHMM_HIP(hipSetDevice(c->device));
     BHMM_HIP(hipStreamSynchronize(c->stream));
     collect_timing(c);
@@ -1722,15 +1688,15 @@ double bhmm_ctx_last_kernel_ms(bhmm_ctx *c, int which)
 {
     if (!c || which < 0 || which > 4)
         return -1.0;
-    return c->last_ms[which];
+    return c->last.ms[which];
 }
 
 int bhmm_ctx_last_kernel_ms_all(bhmm_ctx *c, double *out)
 {
     if (!c || !out)
-        return invalid("bad arguments");
+        return invalid_arg("bad arguments");
     for (int i = 0; i < 5; ++i)
-        out[i] = c->last_ms[i];
+        out[i] = c->last.ms[i];
     return BHMM_OK;
 }
 
@@ -1745,7 +1711,7 @@ static int nonfinite_retry(bhmm_ctx *c, bool *retried)
 {
     if (retried)
         *retried = false;
-    if (c->wide || c->gen || c->G <= c->K || c->serial_retry_done || !c->last_stats)
+    if (c->wide || c->gen || c->G <= c->K || c->ds.serial_retry_done || !c->last_stats)
         return BHMM_OK;
     const int S = stats_size(c);
     const int n = c->n;
@@ -1763,7 +1729,7 @@ static int nonfinite_retry(bhmm_ctx *c, bool *retried)
         maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
     if (finite || !std::isfinite(c->h_pinned[0]) || maxT >= ((int64_t)1 << 30))
         return BHMM_OK;
-    c->serial_retry_done = true;
+    c->ds.serial_retry_done = true;
     // does the one-chunk-per-trajectory plan fit?  Its workspace is (K padded to 64) x maxT records (few
     // long trajectories: hundreds of GB): if not, leave the plan alone -- the fetch then reports the
     // non-finite statistic instead of an allocation failure on a half-replaced plan
@@ -1774,10 +1740,10 @@ static int nonfinite_retry(bhmm_ctx *c, bool *retried)
     const double held = (double)c->d_ws.n * 8.0 + (double)c->d_obs_ci.n + (double)c->d_gamma_ci.n * 8.0;
     const size_t ne = c->kind == BHMM_EMIT_GAUSSIAN ? 2 * (size_t)n
                       : (c->kind == BHMM_EMIT_DISCRETE ? (size_t)n * c->M : 0);
-    if (need > 0.9 * ((double)free_b + held) || c->prev_model.size() != (size_t)n * n + ne ||
+    if (need > 0.9 * ((double)free_b + held) || c->ds.prev_model.size() != (size_t)n * n + ne ||
         c->last_pi.size() != (size_t)n)
         return BHMM_OK;
-    c->chunk_auto = false;
+    c->ds.chunk_auto = false;
     c->gamma_wanted = (c->last_flags & BHMM_FLAG_STORE_GAMMA) != 0; // (the re-plan re-sizes the gamma rows)
     int rc;
     if ((rc = replan_coarse(c, false, (int)maxT))) {
@@ -1785,7 +1751,7 @@ static int nonfinite_retry(bhmm_ctx *c, bool *retried)
         return rc;
     }
     c->prefetched = false;
-    const double *A = c->prev_model.data();
+    const double *A = c->ds.prev_model.data();
     const double *p0 = ne ? A + (size_t)n * n : nullptr;
     const double *p1 = c->kind == BHMM_EMIT_GAUSSIAN ? p0 + n : nullptr;
     if (retried)
@@ -1793,28 +1759,38 @@ static int nonfinite_retry(bhmm_ctx *c, bool *retried)
     return BHMM_DISPATCH_N(c, estep(c, A, c->last_pi.data(), p0, p1, c->last_stats, c->last_flags));
 }
 
-int bhmm_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
-               const double *par1, double *stats_dev, int flags)
+extern "C++" {
+int bhmm::enter_model_call(bhmm_ctx *c, bool given, const char *null_msg, bool emissions, const double *par0,
+                           const double *par1)
 {
     if (c)
         lds_poison(c->stream); // (debugging aid, BHMM_AMD_POISON=1 only)
     if (!c || c->kind < 0)
-        return invalid("no observations loaded");
-    if (!A || !pi)
-        return invalid("A / pi == NULL");
-    if (c->kind == BHMM_EMIT_GAUSSIAN && (!par0 || !par1))
-        return invalid("gaussian emissions need means and sigmas");
-    if (c->kind == BHMM_EMIT_DISCRETE && !par0)
-        return invalid("discrete emissions need B");
+        return invalid_arg("no observations loaded");
+    if (!given)
+        return invalid_arg(null_msg);
+    if (emissions && c->kind == BHMM_EMIT_GAUSSIAN && (!par0 || !par1))
+        return invalid_arg("gaussian emissions need means and sigmas");
+    if (emissions && c->kind == BHMM_EMIT_DISCRETE && !par0)
+        return invalid_arg("discrete emissions need B");
     BHMM_HIP(hipSetDevice(c->device));
-    int rc;
+    return BHMM_OK;
+}
+} // extern "C++"
+
+int bhmm_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
+               const double *par1, double *stats_dev, int flags)
+{
+    int rc = enter_model_call(c, A && pi, "A / pi == NULL", true, par0, par1);
+    if (rc)
+        return rc;
     if (!c->wide && !c->gen && c->kind == BHMM_EMIT_DISCRETE && (rc = upload_Bt(c, par0)))
         return rc;
     if (!c->wide && !c->gen && (flags & BHMM_FLAG_STORE_GAMMA)) {
         if ((rc = c->d_gamma_ci.ensure((size_t)ci_records(c) * c->N * 64)))
             return rc;
     }
-    c->gamma_valid = false;
+    c->ds.gamma_valid = false;
     c->gamma_wanted = (flags & BHMM_FLAG_STORE_GAMMA) != 0;
     c->wide_retry = 0;
     {
@@ -1832,10 +1808,10 @@ int bhmm_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par
             memcpy(cur.data() + (size_t)n * n, par0, ne * sizeof(double));
         }
         double delta = -1.0;
-        if (c->prev_model.size() == cur.size()) {
+        if (c->ds.prev_model.size() == cur.size()) {
             delta = 0.0;
             for (size_t e = 0; e < cur.size(); ++e) {
-                double d = fabs(cur[e] - c->prev_model[e]);
+                double d = fabs(cur[e] - c->ds.prev_model[e]);
                 if (c->kind == BHMM_EMIT_GAUSSIAN && e >= (size_t)n * n)
                     d /= fabs(par1[(e - (size_t)n * n) % n]);
                 if (!(d <= delta))
@@ -1843,7 +1819,7 @@ int bhmm_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par
             }
         }
         c->carry_delta = delta;
-        c->prev_model.swap(cur);
+        c->ds.prev_model.swap(cur);
         c->last_pi.assign(pi, pi + n); // (with prev_model: the model of this call, for nonfinite_retry)
         c->last_flags = flags;
     }
@@ -1865,7 +1841,7 @@ int bhmm_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par
         // such a caller uses to wait for it, takes the same look -- so a sharded caller is repaired too,
         // BEFORE its all-reduce)
         rc = nonfinite_retry(c, nullptr);
-    c->gamma_valid = rc == BHMM_OK && c->gamma_wanted;
+    c->ds.gamma_valid = rc == BHMM_OK && c->gamma_wanted;
     c->gamma_wanted = false;
     return rc;
 }
@@ -1873,14 +1849,14 @@ int bhmm_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par
 int bhmm_estep_fetch(bhmm_ctx *c, double *stats, double *logL_k)
 {
     if (!c || c->kind < 0)
-        return invalid("no observations loaded");
+        return invalid_arg("no observations loaded");
     BHMM_HIP(hipSetDevice(c->device));
     const int S = stats_size(c);
     // statistics come from the buffer the E-step wrote (the caller's, if it gave one: a caller that
     // all-reduces that buffer in place fetches before reducing, or asks for logL_k only)
     bool have_logLk = true;
     if (!c->prefetched && !c->last_stats)
-        return invalid("no E-step has run on these observations");
+        return invalid_arg("no E-step has run on these observations");
     if (!c->last_stats_internal && !c->last_stats_checked) {
         // an E-step launched into the caller's buffer: the FIRST fetch after the launch is where this rank's
         // result is looked at (and, if the counts are not finite, repaired in place) -- once per launch, so a
@@ -1890,7 +1866,7 @@ int bhmm_estep_fetch(bhmm_ctx *c, double *stats, double *logL_k)
         bool retried = false;
         int rc = nonfinite_retry(c, &retried);
         if (retried) { // (what bhmm_estep does at its end)
-            c->gamma_valid = rc == BHMM_OK && c->gamma_wanted;
+            c->ds.gamma_valid = rc == BHMM_OK && c->gamma_wanted;
             c->gamma_wanted = false;
         }
         if (rc)
@@ -1945,11 +1921,11 @@ int bhmm_estep_fetch(bhmm_ctx *c, double *stats, double *logL_k)
 int bhmm_get_gamma(bhmm_ctx *c, int k, double *gamma)
 {
     if (!c || c->kind < 0 || !gamma)
-        return invalid("bad arguments");
-    if (!c->gamma_valid)
-        return invalid("last E-step did not store gamma (BHMM_FLAG_STORE_GAMMA)");
+        return invalid_arg("bad arguments");
+    if (!c->ds.gamma_valid)
+        return invalid_arg("last E-step did not store gamma (BHMM_FLAG_STORE_GAMMA)");
     if (k < 0 || k >= c->K)
-        return invalid("trajectory index out of range");
+        return invalid_arg("trajectory index out of range");
     BHMM_HIP(hipSetDevice(c->device));
     const int64_t T = c->offsets[k + 1] - c->offsets[k];
     if (T == 0)
@@ -1994,7 +1970,7 @@ int current_device()
 int explicit_ctx(TmpCtx &t, const double *pobs, int N, int64_t T)
 {
     if (!pobs || N < 1 || T < 1)
-        return invalid("pobs == NULL or empty problem");
+        return invalid_arg("pobs == NULL or empty problem");
     int rc = bhmm_ctx_create(&t.c, current_device(), nullptr);
     if (rc)
         return rc;
@@ -2021,7 +1997,7 @@ int bhmm_forward(double *alpha, double *logprob, const double *A, const double *
                  const double *pi, int N, int64_t T)
 {
     if (!alpha || !A || !pi)
-        return invalid("NULL argument");
+        return invalid_arg("NULL argument");
     TmpCtx t;
     int rc = explicit_ctx(t, pobs, N, T);
     if (rc)
@@ -2052,7 +2028,7 @@ int bhmm_forward(double *alpha, double *logprob, const double *A, const double *
 int bhmm_backward(double *beta, const double *A, const double *pobs, int N, int64_t T)
 {
     if (!beta || !A)
-        return invalid("NULL argument");
+        return invalid_arg("NULL argument");
     TmpCtx t;
     int rc = explicit_ctx(t, pobs, N, T);
     if (rc)

@@ -9,11 +9,11 @@
 #include <algorithm>
 
 #include "host_common.hpp"
+#include "host_internal.hpp"
 #include "gen_kernels.hpp"
 #include "big_kernels.hpp"
 
 namespace bhmm {
-Segs wide_segs_pub(bhmm_ctx *c, int which);
 
 namespace {
 // ---- more than 128 states: big_kernels.hpp ---------------------------------------------------------
@@ -31,7 +31,7 @@ int big_fwd_t(bhmm_ctx *c, const WideModel &m)
 {
     using G = BigGeo<TPW>;
     lds_poison(c->stream);
-    const Segs sg = wide_segs_pub(c, 1);
+    const Segs sg = segs_of(c, 1);
     const TilePlan tp{c->d_tile_seg[1].p, c->w_ntiles[1]};
     // A in matrix-operand order for both passes (the model of THIS call: the backward pass follows)
     const size_t npk = (size_t)G::NP * G::NP;
@@ -55,7 +55,7 @@ int big_bwd_t(bhmm_ctx *c, const WideModel &m, double *gam, double *stats_dev)
 {
     using G = BigGeo<TPW>;
     lds_poison(c->stream);
-    const Segs sg = wide_segs_pub(c, 1);
+    const Segs sg = segs_of(c, 1);
     const TilePlan tp{c->d_tile_segb[1].p, c->w_ntilesb[1]};
     const int n = c->n;
     // the xi counts: C' = alpha^T W over the rows W this pass stores (k_big_xi_gemm: 128 x 128 blocks of C',

@@ -10,11 +10,7 @@
 #include <mutex>
 #include <string>
 
-#include "ctx.hpp"
-
-namespace bhmm {
-int invalid_arg(const std::string &msg);
-}
+#include "host_internal.hpp"
 
 namespace {
 

@@ -10,21 +10,10 @@
 #include <vector>
 
 #include "host_common.hpp"
+#include "host_internal.hpp"
 #include "gen_kernels.hpp"
 
 namespace bhmm {
-int invalid_arg(const std::string &msg);
-int wide_model_pub(bhmm_ctx *c, int kind, const double *A, const double *pi, const double *par0,
-                   const double *par1, WideModel &m);
-// tile_gen.hip: up to 128 states on the row-batched matrix-core kernels
-bool tile_gen_capable(const bhmm_ctx *c);
-int tile_gen_alloc(bhmm_ctx *c);
-int tile_gen_estep(bhmm_ctx *c, const WideModel &m, double *stats_dev, int flags, bool *done);
-int tile_gen_forward_draw(bhmm_ctx *c, const WideModel &m, bool *done);
-int wide_path_plan_pub(bhmm_ctx *c, int which, int64_t seglen, Segs &sg);
-int draw_watch_prepare(bhmm_ctx *c, double tol, DrawWatch &w, unsigned int *count_slot);
-int draw_verify_run(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
-                    unsigned int count, double thr, int64_t Wlong, bool *ok);
 
 namespace {
 
@@ -126,7 +115,7 @@ int gen_forward(bhmm_ctx *c, const double *A, const double *pi, const double *pa
                 const double *par1)
 {
     WideModel m;
-    int rc = wide_model_pub(c, c->kind, A, pi, par0, par1, m);
+    int rc = wide_model(c, c->kind, A, pi, par0, par1, m);
     if (rc)
         return rc;
     const double *pobs = nullptr;
@@ -140,7 +129,7 @@ int gen_backward(bhmm_ctx *c, const double *A)
 {
     WideModel m;
     std::vector<double> pi(c->n, 1.0 / c->n);
-    int rc = wide_model_pub(c, EMIT_EXPL, A, pi.data(), nullptr, nullptr, m);
+    int rc = wide_model(c, EMIT_EXPL, A, pi.data(), nullptr, nullptr, m);
     if (rc || (rc = gen_transposed(c, m)))
         return rc;
     const double *pobs = reinterpret_cast<const double *>(c->d_obs_rm.p);
@@ -170,7 +159,7 @@ int gen_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par0
               double *stats_dev, int flags)
 {
     WideModel m;
-    int rc = wide_model_pub(c, c->kind, A, pi, par0, par1, m);
+    int rc = wide_model(c, c->kind, A, pi, par0, par1, m);
     if (rc)
         return rc;
     {
@@ -262,11 +251,11 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
     if (out_fmt != 0 && n > 256)
         return invalid_arg("one byte per step holds at most 256 states: use bhmm_viterbi_batch (int32)");
     WideModel m;
-    int rc = wide_model_pub(c, c->kind, A, pi, par0, par1, m);
+    int rc = wide_model(c, c->kind, A, pi, par0, par1, m);
     if (rc)
         return rc;
-    c->viterbi_chunked = false;
-    c->vit_mended = 0;
+    c->last.viterbi_chunked = false;
+    c->last.vit_mended = 0;
     const double *pobs = nullptr;
     if ((rc = gen_pobs(c, m, &pobs)) ||
         (rc = c->d_scratch.ensure((size_t)c->total * n * sizeof(uint16_t))) ||
@@ -277,7 +266,7 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
     int32_t *path = last + K;
     // up to 128 states: over time segments (k_gen_viterbi_seg), accepted only when every segment started
     // from the bit pattern its predecessor computed -- then the back-pointers are the serial run's
-    if (n <= 128 && c->spec_enabled && !c->vit_seg_given_up) {
+    if (n <= 128 && c->opt.spec_enabled && !c->ds.vit_seg_given_up) {
         bool done = false;
         uint8_t *ptr8 = reinterpret_cast<uint8_t *>(c->d_scratch.p);
         const size_t smv = (size_t)(128 * GVS_PITCH + 8 * 128) * sizeof(double);
@@ -293,22 +282,22 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
         // length, and segments as short as one warm-up (round 5; with the path-margin acceptance 25.7 -> 11 ms)
         // -- but never longer than the segments that fill the chip (a slowly forgetting model keeps the E-step's
         // length and its segment count; the rounds then do what the margins cannot)
-        const int seg_warmups = c->vit_margin ? 1 : c->vit_seg_warmups;
-        const int W0 = std::max(64, c->spec_W > 0 ? (c->spec_W + 7) / 8 * 8 : 128);
-        const int64_t fill0 = ((c->total + (int64_t)c->vit_seg_per_simd * c->num_simd - 1) /
-                               ((int64_t)c->vit_seg_per_simd * c->num_simd) + 7) / 8 * 8;
+        const int seg_warmups = c->opt.vit_margin ? 1 : c->opt.vit_seg_warmups;
+        const int W0 = std::max(64, c->ds.spec_W > 0 ? (c->ds.spec_W + 7) / 8 * 8 : 128);
+        const int64_t fill0 = ((c->total + (int64_t)c->opt.vit_seg_per_simd * c->num_simd - 1) /
+                               ((int64_t)c->opt.vit_seg_per_simd * c->num_simd) + 7) / 8 * 8;
         // (round 6: with the mending round the E-step's length is where the margin route starts too -- the few
         // boundaries that need the fourfold length are repaired alone; the length doubles for the next call, up to
         // that fourfold, when a pass could not be mended or needed three or more rounds)
         const int W_cap = (int)std::max<int64_t>(W0, std::min<int64_t>(4 * (int64_t)W0, fill0));
-        int W_try = c->vit_W > 0 ? c->vit_W : ((c->vit_margin && !c->vit_mend) ? W_cap : W0);
+        int W_try = c->ds.vit_W > 0 ? c->ds.vit_W : ((c->opt.vit_margin && !c->opt.vit_mend) ? W_cap : W0);
         Segs sg;
         // the path-margin acceptance of the first pass (k_vit_margin, path_kernels.hpp; see wide_viterbi_run)
         const double vm_tol = 1e-12;
         double *vall = nullptr;
         int64_t maxT = 0;
         const size_t smm = (size_t)n * (n | 1) * sizeof(double); // (odd pitch, k_vit_margin)
-        if (c->vit_margin && c->d_gW.ensure((size_t)c->total * n) == BHMM_OK &&
+        if (c->opt.vit_margin && c->d_gW.ensure((size_t)c->total * n) == BHMM_OK &&
             gen_set_smem(k_vit_margin<int32_t, 2>, smm) == BHMM_OK && gen_set_smem(k_vit_margin<uint8_t, 2>, smm) == BHMM_OK) {
             vall = c->d_gW.p;
             for (int k = 0; k < K; ++k)
@@ -316,8 +305,8 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
         } else {
             (void)hipGetLastError();
         }
-        c->vit_margin_used = 0;
-        c->vit_margin_close = 0;
+        c->last.vit_margin_used = 0;
+        c->last.vit_margin_close = 0;
         const int64_t *off = c->d_offsets.p;
         uint8_t *p8 = out_fmt == 2 ? static_cast<uint8_t *>(paths_out) : reinterpret_cast<uint8_t *>(path);
         // back-trace over the segments: maps, stitch, apply
@@ -328,7 +317,7 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
             hipLaunchKernelGGL((k_wide_vit_walk<false, uint8_t, 2>), dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n,
                                (const uint8_t *)ptr8, c->d_vmaps.p, (const uint8_t *)nullptr, (uint8_t *)nullptr);
             hipLaunchKernelGGL(k_wide_vit_stitch, dim3((K + 63) / 64), dim3(64), 0, c->stream,
-                               (const int32_t *)c->pplan[0].traj0.p, K, (const uint8_t *)c->d_vmaps.p, 128,
+                               (const int32_t *)c->pplan_buf[0].traj0.p, K, (const uint8_t *)c->d_vmaps.p, 128,
                                (const int32_t *)last, c->d_vend.p);
             if (out_fmt == 0)
                 hipLaunchKernelGGL((k_wide_vit_walk<true, int32_t, 2>), dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n,
@@ -342,9 +331,9 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
         for (int attempt = 0; attempt < 2 && !done; ++attempt) {
             if (attempt > 0)
                 W_try *= 2;
-            const int64_t want = (int64_t)c->vit_seg_per_simd * c->num_simd;
+            const int64_t want = (int64_t)c->opt.vit_seg_per_simd * c->num_simd;
             const int64_t seglen = std::max<int64_t>((c->total + want - 1) / want, seg_warmups * (int64_t)W_try);
-            if ((rc = wide_path_plan_pub(c, 0, seglen, sg)))
+            if ((rc = wide_path_plan(c, 0, seglen, sg)))
                 return rc;
             if (sg.nseg <= K)
                 break;
@@ -355,8 +344,8 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
             const dim3 sgrid((sg.nseg + 7) / 8), sblk(512);
             int round = 0;
             bool margin_accepted = false;
-            bool allow_mend = c->vit_mend, mended = false;
-            c->vit_mended = 0;
+            bool allow_mend = c->opt.vit_mend, mended = false;
+            c->last.vit_mended = 0;
             for (; round <= 12; ++round) {
                 BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
                 lds_poison(c->stream);
@@ -376,8 +365,8 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
                                         hipMemcpyDeviceToHost, c->stream));
                 BHMM_HIP(hipStreamSynchronize(c->stream));
                 if (round == 0) {
-                    c->vit_seg_mismatch = (int)c->h_specres[3];
-                    c->vit_far = (int)c->h_specres[0];
+                    c->last.vit_seg_mismatch = (int)c->h_specres[3];
+                    c->last.vit_far = (int)c->h_specres[0];
                 }
                 if (c->h_specres[3] == 0)
                     break;
@@ -396,7 +385,7 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
                     BHMM_HIP(hipMemcpyAsync(&notmet, c->d_specres.p + 1, sizeof(unsigned int), hipMemcpyDeviceToHost,
                                             c->stream));
                     BHMM_HIP(hipStreamSynchronize(c->stream));
-                    c->vit_mended = (int)c->h_specres[0];
+                    c->last.vit_mended = (int)c->h_specres[0];
                     if (notmet == 0) {
                         spliced = (int)c->h_specres[0];
                         c->h_specres[0] = 0;
@@ -409,7 +398,7 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
                     if ((rc = seg_walks()))
                         return rc;
                     BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
-                    const dim3 mgrid(sg.nseg, (unsigned)((c->pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
+                    const dim3 mgrid(sg.nseg, (unsigned)((c->ds.pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
                     if (out_fmt == 0)
                         hipLaunchKernelGGL((k_vit_margin<int32_t, 2>), mgrid, dim3(256), smm, c->stream, m.A, n, off, sg,
                                            (const double *)vall, (const int32_t *)path, margin, c->d_specres.p);
@@ -420,9 +409,9 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
                     BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
                                             hipMemcpyDeviceToHost, c->stream));
                     BHMM_HIP(hipStreamSynchronize(c->stream));
-                    c->vit_margin_close = (int)c->h_specres[2];
+                    c->last.vit_margin_close = (int)c->h_specres[2];
                     if (c->h_specres[2] == 0) {
-                        c->vit_margin_used = 1;
+                        c->last.vit_margin_used = 1;
                         margin_accepted = true;
                         break;
                     }
@@ -436,20 +425,20 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
                     round = -1;
                 }
             }
-            c->vit_seg_rounds = round;
+            c->last.vit_seg_rounds = round;
             if (c->h_specres[3] == 0 || margin_accepted) {
                 done = true;
                 // (what converged is where the next call on these observations starts; longer after a pass whose far
                 // boundaries could not be mended or that needed three or more rounds)
-                const bool longer = (vall && c->vit_far > 0 && !margin_accepted) || (round >= 3 && !margin_accepted);
-                c->vit_W = (longer && W_try < W_cap) ? std::min(2 * W_try, W_cap) : W_try;
+                const bool longer = (vall && c->last.vit_far > 0 && !margin_accepted) || (round >= 3 && !margin_accepted);
+                c->ds.vit_W = (longer && W_try < W_cap) ? std::min(2 * W_try, W_cap) : W_try;
             }
         }
-        if (!done && c->pplan[0].nseg > K)
-            c->vit_seg_given_up = true; // these observations go to the serial kernel from now on
-        c->viterbi_chunked = done;
+        if (!done && c->ds.pplan[0].nseg > K)
+            c->ds.vit_seg_given_up = true; // these observations go to the serial kernel from now on
+        c->last.viterbi_chunked = done;
         if (done) {
-            if (!c->vit_margin_used && (rc = seg_walks())) // (a margin-accepted pass has its path already)
+            if (!c->last.vit_margin_used && (rc = seg_walks())) // (a margin-accepted pass has its path already)
                 return rc;
             if (out_fmt == 0)
                 BHMM_HIP(hipMemcpyAsync(paths_out, path, (size_t)c->total * sizeof(int32_t),
@@ -463,29 +452,29 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
     // 129 .. 256 states (round 5): four segments per workgroup share every pass over A (k_gen_viterbi_rows); first
     // pass only -- accepted when every boundary is bit-identical or by the margins of the decisions on its path
     // (k_vit_margin), else the serial kernel below decides
-    if (n > 128 && n <= 256 && c->spec_enabled && c->vit_margin && !c->vit_seg_given_up) {
+    if (n > 128 && n <= 256 && c->opt.spec_enabled && c->opt.vit_margin && !c->ds.vit_seg_given_up) {
         uint8_t *ptr8 = reinterpret_cast<uint8_t *>(c->d_scratch.p);
         uint8_t *p8 = out_fmt == 2 ? static_cast<uint8_t *>(paths_out) : reinterpret_cast<uint8_t *>(path);
         const int64_t *off = c->d_offsets.p;
         const int64_t want = (int64_t)GVR_ROWS * (c->num_simd / 4); // one workgroup of four segments per compute unit
         const int64_t fill0 = ((c->total + want - 1) / want + 7) / 8 * 8;
-        const int W0 = std::max(64, c->spec_W > 0 ? (c->spec_W + 7) / 8 * 8 : 128);
+        const int W0 = std::max(64, c->ds.spec_W > 0 ? (c->ds.spec_W + 7) / 8 * 8 : 128);
         // (six E-step forgetting lengths, at most one and a half fill lengths: at 256 states one boundary of 749 was
         // still 1e-12 off after 504 steps, none after 750 -- and a pass that is not accepted is lost time)
         // (round 6: with the mending round the E-step's length; a pass that is not accepted doubles it for the next call)
-        const int W_try = c->vit_W > 0 ? c->vit_W
-                          : (c->vit_mend ? W0
+        const int W_try = c->ds.vit_W > 0 ? c->ds.vit_W
+                          : (c->opt.vit_mend ? W0
                                          : (int)std::max<int64_t>(W0, std::min<int64_t>(6 * (int64_t)W0, (3 * fill0 / 2 + 7) / 8 * 8)));
         const int64_t seglen = std::max<int64_t>(fill0, W_try);
         Segs sg;
-        if ((rc = wide_path_plan_pub(c, 0, seglen, sg)))
+        if ((rc = wide_path_plan(c, 0, seglen, sg)))
             return rc;
         int64_t maxT = 0;
         for (int k = 0; k < K; ++k)
             maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
-        c->vit_margin_used = 0;
-        c->vit_margin_close = 0;
-        c->vit_seg_rounds = 0;
+        c->last.vit_margin_used = 0;
+        c->last.vit_margin_close = 0;
+        c->last.vit_seg_rounds = 0;
         // threads per target state (candidate ranges): 2 (BHMM_AMD_GVR_S = 1 / 4: experiments; measured 15.8 / 13.3 /
         // 14.1 ms at 129 states with 1 / 2 / 4)
         static const int gvr_s = getenv("BHMM_AMD_GVR_S") ? atoi(getenv("BHMM_AMD_GVR_S")) : 2;
@@ -521,7 +510,7 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
                 hipLaunchKernelGGL((k_wide_vit_walk<false, uint8_t, 4>), dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n,
                                    (const uint8_t *)ptr8, c->d_vmaps.p, (const uint8_t *)nullptr, (uint8_t *)nullptr);
                 hipLaunchKernelGGL(k_wide_vit_stitch, dim3((K + 63) / 64), dim3(64), 0, c->stream,
-                                   (const int32_t *)c->pplan[0].traj0.p, K, (const uint8_t *)c->d_vmaps.p, 256,
+                                   (const int32_t *)c->pplan_buf[0].traj0.p, K, (const uint8_t *)c->d_vmaps.p, 256,
                                    (const int32_t *)last, c->d_vend.p);
                 if (out_fmt == 0)
                     hipLaunchKernelGGL((k_wide_vit_walk<true, int32_t, 4>), dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n,
@@ -537,11 +526,11 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
             BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost,
                                     c->stream));
             BHMM_HIP(hipStreamSynchronize(c->stream));
-            c->vit_seg_mismatch = (int)c->h_specres[3];
-            c->vit_far = (int)c->h_specres[0];
+            c->last.vit_seg_mismatch = (int)c->h_specres[3];
+            c->last.vit_far = (int)c->h_specres[0];
             bool accepted = c->h_specres[3] == 0;
             int spliced = 0;
-            if (!accepted && c->h_specres[0] != 0 && (int64_t)c->h_specres[0] * 2 <= sg.nseg && c->vit_mend) {
+            if (!accepted && c->h_specres[0] != 0 && (int64_t)c->h_specres[0] * 2 <= sg.nseg && c->opt.vit_mend) {
                 // the mending round (see wide_viterbi_run): the rows of the segments further than vm_tol from their
                 // predecessors' vectors run again up to a vector the first pass kept; then the back-trace again
                 BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
@@ -561,7 +550,7 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
                 unsigned int notmet = 0;
                 BHMM_HIP(hipMemcpyAsync(&notmet, c->d_specres.p + 1, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
                 BHMM_HIP(hipStreamSynchronize(c->stream));
-                c->vit_mended = (int)c->h_specres[0];
+                c->last.vit_mended = (int)c->h_specres[0];
                 if (notmet == 0) {
                     spliced = (int)c->h_specres[0];
                     c->h_specres[0] = 0;
@@ -573,7 +562,7 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
                 const int maxseg = (int)((maxT + seglen - 1) / seglen) + 1 + spliced;
                 const double margin = std::max(1e-10, 16.0 * (2e-15 * (double)maxT + vm_tol * maxseg));
                 BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
-                const dim3 mgrid(sg.nseg, (unsigned)((c->pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
+                const dim3 mgrid(sg.nseg, (unsigned)((c->ds.pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
                 if (out_fmt == 0)
                     hipLaunchKernelGGL((k_vit_margin<int32_t, 4, false>), mgrid, dim3(256), 0, c->stream,
                                        (const double *)c->d_gAt.p, n, off, sg, (const double *)vall, (const int32_t *)path,
@@ -586,14 +575,14 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
                 BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost,
                                         c->stream));
                 BHMM_HIP(hipStreamSynchronize(c->stream));
-                c->vit_margin_close = (int)c->h_specres[2];
+                c->last.vit_margin_close = (int)c->h_specres[2];
                 accepted = c->h_specres[2] == 0;
-                c->vit_margin_used = accepted ? 1 : 0;
+                c->last.vit_margin_used = accepted ? 1 : 0;
             }
             if (accepted) {
-                c->viterbi_chunked = true;
-                c->vit_W = W_try;
-                c->vit_rows_fail = 0;
+                c->last.viterbi_chunked = true;
+                c->ds.vit_W = W_try;
+                c->ds.vit_rows_fail = 0;
                 if (out_fmt == 0)
                     BHMM_HIP(hipMemcpyAsync(paths_out, path, (size_t)c->total * sizeof(int32_t), hipMemcpyDeviceToHost,
                                             c->stream));
@@ -605,10 +594,10 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
             // One pass that was not accepted (a close decision under THIS model -- an early EM iterate, say) sends
             // this call to the serial kernel; the next call tries again with twice the warm-up, and only a second
             // failure in a row (or a warm-up that would exceed half a trajectory) gives the observations up.
-            if (++c->vit_rows_fail >= 2 || 4 * (int64_t)W_try > maxT)
-                c->vit_seg_given_up = true;
+            if (++c->ds.vit_rows_fail >= 2 || 4 * (int64_t)W_try > maxT)
+                c->ds.vit_seg_given_up = true;
             else
-                c->vit_W = 2 * W_try;
+                c->ds.vit_W = 2 * W_try;
         } else {
             (void)hipGetLastError();
         }
@@ -654,7 +643,7 @@ int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double 
                    int64_t *counts, int64_t *n0, double *emis, double *stats_dev)
 {
     WideModel m;
-    int rc = wide_model_pub(c, c->kind, A, pi, par0, par1, m);
+    int rc = wide_model(c, c->kind, A, pi, par0, par1, m);
     if (rc)
         return rc;
     // alpha rows in d_alpha_rm: from the tile forward pass over time segments where it verifies
@@ -664,15 +653,15 @@ int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double 
     bool fwd_seg = false;
     if (!c->draw_force_exact && (rc = tile_gen_forward_draw(c, m, &fwd_seg)))
         return rc;
-    c->draw_fwd_segmented = fwd_seg;
+    c->last.draw_fwd_segmented = fwd_seg;
     if (!fwd_seg) {
-        c->draw_alpha_dev = 0.0;
+        c->last.draw_alpha_dev = 0.0;
         if ((rc = gen_forward(c, A, pi, par0, par1)))
             return rc;
     }
     // rows of a segmented pass: draws within 64 x the deviation its boundary check measured are recorded
     DrawWatch watch;
-    if ((rc = draw_watch_prepare(c, fwd_seg ? 64.0 * std::max(c->draw_alpha_dev, 1e-16) : 0.0, watch, nullptr)))
+    if ((rc = draw_watch_prepare(c, fwd_seg ? 64.0 * std::max(c->last.draw_alpha_dev, 1e-16) : 0.0, watch, nullptr)))
         return rc;
     const int n = c->n, K = c->K;
     const size_t nstat = (size_t)n * n + n;
@@ -698,18 +687,18 @@ int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double 
     BHMM_HIP(hipMemsetAsync(status, 0, sizeof(int), c->stream));
     // up to 512 states: the draw over time segments (k_gen_sample_seg), coupled through the per-step
     // uniforms; segments that did not continue their successor's state are drawn again until none is left
-    c->smp_segmented = false;
+    c->last.smp_segmented = false;
     bool seg_done = false;
-    if (c->spec_enabled && n <= 512) {
-        const int64_t want = (int64_t)c->smp_seg_per_simd * c->num_simd;
+    if (c->opt.spec_enabled && n <= 512) {
+        const int64_t want = (int64_t)c->opt.smp_seg_per_simd * c->num_simd;
         const int64_t seglen = std::max<int64_t>((c->total + want - 1) / want, 64);
         Segs sg;
-        if ((rc = wide_path_plan_pub(c, 1, seglen, sg)))
+        if ((rc = wide_path_plan(c, 1, seglen, sg)))
             return rc;
         if (sg.nseg > K) {
-            if (c->smp_W <= 0)
-                c->smp_W = 64;
-            sg.W = c->smp_W;
+            if (c->ds.smp_W <= 0)
+                c->ds.smp_W = 64;
+            sg.W = c->ds.smp_W;
             if ((rc = gen_transposed(c, m)) || (rc = c->d_sentry.ensure((size_t)sg.nseg)) ||
                 (rc = c->d_sexit.ensure((size_t)sg.nseg)) || (rc = c->d_vflag.ensure((size_t)sg.nseg)) ||
                 (rc = c->d_specres.ensure(4)))
@@ -750,29 +739,29 @@ int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double 
                 BHMM_HIP(hipMemcpyAsync(&c->h_specres[0], status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
                 BHMM_HIP(hipStreamSynchronize(c->stream));
                 if (round == 0)
-                    c->smp_seg_mismatch = (int)c->h_specres[3];
+                    c->last.smp_seg_mismatch = (int)c->h_specres[3];
                 if (c->h_specres[3] == 0)
                     break;
             }
 #undef BHMM_GSS_SPL
 #undef BHMM_GSS
-            c->smp_seg_rounds = round;
+            c->last.smp_seg_rounds = round;
             // (a draw that found no state may belong to a segment that was drawn again afterwards:
             // the serial kernel decides such a call)
             seg_done = c->h_specres[3] == 0 && c->h_specres[0] == 0;
             if (!seg_done)
                 BHMM_HIP(hipMemsetAsync(status, 0, sizeof(int), c->stream));
-            if ((int64_t)c->smp_seg_mismatch * 10 > sg.nseg && c->smp_W < 4096)
-                c->smp_W *= 2;
-            c->smp_segmented = seg_done;
+            if ((int64_t)c->last.smp_seg_mismatch * 10 > sg.nseg && c->ds.smp_W < 4096)
+                c->ds.smp_W *= 2;
+            c->last.smp_segmented = seg_done;
         }
     }
     size_t sm = gen_smem(n, 2, 4);
     if (!seg_done && fwd_seg) { // (the serial draw has no watch: it reads rows of the serial recursion)
         if ((rc = gen_forward(c, A, pi, par0, par1)))
             return rc;
-        c->draw_fwd_segmented = false;
-        c->draw_alpha_dev = 0.0;
+        c->last.draw_fwd_segmented = false;
+        c->last.draw_alpha_dev = 0.0;
     }
     if (seg_done && watch.count) {
         // watched draws are decided again on the serial recursion over a long window; if one does not stand, the
@@ -782,16 +771,16 @@ int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double 
         BHMM_HIP(hipStreamSynchronize(c->stream));
         if (nwatched) {
             bool ok = false;
-            if ((rc = draw_verify_run(c, A, pi, par0, par1, nwatched, watch.tol, 8 * (int64_t)std::max(c->spec_W, 64), &ok)))
+            if ((rc = draw_verify_run(c, A, pi, par0, par1, nwatched, watch.tol, 8 * (int64_t)std::max(c->ds.spec_W, 64), &ok)))
                 return rc;
             if (!ok) {
-                const unsigned int ev = c->draw_events, ck = c->draw_checked;
+                const unsigned int ev = c->last.draw_events, ck = c->last.draw_checked;
                 c->draw_force_exact = true;
                 rc = gen_sample_run(c, A, pi, par0, par1, u, seed, paths, counts, n0, emis, stats_dev);
                 c->draw_force_exact = false;
-                c->draw_events = ev;
-                c->draw_checked = ck;
-                c->draw_redone = 1;
+                c->last.draw_events = ev;
+                c->last.draw_checked = ck;
+                c->last.draw_redone = 1;
                 return rc;
             }
         }

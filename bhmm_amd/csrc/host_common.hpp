@@ -67,13 +67,4 @@ inline void fill_model(Model<N> &m, int n, int kind, int M, const double *A, con
         gauss_pdf_constants(n, N, par1, m.e4, m.e5, &m.emg);
 }
 
-
-inline int pad_states_pub(int n) { return pad_states(n); }
-template <int N>
-inline void fill_model_pub(Model<N> &m, int n, int kind, int M, const double *A, const double *pi,
-                           const double *par0, const double *par1)
-{
-    fill_model<N>(m, n, kind, M, A, pi, par0, par1);
-}
-
 } // namespace bhmm

@@ -1,0 +1,74 @@
+// host_internal.hpp -- functions one translation unit of libbhmm_amd.so calls in another.  Every defining
+// unit includes this header as well, so the compiler checks each declaration against its definition.
+#pragma once
+#include <stdint.h>
+
+#include <string>
+
+#include "ctx.hpp"
+
+namespace bhmm {
+
+struct Chunks;    // estep_kernels.hpp
+struct Segs;      // wide_kernels.hpp
+struct WideModel; // wide_kernels.hpp
+struct DrawWatch; // draw_verify.hpp
+
+// ---- bhmm_amd.hip (up to 8 states, context, E-step) ----
+int invalid_arg(const std::string &msg); // error message + BHMM_ERR_INVALID
+Chunks chunks_of(const bhmm_ctx *c);
+int forward_ci(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1);
+int forward_ci_verdict(bhmm_ctx *c, bool *ok);
+int unpack_ws_rows(bhmm_ctx *c, double *dst_dev);
+// The checks every model entry point (bhmm_estep, bhmm_viterbi_batch[_u8], bhmm_sample_paths[_dev]) starts with:
+// observations loaded; `given` (its pointer arguments are there, else null_msg); with `emissions`, the
+// parameters the emission kind needs.  Then the context's device is made current.
+int enter_model_call(bhmm_ctx *c, bool given, const char *null_msg, bool emissions, const double *par0,
+                     const double *par1);
+
+// ---- wide_api.hip (9..64 states) ----
+int wide_alloc(bhmm_ctx *c);
+int wide_model(bhmm_ctx *c, int kind, const double *A, const double *pi, const double *par0, const double *par1,
+               WideModel &m);
+int wide_plan(bhmm_ctx *c, int which, int64_t seglen, int mult = 1);
+Segs segs_of(bhmm_ctx *c, int which);
+int wide_forward(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1);
+int wide_forward_draw(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1);
+int wide_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+               double *stats_dev, int flags);
+int wide_backward(bhmm_ctx *c, const double *A);
+int wide_transition_counts(double *C, const double *A, const double *pobs, const double *alpha, const double *beta,
+                           int n, int64_t T);
+
+// ---- path_api.hip (Viterbi, path sampling) ----
+int wide_path_plan(bhmm_ctx *c, int which, int64_t seglen, Segs &sg);
+int draw_watch_prepare(bhmm_ctx *c, double tol, DrawWatch &w, unsigned int *count_slot);
+int draw_verify_run(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                    unsigned int count, double thr, int64_t Wlong, bool *ok);
+
+// ---- gen_api.hip (more than 64 states) ----
+int gen_alloc(bhmm_ctx *c);
+int gen_forward(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1);
+int gen_backward(bhmm_ctx *c, const double *A);
+int gen_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+              double *stats_dev, int flags);
+int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                    void *paths_out, int out_fmt);
+int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                   const double *u, uint64_t seed, int32_t *paths, int64_t *counts, int64_t *n0, double *emis,
+                   double *stats_dev);
+int gen_transition_counts(double *C, const double *A, const double *pobs, const double *alpha, const double *beta,
+                          int N, int64_t T);
+int gen_sample_path(int32_t *path, const double *alpha, const double *A, const double *u, int N, int64_t T);
+
+// ---- tile_gen.hip (65..512 states on the row-batched matrix-core kernels) ----
+bool tile_gen_capable(const bhmm_ctx *c);
+int tile_gen_alloc(bhmm_ctx *c);
+int tile_gen_estep(bhmm_ctx *c, const WideModel &m, double *stats_dev, int flags, bool *done);
+int tile_gen_forward_draw(bhmm_ctx *c, const WideModel &m, bool *done);
+
+// ---- big_api.hip (more than 128 states, A streamed from L2) ----
+int big_launch_fwd(bhmm_ctx *c, const WideModel &m);
+int big_launch_bwd(bhmm_ctx *c, const WideModel &m, double *gam, double *stats_dev);
+
+} // namespace bhmm

@@ -11,35 +11,12 @@
 #include <vector>
 
 #include "host_common.hpp"
+#include "host_internal.hpp"
 #include "plan.hpp"
 #include "path_kernels.hpp"
 #include "draw_verify.hpp"
 
 namespace bhmm {
-int invalid_arg(const std::string &msg);
-int wide_model_pub(bhmm_ctx *c, int kind, const double *A, const double *pi, const double *par0,
-                   const double *par1, WideModel &m);
-int wide_forward_draw(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
-                      const double *par1);
-int wide_forward(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
-                 const double *par1);
-int wide_transition_counts(double *C, const double *A, const double *pobs, const double *alpha,
-                           const double *beta, int n, int64_t T);
-int forward_ci(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
-               const double *par1);
-int forward_ci_verdict(bhmm_ctx *c, bool *ok);
-// gen_api.hip (more than 64 states)
-int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
-                    const double *par1, void *paths_out, int out_fmt);
-int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
-                   const double *par1, const double *u, uint64_t seed, int32_t *paths,
-                   int64_t *counts, int64_t *n0, double *emis, double *stats_dev);
-int gen_transition_counts(double *C, const double *A, const double *pobs, const double *alpha,
-                          const double *beta, int N, int64_t T);
-int gen_sample_path(int32_t *path, const double *alpha, const double *A, const double *u, int N,
-                    int64_t T);
-int unpack_ws_rows(bhmm_ctx *c, double *dst_dev);
-Chunks chunks_pub(const bhmm_ctx *c);
 
 // ---- draws inside the reach of the alpha rows' verified deviation (draw_verify.hpp) ---------------
 // d_dv: [count | disagree | unconverged | checked] | DrawEvent[DRAW_EVENT_CAP] | model
@@ -53,8 +30,8 @@ int draw_watch_prepare(bhmm_ctx *c, double tol, DrawWatch &w, unsigned int *coun
     w.ev = nullptr;
     w.count = nullptr;
     w.tol = 0.0;
-    c->draw_events = c->draw_checked = c->draw_redone = 0;
-    if (!c->draw_watch || !(tol > 0.0))
+    c->last.draw_events = c->last.draw_checked = c->last.draw_redone = 0;
+    if (!c->opt.draw_watch || !(tol > 0.0))
         return BHMM_OK;
     const size_t msz = ((size_t)c->n * c->n + 3 * (size_t)c->n +
                         (c->kind == EMIT_DISC ? (size_t)c->n * c->M : 0)) * sizeof(double);
@@ -65,7 +42,7 @@ int draw_watch_prepare(bhmm_ctx *c, double tol, DrawWatch &w, unsigned int *coun
         BHMM_HIP(hipMemsetAsync(c->d_dv.p, 0, 16, c->stream));
     w.count = count_slot ? count_slot : reinterpret_cast<unsigned int *>(c->d_dv.p);
     w.ev = reinterpret_cast<DrawEvent *>(c->d_dv.p + 16);
-    w.tol = c->draw_watch_tol > 0.0 ? c->draw_watch_tol : tol;
+    w.tol = c->opt.draw_watch_tol > 0.0 ? c->opt.draw_watch_tol : tol;
     return BHMM_OK;
 }
 
@@ -75,7 +52,7 @@ int draw_verify_run(bhmm_ctx *c, const double *A, const double *pi, const double
                     unsigned int count, double thr, int64_t Wlong, bool *ok)
 {
     *ok = false;
-    c->draw_events = count;
+    c->last.draw_events = count;
     if (count > DRAW_EVENT_CAP)
         return BHMM_OK; // (more than the list holds: the exact rows decide)
     const int n = c->n;
@@ -99,8 +76,8 @@ int draw_verify_run(bhmm_ctx *c, const double *A, const double *pi, const double
     unsigned int h[4] = {0, 0, 0, 0};
     BHMM_HIP(hipMemcpyAsync(h, res, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     BHMM_HIP(hipStreamSynchronize(c->stream));
-    c->draw_checked = h[3];
-    *ok = h[1] == 0 && h[2] == 0 && !(c->draw_test_redo && h[3] > 0);
+    c->last.draw_checked = h[3];
+    *ok = h[1] == 0 && h[2] == 0 && !(c->opt.draw_test_redo && h[3] > 0);
     return BHMM_OK;
 }
 
@@ -141,11 +118,11 @@ int sample_run(bhmm_ctx *c, const double *A, const double *pi, const double *par
     c->fwd_defer = defer_check && !no_defer && !exact;
     // exact: the transfer-matrix pass (every boundary vector computed, none assumed) -- the repeat of a call
     // in which a watched draw did not stand (draw_verify.hpp)
-    const bool spec_saved = c->spec_enabled;
+    const bool spec_saved = c->opt.spec_enabled;
     if (exact)
-        c->spec_enabled = false;
+        c->opt.spec_enabled = false;
     int rc = forward_ci(c, A, pi, par0, par1);
-    c->spec_enabled = spec_saved;
+    c->opt.spec_enabled = spec_saved;
     c->fwd_defer = false;
     if (rc)
         return rc;
@@ -218,17 +195,17 @@ int sample_run(bhmm_ctx *c, const double *A, const double *pi, const double *par
                                 c->stream));
     }
     Model<N> m;
-    fill_model_pub<N>(m, n, c->kind, c->M, A, pi, par0, par1);
+    fill_model<N>(m, n, c->kind, c->M, A, pi, par0, par1);
     m.bt_global = bigM ? 1 : 0;
     // rows of a speculative pass: draws within 64 x the tolerance of its boundary check are recorded (the
     // measured deviation, usually far smaller, is applied when they are looked at)
     DrawWatch watch;
-    if ((rc = draw_watch_prepare(c, c->rows32_valid && !exact ? 64.0 * c->spec_tol : 0.0, watch,
+    if ((rc = draw_watch_prepare(c, c->rows32_valid && !exact ? 64.0 * c->opt.spec_tol : 0.0, watch,
                                  reinterpret_cast<unsigned int *>(status) + 1))) // (second word of the cleared status slot)
         return rc;
     {
         // exact chunk-parallel sampling: maps per part, stitch, apply + statistics
-        const Chunks chs = chunks_pub(c);
+        const Chunks chs = chunks_of(c);
         const int64_t *offd = c->d_offsets.p;
         const void *obs_ci = c->d_obs_ci.p;
         const int64_t *soffd = c->d_soff.p ? c->d_soff.p : c->d_offsets.p;
@@ -330,21 +307,21 @@ int sample_run(bhmm_ctx *c, const double *A, const double *pi, const double *par
     }
     hstatus = hst[0];
     const unsigned int nwatched = watch.count ? (unsigned int)hst[1] : 0u;
-    c->draw_alpha_dev = watch.count ? (double)c->spec_last_dev : 0.0;
+    c->last.draw_alpha_dev = watch.count ? (double)c->last.spec_last_dev : 0.0;
     if (nwatched) {
         // draws inside 64 x the deviation the boundary check measured: decided again on the serial recursion
         // over a long window; if one does not stand, the whole call again on the transfer-matrix rows
         bool ok = false;
-        const double thr = c->draw_watch_tol > 0.0 ? c->draw_watch_tol
-                                                   : 64.0 * std::max((double)c->spec_last_dev, 1e-16);
-        if ((rc = draw_verify_run(c, A, pi, par0, par1, nwatched, thr, 8 * (int64_t)std::max(c->spec_W, 64), &ok)))
+        const double thr = c->opt.draw_watch_tol > 0.0 ? c->opt.draw_watch_tol
+                                                   : 64.0 * std::max((double)c->last.spec_last_dev, 1e-16);
+        if ((rc = draw_verify_run(c, A, pi, par0, par1, nwatched, thr, 8 * (int64_t)std::max(c->ds.spec_W, 64), &ok)))
             return rc;
         if (!ok) {
-            const unsigned int ev = c->draw_events, ck = c->draw_checked;
+            const unsigned int ev = c->last.draw_events, ck = c->last.draw_checked;
             rc = sample_run<N>(c, A, pi, par0, par1, u, seed, paths, counts, n0, emis, stats_dev, false, true);
-            c->draw_events = ev;
-            c->draw_checked = ck;
-            c->draw_redone = 1;
+            c->last.draw_events = ev;
+            c->last.draw_checked = ck;
+            c->last.draw_redone = 1;
             return rc;
         }
     }
@@ -374,23 +351,26 @@ int sample_run(bhmm_ctx *c, const double *A, const double *pi, const double *par
     return BHMM_OK;
 }
 
+} // namespace
+
 // time segments of at most seglen steps for the segment-parallel Viterbi pass (which = 0) / backward
 // sampler (which = 1); rebuilt only when the length changes
 int wide_path_plan(bhmm_ctx *c, int which, int64_t seglen, Segs &sg)
 {
-    bhmm_ctx::PathPlan &pp = c->pplan[which];
+    auto &pp = c->ds.pplan[which];
+    auto &pb = c->pplan_buf[which];
     if (pp.nseg == 0 || pp.seglen != seglen) {
         plan::SegPlan sp;
         plan::plan_segments(c->offsets, c->K, seglen, 1, sp);
         const int ns = (int)sp.traj.size();
         int rc;
-        if ((rc = pp.traj.ensure(std::max(ns, 1))) || (rc = pp.len.ensure(std::max(ns, 1))) ||
-            (rc = pp.t0.ensure(std::max(ns, 1))) || (rc = pp.traj0.ensure(c->K + 1)))
+        if ((rc = pb.traj.ensure(std::max(ns, 1))) || (rc = pb.len.ensure(std::max(ns, 1))) ||
+            (rc = pb.t0.ensure(std::max(ns, 1))) || (rc = pb.traj0.ensure(c->K + 1)))
             return rc;
-        BHMM_HIP(hipMemcpyAsync(pp.traj0.p, sp.traj0.data(), (c->K + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        BHMM_HIP(hipMemcpyAsync(pp.traj.p, sp.traj.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        BHMM_HIP(hipMemcpyAsync(pp.len.p, sp.len.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        BHMM_HIP(hipMemcpyAsync(pp.t0.p, sp.t0.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipMemcpyAsync(pb.traj0.p, sp.traj0.data(), (c->K + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipMemcpyAsync(pb.traj.p, sp.traj.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipMemcpyAsync(pb.len.p, sp.len.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipMemcpyAsync(pb.t0.p, sp.t0.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
         BHMM_HIP(hipStreamSynchronize(c->stream)); // (the vectors go out of scope)
         pp.nseg = ns;
         pp.seglen = seglen;
@@ -398,12 +378,14 @@ int wide_path_plan(bhmm_ctx *c, int which, int64_t seglen, Segs &sg)
         for (int32_t l : sp.len)
             pp.maxlen = std::max<int64_t>(pp.maxlen, l);
     }
-    sg.traj = pp.traj.p;
-    sg.len = pp.len.p;
-    sg.t0 = pp.t0.p;
+    sg.traj = pb.traj.p;
+    sg.len = pb.len.p;
+    sg.t0 = pb.t0.p;
     sg.nseg = pp.nseg;
     return BHMM_OK;
 }
+
+namespace {
 
 // ---- 9..64 states ---------------------------------------------------------------------
 // out_fmt: 0 = int32 paths to a host buffer (the reference's type, hidden.pyx:161-162),
@@ -413,12 +395,12 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
                      const double *par1, void *paths_out, int out_fmt)
 {
     WideModel m;
-    int rc = wide_model_pub(c, c->kind, A, pi, par0, par1, m);
+    int rc = wide_model(c, c->kind, A, pi, par0, par1, m);
     if (rc)
         return rc;
     const int K = c->K, n = c->n, NP = c->wide ? c->N : 8, GP = 64 / NP;
-    c->viterbi_chunked = false;
-    c->vit_mended = 0;
+    c->last.viterbi_chunked = false;
+    c->last.vit_mended = 0;
     const size_t gpad = c->wide ? 0 : (size_t)c->Gp;
     if ((rc = c->d_scratch.ensure((size_t)c->total * n)) ||
         (rc = c->d_scratch2.ensure(((size_t)c->total + K + 3 * gpad) * sizeof(int32_t))))
@@ -443,7 +425,7 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
     int vkind = c->kind;
     // n <= 8 with a chunk plan: the chunk-parallel kernel evaluates the emission itself (gathers
     // from B / evaluates the gaussian density): no (total, n) emission matrix is written and re-read
-    const bool disc_direct = !c->wide && c->kind != EMIT_EXPL && c->spec_enabled && c->G > K;
+    const bool disc_direct = !c->wide && c->kind != EMIT_EXPL && c->opt.spec_enabled && c->G > K;
     // 9..64 states over time segments, discrete: the kernel gathers from B itself (no (total, n) matrix).
     // Measured for the Gaussian kind too: the division by sigma and the exponential in every step,
     // warm-ups included, cost more than the matrix pass saves (64 states: 9.0 -> 9.7 ms, 16: 0.67 -> 0.81).
@@ -451,7 +433,7 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
     // exponential of k_pobs_lanes -- at 64 states: 6.5 GB less written and read again per call)
     static const bool gauss_matrix = getenv("BHMM_AMD_VIT_GAUSS_MATRIX") != nullptr; // (experiments: the round-5 way)
     const bool wide_direct = c->wide && (c->kind == EMIT_DISC || (c->kind == EMIT_GAUSS && !gauss_matrix)) &&
-                             c->spec_enabled && !c->vit_seg_given_up;
+                             c->opt.spec_enabled && !c->ds.vit_seg_given_up;
     if (c->kind != EMIT_EXPL && !disc_direct && !wide_direct) {
         size_t freeb = 0, totb = 0;
         const size_t need = (size_t)c->total * n * sizeof(double);
@@ -512,7 +494,7 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
     const bool vit4 = !c->wide && n <= 4;
     auto launch_walks_np = [&](auto npc) {
         constexpr int VNP = decltype(npc)::value;
-        const Chunks chs = chunks_pub(c);
+        const Chunks chs = chunks_of(c);
         const dim3 wg((c->G + 64 / VNP - 1) / (64 / VNP));
         if (out_fmt == 0)
             hipLaunchKernelGGL((k_vit_walk<VNP, false, int32_t>), wg, dim3(64), 0, c->stream, chs, c->G, n,
@@ -545,7 +527,7 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
     // n <= 8 with a chunk plan: the chunk-parallel run first; its back-pointers are accepted only
     // if every chunk boundary verifies and no decision was close (k_viterbi_chunks)
     bool done = false;
-    if (!c->wide && (vkind == EMIT_EXPL || disc_direct) && c->spec_enabled && c->G > K) {
+    if (!c->wide && (vkind == EMIT_EXPL || disc_direct) && c->opt.spec_enabled && c->G > K) {
         int maxchunks = 1;
         for (int k = 0; k < K; ++k)
             maxchunks = std::max(maxchunks, c->traj_c0[k + 1] - c->traj_c0[k]);
@@ -556,7 +538,7 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
         if (!c->h_specres)
             BHMM_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_specres), 4 * sizeof(unsigned int),
                                    hipHostMallocDefault));
-        const Chunks chs = chunks_pub(c);
+        const Chunks chs = chunks_of(c);
         // discrete: B in LDS when it is small enough to leave four wavefronts per SIMD their room
         const size_t smB = (disc_direct && c->kind == EMIT_DISC &&
                             (size_t)n * c->M * sizeof(double) <= 16 * 1024)
@@ -570,24 +552,24 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
         // length; every later call that verified tries three quarters of the last good length, until
         // one does not verify -- that one is repeated with the last good length in the same call, and
         // the search ends (at most one lost pass per set of observations).
-        int W_try = c->vit_W > 0 ? c->vit_W : c->spec_W;
+        int W_try = c->ds.vit_W > 0 ? c->ds.vit_W : c->ds.spec_W;
         bool exploring = false;
-        if (c->vit_W > 0 && c->vit_explore && !c->spec_W_fixed) {
-            const int Wn = std::max(32, (c->vit_W * 3 / 4 + 7) / 8 * 8);
-            if (Wn < c->vit_W && Wn > c->vit_bad) {
+        if (c->ds.vit_W > 0 && c->ds.vit_explore && !c->opt.spec_W_fixed) {
+            const int Wn = std::max(32, (c->ds.vit_W * 3 / 4 + 7) / 8 * 8);
+            if (Wn < c->ds.vit_W && Wn > c->ds.vit_bad) {
                 W_try = Wn;
                 exploring = true;
             } else {
-                c->vit_explore = false;
+                c->ds.vit_explore = false;
             }
         }
         for (int attempt = 0; attempt < 3; ++attempt) {
         if (attempt > 0) {
             if (exploring) { // the shorter warm-up did not verify: back to the one that did
-                c->vit_bad = W_try;
-                c->vit_explore = false;
+                c->ds.vit_bad = W_try;
+                c->ds.vit_explore = false;
                 exploring = false;
-                W_try = c->vit_W;
+                W_try = c->ds.vit_W;
             } else {
                 W_try *= 2;
             }
@@ -653,23 +635,23 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
         if (exploring && !accepted)
             continue; // (a shorter warm-up must be as good as the longer one was, not merely tolerable)
         if (c->h_specres[0] == 0) {
-            c->vit_W = W_try; // (what worked is where the next call on these observations starts)
+            c->ds.vit_W = W_try; // (what worked is where the next call on these observations starts)
             break; // every boundary within tolerance: a longer warm-up changes nothing
         }
         }
         // all boundaries bit-identical: it is the serial run; else within tolerance and no
         // close decision
         done = c->h_specres[3] == 0 || (c->h_specres[0] == 0 && c->h_specres[2] == 0);
-        c->viterbi_chunked = done;
+        c->last.viterbi_chunked = done;
         float dev;
         memcpy(&dev, &c->h_specres[1], sizeof(float));
-        c->spec_last_dev = dev;
-        c->viterbi_close = c->h_specres[2];
+        c->last.spec_last_dev = dev;
+        c->last.viterbi_close = c->h_specres[2];
     }
     // 9..64 states: one lane group per time segment (k_wide_viterbi_seg); accepted only if EVERY
     // segment arrives at its first step with the bit pattern its predecessor left there -- then the
     // back-pointers are the serial run's, by induction from the exact first segment of each trajectory
-    if (c->wide && c->spec_enabled && !c->vit_seg_given_up) {
+    if (c->wide && c->opt.spec_enabled && !c->ds.vit_seg_given_up) {
         // warm-up: its own, not the E-step's.  Every length is exact (bitwise check + fix-up rounds), so the length
         // only trades warm-up steps (W / segment length of the first pass) against rounds (1.1 ms each at configs[3],
         // whatever the number of flagged segments) -- and the E-step's length says little about that: its boundary
@@ -677,8 +659,8 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
         // while the max-product vectors are within rounding noise of their predecessors' after 128 (one round
         // either way: 17.6 ms against 23.6).  Start at 128 steps (less if the filter forgets faster); a call that
         // needed three or more rounds doubles the length for the next call on these observations, up to the E-step's.
-        const int W_estep = std::max(64, c->spec_W > 0 ? (c->spec_W + 7) / 8 * 8 : 128);
-        int W_try = c->vit_W > 0 ? c->vit_W : std::min(128, W_estep);
+        const int W_estep = std::max(64, c->ds.spec_W > 0 ? (c->ds.spec_W + 7) / 8 * 8 : 128);
+        int W_try = c->ds.vit_W > 0 ? c->ds.vit_W : std::min(128, W_estep);
         const bool exploring = false;
         if ((rc = c->d_specres.ensure(4)))
             return rc;
@@ -692,15 +674,15 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
         int64_t maxT = 0;
         // (up to 64 states one fix-up round is short -- 1.1 ms at configs[3] -- and cheaper than keeping the
         // vectors and checking the margins: only observations that needed two or more rounds before take this way)
-        if (c->vit_margin && c->vit_margin_want && c->d_gW.ensure((size_t)c->total * n) == BHMM_OK) {
+        if (c->opt.vit_margin && c->ds.vit_margin_want && c->d_gW.ensure((size_t)c->total * n) == BHMM_OK) {
             vall = c->d_gW.p;
             for (int k = 0; k < K; ++k)
                 maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
         } else {
             (void)hipGetLastError();
         }
-        c->vit_margin_used = 0;
-        c->vit_margin_close = 0;
+        c->last.vit_margin_used = 0;
+        c->last.vit_margin_close = 0;
         // back-trace over the segments: maps, stitch, apply
         auto seg_walks = [&]() -> int {
             // on a plan of its own, eight times finer than the pass's: a walk is a chain of dependent look-ups, its
@@ -708,7 +690,7 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
             Segs sgw;
             int rcw;
             static const int walk_div = getenv("BHMM_AMD_WALK_DIV") ? atoi(getenv("BHMM_AMD_WALK_DIV")) : 8;
-            if ((rcw = wide_path_plan(c, 2, std::max<int64_t>(256, c->pplan[0].seglen / walk_div), sgw)))
+            if ((rcw = wide_path_plan(c, 2, std::max<int64_t>(256, c->ds.pplan[0].seglen / walk_div), sgw)))
                 return rcw;
             sgw.W = 0;
             if ((rcw = c->d_vmaps.ensure((size_t)sgw.nseg * 64)) || (rcw = c->d_vend.ensure((size_t)sgw.nseg)))
@@ -716,7 +698,7 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
             hipLaunchKernelGGL((k_wide_vit_walk<false, uint8_t>), dim3(sgw.nseg), dim3(64), 0, c->stream, off, sgw, n,
                                (const uint8_t *)ptr, c->d_vmaps.p, (const uint8_t *)nullptr, (uint8_t *)nullptr);
             hipLaunchKernelGGL(k_wide_vit_stitch, dim3((K + 63) / 64), dim3(64), 0, c->stream,
-                               (const int32_t *)c->pplan[2].traj0.p, K, (const uint8_t *)c->d_vmaps.p, 64,
+                               (const int32_t *)c->pplan_buf[2].traj0.p, K, (const uint8_t *)c->d_vmaps.p, 64,
                                (const int32_t *)last, c->d_vend.p);
             if (out_fmt == 0)
                 hipLaunchKernelGGL((k_wide_vit_walk<true, int32_t>), dim3(sgw.nseg), dim3(64), 0, c->stream, off, sgw, n,
@@ -732,8 +714,8 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
                 W_try *= 2;
             }
             // two lane groups' worth of segments per SIMD, none shorter than two warm-ups
-            const int64_t want = (int64_t)c->vit_seg_per_simd * c->num_simd * GP;
-            const int64_t seglen = std::max<int64_t>((c->total + want - 1) / want, c->vit_seg_warmups * (int64_t)W_try);
+            const int64_t want = (int64_t)c->opt.vit_seg_per_simd * c->num_simd * GP;
+            const int64_t seglen = std::max<int64_t>((c->total + want - 1) / want, c->opt.vit_seg_warmups * (int64_t)W_try);
             Segs sg;
             if ((rc = wide_path_plan(c, 0, seglen, sg)))
                 return rc;
@@ -788,8 +770,8 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
             const int max_rounds = 12;
             int round = 0;
             bool margin_accepted = false;
-            bool allow_mend = c->vit_mend, mended = false;
-            c->vit_mended = 0;
+            bool allow_mend = c->opt.vit_mend, mended = false;
+            c->last.vit_mended = 0;
             for (; round <= max_rounds; ++round) {
                 BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
                 lds_poison(c->stream);
@@ -802,8 +784,8 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
                                         hipMemcpyDeviceToHost, c->stream));
                 BHMM_HIP(hipStreamSynchronize(c->stream));
                 if (round == 0) {
-                    c->vit_seg_mismatch = (int)c->h_specres[3];
-                    c->vit_far = (int)c->h_specres[0];
+                    c->last.vit_seg_mismatch = (int)c->h_specres[3];
+                    c->last.vit_far = (int)c->h_specres[0];
                 }
                 if (c->h_specres[3] == 0)
                     break;
@@ -829,7 +811,7 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
                     BHMM_HIP(hipMemcpyAsync(&notmet, c->d_specres.p + 1, sizeof(unsigned int), hipMemcpyDeviceToHost,
                                             c->stream));
                     BHMM_HIP(hipStreamSynchronize(c->stream));
-                    c->vit_mended = (int)c->h_specres[0];
+                    c->last.vit_mended = (int)c->h_specres[0];
                     if (notmet == 0) {
                         spliced = (int)c->h_specres[0];
                         c->h_specres[0] = 0;
@@ -844,7 +826,7 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
                         return rc;
                     BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
                     const size_t smm = (size_t)n * (n | 1) * sizeof(double); // (odd pitch, k_vit_margin)
-                    const dim3 mgrid(sg.nseg, (unsigned)((c->pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
+                    const dim3 mgrid(sg.nseg, (unsigned)((c->ds.pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
                     static const bool vm_global = getenv("BHMM_AMD_VM_GLOBAL") != nullptr; // (experiment: A^T from L2)
                     if (vm_global) {
                         if ((rc = c->d_gAt.ensure((size_t)n * n)))
@@ -866,9 +848,9 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
                     BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
                                             hipMemcpyDeviceToHost, c->stream));
                     BHMM_HIP(hipStreamSynchronize(c->stream));
-                    c->vit_margin_close = (int)c->h_specres[2];
+                    c->last.vit_margin_close = (int)c->h_specres[2];
                     if (c->h_specres[2] == 0) {
-                        c->vit_margin_used = 1;
+                        c->last.vit_margin_used = 1;
                         margin_accepted = true;
                         break;
                     }
@@ -889,14 +871,14 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
 #undef BHMM_WVS
 #undef BHMM_WVS_MEND_KIND
 #undef BHMM_WVS_MEND
-            c->vit_seg_rounds = round;
+            c->last.vit_seg_rounds = round;
             // (a round runs as long as its longest flagged segment needs to fall onto a vector of the first pass
             // again: 1.1 ms at configs[3] on white-noise observations, 6.7 ms -- half a first pass -- on
             // observations drawn from the model, where 1800 of 2048 boundaries carry rounding noise.  The margins
             // cost about 1.3 ms there: wanted from the next call on when rounds were many, or the flagged
             // segments more than a quarter)
-            if (round >= 2 || (round >= 1 && !margin_accepted && (int64_t)c->vit_seg_mismatch * 4 > sg.nseg))
-                c->vit_margin_want = true;
+            if (round >= 2 || (round >= 1 && !margin_accepted && (int64_t)c->last.vit_seg_mismatch * 4 > sg.nseg))
+                c->ds.vit_margin_want = true;
             const bool accepted = c->h_specres[3] == 0 || margin_accepted;
             // (How many boundaries the first pass left to the fix-up does not say whether the warm-up was
             // too short -- most of them are rounding noise, and a round costs the same for one segment as
@@ -907,15 +889,15 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
                 done = true;
                 // (boundaries further than 1e-12 apart keep the margin rule from being asked: a longer warm-up for
                 // the next call, like after three or more rounds -- never beyond the E-step's)
-                const bool longer = (vall && c->vit_far > 0 && !margin_accepted) || (round >= 3 && !margin_accepted);
-                c->vit_W = (longer && W_try < W_estep) ? std::min(2 * W_try, W_estep) : W_try;
+                const bool longer = (vall && c->last.vit_far > 0 && !margin_accepted) || (round >= 3 && !margin_accepted);
+                c->ds.vit_W = (longer && W_try < W_estep) ? std::min(2 * W_try, W_estep) : W_try;
             }
         }
-        if (!done && c->pplan[0].nseg > K)
-            c->vit_seg_given_up = true; // these observations go to the serial kernel from now on
-        c->viterbi_chunked = done;
+        if (!done && c->ds.pplan[0].nseg > K)
+            c->ds.vit_seg_given_up = true; // these observations go to the serial kernel from now on
+        c->last.viterbi_chunked = done;
         if (done) {
-            if (!c->vit_margin_used && (rc = seg_walks())) // (a margin-accepted pass has its path already)
+            if (!c->last.vit_margin_used && (rc = seg_walks())) // (a margin-accepted pass has its path already)
                 return rc;
             walks_in_flight = true;
         }
@@ -979,16 +961,16 @@ int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double
     if (rc)
         return rc;
     if (c->draw_force_exact) {
-        c->draw_fwd_segmented = false;
-        c->draw_alpha_dev = 0.0;
+        c->last.draw_fwd_segmented = false;
+        c->last.draw_alpha_dev = 0.0;
     }
     WideModel m;
-    if ((rc = wide_model_pub(c, c->kind, A, pi, par0, par1, m)))
+    if ((rc = wide_model(c, c->kind, A, pi, par0, par1, m)))
         return rc;
     const int K = c->K, n = c->n, NP = c->N, GP = 64 / NP;
     // rows of a segmented pass: draws within 64 x the deviation its boundary check measured are recorded
     DrawWatch watch;
-    if ((rc = draw_watch_prepare(c, c->draw_fwd_segmented ? 64.0 * std::max(c->draw_alpha_dev, 1e-16) : 0.0, watch, nullptr)))
+    if ((rc = draw_watch_prepare(c, c->last.draw_fwd_segmented ? 64.0 * std::max(c->last.draw_alpha_dev, 1e-16) : 0.0, watch, nullptr)))
         return rc;
     const size_t nstat = (size_t)n * n + n;
     const size_t esz = c->kind == EMIT_GAUSS ? 3 * (size_t)n
@@ -1032,18 +1014,18 @@ int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double
     // parallel over time segments where that fills more of the device than the trajectories do
     // (k_wide_sample_seg): the draws are coupled through the per-step uniforms, segments that did not
     // continue their successor's state are drawn again until none is left
-    c->smp_segmented = false;
+    c->last.smp_segmented = false;
     bool seg_done = false;
-    if (c->spec_enabled) {
-        const int64_t want = (int64_t)c->smp_seg_per_simd * c->num_simd * GP;
+    if (c->opt.spec_enabled) {
+        const int64_t want = (int64_t)c->opt.smp_seg_per_simd * c->num_simd * GP;
         const int64_t seglen = std::max<int64_t>((c->total + want - 1) / want, 64);
         Segs sg;
         if ((rc = wide_path_plan(c, 1, seglen, sg)))
             return rc;
         if (sg.nseg > K) {
-            if (c->smp_W <= 0)
-                c->smp_W = 64;
-            sg.W = c->smp_W;
+            if (c->ds.smp_W <= 0)
+                c->ds.smp_W = 64;
+            sg.W = c->ds.smp_W;
             if ((rc = c->d_sentry.ensure((size_t)sg.nseg)) || (rc = c->d_sexit.ensure((size_t)sg.nseg)) ||
                 (rc = c->d_vflag.ensure((size_t)sg.nseg)) || (rc = c->d_specres.ensure(4)))
                 return rc;
@@ -1082,30 +1064,30 @@ int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double
                 BHMM_HIP(hipMemcpyAsync(&c->h_specres[0], status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
                 BHMM_HIP(hipStreamSynchronize(c->stream));
                 if (round == 0)
-                    c->smp_seg_mismatch = (int)c->h_specres[3];
+                    c->last.smp_seg_mismatch = (int)c->h_specres[3];
                 if (c->h_specres[3] == 0)
                     break;
             }
 #undef BHMM_WSS_NP
 #undef BHMM_WSS
-            c->smp_seg_rounds = round;
+            c->last.smp_seg_rounds = round;
             // (a draw that found no state may belong to a segment that was drawn again afterwards:
             // the serial kernel decides such a call)
             seg_done = c->h_specres[3] == 0 && c->h_specres[0] == 0;
             if (!seg_done)
                 BHMM_HIP(hipMemsetAsync(status, 0, sizeof(int), c->stream));
             // more than a tenth of the segments left to the fix-up: a longer warm-up next time
-            if ((int64_t)c->smp_seg_mismatch * 10 > sg.nseg && c->smp_W < 4096)
-                c->smp_W *= 2;
-            c->smp_segmented = seg_done;
+            if ((int64_t)c->last.smp_seg_mismatch * 10 > sg.nseg && c->ds.smp_W < 4096)
+                c->ds.smp_W *= 2;
+            c->last.smp_segmented = seg_done;
         }
     }
     if (!seg_done) {
-        if (c->draw_fwd_segmented) { // (the serial draw has no watch: it reads rows of the serial recursion)
+        if (c->last.draw_fwd_segmented) { // (the serial draw has no watch: it reads rows of the serial recursion)
             if ((rc = wide_forward(c, A, pi, par0, par1)))
                 return rc;
-            c->draw_fwd_segmented = false;
-            c->draw_alpha_dev = 0.0;
+            c->last.draw_fwd_segmented = false;
+            c->last.draw_alpha_dev = 0.0;
         }
         launch_serial();
     } else if (watch.count) {
@@ -1116,16 +1098,16 @@ int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double
         BHMM_HIP(hipStreamSynchronize(c->stream));
         if (nwatched) {
             bool ok = false;
-            if ((rc = draw_verify_run(c, A, pi, par0, par1, nwatched, watch.tol, 8 * (int64_t)std::max(c->spec_W, 64), &ok)))
+            if ((rc = draw_verify_run(c, A, pi, par0, par1, nwatched, watch.tol, 8 * (int64_t)std::max(c->ds.spec_W, 64), &ok)))
                 return rc;
             if (!ok) {
-                const unsigned int ev = c->draw_events, ck = c->draw_checked;
+                const unsigned int ev = c->last.draw_events, ck = c->last.draw_checked;
                 c->draw_force_exact = true;
                 rc = wide_sample_run(c, A, pi, par0, par1, u, seed, paths, counts, n0, emis, stats_dev);
                 c->draw_force_exact = false;
-                c->draw_events = ev;
-                c->draw_checked = ck;
-                c->draw_redone = 1;
+                c->last.draw_events = ev;
+                c->last.draw_checked = ck;
+                c->last.draw_redone = 1;
                 return rc;
             }
         }
@@ -1212,8 +1194,6 @@ int cur_device()
 
 } // namespace
 
-int wide_path_plan_pub(bhmm_ctx *c, int which, int64_t seglen, Segs &sg) { return wide_path_plan(c, which, seglen, sg); }
-
 } // namespace bhmm
 
 using namespace bhmm;
@@ -1223,17 +1203,8 @@ extern "C" {
 int bhmm_viterbi_batch(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
                        const double *par1, int32_t *paths)
 {
-    if (c)
-        lds_poison(c->stream); // (debugging aid, BHMM_AMD_POISON=1 only)
-    if (!c || c->kind < 0)
-        return invalid_arg("no observations loaded");
-    if (!A || !pi || !paths)
-        return invalid_arg("NULL argument");
-    if (c->kind == BHMM_EMIT_GAUSSIAN && (!par0 || !par1))
-        return invalid_arg("gaussian emissions need means and sigmas");
-    if (c->kind == BHMM_EMIT_DISCRETE && !par0)
-        return invalid_arg("discrete emissions need B");
-    BHMM_HIP(hipSetDevice(c->device));
+    if (int rc = enter_model_call(c, A && pi && paths, "NULL argument", true, par0, par1))
+        return rc;
     if (c->gen)
         return gen_viterbi_run(c, A, pi, par0, par1, paths, 0);
     // all state counts up to 64 use the LDS-exchange kernels (k_wide_viterbi_*)
@@ -1243,17 +1214,8 @@ int bhmm_viterbi_batch(bhmm_ctx *c, const double *A, const double *pi, const dou
 int bhmm_viterbi_batch_u8(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
                           const double *par1, uint8_t *paths, int paths_on_device)
 {
-    if (c)
-        lds_poison(c->stream); // (debugging aid, BHMM_AMD_POISON=1 only)
-    if (!c || c->kind < 0)
-        return invalid_arg("no observations loaded");
-    if (!A || !pi || !paths)
-        return invalid_arg("NULL argument");
-    if (c->kind == BHMM_EMIT_GAUSSIAN && (!par0 || !par1))
-        return invalid_arg("gaussian emissions need means and sigmas");
-    if (c->kind == BHMM_EMIT_DISCRETE && !par0)
-        return invalid_arg("discrete emissions need B");
-    BHMM_HIP(hipSetDevice(c->device));
+    if (int rc = enter_model_call(c, A && pi && paths, "NULL argument", true, par0, par1))
+        return rc;
     if (c->gen)
         return gen_viterbi_run(c, A, pi, par0, par1, paths, paths_on_device ? 2 : 1);
     return wide_viterbi_run(c, A, pi, par0, par1, paths, paths_on_device ? 2 : 1);
@@ -1263,13 +1225,8 @@ int bhmm_sample_paths(bhmm_ctx *c, const double *A, const double *pi, const doub
                       const double *par1, const double *u, uint64_t seed, int32_t *paths,
                       int64_t *counts, int64_t *n0, double *emis)
 {
-    if (c)
-        lds_poison(c->stream); // (debugging aid, BHMM_AMD_POISON=1 only)
-    if (!c || c->kind < 0)
-        return invalid_arg("no observations loaded");
-    if (!A || !pi)
-        return invalid_arg("NULL argument");
-    BHMM_HIP(hipSetDevice(c->device));
+    if (int rc = enter_model_call(c, A && pi, "NULL argument", false, par0, par1))
+        return rc;
     if (c->gen)
         return gen_sample_run(c, A, pi, par0, par1, u, seed, paths, counts, n0, emis, nullptr);
     if (c->wide)
@@ -1312,13 +1269,8 @@ int bhmm_sample_paths_dev(bhmm_ctx *c, const double *A, const double *pi, const 
                           const double *par1, const double *u, uint64_t seed, int32_t *paths,
                           double *stats_dev)
 {
-    if (c)
-        lds_poison(c->stream); // (debugging aid, BHMM_AMD_POISON=1 only)
-    if (!c || c->kind < 0)
-        return invalid_arg("no observations loaded");
-    if (!A || !pi || !stats_dev)
-        return invalid_arg("NULL argument");
-    BHMM_HIP(hipSetDevice(c->device));
+    if (int rc = enter_model_call(c, A && pi && stats_dev, "NULL argument", false, par0, par1))
+        return rc;
     if (c->gen)
         return gen_sample_run(c, A, pi, par0, par1, u, seed, paths, nullptr, nullptr, nullptr,
                               stats_dev);
@@ -1404,12 +1356,12 @@ int bhmm_sample_path(int32_t *path, const double *alpha, const double *A, const 
         }
         return BHMM_OK;
     }
-    const int NP = pad_states_pub(N);
+    const int NP = pad_states(N);
     std::vector<double> pi(N, 0.0);
 #define BHMM_SAMPLE_CASE(NN)                                                                    \
     {                                                                                           \
         Model<NN> m;                                                                            \
-        fill_model_pub<NN>(m, N, EMIT_EXPL, 0, A, pi.data(), nullptr, nullptr);                 \
+        fill_model<NN>(m, N, EMIT_EXPL, 0, A, pi.data(), nullptr, nullptr);                 \
         hipLaunchKernelGGL((k_sample_path<NN>), dim3(1), dim3(64), 0, 0, m,                     \
                            (const int64_t *)d_off, 1, (const double *)d_alpha,                  \
                            (const double *)d_u, (uint64_t)0, d_path, d_status);                 \
@@ -1476,7 +1428,7 @@ int bhmm_transition_counts(double *C, const double *A, const double *pobs, const
     int rc;
     const size_t cnt = (size_t)T * N;
     const int nblk = (int)std::min<int64_t>(1024, (T + 255) / 256);
-    const int NP = pad_states_pub(N);
+    const int NP = pad_states(N);
     if ((rc = tmp.alloc(&dA, (size_t)N * N)) || (rc = tmp.alloc(&dp, cnt)) ||
         (rc = tmp.alloc(&da, cnt)) || (rc = tmp.alloc(&db, cnt)) ||
         (rc = tmp.alloc(&dpart, (size_t)nblk * NP * NP)) || (rc = tmp.alloc(&dC, (size_t)N * N)))

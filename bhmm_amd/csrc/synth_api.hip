@@ -12,10 +12,9 @@
 #include <string>
 #include <vector>
 
-#include "ctx.hpp"
+#include "host_internal.hpp"
 
 namespace bhmm {
-int invalid_arg(const std::string &msg);
 
 namespace {
 

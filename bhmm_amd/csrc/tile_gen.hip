@@ -24,13 +24,9 @@
 #include "tile_gen_launch.hpp"
 
 namespace bhmm {
-int wide_plan_pub(bhmm_ctx *c, int which, int64_t seglen);
-Segs wide_segs_pub(bhmm_ctx *c, int which);
-int big_launch_fwd(bhmm_ctx *c, const WideModel &m);
-int big_launch_bwd(bhmm_ctx *c, const WideModel &m, double *gam, double *stats_dev);
 
 // 65 .. 128 states: tile_kernels.hpp (A's blocks in registers); 129 .. 512: big_kernels.hpp (streamed from L2)
-bool tile_gen_capable(const bhmm_ctx *c) { return c->tile_latched && c->gen && c->n <= 512; }
+bool tile_gen_capable(const bhmm_ctx *c) { return c->ds.tile_latched && c->gen && c->n <= 512; }
 
 TILE_GEN_LAUNCH_DECL(extern, 5)
 TILE_GEN_LAUNCH_DECL(extern, 6)
@@ -58,7 +54,7 @@ int64_t max_len(const bhmm_ctx *c)
 // warm-ups long
 int64_t fill_len(const bhmm_ctx *c)
 {
-    const int64_t want = 16 * (int64_t)(c->num_simd / 4) * c->tile_per_cu;
+    const int64_t want = 16 * (int64_t)(c->num_simd / 4) * c->opt.tile_per_cu;
     return std::max<int64_t>(((c->total + want - 1) / want + 3) & ~(int64_t)3, 16);
 }
 
@@ -68,14 +64,14 @@ int plan_for(bhmm_ctx *c, int W)
     // segments for every compute unit -- filling the chip is worth more than short warm-ups relative to the
     // segments: half a warm-up is long enough there)
     const int64_t wmin = c->n > big_from() ? std::max<int64_t>(W / 2, 32) : 2 * (int64_t)W;
-    int64_t seglen = c->wseg_len > 0 ? (int64_t)c->wseg_len : std::max<int64_t>(fill_len(c), wmin);
+    int64_t seglen = c->opt.wseg_len > 0 ? (int64_t)c->opt.wseg_len : std::max<int64_t>(fill_len(c), wmin);
     seglen = std::max(seglen, c->wseg_cur_len); // never more segments than allocated for
     if (seglen >= max_len(c))
         seglen = 0; // one segment per trajectory: no boundaries to verify
     if (c->w_nseg[1] > 0 && seglen == c->wseg_cur_len)
         return BHMM_OK;
     c->wseg_cur_len = seglen;
-    return wide_plan_pub(c, 1, seglen);
+    return wide_plan(c, 1, seglen);
 }
 
 // (the dispatch macros below paste the function name)
@@ -95,7 +91,7 @@ int plan_for(bhmm_ctx *c, int W)
 // boundary check of one direction (0 forward, 1 backward): flags -> host
 int run_check(bhmm_ctx *c, int dir)
 {
-    const Segs sg = wide_segs_pub(c, 1);
+    const Segs sg = segs_of(c, 1);
     if (dir == 0)
         hipLaunchKernelGGL(k_wide_check, dim3((sg.nseg + 15) / 16), dim3(256), 0, c->stream, sg, c->n,
                            (const double *)c->d_waentry.p, (const double *)c->d_waexit.p,
@@ -122,10 +118,10 @@ int calibrate(bhmm_ctx *c, const WideModel &m, bool *usable)
 {
     *usable = false;
     const int64_t maxT = max_len(c);
-    int W = std::max(16, (c->spec_W_fixed ? c->spec_W : 32) / 8 * 8);
+    int W = std::max(16, (c->opt.spec_W_fixed ? c->ds.spec_W : 32) / 8 * 8);
     double prevW = 0.0, prevdev = 1.0;
     for (int it = 0; it < 8; ++it) {
-        c->spec_W = W;
+        c->ds.spec_W = W;
         int rc = plan_for(c, W);
         if (rc)
             return rc;
@@ -137,19 +133,19 @@ int calibrate(bhmm_ctx *c, const WideModel &m, bool *usable)
         if ((rc = TILE_GEN_DISPATCH(launch_fwd, c, m)) || (rc = run_check(c, 0)) || (rc = read_flags(c)))
             return rc;
         if (c->h_specres[2]) { // left the range of the lazily scaled kernels: the order-faithful family
-            c->wide_trouble = c->h_specres[2];
+            c->last.wide_trouble = c->h_specres[2];
             c->tile_reason = 1;
             return BHMM_OK;
         }
         float devf;
         memcpy(&devf, &c->h_specres[1], sizeof(float));
         const double dev = std::max((double)devf, 1e-300);
-        c->spec_last_dev = devf;
+        c->last.spec_last_dev = devf;
         if (c->h_specres[0] == 0 && dev <= 3e-13) {
             *usable = true;
             return BHMM_OK;
         }
-        if (c->spec_W_fixed) {
+        if (c->opt.spec_W_fixed) {
             c->tile_reason = 6;
             return BHMM_OK; // the caller's warm-up does not verify: not ours to change
         }
@@ -180,16 +176,14 @@ int tile_gen_alloc(bhmm_ctx *c)
     const int n = c->n;
     c->N = 64; // (not used by this family; wide_fill_len never sees these contexts)
     int rc;
-    if ((rc = wide_plan_pub(c, 0, 0)))
+    if ((rc = wide_plan(c, 0, 0)))
         return rc;
     c->w_nseg[1] = 0;
     c->wseg_cur_len = 0;
-    c->spec_calibrated = c->spec_W_fixed && false;
-    c->wseg_given_up = false;
-    c->wide_careful = false;
+    c->ds.spec_calibrated = false; // (this family calibrates even a fixed warm-up)
     c->tile_reason = 0;
     // buffers for the finest plan there can be
-    const int64_t minlen = c->wseg_len > 0 ? (int64_t)c->wseg_len : fill_len(c);
+    const int64_t minlen = c->opt.wseg_len > 0 ? (int64_t)c->opt.wseg_len : fill_len(c);
     int64_t nsmax = c->K;
     for (int k = 0; k < c->K; ++k)
         nsmax += (c->offsets[k + 1] - c->offsets[k]) / std::max<int64_t>(minlen & ~(int64_t)3, 4) + 1;
@@ -214,17 +208,17 @@ int tile_gen_alloc(bhmm_ctx *c)
 int tile_gen_estep(bhmm_ctx *c, const WideModel &m, double *stats_dev, int flags, bool *done)
 {
     *done = false;
-    c->tile_used = false;
-    if (!tile_gen_capable(c) || c->wseg_given_up || c->wide_careful || !c->wseg_enabled)
+    c->last.tile_used = false;
+    if (!tile_gen_capable(c) || c->ds.wseg_given_up || c->ds.wide_careful || !c->opt.wseg_enabled)
         return BHMM_OK;
     int rc;
-    if (!c->spec_calibrated) {
-        c->spec_calibrated = true;
+    if (!c->ds.spec_calibrated) {
+        c->ds.spec_calibrated = true;
         bool usable = false;
         if ((rc = calibrate(c, m, &usable)))
             return rc;
         if (!usable) {
-            c->wseg_given_up = true;
+            c->ds.wseg_given_up = true;
             return BHMM_OK;
         }
     }
@@ -248,62 +242,62 @@ int tile_gen_estep(bhmm_ctx *c, const WideModel &m, double *stats_dev, int flags
             return rc;
         if ((rc = read_flags(c)))
             return rc;
-        c->wide_trouble = c->h_specres[2];
+        c->last.wide_trouble = c->h_specres[2];
         if (c->h_specres[2]) {
             // A self-check fired: the kernels are deterministic, so these data leave the lazily scaled
             // kernels' range every time (a run that was merely repeated would hide an uninitialised read --
             // round 4's LDS over-read was found because such a flag did NOT repeat).  Nothing of a flagged
             // run is used; the context moves to the order-faithful family for these observations.
-            c->wide_careful = true; // out of the lazily scaled kernels' range on these data: stay away
+            c->ds.wide_careful = true; // out of the lazily scaled kernels' range on these data: stay away
             c->tile_reason = 4;
             return BHMM_OK;
         }
         float devf;
         memcpy(&devf, &c->h_specres[1], sizeof(float));
-        c->spec_last_dev = devf;
+        c->last.spec_last_dev = devf;
         if (!segmented || c->h_specres[0] == 0) {
-            c->spec_ok++;
+            c->last.spec_ok++;
             c->ev_pending = true;
-            c->tile_used = true;
+            c->last.tile_used = true;
             *done = true;
             // (first E-step on these observations: more than two decades inside the tolerance -> 10 %
             // shorter and once more, at most four times; wide_api.hip)
-            if (segmented && !c->spec_W_fixed && c->tile_settle < 4 && devf > 0.f && devf < 1e-13f) {
+            if (segmented && !c->opt.spec_W_fixed && c->ds.tile_settle < 4 && devf > 0.f && devf < 1e-13f) {
                 const double f = std::max(log(3e-13) / log((double)devf), 0.9);
-                const int Wn = std::max(16, ((int)ceil(c->spec_W * f) + 7) / 8 * 8);
-                if (Wn < c->spec_W) {
-                    ++c->tile_settle;
-                    c->tile_W_good = c->spec_W;
-                    c->spec_W = Wn;
+                const int Wn = std::max(16, ((int)ceil(c->ds.spec_W * f) + 7) / 8 * 8);
+                if (Wn < c->ds.spec_W) {
+                    ++c->ds.tile_settle;
+                    c->ds.tile_W_good = c->ds.spec_W;
+                    c->ds.spec_W = Wn;
                     *done = false;
                     attempt = -1; // (not an attempt after a failure)
                     continue;
                 }
             }
-            c->tile_settle = 4;
+            c->ds.tile_settle = 4;
             return BHMM_OK;
         }
-        if (c->tile_W_good > c->spec_W && c->tile_settle > 0 && c->tile_settle <= 4) {
-            c->spec_W = c->tile_W_good; // a refinement too far: back to the warm-up that verified, for good
-            c->tile_W_good = 0;
-            c->tile_settle = 5;
+        if (c->ds.tile_W_good > c->ds.spec_W && c->ds.tile_settle > 0 && c->ds.tile_settle <= 4) {
+            c->ds.spec_W = c->ds.tile_W_good; // a refinement too far: back to the warm-up that verified, for good
+            c->ds.tile_W_good = 0;
+            c->ds.tile_settle = 5;
             attempt = -1;
             continue;
         }
-        c->spec_fail++;
+        c->last.spec_fail++;
         // the model has moved to slower forgetting: extrapolate (geometric decay) and try again
-        if (c->spec_W_fixed)
+        if (c->opt.spec_W_fixed)
             break;
         const double d = std::min(std::max((double)devf, 1e-300), 0.5);
         const double f = std::min(std::max(log(1e-13) / log(d), 1.25), 4.0);
-        const int Wn = ((int)ceil(c->spec_W * f) + 7) / 8 * 8;
+        const int Wn = ((int)ceil(c->ds.spec_W * f) + 7) / 8 * 8;
         if (Wn >= max_len(c) / 2)
             break;
-        c->spec_W = Wn;
+        c->ds.spec_W = Wn;
         if ((rc = plan_for(c, Wn)))
             return rc;
     }
-    c->wseg_given_up = true;
+    c->ds.wseg_given_up = true;
     c->tile_reason = 5;
     return BHMM_OK;
 }
@@ -313,16 +307,16 @@ int tile_gen_estep(bhmm_ctx *c, const WideModel &m, double *stats_dev, int flags
 int tile_gen_forward_draw(bhmm_ctx *c, const WideModel &m, bool *done)
 {
     *done = false;
-    if (!tile_gen_capable(c) || c->wseg_given_up || c->wide_careful || !c->wseg_enabled || !c->spec_enabled)
+    if (!tile_gen_capable(c) || c->ds.wseg_given_up || c->ds.wide_careful || !c->opt.wseg_enabled || !c->opt.spec_enabled)
         return BHMM_OK;
     int rc;
-    if (!c->spec_calibrated) {
-        c->spec_calibrated = true;
+    if (!c->ds.spec_calibrated) {
+        c->ds.spec_calibrated = true;
         bool usable = false;
         if ((rc = calibrate(c, m, &usable)))
             return rc;
         if (!usable) {
-            c->wseg_given_up = true;
+            c->ds.wseg_given_up = true;
             return BHMM_OK;
         }
     }
@@ -338,7 +332,7 @@ int tile_gen_forward_draw(bhmm_ctx *c, const WideModel &m, bool *done)
     float dev = 0.f; // (largest boundary deviation the check saw: what the draws' watch is sized by)
     if (segmented)
         memcpy(&dev, &c->h_specres[1], sizeof(float));
-    c->draw_alpha_dev = *done ? dev : 0.0;
+    c->last.draw_alpha_dev = *done ? dev : 0.0;
     return BHMM_OK;
 }
 

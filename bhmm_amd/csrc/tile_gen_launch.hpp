@@ -10,12 +10,11 @@
 #include <algorithm>
 
 #include "host_common.hpp"
+#include "host_internal.hpp"
 #include "plan.hpp"
 #include "wide_kernels.hpp"
 
 namespace bhmm {
-Segs wide_segs_pub(bhmm_ctx *c, int which);
-
 template <int NT, int KIND>
 int tile_gen_launch_fwd(bhmm_ctx *c, const WideModel &m);
 template <int NT, int KIND>

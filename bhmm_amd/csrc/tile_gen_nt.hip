@@ -12,7 +12,7 @@ template <int NT, int KIND>
 int tile_gen_launch_fwd(bhmm_ctx *c, const WideModel &m)
 {
     lds_poison(c->stream);
-    const Segs sg = wide_segs_pub(c, 1);
+    const Segs sg = segs_of(c, 1);
     const TilePlan tp{c->d_tile_seg[1].p, c->w_ntiles[1]};
     // up to 96 states the forward kernel fits the eight-wavefront form (matrix + stream wavefronts, 225
     // registers); the backward kernel does not (it would spill 440 registers), nor does either at 128
@@ -54,7 +54,7 @@ template <int NT, int KIND>
 int tile_gen_launch_bwd(bhmm_ctx *c, const WideModel &m, double *gam, double *stats_dev)
 {
     lds_poison(c->stream);
-    const Segs sg = wide_segs_pub(c, 1);
+    const Segs sg = segs_of(c, 1);
     const TilePlan tp{c->d_tile_segb[1].p, c->w_ntilesb[1]};
     const int n = c->n;
     // time slabs of the xi GEMM: one workgroup of NT wavefronts each; four per compute unit hide the loads

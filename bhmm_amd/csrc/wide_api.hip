@@ -9,18 +9,18 @@
 #include <vector>
 
 #include "host_common.hpp"
+#include "host_internal.hpp"
 #include "plan.hpp"
 #include "wide_kernels.hpp"
 #include "tile_kernels.hpp"
 
 namespace bhmm {
-int invalid_arg(const std::string &msg);
 
 static int wide_np(int n) { return n <= 16 ? 16 : (n <= 32 ? 32 : 64); }
 
 // upload the model into ctx->d_wmodel and describe it
-static int wide_model(bhmm_ctx *c, int kind, const double *A, const double *pi, const double *par0,
-                      const double *par1, WideModel &m)
+int wide_model(bhmm_ctx *c, int kind, const double *A, const double *pi, const double *par0, const double *par1,
+               WideModel &m)
 {
     const int n = c->n;
     std::vector<double> h((size_t)n * n + 7 * n, 0.0);
@@ -65,7 +65,7 @@ static int wide_model(bhmm_ctx *c, int kind, const double *A, const double *pi, 
     return BHMM_OK;
 }
 
-static Segs segs_of(bhmm_ctx *c, int which)
+Segs segs_of(bhmm_ctx *c, int which)
 {
     Segs sg;
     sg.traj = c->d_wseg_traj[which].p;
@@ -74,7 +74,7 @@ static Segs segs_of(bhmm_ctx *c, int which)
     sg.nseg = c->w_nseg[which];
     // (segment starts and the warm-up are multiples of four: the lazily scaled passes then rescale on
     // the steps t % 4 == 3 whatever plan each of them runs on)
-    sg.W = (c->spec_W + 3) & ~3;
+    sg.W = (c->ds.spec_W + 3) & ~3;
     sg.fmid = (which == 1 && c->w_nseg[2] > c->w_nseg[1]) ? c->d_wseg_fmid.p : nullptr;
     return sg;
 }
@@ -90,7 +90,7 @@ static int wide_fwd_plan(const bhmm_ctx *c, int which)
 // 65..128
 static bool wide_tile(const bhmm_ctx *c)
 {
-    return c->tile_latched && ((c->n > 32 && c->n <= 64 && !c->gen) || (c->gen && c->n <= 512));
+    return c->ds.tile_latched && ((c->n > 32 && c->n <= 64 && !c->gen) || (c->gen && c->n <= 512));
 }
 
 template <int KIND>
@@ -307,7 +307,7 @@ static int64_t wide_fill_len(const bhmm_ctx *c)
 {
     const int64_t groups_per_wave = 64 / c->N;
     if (wide_tile(c)) { // 16 segments per workgroup, tile_per_cu workgroups per compute unit
-        const int64_t want = 16 * (int64_t)(c->num_simd / 4) * c->tile_per_cu;
+        const int64_t want = 16 * (int64_t)(c->num_simd / 4) * c->opt.tile_per_cu;
         return ((c->total + want - 1) / want + 3) & ~(int64_t)3;
     }
     const int64_t want = (c->N == 64) ? (int64_t)c->num_simd : 4 * (int64_t)c->num_simd * groups_per_wave;
@@ -315,7 +315,7 @@ static int64_t wide_fill_len(const bhmm_ctx *c)
 }
 
 // segment plan `which` with segments of at most seglen steps (seglen <= 0: one per trajectory)
-static int wide_plan(bhmm_ctx *c, int which, int64_t seglen, int mult = 1)
+int wide_plan(bhmm_ctx *c, int which, int64_t seglen, int mult)
 {
     plan::SegPlan sp; // (plan.hpp: pure host code, also built under the CPU sanitizers)
     plan::plan_segments(c->offsets, c->K, seglen, mult, sp);
@@ -363,7 +363,7 @@ static int wide_plan_segments(bhmm_ctx *c, int64_t seglen)
         return rc;
     c->w_nseg[2] = 0;
     // (every segment of plan 1 cut in two: the segment count stays a multiple of the SIMD count)
-    if (c->N == 64 && !wide_tile(c) && c->wseg_split && seglen / 2 >= 4 * (int64_t)c->spec_W && seglen >= 128) {
+    if (c->N == 64 && !wide_tile(c) && c->opt.wseg_split && seglen / 2 >= 4 * (int64_t)c->ds.spec_W && seglen >= 128) {
         if ((rc = wide_plan(c, 2, seglen, 2)))
             return rc;
         // for every segment of plan 1: the start of a plan-2 segment strictly inside it (-1: none)
@@ -378,15 +378,6 @@ static int wide_plan_segments(bhmm_ctx *c, int64_t seglen)
     return rc;
 }
 
-int wide_plan_pub(bhmm_ctx *c, int which, int64_t seglen) { return wide_plan(c, which, seglen); }
-Segs wide_segs_pub(bhmm_ctx *c, int which) { return segs_of(c, which); }
-
-int wide_model_pub(bhmm_ctx *c, int kind, const double *A, const double *pi, const double *par0,
-                   const double *par1, WideModel &m)
-{
-    return wide_model(c, kind, A, pi, par0, par1, m);
-}
-
 int wide_alloc(bhmm_ctx *c)
 {
     const int n = c->n;
@@ -398,14 +389,14 @@ int wide_alloc(bhmm_ctx *c)
     // time-segmented plan: ~4 lane groups per SIMD, but segments long against the warm-up
     c->w_nseg[1] = 0;
     {
-        int64_t seglen = c->wseg_len;
+        int64_t seglen = c->opt.wseg_len;
         if (seglen <= 0)
-            seglen = std::max<int64_t>(wide_fill_len(c), (wide_tile(c) ? 2 : 8) * (int64_t)c->spec_W);
+            seglen = std::max<int64_t>(wide_fill_len(c), (wide_tile(c) ? 2 : 8) * (int64_t)c->ds.spec_W);
         int64_t maxT = 0;
         for (int k = 0; k < c->K; ++k)
             maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
         c->wseg_cur_len = seglen;
-        if (c->wseg_enabled && maxT > seglen && (rc = wide_plan_segments(c, seglen)))
+        if (c->opt.wseg_enabled && maxT > seglen && (rc = wide_plan_segments(c, seglen)))
             return rc;
     }
     // (buffers sized for the finest plan there can be: plan 2 has at most twice the segments of plan 1)
@@ -495,7 +486,7 @@ static int wide_probe_run(bhmm_ctx *c, const WideModel &m, int *W_out)
 static int wide_calibrate(bhmm_ctx *c, const WideModel &m)
 {
     int rc = BHMM_OK;
-    c->spec_calibrated = true;
+    c->ds.spec_calibrated = true;
     int W = 0;
     switch (c->kind) {
     case EMIT_GAUSS:
@@ -509,25 +500,25 @@ static int wide_calibrate(bhmm_ctx *c, const WideModel &m)
     }
     if (rc)
         return rc;
-    const int W_planned = c->spec_W;
+    const int W_planned = c->ds.spec_W;
     if (W > 0)
-        c->spec_W = W;
+        c->ds.spec_W = W;
     if (W > W_planned) { // longer warm-ups than the plan assumed: longer segments
         int64_t maxT = 0;
         for (int k = 0; k < c->K; ++k)
             maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
-        int64_t seglen = c->wseg_len;
+        int64_t seglen = c->opt.wseg_len;
         if (seglen <= 0)
             seglen = std::max<int64_t>(wide_fill_len(c), (wide_tile(c) ? 2 : 4) * (int64_t)W);
         seglen = std::max(seglen, c->wseg_cur_len); // never more segments than allocated for
         if (seglen >= maxT) {
-            c->wseg_given_up = true;
+            c->ds.wseg_given_up = true;
         } else if (seglen > c->wseg_cur_len) {
             c->wseg_cur_len = seglen;
             if ((rc = wide_plan_segments(c, seglen)))
                 return rc;
             if (c->w_nseg[1] <= c->w_nseg[0])
-                c->wseg_given_up = true;
+                c->ds.wseg_given_up = true;
         }
     }
     return BHMM_OK;
@@ -561,11 +552,11 @@ int wide_forward_draw(bhmm_ctx *c, const double *A, const double *pi, const doub
     int rc = wide_model(c, c->kind, A, pi, par0, par1, m);
     if (rc)
         return rc;
-    if (c->spec_enabled && c->wseg_enabled) {
-        if (!c->spec_calibrated && c->w_nseg[1] > c->w_nseg[0] && (rc = wide_calibrate(c, m)))
+    if (c->opt.spec_enabled && c->opt.wseg_enabled) {
+        if (!c->ds.spec_calibrated && c->w_nseg[1] > c->w_nseg[0] && (rc = wide_calibrate(c, m)))
             return rc;
-        if (!c->wseg_given_up && c->w_nseg[1] > c->w_nseg[0]) {
-            const bool lazy = !c->careful && !c->wide_careful;
+        if (!c->ds.wseg_given_up && c->w_nseg[1] > c->w_nseg[0]) {
+            const bool lazy = !c->ds.careful && !c->ds.wide_careful;
             BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 3 * sizeof(unsigned int), c->stream));
             switch (c->kind) {
             case EMIT_GAUSS:
@@ -587,17 +578,17 @@ int wide_forward_draw(bhmm_ctx *c, const double *A, const double *pi, const doub
             BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 3 * sizeof(unsigned int),
                                     hipMemcpyDeviceToHost, c->stream));
             BHMM_HIP(hipStreamSynchronize(c->stream));
-            c->draw_fwd_segmented = c->h_specres[0] == 0 && (!lazy || c->h_specres[2] == 0);
-            if (c->draw_fwd_segmented) {
+            c->last.draw_fwd_segmented = c->h_specres[0] == 0 && (!lazy || c->h_specres[2] == 0);
+            if (c->last.draw_fwd_segmented) {
                 float dev; // (largest boundary deviation the check saw: what the draws' watch is sized by)
                 memcpy(&dev, &c->h_specres[1], sizeof(float));
-                c->draw_alpha_dev = dev;
+                c->last.draw_alpha_dev = dev;
                 return BHMM_OK;
             }
         }
     }
-    c->draw_fwd_segmented = false;
-    c->draw_alpha_dev = 0.0;
+    c->last.draw_fwd_segmented = false;
+    c->last.draw_alpha_dev = 0.0;
     return wide_forward(c, A, pi, par0, par1);
 }
 
@@ -613,7 +604,7 @@ int wide_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par
         return rc;
     auto run = [&](int which, bool lazy) -> int {
         int r;
-        c->tile_used = lazy && wide_tile(c);
+        c->last.tile_used = lazy && wide_tile(c);
         // event intervals of this family: [0] forward pass, [2] backward pass + statistics
         BHMM_HIP(hipEventRecord(c->ev[0], c->stream));
 #define BHMM_WIDE_PASSES(KINDV)                                                                  \
@@ -641,12 +632,12 @@ int wide_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par
         BHMM_HIP(hipEventRecord(c->ev[4], c->stream));
         return BHMM_OK;
     };
-    if (c->wseg_enabled && !c->spec_calibrated && c->w_nseg[1] > c->w_nseg[0] && (rc = wide_calibrate(c, m)))
+    if (c->opt.wseg_enabled && !c->ds.spec_calibrated && c->w_nseg[1] > c->w_nseg[0] && (rc = wide_calibrate(c, m)))
         return rc;
-    if (c->wseg_enabled && !c->wseg_given_up && c->w_nseg[1] > c->w_nseg[0]) {
+    if (c->opt.wseg_enabled && !c->ds.wseg_given_up && c->w_nseg[1] > c->w_nseg[0]) {
         // time-segmented run with warm-up boundaries, verified afterwards
         // lazily scaled kernels unless an earlier E-step on these data left their range
-        const bool lazy = !c->careful && !c->wide_careful;
+        const bool lazy = !c->ds.careful && !c->ds.wide_careful;
         BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 3 * sizeof(unsigned int), c->stream));
         if ((rc = run(1, lazy)))
             return rc;
@@ -673,50 +664,50 @@ int wide_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par
         }
         BHMM_HIP(hipStreamSynchronize(c->stream));
         if (lazy)
-            c->wide_trouble = c->h_specres[2];
+            c->last.wide_trouble = c->h_specres[2];
         if (lazy && c->h_specres[2] != 0) {
             // a vector left the range the lazy scaling covers: per-step normalisation from now on
-            c->wide_careful = true;
-            c->careful_retry = true;
+            c->ds.wide_careful = true;
+            c->ds.careful_retry = true;
             return wide_estep(c, A, pi, par0, par1, stats_dev, flags);
         }
         float dev;
         memcpy(&dev, &c->h_specres[1], sizeof(float));
-        c->spec_last_dev = dev;
+        c->last.spec_last_dev = dev;
         if (c->h_specres[0] == 0) {
-            c->spec_ok++;
+            c->last.spec_ok++;
             c->ev_pending = true;
             // The probe's warm-up carries a margin for the boundaries it did not sample; what the check
             // found at EVERY boundary says how much of it this model needs.  First E-step on these
             // observations only (so that repeated calls stay bit-identical): more than two decades
             // inside the tolerance -> 10 % shorter and once more, at most four times, aiming 30 times
             // inside the 1e-11 of the check.
-            if (wide_tile(c) && lazy && !c->spec_W_fixed && c->tile_settle < 4 && dev > 0.f && dev < 1e-13f) {
+            if (wide_tile(c) && lazy && !c->opt.spec_W_fixed && c->ds.tile_settle < 4 && dev > 0.f && dev < 1e-13f) {
                 const double f = std::max(log(3e-13) / log((double)dev), 0.9);
-                const int Wn = ((int)ceil(c->spec_W * f) + 7) / 8 * 8;
-                if (Wn < c->spec_W) {
-                    ++c->tile_settle;
-                    c->tile_W_good = c->spec_W;
-                    c->spec_W = Wn;
+                const int Wn = ((int)ceil(c->ds.spec_W * f) + 7) / 8 * 8;
+                if (Wn < c->ds.spec_W) {
+                    ++c->ds.tile_settle;
+                    c->ds.tile_W_good = c->ds.spec_W;
+                    c->ds.spec_W = Wn;
                     return wide_estep(c, A, pi, par0, par1, stats_dev, flags);
                 }
             }
-            c->tile_settle = 4;
+            c->ds.tile_settle = 4;
             // An EM sequence moves the model, and with it the length the filter needs to forget its start
             // (configs[3]: the worst boundary went 5e-14 -> 1.3e-11 over 14 iterations at a fixed warm-up,
             // profiles/r05).  A check that fails costs this call a second pass, so the warm-up FOLLOWS the
             // measured deviation whenever the model has changed since the previous call: it aims at 3e-13
             // (1.5 decades inside the tolerance), one decade being spec_W / 12.5 steps.  Calls that repeat a
             // model never change it (bit-identical results, as before).
-            if (wide_tile(c) && lazy && !c->spec_W_fixed && c->carry_delta > 0.0 && dev > 0.f) {
+            if (wide_tile(c) && lazy && !c->opt.spec_W_fixed && c->carry_delta > 0.0 && dev > 0.f) {
                 const double dec = log10((double)dev / 3e-13);
-                int Wn = c->spec_W;
+                int Wn = c->ds.spec_W;
                 if (dev > 2e-12f)
-                    Wn = ((int)ceil(c->spec_W * (1.0 + dec / 12.5)) + 7) / 8 * 8;
+                    Wn = ((int)ceil(c->ds.spec_W * (1.0 + dec / 12.5)) + 7) / 8 * 8;
                 else if (dev < 2e-14f)
-                    Wn = std::max(16, ((int)ceil(c->spec_W * (1.0 + 0.5 * dec / 12.5)) + 7) / 8 * 8);
+                    Wn = std::max(16, ((int)ceil(c->ds.spec_W * (1.0 + 0.5 * dec / 12.5)) + 7) / 8 * 8);
                 if ((int64_t)Wn <= c->wseg_cur_len) // (a warm-up may be as long as a segment; beyond: re-plan below)
-                    c->spec_W = Wn;
+                    c->ds.spec_W = Wn;
             }
             if (pre) {
                 c->prefetched = true;
@@ -724,24 +715,24 @@ int wide_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par
             }
             return BHMM_OK;
         }
-        if (c->tile_W_good > c->spec_W && c->tile_settle > 0 && c->tile_settle <= 4) {
+        if (c->ds.tile_W_good > c->ds.spec_W && c->ds.tile_settle > 0 && c->ds.tile_settle <= 4) {
             // a refinement too far: back to the warm-up that verified, for good
-            c->spec_W = c->tile_W_good;
-            c->tile_W_good = 0;
-            c->tile_settle = 5;
+            c->ds.spec_W = c->ds.tile_W_good;
+            c->ds.tile_W_good = 0;
+            c->ds.tile_settle = 5;
             return wide_estep(c, A, pi, par0, par1, stats_dev, flags);
         }
-        c->spec_fail++;
-        if (wide_tile(c) && lazy && !c->spec_W_fixed && c->wide_retry < 2) {
+        c->last.spec_fail++;
+        if (wide_tile(c) && lazy && !c->opt.spec_W_fixed && c->wide_retry < 2) {
             // the tile kernels once more with the warm-up the measured deviation asks for (it decays
             // geometrically with the warm-up length), as long as it is no longer than a segment: 10 ms
             // instead of the 300 ms of the serial plan below
             const double d = std::min(std::max((double)dev, 1e-300), 0.5);
             const double f = std::min(std::max(log(3e-13) / log(d), 1.08), 2.0);
-            const int Wn = ((int)ceil(c->spec_W * f) + 7) / 8 * 8;
+            const int Wn = ((int)ceil(c->ds.spec_W * f) + 7) / 8 * 8;
             if ((int64_t)Wn <= c->wseg_cur_len) {
                 ++c->wide_retry;
-                c->spec_W = Wn;
+                c->ds.spec_W = Wn;
                 return wide_estep(c, A, pi, par0, par1, stats_dev, flags);
             }
         }
@@ -755,23 +746,23 @@ int wide_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par
         const double d = std::min(std::max((double)dev, 1e-300), 0.5);
         double f = log(1e-12) / log(d);
         f = std::min(std::max(f, 1.25), 8.0);
-        const int64_t Wn = ((int64_t)ceil(c->spec_W * f) + 7) / 8 * 8;
-        int64_t seglen = c->wseg_len > 0 ? (int64_t)c->wseg_len : (wide_tile(c) ? 2 : 4) * Wn;
-        if (c->wseg_len <= 0)
+        const int64_t Wn = ((int64_t)ceil(c->ds.spec_W * f) + 7) / 8 * 8;
+        int64_t seglen = c->opt.wseg_len > 0 ? (int64_t)c->opt.wseg_len : (wide_tile(c) ? 2 : 4) * Wn;
+        if (c->opt.wseg_len <= 0)
             seglen = std::max(seglen, wide_fill_len(c));
         seglen = std::max(seglen, c->wseg_cur_len); // never more segments than allocated for
-        if (c->wide_replans >= 3 || seglen >= maxT || Wn >= maxT / 2) {
-            c->wseg_given_up = true;
+        if (c->ds.wide_replans >= 3 || seglen >= maxT || Wn >= maxT / 2) {
+            c->ds.wseg_given_up = true;
         } else {
-            ++c->wide_replans;
-            c->spec_W = (int)Wn;
+            ++c->ds.wide_replans;
+            c->ds.spec_W = (int)Wn;
             if (seglen > c->wseg_cur_len) {
                 c->wseg_cur_len = seglen;
                 if ((rc = wide_plan_segments(c, seglen)))
                     return rc;
             }
             if (c->w_nseg[1] <= c->w_nseg[0])
-                c->wseg_given_up = true;
+                c->ds.wseg_given_up = true;
         }
     }
     if ((rc = run(0, false)))
