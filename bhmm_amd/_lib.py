@@ -28,6 +28,7 @@ EMIT_DISCRETE = 1
 EMIT_EXPLICIT = 2
 
 FLAG_STORE_GAMMA = 1
+FLAG_SINGLE = 2        # the caller accepts a single-precision E-step (up to 8 states; else fp64)
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)

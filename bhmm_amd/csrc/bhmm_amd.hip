@@ -375,8 +375,10 @@ struct Runner {
     // after which two differently started chains agree to 1e-13 on every sampled stretch, in
     // both directions, plus 15 %.  The boundary check of every E-step remains the judge.
     template <int KIND>
-    static int probe_warmup(bhmm_ctx *c, const Model<N> &m, int *W_out)
+    static int probe_warmup(bhmm_ctx *c, const Model<N> &m, int *W_out, double target = 0.0)
     {
+        if (!(target > 0.0))
+            target = 0.01 * c->opt.spec_tol; // (default: 1e-13)
         *W_out = 0;
         int64_t maxT = 0;
         for (int k = 0; k < c->K; ++k)
@@ -415,7 +417,7 @@ struct Runner {
         BHMM_HIP(hipStreamSynchronize(c->stream)); // starts / curve are temporaries
         int last = -1;
         for (int w = 0; w < Wmax; ++w)
-            if (std::max(curve[w], curve[Wmax + w]) >= (float)(0.01 * c->opt.spec_tol)) // (default: 1e-13)
+            if (std::max(curve[w], curve[Wmax + w]) >= (float)target)
                 last = w;
         int W = last + 2; // steps needed to get below the target and stay there
         W = (int)std::ceil(1.15 * W);
@@ -555,6 +557,20 @@ struct Runner {
         BHMM_HIP(hipEventRecord(c->ev[4], c->stream));
         c->ev_pending = true;
         return BHMM_OK;
+    }
+
+    // probe_warmup at another target (the fp32 E-step, estep_f32.hip)
+    static int probe_at(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                        double target, int *W)
+    {
+        Model<N> m;
+        fill_model<N>(m, c->n, c->kind, c->M, A, pi, par0, par1);
+        if (c->kind == EMIT_DISC) {
+            m.dcopies = disc_copies<N>(c->M);
+            m.bt_global = c->bt_global ? 1 : 0;
+            return probe_warmup<EMIT_DISC>(c, m, W, target);
+        }
+        return probe_warmup<EMIT_GAUSS>(c, m, W, target);
     }
 
     static int estep(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
@@ -981,6 +997,12 @@ int forward_ci_verdict(bhmm_ctx *c, bool *ok)
 int unpack_ws_rows(bhmm_ctx *c, double *dst_dev)
 {
     return BHMM_DISPATCH_N(c, unpack_rows(c, c->d_ws.p, dst_dev, -1, 0));
+}
+
+int probe_warmup_target(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                        double target, int *W)
+{
+    return BHMM_DISPATCH_N(c, probe_at(c, A, pi, par0, par1, target, W));
 }
 
 static void collect_timing(bhmm_ctx *c)
@@ -1548,6 +1570,15 @@ int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
         c->opt.vit_seg_per_simd = (int)value;
         c->ds.pplan[0].nseg = 0;
         c->ds.vit_seg_given_up = false;
+    } else if (n == "f32_tol") { // BHMM_FLAG_SINGLE: relative tolerance of the fp32 boundary check
+        if (!(value >= 1e-7 && value <= 1e-3))
+            return invalid_arg("f32_tol outside [1e-7, 1e-3]");
+        c->opt.f32_tol = value;
+        c->ds.f32_W = 0; // (the next fp32 E-step measures the warm-up for it)
+    } else if (n == "f32_W") { // BHMM_FLAG_SINGLE: fixed fp32 warm-up length (0: measured)
+        if (!(value >= 0 && value <= (1 << 20)))
+            return invalid_arg("f32_W outside [0, 2^20]");
+        c->opt.f32_W = (int)value;
     } else if (n == "spec_W") {
         c->ds.carry_valid = false;
         c->ds.spec_W = std::max(1, (int)value);
@@ -1594,6 +1625,16 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->last.spec_fail;
     else if (n == "spec_last_dev")
         *value = c->last.spec_last_dev;
+    else if (n == "f32_used")
+        *value = c->last.f32_used ? 1.0 : 0.0;
+    else if (n == "f32_fallbacks")
+        *value = c->last.f32_fallbacks;
+    else if (n == "f32_tol")
+        *value = c->opt.f32_tol;
+    else if (n == "f32_W")
+        *value = c->opt.f32_W > 0 ? c->opt.f32_W : c->ds.f32_W;
+    else if (n == "f32_last_dev")
+        *value = c->last.f32_last_dev;
     else if (n == "careful")
         *value = (c->ds.careful || c->ds.wide_careful) ? 1.0 : 0.0;
     else if (n == "viterbi_chunked")
@@ -1829,7 +1870,18 @@ int bhmm_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par
     c->last_stats = sd;
     c->prefetched = false;
     c->ev_lean = false;
-    if (c->gen)
+    // BHMM_FLAG_SINGLE: the fp32 kernels where they apply and verify (estep_f32.hip), else this fp64 path
+    bool single_done = false;
+    c->last.f32_used = false;
+    if ((flags & BHMM_FLAG_SINGLE) && (rc = estep_f32(c, A, pi, par0, par1, sd, flags, &single_done)))
+        return rc;
+    if (flags & BHMM_FLAG_SINGLE) {
+        c->last.f32_used = single_done;
+        c->last.f32_fallbacks += single_done ? 0 : 1;
+    }
+    if (single_done)
+        rc = BHMM_OK;
+    else if (c->gen)
         rc = gen_estep(c, A, pi, par0, par1, sd, flags);
     else if (c->wide)
         rc = wide_estep(c, A, pi, par0, par1, sd, flags);

@@ -98,6 +98,8 @@ struct bhmm_ctx {
         bool wseg_enabled = true;
         bool wseg_split = true;          // 64 states: own, finer plan for the forward pass (wide_plan_segments)
         int wseg_len = 0;                // 0 = automatic
+        double f32_tol = 1e-5;           // BHMM_FLAG_SINGLE: tolerance of the fp32 boundary check (option f32_tol)
+        int f32_W = 0;                   // ... fp32 warm-up fixed by the caller (option f32_W; 0: measured)
     } opt;
 
     // ---- loaded problem ----
@@ -160,6 +162,8 @@ struct bhmm_ctx {
         bool tile_latched = true;        // opt.tile_enabled latched: plans, buffers and launches of one data set all use THIS
         int tile_settle = 0;             // warm-up refinements done for these observations (at most 4, first E-step)
         int tile_W_good = 0;             // ... the last warm-up that verified
+        int f32_W = 0;                   // fp32 E-step (estep_f32.hip): warm-up read off the forgetting curve at
+                                         // 0.01 f32_tol (0: not measured yet), doubled after a failed check
     } ds;
 
     // ---- counters and diagnostics of the last calls (bhmm_ctx_get_option) ----
@@ -184,6 +188,9 @@ struct bhmm_ctx {
         unsigned int wide_trouble = 0;   // flag word of the last lazily scaled E-step (which self-check fired)
         bool tile_used = false;          // the last E-step ran on the tile kernels
         double ms[5] = {0, 0, 0, 0, 0};
+        bool f32_used = false;           // the last E-step ran in fp32 end to end (BHMM_FLAG_SINGLE)
+        int f32_fallbacks = 0;           // E-steps that asked for fp32 and ran the fp64 path
+        float f32_last_dev = 0.f;        // largest relative boundary deviation of the last fp32 check
     } last;
 
     // ---- not reset by bhmm_ctx_set_observations: they outlive the observation set ----
@@ -274,6 +281,9 @@ struct bhmm_ctx {
     bhmm::DevBuf<int32_t> d_tile_segb[3]; // ... backward pass (tiles are formed per direction, plan.hpp)
     bhmm::DevBuf<int32_t> d_wexp;    // [total] exponent the forward pass removed at every step
     bhmm::DevBuf<int32_t> d_wePseg;  // [segments] ... summed over the main part of every segment
+    // fp32 E-step (estep_f32.hip): boundary vectors [4][Gp][N], B^T in fp32, verdict words
+    bhmm::DevBuf<float> d_f32vec, d_Bt32;
+    bhmm::DevBuf<unsigned int> d_f32words;
 
     // ---- pinned host buffers ----
     unsigned int *h_specres = nullptr; // pinned

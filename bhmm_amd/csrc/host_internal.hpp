@@ -20,11 +20,19 @@ Chunks chunks_of(const bhmm_ctx *c);
 int forward_ci(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1);
 int forward_ci_verdict(bhmm_ctx *c, bool *ok);
 int unpack_ws_rows(bhmm_ctx *c, double *dst_dev);
+// warm-up length read off the measured forgetting curve (k_forget_probe) at `target` (0: none measured)
+int probe_warmup_target(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                        double target, int *W);
 // The checks every model entry point (bhmm_estep, bhmm_viterbi_batch[_u8], bhmm_sample_paths[_dev]) starts with:
 // observations loaded; `given` (its pointer arguments are there, else null_msg); with `emissions`, the
 // parameters the emission kind needs.  Then the context's device is made current.
 int enter_model_call(bhmm_ctx *c, bool given, const char *null_msg, bool emissions, const double *par0,
                      const double *par1);
+
+// ---- estep_f32.hip (BHMM_FLAG_SINGLE, up to 8 states) ----
+// *done: the E-step ran in fp32 and verified; false: the caller runs the fp64 path (nothing else changed)
+int estep_f32(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+              double *stats_dev, int flags, bool *done);
 
 // ---- wide_api.hip (9..64 states) ----
 int wide_alloc(bhmm_ctx *c);

@@ -215,11 +215,13 @@ class Engine(object):
             out.append(ent[1])
         return out
 
-    def estep_launch(self, A, pi, par0=None, par1=None, stats_dev=None, store_gamma=False):
+    def estep_launch(self, A, pi, par0=None, par1=None, stats_dev=None, store_gamma=False, single=False):
         """Enqueue one E-step.  stats_dev: optional device address receiving the packed
-        statistics (e.g. a torch tensor that is all-reduced across ranks afterwards)."""
+        statistics (e.g. a torch tensor that is all-reduced across ranks afterwards).  single: the
+        caller accepts single-precision accuracy (BHMM_FLAG_SINGLE; get_option('f32_used') tells
+        whether the fp32 kernels ran or the call went to the fp64 path)."""
         A, pi, p0, p1 = self._model_ptrs(A, pi, par0, par1)
-        flags = _lib.FLAG_STORE_GAMMA if store_gamma else 0
+        flags = (_lib.FLAG_STORE_GAMMA if store_gamma else 0) | (_lib.FLAG_SINGLE if single else 0)
         _lib.check(self._L.bhmm_estep(self._h, A, pi, p0, p1,
                                       ctypes.c_void_p(int(stats_dev)) if stats_dev else None,
                                       flags))
@@ -249,8 +251,8 @@ class Engine(object):
         _lib.check(self._L.bhmm_estep_fetch(self._h, None, _lib.dp(logL_k)))
         return logL_k
 
-    def estep(self, A, pi, par0=None, par1=None, store_gamma=False):
-        self.estep_launch(A, pi, par0, par1, store_gamma=store_gamma)
+    def estep(self, A, pi, par0=None, par1=None, store_gamma=False, single=False):
+        self.estep_launch(A, pi, par0, par1, store_gamma=store_gamma, single=single)
         return self.estep_fetch()
 
     def unpack(self, packed, logL_k=None):

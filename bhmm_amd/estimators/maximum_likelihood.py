@@ -78,7 +78,16 @@ class MaximumLikelihoodEstimator(object):
     def __init__(self, observations, nstates, initial_model=None, output='gaussian',
                  reversible=True, stationary=False, p=None, accuracy=1e-3, maxit=1000,
                  maxit_P=100000, device=None, process_group=None, store_gamma=False,
-                 engine_factory=None, multi_start=False):
+                 engine_factory=None, multi_start=False, estep_precision='float64'):
+        # opt-in precision of the E-steps (the reference is fp64 throughout): 'float64' (default),
+        # 'float32' (every E-step may run the single-precision kernels) or 'mixed' (fp32 while the
+        # likelihood still climbs clearly, then fp64 to convergence; see fit()).  Not a speed option yet:
+        # the fp32 E-step is currently slower than the fp64 one
+        if estep_precision not in ('float64', 'float32', 'mixed'):
+            raise ValueError("estep_precision must be 'float64', 'float32' or 'mixed', not %r"
+                             % (estep_precision,))
+        self._estep_precision = estep_precision
+        self.estep_precisions = []   # per iteration what this rank's E-step ran (fp32 may fall back to fp64)
         # maximum_likelihood.py:101-104
         self._observations = copy.deepcopy(observations)
         self._nobs = len(observations)
@@ -218,20 +227,23 @@ class MaximumLikelihoodEstimator(object):
         return self._hmm.initial_distribution
 
     # ---- E-step --------------------------------------------------------------------------
-    def _estep(self):
+    def _estep(self, single=False):
         """All trajectories of this rank on the GPU, then the cross-rank reduction
-        (maximum_likelihood.py:221-282, 383-385).  Returns an EStepResult."""
+        (maximum_likelihood.py:221-282, 383-385).  Returns an EStepResult.  single: ask the engine
+        for a single-precision E-step (the keyword is passed only then, so engines without it keep
+        working); self._ran_single tells whether one ran."""
         om = self._hmm.output_model
         par0, par1 = om.parameters()
         eng, comm = self._engine, self._comm
         A, pi = self._hmm.transition_matrix, self._hmm.initial_distribution
+        kw = {'single': True} if single else {}
         if not comm.active and hasattr(eng, 'estep_fetch_packed'):
             # (the per-trajectory log-likelihoods stay on the device: the EM loop needs their sum,
             # which is packed[0]; with 1e6 short trajectories they would be 8 MB per iteration)
-            eng.estep_launch(A, pi, par0, par1, store_gamma=self._store_gamma)
+            eng.estep_launch(A, pi, par0, par1, store_gamma=self._store_gamma, **kw)
             res = EStepResult(self._output, self._nstates, self._nsymbols, eng.estep_fetch_packed(), None)
         elif not comm.active:
-            res = eng.estep(A, pi, par0, par1, store_gamma=self._store_gamma)
+            res = eng.estep(A, pi, par0, par1, store_gamma=self._store_gamma, **kw)
         elif hasattr(eng, 'estep_launch'):
             # the E-step leaves its packed statistics in a device buffer on the engine's GPU; ONE
             # in-place all-reduce (RCCL over xGMI) and ONE device-to-host copy follow -- the
@@ -242,7 +254,7 @@ class MaximumLikelihoodEstimator(object):
             failed = None
             if self._mine:
                 eng.estep_launch(A, pi, par0, par1, stats_dev=buf.data_ptr(),
-                                 store_gamma=self._store_gamma)
+                                 store_gamma=self._store_gamma, **kw)
                 try:
                     # waits for the E-step of this shard (and repairs what the library can repair,
                     # bhmm_estep_fetch: non-finite counts -> one chunk per trajectory, repeated)
@@ -262,13 +274,19 @@ class MaximumLikelihoodEstimator(object):
         else:
             # host-side engine (the CPU test double of tests/): host all-reduce
             if self._mine:
-                res = eng.estep(A, pi, par0, par1, store_gamma=self._store_gamma)
+                res = eng.estep(A, pi, par0, par1, store_gamma=self._store_gamma, **kw)
                 packed, logL_k = res.packed, res.logL_k
             else:
                 packed = np.zeros(packed_stats_size(self._output, self._nstates, self._nsymbols))
                 logL_k = np.zeros(0)
             packed = comm.allreduce_sum_numpy(packed)
             res = EStepResult(self._output, self._nstates, self._nsymbols, packed, logL_k)
+        # what ran: the engine's own account where it keeps one (fp32 falls back to fp64 by itself),
+        # else what was asked for
+        self._asked_single = single
+        self._ran_single = single
+        if single and self._mine and hasattr(eng, 'get_option'):
+            self._ran_single = eng.get_option('f32_used') != 0.0
         assert np.isfinite(res.loglik)       # maximum_likelihood.py:385
         nn = self._nstates
         assert np.all(np.isfinite(res.packed[:1 + 2 * nn + nn * nn])), \
@@ -388,10 +406,35 @@ class MaximumLikelihoodEstimator(object):
         tmatrix_nonzeros = self.hmm.transition_matrix.nonzero()
         converged = False
         res = None
+        prec = self._estep_precision
+        self.estep_precisions = []
+        # 'mixed': fp32 E-steps while they still move the model clearly (dL >= max(accuracy, 10 delta),
+        # delta = |L32 - L64| of the initial model), fp64 from the first iteration where they do not
+        # to the end; the convergence rule compares consecutive fp64 likelihoods only, so the
+        # returned likelihood, counts and model come from fp64 E-steps.  (The likelihoods are the
+        # all-reduced ones: every rank switches at the same iteration.)
+        # The stopping rule of 'mixed' is gated on the REQUESTED precision, which every rank shares: what
+        # ran (f32_used) is local -- one shard may fall back to fp64 where another verified in fp32 -- and a
+        # rank-local gate could stop one rank while the others go on into the next all-reduce.
+        single = prec != 'float64'
+        delta = 0.0
+        asked_single = []
         while not converged and it < self.maxit:
-            res = self._estep()
+            if prec == 'mixed' and it == 0:
+                loglik32 = self._estep(single=True).loglik
+                res = self._estep()                  # (its statistics go to the M-step)
+                delta = abs(loglik32 - res.loglik)
+            elif single:
+                res = self._estep(single=True)
+                if prec == 'mixed' and res.loglik - self._likelihoods[it - 1] < max(self._accuracy, 10.0 * delta):
+                    single = False
+                    res = self._estep()
+            else:
+                res = self._estep()
+            asked_single.append(self._asked_single)
+            self.estep_precisions.append('float32' if self._ran_single else 'float64')
             loglik = res.loglik
-            if it > 0:
+            if it > 0 and (prec != 'mixed' or not (asked_single[it - 1] or asked_single[it])):
                 dL = loglik - self._likelihoods[it - 1]
                 if dL < self._accuracy:          # signed, as in the reference (:389-394)
                     converged = True

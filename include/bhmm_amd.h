@@ -48,6 +48,11 @@ extern "C" {
 
 /* flags for bhmm_estep */
 #define BHMM_FLAG_STORE_GAMMA 1 /* keep gamma (T,N) per trajectory on the device            */
+#define BHMM_FLAG_SINGLE 2      /* the caller accepts single-precision accuracy for this E-step: up to 8
+                                 * states, gaussian or discrete, without STORE_GAMMA, it runs the fp32
+                                 * kernels (a permission, not a demand: anything else, or an fp32 run whose
+                                 * boundary check or ranges do not hold, runs the fp64 path).  Currently
+                                 * SLOWER than the fp64 path                     */
 
 const char *bhmm_last_error(void);
 int bhmm_device_count(void);
@@ -221,6 +226,13 @@ int bhmm_sample_paths_dev(bhmm_ctx *ctx, const double *A, const double *pi, cons
  *                        had to be repeated
  *   "spec_ok", "spec_fail"  (read-only) E-steps whose boundaries verified / fell back
  *   "spec_last_dev" (read-only) largest relative boundary deviation of the last check
+ *   "f32_used"      (read-only) 1 if the last E-step ran in fp32 end to end (BHMM_FLAG_SINGLE)
+ *   "f32_fallbacks" (read-only) E-steps that asked for fp32 (BHMM_FLAG_SINGLE) and ran the fp64 path
+ *   "f32_tol"       relative tolerance of the fp32 E-step's boundary check (default 1e-5); its
+ *                   warm-up is read off the measured forgetting curve at a thousandth of it, +50 %
+ *   "f32_W"         fixes the fp32 warm-up length in time steps (0: measured, the default; a
+ *                   failed check doubles a measured one for the next call)
+ *   "f32_last_dev"  (read-only) largest relative boundary deviation of the last fp32 check
  *   "careful"       (read-only) 1 after an E-step met an all-zero emission row (gaussian
  *                   outlier rule, outputmodel.py:126-130) and switched to the kernel that
  *                   applies the rule per step; 9..64 states: 1 after a lazily scaled vector
