@@ -86,42 +86,26 @@ struct Runner {
         const Chunks ch = chunks_of(c);
         const size_t sm0 = (size_t)(N * N + 64 * N + (KIND == EMIT_DISC ? lds_symbols(c) * N : 0)) *
                            sizeof(double);
-        if (sm0 > 64 * 1024)
-            BHMM_HIP(hipFuncSetAttribute((const void *)(k_prescan<N, KIND>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm0));
         BHMM_HIP(hipEventRecord(c->ev[0], c->stream));
-        hipLaunchKernelGGL((k_prescan<N, KIND>), dim3(c->Gp / 64), dim3(64 * N), sm0, c->stream, m, ch,
-                           (const void *)c->d_obs_ci.p, (const double *)c->d_Bt.p, c->d_M.p);
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_prescan<N, KIND>, dim3(c->Gp / 64), dim3(64 * N), sm0, c->stream, m, ch, c->d_obs_ci.p,
+                        c->d_Bt.p, c->d_M.p));
         BHMM_HIP(hipEventRecord(c->ev[1], c->stream));
         const int gp = 64 / N;
         if (c->nG == 0) {
             // one level: every trajectory stitched serially over its chunks
             const int nb = (c->K + gp - 1) / gp;
-            hipLaunchKernelGGL((k_stitch<N>), dim3(2 * nb), dim3(64), 0, c->stream,
-                               (const int32_t *)c->d_traj_c0.p, (const int32_t *)c->d_traj_c0.p + 1,
-                               c->K, nb, c->n, (const double *)c->d_M.p, (const double *)nullptr,
-                               (const double *)nullptr, c->d_aentry.p, c->d_bexit.p);
-            BHMM_HIP(hipGetLastError());
+            BHMM_HIP(launch(k_stitch<N>, dim3(2 * nb), dim3(64), 0, c->stream, c->d_traj_c0.p, c->d_traj_c0.p + 1, c->K,
+                            nb, c->n, c->d_M.p, nullptr, nullptr, c->d_aentry.p, c->d_bexit.p));
         } else {
             // two levels: group products, stitch over groups, stitch inside all groups
             const int ngb = (c->nG + gp - 1) / gp;
-            hipLaunchKernelGGL((k_compose<N>), dim3(ngb), dim3(64), 0, c->stream,
-                               (const int32_t *)c->d_grp_c0.p, (const int32_t *)c->d_grp_c1.p, c->nG,
-                               (const double *)c->d_M.p, c->d_P.p);
-            BHMM_HIP(hipGetLastError());
+            BHMM_HIP(launch(k_compose<N>, dim3(ngb), dim3(64), 0, c->stream, c->d_grp_c0.p, c->d_grp_c1.p, c->nG,
+                            c->d_M.p, c->d_P.p));
             const int nb = (c->K + gp - 1) / gp;
-            hipLaunchKernelGGL((k_stitch<N>), dim3(2 * nb), dim3(64), 0, c->stream,
-                               (const int32_t *)c->d_grp_traj0.p,
-                               (const int32_t *)c->d_grp_traj0.p + 1, c->K, nb, c->n,
-                               (const double *)c->d_P.p, (const double *)nullptr,
-                               (const double *)nullptr, c->d_agrp.p, c->d_bgrp.p);
-            BHMM_HIP(hipGetLastError());
-            hipLaunchKernelGGL((k_stitch<N>), dim3(2 * ngb), dim3(64), 0, c->stream,
-                               (const int32_t *)c->d_grp_c0.p, (const int32_t *)c->d_grp_c1.p, c->nG,
-                               ngb, c->n, (const double *)c->d_M.p, (const double *)c->d_agrp.p,
-                               (const double *)c->d_bgrp.p, c->d_aentry.p, c->d_bexit.p);
-            BHMM_HIP(hipGetLastError());
+            BHMM_HIP(launch(k_stitch<N>, dim3(2 * nb), dim3(64), 0, c->stream, c->d_grp_traj0.p, c->d_grp_traj0.p + 1,
+                            c->K, nb, c->n, c->d_P.p, nullptr, nullptr, c->d_agrp.p, c->d_bgrp.p));
+            BHMM_HIP(launch(k_stitch<N>, dim3(2 * ngb), dim3(64), 0, c->stream, c->d_grp_c0.p, c->d_grp_c1.p, c->nG, ngb,
+                            c->n, c->d_M.p, c->d_agrp.p, c->d_bgrp.p, c->d_aentry.p, c->d_bexit.p));
         }
         BHMM_HIP(hipEventRecord(c->ev[2], c->stream));
         return BHMM_OK;
@@ -140,22 +124,14 @@ struct Runner {
             BHMM_HIP(hipMemsetAsync(c->d_dpartials.p, 0,
                                     (size_t)DISC_GLOBAL_TABLES * c->M * N * sizeof(double), c->stream));
         if constexpr (MODE == MODE_ESTEP) {
-            // the exact fallback always uses the gamma-capable, careful instantiation
-            auto launch = [&](auto kern) -> int {
-                if (sm > 64 * 1024)
-                    BHMM_HIP(hipFuncSetAttribute((const void *)kern,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)sm));
-                hipLaunchKernelGGL(kern, dim3(nblk), dim3(32 * N), sm, c->stream, m, ch,
-                                   (const void *)c->d_obs_ci.p, (const void *)c->d_obs_rm.p,
-                                   (const int64_t *)c->d_offsets.p, (const double *)c->d_Bt.p,
-                                   c->d_aentry.p, c->d_bexit.p, c->d_aexit.p, c->d_bentry.p,
-                                   c->ds.spec_W, c->d_ws.p,
-                                   store_gamma ? c->d_gamma_ci.p : (double *)nullptr, c->d_logLc.p,
-                                   c->d_gamma0.p, c->d_partials.p, c->d_dpartials.p, flag_words,
-                                   c->d_ea.p, Carry());
-                return BHMM_OK;
+            // (every E-step kernel takes the same arguments)
+            auto estep = [&](auto kern, int grid, const Model<N> &mm, size_t smem, double *gam, const Carry &cy) {
+                return launch(kern, dim3(grid), dim3(32 * N), smem, c->stream, mm, ch, c->d_obs_ci.p, c->d_obs_rm.p,
+                              c->d_offsets.p, c->d_Bt.p, c->d_aentry.p, c->d_bexit.p, c->d_aexit.p, c->d_bentry.p,
+                              c->ds.spec_W, c->d_ws.p, gam, c->d_logLc.p, c->d_gamma0.p, c->d_partials.p,
+                              c->d_dpartials.p, flag_words, c->d_ea.p, cy);
             };
+            double *gam = store_gamma ? c->d_gamma_ci.p : nullptr;
             // the branch-free instantiation needs the verdict round trip of the speculative
             // path to report zero / denormal vectors; everything else runs the careful one
             // (it rescales only every few steps: emission values must stay far from the
@@ -164,7 +140,6 @@ struct Runner {
             if (KIND == EMIT_GAUSS)
                 for (int i = 0; i < c->n; ++i)
                     fast = fast && m.e2[i] < 1048576.0;
-            int rc;
             if (fast) {
                 if constexpr (SPEC && ESTEP_SPLIT) {
                     // two launches: forward sweeps + backward warm-ups side by side (four
@@ -175,22 +150,6 @@ struct Runner {
                     Model<N> m1 = m;
                     m1.dcopies = 0;
                     const size_t sm1 = KIND == EMIT_DISC ? smem_fwdbwd<N, KIND>(lds_symbols(c), 0) : sm;
-                    auto launch2 = [&](auto kern, int grid, const Model<N> &mm, size_t smem,
-                                       const Carry &cy) -> int {
-                        if (smem > 64 * 1024)
-                            BHMM_HIP(hipFuncSetAttribute((const void *)kern,
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                         (int)smem));
-                        hipLaunchKernelGGL(kern, dim3(grid), dim3(32 * N), smem, c->stream, mm, ch,
-                                           (const void *)c->d_obs_ci.p, (const void *)c->d_obs_rm.p,
-                                           (const int64_t *)c->d_offsets.p,
-                                           (const double *)c->d_Bt.p, c->d_aentry.p, c->d_bexit.p,
-                                           c->d_aexit.p, c->d_bentry.p, c->ds.spec_W, c->d_ws.p,
-                                           (double *)nullptr, c->d_logLc.p, c->d_gamma0.p,
-                                           c->d_partials.p, c->d_dpartials.p, flag_words, c->d_ea.p,
-                                           cy);
-                        return BHMM_OK;
-                    };
                     // boundary vectors carried between E-steps (decided by estep_kind): P1 starts its
                     // warm-ups from them, P2 captures beta for the next E-step
                     Carry c1, c2;
@@ -200,10 +159,7 @@ struct Runner {
                         c1.da = c->d_carry_da.p;
                         c1.db = c->d_carry_db.p;
                     }
-                    if ((rc = launch2(k_estep_light<N, KIND, SPEC, false, false, PH_P1>, 2 * nblk, m1,
-                                      sm1, c1)))
-                        return rc;
-                    BHMM_HIP(hipGetLastError());
+                    BHMM_HIP(estep(k_estep_light<N, KIND, SPEC, false, false, PH_P1>, 2 * nblk, m1, sm1, nullptr, c1));
                     c2.cap = c->ds.carry_cap;
                     if (c->ds.carry_cap > 0 && c->carry_store) {
                         // (P1 has consumed the old vectors: the same buffers take the new ones)
@@ -212,35 +168,25 @@ struct Runner {
                         c2.b_out = c->d_carry_b.p;
                         c2.db_out = c->d_carry_db.p;
                     }
-                    rc = launch2(k_estep<N, KIND, SPEC, false, false, PH_P2>, nblk, m, sm, c2);
-                    if (rc == BHMM_OK && c->ds.carry_cap > 0 && c->carry_store) {
-                        BHMM_HIP(hipGetLastError());
-                        hipLaunchKernelGGL((k_carry_alpha<N>), dim3((c->G + 255) / 256), dim3(256), 0,
-                                           c->stream, ch, c->G, (const double *)c->d_ws.p,
-                                           c->carry_Wout, c->d_carry_a.p, c->d_carry_da.p);
-                    }
+                    BHMM_HIP(estep(k_estep<N, KIND, SPEC, false, false, PH_P2>, nblk, m, sm, nullptr, c2));
+                    if (c->ds.carry_cap > 0 && c->carry_store)
+                        BHMM_HIP(launch(k_carry_alpha<N>, dim3((c->G + 255) / 256), dim3(256), 0, c->stream, ch, c->G,
+                                        c->d_ws.p, c->carry_Wout, c->d_carry_a.p, c->d_carry_da.p));
                 } else {
                     c->ds.carry_cap = 0;
-                    rc = launch(k_estep<N, KIND, SPEC, false, false>);
+                    BHMM_HIP(estep(k_estep<N, KIND, SPEC, false, false>, nblk, m, sm, gam, Carry()));
                 }
             } else {
+                // the exact fallback always uses the gamma-capable, careful instantiation
                 c->ds.carry_cap = 0; // (no capture outside the split launches)
-                rc = launch(k_estep<N, KIND, SPEC, true, true>);
+                BHMM_HIP(estep(k_estep<N, KIND, SPEC, true, true>, nblk, m, sm, gam, Carry()));
             }
-            if (rc)
-                return rc;
         } else {
             static_assert(MODE == MODE_ESTEP || !SPEC, "row passes take exact boundaries");
             const size_t smr = (size_t)(KIND == EMIT_DISC ? lds_symbols(c) * N : 0) * sizeof(double);
-            if (smr > 64 * 1024)
-                BHMM_HIP(hipFuncSetAttribute((const void *)(k_rows<N, KIND, MODE>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smr));
-            hipLaunchKernelGGL((k_rows<N, KIND, MODE>), dim3(nblk), dim3(32 * N), smr, c->stream, m,
-                               ch, (const void *)c->d_obs_ci.p, (const double *)c->d_Bt.p,
-                               (const double *)c->d_aentry.p, (const double *)c->d_bexit.p, c->d_ws.p,
-                               c->d_logLc.p);
+            BHMM_HIP(launch(k_rows<N, KIND, MODE>, dim3(nblk), dim3(32 * N), smr, c->stream, m, ch, c->d_obs_ci.p,
+                            c->d_Bt.p, c->d_aentry.p, c->d_bexit.p, c->d_ws.p, c->d_logLc.p));
         }
-        BHMM_HIP(hipGetLastError());
         BHMM_HIP(hipEventRecord(c->ev[3], c->stream));
         return BHMM_OK;
     }
@@ -248,16 +194,10 @@ struct Runner {
     template <int KIND>
     static int finish(bhmm_ctx *c, const Model<N> &m, double *stats_dev)
     {
-        hipLaunchKernelGGL(k_logl, dim3(c->K), dim3(64), 0, c->stream,
-                           (const int32_t *)c->d_traj_c0.p, c->K, (const double *)c->d_logLc.p,
-                           c->d_logLk.p);
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_logl, dim3(c->K), dim3(64), 0, c->stream, c->d_traj_c0.p, c->K, c->d_logLc.p, c->d_logLk.p));
         const int nfin = StatLayout<N, KIND>::S + (KIND == EMIT_DISC ? c->M * N : 0) + N + 1;
-        hipLaunchKernelGGL((k_finalize<N, KIND>), dim3(nfin), dim3(64), 0, c->stream, m, c->K,
-                           c->Gp / 64, (const double *)c->d_partials.p,
-                           (const double *)c->d_dpartials.p, (const double *)c->d_logLk.p,
-                           (const double *)c->d_gamma0.p, stats_dev);
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_finalize<N, KIND>, dim3(nfin), dim3(64), 0, c->stream, m, c->K, c->Gp / 64, c->d_partials.p,
+                        c->d_dpartials.p, c->d_logLk.p, c->d_gamma0.p, stats_dev));
         return BHMM_OK;
     }
 
@@ -324,34 +264,23 @@ struct Runner {
             const int nf = (nrows + FOLD_ROWS - 1) / FOLD_ROWS;
             if ((rc = c->d_fold.ensure((size_t)nf * (SS + MN))))
                 return rc;
-            hipLaunchKernelGGL(k_fold_rows, dim3(nf), dim3(256), 0, c->stream,
-                               (const double *)c->d_partials.p, nrows, SS, c->d_fold.p);
+            BHMM_HIP(launch(k_fold_rows, dim3(nf), dim3(256), 0, c->stream, c->d_partials.p, nrows, SS, c->d_fold.p));
             part_src = c->d_fold.p;
             if (MN) {
-                hipLaunchKernelGGL(k_fold_rows, dim3(nf), dim3(256), 0, c->stream,
-                                   (const double *)c->d_dpartials.p, nrows, MN,
-                                   c->d_fold.p + (size_t)nf * SS);
+                BHMM_HIP(launch(k_fold_rows, dim3(nf), dim3(256), 0, c->stream, c->d_dpartials.p, nrows, MN,
+                                c->d_fold.p + (size_t)nf * SS));
                 dpart_src = c->d_fold.p + (size_t)nf * SS;
             }
-            BHMM_HIP(hipGetLastError());
             nrows = nf;
         }
-        hipLaunchKernelGGL((k_tail<N, KIND>),
-                           dim3((nfin + nTB + (c->G + 63) / 64 + TAIL_WAVES - 1) / TAIL_WAVES),
-                           dim3(64 * TAIL_WAVES), 0,
-                           c->stream, m, chunks_of(c), c->K, c->G, nrows, nfin,
-                           (const int32_t *)c->d_traj_c0.p, part_src,
-                           dpart_src, (const double *)c->d_logLc.p,
-                           (const double *)c->d_gamma0.p, (const double *)c->d_aentry.p,
-                           (const double *)c->d_aexit.p, (const double *)c->d_bexit.p,
-                           (const double *)c->d_bentry.p, SPEC_TOL, stats_dev, c->d_logLk.p,
-                           c->d_tail.p + 4, S, words, words_next, c->d_tbpart.p, fused_total, tpb);
-        BHMM_HIP(hipGetLastError());
-        if (!fused_total) {
-            hipLaunchKernelGGL((k_tail_total<N>), dim3(1 + N), dim3(64), 0, c->stream, c->n, nTB,
-                               (const double *)c->d_tbpart.p, stats_dev, c->d_tail.p + 4);
-            BHMM_HIP(hipGetLastError());
-        }
+        BHMM_HIP(launch(k_tail<N, KIND>, dim3((nfin + nTB + (c->G + 63) / 64 + TAIL_WAVES - 1) / TAIL_WAVES),
+                        dim3(64 * TAIL_WAVES), 0, c->stream, m, chunks_of(c), c->K, c->G, nrows, nfin, c->d_traj_c0.p,
+                        part_src, dpart_src, c->d_logLc.p, c->d_gamma0.p, c->d_aentry.p, c->d_aexit.p, c->d_bexit.p,
+                        c->d_bentry.p, SPEC_TOL, stats_dev, c->d_logLk.p, c->d_tail.p + 4, S, words, words_next,
+                        c->d_tbpart.p, fused_total, tpb));
+        if (!fused_total)
+            BHMM_HIP(launch(k_tail_total<N>, dim3(1 + N), dim3(64), 0, c->stream, c->n, nTB, c->d_tbpart.p, stats_dev,
+                            c->d_tail.p + 4));
         BHMM_HIP(hipEventRecord(c->ev[4], c->stream));
         c->ev_lean = true;
         // many trajectories: their log-likelihoods (K doubles) stay on the device until somebody asks
@@ -407,10 +336,8 @@ struct Runner {
         BHMM_HIP(hipMemcpyAsync(d_starts, starts.data(), S * sizeof(int64_t), hipMemcpyHostToDevice,
                                 c->stream));
         BHMM_HIP(hipMemsetAsync(d_curve, 0, 2 * (size_t)Wmax * sizeof(unsigned int), c->stream));
-        hipLaunchKernelGGL((k_forget_probe<N, KIND>), dim3((2 * S + 63) / 64), dim3(64), 0, c->stream,
-                           m, (const void *)c->d_obs_rm.p, (const double *)c->d_Bt.p,
-                           (const int64_t *)d_starts, S, Wmax, d_curve);
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_forget_probe<N, KIND>, dim3((2 * S + 63) / 64), dim3(64), 0, c->stream, m, c->d_obs_rm.p,
+                        c->d_Bt.p, d_starts, S, Wmax, d_curve));
         std::vector<float> curve(2 * (size_t)Wmax);
         BHMM_HIP(hipMemcpyAsync(curve.data(), d_curve, curve.size() * sizeof(float),
                                 hipMemcpyDeviceToHost, c->stream));
@@ -544,16 +471,10 @@ struct Runner {
         rc = fwdbwd<KIND, MODE_ESTEP>(c, m, (flags & BHMM_FLAG_STORE_GAMMA) != 0);
         if (rc)
             return rc;
-        hipLaunchKernelGGL(k_logl, dim3(c->K), dim3(64), 0, c->stream,
-                           (const int32_t *)c->d_traj_c0.p, c->K, (const double *)c->d_logLc.p,
-                           c->d_logLk.p);
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_logl, dim3(c->K), dim3(64), 0, c->stream, c->d_traj_c0.p, c->K, c->d_logLc.p, c->d_logLk.p));
         const int nfin = StatLayout<N, KIND>::S + (KIND == EMIT_DISC ? c->M * N : 0) + N + 1;
-        hipLaunchKernelGGL((k_finalize<N, KIND>), dim3(nfin), dim3(64), 0, c->stream, m, c->K,
-                           c->Gp / 64, (const double *)c->d_partials.p,
-                           (const double *)c->d_dpartials.p, (const double *)c->d_logLk.p,
-                           (const double *)c->d_gamma0.p, stats_dev);
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_finalize<N, KIND>, dim3(nfin), dim3(64), 0, c->stream, m, c->K, c->Gp / 64, c->d_partials.p,
+                        c->d_dpartials.p, c->d_logLk.p, c->d_gamma0.p, stats_dev));
         BHMM_HIP(hipEventRecord(c->ev[4], c->stream));
         c->ev_pending = true;
         return BHMM_OK;
@@ -604,12 +525,9 @@ struct Runner {
         rc = fwdbwd<EMIT_EXPL, MODE>(c, m, false);
         if (rc)
             return rc;
-        if (MODE == MODE_FWD) {
-            hipLaunchKernelGGL(k_logl, dim3(c->K), dim3(64), 0, c->stream,
-                               (const int32_t *)c->d_traj_c0.p, c->K,
-                               (const double *)c->d_logLc.p, c->d_logLk.p);
-            BHMM_HIP(hipGetLastError());
-        }
+        if (MODE == MODE_FWD)
+            BHMM_HIP(launch(k_logl, dim3(c->K), dim3(64), 0, c->stream, c->d_traj_c0.p, c->K, c->d_logLc.p,
+                            c->d_logLk.p));
         return BHMM_OK;
     }
 
@@ -617,12 +535,9 @@ struct Runner {
     static int spec_verdict(bhmm_ctx *c, bool with_beta, bool *verified,
                             const double *stats_src = nullptr)
     {
-        hipLaunchKernelGGL((k_spec_check<N>), dim3((c->G + 255) / 256), dim3(256), 0, c->stream,
-                           chunks_of(c), c->G, (const double *)c->d_aentry.p,
-                           (const double *)c->d_aexit.p,
-                           with_beta ? (const double *)c->d_bexit.p : (const double *)nullptr,
-                           (const double *)c->d_bentry.p, SPEC_TOL, c->d_specres.p);
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_spec_check<N>, dim3((c->G + 255) / 256), dim3(256), 0, c->stream, chunks_of(c), c->G,
+                        c->d_aentry.p, c->d_aexit.p, with_beta ? c->d_bexit.p : nullptr, c->d_bentry.p, SPEC_TOL,
+                        c->d_specres.p));
         BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
                                 hipMemcpyDeviceToHost, c->stream));
         c->prefetched = false;
@@ -740,21 +655,15 @@ struct Runner {
         Model<N> m = m_in; // no emission counts in this pass: no count tables in LDS
         m.dcopies = 0;
         const size_t sm = smem_fwdbwd<N, KIND>(lds_symbols(c), KIND == EMIT_DISC ? 0 : 1);
-        auto kern = k_estep_light<N, KIND, true, false, CAREFUL, PH_FWDROWS>;
-        if (sm > 64 * 1024)
-            BHMM_HIP(hipFuncSetAttribute((const void *)kern,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
         // every alpha row in fp32 (in the gamma_ci slot of the kernel), every FWD_CKPT-th in fp64
         int rc = c->d_ws32.ensure((size_t)ci_records(c) * N * 64);
         if (rc)
             return rc;
-        hipLaunchKernelGGL(kern, dim3(c->Gp / 64), dim3(32 * N), sm, c->stream, m, ch,
-                           (const void *)c->d_obs_ci.p, (const void *)c->d_obs_rm.p,
-                           (const int64_t *)c->d_offsets.p, (const double *)c->d_Bt.p, c->d_aentry.p,
-                           c->d_bexit.p, c->d_aexit.p, c->d_bentry.p, c->ds.spec_W, c->d_ws.p,
-                           reinterpret_cast<double *>(c->d_ws32.p), c->d_logLc.p, c->d_gamma0.p,
-                           c->d_partials.p, c->d_dpartials.p, c->d_specres.p, c->d_ea.p, Carry());
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_estep_light<N, KIND, true, false, CAREFUL, PH_FWDROWS>, dim3(c->Gp / 64), dim3(32 * N), sm,
+                        c->stream, m, ch, c->d_obs_ci.p, c->d_obs_rm.p, c->d_offsets.p, c->d_Bt.p, c->d_aentry.p,
+                        c->d_bexit.p, c->d_aexit.p, c->d_bentry.p, c->ds.spec_W, c->d_ws.p,
+                        reinterpret_cast<double *>(c->d_ws32.p), c->d_logLc.p, c->d_gamma0.p, c->d_partials.p,
+                        c->d_dpartials.p, c->d_specres.p, c->d_ea.p, Carry()));
         c->rows32_valid = true;
         return BHMM_OK;
     }
@@ -791,11 +700,8 @@ struct Runner {
                 if (c->fwd_defer && attempt == 0) {
                     // the caller keeps launching on the stream and reads the verdict with its own
                     // results (forward_ci_verdict): one host round trip less per Gibbs sweep
-                    hipLaunchKernelGGL((k_spec_check<N>), dim3((c->G + 255) / 256), dim3(256), 0,
-                                       c->stream, chunks_of(c), c->G, (const double *)c->d_aentry.p,
-                                       (const double *)c->d_aexit.p, (const double *)nullptr,
-                                       (const double *)c->d_bentry.p, SPEC_TOL, c->d_specres.p);
-                    BHMM_HIP(hipGetLastError());
+                    BHMM_HIP(launch(k_spec_check<N>, dim3((c->G + 255) / 256), dim3(256), 0, c->stream, chunks_of(c),
+                                    c->G, c->d_aentry.p, c->d_aexit.p, nullptr, c->d_bentry.p, SPEC_TOL, c->d_specres.p));
                     BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
                                             hipMemcpyDeviceToHost, c->stream));
                     c->prefetched = false;
@@ -845,18 +751,16 @@ struct Runner {
 
     static int pack_rows(bhmm_ctx *c, const double *src_dev)
     {
-        hipLaunchKernelGGL((k_pack_rows<N>), dim3(c->Gp / BLOCK), dim3(BLOCK), 0, c->stream,
-                           chunks_of(c), src_dev, c->n, reinterpret_cast<double *>(c->d_obs_ci.p));
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_pack_rows<N>, dim3(c->Gp / BLOCK), dim3(BLOCK), 0, c->stream, chunks_of(c), src_dev, c->n,
+                        reinterpret_cast<double *>(c->d_obs_ci.p)));
         return BHMM_OK;
     }
 
     static int unpack_rows(bhmm_ctx *c, const double *src_ci, double *dst_dev, int only_traj,
                            int64_t shift)
     {
-        hipLaunchKernelGGL((k_unpack_rows<N>), dim3(c->Gp / BLOCK), dim3(BLOCK), 0, c->stream,
-                           chunks_of(c), src_ci, c->n, dst_dev, only_traj, shift);
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_unpack_rows<N>, dim3(c->Gp / BLOCK), dim3(BLOCK), 0, c->stream, chunks_of(c), src_ci, c->n,
+                        dst_dev, only_traj, shift));
         return BHMM_OK;
     }
 };
@@ -1206,15 +1110,15 @@ static int pack_observations(bhmm_ctx *c, const char *src_dev)
     if (kind == BHMM_EMIT_GAUSSIAN) {
         if ((rc = c->d_obs_ci.ensure(ci_elems * sizeof(double))))
             return rc;
-        hipLaunchKernelGGL((k_pack_scalar<double>), dim3(nblk), dim3(BLOCK), 0, c->stream, ch,
-                           reinterpret_cast<const double *>(src_dev),
-                           reinterpret_cast<double *>(c->d_obs_ci.p), c->d_obsnan.p);
+        BHMM_HIP(launch(k_pack_scalar<double>, dim3(nblk), dim3(BLOCK), 0, c->stream, ch,
+                        reinterpret_cast<const double *>(src_dev), reinterpret_cast<double *>(c->d_obs_ci.p),
+                        c->d_obsnan.p));
     } else if (kind == BHMM_EMIT_DISCRETE) {
         if ((rc = c->d_obs_ci.ensure(ci_elems * sizeof(int32_t))))
             return rc;
-        hipLaunchKernelGGL((k_pack_scalar<int32_t>), dim3(nblk), dim3(BLOCK), 0, c->stream, ch,
-                           reinterpret_cast<const int32_t *>(src_dev),
-                           reinterpret_cast<int32_t *>(c->d_obs_ci.p), c->d_obsnan.p);
+        BHMM_HIP(launch(k_pack_scalar<int32_t>, dim3(nblk), dim3(BLOCK), 0, c->stream, ch,
+                        reinterpret_cast<const int32_t *>(src_dev), reinterpret_cast<int32_t *>(c->d_obs_ci.p),
+                        c->d_obsnan.p));
     } else {
         if ((rc = c->d_obs_ci.ensure(ci_elems * sizeof(double) * c->N)))
             return rc;
@@ -1251,7 +1155,6 @@ int bhmm::replan_coarse(bhmm_ctx *c, bool half, int chunk)
         return rc;
     if ((rc = pack_observations(c, c->d_obs_rm.p)))
         return rc;
-    BHMM_HIP(hipGetLastError());
     BHMM_HIP(hipStreamSynchronize(c->stream));
     // rows stored under the old plan are gone; an E-step in flight that stores gamma (this runs
     // inside its first call) gets rows of the new plan's size -- bhmm_estep sets gamma_valid
@@ -1369,7 +1272,6 @@ int bhmm_ctx_set_observations(bhmm_ctx *c, int kind, const void *obs, const int6
     }
     if ((rc = pack_observations(c, src_dev)))
         return rc;
-    BHMM_HIP(hipGetLastError());
     if (obs_on_device) {
         // keep a trajectory-major copy for the path kernels
         if ((rc = c->d_obs_rm.ensure(bytes)))
@@ -1464,11 +1366,8 @@ int bhmm_ctx_set_observations_lagged(bhmm_ctx *c, int kind, const void *obs, con
         longest = std::max(longest, dst_off[v + 1] - dst_off[v]);
     const unsigned gx = (unsigned)std::min<int64_t>(64, (longest + 255) / 256);
     const unsigned gy = (unsigned)std::min(V, 32768);
-    hipLaunchKernelGGL(k_lag_gather, dim3(gx, gy), dim3(256), 0, c->stream,
-                       reinterpret_cast<const uint32_t *>(src_dev),
-                       reinterpret_cast<uint32_t *>(d_dst.p), (const int64_t *)d_tab.p,
-                       (const int64_t *)(d_tab.p + V), lag, (int)(esz / 4), V);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_lag_gather, dim3(gx, gy), dim3(256), 0, c->stream, reinterpret_cast<const uint32_t *>(src_dev),
+                    reinterpret_cast<uint32_t *>(d_dst.p), d_tab.p, d_tab.p + V, lag, (int)(esz / 4), V));
     BHMM_HIP(hipStreamSynchronize(c->stream)); // the host tables are temporaries
     return bhmm_ctx_set_observations(c, kind, d_dst.p, dst_off.data(), V, nstates, nsymbols, chunk, 1);
 }
@@ -1487,11 +1386,9 @@ int bhmm_diag_gauss_pdf(double *y, const double *o, int64_t n, double mu, double
         e = hipMalloc(&dy, n * sizeof(double));
     if (e == hipSuccess)
         e = hipMemcpy(dx, o, n * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_gauss_pdf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dx, dy,
-                           n, m.e0[0], m.e4[0], m.e5[0], m.emg, nansafe);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess)
+        e = launch(k_gauss_pdf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dx, dy, n, m.e0[0], m.e4[0],
+                   m.e5[0], m.emg, nansafe);
     if (e == hipSuccess)
         e = hipMemcpy(y, dy, n * sizeof(double), hipMemcpyDeviceToHost);
     (void)hipFree(dx);
@@ -1510,11 +1407,8 @@ int bhmm_diag_exp_nonpos(double *y, const double *x, int64_t n)
         return hip_fail(hipErrorOutOfMemory, "hipMalloc");
     }
     hipError_t e = hipMemcpy(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_exp_nonpos, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0,
-                           (const double *)dx, dy, n);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess)
+        e = launch(k_exp_nonpos, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dx, dy, n);
     if (e == hipSuccess)
         e = hipMemcpy(y, dy, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
     (void)hipFree(dx);

@@ -10,6 +10,7 @@
 
 #include "host_common.hpp"
 #include "host_internal.hpp"
+#include "launch.hpp"
 #include "gen_kernels.hpp"
 #include "big_kernels.hpp"
 
@@ -17,15 +18,6 @@ namespace bhmm {
 
 namespace {
 // ---- more than 128 states: big_kernels.hpp ---------------------------------------------------------
-template <typename F>
-int big_set_smem(F *fn, size_t sm)
-{
-    if (sm > 64 * 1024)
-        BHMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)sm));
-    return BHMM_OK;
-}
-
 template <int TPW, int KIND>
 int big_fwd_t(bhmm_ctx *c, const WideModel &m)
 {
@@ -36,17 +28,15 @@ int big_fwd_t(bhmm_ctx *c, const WideModel &m)
     // A in matrix-operand order for both passes (the model of THIS call: the backward pass follows)
     const size_t npk = (size_t)G::NP * G::NP;
     int rc;
-    if ((rc = c->d_bigBf.ensure(npk)) || (rc = c->d_bigBb.ensure(npk)) || (rc = big_set_smem(k_big_fwd<TPW, KIND>, G::smem)))
+    if ((rc = c->d_bigBf.ensure(npk)) || (rc = c->d_bigBb.ensure(npk)))
         return rc;
-    hipLaunchKernelGGL(k_big_pack, dim3((unsigned)((npk + 255) / 256)), dim3(256), 0, c->stream, m.A, c->n, G::NP,
-                       c->d_bigBf.p, c->d_bigBb.p);
-    hipLaunchKernelGGL((k_big_fwd<TPW, KIND>), dim3(tp.ntiles), dim3(256), G::smem, c->stream, m,
-                       (const double *)c->d_bigBf.p, (const int64_t *)c->d_offsets.p, sg, tp, (const void *)c->d_obs_rm.p,
-                       c->d_alpha_rm.p, c->d_wlogLseg.p, c->d_waentry.p, c->d_waexit.p, c->d_specres.p);
-    BHMM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_logl, dim3(c->K), dim3(64), 0, c->stream, (const int32_t *)c->d_wseg_traj0[1].p, c->K,
-                       (const double *)c->d_wlogLseg.p, c->d_logLk.p);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_big_pack, dim3((unsigned)((npk + 255) / 256)), dim3(256), 0, c->stream, m.A, c->n, G::NP,
+                    c->d_bigBf.p, c->d_bigBb.p));
+    BHMM_HIP(launch(k_big_fwd<TPW, KIND>, dim3(tp.ntiles), dim3(256), G::smem, c->stream, m, c->d_bigBf.p,
+                    c->d_offsets.p, sg, tp, c->d_obs_rm.p, c->d_alpha_rm.p, c->d_wlogLseg.p, c->d_waentry.p,
+                    c->d_waexit.p, c->d_specres.p));
+    BHMM_HIP(launch(k_logl, dim3(c->K), dim3(64), 0, c->stream, c->d_wseg_traj0[1].p, c->K, c->d_wlogLseg.p,
+                    c->d_logLk.p));
     return BHMM_OK;
 }
 
@@ -78,34 +68,17 @@ int big_bwd_t(bhmm_ctx *c, const WideModel &m, double *gam, double *stats_dev)
     const int nsplit = (int)std::max<int64_t>(
         1, std::min<int64_t>({(int64_t)(2 * c->num_simd / 4) / (nb * nb), (c->total + 255) / 256, (int64_t)256}));
     int rc;
-    if ((rc = c->d_gW.ensure((size_t)c->total * n)) || (rc = c->d_gxipart.ensure((size_t)nsplit * n * n)) ||
-        (rc = big_set_smem(k_big_bwd<TPW, KIND>, G::smem)))
+    if ((rc = c->d_gW.ensure((size_t)c->total * n)) || (rc = c->d_gxipart.ensure((size_t)nsplit * n * n)))
         return rc;
-    hipLaunchKernelGGL(k_wide_zero_last_rows, dim3(c->K), dim3(64), 0, c->stream, (const int64_t *)c->d_offsets.p,
-                       c->K, n, c->d_gW.p);
-    hipLaunchKernelGGL((k_big_bwd<TPW, KIND>), dim3(tp.ntiles), dim3(256), G::smem, c->stream, m,
-                       (const double *)c->d_bigBb.p, (const int64_t *)c->d_offsets.p, sg, tp, (const void *)c->d_obs_rm.p,
-                       (const double *)c->d_alpha_rm.p, gam, c->d_gamma0.p, c->d_partials.p, c->d_dpartials.p,
-                       c->d_wbexit.p, c->d_wbentry.p, c->d_specres.p, c->d_gW.p);
-    BHMM_HIP(hipGetLastError());
-#define BIG_XI(TIV)                                                                                              \
-    hipLaunchKernelGGL(k_big_xi_gemm<TIV>, dim3(nb * nb * nsplit), dim3(256), 0, c->stream,                        \
-                       (const double *)c->d_alpha_rm.p, (const double *)c->d_gW.p, c->total, n, nb, nsplit,        \
-                       c->d_gxipart.p)
-    if (ti == 3)
-        BIG_XI(3);
-    else if (ti == 5)
-        BIG_XI(5);
-    else if (ti == 6)
-        BIG_XI(6);
-    else
-        BIG_XI(4);
-#undef BIG_XI
-    hipLaunchKernelGGL((k_big_finalize<KIND>), dim3(4096), dim3(64), 0, c->stream, m, c->K, tp.ntiles, nsplit,
-                       (const double *)c->d_gxipart.p, (const double *)c->d_partials.p,
-                       (const double *)c->d_dpartials.p, (const double *)c->d_logLk.p, (const double *)c->d_gamma0.p,
-                       stats_dev);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_wide_zero_last_rows, dim3(c->K), dim3(64), 0, c->stream, c->d_offsets.p, c->K, n, c->d_gW.p));
+    BHMM_HIP(launch(k_big_bwd<TPW, KIND>, dim3(tp.ntiles), dim3(256), G::smem, c->stream, m, c->d_bigBb.p,
+                    c->d_offsets.p, sg, tp, c->d_obs_rm.p, c->d_alpha_rm.p, gam, c->d_gamma0.p, c->d_partials.p,
+                    c->d_dpartials.p, c->d_wbexit.p, c->d_wbentry.p, c->d_specres.p, c->d_gW.p));
+    auto *xi = ti == 3 ? k_big_xi_gemm<3> : ti == 5 ? k_big_xi_gemm<5> : ti == 6 ? k_big_xi_gemm<6> : k_big_xi_gemm<4>;
+    BHMM_HIP(launch(xi, dim3(nb * nb * nsplit), dim3(256), 0, c->stream, c->d_alpha_rm.p, c->d_gW.p, c->total, n, nb,
+                    nsplit, c->d_gxipart.p));
+    BHMM_HIP(launch(k_big_finalize<KIND>, dim3(4096), dim3(64), 0, c->stream, m, c->K, tp.ntiles, nsplit,
+                    c->d_gxipart.p, c->d_partials.p, c->d_dpartials.p, c->d_logLk.p, c->d_gamma0.p, stats_dev));
     return BHMM_OK;
 }
 

@@ -11,6 +11,7 @@
 
 #include "host_common.hpp"
 #include "host_internal.hpp"
+#include "launch.hpp"
 #include "estep_f32.hpp"
 
 namespace bhmm {
@@ -114,30 +115,20 @@ int run(bhmm_ctx *c, const double *A, const double *pi, const double *par0, cons
     BHMM_HIP(hipMemsetAsync(c->d_f32words.p, 0, 2 * sizeof(unsigned int), c->stream));
     const Chunks ch = chunks_of(c);
     const int nblk = c->Gp / 64;
-    if (sm > 64 * 1024)
-        BHMM_HIP(hipFuncSetAttribute((const void *)(k_estep_f32<N, KIND>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
     BHMM_HIP(hipEventRecord(c->ev[2], c->stream));
-    hipLaunchKernelGGL((k_estep_f32<N, KIND>), dim3(nblk), dim3(32 * N), sm, c->stream, mf, ch,
-                       (const void *)c->d_obs_ci.p, (const void *)c->d_obs_rm.p,
-                       (const int64_t *)c->d_offsets.p, (const float *)c->d_Bt32.p,
-                       reinterpret_cast<float *>(c->d_ws.p), c->d_f32vec.p, c->Gp, c->d_logLc.p,
-                       c->d_gamma0.p, c->d_partials.p, c->d_dpartials.p, c->d_f32words.p + 1);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_estep_f32<N, KIND>, dim3(nblk), dim3(32 * N), sm, c->stream, mf, ch, c->d_obs_ci.p,
+                    c->d_obs_rm.p, c->d_offsets.p, c->d_Bt32.p, reinterpret_cast<float *>(c->d_ws.p),
+                    c->d_f32vec.p, c->Gp, c->d_logLc.p, c->d_gamma0.p, c->d_partials.p, c->d_dpartials.p,
+                    c->d_f32words.p + 1));
     BHMM_HIP(hipEventRecord(c->ev[3], c->stream));
-    if (c->G > 1) {
-        hipLaunchKernelGGL((k_f32_check<N>), dim3((c->G + 255) / 256), dim3(256), 0, c->stream, ch, c->G,
-                           c->Gp, (const float *)c->d_f32vec.p, c->d_f32words.p);
-        BHMM_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_logl, dim3(c->K), dim3(64), 0, c->stream, (const int32_t *)c->d_traj_c0.p, c->K,
-                       (const double *)c->d_logLc.p, c->d_logLk.p);
-    BHMM_HIP(hipGetLastError());
+    if (c->G > 1)
+        BHMM_HIP(launch(k_f32_check<N>, dim3((c->G + 255) / 256), dim3(256), 0, c->stream, ch, c->G, c->Gp,
+                        c->d_f32vec.p, c->d_f32words.p));
+    BHMM_HIP(launch(k_logl, dim3(c->K), dim3(64), 0, c->stream, c->d_traj_c0.p, c->K, c->d_logLc.p,
+                    c->d_logLk.p));
     const int nfin = StatLayout<N, KIND>::S + (KIND == EMIT_DISC ? c->M * N : 0) + N + 1;
-    hipLaunchKernelGGL((k_finalize<N, KIND>), dim3(nfin), dim3(64), 0, c->stream, m, c->K, nblk,
-                       (const double *)c->d_partials.p, (const double *)c->d_dpartials.p,
-                       (const double *)c->d_logLk.p, (const double *)c->d_gamma0.p, stats_dev);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_finalize<N, KIND>, dim3(nfin), dim3(64), 0, c->stream, m, c->K, nblk, c->d_partials.p,
+                    c->d_dpartials.p, c->d_logLk.p, c->d_gamma0.p, stats_dev));
     BHMM_HIP(hipEventRecord(c->ev[4], c->stream));
     // verdict words, statistics and (few trajectories) logL_k on one synchronisation
     c->logLk_prefetched = c->K <= 4096;

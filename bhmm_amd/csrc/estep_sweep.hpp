@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "estep_kernels.hpp"
+#include "launch.hpp"
 
 #ifndef ESTEP_SCALE_EVERY
 #define ESTEP_SCALE_EVERY 4 // branch-free sweeps rescale every so many steps
@@ -1592,9 +1593,7 @@ __global__ __launch_bounds__(32 * N) __attribute__((amdgpu_waves_per_eu(4))) voi
     if (!poison)
         return;
     const int bytes = 160 * 1024;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_lds_poison),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    hipLaunchKernelGGL(k_lds_poison, dim3(2048), dim3(1024), bytes, stream, bytes / 4);
+    (void)launch(k_lds_poison, dim3(2048), dim3(1024), bytes, stream, bytes / 4);
     (void)hipGetLastError();
 }
 

@@ -11,6 +11,7 @@
 
 #include "host_common.hpp"
 #include "host_internal.hpp"
+#include "launch.hpp"
 #include "gen_kernels.hpp"
 
 namespace bhmm {
@@ -21,15 +22,6 @@ size_t gen_smem(int n, int vectors, int extra) { return ((size_t)vectors * n + e
 // the workgroup's own copy of the transition matrix behind the vectors, where it fits (gen_kernels.hpp, ALDS)
 size_t gen_a_bytes(int n) { return (size_t)n * n * sizeof(double); }
 bool gen_a_in_lds(int n, size_t vectors_bytes) { return vectors_bytes + gen_a_bytes(n) <= GEN_LDS_LIMIT; }
-
-template <typename F>
-int gen_set_smem(F *fn, size_t sm)
-{
-    if (sm > 64 * 1024)
-        BHMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-    return BHMM_OK;
-}
 
 // emission rows of all steps (the reference materialises them too, maximum_likelihood.py:249-252)
 int gen_pobs(bhmm_ctx *c, const WideModel &m, const double **pobs)
@@ -42,13 +34,8 @@ int gen_pobs(bhmm_ctx *c, const WideModel &m, const double **pobs)
     if (rc)
         return rc;
     const dim3 pg((unsigned)((c->total + 255) / 256)), pb(256);
-    if (c->kind == EMIT_GAUSS)
-        hipLaunchKernelGGL((k_pobs_all<EMIT_GAUSS>), pg, pb, 0, c->stream, m, (const void *)c->d_obs_rm.p,
-                           c->total, c->d_gpobs.p);
-    else
-        hipLaunchKernelGGL((k_pobs_all<EMIT_DISC>), pg, pb, 0, c->stream, m, (const void *)c->d_obs_rm.p,
-                           c->total, c->d_gpobs.p);
-    BHMM_HIP(hipGetLastError());
+    auto *k = c->kind == EMIT_GAUSS ? k_pobs_all<EMIT_GAUSS> : k_pobs_all<EMIT_DISC>;
+    BHMM_HIP(launch(k, pg, pb, 0, c->stream, m, c->d_obs_rm.p, c->total, c->d_gpobs.p));
     *pobs = c->d_gpobs.p;
     return BHMM_OK;
 }
@@ -59,9 +46,8 @@ int gen_transposed(bhmm_ctx *c, const WideModel &m)
     int rc = c->d_gAt.ensure((size_t)n * n);
     if (rc)
         return rc;
-    hipLaunchKernelGGL(k_gen_transpose, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0,
-                       c->stream, m.A, n, c->d_gAt.p);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_gen_transpose, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, c->stream, m.A, n,
+                    c->d_gAt.p));
     return BHMM_OK;
 }
 
@@ -69,20 +55,10 @@ int gen_launch_forward(bhmm_ctx *c, const WideModel &m, const double *pobs)
 {
     size_t sm = gen_smem(c->n, 2, 2);
     const bool alds = gen_a_in_lds(c->n, sm);
-    int rc;
-    if (alds) {
-        sm += gen_a_bytes(c->n);
-        if ((rc = gen_set_smem(k_gen_forward<true>, sm)))
-            return rc;
-        hipLaunchKernelGGL(k_gen_forward<true>, dim3(c->K), dim3(GEN_TPB), sm, c->stream, m,
-                           (const int64_t *)c->d_offsets.p, c->K, pobs, c->d_alpha_rm.p, c->d_logLk.p);
-    } else {
-        if ((rc = gen_set_smem(k_gen_forward<false>, sm)))
-            return rc;
-        hipLaunchKernelGGL(k_gen_forward<false>, dim3(c->K), dim3(GEN_TPB), sm, c->stream, m,
-                           (const int64_t *)c->d_offsets.p, c->K, pobs, c->d_alpha_rm.p, c->d_logLk.p);
-    }
-    BHMM_HIP(hipGetLastError());
+    sm += alds ? gen_a_bytes(c->n) : 0;
+    auto *k = alds ? k_gen_forward<true> : k_gen_forward<false>;
+    BHMM_HIP(launch(k, dim3(c->K), dim3(GEN_TPB), sm, c->stream, m, c->d_offsets.p, c->K, pobs, c->d_alpha_rm.p,
+                    c->d_logLk.p));
     return BHMM_OK;
 }
 
@@ -136,22 +112,9 @@ int gen_backward(bhmm_ctx *c, const double *A)
     size_t sm = gen_smem(c->n, 3, 1 + GEN_TPB);
     const bool alds = gen_a_in_lds(c->n, sm);
     sm += alds ? gen_a_bytes(c->n) : 0;
-#define BHMM_GEN_BETA(ALDSV)                                                                         \
-    do {                                                                                             \
-        if ((rc = gen_set_smem(k_gen_backward<EMIT_EXPL, false, ALDSV>, sm)))                        \
-            return rc;                                                                               \
-        hipLaunchKernelGGL((k_gen_backward<EMIT_EXPL, false, ALDSV>), dim3(c->K), dim3(GEN_TPB), sm, \
-                           c->stream, m, (const double *)c->d_gAt.p, (const int64_t *)c->d_offsets.p, \
-                           c->K, pobs, (const void *)nullptr, (const double *)nullptr,               \
-                           c->d_alpha_rm.p, (double *)nullptr, (double *)nullptr, (double *)nullptr, \
-                           (double *)nullptr, (double *)nullptr);                                    \
-    } while (0)
-    if (alds)
-        BHMM_GEN_BETA(true);
-    else
-        BHMM_GEN_BETA(false);
-#undef BHMM_GEN_BETA
-    BHMM_HIP(hipGetLastError());
+    auto *k = alds ? k_gen_backward<EMIT_EXPL, false, true> : k_gen_backward<EMIT_EXPL, false, false>;
+    BHMM_HIP(launch(k, dim3(c->K), dim3(GEN_TPB), sm, c->stream, m, c->d_gAt.p, c->d_offsets.p, c->K, pobs, nullptr,
+                    nullptr, c->d_alpha_rm.p, nullptr, nullptr, nullptr, nullptr, nullptr));
     return BHMM_OK;
 }
 
@@ -192,52 +155,22 @@ int gen_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par0
     const bool alds = gen_a_in_lds(n, sm);
     sm += alds ? gen_a_bytes(n) : 0;
     double *gam = sg ? c->d_gamma_ci.p : nullptr;
-#define BHMM_GEN_BWD2(KINDV, ALDSV)                                                                  \
-    do {                                                                                             \
-        if ((rc = gen_set_smem(k_gen_backward<KINDV, true, ALDSV>, sm)))                             \
-            return rc;                                                                               \
-        hipLaunchKernelGGL((k_gen_backward<KINDV, true, ALDSV>), dim3(K), dim3(GEN_TPB), sm,         \
-                           c->stream, m, (const double *)c->d_gAt.p, (const int64_t *)c->d_offsets.p, \
-                           K, pobs, (const void *)c->d_obs_rm.p, (const double *)c->d_alpha_rm.p,    \
-                           (double *)nullptr, c->d_gW.p, gam, c->d_gpart.p, c->d_gamma0.p,           \
-                           c->d_gsym.p);                                                             \
-    } while (0)
-#define BHMM_GEN_BWD(KINDV)                                                                          \
-    do {                                                                                             \
-        if (alds)                                                                                    \
-            BHMM_GEN_BWD2(KINDV, true);                                                              \
-        else                                                                                         \
-            BHMM_GEN_BWD2(KINDV, false);                                                             \
-    } while (0)
-    if (c->kind == EMIT_GAUSS)
-        BHMM_GEN_BWD(EMIT_GAUSS);
-    else if (c->kind == EMIT_DISC)
-        BHMM_GEN_BWD(EMIT_DISC);
-    else
-        BHMM_GEN_BWD(EMIT_EXPL);
-#undef BHMM_GEN_BWD
-#undef BHMM_GEN_BWD2
-    BHMM_HIP(hipGetLastError());
+    auto *kb = c->kind == EMIT_GAUSS
+                   ? (alds ? k_gen_backward<EMIT_GAUSS, true, true> : k_gen_backward<EMIT_GAUSS, true, false>)
+               : c->kind == EMIT_DISC
+                   ? (alds ? k_gen_backward<EMIT_DISC, true, true> : k_gen_backward<EMIT_DISC, true, false>)
+                   : (alds ? k_gen_backward<EMIT_EXPL, true, true> : k_gen_backward<EMIT_EXPL, true, false>);
+    BHMM_HIP(launch(kb, dim3(K), dim3(GEN_TPB), sm, c->stream, m, c->d_gAt.p, c->d_offsets.p, K, pobs, c->d_obs_rm.p,
+                    c->d_alpha_rm.p, nullptr, c->d_gW.p, gam, c->d_gpart.p, c->d_gamma0.p, c->d_gsym.p));
     const int tiles = (n + 31) / 32;
-    hipLaunchKernelGGL(k_gen_xi_gemm, dim3(tiles * tiles, nsplit), dim3(256), 0, c->stream,
-                       (const double *)c->d_alpha_rm.p, (const double *)c->d_gW.p, c->total, n, nsplit,
-                       c->d_gxipart.p);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_gen_xi_gemm, dim3(tiles * tiles, nsplit), dim3(256), 0, c->stream, c->d_alpha_rm.p, c->d_gW.p,
+                    c->total, n, nsplit, c->d_gxipart.p));
     BHMM_HIP(hipEventRecord(c->ev[3], c->stream));
-    const dim3 fg(256), fb(256);
-#define BHMM_GEN_FIN(KINDV)                                                                          \
-    hipLaunchKernelGGL((k_gen_finalize<KINDV>), fg, fb, 0, c->stream, m, K, nsplit,                  \
-                       (const double *)c->d_gxipart.p, (const double *)c->d_gpart.p,                 \
-                       (const double *)c->d_gamma0.p, (const double *)c->d_logLk.p,                  \
-                       (const double *)c->d_gsym.p, stats_dev)
-    if (c->kind == EMIT_GAUSS)
-        BHMM_GEN_FIN(EMIT_GAUSS);
-    else if (c->kind == EMIT_DISC)
-        BHMM_GEN_FIN(EMIT_DISC);
-    else
-        BHMM_GEN_FIN(EMIT_EXPL);
-#undef BHMM_GEN_FIN
-    BHMM_HIP(hipGetLastError());
+    auto *kf = c->kind == EMIT_GAUSS ? k_gen_finalize<EMIT_GAUSS>
+               : c->kind == EMIT_DISC ? k_gen_finalize<EMIT_DISC>
+                                      : k_gen_finalize<EMIT_EXPL>;
+    BHMM_HIP(launch(kf, dim3(256), dim3(256), 0, c->stream, m, K, nsplit, c->d_gxipart.p, c->d_gpart.p, c->d_gamma0.p,
+                    c->d_logLk.p, c->d_gsym.p, stats_dev));
     BHMM_HIP(hipEventRecord(c->ev[4], c->stream));
     c->ev_pending = true;
     return BHMM_OK;
@@ -270,8 +203,7 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
         bool done = false;
         uint8_t *ptr8 = reinterpret_cast<uint8_t *>(c->d_scratch.p);
         const size_t smv = (size_t)(128 * GVS_PITCH + 8 * 128) * sizeof(double);
-        if ((rc = gen_set_smem(k_gen_viterbi_seg<false>, smv)) || (rc = gen_set_smem(k_gen_viterbi_seg<true>, smv)) ||
-            (rc = c->d_specres.ensure(4)))
+        if ((rc = c->d_specres.ensure(4)))
             return rc;
         if (!c->h_specres)
             BHMM_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_specres), 4 * sizeof(unsigned int),
@@ -298,7 +230,8 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
         int64_t maxT = 0;
         const size_t smm = (size_t)n * (n | 1) * sizeof(double); // (odd pitch, k_vit_margin)
         if (c->opt.vit_margin && c->d_gW.ensure((size_t)c->total * n) == BHMM_OK &&
-            gen_set_smem(k_vit_margin<int32_t, 2>, smm) == BHMM_OK && gen_set_smem(k_vit_margin<uint8_t, 2>, smm) == BHMM_OK) {
+            allow_lds(k_vit_margin<int32_t, 2>, smm) == hipSuccess &&
+            allow_lds(k_vit_margin<uint8_t, 2>, smm) == hipSuccess) {
             vall = c->d_gW.p;
             for (int k = 0; k < K; ++k)
                 maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
@@ -314,18 +247,14 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
             int rcw;
             if ((rcw = c->d_vmaps.ensure((size_t)sg.nseg * 128)) || (rcw = c->d_vend.ensure((size_t)sg.nseg)))
                 return rcw;
-            hipLaunchKernelGGL((k_wide_vit_walk<false, uint8_t, 2>), dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n,
-                               (const uint8_t *)ptr8, c->d_vmaps.p, (const uint8_t *)nullptr, (uint8_t *)nullptr);
-            hipLaunchKernelGGL(k_wide_vit_stitch, dim3((K + 63) / 64), dim3(64), 0, c->stream,
-                               (const int32_t *)c->pplan_buf[0].traj0.p, K, (const uint8_t *)c->d_vmaps.p, 128,
-                               (const int32_t *)last, c->d_vend.p);
-            if (out_fmt == 0)
-                hipLaunchKernelGGL((k_wide_vit_walk<true, int32_t, 2>), dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n,
-                                   (const uint8_t *)ptr8, (uint8_t *)nullptr, (const uint8_t *)c->d_vend.p, path);
-            else
-                hipLaunchKernelGGL((k_wide_vit_walk<true, uint8_t, 2>), dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n,
-                                   (const uint8_t *)ptr8, (uint8_t *)nullptr, (const uint8_t *)c->d_vend.p, p8);
-            BHMM_HIP(hipGetLastError());
+            BHMM_HIP(launch(k_wide_vit_walk<false, uint8_t, 2>, dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n, ptr8,
+                            c->d_vmaps.p, nullptr, nullptr));
+            BHMM_HIP(launch(k_wide_vit_stitch, dim3((K + 63) / 64), dim3(64), 0, c->stream, c->pplan_buf[0].traj0.p, K,
+                            c->d_vmaps.p, 128, last, c->d_vend.p));
+            auto walk = [&](auto *k, auto *out) {
+                return launch(k, dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n, ptr8, nullptr, c->d_vend.p, out);
+            };
+            BHMM_HIP(out_fmt == 0 ? walk(k_wide_vit_walk<true, int32_t, 2>, path) : walk(k_wide_vit_walk<true, uint8_t, 2>, p8));
             return BHMM_OK;
         };
         for (int attempt = 0; attempt < 2 && !done; ++attempt) {
@@ -349,18 +278,12 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
             for (; round <= 12; ++round) {
                 BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
                 lds_poison(c->stream);
-                if (round == 0)
-                    hipLaunchKernelGGL(k_gen_viterbi_seg<false>, sgrid, sblk, smv, c->stream, m, (const int64_t *)c->d_offsets.p,
-                                       sg, pobs, ptr8, last, c->d_aentry.p, c->d_aexit.p, c->d_vckpt.p,
-                                       (const uint8_t *)c->d_vflag.p, vall);
-                else
-                    hipLaunchKernelGGL(k_gen_viterbi_seg<true>, sgrid, sblk, smv, c->stream, m, (const int64_t *)c->d_offsets.p,
-                                       sg, pobs, ptr8, last, c->d_aentry.p, c->d_aexit.p, c->d_vckpt.p,
-                                       (const uint8_t *)c->d_vflag.p);
-                hipLaunchKernelGGL((k_wide_vit_check<128>), dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
-                                   c->d_aentry.p, (const double *)c->d_aexit.p, c->d_vflag.p, c->d_specres.p,
-                                   (round == 0 && vall) ? vm_tol : 0.0);
-                BHMM_HIP(hipGetLastError());
+                auto *kv = round == 0 ? k_gen_viterbi_seg<false> : k_gen_viterbi_seg<true>;
+                BHMM_HIP(launch(kv, sgrid, sblk, smv, c->stream, m, c->d_offsets.p, sg, pobs, ptr8, last, c->d_aentry.p,
+                                c->d_aexit.p, c->d_vckpt.p, c->d_vflag.p, round == 0 ? vall : nullptr, 0.0, nullptr));
+                BHMM_HIP(launch(k_wide_vit_check<128>, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
+                                c->d_aentry.p, c->d_aexit.p, c->d_vflag.p, c->d_specres.p,
+                                (round == 0 && vall) ? vm_tol : 0.0));
                 BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
                                         hipMemcpyDeviceToHost, c->stream));
                 BHMM_HIP(hipStreamSynchronize(c->stream));
@@ -377,10 +300,9 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
                     mended = true;
                     BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
                     lds_poison(c->stream);
-                    hipLaunchKernelGGL(k_gen_viterbi_seg<true>, sgrid, sblk, smv, c->stream, m, (const int64_t *)c->d_offsets.p,
-                                       sg, pobs, ptr8, last, c->d_aentry.p, c->d_aexit.p, c->d_vckpt.p,
-                                       (const uint8_t *)c->d_vflag.p + sg.nseg, vall, vm_tol, c->d_specres.p + 1);
-                    BHMM_HIP(hipGetLastError());
+                    BHMM_HIP(launch(k_gen_viterbi_seg<true>, sgrid, sblk, smv, c->stream, m, c->d_offsets.p, sg, pobs, ptr8,
+                                    last, c->d_aentry.p, c->d_aexit.p, c->d_vckpt.p, c->d_vflag.p + sg.nseg, vall, vm_tol,
+                                    c->d_specres.p + 1));
                     unsigned int notmet = 0;
                     BHMM_HIP(hipMemcpyAsync(&notmet, c->d_specres.p + 1, sizeof(unsigned int), hipMemcpyDeviceToHost,
                                             c->stream));
@@ -399,13 +321,10 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
                         return rc;
                     BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
                     const dim3 mgrid(sg.nseg, (unsigned)((c->ds.pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
-                    if (out_fmt == 0)
-                        hipLaunchKernelGGL((k_vit_margin<int32_t, 2>), mgrid, dim3(256), smm, c->stream, m.A, n, off, sg,
-                                           (const double *)vall, (const int32_t *)path, margin, c->d_specres.p);
-                    else
-                        hipLaunchKernelGGL((k_vit_margin<uint8_t, 2>), mgrid, dim3(256), smm, c->stream, m.A, n, off, sg,
-                                           (const double *)vall, (const uint8_t *)p8, margin, c->d_specres.p);
-                    BHMM_HIP(hipGetLastError());
+                    auto margins = [&](auto *k, auto *p) {
+                        return launch(k, mgrid, dim3(256), smm, c->stream, m.A, n, off, sg, vall, p, margin, c->d_specres.p);
+                    };
+                    BHMM_HIP(out_fmt == 0 ? margins(k_vit_margin<int32_t, 2>, path) : margins(k_vit_margin<uint8_t, 2>, p8));
                     BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
                                             hipMemcpyDeviceToHost, c->stream));
                     BHMM_HIP(hipStreamSynchronize(c->stream));
@@ -493,32 +412,25 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
             double *vall = c->d_gW.p;
             BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
             lds_poison(c->stream);
-#define BHMM_GVR(SV)                                                                                                  \
-    hipLaunchKernelGGL((k_gen_viterbi_rows<GVR_ROWS, SV>), dim3((sg.nseg + GVR_ROWS - 1) / GVR_ROWS), dim3(256 * SV), smr, \
-                       c->stream, m, off, sg, pobs, ptr8, last, c->d_aentry.p, c->d_aexit.p, vall)
-            if (GVR_S == 1)
-                BHMM_GVR(1);
-            else if (GVR_S == 2)
-                BHMM_GVR(2);
-            else
-                BHMM_GVR(4);
-#undef BHMM_GVR
-            hipLaunchKernelGGL((k_wide_vit_check<256>), dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
-                               c->d_aentry.p, (const double *)c->d_aexit.p, c->d_vflag.p, c->d_specres.p, vm_tol);
+            auto *kr = GVR_S == 1   ? k_gen_viterbi_rows<GVR_ROWS, 1>
+                       : GVR_S == 2 ? k_gen_viterbi_rows<GVR_ROWS, 2>
+                                    : k_gen_viterbi_rows<GVR_ROWS, 4>;
+            const dim3 rgrid((sg.nseg + GVR_ROWS - 1) / GVR_ROWS), rblk(256 * GVR_S);
+            BHMM_HIP(launch(kr, rgrid, rblk, smr, c->stream, m, off, sg, pobs, ptr8, last, c->d_aentry.p, c->d_aexit.p,
+                            vall, nullptr, 0.0, nullptr));
+            BHMM_HIP(launch(k_wide_vit_check<256>, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
+                            c->d_aentry.p, c->d_aexit.p, c->d_vflag.p, c->d_specres.p, vm_tol));
             // the back-trace of this pass (needed either way)
             auto rows_walks = [&]() -> int {
-                hipLaunchKernelGGL((k_wide_vit_walk<false, uint8_t, 4>), dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n,
-                                   (const uint8_t *)ptr8, c->d_vmaps.p, (const uint8_t *)nullptr, (uint8_t *)nullptr);
-                hipLaunchKernelGGL(k_wide_vit_stitch, dim3((K + 63) / 64), dim3(64), 0, c->stream,
-                                   (const int32_t *)c->pplan_buf[0].traj0.p, K, (const uint8_t *)c->d_vmaps.p, 256,
-                                   (const int32_t *)last, c->d_vend.p);
-                if (out_fmt == 0)
-                    hipLaunchKernelGGL((k_wide_vit_walk<true, int32_t, 4>), dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n,
-                                       (const uint8_t *)ptr8, (uint8_t *)nullptr, (const uint8_t *)c->d_vend.p, path);
-                else
-                    hipLaunchKernelGGL((k_wide_vit_walk<true, uint8_t, 4>), dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n,
-                                       (const uint8_t *)ptr8, (uint8_t *)nullptr, (const uint8_t *)c->d_vend.p, p8);
-                BHMM_HIP(hipGetLastError());
+                BHMM_HIP(launch(k_wide_vit_walk<false, uint8_t, 4>, dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n,
+                                ptr8, c->d_vmaps.p, nullptr, nullptr));
+                BHMM_HIP(launch(k_wide_vit_stitch, dim3((K + 63) / 64), dim3(64), 0, c->stream, c->pplan_buf[0].traj0.p,
+                                K, c->d_vmaps.p, 256, last, c->d_vend.p));
+                auto walk = [&](auto *k, auto *out) {
+                    return launch(k, dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n, ptr8, nullptr, c->d_vend.p, out);
+                };
+                BHMM_HIP(out_fmt == 0 ? walk(k_wide_vit_walk<true, int32_t, 4>, path)
+                                      : walk(k_wide_vit_walk<true, uint8_t, 4>, p8));
                 return BHMM_OK;
             };
             if ((rc = rows_walks()))
@@ -535,18 +447,11 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
                 // predecessors' vectors run again up to a vector the first pass kept; then the back-trace again
                 BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
                 lds_poison(c->stream);
-#define BHMM_GVR_MEND(SV)                                                                                                    \
-    hipLaunchKernelGGL((k_gen_viterbi_rows<GVR_ROWS, SV, true>), dim3((sg.nseg + GVR_ROWS - 1) / GVR_ROWS), dim3(256 * SV), smr, \
-                       c->stream, m, off, sg, pobs, ptr8, last, c->d_aentry.p, c->d_aexit.p, vall,                           \
-                       (const uint8_t *)c->d_vflag.p + sg.nseg, vm_tol, c->d_specres.p + 1)
-                if (GVR_S == 1)
-                    BHMM_GVR_MEND(1);
-                else if (GVR_S == 2)
-                    BHMM_GVR_MEND(2);
-                else
-                    BHMM_GVR_MEND(4);
-#undef BHMM_GVR_MEND
-                BHMM_HIP(hipGetLastError());
+                auto *km = GVR_S == 1   ? k_gen_viterbi_rows<GVR_ROWS, 1, true>
+                           : GVR_S == 2 ? k_gen_viterbi_rows<GVR_ROWS, 2, true>
+                                        : k_gen_viterbi_rows<GVR_ROWS, 4, true>;
+                BHMM_HIP(launch(km, rgrid, rblk, smr, c->stream, m, off, sg, pobs, ptr8, last, c->d_aentry.p, c->d_aexit.p,
+                                vall, c->d_vflag.p + sg.nseg, vm_tol, c->d_specres.p + 1));
                 unsigned int notmet = 0;
                 BHMM_HIP(hipMemcpyAsync(&notmet, c->d_specres.p + 1, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
                 BHMM_HIP(hipStreamSynchronize(c->stream));
@@ -563,15 +468,11 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
                 const double margin = std::max(1e-10, 16.0 * (2e-15 * (double)maxT + vm_tol * maxseg));
                 BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
                 const dim3 mgrid(sg.nseg, (unsigned)((c->ds.pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
-                if (out_fmt == 0)
-                    hipLaunchKernelGGL((k_vit_margin<int32_t, 4, false>), mgrid, dim3(256), 0, c->stream,
-                                       (const double *)c->d_gAt.p, n, off, sg, (const double *)vall, (const int32_t *)path,
-                                       margin, c->d_specres.p);
-                else
-                    hipLaunchKernelGGL((k_vit_margin<uint8_t, 4, false>), mgrid, dim3(256), 0, c->stream,
-                                       (const double *)c->d_gAt.p, n, off, sg, (const double *)vall, (const uint8_t *)p8,
-                                       margin, c->d_specres.p);
-                BHMM_HIP(hipGetLastError());
+                auto margins = [&](auto *k, auto *p) {
+                    return launch(k, mgrid, dim3(256), 0, c->stream, c->d_gAt.p, n, off, sg, vall, p, margin, c->d_specres.p);
+                };
+                BHMM_HIP(out_fmt == 0 ? margins(k_vit_margin<int32_t, 4, false>, path)
+                                      : margins(k_vit_margin<uint8_t, 4, false>, p8));
                 BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost,
                                         c->stream));
                 BHMM_HIP(hipStreamSynchronize(c->stream));
@@ -603,33 +504,18 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
         }
     }
     size_t sm = gen_smem(n, 2, 2);
-    if (gen_a_in_lds(n, sm)) {
-        sm += gen_a_bytes(n);
-        if ((rc = gen_set_smem(k_gen_viterbi_fwd<true>, sm)))
-            return rc;
-        hipLaunchKernelGGL(k_gen_viterbi_fwd<true>, dim3(K), dim3(GEN_TPB), sm, c->stream, m,
-                           (const int64_t *)c->d_offsets.p, K, pobs, ptr, last);
-    } else {
-        if ((rc = gen_set_smem(k_gen_viterbi_fwd<false>, sm)))
-            return rc;
-        hipLaunchKernelGGL(k_gen_viterbi_fwd<false>, dim3(K), dim3(GEN_TPB), sm, c->stream, m,
-                           (const int64_t *)c->d_offsets.p, K, pobs, ptr, last);
-    }
-    BHMM_HIP(hipGetLastError());
+    const bool alds = gen_a_in_lds(n, sm);
+    sm += alds ? gen_a_bytes(n) : 0;
+    auto *kvf = alds ? k_gen_viterbi_fwd<true> : k_gen_viterbi_fwd<false>;
+    BHMM_HIP(launch(kvf, dim3(K), dim3(GEN_TPB), sm, c->stream, m, c->d_offsets.p, K, pobs, ptr, last));
     const dim3 tg((K + 63) / 64), tb(64);
     if (out_fmt == 0) {
-        hipLaunchKernelGGL(k_gen_viterbi_trace<int32_t>, tg, tb, 0, c->stream,
-                           (const int64_t *)c->d_offsets.p, K, n, (const uint16_t *)ptr,
-                           (const int32_t *)last, path);
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_gen_viterbi_trace<int32_t>, tg, tb, 0, c->stream, c->d_offsets.p, K, n, ptr, last, path));
         BHMM_HIP(hipMemcpyAsync(paths_out, path, (size_t)c->total * sizeof(int32_t),
                                 hipMemcpyDeviceToHost, c->stream));
     } else {
         uint8_t *p8 = out_fmt == 2 ? static_cast<uint8_t *>(paths_out) : reinterpret_cast<uint8_t *>(path);
-        hipLaunchKernelGGL(k_gen_viterbi_trace<uint8_t>, tg, tb, 0, c->stream,
-                           (const int64_t *)c->d_offsets.p, K, n, (const uint16_t *)ptr,
-                           (const int32_t *)last, p8);
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_gen_viterbi_trace<uint8_t>, tg, tb, 0, c->stream, c->d_offsets.p, K, n, ptr, last, p8));
         if (out_fmt == 1)
             BHMM_HIP(hipMemcpyAsync(paths_out, p8, (size_t)c->total, hipMemcpyDeviceToHost, c->stream));
     }
@@ -707,33 +593,23 @@ int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double 
                 BHMM_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_specres), 4 * sizeof(unsigned int),
                                        hipHostMallocDefault));
             const dim3 sgrid((sg.nseg + 3) / 4), sblk(256);
-#define BHMM_GSS(SPLV, FIXV)                                                                            \
-    hipLaunchKernelGGL((k_gen_sample_seg<SPLV, FIXV>), sgrid, sblk, 0, c->stream, m,                    \
-                       (const double *)c->d_gAt.p, (const int64_t *)c->d_offsets.p, sg,                 \
-                       (const double *)c->d_alpha_rm.p, (const double *)udev, seed,                     \
-                       (const int64_t *)c->d_soff.p, path, status, c->d_sentry.p, c->d_sexit.p,         \
-                       (const uint8_t *)c->d_vflag.p, watch)
-#define BHMM_GSS_SPL(FIXV)       \
-    do {                         \
-        if (n <= 128)            \
-            BHMM_GSS(2, FIXV);   \
-        else if (n <= 256)       \
-            BHMM_GSS(4, FIXV);   \
-        else                     \
-            BHMM_GSS(8, FIXV);   \
-    } while (0)
+            // (first round, then the rounds that draw the flagged segments again)
+            auto *kfirst = n <= 128   ? k_gen_sample_seg<2, false>
+                           : n <= 256 ? k_gen_sample_seg<4, false>
+                                      : k_gen_sample_seg<8, false>;
+            auto *kfix = n <= 128   ? k_gen_sample_seg<2, true>
+                         : n <= 256 ? k_gen_sample_seg<4, true>
+                                    : k_gen_sample_seg<8, true>;
             const int max_rounds = 16;
             int round = 0;
             for (; round <= max_rounds; ++round) {
                 BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
                 lds_poison(c->stream);
-                if (round == 0)
-                    BHMM_GSS_SPL(false);
-                else
-                    BHMM_GSS_SPL(true);
-                hipLaunchKernelGGL(k_wide_smp_check, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
-                                   c->d_sentry.p, (const int32_t *)c->d_sexit.p, c->d_vflag.p, c->d_specres.p);
-                BHMM_HIP(hipGetLastError());
+                BHMM_HIP(launch(round == 0 ? kfirst : kfix, sgrid, sblk, 0, c->stream, m, c->d_gAt.p, c->d_offsets.p, sg,
+                                c->d_alpha_rm.p, udev, seed, c->d_soff.p, path, status, c->d_sentry.p, c->d_sexit.p,
+                                c->d_vflag.p, watch));
+                BHMM_HIP(launch(k_wide_smp_check, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg, c->d_sentry.p,
+                                c->d_sexit.p, c->d_vflag.p, c->d_specres.p));
                 BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
                                         hipMemcpyDeviceToHost, c->stream));
                 BHMM_HIP(hipMemcpyAsync(&c->h_specres[0], status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -743,8 +619,6 @@ int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double 
                 if (c->h_specres[3] == 0)
                     break;
             }
-#undef BHMM_GSS_SPL
-#undef BHMM_GSS
             c->last.smp_seg_rounds = round;
             // (a draw that found no state may belong to a segment that was drawn again afterwards:
             // the serial kernel decides such a call)
@@ -785,23 +659,13 @@ int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double 
             }
         }
     }
-    if (seg_done) {
-        ;
-    } else if (gen_a_in_lds(n, sm)) {
-        sm += gen_a_bytes(n);
-        if ((rc = gen_set_smem(k_gen_sample<true>, sm)))
-            return rc;
-        hipLaunchKernelGGL(k_gen_sample<true>, dim3(K), dim3(GEN_TPB), sm, c->stream, m,
-                           (const int64_t *)c->d_offsets.p, K, (const double *)c->d_alpha_rm.p,
-                           (const double *)udev, seed, (const int64_t *)c->d_soff.p, path, status);
-    } else {
-        if ((rc = gen_set_smem(k_gen_sample<false>, sm)))
-            return rc;
-        hipLaunchKernelGGL(k_gen_sample<false>, dim3(K), dim3(GEN_TPB), sm, c->stream, m,
-                           (const int64_t *)c->d_offsets.p, K, (const double *)c->d_alpha_rm.p,
-                           (const double *)udev, seed, (const int64_t *)c->d_soff.p, path, status);
+    if (!seg_done) {
+        const bool alds = gen_a_in_lds(n, sm);
+        sm += alds ? gen_a_bytes(n) : 0;
+        auto *ks = alds ? k_gen_sample<true> : k_gen_sample<false>;
+        BHMM_HIP(launch(ks, dim3(K), dim3(GEN_TPB), sm, c->stream, m, c->d_offsets.p, K, c->d_alpha_rm.p, udev, seed,
+                        c->d_soff.p, path, status));
     }
-    BHMM_HIP(hipGetLastError());
     int hstatus = 0;
     BHMM_HIP(hipMemcpyAsync(&hstatus, status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     BHMM_HIP(hipStreamSynchronize(c->stream));
@@ -811,23 +675,15 @@ int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double 
     }
     const void *obs = c->d_obs_rm.p;
     const dim3 pg(256), pb(256);
-#define BHMM_GEN_PS(KINDV)                                                                          \
-    do {                                                                                            \
-        hipLaunchKernelGGL((k_gen_path_stats<KINDV>), dim3(K, GEN_PS_SLABS), dim3(GEN_TPB), 0, c->stream, m,      \
-                           (const int64_t *)c->d_offsets.p, K, obs, (const int32_t *)path, cnt,     \
-                           epart, symcnt);                                                          \
-        hipLaunchKernelGGL((k_gen_pack_path_stats<KINDV>), pg, pb, 0, c->stream, m, K,              \
-                           (const unsigned long long *)cnt, (const double *)epart,                  \
-                           (const unsigned long long *)symcnt, stats_dev ? stats_dev : packed);     \
-    } while (0)
-    if (c->kind == EMIT_GAUSS)
-        BHMM_GEN_PS(EMIT_GAUSS);
-    else if (c->kind == EMIT_DISC)
-        BHMM_GEN_PS(EMIT_DISC);
-    else
-        BHMM_GEN_PS(EMIT_EXPL);
-#undef BHMM_GEN_PS
-    BHMM_HIP(hipGetLastError());
+    auto *kps = c->kind == EMIT_GAUSS ? k_gen_path_stats<EMIT_GAUSS>
+                : c->kind == EMIT_DISC ? k_gen_path_stats<EMIT_DISC>
+                                       : k_gen_path_stats<EMIT_EXPL>;
+    auto *kpack = c->kind == EMIT_GAUSS ? k_gen_pack_path_stats<EMIT_GAUSS>
+                  : c->kind == EMIT_DISC ? k_gen_pack_path_stats<EMIT_DISC>
+                                         : k_gen_pack_path_stats<EMIT_EXPL>;
+    BHMM_HIP(launch(kps, dim3(K, GEN_PS_SLABS), dim3(GEN_TPB), 0, c->stream, m, c->d_offsets.p, K, obs, path, cnt, epart,
+                    symcnt));
+    BHMM_HIP(launch(kpack, pg, pb, 0, c->stream, m, K, cnt, epart, symcnt, stats_dev ? stats_dev : packed));
     std::vector<double> hp;
     if (!stats_dev && (counts || n0 || emis)) {
         hp.resize(nstat + esz);
@@ -879,14 +735,10 @@ int gen_transition_counts(double *C, const double *A, const double *pobs, const 
     BHMM_HIP(hipMemcpy(da, alpha, rows * sizeof(double), hipMemcpyHostToDevice));
     BHMM_HIP(hipMemcpy(db, beta, rows * sizeof(double), hipMemcpyHostToDevice));
     BHMM_HIP(hipMemcpy(dA, A, nn * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_gen_transpose, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, 0,
-                       (const double *)dA, N, dAt);
+    BHMM_HIP(launch(k_gen_transpose, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, 0, dA, N, dAt));
     const size_t sm = ((size_t)N + GEN_TPB) * sizeof(double);
-    hipLaunchKernelGGL(k_gen_w_rows, dim3((unsigned)T), dim3(GEN_TPB), sm, 0, (const double *)dAt, N, T,
-                       (const double *)dp, (const double *)da, (const double *)db, dW);
-    hipLaunchKernelGGL(k_gen_xi_gemm, dim3(tiles * tiles, nsplit), dim3(256), 0, 0, (const double *)da,
-                       (const double *)dW, T, N, nsplit, dpart);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_gen_w_rows, dim3((unsigned)T), dim3(GEN_TPB), sm, 0, dAt, N, T, dp, da, db, dW));
+    BHMM_HIP(launch(k_gen_xi_gemm, dim3(tiles * tiles, nsplit), dim3(256), 0, 0, da, dW, T, N, nsplit, dpart));
     std::vector<double> hpart((size_t)nsplit * nn);
     BHMM_HIP(hipMemcpy(hpart.data(), dpart, hpart.size() * sizeof(double), hipMemcpyDeviceToHost));
     (void)dC;
@@ -932,13 +784,8 @@ int gen_sample_path(int32_t *path, const double *alpha, const double *A, const d
     m.A = dA;
     m.n = N;
     const size_t sm = gen_smem(N, 2, 4);
-    int rc = gen_set_smem(k_gen_sample<false>, sm);
-    if (rc)
-        return rc;
-    hipLaunchKernelGGL(k_gen_sample<false>, dim3(1), dim3(GEN_TPB), sm, 0, m, (const int64_t *)doff, 1,
-                       (const double *)da, (const double *)du, (uint64_t)0, (const int64_t *)nullptr,
-                       dpath, status);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_gen_sample<false>, dim3(1), dim3(GEN_TPB), sm, 0, m, doff, 1, da, du, (uint64_t)0, nullptr, dpath,
+                    status));
     int hstatus = 0;
     BHMM_HIP(hipMemcpy(&hstatus, status, sizeof(int), hipMemcpyDeviceToHost));
     if (hstatus) {

@@ -12,6 +12,7 @@
 
 #include "host_common.hpp"
 #include "host_internal.hpp"
+#include "launch.hpp"
 #include "plan.hpp"
 #include "path_kernels.hpp"
 #include "draw_verify.hpp"
@@ -69,10 +70,8 @@ int draw_verify_run(bhmm_ctx *c, const double *A, const double *pi, const double
     unsigned int *res = reinterpret_cast<unsigned int *>(c->d_dv.p);
     BHMM_HIP(hipMemsetAsync(res + 1, 0, 12, c->stream)); // (the three result words; rare path)
     const size_t sm = (4 * (size_t)n + 8) * sizeof(double);
-    hipLaunchKernelGGL(k_draw_verify, dim3(count), dim3(256), sm, c->stream,
-                       reinterpret_cast<const DrawEvent *>(c->d_dv.p + 16), (int)count, (const double *)md, n, c->M,
-                       c->kind, (const void *)c->d_obs_rm.p, (const int64_t *)c->d_offsets.p, Wlong, thr, res + 1);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_draw_verify, dim3(count), dim3(256), sm, c->stream, reinterpret_cast<const DrawEvent *>(c->d_dv.p + 16),
+                    (int)count, md, n, c->M, c->kind, c->d_obs_rm.p, c->d_offsets.p, Wlong, thr, res + 1));
     unsigned int h[4] = {0, 0, 0, 0};
     BHMM_HIP(hipMemcpyAsync(h, res, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     BHMM_HIP(hipStreamSynchronize(c->stream));
@@ -212,58 +211,26 @@ int sample_run(bhmm_ctx *c, const double *A, const double *pi, const double *par
         const double *wsd = c->d_ws.p, *Btd = c->d_Bt.p;
         // fp32 copies of the alpha rows, if the forward pass that just ran wrote them
         const float *r32 = c->rows32_valid ? c->d_ws32.p : nullptr;
-#define BHMM_SMP_MAPS(KINDV, R32V)                                                                         \
-    hipLaunchKernelGGL((k_smp_maps<N, KINDV, R32V>), dim3(nblk), dim3(BLOCK), 0, c->stream, m, chs, offd, soffd, \
-                       wsd, r32, obs_ci, Btd, (const double *)udev, seed, P, fmap, status, dmark, nib, W8, Gp64, \
-                       gw, Lp, watch)
-        if (c->kind == EMIT_GAUSS) {
-            if (r32)
-                BHMM_SMP_MAPS(EMIT_GAUSS, true);
-            else
-                BHMM_SMP_MAPS(EMIT_GAUSS, false);
-        } else if (c->kind == EMIT_DISC) {
-            if (r32)
-                BHMM_SMP_MAPS(EMIT_DISC, true);
-            else
-                BHMM_SMP_MAPS(EMIT_DISC, false);
-        } else {
-            if (r32)
-                BHMM_SMP_MAPS(EMIT_EXPL, true);
-            else
-                BHMM_SMP_MAPS(EMIT_EXPL, false);
-        }
-#undef BHMM_SMP_MAPS
-        BHMM_HIP(hipGetLastError());
+        auto *km = c->kind == EMIT_GAUSS ? (r32 ? k_smp_maps<N, EMIT_GAUSS, true> : k_smp_maps<N, EMIT_GAUSS, false>)
+                   : c->kind == EMIT_DISC ? (r32 ? k_smp_maps<N, EMIT_DISC, true> : k_smp_maps<N, EMIT_DISC, false>)
+                                          : (r32 ? k_smp_maps<N, EMIT_EXPL, true> : k_smp_maps<N, EMIT_EXPL, false>);
+        BHMM_HIP(launch(km, dim3(nblk), dim3(BLOCK), 0, c->stream, m, chs, offd, soffd, wsd, r32, obs_ci, Btd, udev, seed,
+                        P, fmap, status, dmark, nib, W8, Gp64, gw, Lp, watch));
         if ((int64_t)c->G * P >= (int64_t)32 * K) // long chains: one wavefront per trajectory
-            hipLaunchKernelGGL(k_smp_stitch, dim3(K), dim3(64), 0, c->stream,
-                               (const int32_t *)c->d_traj_c0.p, K, P, (const uint32_t *)fmap, nstate);
+            BHMM_HIP(launch(k_smp_stitch, dim3(K), dim3(64), 0, c->stream, c->d_traj_c0.p, K, P, fmap, nstate, nullptr));
         else
-            hipLaunchKernelGGL(k_smp_stitch_serial, dim3((K + SMP_STITCH_TPB - 1) / SMP_STITCH_TPB),
-                               dim3(64), 0, c->stream, (const int32_t *)c->d_traj_c0.p, K, P,
-                               (const uint32_t *)fmap, nstate);
-        BHMM_HIP(hipGetLastError());
+            BHMM_HIP(launch(k_smp_stitch_serial, dim3((K + SMP_STITCH_TPB - 1) / SMP_STITCH_TPB), dim3(64), 0, c->stream,
+                            c->d_traj_c0.p, K, P, fmap, nstate, nullptr));
         const int32_t *ns = nstate, *dmk = dmark;
         const uint32_t *nb = nib, *gwc = gw;
-        if (c->kind == EMIT_GAUSS)
-            hipLaunchKernelGGL((k_smp_apply<N, EMIT_GAUSS>), dim3(nblk), dim3(BLOCK), 0, c->stream, m,
-                               chs, offd, obs_ci, P, ns, path, cnt, epart, dmk, nb, W8, Gp64, gwc, Lp, status);
-        else if (c->kind == EMIT_DISC) {
-            const size_t smd = bigM ? 0 : (size_t)c->M * N * sizeof(double);
-            if (smd > 64 * 1024)
-                BHMM_HIP(hipFuncSetAttribute((const void *)(k_smp_apply<N, EMIT_DISC>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smd));
-            hipLaunchKernelGGL((k_smp_apply<N, EMIT_DISC>), dim3(nblk), dim3(BLOCK), smd, c->stream, m,
-                               chs, offd, obs_ci, P, ns, path, cnt, epart, dmk, nb, W8, Gp64, gwc, Lp, status);
-        }
-        else
-            hipLaunchKernelGGL((k_smp_apply<N, EMIT_EXPL>), dim3(nblk), dim3(BLOCK), 0, c->stream, m,
-                               chs, offd, obs_ci, P, ns, path, cnt, epart, dmk, nb, W8, Gp64, gwc, Lp, status);
-        BHMM_HIP(hipGetLastError());
-        if (esz) {
-            hipLaunchKernelGGL(k_add_partials, dim3((unsigned)esz), dim3(64), 0,
-                               c->stream, (const double *)epart, (int)ntab, (int)esz, ered);
-            BHMM_HIP(hipGetLastError());
-        }
+        auto *ka = c->kind == EMIT_GAUSS  ? k_smp_apply<N, EMIT_GAUSS>
+                   : c->kind == EMIT_DISC ? k_smp_apply<N, EMIT_DISC>
+                                          : k_smp_apply<N, EMIT_EXPL>;
+        const size_t smd = c->kind == EMIT_DISC && !bigM ? (size_t)c->M * N * sizeof(double) : 0;
+        BHMM_HIP(launch(ka, dim3(nblk), dim3(BLOCK), smd, c->stream, m, chs, offd, obs_ci, P, ns, path, cnt, epart, dmk, nb,
+                        W8, Gp64, gwc, Lp, status));
+        if (esz)
+            BHMM_HIP(launch(k_add_partials, dim3((unsigned)esz), dim3(64), 0, c->stream, epart, (int)ntab, (int)esz, ered));
     }
     // counts | reduced emission statistics | [status, watched draws] are contiguous on the device: ONE copy, into
     // pinned memory where it fits (a pageable destination makes every small copy a round trip of its own)
@@ -281,10 +248,7 @@ int sample_run(bhmm_ctx *c, const double *A, const double *pi, const double *par
     int hstatus = 0;
     if (stats_dev) {
         // statistics stay on the device, packed for the caller's all-reduce
-        hipLaunchKernelGGL(k_pack_path_stats, dim3(1), dim3(256), 0, c->stream,
-                           (const unsigned long long *)cnt, (const double *)ered, n, N, c->M, c->kind,
-                           1, stats_dev);
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_pack_path_stats, dim3(1), dim3(256), 0, c->stream, cnt, ered, n, N, c->M, c->kind, 1, stats_dev));
         BHMM_HIP(hipMemcpyAsync(hres + nres - 1, status, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     } else {
         BHMM_HIP(hipMemcpyAsync(hres, cnt, nres * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -441,54 +405,26 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
             c->d_alpha_rm.ensure((size_t)c->total * n) == BHMM_OK) {
             const dim3 pg((unsigned)((c->total + 255) / 256)), pb(256);
             const dim3 pl((unsigned)(((size_t)c->total * n + 256 * POBS_LANES_R - 1) / (256 * POBS_LANES_R)));
-#define BHMM_POBS_LANES(NLV)                                                                        \
-    do {                                                                                            \
-        if (c->kind == EMIT_GAUSS)                                                                  \
-            hipLaunchKernelGGL((k_pobs_lanes<EMIT_GAUSS, NLV>), pl, pb, 0, c->stream, m, obs,       \
-                               c->total, c->d_alpha_rm.p);                                          \
-        else                                                                                        \
-            hipLaunchKernelGGL((k_pobs_lanes<EMIT_DISC, NLV>), pl, pb, 0, c->stream, m, obs,        \
-                               c->total, c->d_alpha_rm.p);                                          \
-    } while (0)
             // one thread per element where n is a power of two (coalesced stores), else per step
-            if (n == 2)
-                BHMM_POBS_LANES(2);
-            else if (n == 4)
-                BHMM_POBS_LANES(4);
-            else if (n == 8)
-                BHMM_POBS_LANES(8);
-            else if (n == 16)
-                BHMM_POBS_LANES(16);
-            else if (n == 32)
-                BHMM_POBS_LANES(32);
-            else if (n == 64)
-                BHMM_POBS_LANES(64);
-            else if (c->kind == EMIT_GAUSS)
-                hipLaunchKernelGGL((k_pobs_all<EMIT_GAUSS>), pg, pb, 0, c->stream, m, obs, c->total,
-                                   c->d_alpha_rm.p);
+            const bool gauss = c->kind == EMIT_GAUSS;
+            auto *kl = n == 2    ? (gauss ? k_pobs_lanes<EMIT_GAUSS, 2> : k_pobs_lanes<EMIT_DISC, 2>)
+                       : n == 4  ? (gauss ? k_pobs_lanes<EMIT_GAUSS, 4> : k_pobs_lanes<EMIT_DISC, 4>)
+                       : n == 8  ? (gauss ? k_pobs_lanes<EMIT_GAUSS, 8> : k_pobs_lanes<EMIT_DISC, 8>)
+                       : n == 16 ? (gauss ? k_pobs_lanes<EMIT_GAUSS, 16> : k_pobs_lanes<EMIT_DISC, 16>)
+                       : n == 32 ? (gauss ? k_pobs_lanes<EMIT_GAUSS, 32> : k_pobs_lanes<EMIT_DISC, 32>)
+                       : n == 64 ? (gauss ? k_pobs_lanes<EMIT_GAUSS, 64> : k_pobs_lanes<EMIT_DISC, 64>)
+                                 : nullptr;
+            if (kl)
+                BHMM_HIP(launch(kl, pl, pb, 0, c->stream, m, obs, c->total, c->d_alpha_rm.p));
             else
-                hipLaunchKernelGGL((k_pobs_all<EMIT_DISC>), pg, pb, 0, c->stream, m, obs, c->total,
-                                   c->d_alpha_rm.p);
-#undef BHMM_POBS_LANES
-            BHMM_HIP(hipGetLastError());
+                BHMM_HIP(launch(gauss ? k_pobs_all<EMIT_GAUSS> : k_pobs_all<EMIT_DISC>, pg, pb, 0, c->stream, m, obs, c->total,
+                                c->d_alpha_rm.p));
             obs = c->d_alpha_rm.p;
             vkind = EMIT_EXPL;
         } else {
             (void)hipGetLastError();
         }
     }
-#define BHMM_WV(NPV, KINDV)                                                                     \
-    hipLaunchKernelGGL((k_wide_viterbi_fwd<NPV, KINDV, 1>), grid,                                  \
-                       blk, 0, c->stream, m, off, K, obs, ptr, last)
-#define BHMM_WV_KIND(NPV)                                 \
-    do {                                                  \
-        if (vkind == EMIT_GAUSS)                          \
-            BHMM_WV(NPV, EMIT_GAUSS);                     \
-        else if (vkind == EMIT_DISC)                      \
-            BHMM_WV(NPV, EMIT_DISC);                      \
-        else                                              \
-            BHMM_WV(NPV, EMIT_EXPL);                      \
-    } while (0)
     // back-trace of an accepted chunk-parallel run (k_vit_walk, maps -> stitch -> paths)
     // (models of up to four states: four lanes per chunk, 16 chunks per wavefront)
     const bool vit4 = !c->wide && n <= 4;
@@ -496,32 +432,22 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
         constexpr int VNP = decltype(npc)::value;
         const Chunks chs = chunks_of(c);
         const dim3 wg((c->G + 64 / VNP - 1) / (64 / VNP));
-        if (out_fmt == 0)
-            hipLaunchKernelGGL((k_vit_walk<VNP, false, int32_t>), wg, dim3(64), 0, c->stream, chs, c->G, n,
-                               (const uint8_t *)ptr, (const int32_t *)nullptr, vmaps, path, vcoal);
-        else
-            hipLaunchKernelGGL((k_vit_walk<VNP, false, uint8_t>), wg, dim3(64), 0, c->stream, chs, c->G, n,
-                               (const uint8_t *)ptr, (const int32_t *)nullptr, vmaps, path8, vcoal);
-        if ((int64_t)c->G >= (int64_t)32 * K)
-            hipLaunchKernelGGL(k_smp_stitch, dim3(K), dim3(64), 0, c->stream,
-                               (const int32_t *)c->d_traj_c0.p, K, 1, (const uint32_t *)vmaps, vend,
-                               (const int32_t *)last);
-        else
-            hipLaunchKernelGGL(k_smp_stitch_serial, dim3((K + SMP_STITCH_TPB - 1) / SMP_STITCH_TPB),
-                               dim3(64), 0, c->stream, (const int32_t *)c->d_traj_c0.p, K, 1,
-                               (const uint32_t *)vmaps, vend, (const int32_t *)last);
-        if (out_fmt == 0)
-            hipLaunchKernelGGL((k_vit_walk<VNP, true, int32_t>), wg, dim3(64), 0, c->stream, chs, c->G, n,
-                               (const uint8_t *)ptr, (const int32_t *)vend, (uint32_t *)nullptr, path, vcoal);
-        else
-            hipLaunchKernelGGL((k_vit_walk<VNP, true, uint8_t>), wg, dim3(64), 0, c->stream, chs, c->G, n,
-                               (const uint8_t *)ptr, (const int32_t *)vend, (uint32_t *)nullptr, path8, vcoal);
+        auto walk = [&](auto *kmaps, auto *kpath, auto *out) {
+            hipError_t e = launch(kmaps, wg, dim3(64), 0, c->stream, chs, c->G, n, ptr, nullptr, vmaps, out, vcoal);
+            if (e == hipSuccess)
+                e = (int64_t)c->G >= (int64_t)32 * K
+                        ? launch(k_smp_stitch, dim3(K), dim3(64), 0, c->stream, c->d_traj_c0.p, K, 1, vmaps, vend, last)
+                        : launch(k_smp_stitch_serial, dim3((K + SMP_STITCH_TPB - 1) / SMP_STITCH_TPB), dim3(64), 0,
+                                 c->stream, c->d_traj_c0.p, K, 1, vmaps, vend, last);
+            if (e == hipSuccess)
+                e = launch(kpath, wg, dim3(64), 0, c->stream, chs, c->G, n, ptr, vend, nullptr, out, vcoal);
+            return e;
+        };
+        return out_fmt == 0 ? walk(k_vit_walk<VNP, false, int32_t>, k_vit_walk<VNP, true, int32_t>, path)
+                            : walk(k_vit_walk<VNP, false, uint8_t>, k_vit_walk<VNP, true, uint8_t>, path8);
     };
     auto launch_walks = [&]() {
-        if (vit4)
-            launch_walks_np(std::integral_constant<int, 4>{});
-        else
-            launch_walks_np(std::integral_constant<int, 8>{});
+        return vit4 ? launch_walks_np(std::integral_constant<int, 4>{}) : launch_walks_np(std::integral_constant<int, 8>{});
     };
     bool walks_in_flight = false;
     // n <= 8 with a chunk plan: the chunk-parallel run first; its back-pointers are accepted only
@@ -577,46 +503,21 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
         // first without the close-decision count; bit-identical boundaries make it irrelevant
         for (int pass = 0; pass < 2; ++pass) {
             BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
-#define BHMM_VC_NP(VNP, KINDV, MARGINV)                                                             \
-    hipLaunchKernelGGL((k_viterbi_chunks<VNP, KINDV, MARGINV>),                                     \
-                       dim3((c->G + 64 / VNP - 1) / (64 / VNP)), dim3(64), smB, c->stream, m, chs,   \
-                       c->G, off, obs, W_try, margin, ptr, last, c->d_aentry.p, c->d_aexit.p,       \
-                       c->d_specres.p, smB ? 1 : 0)
-#define BHMM_VC(KINDV, MARGINV)                 \
-    do {                                        \
-        if (vit4)                               \
-            BHMM_VC_NP(4, KINDV, MARGINV);      \
-        else                                    \
-            BHMM_VC_NP(8, KINDV, MARGINV);      \
-    } while (0)
-            if (disc_direct && c->kind == EMIT_DISC) {
-                if (pass == 0)
-                    BHMM_VC(EMIT_DISC, false);
-                else
-                    BHMM_VC(EMIT_DISC, true);
-            } else if (disc_direct) {
-                if (pass == 0)
-                    BHMM_VC(EMIT_GAUSS, false);
-                else
-                    BHMM_VC(EMIT_GAUSS, true);
-            } else {
-                if (pass == 0)
-                    BHMM_VC(EMIT_EXPL, false);
-                else
-                    BHMM_VC(EMIT_EXPL, true);
-            }
-#undef BHMM_VC
-#undef BHMM_VC_NP
-            BHMM_HIP(hipGetLastError());
-            if (vit4)
-                hipLaunchKernelGGL((k_viterbi_check<4>), dim3((c->G + 255) / 256), dim3(256), 0, c->stream,
-                                   chs, c->G, (const double *)c->d_aentry.p,
-                                   (const double *)c->d_aexit.p, tol, c->d_specres.p);
-            else
-                hipLaunchKernelGGL((k_viterbi_check<8>), dim3((c->G + 255) / 256), dim3(256), 0, c->stream,
-                                   chs, c->G, (const double *)c->d_aentry.p,
-                                   (const double *)c->d_aexit.p, tol, c->d_specres.p);
-            BHMM_HIP(hipGetLastError());
+            const int vk = disc_direct && c->kind == EMIT_DISC ? EMIT_DISC : disc_direct ? EMIT_GAUSS : EMIT_EXPL;
+            auto vc = [&](auto npc) {
+                constexpr int VNP = decltype(npc)::value;
+                const bool mg = pass > 0; // (the close-decision count)
+                auto *k = vk == EMIT_DISC    ? (mg ? k_viterbi_chunks<VNP, EMIT_DISC, true> : k_viterbi_chunks<VNP, EMIT_DISC, false>)
+                          : vk == EMIT_GAUSS ? (mg ? k_viterbi_chunks<VNP, EMIT_GAUSS, true> : k_viterbi_chunks<VNP, EMIT_GAUSS, false>)
+                                             : (mg ? k_viterbi_chunks<VNP, EMIT_EXPL, true> : k_viterbi_chunks<VNP, EMIT_EXPL, false>);
+                hipError_t e = launch(k, dim3((c->G + 64 / VNP - 1) / (64 / VNP)), dim3(64), smB, c->stream, m, chs, c->G, off,
+                                      obs, W_try, margin, ptr, last, c->d_aentry.p, c->d_aexit.p, c->d_specres.p, smB ? 1 : 0);
+                if (e == hipSuccess)
+                    e = launch(k_viterbi_check<VNP>, dim3((c->G + 255) / 256), dim3(256), 0, c->stream, chs, c->G,
+                               c->d_aentry.p, c->d_aexit.p, tol, c->d_specres.p);
+                return e;
+            };
+            BHMM_HIP(vit4 ? vc(std::integral_constant<int, 4>{}) : vc(std::integral_constant<int, 8>{}));
             BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
                                     hipMemcpyDeviceToHost, c->stream));
             // the normal case is "all boundaries bit-identical": the back-trace is enqueued behind
@@ -625,7 +526,7 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
             // repeated after any further pass
             const bool speculative = attempt == 0 && pass == 0;
             if (speculative)
-                launch_walks();
+                BHMM_HIP(launch_walks());
             BHMM_HIP(hipStreamSynchronize(c->stream));
             walks_in_flight = speculative && c->h_specres[3] == 0;
             if (c->h_specres[3] == 0 || c->h_specres[0] != 0)
@@ -695,18 +596,14 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
             sgw.W = 0;
             if ((rcw = c->d_vmaps.ensure((size_t)sgw.nseg * 64)) || (rcw = c->d_vend.ensure((size_t)sgw.nseg)))
                 return rcw;
-            hipLaunchKernelGGL((k_wide_vit_walk<false, uint8_t>), dim3(sgw.nseg), dim3(64), 0, c->stream, off, sgw, n,
-                               (const uint8_t *)ptr, c->d_vmaps.p, (const uint8_t *)nullptr, (uint8_t *)nullptr);
-            hipLaunchKernelGGL(k_wide_vit_stitch, dim3((K + 63) / 64), dim3(64), 0, c->stream,
-                               (const int32_t *)c->pplan_buf[2].traj0.p, K, (const uint8_t *)c->d_vmaps.p, 64,
-                               (const int32_t *)last, c->d_vend.p);
-            if (out_fmt == 0)
-                hipLaunchKernelGGL((k_wide_vit_walk<true, int32_t>), dim3(sgw.nseg), dim3(64), 0, c->stream, off, sgw, n,
-                                   (const uint8_t *)ptr, (uint8_t *)nullptr, (const uint8_t *)c->d_vend.p, path);
-            else
-                hipLaunchKernelGGL((k_wide_vit_walk<true, uint8_t>), dim3(sgw.nseg), dim3(64), 0, c->stream, off, sgw, n,
-                                   (const uint8_t *)ptr, (uint8_t *)nullptr, (const uint8_t *)c->d_vend.p, path8);
-            BHMM_HIP(hipGetLastError());
+            BHMM_HIP(launch(k_wide_vit_walk<false, uint8_t>, dim3(sgw.nseg), dim3(64), 0, c->stream, off, sgw, n, ptr,
+                            c->d_vmaps.p, nullptr, nullptr));
+            BHMM_HIP(launch(k_wide_vit_stitch, dim3((K + 63) / 64), dim3(64), 0, c->stream, c->pplan_buf[2].traj0.p, K,
+                            c->d_vmaps.p, 64, last, c->d_vend.p));
+            auto walk = [&](auto *k, auto *out) {
+                return launch(k, dim3(sgw.nseg), dim3(64), 0, c->stream, off, sgw, n, ptr, nullptr, c->d_vend.p, out);
+            };
+            BHMM_HIP(out_fmt == 0 ? walk(k_wide_vit_walk<true, int32_t>, path) : walk(k_wide_vit_walk<true, uint8_t>, path8));
             return BHMM_OK;
         };
         for (int attempt = 0; attempt < 2 && !done; ++attempt) {
@@ -728,44 +625,34 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
             if ((rc = c->d_vckpt.ensure(((size_t)(c->total >> 6) + 1) * NP)) ||
                 (rc = c->d_vflag.ensure(2 * (size_t)sg.nseg))) // ([nseg] flagged | [nseg] flagged and further than vm_tol)
                 return rc;
-#define BHMM_WVS(NPV, KINDV, FIXV)                                                                    \
-    hipLaunchKernelGGL((k_wide_viterbi_seg<NPV, KINDV, FIXV>), sgrid, sblk, 0, c->stream, m, off, sg,  \
-                       obs, ptr, last, c->d_aentry.p, c->d_aexit.p, c->d_vckpt.p,                     \
-                       (const uint8_t *)c->d_vflag.p, FIXV ? (double *)nullptr : vall)
-#define BHMM_WVS_KIND(NPV, FIXV)                                                                      \
-    do {                                                                                              \
-        if (vkind == EMIT_GAUSS)                                                                      \
-            BHMM_WVS(NPV, EMIT_GAUSS, FIXV);                                                          \
-        else if (vkind == EMIT_DISC)                                                                  \
-            BHMM_WVS(NPV, EMIT_DISC, FIXV);                                                           \
-        else                                                                                          \
-            BHMM_WVS(NPV, EMIT_EXPL, FIXV);                                                           \
-        hipLaunchKernelGGL((k_wide_vit_check<NPV>), dim3((sg.nseg + 255) / 256), dim3(256), 0,      \
-                           c->stream, sg, c->d_aentry.p, (const double *)c->d_aexit.p, c->d_vflag.p,  \
-                           c->d_specres.p, (!FIXV && vall) ? vm_tol : 0.0);                           \
-    } while (0)
-#define BHMM_WVS_NP(FIXV)              \
-    do {                               \
-        if (NP == 16)                  \
-            BHMM_WVS_KIND(16, FIXV);   \
-        else if (NP == 32)             \
-            BHMM_WVS_KIND(32, FIXV);   \
-        else                           \
-            BHMM_WVS_KIND(64, FIXV);   \
-    } while (0)
-#define BHMM_WVS_MEND(NPV, KINDV)                                                                      \
-    hipLaunchKernelGGL((k_wide_viterbi_seg<NPV, KINDV, true>), sgrid, sblk, 0, c->stream, m, off, sg,   \
-                       obs, ptr, last, c->d_aentry.p, c->d_aexit.p, c->d_vckpt.p,                      \
-                       (const uint8_t *)c->d_vflag.p + sg.nseg, vall, vm_tol, c->d_specres.p + 1)
-#define BHMM_WVS_MEND_KIND(NPV)                   \
-    do {                                          \
-        if (vkind == EMIT_GAUSS)                  \
-            BHMM_WVS_MEND(NPV, EMIT_GAUSS);       \
-        else if (vkind == EMIT_DISC)              \
-            BHMM_WVS_MEND(NPV, EMIT_DISC);        \
-        else                                      \
-            BHMM_WVS_MEND(NPV, EMIT_EXPL);        \
-    } while (0)
+            // one pass over the segments (FIX: a fix-up round) and its boundary check; the mending round
+            auto seg_pass = [&](auto npc, bool fix) {
+                constexpr int V = decltype(npc)::value;
+                auto *k = vkind == EMIT_GAUSS
+                              ? (fix ? k_wide_viterbi_seg<V, EMIT_GAUSS, true> : k_wide_viterbi_seg<V, EMIT_GAUSS, false>)
+                          : vkind == EMIT_DISC
+                              ? (fix ? k_wide_viterbi_seg<V, EMIT_DISC, true> : k_wide_viterbi_seg<V, EMIT_DISC, false>)
+                              : (fix ? k_wide_viterbi_seg<V, EMIT_EXPL, true> : k_wide_viterbi_seg<V, EMIT_EXPL, false>);
+                hipError_t e = launch(k, sgrid, sblk, 0, c->stream, m, off, sg, obs, ptr, last, c->d_aentry.p, c->d_aexit.p,
+                                      c->d_vckpt.p, c->d_vflag.p, fix ? nullptr : vall, 0.0, nullptr);
+                if (e == hipSuccess)
+                    e = launch(k_wide_vit_check<V>, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg, c->d_aentry.p,
+                               c->d_aexit.p, c->d_vflag.p, c->d_specres.p, (!fix && vall) ? vm_tol : 0.0);
+                return e;
+            };
+            auto mend_pass = [&](auto npc) {
+                constexpr int V = decltype(npc)::value;
+                auto *k = vkind == EMIT_GAUSS  ? k_wide_viterbi_seg<V, EMIT_GAUSS, true>
+                          : vkind == EMIT_DISC ? k_wide_viterbi_seg<V, EMIT_DISC, true>
+                                               : k_wide_viterbi_seg<V, EMIT_EXPL, true>;
+                return launch(k, sgrid, sblk, 0, c->stream, m, off, sg, obs, ptr, last, c->d_aentry.p, c->d_aexit.p,
+                              c->d_vckpt.p, c->d_vflag.p + sg.nseg, vall, vm_tol, c->d_specres.p + 1);
+            };
+            auto by_np = [&](auto f) {
+                return NP == 16 ? f(std::integral_constant<int, 16>{})
+                       : NP == 32 ? f(std::integral_constant<int, 32>{})
+                                  : f(std::integral_constant<int, 64>{});
+            };
             // pass 0 with warm-ups, then fix-up rounds while any boundary is not bit-identical
             const int max_rounds = 12;
             int round = 0;
@@ -775,11 +662,7 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
             for (; round <= max_rounds; ++round) {
                 BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
                 lds_poison(c->stream);
-                if (round == 0)
-                    BHMM_WVS_NP(false);
-                else
-                    BHMM_WVS_NP(true);
-                BHMM_HIP(hipGetLastError());
+                BHMM_HIP(by_np([&](auto npc) { return seg_pass(npc, round > 0); }));
                 BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
                                         hipMemcpyDeviceToHost, c->stream));
                 BHMM_HIP(hipStreamSynchronize(c->stream));
@@ -800,13 +683,7 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
                     // instead of lengthening every warm-up.  If one reaches its end the rounds decide.
                     BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
                     lds_poison(c->stream);
-                    if (NP == 16)
-                        BHMM_WVS_MEND_KIND(16);
-                    else if (NP == 32)
-                        BHMM_WVS_MEND_KIND(32);
-                    else
-                        BHMM_WVS_MEND_KIND(64);
-                    BHMM_HIP(hipGetLastError());
+                    BHMM_HIP(by_np(mend_pass));
                     unsigned int notmet = 0;
                     BHMM_HIP(hipMemcpyAsync(&notmet, c->d_specres.p + 1, sizeof(unsigned int), hipMemcpyDeviceToHost,
                                             c->stream));
@@ -831,20 +708,17 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
                     if (vm_global) {
                         if ((rc = c->d_gAt.ensure((size_t)n * n)))
                             return rc;
-                        hipLaunchKernelGGL(k_vm_transpose, dim3((n * n + 255) / 256), dim3(256), 0, c->stream, m.A, n, c->d_gAt.p);
-                        if (out_fmt == 0)
-                            hipLaunchKernelGGL((k_vit_margin<int32_t, 1, false>), mgrid, dim3(256), 0, c->stream, (const double *)c->d_gAt.p, n, off,
-                                               sg, (const double *)vall, (const int32_t *)path, margin, c->d_specres.p);
-                        else
-                            hipLaunchKernelGGL((k_vit_margin<uint8_t, 1, false>), mgrid, dim3(256), 0, c->stream, (const double *)c->d_gAt.p, n, off,
-                                               sg, (const double *)vall, (const uint8_t *)path8, margin, c->d_specres.p);
-                    } else if (out_fmt == 0)
-                        hipLaunchKernelGGL((k_vit_margin<int32_t, 1>), mgrid, dim3(256), smm, c->stream, m.A, n, off,
-                                           sg, (const double *)vall, (const int32_t *)path, margin, c->d_specres.p);
+                        BHMM_HIP(launch(k_vm_transpose, dim3((n * n + 255) / 256), dim3(256), 0, c->stream, m.A, n, c->d_gAt.p));
+                    }
+                    auto margins = [&](auto *k, const double *At, size_t lds, auto *p) {
+                        return launch(k, mgrid, dim3(256), lds, c->stream, At, n, off, sg, vall, p, margin, c->d_specres.p);
+                    };
+                    if (vm_global)
+                        BHMM_HIP(out_fmt == 0 ? margins(k_vit_margin<int32_t, 1, false>, c->d_gAt.p, 0, path)
+                                              : margins(k_vit_margin<uint8_t, 1, false>, c->d_gAt.p, 0, path8));
                     else
-                        hipLaunchKernelGGL((k_vit_margin<uint8_t, 1>), mgrid, dim3(256), smm, c->stream, m.A, n, off,
-                                           sg, (const double *)vall, (const uint8_t *)path8, margin, c->d_specres.p);
-                    BHMM_HIP(hipGetLastError());
+                        BHMM_HIP(out_fmt == 0 ? margins(k_vit_margin<int32_t, 1>, m.A, smm, path)
+                                              : margins(k_vit_margin<uint8_t, 1>, m.A, smm, path8));
                     BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
                                             hipMemcpyDeviceToHost, c->stream));
                     BHMM_HIP(hipStreamSynchronize(c->stream));
@@ -866,11 +740,6 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
                     round = -1;
                 }
             }
-#undef BHMM_WVS_NP
-#undef BHMM_WVS_KIND
-#undef BHMM_WVS
-#undef BHMM_WVS_MEND_KIND
-#undef BHMM_WVS_MEND
             c->last.vit_seg_rounds = round;
             // (a round runs as long as its longest flagged segment needs to fall onto a vector of the first pass
             // again: 1.1 ms at configs[3] on white-noise observations, 6.7 ms -- half a first pass -- on
@@ -902,28 +771,28 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
             walks_in_flight = true;
         }
     }
-    if (done)
-        ;
-    else if (NP == 8)
-        BHMM_WV_KIND(8);
-    else if (NP == 16)
-        BHMM_WV_KIND(16);
-    else if (NP == 32)
-        BHMM_WV_KIND(32);
-    else
-        BHMM_WV_KIND(64);
-    BHMM_HIP(hipGetLastError());
     if (done) {
         if (!walks_in_flight)
-            launch_walks();
-    } else if (out_fmt == 0) {
-        hipLaunchKernelGGL(k_wide_viterbi_trace<int32_t>, dim3(K), dim3(64), 0, c->stream, off, K, n,
-                           (const uint8_t *)ptr, (const int32_t *)last, path);
+            BHMM_HIP(launch_walks());
     } else {
-        hipLaunchKernelGGL(k_wide_viterbi_trace<uint8_t>, dim3(K), dim3(64), 0, c->stream, off, K, n,
-                           (const uint8_t *)ptr, (const int32_t *)last, path8);
+        auto *kv = NP == 8    ? (vkind == EMIT_GAUSS  ? k_wide_viterbi_fwd<8, EMIT_GAUSS, 1>
+                                 : vkind == EMIT_DISC ? k_wide_viterbi_fwd<8, EMIT_DISC, 1>
+                                                      : k_wide_viterbi_fwd<8, EMIT_EXPL, 1>)
+                   : NP == 16 ? (vkind == EMIT_GAUSS  ? k_wide_viterbi_fwd<16, EMIT_GAUSS, 1>
+                                 : vkind == EMIT_DISC ? k_wide_viterbi_fwd<16, EMIT_DISC, 1>
+                                                      : k_wide_viterbi_fwd<16, EMIT_EXPL, 1>)
+                   : NP == 32 ? (vkind == EMIT_GAUSS  ? k_wide_viterbi_fwd<32, EMIT_GAUSS, 1>
+                                 : vkind == EMIT_DISC ? k_wide_viterbi_fwd<32, EMIT_DISC, 1>
+                                                      : k_wide_viterbi_fwd<32, EMIT_EXPL, 1>)
+                              : (vkind == EMIT_GAUSS  ? k_wide_viterbi_fwd<64, EMIT_GAUSS, 1>
+                                 : vkind == EMIT_DISC ? k_wide_viterbi_fwd<64, EMIT_DISC, 1>
+                                                      : k_wide_viterbi_fwd<64, EMIT_EXPL, 1>);
+        BHMM_HIP(launch(kv, grid, blk, 0, c->stream, m, off, K, obs, ptr, last));
+        if (out_fmt == 0)
+            BHMM_HIP(launch(k_wide_viterbi_trace<int32_t>, dim3(K), dim3(64), 0, c->stream, off, K, n, ptr, last, path));
+        else
+            BHMM_HIP(launch(k_wide_viterbi_trace<uint8_t>, dim3(K), dim3(64), 0, c->stream, off, K, n, ptr, last, path8));
     }
-    BHMM_HIP(hipGetLastError());
     if (out_fmt == 2) { // the paths are where the caller wants them; the call still completes them
         BHMM_HIP(hipStreamSynchronize(c->stream));
         return BHMM_OK;
@@ -997,20 +866,6 @@ int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double
         BHMM_HIP(hipMemsetAsync(ered, 0, esz * sizeof(double), c->stream));
     const dim3 grid((K + GP - 1) / GP), blk(64);
     const int64_t *off = c->d_offsets.p;
-    auto launch_serial = [&]() {
-        if (NP == 16)
-            hipLaunchKernelGGL((k_wide_sample_path<16>), grid, blk, 0, c->stream, m, off, K,
-                               (const double *)c->d_alpha_rm.p, (const double *)udev, seed, path, status,
-                               (const int64_t *)c->d_soff.p);
-        else if (NP == 32)
-            hipLaunchKernelGGL((k_wide_sample_path<32>), grid, blk, 0, c->stream, m, off, K,
-                               (const double *)c->d_alpha_rm.p, (const double *)udev, seed, path, status,
-                               (const int64_t *)c->d_soff.p);
-        else
-            hipLaunchKernelGGL((k_wide_sample_path<64>), grid, blk, 0, c->stream, m, off, K,
-                               (const double *)c->d_alpha_rm.p, (const double *)udev, seed, path, status,
-                               (const int64_t *)c->d_soff.p);
-    };
     // parallel over time segments where that fills more of the device than the trajectories do
     // (k_wide_sample_seg): the draws are coupled through the per-step uniforms, segments that did not
     // continue their successor's state are drawn again until none is left
@@ -1033,32 +888,21 @@ int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double
                 BHMM_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_specres), 4 * sizeof(unsigned int),
                                        hipHostMallocDefault));
             const dim3 sgrid((sg.nseg + GP * WVS_WPB - 1) / (GP * WVS_WPB)), sblk(64 * WVS_WPB);
-#define BHMM_WSS(NPV, FIXV)                                                                              \
-    hipLaunchKernelGGL((k_wide_sample_seg<NPV, FIXV>), sgrid, sblk, 0, c->stream, m, off, sg,           \
-                       (const double *)c->d_alpha_rm.p, (const double *)udev, seed, path, status,       \
-                       (const int64_t *)c->d_soff.p, c->d_sentry.p, c->d_sexit.p,                       \
-                       (const uint8_t *)c->d_vflag.p, watch)
-#define BHMM_WSS_NP(FIXV)          \
-    do {                           \
-        if (NP == 16)              \
-            BHMM_WSS(16, FIXV);    \
-        else if (NP == 32)         \
-            BHMM_WSS(32, FIXV);    \
-        else                       \
-            BHMM_WSS(64, FIXV);    \
-    } while (0)
+            auto *kfirst = NP == 16   ? k_wide_sample_seg<16, false>
+                           : NP == 32 ? k_wide_sample_seg<32, false>
+                                      : k_wide_sample_seg<64, false>;
+            auto *kfix = NP == 16   ? k_wide_sample_seg<16, true>
+                         : NP == 32 ? k_wide_sample_seg<32, true>
+                                    : k_wide_sample_seg<64, true>;
             const int max_rounds = 16;
             int round = 0;
             for (; round <= max_rounds; ++round) {
                 BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
                 lds_poison(c->stream);
-                if (round == 0)
-                    BHMM_WSS_NP(false);
-                else
-                    BHMM_WSS_NP(true);
-                hipLaunchKernelGGL(k_wide_smp_check, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
-                                   c->d_sentry.p, (const int32_t *)c->d_sexit.p, c->d_vflag.p, c->d_specres.p);
-                BHMM_HIP(hipGetLastError());
+                BHMM_HIP(launch(round == 0 ? kfirst : kfix, sgrid, sblk, 0, c->stream, m, off, sg, c->d_alpha_rm.p, udev, seed,
+                                path, status, c->d_soff.p, c->d_sentry.p, c->d_sexit.p, c->d_vflag.p, watch));
+                BHMM_HIP(launch(k_wide_smp_check, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg, c->d_sentry.p,
+                                c->d_sexit.p, c->d_vflag.p, c->d_specres.p));
                 BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
                                         hipMemcpyDeviceToHost, c->stream));
                 BHMM_HIP(hipMemcpyAsync(&c->h_specres[0], status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1068,8 +912,6 @@ int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double
                 if (c->h_specres[3] == 0)
                     break;
             }
-#undef BHMM_WSS_NP
-#undef BHMM_WSS
             c->last.smp_seg_rounds = round;
             // (a draw that found no state may belong to a segment that was drawn again afterwards:
             // the serial kernel decides such a call)
@@ -1089,7 +931,8 @@ int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double
             c->last.draw_fwd_segmented = false;
             c->last.draw_alpha_dev = 0.0;
         }
-        launch_serial();
+        auto *ks = NP == 16 ? k_wide_sample_path<16> : NP == 32 ? k_wide_sample_path<32> : k_wide_sample_path<64>;
+        BHMM_HIP(launch(ks, grid, blk, 0, c->stream, m, off, K, c->d_alpha_rm.p, udev, seed, path, status, c->d_soff.p));
     } else if (watch.count) {
         // watched draws are decided again on the serial recursion over a long window; if one does not stand, the
         // whole call again on the rows of the serial recursion
@@ -1112,7 +955,6 @@ int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double
             }
         }
     }
-    BHMM_HIP(hipGetLastError());
     if (counts || n0 || emis || stats_dev) {
         // the per-trajectory emission table in LDS, or -- alphabets too large for it -- in epart itself
         const bool gtab = c->kind == EMIT_DISC &&
@@ -1121,33 +963,18 @@ int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double
         if (gtab)
             BHMM_HIP(hipMemsetAsync(epart, 0, (size_t)K * esz * sizeof(double), c->stream));
         const void *obs = c->d_obs_rm.p;
-        if (c->kind == EMIT_GAUSS)
-            hipLaunchKernelGGL((k_wide_path_stats<EMIT_GAUSS>), dim3(K), dim3(256), sm, c->stream, m,
-                               off, obs, (const int32_t *)path, cnt, epart, 0);
-        else if (c->kind == EMIT_DISC) {
-            if (sm > 64 * 1024)
-                BHMM_HIP(hipFuncSetAttribute((const void *)(k_wide_path_stats<EMIT_DISC>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-            hipLaunchKernelGGL((k_wide_path_stats<EMIT_DISC>), dim3(K), dim3(256), sm, c->stream, m,
-                               off, obs, (const int32_t *)path, cnt, epart, gtab ? 1 : 0);
-        } else
-            hipLaunchKernelGGL((k_wide_path_stats<EMIT_EXPL>), dim3(K), dim3(256), sm, c->stream, m,
-                               off, obs, (const int32_t *)path, cnt, epart, 0);
-        BHMM_HIP(hipGetLastError());
-        if (esz) {
-            hipLaunchKernelGGL(k_add_partials, dim3((unsigned)esz), dim3(64), 0,
-                               c->stream, (const double *)epart, K, (int)esz, ered);
-            BHMM_HIP(hipGetLastError());
-        }
+        auto *kst = c->kind == EMIT_GAUSS  ? k_wide_path_stats<EMIT_GAUSS>
+                    : c->kind == EMIT_DISC ? k_wide_path_stats<EMIT_DISC>
+                                           : k_wide_path_stats<EMIT_EXPL>;
+        BHMM_HIP(launch(kst, dim3(K), dim3(256), sm, c->stream, m, off, obs, path, cnt, epart, gtab ? 1 : 0));
+        if (esz)
+            BHMM_HIP(launch(k_add_partials, dim3((unsigned)esz), dim3(64), 0, c->stream, epart, K, (int)esz, ered));
     }
     std::vector<unsigned long long> hc(nstat);
     std::vector<double> he(esz);
     int hstatus = 0;
     if (stats_dev) {
-        hipLaunchKernelGGL(k_pack_path_stats, dim3(16), dim3(256), 0, c->stream,
-                           (const unsigned long long *)cnt, (const double *)ered, n, n, c->M, c->kind,
-                           0, stats_dev);
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_pack_path_stats, dim3(16), dim3(256), 0, c->stream, cnt, ered, n, n, c->M, c->kind, 0, stats_dev));
     } else {
         BHMM_HIP(hipMemcpyAsync(hc.data(), cnt, nstat * sizeof(unsigned long long),
                                 hipMemcpyDeviceToHost, c->stream));
@@ -1334,19 +1161,8 @@ int bhmm_sample_path(int32_t *path, const double *alpha, const double *A, const 
         memset(&m, 0, sizeof(m));
         m.A = d_A;
         m.n = N;
-        if (N <= 16)
-            hipLaunchKernelGGL((k_wide_sample_path<16>), dim3(1), dim3(64), 0, 0, m,
-                               (const int64_t *)d_off, 1, (const double *)d_alpha,
-                               (const double *)d_u, (uint64_t)0, d_path, d_status);
-        else if (N <= 32)
-            hipLaunchKernelGGL((k_wide_sample_path<32>), dim3(1), dim3(64), 0, 0, m,
-                               (const int64_t *)d_off, 1, (const double *)d_alpha,
-                               (const double *)d_u, (uint64_t)0, d_path, d_status);
-        else
-            hipLaunchKernelGGL((k_wide_sample_path<64>), dim3(1), dim3(64), 0, 0, m,
-                               (const int64_t *)d_off, 1, (const double *)d_alpha,
-                               (const double *)d_u, (uint64_t)0, d_path, d_status);
-        BHMM_HIP(hipGetLastError());
+        auto *k = N <= 16 ? k_wide_sample_path<16> : N <= 32 ? k_wide_sample_path<32> : k_wide_sample_path<64>;
+        BHMM_HIP(launch(k, dim3(1), dim3(64), 0, 0, m, d_off, 1, d_alpha, d_u, (uint64_t)0, d_path, d_status, nullptr));
         int stw = 0;
         BHMM_HIP(hipMemcpy(path, d_path, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost));
         BHMM_HIP(hipMemcpy(&stw, d_status, sizeof(int), hipMemcpyDeviceToHost));
@@ -1362,9 +1178,8 @@ int bhmm_sample_path(int32_t *path, const double *alpha, const double *A, const 
     {                                                                                           \
         Model<NN> m;                                                                            \
         fill_model<NN>(m, N, EMIT_EXPL, 0, A, pi.data(), nullptr, nullptr);                 \
-        hipLaunchKernelGGL((k_sample_path<NN>), dim3(1), dim3(64), 0, 0, m,                     \
-                           (const int64_t *)d_off, 1, (const double *)d_alpha,                  \
-                           (const double *)d_u, (uint64_t)0, d_path, d_status);                 \
+        BHMM_HIP(launch(k_sample_path<NN>, dim3(1), dim3(64), 0, 0, m, d_off, 1, d_alpha, d_u,    \
+                        (uint64_t)0, d_path, d_status));                                        \
     }
     if (NP == 2)
         BHMM_SAMPLE_CASE(2)
@@ -1372,7 +1187,6 @@ int bhmm_sample_path(int32_t *path, const double *alpha, const double *A, const 
         BHMM_SAMPLE_CASE(4)
     else
         BHMM_SAMPLE_CASE(8)
-    BHMM_HIP(hipGetLastError());
     int st = 0;
     BHMM_HIP(hipMemcpy(path, d_path, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost));
     BHMM_HIP(hipMemcpy(&st, d_status, sizeof(int), hipMemcpyDeviceToHost));
@@ -1407,9 +1221,7 @@ int bhmm_state_probabilities(double *gamma, const double *alpha, const double *b
         return rc;
     BHMM_HIP(hipMemcpy(da, alpha, cnt * sizeof(double), hipMemcpyHostToDevice));
     BHMM_HIP(hipMemcpy(db, beta, cnt * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_gamma_rows, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, 0,
-                       (const double *)da, (const double *)db, dg, N, T);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_gamma_rows, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, 0, da, db, dg, N, T));
     BHMM_HIP(hipMemcpy(gamma, dg, cnt * sizeof(double), hipMemcpyDeviceToHost));
     return BHMM_OK;
 }
@@ -1439,11 +1251,8 @@ int bhmm_transition_counts(double *C, const double *A, const double *pobs, const
     BHMM_HIP(hipMemcpy(db, beta, cnt * sizeof(double), hipMemcpyHostToDevice));
 #define BHMM_XI_CASE(NN)                                                                        \
     {                                                                                           \
-        hipLaunchKernelGGL((k_xi_rows<NN>), dim3(nblk), dim3(256), 0, 0, (const double *)dA,    \
-                           (const double *)dp, (const double *)da, (const double *)db, N, T,    \
-                           dpart);                                                              \
-        hipLaunchKernelGGL((k_sum_partials<NN>), dim3(1), dim3(64), 0, 0,                       \
-                           (const double *)dpart, nblk, N, dC);                                 \
+        BHMM_HIP(launch(k_xi_rows<NN>, dim3(nblk), dim3(256), 0, 0, dA, dp, da, db, N, T, dpart));  \
+        BHMM_HIP(launch(k_sum_partials<NN>, dim3(1), dim3(64), 0, 0, dpart, nblk, N, dC));       \
     }
     if (NP == 2)
         BHMM_XI_CASE(2)
@@ -1451,7 +1260,6 @@ int bhmm_transition_counts(double *C, const double *A, const double *pobs, const
         BHMM_XI_CASE(4)
     else
         BHMM_XI_CASE(8)
-    BHMM_HIP(hipGetLastError());
     BHMM_HIP(hipMemcpy(C, dC, (size_t)N * N * sizeof(double), hipMemcpyDeviceToHost));
     return BHMM_OK;
 }
@@ -1470,10 +1278,8 @@ int bhmm_pobs_gaussian(double *pobs, const double *obs, const double *mu, const 
     BHMM_HIP(hipMemcpy(dobs, obs, (size_t)T * sizeof(double), hipMemcpyHostToDevice));
     BHMM_HIP(hipMemcpy(dmu, mu, (size_t)N * sizeof(double), hipMemcpyHostToDevice));
     BHMM_HIP(hipMemcpy(dsig, sigma, (size_t)N * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_pobs_gaussian, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, 0,
-                       (const double *)dobs, (const double *)dmu, (const double *)dsig, dp, N, T,
-                       ignore_outliers);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_pobs_gaussian, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, 0, dobs, dmu, dsig, dp, N, T,
+                    ignore_outliers));
     BHMM_HIP(hipMemcpy(pobs, dp, (size_t)T * N * sizeof(double), hipMemcpyDeviceToHost));
     return BHMM_OK;
 }
@@ -1496,11 +1302,8 @@ int bhmm_update_pout(double *pout, const int32_t *obs, const double *weights, in
     BHMM_HIP(hipMemcpy(dobs, obs, (size_t)T * sizeof(int32_t), hipMemcpyHostToDevice));
     BHMM_HIP(hipMemcpy(dw, weights, (size_t)T * N * sizeof(double), hipMemcpyHostToDevice));
     BHMM_HIP(hipMemcpy(dout, pout, (size_t)N * M * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_update_pout, dim3(nblk), dim3(256), (size_t)N * M * sizeof(double), 0,
-                       (const int32_t *)dobs, (const double *)dw, T, N, M, dpart);
-    hipLaunchKernelGGL(k_add_partials, dim3(N * M), dim3(64), 0, 0,
-                       (const double *)dpart, nblk, N * M, dout);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_update_pout, dim3(nblk), dim3(256), (size_t)N * M * sizeof(double), 0, dobs, dw, T, N, M, dpart));
+    BHMM_HIP(launch(k_add_partials, dim3(N * M), dim3(64), 0, 0, dpart, nblk, N * M, dout));
     BHMM_HIP(hipMemcpy(pout, dout, (size_t)N * M * sizeof(double), hipMemcpyDeviceToHost));
     return BHMM_OK;
 }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "host_internal.hpp"
+#include "launch.hpp"
 
 namespace bhmm {
 
@@ -181,25 +182,9 @@ extern "C" int bhmm_synth_observations_at(void *obs_dev, uint8_t *states_dev, in
         const size_t sm = ((size_t)N * N + (gauss ? 2 * (size_t)N : (size_t)N * M)) * sizeof(double) +
                           64 * 64 * (gauss ? sizeof(double) : sizeof(int32_t)) + 64 * 64;
         const dim3 grid((unsigned)((K + 63) / 64)), blk(64);
-        if (gauss) {
-            if (sm > 64 * 1024)
-                rc = hipFuncSetAttribute((const void *)k_synth<true>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-            if (rc == hipSuccess)
-                hipLaunchKernelGGL(k_synth<true>, grid, blk, sm, st, (const double *)dA,
-                                   (const double *)dpi, (const double *)d0, (const double *)d1, N, M, K,
-                                   T, seed, obs_dev, states_dev, first_traj);
-        } else {
-            if (sm > 64 * 1024)
-                rc = hipFuncSetAttribute((const void *)k_synth<false>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-            if (rc == hipSuccess)
-                hipLaunchKernelGGL(k_synth<false>, grid, blk, sm, st, (const double *)dA,
-                                   (const double *)dpi, (const double *)d0, (const double *)nullptr, N,
-                                   M, K, T, seed, obs_dev, states_dev, first_traj);
-        }
-        if (rc == hipSuccess)
-            rc = hipGetLastError();
+        auto *k = gauss ? k_synth<true> : k_synth<false>;
+        rc = launch(k, grid, blk, sm, st, dA, dpi, d0, gauss ? d1 : nullptr, N, M, K, T, seed, obs_dev,
+                    states_dev, first_traj);
     }
     if (rc == hipSuccess)
         rc = hipStreamSynchronize(st);

@@ -93,14 +93,11 @@ int run_check(bhmm_ctx *c, int dir)
 {
     const Segs sg = segs_of(c, 1);
     if (dir == 0)
-        hipLaunchKernelGGL(k_wide_check, dim3((sg.nseg + 15) / 16), dim3(256), 0, c->stream, sg, c->n,
-                           (const double *)c->d_waentry.p, (const double *)c->d_waexit.p,
-                           (const double *)nullptr, (const double *)nullptr, 1e-11, c->d_specres.p);
+        BHMM_HIP(launch(k_wide_check, dim3((sg.nseg + 15) / 16), dim3(256), 0, c->stream, sg, c->n, c->d_waentry.p,
+                        c->d_waexit.p, nullptr, nullptr, 1e-11, c->d_specres.p));
     else
-        hipLaunchKernelGGL(k_wide_check, dim3((sg.nseg + 15) / 16), dim3(256), 0, c->stream, sg, c->n,
-                           (const double *)nullptr, (const double *)nullptr, (const double *)c->d_wbexit.p,
-                           (const double *)c->d_wbentry.p, 1e-11, c->d_specres.p);
-    BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_wide_check, dim3((sg.nseg + 15) / 16), dim3(256), 0, c->stream, sg, c->n, nullptr, nullptr,
+                        c->d_wbexit.p, c->d_wbentry.p, 1e-11, c->d_specres.p));
     return BHMM_OK;
 }
 

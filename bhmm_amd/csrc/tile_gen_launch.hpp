@@ -11,6 +11,7 @@
 
 #include "host_common.hpp"
 #include "host_internal.hpp"
+#include "launch.hpp"
 #include "plan.hpp"
 #include "wide_kernels.hpp"
 

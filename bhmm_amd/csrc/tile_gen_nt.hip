@@ -26,11 +26,9 @@ int tile_gen_launch_fwd(bhmm_ctx *c, const WideModel &m)
         probe = reinterpret_cast<unsigned long long *>(c->d_probe.p);
         BHMM_HIP(hipMemsetAsync(probe, 0, 64, c->stream));
     }
-    hipLaunchKernelGGL((k_tile_fwd<NT, KIND, false, FWD_SPLIT>), dim3(tp.ntiles), dim3(tile_threads<FWD_SPLIT>()), 0,
-                       c->stream, m, (const int64_t *)c->d_offsets.p, sg, tp, (const void *)c->d_obs_rm.p,
-                       c->d_alpha_rm.p, c->d_wexp.p, c->d_wePseg.p, c->d_waentry.p, c->d_waexit.p,
-                       c->d_specres.p, probe);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_tile_fwd<NT, KIND, false, FWD_SPLIT>, dim3(tp.ntiles), dim3(tile_threads<FWD_SPLIT>()), 0,
+                    c->stream, m, c->d_offsets.p, sg, tp, c->d_obs_rm.p, c->d_alpha_rm.p, c->d_wexp.p, c->d_wePseg.p,
+                    c->d_waentry.p, c->d_waexit.p, c->d_specres.p, probe));
     if (probe_on) {
         unsigned long long h[8];
         BHMM_HIP(hipMemcpyAsync(h, probe, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -41,12 +39,10 @@ int tile_gen_launch_fwd(bhmm_ctx *c, const WideModel &m)
                     (double)h[0] / h[3], (double)h[1] / h[3], (double)h[2] / h[3], (double)h[4] / h[7],
                     (double)h[5] / h[7], (double)h[6] / h[7], h[3]);
     }
-    hipLaunchKernelGGL(k_tile_logl, dim3((sg.nseg + 15) / 16), dim3(256), 0, c->stream, sg, c->n,
-                       (const double *)c->d_waentry.p, (const double *)c->d_waexit.p,
-                       (const int32_t *)c->d_wePseg.p, c->d_wlogLseg.p, c->d_specres.p);
-    hipLaunchKernelGGL(k_logl, dim3(c->K), dim3(64), 0, c->stream, (const int32_t *)c->d_wseg_traj0[1].p,
-                       c->K, (const double *)c->d_wlogLseg.p, c->d_logLk.p);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_tile_logl, dim3((sg.nseg + 15) / 16), dim3(256), 0, c->stream, sg, c->n, c->d_waentry.p,
+                    c->d_waexit.p, c->d_wePseg.p, c->d_wlogLseg.p, c->d_specres.p));
+    BHMM_HIP(launch(k_logl, dim3(c->K), dim3(64), 0, c->stream, c->d_wseg_traj0[1].p, c->K, c->d_wlogLseg.p,
+                    c->d_logLk.p));
     return BHMM_OK;
 }
 
@@ -62,8 +58,7 @@ int tile_gen_launch_bwd(bhmm_ctx *c, const WideModel &m, double *gam, double *st
     int rc;
     if ((rc = c->d_gW.ensure((size_t)c->total * n)) || (rc = c->d_gxipart.ensure((size_t)nsplit * n * n)))
         return rc;
-    hipLaunchKernelGGL(k_wide_zero_last_rows, dim3(c->K), dim3(64), 0, c->stream, (const int64_t *)c->d_offsets.p,
-                       c->K, n, c->d_gW.p);
+    BHMM_HIP(launch(k_wide_zero_last_rows, dim3(c->K), dim3(64), 0, c->stream, c->d_offsets.p, c->K, n, c->d_gW.p));
     // BHMM_AMD_TILE_PROBE=1: cycles of the phases of a step (last workgroup, wavefront 0), printed after the pass
     static const bool probe_on = getenv("BHMM_AMD_TILE_PROBE") != nullptr && atoi(getenv("BHMM_AMD_TILE_PROBE")) == 1;
     unsigned long long *probe = nullptr;
@@ -73,12 +68,10 @@ int tile_gen_launch_bwd(bhmm_ctx *c, const WideModel &m, double *gam, double *st
         probe = reinterpret_cast<unsigned long long *>(c->d_probe.p) + 16;
         BHMM_HIP(hipMemsetAsync(probe, 0, 48 * 8, c->stream));
     }
-    hipLaunchKernelGGL((k_tile_bwd<NT, KIND, false, true, false>), dim3(tp.ntiles), dim3(tile_threads<false>()), 0,
-                       c->stream, m, (const int64_t *)c->d_offsets.p, sg, tp, (const void *)c->d_obs_rm.p,
-                       (const double *)c->d_alpha_rm.p, (const int32_t *)c->d_wexp.p, gam, c->d_gamma0.p,
-                       c->d_partials.p, c->d_dpartials.p, c->d_wbexit.p, c->d_wbentry.p, c->d_specres.p,
-                       c->d_gW.p, probe);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_tile_bwd<NT, KIND, false, true, false>, dim3(tp.ntiles), dim3(tile_threads<false>()), 0,
+                    c->stream, m, c->d_offsets.p, sg, tp, c->d_obs_rm.p, c->d_alpha_rm.p, c->d_wexp.p, gam,
+                    c->d_gamma0.p, c->d_partials.p, c->d_dpartials.p, c->d_wbexit.p, c->d_wbentry.p, c->d_specres.p,
+                    c->d_gW.p, probe));
     if (probe_on) {
         unsigned long long h[48];
         BHMM_HIP(hipMemcpyAsync(h, probe, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -108,37 +101,23 @@ int tile_gen_launch_bwd(bhmm_ctx *c, const WideModel &m, double *gam, double *st
     const bool xi_rows = xi_rows_env;
     const int nsl = xi_rows ? nsplit : std::min(nsplit, 2 * c->num_simd / 4); // (two workgroups per compute unit)
     if (!xi_rows) {
-        if (n <= 96) // (one 96 x 96 block, 3 x 3 tiles per wavefront)
-            hipLaunchKernelGGL(k_big_xi_gemm<3>, dim3(nsl), dim3(256), 0, c->stream, (const double *)c->d_alpha_rm.p,
-                               (const double *)c->d_gW.p, c->total, n, 1, nsl, c->d_gxipart.p);
-        else
-            hipLaunchKernelGGL(k_big_xi_gemm<4>, dim3(nsl), dim3(256), 0, c->stream, (const double *)c->d_alpha_rm.p,
-                               (const double *)c->d_gW.p, c->total, n, 1, nsl, c->d_gxipart.p);
-    } else
-    switch ((n + 15) / 16) {
-    case 5:
-        hipLaunchKernelGGL((k_gen_xi_gemm_rows<5>), dim3(nsplit), dim3(320), 0, c->stream, (const double *)c->d_alpha_rm.p,
-                           (const double *)c->d_gW.p, c->total, n, nsplit, c->d_gxipart.p);
-        break;
-    case 6:
-        hipLaunchKernelGGL((k_gen_xi_gemm_rows<6>), dim3(nsplit), dim3(384), 0, c->stream, (const double *)c->d_alpha_rm.p,
-                           (const double *)c->d_gW.p, c->total, n, nsplit, c->d_gxipart.p);
-        break;
-    case 7:
-        hipLaunchKernelGGL((k_gen_xi_gemm_rows<7>), dim3(nsplit), dim3(448), 0, c->stream, (const double *)c->d_alpha_rm.p,
-                           (const double *)c->d_gW.p, c->total, n, nsplit, c->d_gxipart.p);
-        break;
-    default:
-        hipLaunchKernelGGL((k_gen_xi_gemm_rows<8>), dim3(nsplit), dim3(512), 0, c->stream, (const double *)c->d_alpha_rm.p,
-                           (const double *)c->d_gW.p, c->total, n, nsplit, c->d_gxipart.p);
+        // (up to 96 states: one 96 x 96 block, 3 x 3 tiles per wavefront)
+        auto *xi = n <= 96 ? k_big_xi_gemm<3> : k_big_xi_gemm<4>;
+        BHMM_HIP(launch(xi, dim3(nsl), dim3(256), 0, c->stream, c->d_alpha_rm.p, c->d_gW.p, c->total, n, 1, nsl,
+                        c->d_gxipart.p));
+    } else {
+        const int r = (n + 15) / 16, nt = r >= 5 && r <= 7 ? r : 8; // (NT wavefronts)
+        auto *xi = nt == 5   ? k_gen_xi_gemm_rows<5>
+                   : nt == 6 ? k_gen_xi_gemm_rows<6>
+                   : nt == 7 ? k_gen_xi_gemm_rows<7>
+                             : k_gen_xi_gemm_rows<8>;
+        BHMM_HIP(launch(xi, dim3(nsplit), dim3(64 * nt), 0, c->stream, c->d_alpha_rm.p, c->d_gW.p, c->total, n, nsplit,
+                        c->d_gxipart.p));
     }
     const int64_t nfin = (int64_t)n * n + n + (KIND == EMIT_GAUSS ? 2 * n : 0) +
                          (KIND == EMIT_DISC ? (int64_t)n * c->M : 0) + n + 1;
-    hipLaunchKernelGGL((k_tile_finalize_xig<KIND>), dim3((unsigned)nfin), dim3(64), 0, c->stream, m, c->K, tp.ntiles,
-                       nsl, (const double *)c->d_gxipart.p, (const double *)c->d_partials.p,
-                       (const double *)c->d_dpartials.p, (const double *)c->d_logLk.p,
-                       (const double *)c->d_gamma0.p, stats_dev);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_tile_finalize_xig<KIND>, dim3((unsigned)nfin), dim3(64), 0, c->stream, m, c->K, tp.ntiles, nsl,
+                    c->d_gxipart.p, c->d_partials.p, c->d_dpartials.p, c->d_logLk.p, c->d_gamma0.p, stats_dev));
     return BHMM_OK;
 }
 

@@ -10,6 +10,7 @@
 
 #include "host_common.hpp"
 #include "host_internal.hpp"
+#include "launch.hpp"
 #include "plan.hpp"
 #include "wide_kernels.hpp"
 #include "tile_kernels.hpp"
@@ -113,17 +114,10 @@ static int tile_launch_fwd(bhmm_ctx *c, const WideModel &m, int which)
     }
     static const bool probe_in = probe_on && atoi(getenv("BHMM_AMD_TILE_PROBE")) == 1; // (2: kernel times only)
     lds_poison(c->stream);
-    if (c->n == 64)
-        hipLaunchKernelGGL((k_tile_fwd<4, KIND, true, true>), dim3(tp.ntiles), dim3(TILE_THREADS), 0, c->stream, m,
-                           (const int64_t *)c->d_offsets.p, sg, tp, (const void *)c->d_obs_rm.p, c->d_alpha_rm.p,
-                           c->d_wexp.p, c->d_wePseg.p, c->d_waentry.p, c->d_waexit.p, c->d_specres.p,
-                           probe_in ? probe : (unsigned long long *)nullptr);
-    else
-        hipLaunchKernelGGL((k_tile_fwd<4, KIND, false, true>), dim3(tp.ntiles), dim3(TILE_THREADS), 0, c->stream, m,
-                           (const int64_t *)c->d_offsets.p, sg, tp, (const void *)c->d_obs_rm.p, c->d_alpha_rm.p,
-                           c->d_wexp.p, c->d_wePseg.p, c->d_waentry.p, c->d_waexit.p, c->d_specres.p,
-                           probe_in ? probe : (unsigned long long *)nullptr);
-    BHMM_HIP(hipGetLastError());
+    auto *kf = c->n == 64 ? k_tile_fwd<4, KIND, true, true> : k_tile_fwd<4, KIND, false, true>;
+    BHMM_HIP(launch(kf, dim3(tp.ntiles), dim3(TILE_THREADS), 0, c->stream, m, c->d_offsets.p, sg, tp, c->d_obs_rm.p,
+                    c->d_alpha_rm.p, c->d_wexp.p, c->d_wePseg.p, c->d_waentry.p, c->d_waexit.p, c->d_specres.p,
+                    probe_in ? probe : nullptr));
     if (probe_on) {
         unsigned long long h[8];
         BHMM_HIP(hipEventRecord(c->ev[1], c->stream));
@@ -138,13 +132,10 @@ static int tile_launch_fwd(bhmm_ctx *c, const WideModel &m, int which)
                 (double)h[0] / h[3], (double)h[1] / h[3], (double)h[2] / h[3], (double)h[4] / h[7],
                 (double)h[5] / h[7], (double)h[6] / h[7], h[3]);
     }
-    hipLaunchKernelGGL(k_tile_logl, dim3((sg.nseg + 15) / 16), dim3(256), 0, c->stream, sg, c->n,
-                       (const double *)c->d_waentry.p, (const double *)c->d_waexit.p,
-                       (const int32_t *)c->d_wePseg.p, c->d_wlogLseg.p, c->d_specres.p);
-    hipLaunchKernelGGL(k_logl, dim3(c->K), dim3(64), 0, c->stream,
-                       (const int32_t *)c->d_wseg_traj0[which].p, c->K,
-                       (const double *)c->d_wlogLseg.p, c->d_logLk.p);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_tile_logl, dim3((sg.nseg + 15) / 16), dim3(256), 0, c->stream, sg, c->n, c->d_waentry.p,
+                    c->d_waexit.p, c->d_wePseg.p, c->d_wlogLseg.p, c->d_specres.p));
+    BHMM_HIP(launch(k_logl, dim3(c->K), dim3(64), 0, c->stream, c->d_wseg_traj0[which].p, c->K, c->d_wlogLseg.p,
+                    c->d_logLk.p));
     return BHMM_OK;
 }
 
@@ -153,7 +144,7 @@ static int tile_launch_bwd(bhmm_ctx *c, const WideModel &m, int which, bool stor
 {
     const Segs sg = segs_of(c, which);
     const TilePlan tp{c->d_tile_segb[which].p, c->w_ntilesb[which]};
-    double *gam = store_gamma ? c->d_gamma_ci.p : (double *)nullptr;
+    double *gam = store_gamma ? c->d_gamma_ci.p : nullptr;
     static const bool probe_on = getenv("BHMM_AMD_TILE_PROBE") != nullptr;
     unsigned long long *probe = nullptr;
     if (probe_on) {
@@ -165,21 +156,11 @@ static int tile_launch_bwd(bhmm_ctx *c, const WideModel &m, int which, bool stor
         BHMM_HIP(hipEventRecord(c->ev[5], c->stream));
     }
     lds_poison(c->stream);
-    if (c->n == 64)
-        hipLaunchKernelGGL((k_tile_bwd<4, KIND, true, false, true>), dim3(tp.ntiles), dim3(TILE_THREADS), 0, c->stream, m,
-                           (const int64_t *)c->d_offsets.p, sg, tp, (const void *)c->d_obs_rm.p,
-                           (const double *)c->d_alpha_rm.p, (const int32_t *)c->d_wexp.p, gam, c->d_gamma0.p,
-                           c->d_partials.p, c->d_dpartials.p, c->d_wbexit.p, c->d_wbentry.p, c->d_specres.p,
-                           (double *)nullptr,
-                           atoi(getenv("BHMM_AMD_TILE_PROBE") ? getenv("BHMM_AMD_TILE_PROBE") : "0") == 1 ? probe : (unsigned long long *)nullptr);
-    else
-        hipLaunchKernelGGL((k_tile_bwd<4, KIND, false, false, true>), dim3(tp.ntiles), dim3(TILE_THREADS), 0, c->stream, m,
-                           (const int64_t *)c->d_offsets.p, sg, tp, (const void *)c->d_obs_rm.p,
-                           (const double *)c->d_alpha_rm.p, (const int32_t *)c->d_wexp.p, gam, c->d_gamma0.p,
-                           c->d_partials.p, c->d_dpartials.p, c->d_wbexit.p, c->d_wbentry.p, c->d_specres.p,
-                           (double *)nullptr,
-                           atoi(getenv("BHMM_AMD_TILE_PROBE") ? getenv("BHMM_AMD_TILE_PROBE") : "0") == 1 ? probe : (unsigned long long *)nullptr);
-    BHMM_HIP(hipGetLastError());
+    const bool probe_in = atoi(getenv("BHMM_AMD_TILE_PROBE") ? getenv("BHMM_AMD_TILE_PROBE") : "0") == 1;
+    auto *kb = c->n == 64 ? k_tile_bwd<4, KIND, true, false, true> : k_tile_bwd<4, KIND, false, false, true>;
+    BHMM_HIP(launch(kb, dim3(tp.ntiles), dim3(TILE_THREADS), 0, c->stream, m, c->d_offsets.p, sg, tp, c->d_obs_rm.p,
+                    c->d_alpha_rm.p, c->d_wexp.p, gam, c->d_gamma0.p, c->d_partials.p, c->d_dpartials.p,
+                    c->d_wbexit.p, c->d_wbentry.p, c->d_specres.p, nullptr, probe_in ? probe : nullptr));
     if (probe_on) {
         unsigned long long h[16];
         BHMM_HIP(hipEventRecord(c->ev[3], c->stream));
@@ -197,10 +178,8 @@ static int tile_launch_bwd(bhmm_ctx *c, const WideModel &m, int which, bool stor
     const int n = c->n;
     const int nfin = n * n + n + (KIND == EMIT_GAUSS ? 2 * n : 0) + (KIND == EMIT_DISC ? n * c->M : 0) +
                      n + 1;
-    hipLaunchKernelGGL((k_wide_finalize<KIND>), dim3(nfin), dim3(64), 0, c->stream, m, c->K, tp.ntiles,
-                       4 * tp.ntiles, (const double *)c->d_partials.p, (const double *)c->d_dpartials.p,
-                       (const double *)c->d_logLk.p, (const double *)c->d_gamma0.p, stats_dev);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_wide_finalize<KIND>, dim3(nfin), dim3(64), 0, c->stream, m, c->K, tp.ntiles, 4 * tp.ntiles,
+                    c->d_partials.p, c->d_dpartials.p, c->d_logLk.p, c->d_gamma0.p, stats_dev));
     return BHMM_OK;
 }
 
@@ -212,26 +191,13 @@ static int wide_launch_fwd(bhmm_ctx *c, const WideModel &m, int which, bool lazy
         return tile_launch_fwd<KIND>(c, m, which);
     which = wide_fwd_plan(c, which);
     const Segs sg = segs_of(c, which);
-    if (lazy && NP == 64 && c->n == 64) // the shape of BASELINE configs[3]
-        hipLaunchKernelGGL((k_wide_fwd<NP, KIND, true, NP == 64>), dim3((sg.nseg + GP - 1) / GP),
-                           dim3(64), 0, c->stream, m, (const int64_t *)c->d_offsets.p, sg,
-                           (const void *)c->d_obs_rm.p, c->d_alpha_rm.p, c->d_wlogLseg.p,
-                           c->d_waentry.p, c->d_waexit.p, c->d_specres.p);
-    else if (lazy)
-        hipLaunchKernelGGL((k_wide_fwd<NP, KIND, true>), dim3((sg.nseg + GP - 1) / GP), dim3(64), 0,
-                           c->stream, m, (const int64_t *)c->d_offsets.p, sg,
-                           (const void *)c->d_obs_rm.p, c->d_alpha_rm.p, c->d_wlogLseg.p,
-                           c->d_waentry.p, c->d_waexit.p, c->d_specres.p);
-    else
-        hipLaunchKernelGGL((k_wide_fwd<NP, KIND, false>), dim3((sg.nseg + GP - 1) / GP), dim3(64), 0,
-                           c->stream, m, (const int64_t *)c->d_offsets.p, sg,
-                           (const void *)c->d_obs_rm.p, c->d_alpha_rm.p, c->d_wlogLseg.p,
-                           c->d_waentry.p, c->d_waexit.p, (unsigned int *)nullptr);
-    BHMM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_logl, dim3(c->K), dim3(64), 0, c->stream,
-                       (const int32_t *)c->d_wseg_traj0[which].p, c->K,
-                       (const double *)c->d_wlogLseg.p, c->d_logLk.p);
-    BHMM_HIP(hipGetLastError());
+    auto *k = lazy && NP == 64 && c->n == 64 ? k_wide_fwd<NP, KIND, true, NP == 64> // the shape of BASELINE configs[3]
+              : lazy                         ? k_wide_fwd<NP, KIND, true>
+                                             : k_wide_fwd<NP, KIND, false>;
+    BHMM_HIP(launch(k, dim3((sg.nseg + GP - 1) / GP), dim3(64), 0, c->stream, m, c->d_offsets.p, sg, c->d_obs_rm.p,
+                    c->d_alpha_rm.p, c->d_wlogLseg.p, c->d_waentry.p, c->d_waexit.p, lazy ? c->d_specres.p : nullptr));
+    BHMM_HIP(launch(k_logl, dim3(c->K), dim3(64), 0, c->stream, c->d_wseg_traj0[which].p, c->K, c->d_wlogLseg.p,
+                    c->d_logLk.p));
     return BHMM_OK;
 }
 
@@ -245,7 +211,8 @@ static int wide_launch_bwd(bhmm_ctx *c, const WideModel &m, int which, bool stor
     const Segs sg = segs_of(c, which);
     // A's rows in LDS for fewer than 64 lanes per segment; the 64-lane kernel keeps them in VGPRs
     const size_t sm = NP == 64 ? 0 : (size_t)(NP * wide_pitch(NP)) * sizeof(double);
-    double *gam = store_gamma ? c->d_gamma_ci.p : (double *)nullptr;
+    const dim3 grid((sg.nseg + GP - 1) / GP);
+    double *gam = store_gamma ? c->d_gamma_ci.p : nullptr;
     // control experiment: xi counts as a separate time-parallel GEMM
     static const bool xi_gemm = getenv("BHMM_AMD_WIDE_XI_GEMM") != nullptr;
     if (lazy && NP == 64 && c->n == 64 && xi_gemm) {
@@ -253,44 +220,26 @@ static int wide_launch_bwd(bhmm_ctx *c, const WideModel &m, int which, bool stor
         int rc;
         if ((rc = c->d_gW.ensure((size_t)c->total * 64)) || (rc = c->d_gxipart.ensure((size_t)nsplit * 4096)))
             return rc;
-        hipLaunchKernelGGL(k_wide_zero_last_rows, dim3(c->K), dim3(64), 0, c->stream,
-                           (const int64_t *)c->d_offsets.p, c->K, 64, c->d_gW.p);
-        hipLaunchKernelGGL((k_wide_bwd<NP, KIND, true, NP == 64, NP == 64>), dim3((sg.nseg + GP - 1) / GP),
-                           dim3(64), sm, c->stream, m, (const int64_t *)c->d_offsets.p, sg,
-                           (const void *)c->d_obs_rm.p, (const double *)c->d_alpha_rm.p, gam,
-                           c->d_gamma0.p, c->d_partials.p, c->d_dpartials.p, c->d_wbexit.p,
-                           c->d_wbentry.p, c->d_specres.p, c->d_gW.p);
-        hipLaunchKernelGGL(k_wide_xi_gemm64, dim3(nsplit), dim3(64), 0, c->stream,
-                           (const double *)c->d_alpha_rm.p, (const double *)c->d_gW.p, c->total, nsplit,
-                           c->d_gxipart.p);
-        hipLaunchKernelGGL(k_wide_xi_reduce, dim3(16), dim3(256), 0, c->stream,
-                           (const double *)c->d_gxipart.p, nsplit, c->d_partials.p);
-    } else if (lazy && NP == 64 && c->n == 64)
-        hipLaunchKernelGGL((k_wide_bwd<NP, KIND, true, NP == 64>), dim3((sg.nseg + GP - 1) / GP),
-                           dim3(64), sm, c->stream, m, (const int64_t *)c->d_offsets.p, sg,
-                           (const void *)c->d_obs_rm.p, (const double *)c->d_alpha_rm.p, gam,
-                           c->d_gamma0.p, c->d_partials.p, c->d_dpartials.p, c->d_wbexit.p,
-                           c->d_wbentry.p, c->d_specres.p);
-    else if (lazy)
-        hipLaunchKernelGGL((k_wide_bwd<NP, KIND, true>), dim3((sg.nseg + GP - 1) / GP), dim3(64), sm,
-                           c->stream, m, (const int64_t *)c->d_offsets.p, sg,
-                           (const void *)c->d_obs_rm.p, (const double *)c->d_alpha_rm.p, gam,
-                           c->d_gamma0.p, c->d_partials.p, c->d_dpartials.p, c->d_wbexit.p,
-                           c->d_wbentry.p, c->d_specres.p);
-    else
-        hipLaunchKernelGGL((k_wide_bwd<NP, KIND, false>), dim3((sg.nseg + GP - 1) / GP), dim3(64), sm,
-                           c->stream, m, (const int64_t *)c->d_offsets.p, sg,
-                           (const void *)c->d_obs_rm.p, (const double *)c->d_alpha_rm.p, gam,
-                           c->d_gamma0.p, c->d_partials.p, c->d_dpartials.p, c->d_wbexit.p,
-                           c->d_wbentry.p, (unsigned int *)nullptr);
-    BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_wide_zero_last_rows, dim3(c->K), dim3(64), 0, c->stream, c->d_offsets.p, c->K, 64, c->d_gW.p));
+        BHMM_HIP(launch(k_wide_bwd<NP, KIND, true, NP == 64, NP == 64>, grid, dim3(64), sm, c->stream, m, c->d_offsets.p,
+                        sg, c->d_obs_rm.p, c->d_alpha_rm.p, gam, c->d_gamma0.p, c->d_partials.p, c->d_dpartials.p,
+                        c->d_wbexit.p, c->d_wbentry.p, c->d_specres.p, c->d_gW.p));
+        BHMM_HIP(launch(k_wide_xi_gemm64, dim3(nsplit), dim3(64), 0, c->stream, c->d_alpha_rm.p, c->d_gW.p, c->total,
+                        nsplit, c->d_gxipart.p));
+        BHMM_HIP(launch(k_wide_xi_reduce, dim3(16), dim3(256), 0, c->stream, c->d_gxipart.p, nsplit, c->d_partials.p));
+    } else {
+        auto *k = lazy && NP == 64 && c->n == 64 ? k_wide_bwd<NP, KIND, true, NP == 64>
+                  : lazy                         ? k_wide_bwd<NP, KIND, true>
+                                                 : k_wide_bwd<NP, KIND, false>;
+        BHMM_HIP(launch(k, grid, dim3(64), sm, c->stream, m, c->d_offsets.p, sg, c->d_obs_rm.p, c->d_alpha_rm.p, gam,
+                        c->d_gamma0.p, c->d_partials.p, c->d_dpartials.p, c->d_wbexit.p, c->d_wbentry.p,
+                        lazy ? c->d_specres.p : nullptr, nullptr));
+    }
     const int n = c->n;
     const int nfin = n * n + n + (KIND == EMIT_GAUSS ? 2 * n : 0) + (KIND == EMIT_DISC ? n * c->M : 0) +
                      n + 1;
-    hipLaunchKernelGGL((k_wide_finalize<KIND>), dim3(nfin), dim3(64), 0, c->stream, m, c->K, sg.nseg,
-                       sg.nseg, (const double *)c->d_partials.p, (const double *)c->d_dpartials.p,
-                       (const double *)c->d_logLk.p, (const double *)c->d_gamma0.p, stats_dev);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_wide_finalize<KIND>, dim3(nfin), dim3(64), 0, c->stream, m, c->K, sg.nseg, sg.nseg,
+                    c->d_partials.p, c->d_dpartials.p, c->d_logLk.p, c->d_gamma0.p, stats_dev));
     return BHMM_OK;
 }
 
@@ -459,9 +408,8 @@ static int wide_probe_run(bhmm_ctx *c, const WideModel &m, int *W_out)
                             c->stream));
     BHMM_HIP(hipMemsetAsync(d_curve, 0, 2 * (size_t)Wmax * sizeof(unsigned int), c->stream));
     constexpr int GP = 64 / NP;
-    hipLaunchKernelGGL((k_wide_probe<NP, KIND>), dim3((2 * S + GP - 1) / GP), dim3(64), 0, c->stream, m,
-                       (const void *)c->d_obs_rm.p, (const int64_t *)d_starts, S, Wmax, d_curve);
-    BHMM_HIP(hipGetLastError());
+    BHMM_HIP(launch(k_wide_probe<NP, KIND>, dim3((2 * S + GP - 1) / GP), dim3(64), 0, c->stream, m, c->d_obs_rm.p,
+                    d_starts, S, Wmax, d_curve));
     std::vector<float> curve(2 * (size_t)Wmax);
     BHMM_HIP(hipMemcpyAsync(curve.data(), d_curve, curve.size() * sizeof(float), hipMemcpyDeviceToHost,
                             c->stream));
@@ -571,10 +519,8 @@ int wide_forward_draw(bhmm_ctx *c, const double *A, const double *pi, const doub
             if (rc)
                 return rc;
             const Segs sgf = segs_of(c, wide_fwd_plan(c, 1));
-            hipLaunchKernelGGL(k_wide_check, dim3((sgf.nseg + 15) / 16), dim3(256), 0, c->stream, sgf,
-                               c->n, (const double *)c->d_waentry.p, (const double *)c->d_waexit.p,
-                               (const double *)nullptr, (const double *)nullptr, 1e-11, c->d_specres.p);
-            BHMM_HIP(hipGetLastError());
+            BHMM_HIP(launch(k_wide_check, dim3((sgf.nseg + 15) / 16), dim3(256), 0, c->stream, sgf, c->n,
+                            c->d_waentry.p, c->d_waexit.p, nullptr, nullptr, 1e-11, c->d_specres.p));
             BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 3 * sizeof(unsigned int),
                                     hipMemcpyDeviceToHost, c->stream));
             BHMM_HIP(hipStreamSynchronize(c->stream));
@@ -642,14 +588,10 @@ int wide_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par
         if ((rc = run(1, lazy)))
             return rc;
         const Segs sgs = segs_of(c, 1), sgf = segs_of(c, wide_fwd_plan(c, 1));
-        hipLaunchKernelGGL(k_wide_check, dim3((sgf.nseg + 15) / 16), dim3(256), 0, c->stream, sgf,
-                           c->n, (const double *)c->d_waentry.p, (const double *)c->d_waexit.p,
-                           (const double *)nullptr, (const double *)nullptr, 1e-11, c->d_specres.p);
-        hipLaunchKernelGGL(k_wide_check, dim3((sgs.nseg + 15) / 16), dim3(256), 0, c->stream, sgs,
-                           c->n, (const double *)nullptr, (const double *)nullptr,
-                           (const double *)c->d_wbexit.p, (const double *)c->d_wbentry.p, 1e-11,
-                           c->d_specres.p);
-        BHMM_HIP(hipGetLastError());
+        BHMM_HIP(launch(k_wide_check, dim3((sgf.nseg + 15) / 16), dim3(256), 0, c->stream, sgf, c->n, c->d_waentry.p,
+                        c->d_waexit.p, nullptr, nullptr, 1e-11, c->d_specres.p));
+        BHMM_HIP(launch(k_wide_check, dim3((sgs.nseg + 15) / 16), dim3(256), 0, c->stream, sgs, c->n, nullptr, nullptr,
+                        c->d_wbexit.p, c->d_wbentry.p, 1e-11, c->d_specres.p));
         BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 3 * sizeof(unsigned int),
                                 hipMemcpyDeviceToHost, c->stream));
         // the statistics (and, for moderately many trajectories, the log-likelihoods) travel with the verdict
@@ -782,16 +724,8 @@ int wide_backward(bhmm_ctx *c, const double *A)
     const size_t sm = (size_t)(NP * wide_pitch(NP) + GP * NP) * sizeof(double);
     const dim3 grid((c->K + GP - 1) / GP), blk(64);
     const double *pobs = reinterpret_cast<const double *>(c->d_obs_rm.p);
-    if (NP == 16)
-        hipLaunchKernelGGL((k_wide_beta<16>), grid, blk, sm, c->stream, m,
-                           (const int64_t *)c->d_offsets.p, c->K, pobs, c->d_alpha_rm.p);
-    else if (NP == 32)
-        hipLaunchKernelGGL((k_wide_beta<32>), grid, blk, sm, c->stream, m,
-                           (const int64_t *)c->d_offsets.p, c->K, pobs, c->d_alpha_rm.p);
-    else
-        hipLaunchKernelGGL((k_wide_beta<64>), grid, blk, sm, c->stream, m,
-                           (const int64_t *)c->d_offsets.p, c->K, pobs, c->d_alpha_rm.p);
-    BHMM_HIP(hipGetLastError());
+    auto *k = NP == 16 ? k_wide_beta<16> : NP == 32 ? k_wide_beta<32> : k_wide_beta<64>;
+    BHMM_HIP(launch(k, grid, blk, sm, c->stream, m, c->d_offsets.p, c->K, pobs, c->d_alpha_rm.p));
     return BHMM_OK;
 }
 
@@ -829,18 +763,10 @@ int wide_transition_counts(double *C, const double *A, const double *pobs, const
     if (e == hipSuccess) {
         const size_t sm = (size_t)(NP * wide_pitch(NP) + GP * NP) * sizeof(double);
         const dim3 grid((nslab + GP - 1) / GP), blk(64);
-        if (NP == 16)
-            hipLaunchKernelGGL((k_wide_xi<16>), grid, blk, sm, 0, (const double *)dA, (const double *)dp,
-                               (const double *)da, (const double *)db, n, T, nslab, dpart);
-        else if (NP == 32)
-            hipLaunchKernelGGL((k_wide_xi<32>), grid, blk, sm, 0, (const double *)dA, (const double *)dp,
-                               (const double *)da, (const double *)db, n, T, nslab, dpart);
-        else
-            hipLaunchKernelGGL((k_wide_xi<64>), grid, blk, sm, 0, (const double *)dA, (const double *)dp,
-                               (const double *)da, (const double *)db, n, T, nslab, dpart);
-        hipLaunchKernelGGL(k_wide_xi_sum, dim3(n * n), dim3(64), 0, 0, (const double *)dA,
-                           (const double *)dpart, n, nslab, dC);
-        e = hipGetLastError();
+        auto *k = NP == 16 ? k_wide_xi<16> : NP == 32 ? k_wide_xi<32> : k_wide_xi<64>;
+        e = launch(k, grid, blk, sm, 0, dA, dp, da, db, n, T, nslab, dpart);
+        if (e == hipSuccess)
+            e = launch(k_wide_xi_sum, dim3(n * n), dim3(64), 0, 0, dA, dpart, n, nslab, dC);
     }
     if (e == hipSuccess) e = hipMemcpy(C, dC, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost);
     cleanup();
