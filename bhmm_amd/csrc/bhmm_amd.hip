@@ -43,6 +43,38 @@ Chunks chunks_of(const bhmm_ctx *c)
     return ch;
 }
 
+int64_t longest_traj(const bhmm_ctx *c)
+{
+    int64_t maxT = 0;
+    for (int k = 0; k < c->K; ++k)
+        maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
+    return maxT;
+}
+
+int ensure_specres(bhmm_ctx *c, size_t words)
+{
+    if (int rc = c->d_specres.ensure(words))
+        return rc;
+    if (!c->h_specres)
+        BHMM_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_specres), 4 * sizeof(unsigned int), hipHostMallocDefault));
+    return BHMM_OK;
+}
+
+int specres_reset(bhmm_ctx *c, int words)
+{
+    BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, words * sizeof(unsigned int), c->stream));
+    return BHMM_OK;
+}
+
+int specres_read(bhmm_ctx *c, int words, bool wait)
+{
+    BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, words * sizeof(unsigned int), hipMemcpyDeviceToHost,
+                            c->stream));
+    if (wait)
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+    return BHMM_OK;
+}
+
 template <int N, int KIND>
 static size_t smem_fwdbwd(int M, int dcopies = 1)
 {
@@ -309,9 +341,7 @@ struct Runner {
         if (!(target > 0.0))
             target = 0.01 * c->opt.spec_tol; // (default: 1e-13)
         *W_out = 0;
-        int64_t maxT = 0;
-        for (int k = 0; k < c->K; ++k)
-            maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
+        const int64_t maxT = longest_traj(c);
         const int Wmax = (int)std::min<int64_t>(1024, maxT / 2) / 4 * 4;
         if (Wmax < 32)
             return BHMM_OK;
@@ -538,8 +568,8 @@ struct Runner {
         BHMM_HIP(launch(k_spec_check<N>, dim3((c->G + 255) / 256), dim3(256), 0, c->stream, chunks_of(c), c->G,
                         c->d_aentry.p, c->d_aexit.p, with_beta ? c->d_bexit.p : nullptr, c->d_bentry.p, SPEC_TOL,
                         c->d_specres.p));
-        BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
-                                hipMemcpyDeviceToHost, c->stream));
+        if (int rc = specres_read(c, 4, false))
+            return rc;
         c->prefetched = false;
         if (stats_src) { // the results ride on the same synchronisation as the verdict
             const int S = stats_size(c);
@@ -634,17 +664,12 @@ struct Runner {
         int rc;
         if ((rc = c->d_aexit.ensure((size_t)c->Gp * N)) || (rc = c->d_bentry.ensure((size_t)c->Gp * N)) ||
 #ifdef ESTEP_CLOCKPROBE
-            (rc = c->d_specres.ensure(4 + 16 * (size_t)(c->Gp / 64))))
+            (rc = ensure_specres(c, 4 + 16 * (size_t)(c->Gp / 64))))
 #else
-            (rc = c->d_specres.ensure(4)))
+            (rc = ensure_specres(c)))
 #endif
             return rc;
-        if (!c->h_specres)
-            BHMM_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_specres), 4 * sizeof(unsigned int),
-                                   hipHostMallocDefault));
-        if (clear_words)
-            BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
-        return BHMM_OK;
+        return clear_words ? specres_reset(c) : BHMM_OK;
     }
 
     // forward sweep only with k_estep<..., FWDONLY> (alpha rows up to a power of two)
@@ -702,8 +727,8 @@ struct Runner {
                     // results (forward_ci_verdict): one host round trip less per Gibbs sweep
                     BHMM_HIP(launch(k_spec_check<N>, dim3((c->G + 255) / 256), dim3(256), 0, c->stream, chunks_of(c),
                                     c->G, c->d_aentry.p, c->d_aexit.p, nullptr, c->d_bentry.p, SPEC_TOL, c->d_specres.p));
-                    BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
-                                            hipMemcpyDeviceToHost, c->stream));
+                    if ((rc = specres_read(c, 4, false)))
+                        return rc;
                     c->prefetched = false;
                     c->fwd_pending = true;
                     return BHMM_OK;
@@ -1659,9 +1684,7 @@ static int nonfinite_retry(bhmm_ctx *c, bool *retried)
     bool finite = true;
     for (int e = 0; e < ncheck; ++e)
         finite = finite && std::isfinite(c->h_pinned[e]);
-    int64_t maxT = 0;
-    for (int k = 0; k < c->K; ++k)
-        maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
+    const int64_t maxT = longest_traj(c);
     if (finite || !std::isfinite(c->h_pinned[0]) || maxT >= ((int64_t)1 << 30))
         return BHMM_OK;
     c->ds.serial_retry_done = true;

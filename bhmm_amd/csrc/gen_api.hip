@@ -197,17 +197,31 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
     uint16_t *ptr = reinterpret_cast<uint16_t *>(c->d_scratch.p);
     int32_t *last = reinterpret_cast<int32_t *>(c->d_scratch2.p);
     int32_t *path = last + K;
-    // up to 128 states: over time segments (k_gen_viterbi_seg), accepted only when every segment started
-    // from the bit pattern its predecessor computed -- then the back-pointers are the serial run's
+    uint8_t *ptr8 = reinterpret_cast<uint8_t *>(c->d_scratch.p);
+    uint8_t *p8 = out_fmt == 2 ? static_cast<uint8_t *>(paths_out) : reinterpret_cast<uint8_t *>(path);
+    const int64_t *off = c->d_offsets.p;
+    const int64_t maxT = longest_traj(c);
+    const int W0 = std::max(64, c->ds.spec_W > 0 ? (c->ds.spec_W + 7) / 8 * 8 : 128);
+    // back-trace over the segments of plan 0: maps, stitch, apply (NC: column tiles of the back-pointer maps)
+    auto walks_of = [&](const Segs &sg, auto ncc) -> int {
+        constexpr int NC = decltype(ncc)::value;
+        int rcw;
+        if ((rcw = c->d_vmaps.ensure((size_t)sg.nseg * 64 * NC)) || (rcw = c->d_vend.ensure((size_t)sg.nseg)))
+            return rcw;
+        BHMM_HIP(launch(k_wide_vit_walk<false, uint8_t, NC>, dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n, ptr8,
+                        c->d_vmaps.p, nullptr, nullptr));
+        BHMM_HIP(launch(k_wide_vit_stitch, dim3((K + 63) / 64), dim3(64), 0, c->stream, c->pplan_buf[0].traj0.p, K,
+                        c->d_vmaps.p, 64 * NC, last, c->d_vend.p));
+        auto walk = [&](auto *k, auto *out) {
+            return launch(k, dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n, ptr8, nullptr, c->d_vend.p, out);
+        };
+        BHMM_HIP(out_fmt == 0 ? walk(k_wide_vit_walk<true, int32_t, NC>, path) : walk(k_wide_vit_walk<true, uint8_t, NC>, p8));
+        return BHMM_OK;
+    };
+    // up to 128 states: over time segments (k_gen_viterbi_seg), accepted by seg_viterbi (path_api.hip)
     if (n <= 128 && c->opt.spec_enabled && !c->ds.vit_seg_given_up) {
         bool done = false;
-        uint8_t *ptr8 = reinterpret_cast<uint8_t *>(c->d_scratch.p);
         const size_t smv = (size_t)(128 * GVS_PITCH + 8 * 128) * sizeof(double);
-        if ((rc = c->d_specres.ensure(4)))
-            return rc;
-        if (!c->h_specres)
-            BHMM_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_specres), 4 * sizeof(unsigned int),
-                                   hipHostMallocDefault));
         // warm-up: the max-product survivors of these larger models meet later than the filter forgets (128
         // states, 128 x 10 000: 236 of 2048 boundaries further than 1e-12 apart after the E-step's 120 steps, 4
         // after 240, none after 480), and a fix-up round costs half a first pass here: four times the E-step's
@@ -215,7 +229,6 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
         // -- but never longer than the segments that fill the chip (a slowly forgetting model keeps the E-step's
         // length and its segment count; the rounds then do what the margins cannot)
         const int seg_warmups = c->opt.vit_margin ? 1 : c->opt.vit_seg_warmups;
-        const int W0 = std::max(64, c->ds.spec_W > 0 ? (c->ds.spec_W + 7) / 8 * 8 : 128);
         const int64_t fill0 = ((c->total + (int64_t)c->opt.vit_seg_per_simd * c->num_simd - 1) /
                                ((int64_t)c->opt.vit_seg_per_simd * c->num_simd) + 7) / 8 * 8;
         // (round 6: with the mending round the E-step's length is where the margin route starts too -- the few
@@ -223,45 +236,23 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
         // that fourfold, when a pass could not be mended or needed three or more rounds)
         const int W_cap = (int)std::max<int64_t>(W0, std::min<int64_t>(4 * (int64_t)W0, fill0));
         int W_try = c->ds.vit_W > 0 ? c->ds.vit_W : ((c->opt.vit_margin && !c->opt.vit_mend) ? W_cap : W0);
-        Segs sg;
-        // the path-margin acceptance of the first pass (k_vit_margin, path_kernels.hpp; see wide_viterbi_run)
-        const double vm_tol = 1e-12;
+        // the path-margin acceptance of the first pass (k_vit_margin, path_kernels.hpp)
         double *vall = nullptr;
-        int64_t maxT = 0;
         const size_t smm = (size_t)n * (n | 1) * sizeof(double); // (odd pitch, k_vit_margin)
         if (c->opt.vit_margin && c->d_gW.ensure((size_t)c->total * n) == BHMM_OK &&
             allow_lds(k_vit_margin<int32_t, 2>, smm) == hipSuccess &&
-            allow_lds(k_vit_margin<uint8_t, 2>, smm) == hipSuccess) {
+            allow_lds(k_vit_margin<uint8_t, 2>, smm) == hipSuccess)
             vall = c->d_gW.p;
-            for (int k = 0; k < K; ++k)
-                maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
-        } else {
+        else
             (void)hipGetLastError();
-        }
         c->last.vit_margin_used = 0;
         c->last.vit_margin_close = 0;
-        const int64_t *off = c->d_offsets.p;
-        uint8_t *p8 = out_fmt == 2 ? static_cast<uint8_t *>(paths_out) : reinterpret_cast<uint8_t *>(path);
-        // back-trace over the segments: maps, stitch, apply
-        auto seg_walks = [&]() -> int {
-            int rcw;
-            if ((rcw = c->d_vmaps.ensure((size_t)sg.nseg * 128)) || (rcw = c->d_vend.ensure((size_t)sg.nseg)))
-                return rcw;
-            BHMM_HIP(launch(k_wide_vit_walk<false, uint8_t, 2>, dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n, ptr8,
-                            c->d_vmaps.p, nullptr, nullptr));
-            BHMM_HIP(launch(k_wide_vit_stitch, dim3((K + 63) / 64), dim3(64), 0, c->stream, c->pplan_buf[0].traj0.p, K,
-                            c->d_vmaps.p, 128, last, c->d_vend.p));
-            auto walk = [&](auto *k, auto *out) {
-                return launch(k, dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n, ptr8, nullptr, c->d_vend.p, out);
-            };
-            BHMM_HIP(out_fmt == 0 ? walk(k_wide_vit_walk<true, int32_t, 2>, path) : walk(k_wide_vit_walk<true, uint8_t, 2>, p8));
-            return BHMM_OK;
-        };
         for (int attempt = 0; attempt < 2 && !done; ++attempt) {
             if (attempt > 0)
                 W_try *= 2;
             const int64_t want = (int64_t)c->opt.vit_seg_per_simd * c->num_simd;
             const int64_t seglen = std::max<int64_t>((c->total + want - 1) / want, seg_warmups * (int64_t)W_try);
+            Segs sg;
             if ((rc = wide_path_plan(c, 0, seglen, sg)))
                 return rc;
             if (sg.nseg <= K)
@@ -271,113 +262,53 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
                 (rc = c->d_vckpt.ensure(((size_t)(c->total >> 6) + 1) * 128)) || (rc = c->d_vflag.ensure(2 * (size_t)sg.nseg)))
                 return rc;
             const dim3 sgrid((sg.nseg + 7) / 8), sblk(512);
-            int round = 0;
-            bool margin_accepted = false;
-            bool allow_mend = c->opt.vit_mend, mended = false;
-            c->last.vit_mended = 0;
-            for (; round <= 12; ++round) {
-                BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
-                lds_poison(c->stream);
-                auto *kv = round == 0 ? k_gen_viterbi_seg<false> : k_gen_viterbi_seg<true>;
-                BHMM_HIP(launch(kv, sgrid, sblk, smv, c->stream, m, c->d_offsets.p, sg, pobs, ptr8, last, c->d_aentry.p,
-                                c->d_aexit.p, c->d_vckpt.p, c->d_vflag.p, round == 0 ? vall : nullptr, 0.0, nullptr));
+            SegViterbi f;
+            f.pass = [&](bool fix) -> int {
+                BHMM_HIP(launch(fix ? k_gen_viterbi_seg<true> : k_gen_viterbi_seg<false>, sgrid, sblk, smv, c->stream, m,
+                                off, sg, pobs, ptr8, last, c->d_aentry.p, c->d_aexit.p, c->d_vckpt.p, c->d_vflag.p,
+                                fix ? nullptr : vall, 0.0, nullptr));
                 BHMM_HIP(launch(k_wide_vit_check<128>, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
-                                c->d_aentry.p, c->d_aexit.p, c->d_vflag.p, c->d_specres.p,
-                                (round == 0 && vall) ? vm_tol : 0.0));
-                BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
-                                        hipMemcpyDeviceToHost, c->stream));
-                BHMM_HIP(hipStreamSynchronize(c->stream));
-                if (round == 0) {
-                    c->last.vit_seg_mismatch = (int)c->h_specres[3];
-                    c->last.vit_far = (int)c->h_specres[0];
-                }
-                if (c->h_specres[3] == 0)
-                    break;
-                int spliced = 0;
-                if (round == 0 && vall && c->h_specres[0] != 0 && (int64_t)c->h_specres[0] * 2 <= sg.nseg && allow_mend) {
-                    // the mending round of wide_viterbi_run (path_api.hip): the segments further than vm_tol from their
-                    // predecessors' vectors alone run again up to a kept vector of the first pass
-                    mended = true;
-                    BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
-                    lds_poison(c->stream);
-                    BHMM_HIP(launch(k_gen_viterbi_seg<true>, sgrid, sblk, smv, c->stream, m, c->d_offsets.p, sg, pobs, ptr8,
-                                    last, c->d_aentry.p, c->d_aexit.p, c->d_vckpt.p, c->d_vflag.p + sg.nseg, vall, vm_tol,
-                                    c->d_specres.p + 1));
-                    unsigned int notmet = 0;
-                    BHMM_HIP(hipMemcpyAsync(&notmet, c->d_specres.p + 1, sizeof(unsigned int), hipMemcpyDeviceToHost,
-                                            c->stream));
-                    BHMM_HIP(hipStreamSynchronize(c->stream));
-                    c->last.vit_mended = (int)c->h_specres[0];
-                    if (notmet == 0) {
-                        spliced = (int)c->h_specres[0];
-                        c->h_specres[0] = 0;
-                    }
-                }
-                if (round == 0 && vall && c->h_specres[0] == 0) {
-                    // every boundary (and splice) within vm_tol: the path of this pass, and the margins of the decisions on it
-                    const int maxseg = (int)((maxT + seglen - 1) / seglen) + 1 + spliced;
-                    const double margin = std::max(1e-10, 16.0 * (2e-15 * (double)maxT + vm_tol * maxseg));
-                    if ((rc = seg_walks()))
-                        return rc;
-                    BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
-                    const dim3 mgrid(sg.nseg, (unsigned)((c->ds.pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
-                    auto margins = [&](auto *k, auto *p) {
-                        return launch(k, mgrid, dim3(256), smm, c->stream, m.A, n, off, sg, vall, p, margin, c->d_specres.p);
-                    };
-                    BHMM_HIP(out_fmt == 0 ? margins(k_vit_margin<int32_t, 2>, path) : margins(k_vit_margin<uint8_t, 2>, p8));
-                    BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
-                                            hipMemcpyDeviceToHost, c->stream));
-                    BHMM_HIP(hipStreamSynchronize(c->stream));
-                    c->last.vit_margin_close = (int)c->h_specres[2];
-                    if (c->h_specres[2] == 0) {
-                        c->last.vit_margin_used = 1;
-                        margin_accepted = true;
-                        break;
-                    }
-                    // (a close decision on the path: the rounds decide)
-                }
-                if (round == 0 && mended) {
-                    // (the rounds compare bitwise with the kept vectors: a pass that was mended and then not accepted is
-                    // run again from scratch, without mending -- see wide_viterbi_run)
-                    allow_mend = false;
-                    mended = false;
-                    round = -1;
-                }
-            }
-            c->last.vit_seg_rounds = round;
-            if (c->h_specres[3] == 0 || margin_accepted) {
+                                c->d_aentry.p, c->d_aexit.p, c->d_vflag.p, c->d_specres.p, (!fix && vall) ? SEG_VIT_TOL : 0.0));
+                return BHMM_OK;
+            };
+            f.mend = [&]() -> int {
+                BHMM_HIP(launch(k_gen_viterbi_seg<true>, sgrid, sblk, smv, c->stream, m, off, sg, pobs, ptr8, last,
+                                c->d_aentry.p, c->d_aexit.p, c->d_vckpt.p, c->d_vflag.p + sg.nseg, vall, SEG_VIT_TOL,
+                                c->d_specres.p + 1));
+                return BHMM_OK;
+            };
+            f.margins = [&](double margin) -> int {
+                const dim3 mgrid(sg.nseg, (unsigned)((c->ds.pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
+                auto margins = [&](auto *k, auto *p) {
+                    return launch(k, mgrid, dim3(256), smm, c->stream, m.A, n, off, sg, vall, p, margin, c->d_specres.p);
+                };
+                BHMM_HIP(out_fmt == 0 ? margins(k_vit_margin<int32_t, 2>, path) : margins(k_vit_margin<uint8_t, 2>, p8));
+                return BHMM_OK;
+            };
+            f.walks = [&]() { return walks_of(sg, std::integral_constant<int, 2>{}); };
+            SegVitResult r;
+            if ((rc = seg_viterbi(c, f, sg, seglen, vall, maxT, 12, false, &r)))
+                return rc;
+            if (r.accepted) {
                 done = true;
                 // (what converged is where the next call on these observations starts; longer after a pass whose far
                 // boundaries could not be mended or that needed three or more rounds)
-                const bool longer = (vall && c->last.vit_far > 0 && !margin_accepted) || (round >= 3 && !margin_accepted);
+                const bool longer = !r.margin_accepted && ((vall && c->last.vit_far > 0) || r.rounds >= 3);
                 c->ds.vit_W = (longer && W_try < W_cap) ? std::min(2 * W_try, W_cap) : W_try;
             }
         }
         if (!done && c->ds.pplan[0].nseg > K)
             c->ds.vit_seg_given_up = true; // these observations go to the serial kernel from now on
         c->last.viterbi_chunked = done;
-        if (done) {
-            if (!c->last.vit_margin_used && (rc = seg_walks())) // (a margin-accepted pass has its path already)
-                return rc;
-            if (out_fmt == 0)
-                BHMM_HIP(hipMemcpyAsync(paths_out, path, (size_t)c->total * sizeof(int32_t),
-                                        hipMemcpyDeviceToHost, c->stream));
-            else if (out_fmt == 1)
-                BHMM_HIP(hipMemcpyAsync(paths_out, p8, (size_t)c->total, hipMemcpyDeviceToHost, c->stream));
-            BHMM_HIP(hipStreamSynchronize(c->stream));
-            return BHMM_OK;
-        }
+        if (done)
+            return deliver_paths(c, paths_out, out_fmt, path);
     }
     // 129 .. 256 states (round 5): four segments per workgroup share every pass over A (k_gen_viterbi_rows); first
     // pass only -- accepted when every boundary is bit-identical or by the margins of the decisions on its path
     // (k_vit_margin), else the serial kernel below decides
     if (n > 128 && n <= 256 && c->opt.spec_enabled && c->opt.vit_margin && !c->ds.vit_seg_given_up) {
-        uint8_t *ptr8 = reinterpret_cast<uint8_t *>(c->d_scratch.p);
-        uint8_t *p8 = out_fmt == 2 ? static_cast<uint8_t *>(paths_out) : reinterpret_cast<uint8_t *>(path);
-        const int64_t *off = c->d_offsets.p;
         const int64_t want = (int64_t)GVR_ROWS * (c->num_simd / 4); // one workgroup of four segments per compute unit
         const int64_t fill0 = ((c->total + want - 1) / want + 7) / 8 * 8;
-        const int W0 = std::max(64, c->ds.spec_W > 0 ? (c->ds.spec_W + 7) / 8 * 8 : 128);
         // (six E-step forgetting lengths, at most one and a half fill lengths: at 256 states one boundary of 749 was
         // still 1e-12 off after 504 steps, none after 750 -- and a pass that is not accepted is lost time)
         // (round 6: with the mending round the E-step's length; a pass that is not accepted doubles it for the next call)
@@ -388,109 +319,52 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
         Segs sg;
         if ((rc = wide_path_plan(c, 0, seglen, sg)))
             return rc;
-        int64_t maxT = 0;
-        for (int k = 0; k < K; ++k)
-            maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
         c->last.vit_margin_used = 0;
         c->last.vit_margin_close = 0;
         c->last.vit_seg_rounds = 0;
-        // threads per target state (candidate ranges): 2 (BHMM_AMD_GVR_S = 1 / 4: experiments; measured 15.8 / 13.3 /
-        // 14.1 ms at 129 states with 1 / 2 / 4)
-        static const int gvr_s = getenv("BHMM_AMD_GVR_S") ? atoi(getenv("BHMM_AMD_GVR_S")) : 2;
-        const int GVR_S = gvr_s == 1 ? 1 : (gvr_s == 2 ? 2 : 4);
+        // two threads per target state (candidate ranges; measured 15.8 / 13.3 / 14.1 ms at 129 states with 1 / 2 / 4)
         const size_t smr = (size_t)(2 * GVR_ROWS * n + GVR_ROWS) * sizeof(double) +
-                           (size_t)(GVR_S - 1) * GVR_ROWS * 256 * (sizeof(double) + sizeof(int));
+                           (size_t)GVR_ROWS * 256 * (sizeof(double) + sizeof(int));
         if (sg.nseg > K && (rc = gen_transposed(c, m)) == BHMM_OK && c->d_gW.ensure((size_t)c->total * n) == BHMM_OK &&
             c->d_aentry.ensure((size_t)sg.nseg * 256) == BHMM_OK && c->d_aexit.ensure((size_t)sg.nseg * 256) == BHMM_OK &&
-            c->d_vflag.ensure(2 * (size_t)sg.nseg) == BHMM_OK && c->d_specres.ensure(4) == BHMM_OK &&
+            c->d_vflag.ensure(2 * (size_t)sg.nseg) == BHMM_OK && ensure_specres(c) == BHMM_OK &&
             c->d_vmaps.ensure((size_t)sg.nseg * 256) == BHMM_OK && c->d_vend.ensure((size_t)sg.nseg) == BHMM_OK) {
-            if (!c->h_specres)
-                BHMM_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_specres), 4 * sizeof(unsigned int),
-                                       hipHostMallocDefault));
             sg.W = W_try;
-            const double vm_tol = 1e-12;
             double *vall = c->d_gW.p;
-            BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
-            lds_poison(c->stream);
-            auto *kr = GVR_S == 1   ? k_gen_viterbi_rows<GVR_ROWS, 1>
-                       : GVR_S == 2 ? k_gen_viterbi_rows<GVR_ROWS, 2>
-                                    : k_gen_viterbi_rows<GVR_ROWS, 4>;
-            const dim3 rgrid((sg.nseg + GVR_ROWS - 1) / GVR_ROWS), rblk(256 * GVR_S);
-            BHMM_HIP(launch(kr, rgrid, rblk, smr, c->stream, m, off, sg, pobs, ptr8, last, c->d_aentry.p, c->d_aexit.p,
-                            vall, nullptr, 0.0, nullptr));
-            BHMM_HIP(launch(k_wide_vit_check<256>, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
-                            c->d_aentry.p, c->d_aexit.p, c->d_vflag.p, c->d_specres.p, vm_tol));
-            // the back-trace of this pass (needed either way)
-            auto rows_walks = [&]() -> int {
-                BHMM_HIP(launch(k_wide_vit_walk<false, uint8_t, 4>, dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n,
-                                ptr8, c->d_vmaps.p, nullptr, nullptr));
-                BHMM_HIP(launch(k_wide_vit_stitch, dim3((K + 63) / 64), dim3(64), 0, c->stream, c->pplan_buf[0].traj0.p,
-                                K, c->d_vmaps.p, 256, last, c->d_vend.p));
-                auto walk = [&](auto *k, auto *out) {
-                    return launch(k, dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n, ptr8, nullptr, c->d_vend.p, out);
-                };
-                BHMM_HIP(out_fmt == 0 ? walk(k_wide_vit_walk<true, int32_t, 4>, path)
-                                      : walk(k_wide_vit_walk<true, uint8_t, 4>, p8));
+            const dim3 rgrid((sg.nseg + GVR_ROWS - 1) / GVR_ROWS), rblk(512);
+            SegViterbi f;
+            f.pass = [&](bool) -> int { // (first pass only: no fix-up rounds)
+                BHMM_HIP(launch(k_gen_viterbi_rows<GVR_ROWS, 2>, rgrid, rblk, smr, c->stream, m, off, sg, pobs, ptr8, last,
+                                c->d_aentry.p, c->d_aexit.p, vall, nullptr, 0.0, nullptr));
+                BHMM_HIP(launch(k_wide_vit_check<256>, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
+                                c->d_aentry.p, c->d_aexit.p, c->d_vflag.p, c->d_specres.p, SEG_VIT_TOL));
                 return BHMM_OK;
             };
-            if ((rc = rows_walks()))
-                return rc;
-            BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost,
-                                    c->stream));
-            BHMM_HIP(hipStreamSynchronize(c->stream));
-            c->last.vit_seg_mismatch = (int)c->h_specres[3];
-            c->last.vit_far = (int)c->h_specres[0];
-            bool accepted = c->h_specres[3] == 0;
-            int spliced = 0;
-            if (!accepted && c->h_specres[0] != 0 && (int64_t)c->h_specres[0] * 2 <= sg.nseg && c->opt.vit_mend) {
-                // the mending round (see wide_viterbi_run): the rows of the segments further than vm_tol from their
-                // predecessors' vectors run again up to a vector the first pass kept; then the back-trace again
-                BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
-                lds_poison(c->stream);
-                auto *km = GVR_S == 1   ? k_gen_viterbi_rows<GVR_ROWS, 1, true>
-                           : GVR_S == 2 ? k_gen_viterbi_rows<GVR_ROWS, 2, true>
-                                        : k_gen_viterbi_rows<GVR_ROWS, 4, true>;
-                BHMM_HIP(launch(km, rgrid, rblk, smr, c->stream, m, off, sg, pobs, ptr8, last, c->d_aentry.p, c->d_aexit.p,
-                                vall, c->d_vflag.p + sg.nseg, vm_tol, c->d_specres.p + 1));
-                unsigned int notmet = 0;
-                BHMM_HIP(hipMemcpyAsync(&notmet, c->d_specres.p + 1, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-                BHMM_HIP(hipStreamSynchronize(c->stream));
-                c->last.vit_mended = (int)c->h_specres[0];
-                if (notmet == 0) {
-                    spliced = (int)c->h_specres[0];
-                    c->h_specres[0] = 0;
-                    if ((rc = rows_walks()))
-                        return rc;
-                }
-            }
-            if (!accepted && c->h_specres[0] == 0) {
-                const int maxseg = (int)((maxT + seglen - 1) / seglen) + 1 + spliced;
-                const double margin = std::max(1e-10, 16.0 * (2e-15 * (double)maxT + vm_tol * maxseg));
-                BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
+            f.mend = [&]() -> int {
+                BHMM_HIP(launch(k_gen_viterbi_rows<GVR_ROWS, 2, true>, rgrid, rblk, smr, c->stream, m, off, sg, pobs, ptr8,
+                                last, c->d_aentry.p, c->d_aexit.p, vall, c->d_vflag.p + sg.nseg, SEG_VIT_TOL,
+                                c->d_specres.p + 1));
+                return BHMM_OK;
+            };
+            f.margins = [&](double margin) -> int {
                 const dim3 mgrid(sg.nseg, (unsigned)((c->ds.pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
                 auto margins = [&](auto *k, auto *p) {
                     return launch(k, mgrid, dim3(256), 0, c->stream, c->d_gAt.p, n, off, sg, vall, p, margin, c->d_specres.p);
                 };
                 BHMM_HIP(out_fmt == 0 ? margins(k_vit_margin<int32_t, 4, false>, path)
                                       : margins(k_vit_margin<uint8_t, 4, false>, p8));
-                BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost,
-                                        c->stream));
-                BHMM_HIP(hipStreamSynchronize(c->stream));
-                c->last.vit_margin_close = (int)c->h_specres[2];
-                accepted = c->h_specres[2] == 0;
-                c->last.vit_margin_used = accepted ? 1 : 0;
-            }
-            if (accepted) {
+                return BHMM_OK;
+            };
+            // (the back-trace of the pass is needed either way: enqueued before its verdict is read)
+            f.walks = [&]() { return walks_of(sg, std::integral_constant<int, 4>{}); };
+            SegVitResult r;
+            if ((rc = seg_viterbi(c, f, sg, seglen, vall, maxT, 0, true, &r)))
+                return rc;
+            if (r.accepted) {
                 c->last.viterbi_chunked = true;
                 c->ds.vit_W = W_try;
                 c->ds.vit_rows_fail = 0;
-                if (out_fmt == 0)
-                    BHMM_HIP(hipMemcpyAsync(paths_out, path, (size_t)c->total * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                            c->stream));
-                else if (out_fmt == 1)
-                    BHMM_HIP(hipMemcpyAsync(paths_out, p8, (size_t)c->total, hipMemcpyDeviceToHost, c->stream));
-                BHMM_HIP(hipStreamSynchronize(c->stream));
-                return BHMM_OK;
+                return deliver_paths(c, paths_out, out_fmt, path);
             }
             // One pass that was not accepted (a close decision under THIS model -- an early EM iterate, say) sends
             // this call to the serial kernel; the next call tries again with twice the warm-up, and only a second
@@ -507,20 +381,13 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
     const bool alds = gen_a_in_lds(n, sm);
     sm += alds ? gen_a_bytes(n) : 0;
     auto *kvf = alds ? k_gen_viterbi_fwd<true> : k_gen_viterbi_fwd<false>;
-    BHMM_HIP(launch(kvf, dim3(K), dim3(GEN_TPB), sm, c->stream, m, c->d_offsets.p, K, pobs, ptr, last));
+    BHMM_HIP(launch(kvf, dim3(K), dim3(GEN_TPB), sm, c->stream, m, off, K, pobs, ptr, last));
     const dim3 tg((K + 63) / 64), tb(64);
-    if (out_fmt == 0) {
-        BHMM_HIP(launch(k_gen_viterbi_trace<int32_t>, tg, tb, 0, c->stream, c->d_offsets.p, K, n, ptr, last, path));
-        BHMM_HIP(hipMemcpyAsync(paths_out, path, (size_t)c->total * sizeof(int32_t),
-                                hipMemcpyDeviceToHost, c->stream));
-    } else {
-        uint8_t *p8 = out_fmt == 2 ? static_cast<uint8_t *>(paths_out) : reinterpret_cast<uint8_t *>(path);
-        BHMM_HIP(launch(k_gen_viterbi_trace<uint8_t>, tg, tb, 0, c->stream, c->d_offsets.p, K, n, ptr, last, p8));
-        if (out_fmt == 1)
-            BHMM_HIP(hipMemcpyAsync(paths_out, p8, (size_t)c->total, hipMemcpyDeviceToHost, c->stream));
-    }
-    BHMM_HIP(hipStreamSynchronize(c->stream));
-    return BHMM_OK;
+    if (out_fmt == 0)
+        BHMM_HIP(launch(k_gen_viterbi_trace<int32_t>, tg, tb, 0, c->stream, off, K, n, ptr, last, path));
+    else
+        BHMM_HIP(launch(k_gen_viterbi_trace<uint8_t>, tg, tb, 0, c->stream, off, K, n, ptr, last, p8));
+    return deliver_paths(c, paths_out, out_fmt, path);
 }
 
 // alpha_dev: rows to sample from (the context's own forward pass when NULL)
@@ -587,11 +454,8 @@ int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double 
             sg.W = c->ds.smp_W;
             if ((rc = gen_transposed(c, m)) || (rc = c->d_sentry.ensure((size_t)sg.nseg)) ||
                 (rc = c->d_sexit.ensure((size_t)sg.nseg)) || (rc = c->d_vflag.ensure((size_t)sg.nseg)) ||
-                (rc = c->d_specres.ensure(4)))
+                (rc = ensure_specres(c)))
                 return rc;
-            if (!c->h_specres)
-                BHMM_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_specres), 4 * sizeof(unsigned int),
-                                       hipHostMallocDefault));
             const dim3 sgrid((sg.nseg + 3) / 4), sblk(256);
             // (first round, then the rounds that draw the flagged segments again)
             auto *kfirst = n <= 128   ? k_gen_sample_seg<2, false>
@@ -603,15 +467,16 @@ int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double 
             const int max_rounds = 16;
             int round = 0;
             for (; round <= max_rounds; ++round) {
-                BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
+                if ((rc = specres_reset(c)))
+                    return rc;
                 lds_poison(c->stream);
                 BHMM_HIP(launch(round == 0 ? kfirst : kfix, sgrid, sblk, 0, c->stream, m, c->d_gAt.p, c->d_offsets.p, sg,
                                 c->d_alpha_rm.p, udev, seed, c->d_soff.p, path, status, c->d_sentry.p, c->d_sexit.p,
                                 c->d_vflag.p, watch));
                 BHMM_HIP(launch(k_wide_smp_check, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg, c->d_sentry.p,
                                 c->d_sexit.p, c->d_vflag.p, c->d_specres.p));
-                BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
-                                        hipMemcpyDeviceToHost, c->stream));
+                if ((rc = specres_read(c, 4, false)))
+                    return rc;
                 BHMM_HIP(hipMemcpyAsync(&c->h_specres[0], status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
                 BHMM_HIP(hipStreamSynchronize(c->stream));
                 if (round == 0)

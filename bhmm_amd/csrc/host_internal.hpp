@@ -3,6 +3,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <functional>
 #include <string>
 
 #include "ctx.hpp"
@@ -28,6 +29,13 @@ int probe_warmup_target(bhmm_ctx *c, const double *A, const double *pi, const do
 // parameters the emission kind needs.  Then the context's device is made current.
 int enter_model_call(bhmm_ctx *c, bool given, const char *null_msg, bool emissions, const double *par0,
                      const double *par1);
+int64_t longest_traj(const bhmm_ctx *c); // steps of the longest trajectory
+// The status words of the verifying passes: d_specres (at least `words`) and its pinned host copy h_specres
+// (four words).  specres_reset clears the first `words` on the stream; specres_read copies them into
+// h_specres and waits for the stream (wait = false: the caller synchronises, after copies of its own).
+int ensure_specres(bhmm_ctx *c, size_t words = 4);
+int specres_reset(bhmm_ctx *c, int words = 4);
+int specres_read(bhmm_ctx *c, int words = 4, bool wait = true);
 
 // ---- estep_f32.hip (BHMM_FLAG_SINGLE, up to 8 states) ----
 // *done: the E-step ran in fp32 and verified; false: the caller runs the fp64 path (nothing else changed)
@@ -50,6 +58,31 @@ int wide_transition_counts(double *C, const double *A, const double *pobs, const
 
 // ---- path_api.hip (Viterbi, path sampling) ----
 int wide_path_plan(bhmm_ctx *c, int which, int64_t seglen, Segs &sg);
+// The paths of a Viterbi call to the caller (out_fmt 0: int32 to a host buffer, 1: one byte per step to a host
+// buffer, 2: one byte per step in a device buffer, written there already); completes the call's stream.  A
+// pageable host buffer of 8 MiB or more is registered for the copy.
+int deliver_paths(bhmm_ctx *c, void *paths_out, int out_fmt, const void *dev_paths);
+// The acceptance protocol of a segment-parallel Viterbi pass on one plan: the first pass is
+// accepted when every boundary is bit-identical to its predecessor's vector, or -- vall kept -- when every
+// boundary is within SEG_VIT_TOL (after mending the far ones) and every decision on the path clears the margin;
+// else fix-up rounds up to max_rounds decide.  The family's hooks launch its kernels (BHMM_* codes):
+struct SegViterbi {
+    std::function<int(bool fix)> pass;         // the segment pass (fix: a fix-up round) + k_wide_vit_check
+    std::function<int()> mend;                 // the far segments again up to a kept vector (empty: no mending)
+    std::function<int(double margin)> margins; // k_vit_margin over the path the walks wrote
+    std::function<int()> walks;                // back-trace over the segments: maps, stitch, apply
+};
+constexpr double SEG_VIT_TOL = 1e-12; // boundaries this close count as usable for the margins
+struct SegVitResult {
+    bool accepted = false;        // the path of the walks is the serial run's (the walks have run)
+    bool margin_accepted = false; // ... by the margins of the decisions on it
+    int rounds = 0;               // fix-up rounds (max_rounds + 1: they ran out)
+};
+// seglen: the plan's segment length; maxT: longest_traj; walks_first: the walks follow every pass before its
+// verdict is read.  Sets the vit_seg_mismatch, vit_far, vit_mended, vit_margin_used, vit_margin_close and
+// vit_seg_rounds counters.
+int seg_viterbi(bhmm_ctx *c, const SegViterbi &f, const Segs &sg, int64_t seglen, const double *vall, int64_t maxT,
+                int max_rounds, bool walks_first, SegVitResult *res);
 int draw_watch_prepare(bhmm_ctx *c, double tol, DrawWatch &w, unsigned int *count_slot);
 int draw_verify_run(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
                     unsigned int count, double thr, int64_t Wlong, bool *ok);

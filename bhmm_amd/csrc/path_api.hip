@@ -349,6 +349,126 @@ int wide_path_plan(bhmm_ctx *c, int which, int64_t seglen, Segs &sg)
     return BHMM_OK;
 }
 
+int deliver_paths(bhmm_ctx *c, void *paths_out, int out_fmt, const void *dev_paths)
+{
+    if (out_fmt == 2) { // the paths are where the caller wants them; the call still completes them
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+        return BHMM_OK;
+    }
+    // large results into a pageable buffer: pin it for the transfer (a pageable destination goes
+    // through the runtime's staging buffers at a fraction of the link rate); a buffer the caller
+    // pinned already (hipHostMalloc / hipHostRegister, torch pin_memory) is used as it is
+    const size_t pbytes = (size_t)c->total * (out_fmt == 0 ? sizeof(int32_t) : sizeof(uint8_t));
+    hipPointerAttribute_t attr;
+    bool caller_pinned = hipPointerGetAttributes(&attr, paths_out) == hipSuccess &&
+                         attr.type == hipMemoryTypeHost;
+    (void)hipGetLastError();
+    const bool pinned = !caller_pinned && pbytes >= ((size_t)8 << 20) &&
+                        hipHostRegister(paths_out, pbytes, hipHostRegisterDefault) == hipSuccess;
+    if (!pinned)
+        (void)hipGetLastError();
+    hipError_t ce = hipMemcpyAsync(paths_out, dev_paths, pbytes, hipMemcpyDeviceToHost, c->stream);
+    if (ce == hipSuccess)
+        ce = hipStreamSynchronize(c->stream);
+    if (pinned)
+        (void)hipHostUnregister(paths_out);
+    BHMM_HIP(ce);
+    return BHMM_OK;
+}
+
+// Accepted only if EVERY segment arrives at its first step with the bit pattern its predecessor left there --
+// then the back-pointers are the serial run's, by induction from the exact first segment of each trajectory --
+// or by the path margins (k_vit_margin) when every boundary is within SEG_VIT_TOL.
+int seg_viterbi(bhmm_ctx *c, const SegViterbi &f, const Segs &sg, int64_t seglen, const double *vall, int64_t maxT,
+                int max_rounds, bool walks_first, SegVitResult *res)
+{
+    *res = SegVitResult();
+    int rc;
+    if ((rc = ensure_specres(c)))
+        return rc;
+    unsigned int *h = c->h_specres;
+    bool allow_mend = c->opt.vit_mend && f.mend, mended = false, walked = false, bitwise = false;
+    c->last.vit_mended = 0;
+    // pass 0 with warm-ups, then fix-up rounds while any boundary is not bit-identical
+    int round = 0;
+    for (; round <= max_rounds; ++round) {
+        if ((rc = specres_reset(c)))
+            return rc;
+        lds_poison(c->stream);
+        if ((rc = f.pass(round > 0)))
+            return rc;
+        walked = walks_first;
+        if ((walks_first && (rc = f.walks())) || (rc = specres_read(c)))
+            return rc;
+        if (round == 0) {
+            c->last.vit_seg_mismatch = (int)h[3];
+            c->last.vit_far = (int)h[0];
+        }
+        if (h[3] == 0) {
+            bitwise = true;
+            break;
+        }
+        if (round > 0)
+            continue;
+        int spliced = 0;
+        if (vall && h[0] != 0 && (int64_t)h[0] * 2 <= sg.nseg && allow_mend) {
+            mended = true;
+            // Some boundaries are further than SEG_VIT_TOL from their predecessors' vectors (the warm-up was too short
+            // THERE; the max-product vectors of a metastable model need several times the filter's forgetting length
+            // at a few boundaries -- configs[3]: 276 of 2048 after 256 steps, none after 904): those segments alone
+            // are run again from the predecessor's vector until they are within SEG_VIT_TOL of a kept vector of the
+            // first pass instead of lengthening every warm-up.  If one reaches its end the rounds decide.
+            if ((rc = specres_reset(c)))
+                return rc;
+            lds_poison(c->stream);
+            if ((rc = f.mend()))
+                return rc;
+            walked = false;
+            unsigned int notmet = 0;
+            BHMM_HIP(hipMemcpyAsync(&notmet, c->d_specres.p + 1, sizeof(unsigned int), hipMemcpyDeviceToHost,
+                                    c->stream));
+            BHMM_HIP(hipStreamSynchronize(c->stream));
+            c->last.vit_mended = (int)h[0];
+            if (notmet == 0) {
+                spliced = (int)h[0];
+                h[0] = 0;
+            }
+        }
+        if (vall && h[0] == 0) {
+            // every boundary (and splice) within SEG_VIT_TOL: the path of this pass, and the margins of the
+            // decisions on it
+            const int maxseg = (int)((maxT + seglen - 1) / seglen) + 1 + spliced;
+            const double margin = std::max(1e-10, 16.0 * (2e-15 * (double)maxT + SEG_VIT_TOL * maxseg));
+            if (!walked && (rc = f.walks()))
+                return rc;
+            walked = true;
+            if ((rc = specres_reset(c)) || (rc = f.margins(margin)) || (rc = specres_read(c)))
+                return rc;
+            c->last.vit_margin_close = (int)h[2];
+            if (h[2] == 0) {
+                c->last.vit_margin_used = 1;
+                res->margin_accepted = true;
+                break;
+            }
+            // (a close decision on the path: the rounds decide)
+        }
+        if (mended && max_rounds > 0) {
+            // The rounds compare BITWISE with the kept vectors of the first pass; a mended segment now holds exact
+            // vectors up to its splice and first-pass vectors behind it, so a repeated run would stop at the first
+            // kept vector and take the rest for exact.  A pass that was mended and then not accepted is therefore
+            // run again from scratch, without mending (one first pass lost).
+            allow_mend = false;
+            mended = false;
+            round = -1;
+        }
+    }
+    res->rounds = c->last.vit_seg_rounds = max_rounds > 0 ? round : 0;
+    res->accepted = bitwise || res->margin_accepted;
+    if (res->accepted && !walked && (rc = f.walks()))
+        return rc;
+    return BHMM_OK;
+}
+
 namespace {
 
 // ---- 9..64 states ---------------------------------------------------------------------
@@ -395,9 +515,8 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
     // warm-ups included, cost more than the matrix pass saves (64 states: 9.0 -> 9.7 ms, 16: 0.67 -> 0.81).
     // (round 6: the Gaussian density in the step too, with the reciprocal-based quotient and the one-block
     // exponential of k_pobs_lanes -- at 64 states: 6.5 GB less written and read again per call)
-    static const bool gauss_matrix = getenv("BHMM_AMD_VIT_GAUSS_MATRIX") != nullptr; // (experiments: the round-5 way)
-    const bool wide_direct = c->wide && (c->kind == EMIT_DISC || (c->kind == EMIT_GAUSS && !gauss_matrix)) &&
-                             c->opt.spec_enabled && !c->ds.vit_seg_given_up;
+    const bool wide_direct = c->wide && (c->kind == EMIT_DISC || c->kind == EMIT_GAUSS) && c->opt.spec_enabled &&
+                             !c->ds.vit_seg_given_up;
     if (c->kind != EMIT_EXPL && !disc_direct && !wide_direct) {
         size_t freeb = 0, totb = 0;
         const size_t need = (size_t)c->total * n * sizeof(double);
@@ -459,11 +578,8 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
             maxchunks = std::max(maxchunks, c->traj_c0[k + 1] - c->traj_c0[k]);
         const double tol = 1e-11, margin = std::max(1e-7, 16.0 * tol * maxchunks);
         if ((rc = c->d_aentry.ensure((size_t)c->Gp * 8)) || (rc = c->d_aexit.ensure((size_t)c->Gp * 8)) ||
-            (rc = c->d_specres.ensure(4)))
+            (rc = ensure_specres(c)))
             return rc;
-        if (!c->h_specres)
-            BHMM_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_specres), 4 * sizeof(unsigned int),
-                                   hipHostMallocDefault));
         const Chunks chs = chunks_of(c);
         // discrete: B in LDS when it is small enough to leave four wavefronts per SIMD their room
         const size_t smB = (disc_direct && c->kind == EMIT_DISC &&
@@ -502,7 +618,8 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
         }
         // first without the close-decision count; bit-identical boundaries make it irrelevant
         for (int pass = 0; pass < 2; ++pass) {
-            BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
+            if ((rc = specres_reset(c)))
+                return rc;
             const int vk = disc_direct && c->kind == EMIT_DISC ? EMIT_DISC : disc_direct ? EMIT_GAUSS : EMIT_EXPL;
             auto vc = [&](auto npc) {
                 constexpr int VNP = decltype(npc)::value;
@@ -518,8 +635,8 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
                 return e;
             };
             BHMM_HIP(vit4 ? vc(std::integral_constant<int, 4>{}) : vc(std::integral_constant<int, 8>{}));
-            BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
-                                    hipMemcpyDeviceToHost, c->stream));
+            if ((rc = specres_read(c, 4, false)))
+                return rc;
             // the normal case is "all boundaries bit-identical": the back-trace is enqueued behind
             // the first pass before its verdict is known (one host round trip less); the walks only
             // read back-pointers, which are valid state indices whatever the verdict, and are
@@ -549,9 +666,7 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
         c->last.spec_last_dev = dev;
         c->last.viterbi_close = c->h_specres[2];
     }
-    // 9..64 states: one lane group per time segment (k_wide_viterbi_seg); accepted only if EVERY
-    // segment arrives at its first step with the bit pattern its predecessor left there -- then the
-    // back-pointers are the serial run's, by induction from the exact first segment of each trajectory
+    // 9..64 states: one lane group per time segment (k_wide_viterbi_seg), accepted by seg_viterbi
     if (c->wide && c->opt.spec_enabled && !c->ds.vit_seg_given_up) {
         // warm-up: its own, not the E-step's.  Every length is exact (bitwise check + fix-up rounds), so the length
         // only trades warm-up steps (W / segment length of the first pass) against rounds (1.1 ms each at configs[3],
@@ -562,36 +677,25 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
         // needed three or more rounds doubles the length for the next call on these observations, up to the E-step's.
         const int W_estep = std::max(64, c->ds.spec_W > 0 ? (c->ds.spec_W + 7) / 8 * 8 : 128);
         int W_try = c->ds.vit_W > 0 ? c->ds.vit_W : std::min(128, W_estep);
-        const bool exploring = false;
-        if ((rc = c->d_specres.ensure(4)))
-            return rc;
-        if (!c->h_specres)
-            BHMM_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_specres), 4 * sizeof(unsigned int),
-                                   hipHostMallocDefault));
         // the path-margin acceptance (k_vit_margin): every vector of the first pass is kept ([total][n], in the
-        // buffer of the 65..128-state E-step's W rows), boundaries equal to vm_tol count as usable
-        const double vm_tol = 1e-12;
+        // buffer of the 65..128-state E-step's W rows)
         double *vall = nullptr;
-        int64_t maxT = 0;
         // (up to 64 states one fix-up round is short -- 1.1 ms at configs[3] -- and cheaper than keeping the
         // vectors and checking the margins: only observations that needed two or more rounds before take this way)
-        if (c->opt.vit_margin && c->ds.vit_margin_want && c->d_gW.ensure((size_t)c->total * n) == BHMM_OK) {
+        if (c->opt.vit_margin && c->ds.vit_margin_want && c->d_gW.ensure((size_t)c->total * n) == BHMM_OK)
             vall = c->d_gW.p;
-            for (int k = 0; k < K; ++k)
-                maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
-        } else {
+        else
             (void)hipGetLastError();
-        }
         c->last.vit_margin_used = 0;
         c->last.vit_margin_close = 0;
-        // back-trace over the segments: maps, stitch, apply
+        const int64_t maxT = longest_traj(c);
+        // back-trace over the segments: maps, stitch, apply -- on a plan of its own, eight times finer than the
+        // pass's: a walk is a chain of dependent look-ups, its time the length of a segment (configs[3]: 2 x 0.49 ms
+        // on the 2048 segments of the pass)
         auto seg_walks = [&]() -> int {
-            // on a plan of its own, eight times finer than the pass's: a walk is a chain of dependent look-ups, its
-            // time the length of a segment (configs[3]: 2 x 0.49 ms on the 2048 segments of the pass)
             Segs sgw;
             int rcw;
-            static const int walk_div = getenv("BHMM_AMD_WALK_DIV") ? atoi(getenv("BHMM_AMD_WALK_DIV")) : 8;
-            if ((rcw = wide_path_plan(c, 2, std::max<int64_t>(256, c->ds.pplan[0].seglen / walk_div), sgw)))
+            if ((rcw = wide_path_plan(c, 2, std::max<int64_t>(256, c->ds.pplan[0].seglen / 8), sgw)))
                 return rcw;
             sgw.W = 0;
             if ((rcw = c->d_vmaps.ensure((size_t)sgw.nseg * 64)) || (rcw = c->d_vend.ensure((size_t)sgw.nseg)))
@@ -607,9 +711,8 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
             return BHMM_OK;
         };
         for (int attempt = 0; attempt < 2 && !done; ++attempt) {
-            if (attempt > 0) {
+            if (attempt > 0)
                 W_try *= 2;
-            }
             // two lane groups' worth of segments per SIMD, none shorter than two warm-ups
             const int64_t want = (int64_t)c->opt.vit_seg_per_simd * c->num_simd * GP;
             const int64_t seglen = std::max<int64_t>((c->total + want - 1) / want, c->opt.vit_seg_warmups * (int64_t)W_try);
@@ -625,151 +728,76 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
             if ((rc = c->d_vckpt.ensure(((size_t)(c->total >> 6) + 1) * NP)) ||
                 (rc = c->d_vflag.ensure(2 * (size_t)sg.nseg))) // ([nseg] flagged | [nseg] flagged and further than vm_tol)
                 return rc;
-            // one pass over the segments (FIX: a fix-up round) and its boundary check; the mending round
-            auto seg_pass = [&](auto npc, bool fix) {
-                constexpr int V = decltype(npc)::value;
-                auto *k = vkind == EMIT_GAUSS
-                              ? (fix ? k_wide_viterbi_seg<V, EMIT_GAUSS, true> : k_wide_viterbi_seg<V, EMIT_GAUSS, false>)
-                          : vkind == EMIT_DISC
-                              ? (fix ? k_wide_viterbi_seg<V, EMIT_DISC, true> : k_wide_viterbi_seg<V, EMIT_DISC, false>)
-                              : (fix ? k_wide_viterbi_seg<V, EMIT_EXPL, true> : k_wide_viterbi_seg<V, EMIT_EXPL, false>);
-                hipError_t e = launch(k, sgrid, sblk, 0, c->stream, m, off, sg, obs, ptr, last, c->d_aentry.p, c->d_aexit.p,
-                                      c->d_vckpt.p, c->d_vflag.p, fix ? nullptr : vall, 0.0, nullptr);
-                if (e == hipSuccess)
-                    e = launch(k_wide_vit_check<V>, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg, c->d_aentry.p,
-                               c->d_aexit.p, c->d_vflag.p, c->d_specres.p, (!fix && vall) ? vm_tol : 0.0);
-                return e;
-            };
-            auto mend_pass = [&](auto npc) {
-                constexpr int V = decltype(npc)::value;
-                auto *k = vkind == EMIT_GAUSS  ? k_wide_viterbi_seg<V, EMIT_GAUSS, true>
-                          : vkind == EMIT_DISC ? k_wide_viterbi_seg<V, EMIT_DISC, true>
-                                               : k_wide_viterbi_seg<V, EMIT_EXPL, true>;
-                return launch(k, sgrid, sblk, 0, c->stream, m, off, sg, obs, ptr, last, c->d_aentry.p, c->d_aexit.p,
-                              c->d_vckpt.p, c->d_vflag.p + sg.nseg, vall, vm_tol, c->d_specres.p + 1);
-            };
             auto by_np = [&](auto f) {
                 return NP == 16 ? f(std::integral_constant<int, 16>{})
                        : NP == 32 ? f(std::integral_constant<int, 32>{})
                                   : f(std::integral_constant<int, 64>{});
             };
-            // pass 0 with warm-ups, then fix-up rounds while any boundary is not bit-identical
-            const int max_rounds = 12;
-            int round = 0;
-            bool margin_accepted = false;
-            bool allow_mend = c->opt.vit_mend, mended = false;
-            c->last.vit_mended = 0;
-            for (; round <= max_rounds; ++round) {
-                BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
-                lds_poison(c->stream);
-                BHMM_HIP(by_np([&](auto npc) { return seg_pass(npc, round > 0); }));
-                BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
-                                        hipMemcpyDeviceToHost, c->stream));
-                BHMM_HIP(hipStreamSynchronize(c->stream));
-                if (round == 0) {
-                    c->last.vit_seg_mismatch = (int)c->h_specres[3];
-                    c->last.vit_far = (int)c->h_specres[0];
-                }
-                if (c->h_specres[3] == 0)
-                    break;
-                int spliced = 0;
-                if (round == 0 && vall && c->h_specres[0] != 0 && (int64_t)c->h_specres[0] * 2 <= sg.nseg && allow_mend) {
-                    mended = true;
-                    // Some boundaries are further than vm_tol from their predecessors' vectors (the warm-up was
-                    // too short THERE; the max-product vectors of a metastable model need several times the
-                    // filter's forgetting length at a few boundaries -- configs[3]: 276 of 2048 after 256 steps,
-                    // none after 904): those segments alone are run again from the predecessor's vector until
-                    // they are within vm_tol of a kept vector of the first pass (k_wide_viterbi_seg, mend_tol)
-                    // instead of lengthening every warm-up.  If one reaches its end the rounds decide.
-                    BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
-                    lds_poison(c->stream);
-                    BHMM_HIP(by_np(mend_pass));
-                    unsigned int notmet = 0;
-                    BHMM_HIP(hipMemcpyAsync(&notmet, c->d_specres.p + 1, sizeof(unsigned int), hipMemcpyDeviceToHost,
-                                            c->stream));
-                    BHMM_HIP(hipStreamSynchronize(c->stream));
-                    c->last.vit_mended = (int)c->h_specres[0];
-                    if (notmet == 0) {
-                        spliced = (int)c->h_specres[0];
-                        c->h_specres[0] = 0;
-                    }
-                }
-                if (round == 0 && vall && c->h_specres[0] == 0) {
-                    // every boundary (and splice) within vm_tol: the path of this pass, and the margins of the
-                    // decisions on it
-                    const int maxseg = (int)((maxT + seglen - 1) / seglen) + 1 + spliced;
-                    const double margin = std::max(1e-10, 16.0 * (2e-15 * (double)maxT + vm_tol * maxseg));
-                    if ((rc = seg_walks()))
-                        return rc;
-                    BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
-                    const size_t smm = (size_t)n * (n | 1) * sizeof(double); // (odd pitch, k_vit_margin)
-                    const dim3 mgrid(sg.nseg, (unsigned)((c->ds.pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
-                    static const bool vm_global = getenv("BHMM_AMD_VM_GLOBAL") != nullptr; // (experiment: A^T from L2)
-                    if (vm_global) {
-                        if ((rc = c->d_gAt.ensure((size_t)n * n)))
-                            return rc;
-                        BHMM_HIP(launch(k_vm_transpose, dim3((n * n + 255) / 256), dim3(256), 0, c->stream, m.A, n, c->d_gAt.p));
-                    }
-                    auto margins = [&](auto *k, const double *At, size_t lds, auto *p) {
-                        return launch(k, mgrid, dim3(256), lds, c->stream, At, n, off, sg, vall, p, margin, c->d_specres.p);
-                    };
-                    if (vm_global)
-                        BHMM_HIP(out_fmt == 0 ? margins(k_vit_margin<int32_t, 1, false>, c->d_gAt.p, 0, path)
-                                              : margins(k_vit_margin<uint8_t, 1, false>, c->d_gAt.p, 0, path8));
-                    else
-                        BHMM_HIP(out_fmt == 0 ? margins(k_vit_margin<int32_t, 1>, m.A, smm, path)
-                                              : margins(k_vit_margin<uint8_t, 1>, m.A, smm, path8));
-                    BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
-                                            hipMemcpyDeviceToHost, c->stream));
-                    BHMM_HIP(hipStreamSynchronize(c->stream));
-                    c->last.vit_margin_close = (int)c->h_specres[2];
-                    if (c->h_specres[2] == 0) {
-                        c->last.vit_margin_used = 1;
-                        margin_accepted = true;
-                        break;
-                    }
-                    // (a close decision on the path: the rounds decide)
-                }
-                if (round == 0 && mended) {
-                    // The rounds compare BITWISE with the kept vectors of the first pass; a mended segment now
-                    // holds exact vectors up to its splice and first-pass vectors behind it, so a repeated run
-                    // would stop at the first kept vector and take the rest for exact.  A pass that was mended and
-                    // then not accepted is therefore run again from scratch, without mending (one first pass lost).
-                    allow_mend = false;
-                    mended = false;
-                    round = -1;
-                }
-            }
-            c->last.vit_seg_rounds = round;
+            SegViterbi f;
+            f.pass = [&](bool fix) -> int {
+                BHMM_HIP(by_np([&](auto npc) {
+                    constexpr int V = decltype(npc)::value;
+                    auto *k = vkind == EMIT_GAUSS
+                                  ? (fix ? k_wide_viterbi_seg<V, EMIT_GAUSS, true> : k_wide_viterbi_seg<V, EMIT_GAUSS, false>)
+                              : vkind == EMIT_DISC
+                                  ? (fix ? k_wide_viterbi_seg<V, EMIT_DISC, true> : k_wide_viterbi_seg<V, EMIT_DISC, false>)
+                                  : (fix ? k_wide_viterbi_seg<V, EMIT_EXPL, true> : k_wide_viterbi_seg<V, EMIT_EXPL, false>);
+                    hipError_t e = launch(k, sgrid, sblk, 0, c->stream, m, off, sg, obs, ptr, last, c->d_aentry.p,
+                                          c->d_aexit.p, c->d_vckpt.p, c->d_vflag.p, fix ? nullptr : vall, 0.0, nullptr);
+                    if (e == hipSuccess)
+                        e = launch(k_wide_vit_check<V>, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
+                                   c->d_aentry.p, c->d_aexit.p, c->d_vflag.p, c->d_specres.p,
+                                   (!fix && vall) ? SEG_VIT_TOL : 0.0);
+                    return e;
+                }));
+                return BHMM_OK;
+            };
+            f.mend = [&]() -> int {
+                BHMM_HIP(by_np([&](auto npc) {
+                    constexpr int V = decltype(npc)::value;
+                    auto *k = vkind == EMIT_GAUSS  ? k_wide_viterbi_seg<V, EMIT_GAUSS, true>
+                              : vkind == EMIT_DISC ? k_wide_viterbi_seg<V, EMIT_DISC, true>
+                                                   : k_wide_viterbi_seg<V, EMIT_EXPL, true>;
+                    return launch(k, sgrid, sblk, 0, c->stream, m, off, sg, obs, ptr, last, c->d_aentry.p, c->d_aexit.p,
+                                  c->d_vckpt.p, c->d_vflag.p + sg.nseg, vall, SEG_VIT_TOL, c->d_specres.p + 1);
+                }));
+                return BHMM_OK;
+            };
+            f.margins = [&](double margin) -> int {
+                const size_t smm = (size_t)n * (n | 1) * sizeof(double); // (odd pitch, k_vit_margin)
+                const dim3 mgrid(sg.nseg, (unsigned)((c->ds.pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
+                auto margins = [&](auto *k, auto *p) {
+                    return launch(k, mgrid, dim3(256), smm, c->stream, m.A, n, off, sg, vall, p, margin, c->d_specres.p);
+                };
+                BHMM_HIP(out_fmt == 0 ? margins(k_vit_margin<int32_t, 1>, path) : margins(k_vit_margin<uint8_t, 1>, path8));
+                return BHMM_OK;
+            };
+            f.walks = seg_walks;
+            SegVitResult r;
+            if ((rc = seg_viterbi(c, f, sg, seglen, vall, maxT, 12, false, &r)))
+                return rc;
             // (a round runs as long as its longest flagged segment needs to fall onto a vector of the first pass
             // again: 1.1 ms at configs[3] on white-noise observations, 6.7 ms -- half a first pass -- on
             // observations drawn from the model, where 1800 of 2048 boundaries carry rounding noise.  The margins
             // cost about 1.3 ms there: wanted from the next call on when rounds were many, or the flagged
             // segments more than a quarter)
-            if (round >= 2 || (round >= 1 && !margin_accepted && (int64_t)c->last.vit_seg_mismatch * 4 > sg.nseg))
+            if (r.rounds >= 2 || (r.rounds >= 1 && !r.margin_accepted && (int64_t)c->last.vit_seg_mismatch * 4 > sg.nseg))
                 c->ds.vit_margin_want = true;
-            const bool accepted = c->h_specres[3] == 0 || margin_accepted;
             // (How many boundaries the first pass left to the fix-up does not say whether the warm-up was
             // too short -- most of them are rounding noise, and a round costs the same for one segment as
             // for a thousand: doubling the warm-up on that count was measured slower everywhere.)
-            if (exploring && !accepted)
-                continue;
-            if (accepted) {
+            if (r.accepted) {
                 done = true;
                 // (boundaries further than 1e-12 apart keep the margin rule from being asked: a longer warm-up for
                 // the next call, like after three or more rounds -- never beyond the E-step's)
-                const bool longer = (vall && c->last.vit_far > 0 && !margin_accepted) || (round >= 3 && !margin_accepted);
+                const bool longer = !r.margin_accepted && ((vall && c->last.vit_far > 0) || r.rounds >= 3);
                 c->ds.vit_W = (longer && W_try < W_estep) ? std::min(2 * W_try, W_estep) : W_try;
             }
         }
         if (!done && c->ds.pplan[0].nseg > K)
             c->ds.vit_seg_given_up = true; // these observations go to the serial kernel from now on
         c->last.viterbi_chunked = done;
-        if (done) {
-            if (!c->last.vit_margin_used && (rc = seg_walks())) // (a margin-accepted pass has its path already)
-                return rc;
-            walks_in_flight = true;
-        }
+        walks_in_flight = done; // (seg_viterbi ran the walks of an accepted pass)
     }
     if (done) {
         if (!walks_in_flight)
@@ -793,31 +821,7 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
         else
             BHMM_HIP(launch(k_wide_viterbi_trace<uint8_t>, dim3(K), dim3(64), 0, c->stream, off, K, n, ptr, last, path8));
     }
-    if (out_fmt == 2) { // the paths are where the caller wants them; the call still completes them
-        BHMM_HIP(hipStreamSynchronize(c->stream));
-        return BHMM_OK;
-    }
-    // large results into a pageable buffer: pin it for the transfer (a pageable destination goes
-    // through the runtime's staging buffers at a fraction of the link rate); a buffer the caller
-    // pinned already (hipHostMalloc / hipHostRegister, torch pin_memory) is used as it is
-    const size_t pbytes = (size_t)c->total * (out_fmt == 0 ? sizeof(int32_t) : sizeof(uint8_t));
-    hipPointerAttribute_t attr;
-    bool caller_pinned = hipPointerGetAttributes(&attr, paths_out) == hipSuccess &&
-                         attr.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    const bool pinned = !caller_pinned && pbytes >= ((size_t)8 << 20) &&
-                        hipHostRegister(paths_out, pbytes, hipHostRegisterDefault) == hipSuccess;
-    if (!pinned)
-        (void)hipGetLastError();
-    hipError_t ce = hipMemcpyAsync(paths_out, out_fmt == 0 ? static_cast<const void *>(path)
-                                                           : static_cast<const void *>(path8),
-                                   pbytes, hipMemcpyDeviceToHost, c->stream);
-    if (ce == hipSuccess)
-        ce = hipStreamSynchronize(c->stream);
-    if (pinned)
-        (void)hipHostUnregister(paths_out);
-    BHMM_HIP(ce);
-    return BHMM_OK;
+    return deliver_paths(c, paths_out, out_fmt, path);
 }
 
 int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
@@ -882,11 +886,8 @@ int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double
                 c->ds.smp_W = 64;
             sg.W = c->ds.smp_W;
             if ((rc = c->d_sentry.ensure((size_t)sg.nseg)) || (rc = c->d_sexit.ensure((size_t)sg.nseg)) ||
-                (rc = c->d_vflag.ensure((size_t)sg.nseg)) || (rc = c->d_specres.ensure(4)))
+                (rc = c->d_vflag.ensure((size_t)sg.nseg)) || (rc = ensure_specres(c)))
                 return rc;
-            if (!c->h_specres)
-                BHMM_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_specres), 4 * sizeof(unsigned int),
-                                       hipHostMallocDefault));
             const dim3 sgrid((sg.nseg + GP * WVS_WPB - 1) / (GP * WVS_WPB)), sblk(64 * WVS_WPB);
             auto *kfirst = NP == 16   ? k_wide_sample_seg<16, false>
                            : NP == 32 ? k_wide_sample_seg<32, false>
@@ -897,14 +898,15 @@ int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double
             const int max_rounds = 16;
             int round = 0;
             for (; round <= max_rounds; ++round) {
-                BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 4 * sizeof(unsigned int), c->stream));
+                if ((rc = specres_reset(c)))
+                    return rc;
                 lds_poison(c->stream);
                 BHMM_HIP(launch(round == 0 ? kfirst : kfix, sgrid, sblk, 0, c->stream, m, off, sg, c->d_alpha_rm.p, udev, seed,
                                 path, status, c->d_soff.p, c->d_sentry.p, c->d_sexit.p, c->d_vflag.p, watch));
                 BHMM_HIP(launch(k_wide_smp_check, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg, c->d_sentry.p,
                                 c->d_sexit.p, c->d_vflag.p, c->d_specres.p));
-                BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 4 * sizeof(unsigned int),
-                                        hipMemcpyDeviceToHost, c->stream));
+                if ((rc = specres_read(c, 4, false)))
+                    return rc;
                 BHMM_HIP(hipMemcpyAsync(&c->h_specres[0], status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
                 BHMM_HIP(hipStreamSynchronize(c->stream));
                 if (round == 0)

@@ -1764,12 +1764,6 @@ __global__ void k_wide_vit_check(const Segs sg, double *v_entry, const double *v
 // rounds, which need none of this.   vall [total][n]: every vector of the first pass.
 // =========================================================================================
 constexpr int VM_STEPS = 1024; // steps of a segment per workgroup of k_vit_margin (A^T is staged once per workgroup)
-[[maybe_unused]] static __global__ void k_vm_transpose(const double *A, int n, double *At)
-{
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < n * n)
-        At[(e % n) * n + e / n] = A[e];
-}
 // ALDS = false (more than 128 states: A^T does not fit LDS): `A` is A TRANSPOSED in global memory, read per step.
 template <typename PT, int NC, bool ALDS = true>
 __global__ __launch_bounds__(256) void k_vit_margin(const double *A, int n, const int64_t *off, const Segs sg,

@@ -42,14 +42,6 @@ static int big_from()
     return v;
 }
 
-int64_t max_len(const bhmm_ctx *c)
-{
-    int64_t maxT = 0;
-    for (int k = 0; k < c->K; ++k)
-        maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
-    return maxT;
-}
-
 // segments that fill the chip (16 per workgroup, one workgroup per compute unit), but at least two
 // warm-ups long
 int64_t fill_len(const bhmm_ctx *c)
@@ -66,7 +58,7 @@ int plan_for(bhmm_ctx *c, int W)
     const int64_t wmin = c->n > big_from() ? std::max<int64_t>(W / 2, 32) : 2 * (int64_t)W;
     int64_t seglen = c->opt.wseg_len > 0 ? (int64_t)c->opt.wseg_len : std::max<int64_t>(fill_len(c), wmin);
     seglen = std::max(seglen, c->wseg_cur_len); // never more segments than allocated for
-    if (seglen >= max_len(c))
+    if (seglen >= longest_traj(c))
         seglen = 0; // one segment per trajectory: no boundaries to verify
     if (c->w_nseg[1] > 0 && seglen == c->wseg_cur_len)
         return BHMM_OK;
@@ -101,20 +93,12 @@ int run_check(bhmm_ctx *c, int dir)
     return BHMM_OK;
 }
 
-int read_flags(bhmm_ctx *c)
-{
-    BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 3 * sizeof(unsigned int), hipMemcpyDeviceToHost,
-                            c->stream));
-    BHMM_HIP(hipStreamSynchronize(c->stream));
-    return BHMM_OK;
-}
-
 // The warm-up length from forward passes: deviation at the segment boundaries after W steps, twice,
 // and the geometric decay between the two (the filter forgets its start vector) extrapolated to 1e-13.
 int calibrate(bhmm_ctx *c, const WideModel &m, bool *usable)
 {
     *usable = false;
-    const int64_t maxT = max_len(c);
+    const int64_t maxT = longest_traj(c);
     int W = std::max(16, (c->opt.spec_W_fixed ? c->ds.spec_W : 32) / 8 * 8);
     double prevW = 0.0, prevdev = 1.0;
     for (int it = 0; it < 8; ++it) {
@@ -126,8 +110,8 @@ int calibrate(bhmm_ctx *c, const WideModel &m, bool *usable)
             *usable = true;
             return BHMM_OK;
         }
-        BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 3 * sizeof(unsigned int), c->stream));
-        if ((rc = TILE_GEN_DISPATCH(launch_fwd, c, m)) || (rc = run_check(c, 0)) || (rc = read_flags(c)))
+        if ((rc = specres_reset(c, 3)) || (rc = TILE_GEN_DISPATCH(launch_fwd, c, m)) || (rc = run_check(c, 0)) ||
+            (rc = specres_read(c, 3)))
             return rc;
         if (c->h_specres[2]) { // left the range of the lazily scaled kernels: the order-faithful family
             c->last.wide_trouble = c->h_specres[2];
@@ -189,14 +173,11 @@ int tile_gen_alloc(bhmm_ctx *c)
     if ((rc = c->d_wlogLseg.ensure(nsmax)) || (rc = c->d_wePseg.ensure(nsmax)) ||
         (rc = c->d_waentry.ensure((size_t)nsmax * n)) || (rc = c->d_waexit.ensure((size_t)nsmax * n)) ||
         (rc = c->d_wbexit.ensure((size_t)nsmax * n)) || (rc = c->d_wbentry.ensure((size_t)nsmax * n)) ||
-        (rc = c->d_wexp.ensure((size_t)std::max<int64_t>(c->total, 1))) || (rc = c->d_specres.ensure(4)) ||
+        (rc = c->d_wexp.ensure((size_t)std::max<int64_t>(c->total, 1))) || (rc = ensure_specres(c)) ||
         (rc = c->d_partials.ensure(ntmax * S)))
         return rc;
     if (c->kind == EMIT_DISC && (rc = c->d_dpartials.ensure(4 * ntmax * (size_t)n * c->M)))
         return rc;
-    if (!c->h_specres)
-        BHMM_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_specres), 4 * sizeof(unsigned int),
-                               hipHostMallocDefault));
     BHMM_HIP(hipMemsetAsync(c->d_gamma0.p, 0, (size_t)std::max(c->K, 1) * n * sizeof(double), c->stream));
     return BHMM_OK;
 }
@@ -224,7 +205,8 @@ int tile_gen_estep(bhmm_ctx *c, const WideModel &m, double *stats_dev, int flags
         return rc;
     double *gam = sg ? c->d_gamma_ci.p : nullptr;
     for (int attempt = 0; attempt < 3; ++attempt) {
-        BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 3 * sizeof(unsigned int), c->stream));
+        if ((rc = specres_reset(c, 3)))
+            return rc;
         BHMM_HIP(hipEventRecord(c->ev[0], c->stream));
         if ((rc = TILE_GEN_DISPATCH(launch_fwd, c, m)))
             return rc;
@@ -237,7 +219,7 @@ int tile_gen_estep(bhmm_ctx *c, const WideModel &m, double *stats_dev, int flags
         const bool segmented = c->w_nseg[1] > c->w_nseg[0];
         if (segmented && ((rc = run_check(c, 0)) || (rc = run_check(c, 1))))
             return rc;
-        if ((rc = read_flags(c)))
+        if ((rc = specres_read(c, 3)))
             return rc;
         c->last.wide_trouble = c->h_specres[2];
         if (c->h_specres[2]) {
@@ -288,7 +270,7 @@ int tile_gen_estep(bhmm_ctx *c, const WideModel &m, double *stats_dev, int flags
         const double d = std::min(std::max((double)devf, 1e-300), 0.5);
         const double f = std::min(std::max(log(1e-13) / log(d), 1.25), 4.0);
         const int Wn = ((int)ceil(c->ds.spec_W * f) + 7) / 8 * 8;
-        if (Wn >= max_len(c) / 2)
+        if (Wn >= longest_traj(c) / 2)
             break;
         c->ds.spec_W = Wn;
         if ((rc = plan_for(c, Wn)))
@@ -317,13 +299,10 @@ int tile_gen_forward_draw(bhmm_ctx *c, const WideModel &m, bool *done)
             return BHMM_OK;
         }
     }
-    BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 3 * sizeof(unsigned int), c->stream));
-    if ((rc = TILE_GEN_DISPATCH(launch_fwd, c, m)))
+    if ((rc = specres_reset(c, 3)) || (rc = TILE_GEN_DISPATCH(launch_fwd, c, m)))
         return rc;
     const bool segmented = c->w_nseg[1] > c->w_nseg[0];
-    if (segmented && (rc = run_check(c, 0)))
-        return rc;
-    if ((rc = read_flags(c)))
+    if ((segmented && (rc = run_check(c, 0))) || (rc = specres_read(c, 3)))
         return rc;
     *done = c->h_specres[2] == 0 && (!segmented || c->h_specres[0] == 0);
     float dev = 0.f; // (largest boundary deviation the check saw: what the draws' watch is sized by)

@@ -341,11 +341,8 @@ int wide_alloc(bhmm_ctx *c)
         int64_t seglen = c->opt.wseg_len;
         if (seglen <= 0)
             seglen = std::max<int64_t>(wide_fill_len(c), (wide_tile(c) ? 2 : 8) * (int64_t)c->ds.spec_W);
-        int64_t maxT = 0;
-        for (int k = 0; k < c->K; ++k)
-            maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
         c->wseg_cur_len = seglen;
-        if (c->opt.wseg_enabled && maxT > seglen && (rc = wide_plan_segments(c, seglen)))
+        if (c->opt.wseg_enabled && longest_traj(c) > seglen && (rc = wide_plan_segments(c, seglen)))
             return rc;
     }
     // (buffers sized for the finest plan there can be: plan 2 has at most twice the segments of plan 1)
@@ -356,7 +353,7 @@ int wide_alloc(bhmm_ctx *c)
         (rc = c->d_partials.ensure((size_t)nsmax * S)) ||
         (rc = c->d_waentry.ensure((size_t)nsmax * n)) || (rc = c->d_waexit.ensure((size_t)nsmax * n)) ||
         (rc = c->d_wbexit.ensure((size_t)nsmax * n)) || (rc = c->d_wbentry.ensure((size_t)nsmax * n)) ||
-        (rc = c->d_specres.ensure(4)) ||
+        (rc = ensure_specres(c)) ||
         (rc = c->d_stats.ensure(1 + n + n * n + n + std::max(2 * n, n * c->M))))
         return rc;
     if (c->kind == EMIT_DISC && (rc = c->d_dpartials.ensure((size_t)std::max(nsmax, 4 * (nsmax / 16 + 2)) * n * c->M)))
@@ -364,9 +361,6 @@ int wide_alloc(bhmm_ctx *c)
     if (wide_tile(c) && ((rc = c->d_wexp.ensure((size_t)std::max<int64_t>(c->total, 1))) ||
                          (rc = c->d_wePseg.ensure(nsmax))))
         return rc;
-    if (!c->h_specres)
-        BHMM_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_specres), 4 * sizeof(unsigned int),
-                               hipHostMallocDefault));
     BHMM_HIP(hipMemsetAsync(c->d_gamma0.p, 0, (size_t)std::max(c->K, 1) * n * sizeof(double),
                             c->stream));
     return BHMM_OK;
@@ -380,10 +374,7 @@ template <int NP, int KIND>
 static int wide_probe_run(bhmm_ctx *c, const WideModel &m, int *W_out)
 {
     *W_out = 0;
-    int64_t maxT = 0;
-    for (int k = 0; k < c->K; ++k)
-        maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
-    const int Wmax = (int)std::min<int64_t>(8192, maxT / 2) / 8 * 8;
+    const int Wmax = (int)std::min<int64_t>(8192, longest_traj(c) / 2) / 8 * 8;
     if (Wmax < 64)
         return BHMM_OK;
     std::vector<int> longk;
@@ -452,14 +443,11 @@ static int wide_calibrate(bhmm_ctx *c, const WideModel &m)
     if (W > 0)
         c->ds.spec_W = W;
     if (W > W_planned) { // longer warm-ups than the plan assumed: longer segments
-        int64_t maxT = 0;
-        for (int k = 0; k < c->K; ++k)
-            maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
         int64_t seglen = c->opt.wseg_len;
         if (seglen <= 0)
             seglen = std::max<int64_t>(wide_fill_len(c), (wide_tile(c) ? 2 : 4) * (int64_t)W);
         seglen = std::max(seglen, c->wseg_cur_len); // never more segments than allocated for
-        if (seglen >= maxT) {
+        if (seglen >= longest_traj(c)) {
             c->ds.wseg_given_up = true;
         } else if (seglen > c->wseg_cur_len) {
             c->wseg_cur_len = seglen;
@@ -505,7 +493,8 @@ int wide_forward_draw(bhmm_ctx *c, const double *A, const double *pi, const doub
             return rc;
         if (!c->ds.wseg_given_up && c->w_nseg[1] > c->w_nseg[0]) {
             const bool lazy = !c->ds.careful && !c->ds.wide_careful;
-            BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 3 * sizeof(unsigned int), c->stream));
+            if ((rc = specres_reset(c, 3)))
+                return rc;
             switch (c->kind) {
             case EMIT_GAUSS:
                 rc = WIDE_DISPATCH(c, EMIT_GAUSS, wide_launch_fwd, c, m, 1, lazy);
@@ -521,9 +510,8 @@ int wide_forward_draw(bhmm_ctx *c, const double *A, const double *pi, const doub
             const Segs sgf = segs_of(c, wide_fwd_plan(c, 1));
             BHMM_HIP(launch(k_wide_check, dim3((sgf.nseg + 15) / 16), dim3(256), 0, c->stream, sgf, c->n,
                             c->d_waentry.p, c->d_waexit.p, nullptr, nullptr, 1e-11, c->d_specres.p));
-            BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 3 * sizeof(unsigned int),
-                                    hipMemcpyDeviceToHost, c->stream));
-            BHMM_HIP(hipStreamSynchronize(c->stream));
+            if ((rc = specres_read(c, 3)))
+                return rc;
             c->last.draw_fwd_segmented = c->h_specres[0] == 0 && (!lazy || c->h_specres[2] == 0);
             if (c->last.draw_fwd_segmented) {
                 float dev; // (largest boundary deviation the check saw: what the draws' watch is sized by)
@@ -584,16 +572,15 @@ int wide_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par
         // time-segmented run with warm-up boundaries, verified afterwards
         // lazily scaled kernels unless an earlier E-step on these data left their range
         const bool lazy = !c->ds.careful && !c->ds.wide_careful;
-        BHMM_HIP(hipMemsetAsync(c->d_specres.p, 0, 3 * sizeof(unsigned int), c->stream));
-        if ((rc = run(1, lazy)))
+        if ((rc = specres_reset(c, 3)) || (rc = run(1, lazy)))
             return rc;
         const Segs sgs = segs_of(c, 1), sgf = segs_of(c, wide_fwd_plan(c, 1));
         BHMM_HIP(launch(k_wide_check, dim3((sgf.nseg + 15) / 16), dim3(256), 0, c->stream, sgf, c->n, c->d_waentry.p,
                         c->d_waexit.p, nullptr, nullptr, 1e-11, c->d_specres.p));
         BHMM_HIP(launch(k_wide_check, dim3((sgs.nseg + 15) / 16), dim3(256), 0, c->stream, sgs, c->n, nullptr, nullptr,
                         c->d_wbexit.p, c->d_wbentry.p, 1e-11, c->d_specres.p));
-        BHMM_HIP(hipMemcpyAsync(c->h_specres, c->d_specres.p, 3 * sizeof(unsigned int),
-                                hipMemcpyDeviceToHost, c->stream));
+        if ((rc = specres_read(c, 3, false)))
+            return rc;
         // the statistics (and, for moderately many trajectories, the log-likelihoods) travel with the verdict
         // words: ONE host round trip per verified E-step -- bhmm_estep_fetch finds them in the pinned buffer
         const int S = bhmm_ctx_stats_size(c);
@@ -682,9 +669,7 @@ int wide_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par
         // vector): extrapolate to where it reaches a tenth of the tolerance, lengthen the
         // segments to at least four warm-ups and try again at the next call; give up (serial
         // plan) after three re-plans or when the segments would no longer split a trajectory.
-        int64_t maxT = 0;
-        for (int k = 0; k < c->K; ++k)
-            maxT = std::max(maxT, c->offsets[k + 1] - c->offsets[k]);
+        const int64_t maxT = longest_traj(c);
         const double d = std::min(std::max((double)dev, 1e-300), 0.5);
         double f = log(1e-12) / log(d);
         f = std::min(std::max(f, 1.25), 8.0);
