@@ -17,19 +17,26 @@ committed N = 1 value), and the packed sufficient statistics are all-reduced ove
     python bench.py --gpus 1 --steps 200 --warmup 50    # the defaults
     python bench.py --gpus N ...        # WORLD_SIZE unset: starts N ranks itself (torchrun)
     python bench.py ... --dump-outputs DIR   # + the statistics of the last timed step as DIR/<field>.npy
+    python bench.py ... --full          # + everything below that is not the headline figure
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-The JSON line carries, for THAT workload, `roofline` (algorithmic bytes of SURVEY.md 8(d), 136 B per
-time step, over the sweep kernels' duration by HIP events; PMC traffic and issue rate from the offline
-passes named in `traffic_source`) and `cpu_baseline` (the reference's own C kernels on one core on a
-bounded sample of the same trajectories, plus `all_cores`; rank 0, also at N > 1).
+A plain run does what `value` needs and nothing more: it draws the data, warms up, times the K steps,
+writes --dump-outputs and prints the line.  The line carries, for THAT workload, `roofline` (algorithmic
+bytes of SURVEY.md 8(d), 136 B per time step, over the sweep kernels' duration by HIP events of the
+timed steps; PMC traffic and issue rate from the offline passes named in `traffic_source`) and
+`kernel_ms`, both read off the timed steps themselves.
 
-At N = 1 the line additionally carries `configs1_gaussian` -- BASELINE configs[1] (8-state Gaussian,
-256 x 1e5), the headline of rounds 1-4, with its own roofline and CPU figure so that series
-continues -- `configs3_64_states`, `more_than_64_states`, and `secondary` (Viterbi and the Gibbs
-path step at the configs[1] shape, whole EM iterations and whole Gibbs sweeps, host side included).
-At N > 1 `secondary` holds the whole EM iterations / Gibbs sweeps of the estimator classes, sharded.
+With --full the run goes on after the headline: a steady-state window behind the timed steps
+(`steady_state_ms`), `cpu_baseline` (the reference's own C kernels on one core on a bounded sample of
+the same trajectories, plus `all_cores`; rank 0, also at N > 1), at N > 1 the all-reduce alone, and at
+N = 1 the PMC traffic and issue rate measured by the run itself (three rocprofv3 passes), plus
+`configs1_gaussian` -- BASELINE configs[1] (8-state Gaussian, 256 x 1e5), the headline of rounds 1-4,
+with its own roofline and CPU figure so that series continues -- `configs3_64_states`,
+`more_than_64_states`, `secondary` (Viterbi and the Gibbs path step at the configs[1] shape, whole EM
+iterations and whole Gibbs sweeps, host side included) and `projected_8gpu`.  At N > 1 `secondary`
+holds the whole EM iterations / Gibbs sweeps of the estimator classes, sharded.  The --no-* options
+below take parts out of a --full run.
 """
 import argparse
 import json
@@ -992,6 +999,10 @@ def main():
     ap.add_argument("--ntraj", type=int, default=1024, help="trajectories of the headline workload, IN TOTAL")
     ap.add_argument("--length", type=int, default=1000000)
     ap.add_argument("--chunk", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the steady-state window, the CPU baselines, the live counter "
+                         "passes, the other configurations and the 8-GPU projection (several minutes); the "
+                         "--no-* options below take parts out of it")
     ap.add_argument("--cpu-traj", type=int, default=48,
                     help="trajectories in the 1-core CPU baseline of the headline (~10 s at 1e6 steps each)")
     ap.add_argument("--no-cpu", action="store_true")
@@ -1079,7 +1090,7 @@ def main():
     # and the timed loop would let the GPU fall back to its idle clocks right before the warm-up steps)
     wl = workload_configs2(K, T)
     ser = Series(rk, wl, Kloc, rank * Kloc, chunk=args.chunk)
-    ser.run(args.warmup, args.steps, 0 if args.no_steady else 40)
+    ser.run(args.warmup, args.steps, 40 if args.full and not args.no_steady else 0)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, ser.eng.unpack(ser.last_timed))
     elapsed = ser.elapsed
@@ -1099,9 +1110,9 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         same = bool(torch.equal(lo, hi))
         assert same, "the ranks hold different reduced statistics"
-    coll_ms = ser.collective_ms()
+    coll_ms = ser.collective_ms() if args.full else None
     cb = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         if rank == 0:
             # at N > 1 a smaller sample: the other ranks wait at the next barrier meanwhile
             cb = cpu_legs(wl, ser, args.cpu_traj if world == 1 else min(args.cpu_traj, 8), all_cores=(world == 1))
@@ -1139,7 +1150,7 @@ def main():
             "allreduce_plus_copy_ms": coll_ms,
             "synth_seconds": ser.synth_seconds,
             "timing_note": "ms_per_step covers exactly the requested steps, max over ranks, between barriers; "
-                           "steady_state_ms is the median of the last 20 steps of an extra 40-step window "
+                           "steady_state_ms (--full) is the median of the last 20 steps of an extra 40-step window "
                            "right behind them (DESIGN.md section 7)",
         }
         if cb is not None:
@@ -1152,7 +1163,8 @@ def main():
     ser.close()
     del ser
 
-    if rank == 0 and world == 1 and out is not None and not (args.no_live_traffic or args.no_secondary or args.only):
+    if args.full and rank == 0 and world == 1 and out is not None and \
+            not (args.no_live_traffic or args.no_secondary or args.only):
         # roofline.traffic of THIS run (the engine above is closed: its 20 GB are free for the child processes)
         lt = live_traffic(K, T)
         if lt is not None:
@@ -1168,7 +1180,7 @@ def main():
                                                                        rf["sweep_kernel_ms"] * 1e3)
                 rf["traffic_live_detail"]["issue"] = iss
 
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         # the secondary measurements run on ALL ranks (their collectives need everyone)
         sec = []
         c1 = c4 = gen = None

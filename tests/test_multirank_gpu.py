@@ -96,9 +96,9 @@ def test_bench_starts_its_own_ranks(launcher):
     """`python bench.py --gpus 2` without a launcher environment starts two ranks itself and
     reports n_gpus = 2 (here both ranks share the box's one GPU: --oversubscribe, gloo).  `value` is
     configs[2] STRONG-scaled: the trajectories are drawn by global index, so the 2-rank run sees the
-    data of the 1-rank run -- same log-likelihood --, the line carries the same roofline /
+    data of the 1-rank run -- same log-likelihood --, the --full line carries the same roofline /
     cpu_baseline keys at both N, and `secondary` the whole iterations of the estimator classes."""
-    small = ["--steps", "3", "--warmup", "1", "--ntraj", "8", "--length", "50000", "--cpu-traj", "2",
+    small = ["--full", "--steps", "3", "--warmup", "1", "--ntraj", "8", "--length", "50000", "--cpu-traj", "2",
              "--c1-ntraj", "16", "--c1-length", "20000", "--c1-steps", "3", "--c1-warmup", "1",
              "--c1-cpu-traj", "2", "--chain-sweeps", "3", "--em-iterations", "3"]
     one, two = [_bench_line(launcher, g, small) for g in (1, 2)]
@@ -147,13 +147,33 @@ def test_bench_dumps_the_last_timed_step(launcher, tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_alone(launcher):
+    """Without --full the run times the requested steps and stops: the line has the headline fields, the
+    roofline and kernel times of the timed steps and the offline counter figures, and none of what --full adds
+    (steady-state window, CPU legs, live counter passes, other configurations, projection)."""
+    K, T = 16, 30000
+    line = _bench_line(launcher, 1, ["--steps", "3", "--warmup", "1", "--ntraj", str(K), "--length", str(T)])
+    assert line["metric"].startswith("timesteps/sec") and line["unit"] == "timesteps/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["steps"] == 3 and line["warmup"] == 1
+    assert abs(line["value"] - K * T * 3 / (line["ms_per_step"] * 3e-3)) < 1e-6 * line["value"]
+    assert line["roofline"]["alg_bytes_per_launch"] == 136 * K * T and line["roofline"]["sweep_kernel_ms"] > 0
+    assert line["roofline"]["traffic_is_live"] is False and line["kernel_ms"]["estep_total"] > 0
+    assert line["steady_state_ms"] is None and line["allreduce_plus_copy_ms"] is None
+    for key in ("cpu_baseline", "speedup_vs_1core", "target_50x_met", "secondary", "configs1_gaussian",
+                "configs3_64_states", "more_than_64_states", "projected_8gpu"):
+        assert key not in line, key
+    assert "traffic_live_detail" not in line["roofline"]
+
+
+@pytest.mark.gpu
 def test_bench_collective_path_on_rccl_with_one_rank(launcher):
     """The driver launches `bench.py --gpus N` under torch.distributed.run with backend nccl (= RCCL).  A
     one-GPU box can run that code path with ONE rank: RANK / WORLD_SIZE in the environment make the bench take
     its distributed branch -- statistics into a device buffer, `all_reduce` on the engine's stream, one
     non-blocking copy, the MIN / MAX comparison of the ranks' statistics, the max-over-ranks timing -- on RCCL,
-    and the line must equal the plain one-process run's."""
-    small = ["--steps", "2", "--warmup", "1", "--ntraj", "16", "--length", "30000", "--cpu-traj", "2",
+    and the line (with --full: also the CPU legs and the all-reduce alone) must equal the one-process run's."""
+    small = ["--full", "--steps", "2", "--warmup", "1", "--ntraj", "16", "--length", "30000", "--cpu-traj", "2",
              "--no-secondary", "--no-steady"]
     plain = _bench_line(launcher, 1, small)
     import json

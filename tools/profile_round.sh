@@ -7,8 +7,8 @@ tag=$1
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --steps 20 --warmup 3 > $O/${tag}_bench.json 2> /tmp/bench.err || tail -5 /tmp/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_k -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu > $O/${tag}_bench_under_rocprof.json 2> /tmp/prof_k.err
+python3 $R/bench.py --full --steps 20 --warmup 3 > $O/${tag}_bench.json 2> /tmp/bench.err || tail -5 /tmp/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_k -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu > $O/${tag}_bench_under_rocprof.json 2> /tmp/prof_k.err
 cp $(find /tmp/prof_k -name "*kernel_stats.csv" | head -1) $O/${tag}_kernel_stats.csv
 for ctr in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d /tmp/prof_$ctr -- python3 $R/tools/pmc_traffic.py > /tmp/prof_$ctr.log 2>&1

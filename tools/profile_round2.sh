@@ -12,9 +12,9 @@ tag=$1
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $O/${tag}_bench.json 2> /tmp/bench.err || tail -5 /tmp/bench.err
+python3 $R/bench.py --full > $O/${tag}_bench.json 2> /tmp/bench.err || tail -5 /tmp/bench.err
 rm -rf /tmp/prof_k
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_k -- python3 $R/bench.py --no-cpu > $O/${tag}_bench_under_rocprof.json 2> /tmp/prof_k.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_k -- python3 $R/bench.py --full --no-cpu > $O/${tag}_bench_under_rocprof.json 2> /tmp/prof_k.err
 cp $(find /tmp/prof_k -name "*kernel_stats.csv" | head -1) $O/${tag}_kernel_stats.csv
 # the headline loop alone (50 + 200 launches of the sweep pair, nothing else): the averages that
 # roofline.achieved of the bench line must agree with
