@@ -602,19 +602,14 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
-// value of lane K (0..H-1) of my H-lane group, H in {1,2,4}: one quad permute per dword
-template <int H, int K>
-__device__ __forceinline__ double grp_bcast(double x)
+// value of lane q ^ K of my group (K = 1..3, inside the quad): one quad permute per dword
+template <int K>
+__device__ __forceinline__ double grp_xor(double x)
 {
-    if constexpr (H == 1) {
-        return x;
-    } else {
-        constexpr int CTRL = (H == 4) ? (K | (K << 2) | (K << 4) | (K << 6))
-                                      : (K | (K << 2) | ((2 + K) << 4) | ((2 + K) << 6));
-        const int lo = dpp_i32<CTRL>(__double2loint(x));
-        const int hi = dpp_i32<CTRL>(__double2hiint(x));
-        return __hiloint2double(hi, lo);
-    }
+    constexpr int CTRL = (0 ^ K) | ((1 ^ K) << 2) | ((2 ^ K) << 4) | ((3 ^ K) << 6);
+    const int lo = dpp_i32<CTRL>(__double2loint(x));
+    const int hi = dpp_i32<CTRL>(__double2hiint(x));
+    return __hiloint2double(hi, lo);
 }
 template <int H>
 __device__ __forceinline__ double grp_sum(double x)
@@ -634,22 +629,29 @@ __device__ __forceinline__ int grp_max_i32(int v)
         v = max(v, xchg_i32<2>(v));
     return v;
 }
-// all-gather: full[2k + b] = pair[b] of lane k
+// Lane-relative all-gather: full[2k + b] = pair[b] of lane q ^ k, so slot i of the gathered
+// vector holds state slot_state(i, q) = i ^ 2q.  Slot 0..1 is my own pair and costs nothing: 2 (H - 1)
+// doubles move, not 2 H.  Whatever is combined with a gathered vector entry by entry (the columns and
+// rows of A, the xi accumulators) is kept in the same slot order.
+__device__ __forceinline__ int slot_state(int i, int q)
+{
+    return i ^ (2 * q);
+}
 template <int N>
 __device__ __forceinline__ void grp_gather(const double (&pair)[2], double (&full)[N])
 {
     constexpr int H = N / 2;
-    full[0] = grp_bcast<H, 0>(pair[0]);
-    full[1] = grp_bcast<H, 0>(pair[1]);
+    full[0] = pair[0];
+    full[1] = pair[1];
     if constexpr (H >= 2) {
-        full[2] = grp_bcast<H, 1>(pair[0]);
-        full[3] = grp_bcast<H, 1>(pair[1]);
+        full[2] = grp_xor<1>(pair[0]);
+        full[3] = grp_xor<1>(pair[1]);
     }
     if constexpr (H >= 4) {
-        full[4] = grp_bcast<H, 2>(pair[0]);
-        full[5] = grp_bcast<H, 2>(pair[1]);
-        full[6] = grp_bcast<H, 3>(pair[0]);
-        full[7] = grp_bcast<H, 3>(pair[1]);
+        full[4] = grp_xor<2>(pair[0]);
+        full[5] = grp_xor<2>(pair[1]);
+        full[6] = grp_xor<3>(pair[0]);
+        full[7] = grp_xor<3>(pair[1]);
     }
 }
 
@@ -766,11 +768,11 @@ __global__ __launch_bounds__(32 * N) void k_rows(const Model<N> m, const Chunks 
         pi2[b] = m.pi[2 * q + b];
     }
     if constexpr (MODE == MODE_FWD) {
-        double Ac[N][2], a[2];
+        double Ac[N][2], a[2]; // in the slot order of grp_gather
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            Ac[i][0] = m.A[i * N + 2 * q];
-            Ac[i][1] = m.A[i * N + 2 * q + 1];
+            Ac[i][0] = m.A[slot_state(i, q) * N + 2 * q];
+            Ac[i][1] = m.A[slot_state(i, q) * N + 2 * q + 1];
         }
         double P = 1.0; // running product of the scaling factors c_t, mantissa part
         int eP = 0;     // ... and its binary exponent: logL = log(P) + eP ln 2
@@ -842,11 +844,11 @@ __global__ __launch_bounds__(32 * N) void k_rows(const Model<N> m, const Chunks 
         if (q == 0)
             logL_chunk[g] = log(P) + (double)eP * 0.693147180559945309417232121458;
     } else {
-        double Ar[2][N], b2[2];
+        double Ar[2][N], b2[2]; // in the slot order of grp_gather
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            Ar[0][i] = m.A[(2 * q) * N + i];
-            Ar[1][i] = m.A[(2 * q + 1) * N + i];
+            Ar[0][i] = m.A[(2 * q) * N + slot_state(i, q)];
+            Ar[1][i] = m.A[(2 * q + 1) * N + slot_state(i, q)];
         }
         {
             const double2 x = *reinterpret_cast<const double2 *>(beta_exit + g * N + 2 * q);

@@ -370,11 +370,16 @@ __device__ __forceinline__ int scaled_emit(const ObsIn &in, int q, int nreal,
     return -ne - extra;
 }
 
-// All-gather of a state-pair over the H lanes of a chunk.  ESTEP_LDS_GATHER: through a
-// per-wavefront LDS exchange area (one 16-byte write, H 16-byte broadcast reads: LDS
-// instructions, which leave the VALU to the arithmetic); otherwise on DPP quad permutes (2 VALU
-// moves per double).  LDS operations of one wavefront execute in order, so the reads see the
-// writes of the same step and no barrier is needed -- only the compiler has to keep the order.
+// All-gather of a state-pair over the H lanes of a chunk; slot i of the gathered vector holds
+// state slot(i, q), and the columns / rows of A and the xi accumulators are kept in that order.
+// ESTEP_LDS_GATHER: through a per-wavefront LDS exchange area (one 16-byte write, H 16-byte
+// broadcast reads: LDS instructions, which leave the VALU to the arithmetic), in state order.
+// Otherwise on DPP quad permutes (2 VALU moves per double) in the lane-relative order of
+// grp_gather, which moves H - 1 pairs instead of H.  (The LDS exchange keeps the state order:
+// reading lane q ^ k takes one address register per slot where the broadcast reads share one,
+// and the four-wavefront launches have none to spare.)  LDS operations of one wavefront execute
+// in order, so the reads see the writes of the same step and no barrier is needed -- only the
+// compiler has to keep the order.
 #ifndef ESTEP_LDS_GATHER
 #define ESTEP_LDS_GATHER 1
 #endif
@@ -393,6 +398,10 @@ struct Gather {
         double2 *base = reinterpret_cast<double2 *>(area) + wv * 64;
         w = base + (lane % H) * (64 / H) + lane / H;
         r = base + lane / H;
+    }
+    __device__ __forceinline__ static int slot(int i, int q)
+    {
+        return LDS ? i : slot_state(i, q);
     }
     __device__ __forceinline__ void operator()(const double (&pair)[2], double (&full)[N]) const
     {
@@ -635,8 +644,8 @@ __device__ __forceinline__ void estep_body(
     // the discrete kind keeps its LDS unit busy with the emission table and the count atomics:
     // its all-gather runs on DPP instead (measured: 13 % faster there, equal for the gaussian)
     // (P1 and the forward-only pass keep no counts: there the discrete kind exchanges through LDS too)
-    const Gather<N, ESTEP_LDS_GATHER && (KIND != EMIT_DISC || ESTEP_DISC_P1_LDS * (PHASE == PH_P1 || PHASE == PH_FWDROWS))>
-        gather(dstat0 + dcopies * Mlds * N);
+    using G = Gather<N, ESTEP_LDS_GATHER && (KIND != EMIT_DISC || ESTEP_DISC_P1_LDS * (PHASE == PH_P1 || PHASE == PH_FWDROWS))>;
+    const G gather(dstat0 + dcopies * Mlds * N);
     int hmin = 0x7fffffff;
     [[maybe_unused]] int wmax = 0; // branch-free sweeps: largest alpha / S seen (high dword), see the self-check
 #ifdef ESTEP_CLOCKPROBE
@@ -690,12 +699,13 @@ __device__ __forceinline__ void estep_body(
     if (len > 0) {
         double a[2];
         double2 aent = make_double2(0.0, 0.0); // the vector this chunk was entered with
-        // my two columns of A (forward products; with ESTEP_CKPT also the backward sweep)
+        // my two columns of A (forward products; with ESTEP_CKPT also the backward sweep), in the
+        // slot order of the gathered vectors
         double Ac[N][2];
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            Ac[i][0] = m.A[i * N + 2 * q];
-            Ac[i][1] = m.A[i * N + 2 * q + 1];
+            Ac[i][0] = m.A[G::slot(i, q) * N + 2 * q];
+            Ac[i][1] = m.A[G::slot(i, q) * N + 2 * q + 1];
         }
         // ---------------- forward sweep (_hidden.c:16-66) ------------------------------
         if constexpr (PHASE == PH_P2) {
@@ -941,11 +951,11 @@ __device__ __forceinline__ void estep_body(
         if constexpr (!FWDONLY) {
         if (role_b) {
         // ---------------- backward sweep (_hidden.c:69-110, hidden/api.py:176-186) ----------
-        double Ar[2][N];
+        double Ar[2][N]; // my two rows of A, in slot order (as Cacc)
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            Ar[0][i] = m.A[(2 * q) * N + i];
-            Ar[1][i] = m.A[(2 * q + 1) * N + i];
+            Ar[0][i] = m.A[(2 * q) * N + G::slot(i, q)];
+            Ar[1][i] = m.A[(2 * q + 1) * N + G::slot(i, q)];
         }
         const int k = ch.traj[g];
         double b2[2], gam[2];
@@ -1498,9 +1508,9 @@ __device__ __forceinline__ void estep_body(
         for (int b = 0; b < 2; ++b) {
 #pragma unroll
             for (int j = 0; j < N; ++j) {
-                const double v = chunk_sum(Cacc[b][j]);
+                const double v = chunk_sum(Cacc[b][j]); // (slot j: lanes of equal q agree)
                 if (lane < H)
-                    mine[(2 * q + b) * N + j] = v;
+                    mine[(2 * q + b) * N + G::slot(j, q)] = v;
             }
             const double v = chunk_sum(sg[b]);
             if (lane < H)
