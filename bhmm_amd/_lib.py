@@ -71,6 +71,8 @@ SIGNATURES = {
                                   c_void_p, ctypes.c_int]),
     "bhmm_estep_fetch": (ctypes.c_int, [c_void_p, c_double_p, c_double_p]),
     "bhmm_get_gamma": (ctypes.c_int, [c_void_p, ctypes.c_int, c_double_p]),
+    "bhmm_score": (ctypes.c_int, [c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p,
+                                  c_double_p]),
     "bhmm_viterbi_batch": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,
                                           c_double_p, c_int32_p]),
     "bhmm_viterbi_batch_u8": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,

@@ -121,3 +121,55 @@ def bayesian_hmm(observations, estimated_hmm, nsample=100, reversible=True, stat
     sampled = sampler.sample(nsamples=nsample, save_hidden_state_trajectory=store_hidden,
                              call_back=call_back)
     return SampledHMM(estimated_hmm, sampled)
+
+
+def score(observations, models, lag=1, per_trajectory=False, **engine_kwargs):
+    """Log-likelihood of `observations` under each of `models` (one forward pass per model, all
+    models of a call on the GPU together, bhmm_score).  `models`: one HMM, a list of HMMs of the same
+    output type and number of states, or a SampledHMM (its sampled models).  lag > 1 scores the lagged
+    views (lag_observations).  Returns one total per model (an array of shape (S,)), or with
+    per_trajectory the (S, K) array of per-trajectory log-likelihoods.  A trajectory of probability zero
+    under a model scores -inf.  engine_kwargs: device (default 0)."""
+    from .engine import Engine
+    from .estimators.maximum_likelihood import model_tuple
+    if isinstance(models, SampledHMM):
+        models = models.sampled_hmms
+    elif isinstance(models, HMM):
+        models = [models]
+    models = list(models)
+    if not models:
+        raise ValueError("score needs at least one model")
+    for m in models:
+        if not isinstance(m, HMM):
+            raise TypeError("models must be HMM objects (or a SampledHMM)")
+    output = models[0].output_model.model_type
+    nstates = models[0].nstates
+    for m in models[1:]:
+        if m.output_model.model_type != output:
+            raise ValueError("all models must have the same output type (got %r and %r)"
+                             % (output, m.output_model.model_type))
+        if m.nstates != nstates:
+            raise ValueError("all models must have the same number of states")
+    nsymbols = models[0].output_model.nsymbols if output == 'discrete' else 0
+    if output == 'discrete':
+        for m in models[1:]:
+            if m.output_model.nsymbols != nsymbols:
+                raise ValueError("all models must have the same number of symbols")
+    if len(observations) == 0:
+        raise ValueError("no observations")
+    device = engine_kwargs.pop('device', 0)
+    if engine_kwargs:
+        raise TypeError("unexpected keyword arguments: %s" % ", ".join(sorted(engine_kwargs)))
+    if lag > 1:
+        observations = lag_observations(observations, lag)
+    eng = Engine(device)
+    try:
+        if output == 'discrete':
+            obs = [np.asarray(o) for o in observations]
+            eng.set_observations('discrete', obs, nstates, nsymbols=nsymbols)
+        else:
+            eng.set_observations(output, [np.asarray(o, dtype=np.float64) for o in observations], nstates)
+        logL = eng.score([model_tuple(m) for m in models])
+    finally:
+        eng.close()
+    return logL if per_trajectory else logL.sum(axis=1)

@@ -1522,6 +1522,13 @@ int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
         c->opt.tile_enabled = value != 0.0; // row-batched matrix-core recursions (next set_observations)
     else if (n == "tile_per_cu")
         c->opt.tile_per_cu = std::max(1, std::min(4, (int)value)); // (next set_observations)
+    else if (n == "score_W") // bhmm_score only: fixed warm-up (0: measured per model); no E-step state changes
+        c->opt.score_W = std::max(0, (int)value);
+    else if (n == "score_layout") { // bhmm_score, N <= 8: 1 = one lane per chunk, 2 = N/2 lanes per chunk
+        if (value != 1.0 && value != 2.0)
+            return invalid_arg("score_layout must be 1 or 2");
+        c->opt.score_layout = (int)value;
+    }
     else
         return invalid_arg("unknown or read-only option: " + n);
     return BHMM_OK;
@@ -1623,6 +1630,12 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
     else if (n == "wide_fwd_segments") // the forward pass's own, finer plan (64 states), 0 if none
         *value = (c->opt.wseg_enabled && !c->ds.wseg_given_up && c->w_nseg[1] > c->w_nseg[0] &&
                   c->w_nseg[2] > c->w_nseg[1]) ? c->w_nseg[2] : 0;
+    else if (n == "score_W")
+        *value = c->opt.score_W;
+    else if (n == "score_layout")
+        *value = c->opt.score_layout;
+    else if (n == "score_fallbacks") // bhmm_score: models whose boundaries did not verify at the first warm-up
+        *value = c->last.score_fallbacks;
     else
         return invalid_arg("unknown option: " + n);
     return BHMM_OK;

@@ -100,6 +100,8 @@ struct bhmm_ctx {
         int wseg_len = 0;                // 0 = automatic
         double f32_tol = 1e-5;           // BHMM_FLAG_SINGLE: tolerance of the fp32 boundary check (option f32_tol)
         int f32_W = 0;                   // ... fp32 warm-up fixed by the caller (option f32_W; 0: measured)
+        int score_W = 0;                 // bhmm_score: warm-up fixed by the caller (option score_W; 0: measured per model)
+        int score_layout = 1;            // bhmm_score, N <= 8: 1 = one lane per chunk (default), 2 = N/2 lanes per chunk
     } opt;
 
     // ---- loaded problem ----
@@ -191,6 +193,7 @@ struct bhmm_ctx {
         bool f32_used = false;           // the last E-step ran in fp32 end to end (BHMM_FLAG_SINGLE)
         int f32_fallbacks = 0;           // E-steps that asked for fp32 and ran the fp64 path
         float f32_last_dev = 0.f;        // largest relative boundary deviation of the last fp32 check
+        int score_fallbacks = 0;         // bhmm_score: models whose boundaries did not verify at the first warm-up
     } last;
 
     // ---- not reset by bhmm_ctx_set_observations: they outlive the observation set ----
@@ -284,6 +287,14 @@ struct bhmm_ctx {
     // fp32 E-step (estep_f32.hip): boundary vectors [4][Gp][N], B^T in fp32, verdict words
     bhmm::DevBuf<float> d_f32vec, d_Bt32;
     bhmm::DevBuf<unsigned int> d_f32words;
+    // bhmm_score (score_api.hip): its own buffers -- model table, B^T per model, per (model, chunk) log-normaliser
+    // and boundary vectors, per (model, trajectory) logL, failure counters, probe curve; nothing else reads them
+    struct ScoreBufs {
+        bhmm::DevBuf<char> models, probe;
+        bhmm::DevBuf<double> Bt, logLc, aentry, aexit, logLk, par;
+        bhmm::DevBuf<int32_t> W;
+        bhmm::DevBuf<unsigned int> fails;
+    } score;
 
     // ---- pinned host buffers ----
     unsigned int *h_specres = nullptr; // pinned

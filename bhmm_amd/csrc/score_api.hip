@@ -1,0 +1,344 @@
+// score_api.hip -- bhmm_score: log-likelihood of every loaded trajectory under each of several models
+// (forward pass only).  Kernels in score_kernels.hpp; DESIGN.md section 13.
+//
+// Up to 8 states, gaussian or discrete: k_score_fwd over the E-step's chunk plan, all models of a batch
+// (at most SCORE_MAX_MODELS) in one launch, then k_score_check and k_score_logl.  Every model has a
+// warm-up of its own (the forgetting probe of the E-step, k_forget_probe, or the option score_W), so
+// its result does not depend on the other models of the call.  A model whose boundaries do not verify
+// runs again alone with twice the warm-up; if they fail again it takes the exact serial recursion
+// (k_score_serial).  More than 8 states and explicit pobs always take the exact path.
+//
+// Nothing here reads or writes the E-step's state (ds.*, carried vectors, warm-up lengths, d_Bt, the
+// timing events, the pinned landing zones): the buffers are c->score.*, the only other fields touched
+// are opt.score_W (read) and last.score_fallbacks.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "host_common.hpp"
+#include "host_internal.hpp"
+#include "launch.hpp"
+#include "score_kernels.hpp"
+
+namespace bhmm {
+
+namespace {
+
+constexpr double SCORE_TOL = 1e-11;         // boundary check: componentwise relative (the E-step's spec_tol default)
+constexpr int SCORE_W_UNPROBED = 288;       // warm-up when the trajectories are too short to probe (the E-step's)
+constexpr size_t SCORE_LDS_BT = 16 * 1024;  // B^T of a model staged in LDS up to this size
+constexpr double SCORE_STOCH_TOL = 1e-8;    // rows of A, pi and B must sum to 1 within this
+
+int check_prob_rows(const double *p, int rows, int cols, int s, const char *what)
+{
+    for (int r = 0; r < rows; ++r) {
+        double sum = 0.0;
+        for (int j = 0; j < cols; ++j) {
+            const double v = p[(size_t)r * cols + j];
+            if (!std::isfinite(v) || v < 0.0)
+                return invalid_arg("bhmm_score: model " + std::to_string(s) + ": " + what +
+                                   " has a negative or non-finite entry");
+            sum += v;
+        }
+        if (!(fabs(sum - 1.0) <= SCORE_STOCH_TOL))
+            return invalid_arg("bhmm_score: model " + std::to_string(s) + ": " + what +
+                               (rows > 1 ? " row " + std::to_string(r) : std::string()) + " sums to " +
+                               std::to_string(sum) + ", not 1");
+    }
+    return BHMM_OK;
+}
+
+int check_models(const bhmm_ctx *c, int S, const double *A, const double *pi, const double *par0,
+                 const double *par1)
+{
+    const int n = c->n;
+    int rc;
+    for (int s = 0; s < S; ++s) {
+        if ((rc = check_prob_rows(A + (size_t)s * n * n, n, n, s, "A")) ||
+            (rc = check_prob_rows(pi + (size_t)s * n, 1, n, s, "pi")))
+            return rc;
+        if (c->kind == EMIT_GAUSS) {
+            for (int i = 0; i < n; ++i) {
+                const double mu = par0[(size_t)s * n + i], sg = par1[(size_t)s * n + i];
+                if (!std::isfinite(mu) || !std::isfinite(sg) || !(sg > 0.0) ||
+                    !std::isfinite(1.0 / (sqrt(2.0 * M_PI) * sg)))
+                    return invalid_arg("bhmm_score: model " + std::to_string(s) +
+                                       ": means must be finite and sigmas positive and finite");
+            }
+        } else if (c->kind == EMIT_DISC) {
+            if ((rc = check_prob_rows(par0 + (size_t)s * n * c->M, n, c->M, s, "B")))
+                return rc;
+        }
+    }
+    return BHMM_OK;
+}
+
+// per (trajectory, model) log-likelihood on the exact serial recursion for models [0, S) of the stacked
+// arrays; out[s * K + k]
+int score_serial(bhmm_ctx *c, int S, const double *A, const double *pi, const double *par0, const double *par1,
+                 double *out)
+{
+    const int n = c->n, K = c->K;
+    const size_t np0 = c->kind == EMIT_GAUSS ? (size_t)n : (c->kind == EMIT_DISC ? (size_t)n * c->M : 0);
+    const size_t np1 = c->kind == EMIT_GAUSS ? (size_t)n : 0;
+    const size_t per = (size_t)n * n + n + np0 + np1;
+    const int bd = std::min(1024, (n + 63) / 64 * 64);
+    const size_t lds = ((size_t)n + 16) * sizeof(double);
+    auto &b = c->score;
+    int rc;
+    for (int s0 = 0; s0 < S; s0 += SCORE_MAX_MODELS) {
+        const int Sb = std::min(SCORE_MAX_MODELS, S - s0);
+        if ((rc = b.par.ensure(per * Sb)) || (rc = b.logLk.ensure((size_t)Sb * K)))
+            return rc;
+        double *dA = b.par.p, *dpi = dA + (size_t)Sb * n * n, *dp0 = dpi + (size_t)Sb * n, *dp1 = dp0 + Sb * np0;
+        BHMM_HIP(hipMemcpyAsync(dA, A + (size_t)s0 * n * n, (size_t)Sb * n * n * sizeof(double),
+                                hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipMemcpyAsync(dpi, pi + (size_t)s0 * n, (size_t)Sb * n * sizeof(double), hipMemcpyHostToDevice,
+                                c->stream));
+        if (np0)
+            BHMM_HIP(hipMemcpyAsync(dp0, par0 + s0 * np0, Sb * np0 * sizeof(double), hipMemcpyHostToDevice,
+                                    c->stream));
+        if (np1)
+            BHMM_HIP(hipMemcpyAsync(dp1, par1 + s0 * np1, Sb * np1 * sizeof(double), hipMemcpyHostToDevice,
+                                    c->stream));
+        const dim3 grid(K, Sb);
+        const void *obs = c->d_obs_rm.p;
+        hipError_t e;
+        if (c->kind == EMIT_GAUSS)
+            e = launch(k_score_serial<EMIT_GAUSS>, grid, dim3(bd), lds, c->stream, n, c->M, K, c->d_offsets.p, obs,
+                       dA, dpi, dp0, dp1, b.logLk.p);
+        else if (c->kind == EMIT_DISC)
+            e = launch(k_score_serial<EMIT_DISC>, grid, dim3(bd), lds, c->stream, n, c->M, K, c->d_offsets.p, obs,
+                       dA, dpi, dp0, nullptr, b.logLk.p);
+        else
+            e = launch(k_score_serial<EMIT_EXPL>, grid, dim3(bd), lds, c->stream, n, c->M, K, c->d_offsets.p, obs,
+                       dA, dpi, nullptr, nullptr, b.logLk.p);
+        BHMM_HIP(e);
+        BHMM_HIP(hipMemcpyAsync(out + (size_t)s0 * K, b.logLk.p, (size_t)Sb * K * sizeof(double),
+                                hipMemcpyDeviceToHost, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream)); // (the parameter buffer is reused by the next batch)
+    }
+    return BHMM_OK;
+}
+
+// N: the kernel's state count (the real one for the lane-per-chunk layout, 2 / 4 / 8 padded for PAIR)
+template <int N, int KIND, bool PAIR>
+struct Fast {
+    // warm-up of every model of the batch from the forgetting curve: the E-step's probe_warmup reading (forward
+    // chains within 1e-13 from then on, + 15 %), doubled -- the E-step lengthens its warm-up after a failed
+    // check and keeps it for the observation set, a score call keeps nothing (1024 x 1e6 steps, slowly mixing
+    // models: the plain reading failed the check for three models of four, twice that passed).  W[s] = 0 where
+    // the trajectories are too short to probe
+    static int probe(bhmm_ctx *c, int Sb, const std::vector<Model<N>> &m, const double *dBt, std::vector<int> &W)
+    {
+        W.assign(Sb, 0);
+        const int64_t maxT = longest_traj(c);
+        const int Wmax = (int)std::min<int64_t>(1024, maxT / 2) / 4 * 4;
+        if (Wmax < 32)
+            return BHMM_OK;
+        std::vector<int> longk;
+        for (int k = 0; k < c->K; ++k)
+            if (c->offsets[k + 1] - c->offsets[k] >= Wmax)
+                longk.push_back(k);
+        const int P = 256;
+        std::vector<int64_t> starts(P);
+        for (int i = 0; i < P; ++i) {
+            const int k = longk[i % longk.size()];
+            const int64_t room = c->offsets[k + 1] - c->offsets[k] - Wmax + 1;
+            const int64_t rep = i / (int64_t)longk.size(), reps = (P + longk.size() - 1) / longk.size();
+            starts[i] = c->offsets[k] + (room - 1) * rep / std::max<int64_t>(reps - 1, 1);
+        }
+        const size_t curve_words = 2 * (size_t)Wmax;
+        const size_t bytes = P * sizeof(int64_t) + (size_t)Sb * curve_words * sizeof(unsigned int);
+        int rc;
+        if ((rc = c->score.probe.ensure(bytes)))
+            return rc;
+        int64_t *d_starts = reinterpret_cast<int64_t *>(c->score.probe.p);
+        unsigned int *d_curve = reinterpret_cast<unsigned int *>(d_starts + P);
+        BHMM_HIP(hipMemcpyAsync(d_starts, starts.data(), P * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipMemsetAsync(d_curve, 0, (size_t)Sb * curve_words * sizeof(unsigned int), c->stream));
+        for (int s = 0; s < Sb; ++s)
+            BHMM_HIP(launch(k_forget_probe<N, KIND>, dim3((2 * P + 63) / 64), dim3(64), 0, c->stream, m[s],
+                            c->d_obs_rm.p, KIND == EMIT_DISC ? dBt + (size_t)s * c->M * N : nullptr, d_starts, P,
+                            Wmax, d_curve + s * curve_words));
+        std::vector<float> curve((size_t)Sb * curve_words);
+        BHMM_HIP(hipMemcpyAsync(curve.data(), d_curve, curve.size() * sizeof(float), hipMemcpyDeviceToHost,
+                                c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+        const float target = (float)(0.01 * SCORE_TOL);
+        for (int s = 0; s < Sb; ++s) {
+            const float *cv = curve.data() + s * curve_words; // forward direction: the first Wmax entries
+            int last = -1;
+            for (int w = 0; w < Wmax; ++w)
+                if (cv[w] >= target)
+                    last = w;
+            int w = (int)std::ceil(1.15 * (last + 2));
+            W[s] = 2 * std::min(std::max(16, (w + 3) / 4 * 4), Wmax);
+        }
+        return BHMM_OK;
+    }
+
+    // one launch sequence for models [0, Sb) of the tables on the device; logLk and the failure counters to the host
+    static int pass(bhmm_ctx *c, int Sb, const Model<N> *dm, const int32_t *dW, const double *dBt, double *logLk_h,
+                    unsigned int *fails_h)
+    {
+        auto &b = c->score;
+        const int K = c->K, G = c->G, Gp = c->Gp;
+        const Chunks ch = chunks_of(c);
+        const size_t lds_bt = (size_t)c->M * score_bt_stride(N) * sizeof(double);
+        const bool bt_lds = KIND == EMIT_DISC && lds_bt <= SCORE_LDS_BT;
+        BHMM_HIP(hipMemsetAsync(b.fails.p, 0, Sb * sizeof(unsigned int), c->stream));
+        const dim3 grid(Gp / 64, Sb);
+        const dim3 block(PAIR ? 32 * N : 64);
+        auto kern = [&]() {
+            if constexpr (PAIR)
+                return bt_lds ? k_score_pair<N, KIND, true> : k_score_pair<N, KIND, false>;
+            else
+                return bt_lds ? k_score_fwd<N, KIND, true> : k_score_fwd<N, KIND, false>;
+        }();
+        BHMM_HIP(launch(kern, grid, block, bt_lds ? lds_bt : 0, c->stream, dm, dW, ch, G, Gp, c->d_obs_ci.p,
+                        c->d_obs_rm.p, dBt, c->M, b.logLc.p, b.aentry.p, b.aexit.p));
+        if (G > 1)
+            BHMM_HIP(launch(k_score_check<N>, dim3((G + 255) / 256, Sb), dim3(256), 0, c->stream, ch, G, Gp, b.logLc.p,
+                            b.aentry.p, b.aexit.p, SCORE_TOL, b.fails.p));
+        BHMM_HIP(launch(k_score_logl, dim3(K, Sb), dim3(64), 0, c->stream, c->d_traj_c0.p, K, Gp, b.logLc.p,
+                        b.logLk.p));
+        BHMM_HIP(hipMemcpyAsync(fails_h, b.fails.p, Sb * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        BHMM_HIP(hipMemcpyAsync(logLk_h, b.logLk.p, (size_t)Sb * K * sizeof(double), hipMemcpyDeviceToHost,
+                                c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+        return BHMM_OK;
+    }
+
+    static int run(bhmm_ctx *c, int S, const double *A, const double *pi, const double *par0, const double *par1,
+                   double *logL)
+    {
+        auto &b = c->score;
+        const int K = c->K, M = c->M, n = c->n;
+        // models per launch: at most SCORE_MAX_MODELS, and boundary vectors of at most 1 GiB
+        const size_t per_model = (size_t)c->Gp * (2 * N + 1) * sizeof(double);
+        const int Sb_max = (int)std::max<size_t>(1, std::min<size_t>(SCORE_MAX_MODELS, ((size_t)1 << 30) / per_model));
+        int rc;
+        if ((rc = b.logLc.ensure((size_t)Sb_max * c->Gp)) || (rc = b.aentry.ensure((size_t)Sb_max * c->Gp * N)) ||
+            (rc = b.aexit.ensure((size_t)Sb_max * c->Gp * N)) || (rc = b.logLk.ensure((size_t)Sb_max * K)) ||
+            (rc = b.fails.ensure(Sb_max)) || (rc = b.W.ensure(Sb_max)) ||
+            (rc = b.models.ensure((size_t)Sb_max * sizeof(Model<N>))) ||
+            (KIND == EMIT_DISC && (rc = b.Bt.ensure((size_t)Sb_max * M * N))))
+            return rc;
+        Model<N> *dm = reinterpret_cast<Model<N> *>(b.models.p);
+        std::vector<unsigned int> fails(Sb_max);
+        for (int s0 = 0; s0 < S; s0 += Sb_max) {
+            const int Sb = std::min(Sb_max, S - s0);
+            std::vector<Model<N>> m(Sb);
+            for (int s = 0; s < Sb; ++s) {
+                const int g = s0 + s;
+                fill_model<N>(m[s], n, KIND, M, A + (size_t)g * n * n, pi + (size_t)g * n,
+                              KIND == EMIT_DISC ? par0 + (size_t)g * n * M : par0 + (size_t)g * n,
+                              KIND == EMIT_GAUSS ? par1 + (size_t)g * n : nullptr);
+            }
+            if (KIND == EMIT_DISC) {
+                std::vector<double> bt((size_t)Sb * M * N, 0.0); // (padded states: zero)
+                for (int s = 0; s < Sb; ++s)
+                    for (int i = 0; i < n; ++i)
+                        for (int o = 0; o < M; ++o)
+                            bt[((size_t)s * M + o) * N + i] = par0[((size_t)(s0 + s) * n + i) * M + o];
+                BHMM_HIP(hipMemcpyAsync(b.Bt.p, bt.data(), bt.size() * sizeof(double), hipMemcpyHostToDevice,
+                                        c->stream));
+                BHMM_HIP(hipStreamSynchronize(c->stream)); // (bt is a temporary)
+            }
+            BHMM_HIP(hipMemcpyAsync(dm, m.data(), Sb * sizeof(Model<N>), hipMemcpyHostToDevice, c->stream));
+            std::vector<int> W(Sb, c->opt.score_W);
+            if (c->opt.score_W <= 0) {
+                if ((rc = probe(c, Sb, m, b.Bt.p, W)))
+                    return rc;
+                for (int &w : W)
+                    w = w > 0 ? w : SCORE_W_UNPROBED;
+            }
+            BHMM_HIP(hipMemcpyAsync(b.W.p, W.data(), Sb * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            double *out = logL + (size_t)s0 * K;
+            if ((rc = pass(c, Sb, dm, b.W.p, b.Bt.p, out, fails.data())))
+                return rc;
+            // boundaries that did not verify: that model alone with twice the warm-up, then the exact path
+            for (int s = 0; s < Sb; ++s) {
+                if (fails[s] == 0)
+                    continue;
+                ++c->last.score_fallbacks;
+                const int W2 = (int)std::min<int64_t>(2 * (int64_t)W[s], 1 << 30);
+                BHMM_HIP(hipMemcpyAsync(b.W.p + s, &W2, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+                unsigned int f2 = 0;
+                if ((rc = pass(c, 1, dm + s, b.W.p + s, KIND == EMIT_DISC ? b.Bt.p + (size_t)s * M * N : nullptr,
+                               out + (size_t)s * K, &f2)))
+                    return rc;
+                if (f2 != 0 && (rc = score_serial(c, 1, A + (size_t)(s0 + s) * n * n, pi + (size_t)(s0 + s) * n,
+                                                  par0 ? par0 + (size_t)(s0 + s) * n * (KIND == EMIT_DISC ? M : 1)
+                                                       : nullptr,
+                                                  KIND == EMIT_GAUSS ? par1 + (size_t)(s0 + s) * n : nullptr,
+                                                  out + (size_t)s * K)))
+                    return rc;
+            }
+        }
+        return BHMM_OK;
+    }
+};
+
+template <int N, bool PAIR>
+int run_n(bhmm_ctx *c, int S, const double *A, const double *pi, const double *par0, const double *par1, double *logL)
+{
+    return c->kind == EMIT_GAUSS ? Fast<N, EMIT_GAUSS, PAIR>::run(c, S, A, pi, par0, par1, logL)
+                                 : Fast<N, EMIT_DISC, PAIR>::run(c, S, A, pi, par0, par1, logL);
+}
+
+} // namespace
+} // namespace bhmm
+
+using namespace bhmm;
+
+extern "C" {
+
+int bhmm_score(bhmm_ctx *c, int nmodels, const double *A, const double *pi, const double *par0, const double *par1,
+               double *logL)
+{
+    int rc = enter_model_call(c, A && pi && logL, "A / pi / logL == NULL", true, par0, par1);
+    if (rc)
+        return rc;
+    if (nmodels < 1)
+        return invalid_arg("bhmm_score: nmodels must be >= 1");
+    if ((rc = check_models(c, nmodels, A, pi, par0, par1)))
+        return rc;
+    const bool fast = !c->wide && !c->gen && c->n <= 8 && (c->kind == EMIT_GAUSS || c->kind == EMIT_DISC) && c->G > 0;
+    if (!fast)
+        return score_serial(c, nmodels, A, pi, par0, par1, logL);
+    if (c->opt.score_layout == 1) // one lane per chunk, the real state count
+        switch (c->n) {
+        case 1:
+            return run_n<1, false>(c, nmodels, A, pi, par0, par1, logL);
+        case 2:
+            return run_n<2, false>(c, nmodels, A, pi, par0, par1, logL);
+        case 3:
+            return run_n<3, false>(c, nmodels, A, pi, par0, par1, logL);
+        case 4:
+            return run_n<4, false>(c, nmodels, A, pi, par0, par1, logL);
+        case 5:
+            return run_n<5, false>(c, nmodels, A, pi, par0, par1, logL);
+        case 6:
+            return run_n<6, false>(c, nmodels, A, pi, par0, par1, logL);
+        case 7:
+            return run_n<7, false>(c, nmodels, A, pi, par0, par1, logL);
+        default:
+            return run_n<8, false>(c, nmodels, A, pi, par0, par1, logL);
+        }
+    switch (c->N) { // N/2 lanes per chunk (P1's layout), padded state count
+    case 2:
+        return run_n<2, true>(c, nmodels, A, pi, par0, par1, logL);
+    case 4:
+        return run_n<4, true>(c, nmodels, A, pi, par0, par1, logL);
+    default:
+        return run_n<8, true>(c, nmodels, A, pi, par0, par1, logL);
+    }
+}
+
+} // extern "C"

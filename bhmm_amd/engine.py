@@ -264,6 +264,20 @@ class Engine(object):
         _lib.check(self._L.bhmm_get_gamma(self._h, int(k), _lib.dp(g)))
         return g
 
+    # -- scoring -------------------------------------------------------------------------
+    def score(self, models):
+        """Log-likelihood of every loaded trajectory under each model (bhmm_score): `models` is a
+        list of (A, pi, par0, par1) tuples as for estep.  Returns an (S, K) array; a trajectory of
+        probability zero under a model scores -inf there.  Forward pass only; leaves the state that
+        later E-steps, Viterbi and sampling calls use untouched."""
+        if self.kind is None:
+            raise ValueError("no observations loaded")
+        A, pi, p0, p1 = stack_models(self.kind, self.nstates, self.nsymbols, models)
+        logL = np.empty((len(models), len(self.lengths)))
+        _lib.check(self._L.bhmm_score(self._h, len(models), _lib.dp(A), _lib.dp(pi), _lib.dp(p0), _lib.dp(p1),
+                                      _lib.dp(logL)))
+        return logL
+
     # -- paths ---------------------------------------------------------------------------
     def viterbi(self, A, pi, par0=None, par1=None):
         A, pi, p0, p1 = self._model_ptrs(A, pi, par0, par1)
@@ -360,6 +374,43 @@ class Engine(object):
         if want_paths:
             plist = [paths[self.offsets[k]:self.offsets[k + 1]] for k in range(len(self.lengths))]
         return plist, C, n0, emis
+
+
+def stack_models(kind, nstates, nsymbols, models):
+    """The stacked model arrays of bhmm_score (include/bhmm_amd.h): A (S, n, n), pi (S, n), par0 (S, n) means /
+    (S, n, M) emission matrices / None, par1 (S, n) sigmas / None, each C-contiguous float64."""
+    models = list(models)
+    if not models:
+        raise ValueError("score needs at least one model")
+    n, M = int(nstates), int(nsymbols)
+    A, pi, p0, p1 = [], [], [], []
+    for i, m in enumerate(models):
+        if len(m) != 4:
+            raise ValueError("model %d: expected an (A, pi, par0, par1) tuple" % i)
+        a, p, e0, e1 = m
+        a = np.asarray(a, dtype=np.float64)
+        p = np.asarray(p, dtype=np.float64)
+        if a.shape != (n, n) or p.shape != (n,):
+            raise ValueError("model %d: A must be (%d, %d) and pi (%d,)" % (i, n, n, n))
+        A.append(a)
+        pi.append(p)
+        if kind == 'gaussian':
+            if e0 is None or e1 is None:
+                raise ValueError("model %d: gaussian emissions need means and sigmas" % i)
+            e0, e1 = np.asarray(e0, dtype=np.float64), np.asarray(e1, dtype=np.float64)
+            if e0.shape != (n,) or e1.shape != (n,):
+                raise ValueError("model %d: means and sigmas must be (%d,)" % (i, n))
+            p0.append(e0)
+            p1.append(e1)
+        elif kind == 'discrete':
+            if e0 is None:
+                raise ValueError("model %d: discrete emissions need B" % i)
+            e0 = np.asarray(e0, dtype=np.float64)
+            if e0.shape != (n, M):
+                raise ValueError("model %d: B must be (%d, %d)" % (i, n, M))
+            p0.append(e0)
+    st = lambda xs: np.ascontiguousarray(np.stack(xs)) if xs else None  # noqa: E731
+    return st(A), st(pi), st(p0), st(p1)
 
 
 class NativeComm(object):

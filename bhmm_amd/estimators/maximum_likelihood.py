@@ -69,6 +69,14 @@ def _load_observations(engine, kind, given, copied, mine, comm, nstates, nsymbol
         engine.set_observations(kind, [copied[k] for k in mine], nstates, nsymbols=nsymbols)
 
 
+def model_tuple(m):
+    """(A, pi, par0, par1) of an HMM (or a tuple passed through) -- the model form of Engine.score."""
+    if isinstance(m, tuple):
+        return m
+    par0, par1 = m.output_model.parameters()
+    return (m.transition_matrix, m.initial_distribution, par0, par1)
+
+
 def packed_stats_size(kind, n, M):
     """Length of the packed E-step statistics vector (include/bhmm_amd.h, bhmm_ctx_stats_size)."""
     return 1 + n + n * n + n + (2 * n if kind == 'gaussian' else (n * M if kind == 'discrete' else 0))
@@ -362,6 +370,28 @@ class MaximumLikelihoodEstimator(object):
             for k, pth in zip(self._mine, local):
                 paths[k] = pth
         return paths
+
+    def score(self, models=None):
+        """Total log-likelihood of the estimator's observations under each model (forward pass
+        only, Engine.score): `models` is one HMM, a list of HMMs or (A, pi, par0, par1) tuples, or
+        a SampledHMM (its sampled models); None scores the current hmm.  Returns an array of one total per model.  With a
+        process_group every rank scores its own trajectories and the totals are all-reduced once.
+        Leaves the state of the EM iterations untouched."""
+        from ..hmm import SampledHMM
+        if models is None:
+            models = [self._hmm]
+        elif isinstance(models, SampledHMM):        # its sampled models, as bhmm_amd.score
+            models = models.sampled_hmms
+        elif hasattr(models, 'transition_matrix'):
+            models = [models]
+        tuples = [model_tuple(m) for m in models]
+        if not tuples:
+            raise ValueError("score needs at least one model")
+        if self._mine:
+            totals = np.ascontiguousarray(self._engine.score(tuples).sum(axis=1))
+        else:
+            totals = np.zeros(len(tuples))
+        return self._comm.allreduce_sum_numpy(totals)
 
     def _select_start(self, ntrial=20):
         """Multi-start: run `ntrial` EM iterations from every candidate initial model (only when

@@ -159,6 +159,17 @@ int bhmm_estep_fetch(bhmm_ctx *ctx, double *stats, double *logL_k);
  * row-major, to the host. */
 int bhmm_get_gamma(bhmm_ctx *ctx, int k, double *gamma);
 
+/* log-likelihood of every loaded trajectory under each of nmodels models, stacked:
+   A[nmodels*N*N], pi[nmodels*N], par0/par1 as bhmm_estep per model (gaussian: mu, sigma [N];
+   discrete: B [N*M], par1 NULL).  logL[nmodels*K] (host, row s = model s).
+   Leaves every carried state of the context untouched.  A trajectory of probability zero under a
+   model scores -inf there; a non-finite or non-stochastic model entry is BHMM_ERR_INVALID.
+   Forward pass only, no statistics; synchronous.  Up to 8 states (gaussian, discrete): chunk-parallel
+   with verified warm-up boundaries (options score_W, score_fallbacks); otherwise (more states,
+   explicit pobs) the exact serial recursion, one workgroup per trajectory and model. */
+int bhmm_score(bhmm_ctx *ctx, int nmodels, const double *A, const double *pi,
+               const double *par0, const double *par1, double *logL);
+
 /* Viterbi paths of all trajectories (maximum_likelihood.py:332-352).  paths is a host
  * buffer of sum_k T_k int32, trajectory-concatenated like obs. */
 int bhmm_viterbi_batch(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0,
