@@ -139,6 +139,19 @@ inline void plan_segments(const std::vector<int64_t> &offsets, int K, int64_t se
     s.traj0[K] = (int32_t)s.traj.size();
 }
 
+// Segment length of the scoring plan for 9..64 states (score_api.hip: plan_segments with it, mult 1).  A
+// function of the observation set's size, the lane-group width np (16, 32, 64) and the device only: a score
+// must not depend on what earlier calls found out.  asked > 0: the caller's length (option score_seglen).
+// Automatic: two wavefronts per SIMD for ONE model (the kernel's registers allow two at np = 64; more models
+// bring their own wavefronts), but at least 2048 steps, against which a warm-up of a few hundred is small.
+inline int64_t score_seglen(int64_t total, int np, int num_simd, int64_t asked)
+{
+    if (asked > 0)
+        return (asked + 3) & ~(int64_t)3;
+    const int64_t want = 2 * (int64_t)num_simd * (64 / np);
+    return (std::max<int64_t>((total + want - 1) / want, 2048) + 3) & ~(int64_t)3;
+}
+
 // Tiles of the row-batched kernels (tile_kernels.hpp): 16 segments per workgroup, which runs as long
 // as its longest row and takes its fast paths where all 16 rows are in the same phase -- so segments
 // without a warm-up in the direction of the pass (backward = false: those that start a trajectory;

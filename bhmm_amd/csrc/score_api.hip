@@ -6,11 +6,19 @@
 // warm-up of its own (the forgetting probe of the E-step, k_forget_probe, or the option score_W), so
 // its result does not depend on the other models of the call.  A model whose boundaries do not verify
 // runs again alone with twice the warm-up; if they fail again it takes the exact serial recursion
-// (k_score_serial).  More than 8 states and explicit pobs always take the exact path.
+// (k_score_serial).
 //
-// Nothing here reads or writes the E-step's state (ds.*, carried vectors, warm-up lengths, d_Bt, the
-// timing events, the pinned landing zones): the buffers are c->score.*, the only other fields touched
-// are opt.score_W (read) and last.score_fallbacks.
+// 9 to 64 states, gaussian or discrete: k_score_wide (score_wide_kernels.hpp) over a segment plan that belongs
+// to scoring alone (score_plan: a function of the offsets, the state count and the device; option
+// score_seglen), all models of a batch in one launch, then k_score_wide_check and k_score_logl.  W per model
+// from k_wide_probe (or score_W); the same protocol: a failed model runs again alone with twice the warm-up,
+// on the kernel that sums every step, then takes the exact serial recursion.
+//
+// Explicit pobs, more than 64 states and a context on the any-N family always take the exact path.
+//
+// Nothing here reads or writes the E-step's state (ds.* but the score plan's own fields, carried vectors,
+// warm-up lengths, d_Bt, the E-step's segment plans, the timing events, the pinned landing zones): the
+// buffers are c->score.*, the only other fields touched are opt.score_* (read) and last.score_*.
 #include <math.h>
 #include <string.h>
 
@@ -22,7 +30,9 @@
 #include "host_common.hpp"
 #include "host_internal.hpp"
 #include "launch.hpp"
+#include "plan.hpp"
 #include "score_kernels.hpp"
+#include "score_wide_kernels.hpp"
 
 namespace bhmm {
 
@@ -32,6 +42,7 @@ constexpr double SCORE_TOL = 1e-11;         // boundary check: componentwise rel
 constexpr int SCORE_W_UNPROBED = 288;       // warm-up when the trajectories are too short to probe (the E-step's)
 constexpr size_t SCORE_LDS_BT = 16 * 1024;  // B^T of a model staged in LDS up to this size
 constexpr double SCORE_STOCH_TOL = 1e-8;    // rows of A, pi and B must sum to 1 within this
+constexpr double SCORE_WIDE_MARGIN = 1.5;   // 9..64 states: warm-up over the probe's reading (wide_probe_run's factor)
 
 int check_prob_rows(const double *p, int rows, int cols, int s, const char *what)
 {
@@ -292,6 +303,231 @@ int run_n(bhmm_ctx *c, int S, const double *A, const double *pi, const double *p
                                  : Fast<N, EMIT_DISC, PAIR>::run(c, S, A, pi, par0, par1, logL);
 }
 
+// ---- 9..64 states ------------------------------------------------------------------------------
+
+// the segment plan of scoring on this observation set: made once (and again when score_seglen changes),
+// never after a check
+int score_plan(bhmm_ctx *c)
+{
+    auto &d = c->ds;
+    auto &b = c->score;
+    if (d.score_nseg > 0 && d.score_seglen_opt == c->opt.score_seglen)
+        return BHMM_OK;
+    plan::SegPlan sp; // (plan.hpp: pure host code)
+    plan::plan_segments(c->offsets, c->K, plan::score_seglen(c->total, c->N, c->num_simd, c->opt.score_seglen), 1,
+                        sp);
+    const size_t ns = sp.traj.size();
+    int rc;
+    if ((rc = b.seg_traj.ensure(ns)) || (rc = b.seg_len.ensure(ns)) || (rc = b.seg_t0.ensure(ns)) ||
+        (rc = b.seg_traj0.ensure(c->K + 1)))
+        return rc;
+    BHMM_HIP(hipMemcpyAsync(b.seg_traj.p, sp.traj.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.seg_len.p, sp.len.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.seg_t0.p, sp.t0.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.seg_traj0.p, sp.traj0.data(), (c->K + 1) * sizeof(int32_t), hipMemcpyHostToDevice,
+                            c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream)); // (sp is a temporary)
+    d.score_nseg = (int)ns;
+    d.score_ntraj = 0;
+    for (int k = 0; k < c->K; ++k)
+        d.score_ntraj += c->offsets[k + 1] > c->offsets[k];
+    d.score_seglen_opt = c->opt.score_seglen;
+    return BHMM_OK;
+}
+
+template <int NP, int KIND>
+struct Wide {
+    static constexpr int GP = 64 / NP;
+
+    // warm-up of every model of the batch: k_wide_probe once per model (its forward chains only: the first
+    // P / GP workgroups), read like wide_probe_run -- chains within 1e-13 from then on, times 1.5
+    static int probe(bhmm_ctx *c, int Sb, const std::vector<ScoreWideModel> &m, std::vector<int> &W)
+    {
+        W.assign(Sb, SCORE_W_UNPROBED);
+        const int Wmax = (int)std::min<int64_t>(8192, longest_traj(c) / 2) / 8 * 8;
+        if (Wmax < 64)
+            return BHMM_OK; // (trajectories of fewer than 128 steps)
+        std::vector<int> longk;
+        for (int k = 0; k < c->K; ++k)
+            if (c->offsets[k + 1] - c->offsets[k] >= Wmax)
+                longk.push_back(k);
+        const int P = 256;
+        std::vector<int64_t> starts(P);
+        for (int i = 0; i < P; ++i) {
+            const int k = longk[i % longk.size()];
+            const int64_t room = c->offsets[k + 1] - c->offsets[k] - Wmax + 1;
+            const int64_t rep = i / (int64_t)longk.size(), reps = (P + longk.size() - 1) / longk.size();
+            starts[i] = c->offsets[k] + (room - 1) * rep / std::max<int64_t>(reps - 1, 1);
+        }
+        const size_t curve_words = 2 * (size_t)Wmax; // (the kernel's layout: forward | backward, the latter stays zero)
+        int rc;
+        if ((rc = c->score.probe.ensure(P * sizeof(int64_t) + (size_t)Sb * curve_words * sizeof(unsigned int))))
+            return rc;
+        int64_t *d_starts = reinterpret_cast<int64_t *>(c->score.probe.p);
+        unsigned int *d_curve = reinterpret_cast<unsigned int *>(d_starts + P);
+        BHMM_HIP(hipMemcpyAsync(d_starts, starts.data(), P * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipMemsetAsync(d_curve, 0, (size_t)Sb * curve_words * sizeof(unsigned int), c->stream));
+        for (int s = 0; s < Sb; ++s)
+            BHMM_HIP(launch(k_wide_probe<NP, KIND>, dim3(P / GP), dim3(64), 0, c->stream, m[s].w, c->d_obs_rm.p,
+                            d_starts, P, Wmax, d_curve + s * curve_words));
+        std::vector<float> curve((size_t)Sb * curve_words);
+        BHMM_HIP(hipMemcpyAsync(curve.data(), d_curve, curve.size() * sizeof(float), hipMemcpyDeviceToHost,
+                                c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+        for (int s = 0; s < Sb; ++s) {
+            const float *cv = curve.data() + s * curve_words;
+            int last = -1;
+            for (int w = 0; w < Wmax; ++w)
+                if (cv[w] >= 1e-13f)
+                    last = w;
+            const int w = (int)std::ceil(SCORE_WIDE_MARGIN * (last + 2));
+            W[s] = std::min(std::max(16, (w + 7) / 8 * 8), Wmax); // (not forgotten within Wmax: Wmax, the check decides)
+        }
+        return BHMM_OK;
+    }
+
+    // one launch sequence for models [0, Sb) of the tables on the device
+    static int pass(bhmm_ctx *c, int Sb, const ScoreWideModel *dm, const int32_t *dW, bool lazy, double *logLk_h,
+                    unsigned int *fails_h)
+    {
+        auto &b = c->score;
+        const int K = c->K, nseg = c->ds.score_nseg;
+        Segs sg;
+        sg.traj = b.seg_traj.p;
+        sg.t0 = b.seg_t0.p;
+        sg.len = b.seg_len.p;
+        sg.nseg = nseg;
+        sg.W = 0; // (per model: dW)
+        const size_t lds_bt = (size_t)c->M * NP * sizeof(double);
+        const bool bt_lds = KIND == EMIT_DISC && lds_bt <= SCORE_LDS_BT;
+        BHMM_HIP(hipMemsetAsync(b.fails.p, 0, Sb * sizeof(unsigned int), c->stream));
+        constexpr bool D = KIND == EMIT_DISC; // (gaussian: one instantiation per scaling)
+        auto *kern = lazy ? (bt_lds ? k_score_wide<NP, KIND, true, D> : k_score_wide<NP, KIND, true, false>)
+                          : (bt_lds ? k_score_wide<NP, KIND, false, D> : k_score_wide<NP, KIND, false, false>);
+        BHMM_HIP(launch(kern, dim3((nseg + GP - 1) / GP, Sb), dim3(64), bt_lds ? lds_bt : 0, c->stream, dm, dW,
+                        c->d_offsets.p, sg, c->d_obs_rm.p, b.logLc.p, b.aentry.p, b.aexit.p, b.fails.p));
+        if (nseg > c->ds.score_ntraj)
+            BHMM_HIP(launch(k_score_wide_check, dim3((nseg + 15) / 16, Sb), dim3(256), 0, c->stream, sg, c->n,
+                            b.logLc.p, b.aentry.p, b.aexit.p, SCORE_TOL, b.fails.p));
+        BHMM_HIP(launch(k_score_logl, dim3(K, Sb), dim3(64), 0, c->stream, b.seg_traj0.p, K, nseg, b.logLc.p,
+                        b.logLk.p));
+        BHMM_HIP(hipMemcpyAsync(fails_h, b.fails.p, Sb * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        BHMM_HIP(hipMemcpyAsync(logLk_h, b.logLk.p, (size_t)Sb * K * sizeof(double), hipMemcpyDeviceToHost,
+                                c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+        return BHMM_OK;
+    }
+
+    static int run(bhmm_ctx *c, int S, const double *A, const double *pi, const double *par0, const double *par1,
+                   double *logL)
+    {
+        auto &b = c->score;
+        const int K = c->K, M = c->M, n = c->n;
+        int rc;
+        if ((rc = score_plan(c)))
+            return rc;
+        const int nseg = c->last.score_segments = c->ds.score_nseg;
+        // models per launch: at most SCORE_MAX_MODELS, and boundary vectors of at most 1 GiB
+        const size_t per_model = (size_t)nseg * (2 * n + 1) * sizeof(double);
+        const int Sb_max = (int)std::max<size_t>(1, std::min<size_t>(SCORE_MAX_MODELS, ((size_t)1 << 30) / per_model));
+        // parameter block of a model: wide_model's layout, then B and B^T
+        const size_t nB = KIND == EMIT_DISC ? (size_t)n * M : 0, np = (size_t)n * n + 7 * n + 2 * nB;
+        if ((rc = b.logLc.ensure((size_t)Sb_max * nseg)) || (rc = b.aentry.ensure((size_t)Sb_max * nseg * n)) ||
+            (rc = b.aexit.ensure((size_t)Sb_max * nseg * n)) || (rc = b.logLk.ensure((size_t)Sb_max * K)) ||
+            (rc = b.fails.ensure(Sb_max)) || (rc = b.W.ensure(Sb_max)) ||
+            (rc = b.models.ensure((size_t)Sb_max * sizeof(ScoreWideModel))) || (rc = b.wpar.ensure(Sb_max * np)))
+            return rc;
+        ScoreWideModel *dm = reinterpret_cast<ScoreWideModel *>(b.models.p);
+        std::vector<unsigned int> fails(Sb_max);
+        for (int s0 = 0; s0 < S; s0 += Sb_max) {
+            const int Sb = std::min(Sb_max, S - s0);
+            std::vector<double> h(Sb * np, 0.0);
+            std::vector<ScoreWideModel> m(Sb);
+            for (int s = 0; s < Sb; ++s) {
+                const int g = s0 + s;
+                double *hp = h.data() + s * np;
+                const double *dp = b.wpar.p + s * np;
+                memcpy(hp, A + (size_t)g * n * n, sizeof(double) * n * n);
+                memcpy(hp + (size_t)n * n, pi + (size_t)g * n, sizeof(double) * n);
+                WideModel &w = m[s].w;
+                w.A = dp;
+                w.pi = dp + (size_t)n * n;
+                w.mu = w.pi + n;
+                w.isig = w.mu + n;
+                w.cnorm = w.isig + n;
+                w.sigma = w.cnorm + n;
+                w.ga = w.sigma + n;
+                w.gb = w.ga + n;
+                w.gmg = 0.0;
+                w.B = nullptr;
+                w.n = n;
+                w.M = M;
+                m[s].Bt = nullptr;
+                double *q = hp + (size_t)n * n + n;
+                if (KIND == EMIT_GAUSS) {
+                    const double *mu = par0 + (size_t)g * n, *sg = par1 + (size_t)g * n;
+                    for (int i = 0; i < n; ++i) {
+                        q[i] = mu[i];
+                        q[n + i] = 1.0 / sg[i];
+                        q[2 * n + i] = 1.0 / (sqrt(2.0 * M_PI) * sg[i]);
+                        q[3 * n + i] = sg[i];
+                    }
+                    gauss_pdf_constants(n, n, sg, q + 4 * n, q + 5 * n, &w.gmg);
+                } else {
+                    const double *B = par0 + (size_t)g * nB;
+                    double *hB = q + 6 * n, *hBt = hB + nB;
+                    memcpy(hB, B, sizeof(double) * nB);
+                    for (int i = 0; i < n; ++i)
+                        for (int o = 0; o < M; ++o)
+                            hBt[(size_t)o * n + i] = B[(size_t)i * M + o];
+                    w.B = w.gb + n;
+                    m[s].Bt = w.B + nB;
+                }
+            }
+            BHMM_HIP(hipMemcpyAsync(b.wpar.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            BHMM_HIP(hipMemcpyAsync(dm, m.data(), Sb * sizeof(ScoreWideModel), hipMemcpyHostToDevice, c->stream));
+            BHMM_HIP(hipStreamSynchronize(c->stream)); // (h and m are temporaries; the probe takes m by value)
+            // W: multiples of four (the lazy refresh); no boundary at all, no warm-up to measure
+            std::vector<int> W(Sb, (c->opt.score_W + 3) & ~3);
+            if (c->opt.score_W <= 0 && nseg > c->ds.score_ntraj && (rc = probe(c, Sb, m, W)))
+                return rc;
+            if (nseg > c->ds.score_ntraj)
+                c->last.score_W_max = std::max(c->last.score_W_max, *std::max_element(W.begin(), W.end()));
+            BHMM_HIP(hipMemcpyAsync(b.W.p, W.data(), Sb * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            double *out = logL + (size_t)s0 * K;
+            if ((rc = pass(c, Sb, dm, b.W.p, c->opt.score_lazy, out, fails.data())))
+                return rc;
+            // boundaries that did not verify, a vector outside the lazy kernel's range: that model alone with twice
+            // the warm-up on the kernel that sums every step, then the exact path
+            for (int s = 0; s < Sb; ++s) {
+                if (fails[s] == 0)
+                    continue;
+                ++c->last.score_fallbacks;
+                const int W2 = (int)std::min<int64_t>(2 * (int64_t)W[s], 1 << 30);
+                BHMM_HIP(hipMemcpyAsync(b.W.p + s, &W2, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+                unsigned int f2 = 0;
+                if ((rc = pass(c, 1, dm + s, b.W.p + s, false, out + (size_t)s * K, &f2)))
+                    return rc;
+                const int g = s0 + s;
+                if (f2 != 0 && (rc = score_serial(c, 1, A + (size_t)g * n * n, pi + (size_t)g * n,
+                                                  par0 + (size_t)g * (KIND == EMIT_DISC ? nB : (size_t)n),
+                                                  KIND == EMIT_GAUSS ? par1 + (size_t)g * n : nullptr,
+                                                  out + (size_t)s * K)))
+                    return rc;
+            }
+        }
+        return BHMM_OK;
+    }
+};
+
+template <int NP>
+int run_wide(bhmm_ctx *c, int S, const double *A, const double *pi, const double *par0, const double *par1,
+             double *logL)
+{
+    return c->kind == EMIT_GAUSS ? Wide<NP, EMIT_GAUSS>::run(c, S, A, pi, par0, par1, logL)
+                                 : Wide<NP, EMIT_DISC>::run(c, S, A, pi, par0, par1, logL);
+}
+
 } // namespace
 } // namespace bhmm
 
@@ -309,7 +545,14 @@ int bhmm_score(bhmm_ctx *c, int nmodels, const double *A, const double *pi, cons
         return invalid_arg("bhmm_score: nmodels must be >= 1");
     if ((rc = check_models(c, nmodels, A, pi, par0, par1)))
         return rc;
-    const bool fast = !c->wide && !c->gen && c->n <= 8 && (c->kind == EMIT_GAUSS || c->kind == EMIT_DISC) && c->G > 0;
+    const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
+    const bool fast = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;
+    c->last.score_path = fast ? 1 : (c->wide && emis ? 2 : 0);
+    c->last.score_segments = c->last.score_W_max = 0;
+    if (c->last.score_path == 2) // 9..64 states: lanes per segment in c->N
+        return c->N == 16   ? run_wide<16>(c, nmodels, A, pi, par0, par1, logL)
+               : c->N == 32 ? run_wide<32>(c, nmodels, A, pi, par0, par1, logL)
+                            : run_wide<64>(c, nmodels, A, pi, par0, par1, logL);
     if (!fast)
         return score_serial(c, nmodels, A, pi, par0, par1, logL);
     if (c->opt.score_layout == 1) // one lane per chunk, the real state count

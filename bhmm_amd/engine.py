@@ -269,7 +269,10 @@ class Engine(object):
         """Log-likelihood of every loaded trajectory under each model (bhmm_score): `models` is a
         list of (A, pi, par0, par1) tuples as for estep.  Returns an (S, K) array; a trajectory of
         probability zero under a model scores -inf there.  Forward pass only; leaves the state that
-        later E-steps, Viterbi and sampling calls use untouched."""
+        later E-steps, Viterbi and sampling calls use untouched.  Gaussian and discrete models run parallel
+        over time: up to 8 states over the chunk plan, 9 to 64 states over a segment plan of its own (option
+        score_seglen; get_option("score_path") is 2 there, "score_segments" the plan's size); more than 64
+        states and explicit pobs take the exact serial recursion (score_path 0)."""
         if self.kind is None:
             raise ValueError("no observations loaded")
         A, pi, p0, p1 = stack_models(self.kind, self.nstates, self.nsymbols, models)

@@ -165,8 +165,11 @@ int bhmm_get_gamma(bhmm_ctx *ctx, int k, double *gamma);
    Leaves every carried state of the context untouched.  A trajectory of probability zero under a
    model scores -inf there; a non-finite or non-stochastic model entry is BHMM_ERR_INVALID.
    Forward pass only, no statistics; synchronous.  Up to 8 states (gaussian, discrete): chunk-parallel
-   with verified warm-up boundaries (options score_W, score_fallbacks); otherwise (more states,
-   explicit pobs) the exact serial recursion, one workgroup per trajectory and model. */
+   with verified warm-up boundaries (options score_W, score_layout, score_fallbacks).  9 to 64 states
+   (gaussian, discrete): parallel over time segments of a plan of its own, same verification and fallbacks
+   (options score_seglen: segment length, 0 = automatic; score_lazy; read-only score_segments, score_W_max
+   and score_path: 0 serial, 1 chunk kernels, 2 segment kernel).  Otherwise (more than 64 states, explicit
+   pobs) the exact serial recursion, one workgroup per trajectory and model. */
 int bhmm_score(bhmm_ctx *ctx, int nmodels, const double *A, const double *pi,
                const double *par0, const double *par1, double *logL);
 

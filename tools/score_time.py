@@ -3,9 +3,11 @@
 
 For configs[2] (8-state discrete, M = 64, 1024 x 1e6) and configs[1] (8-state gaussian, 256 x 1e5):
 one Engine.score call with S = 1, 8 and 64 models for each kernel layout (option score_layout), and the same
-S models as S E-steps.  Prints one JSON
-object per measurement.  Options: --only c2|c1 (one config), --reps R, --score-only (S = 1 and 8 score
-calls alone: the workload of a rocprofv3 pass)."""
+S models as S E-steps.  For the 9..64-state setups -- configs[3] (64-state gaussian, 128 x 1e5: the model,
+observations and seed of bench.py's configs[3] block) and a 16- and a 32-state gaussian setup of the same size -- the
+same per scaling of the segmented kernel (option score_lazy; on a library without the option: as it is).  Prints one
+JSON object per measurement, with the minimum and maximum over the repetitions.  Options: --only c2|c1|c3|g16|g32
+(one config), --reps R, --label TEXT (a "build" field in every line: which library was timed), --score-only (S = 1 and 8 score calls alone: the workload of a rocprofv3 pass)."""
 import argparse
 import json
 import os
@@ -29,6 +31,87 @@ def timed(fn, reps):
         fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / reps
+
+
+def timed_all(fn, reps):
+    """ms of each of `reps` calls after one warm-up call"""
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append(1e3 * (time.perf_counter() - t0))
+    return out
+
+
+def wide_setup(n, seed, name):
+    """bench.py's configs[3] block at n states: 128 x 1e5 gaussian, 64 candidate models around the generating one"""
+    rng = np.random.default_rng(seed)
+    K, T = 128, 100000
+    A = metastable_matrix(n, rng)
+    pi = stationary(A)
+    mu, sig = np.linspace(-5, 5, n), np.linspace(0.5, 2.0, n)
+    obs = torch.empty(K * T, dtype=torch.float64, device="cuda:0")
+    synth_observations("gaussian", obs.data_ptr(), A, pi, mu, sig, K, T, seed=100 * seed)
+    torch.cuda.synchronize()
+    eng = Engine(0)
+    eng.set_observations_device("gaussian", obs.data_ptr(), np.arange(K + 1, dtype=np.int64) * T, n)
+    models = []
+    for s in range(64):
+        w = 0.85 + 0.1 * s / 63
+        models.append((w * A + (1 - w) / n, pi, mu + 0.2 * ((s * 37) % 64) / 63, sig))
+    return name, eng, models, obs, K * T
+
+
+def c3_setup():
+    return wide_setup(64, 64, "configs[3] 64-state gaussian 128 x 1e5")
+
+
+def g16_setup():
+    return wide_setup(16, 16, "16-state gaussian 128 x 1e5")
+
+
+def g32_setup():
+    return wide_setup(32, 32, "32-state gaussian 128 x 1e5")
+
+
+def opt(eng, name):
+    try:
+        return eng.get_option(name)
+    except ValueError:
+        return None
+
+
+def wide_main(args, setup):
+    name, eng, models, obs, steps = setup()
+    lazies = [int(x) for x in args.lazy.split(",")] if opt(eng, "score_lazy") is not None else [None]
+    if args.score_only:
+        for S in (1, 8):
+            eng.score(models[:S])
+        torch.cuda.synchronize()
+        eng.close()
+        return
+    for S in (1, 8, 64):
+        ms = models[:S]
+        reps = args.reps if S < 64 else max(2, args.reps // 2)
+        te = timed_all(lambda: [eng.estep(*m) for m in ms], args.reps if S < 64 else 1)
+        for lazy in lazies:
+            if lazy is not None:
+                eng.set_option("score_lazy", lazy)
+            ts = timed_all(lambda: eng.score(ms), reps)
+            print(json.dumps(dict(build=args.label, config=name, lazy=lazy, S=S, reps=reps, score_ms_per_model=np.mean(ts) / S,
+                                  score_ms_per_model_min=min(ts) / S, score_ms_per_model_max=max(ts) / S,
+                                  estep_ms_per_model=np.mean(te) / S, estep_ms_per_model_min=min(te) / S,
+                                  estep_ms_per_model_max=max(te) / S,
+                                  timesteps_models_per_s=steps * S / (1e-3 * np.mean(ts)),
+                                  score_path=opt(eng, "score_path"), score_segments=opt(eng, "score_segments"),
+                                  score_W_max=opt(eng, "score_W_max"),
+                                  score_fallbacks=opt(eng, "score_fallbacks"))), flush=True)
+    eng.close()
+    del obs
+    torch.cuda.empty_cache()
 
 
 def c2_setup():
@@ -67,11 +150,17 @@ def c1_setup():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=["c2", "c1"])
+    ap.add_argument("--only", choices=["c2", "c1", "c3", "g16", "g32"])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--score-only", action="store_true")
     ap.add_argument("--layouts", default="1,2", help="score_layout values to time (1: lane per chunk, 2: N/2 lanes)")
+    ap.add_argument("--label", default=None, help="written as \"build\" into every line (e.g. the commit timed)")
+    ap.add_argument("--lazy", default="1,0", help="score_lazy values to time at 9..64 states (1: refresh every "
+                                                   "fourth step, 0: sum every step)")
     args = ap.parse_args()
+    for key, setup in (("c3", c3_setup), ("g16", g16_setup), ("g32", g32_setup)):
+        if not args.only or key == args.only:
+            wide_main(args, setup)
     for key, setup in (("c2", c2_setup), ("c1", c1_setup)):
         if args.only and key != args.only:
             continue
@@ -87,7 +176,7 @@ def main():
         # the E-step of the first model, as the reference point (kernel intervals: prescan, stitch, sweep, ...)
         t_e1 = timed(lambda: eng.estep(*models[0]), args.reps)
         kms = eng.kernel_ms_all().tolist()
-        print(json.dumps(dict(config=name, what="E-step, one model", ms=1e3 * t_e1, kernel_ms=kms,
+        print(json.dumps(dict(build=args.label, config=name, what="E-step, one model", ms=1e3 * t_e1, kernel_ms=kms,
                               spec_W=eng.get_option("spec_W"))), flush=True)
         layouts = [int(x) for x in args.layouts.split(",")]
         for S in (1, 8, 64):
@@ -96,7 +185,7 @@ def main():
             for layout in layouts:
                 eng.set_option("score_layout", layout)
                 t_s = timed(lambda: eng.score(ms), args.reps)
-                print(json.dumps(dict(config=name, layout=layout, S=S, score_ms=1e3 * t_s,
+                print(json.dumps(dict(build=args.label, config=name, layout=layout, S=S, score_ms=1e3 * t_s,
                                       score_ms_per_model=1e3 * t_s / S, estep_ms=1e3 * t_e,
                                       estep_ms_per_model=1e3 * t_e / S, score_over_estep=t_s / t_e,
                                       timesteps_models_per_s=steps * S / t_s,
