@@ -129,8 +129,9 @@ def score(observations, models, lag=1, per_trajectory=False, **engine_kwargs):
     output type and number of states, or a SampledHMM (its sampled models).  lag > 1 scores the lagged
     views (lag_observations).  Returns one total per model (an array of shape (S,)), or with
     per_trajectory the (S, K) array of per-trajectory log-likelihoods.  A trajectory of probability zero
-    under a model scores -inf.  Gaussian and discrete models of up to 64 states run parallel over time (verified
-    against the serial recursion, which more states take).  engine_kwargs: device (default 0)."""
+    under a model scores -inf.  Gaussian and discrete models of up to 128 states run parallel over time
+    (verified against the serial recursion, which more states take; Engine.get_option("score_path") is 3 for 65 to
+    128 states).  engine_kwargs: device (default 0)."""
     from .engine import Engine
     from .estimators.maximum_likelihood import model_tuple
     if isinstance(models, SampledHMM):

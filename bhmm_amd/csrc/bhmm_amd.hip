@@ -1528,7 +1528,7 @@ int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
         if (value != 1.0 && value != 2.0)
             return invalid_arg("score_layout must be 1 or 2");
         c->opt.score_layout = (int)value;
-    } else if (n == "score_seglen") { // bhmm_score, 9..64 states: segment length of its plan from the next call on (0: automatic)
+    } else if (n == "score_seglen") { // bhmm_score, 9..128 states: segment length of its plan from the next call on (0: automatic)
         if (!(value >= 0 && value <= (1 << 30)))
             return invalid_arg("score_seglen outside [0, 2^30]");
         c->opt.score_seglen = ((int)value + 3) & ~3;
@@ -1647,9 +1647,9 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->opt.score_lazy ? 1.0 : 0.0;
     else if (n == "score_segments") // ... segments of the score plan the last call ran on (0: the serial kernel, N <= 8)
         *value = c->last.score_segments;
-    else if (n == "score_W_max") // ... longest warm-up of its first pass at 9..64 states (0: no boundary, other paths)
+    else if (n == "score_W_max") // ... longest warm-up of its first pass at 9..128 states (0: no boundary, other paths)
         *value = c->last.score_W_max;
-    else if (n == "score_path") // ... first pass of the last call: 0 serial kernel, 1 chunk kernels (N <= 8), 2 k_score_wide
+    else if (n == "score_path") // ... first pass of the last call: 0 serial kernel, 1 chunk kernels (N <= 8), 2 k_score_wide, 3 k_score_tile
         *value = c->last.score_path;
     else
         return invalid_arg("unknown option: " + n);

@@ -102,7 +102,7 @@ struct bhmm_ctx {
         int f32_W = 0;                   // ... fp32 warm-up fixed by the caller (option f32_W; 0: measured)
         int score_W = 0;                 // bhmm_score: warm-up fixed by the caller (option score_W; 0: measured per model)
         int score_layout = 1;            // bhmm_score, N <= 8: 1 = one lane per chunk (default), 2 = N/2 lanes per chunk
-        int score_seglen = 0;            // bhmm_score, 9..64 states: segment length of its plan (option score_seglen; 0: automatic)
+        int score_seglen = 0;            // bhmm_score, 9..128 states: segment length of its plan (option score_seglen; 0: automatic)
         bool score_lazy = true;          // ... first pass on the lazily scaled kernel (option score_lazy; 0: sum every step)
     } opt;
 
@@ -168,11 +168,13 @@ struct bhmm_ctx {
         int tile_W_good = 0;             // ... the last warm-up that verified
         int f32_W = 0;                   // fp32 E-step (estep_f32.hip): warm-up read off the forgetting curve at
                                          // 0.01 f32_tol (0: not measured yet), doubled after a failed check
-        // bhmm_score, 9..64 states: its own segment plan (tables in score.seg_*), made at the first score call on
-        // these observations from the offsets, the state count and the device alone -- never re-made after a check
+        // bhmm_score, 9..128 states: its own segment plan (tables in score.seg_*; 65..128 states: and the tile table
+        // score.tile_seg), made at the first score call on these observations from the offsets, the state count and
+        // the device alone -- never re-made after a check
         int score_nseg = 0;              // segments of the plan (0: not made yet)
         int score_ntraj = 0;             // ... trajectories with at least one step (nseg == ntraj: no boundary)
         int score_seglen_opt = 0;        // ... opt.score_seglen it was made for
+        int score_ntiles = 0;            // ... 65..128 states: tiles of 16 segments (k_score_tile)
     } ds;
 
     // ---- counters and diagnostics of the last calls (bhmm_ctx_get_option) ----
@@ -201,9 +203,10 @@ struct bhmm_ctx {
         int f32_fallbacks = 0;           // E-steps that asked for fp32 and ran the fp64 path
         float f32_last_dev = 0.f;        // largest relative boundary deviation of the last fp32 check
         int score_fallbacks = 0;         // bhmm_score: models whose boundaries did not verify at the first warm-up
-        int score_path = 0;              // ... first pass of the last call: 0 serial, 1 chunk kernels (N <= 8), 2 k_score_wide
+        int score_path = 0;              // ... first pass of the last call: 0 serial, 1 chunk kernels (N <= 8), 2 k_score_wide,
+                                         // 3 k_score_tile (65..128 states)
         int score_segments = 0;          // ... segments of the score plan it ran on (0: no such plan)
-        int score_W_max = 0;             // ... longest warm-up of its first pass at 9..64 states (0: no boundary, other paths)
+        int score_W_max = 0;             // ... longest warm-up of its first pass at 9..128 states (0: no boundary, other paths)
     } last;
 
     // ---- not reset by bhmm_ctx_set_observations: they outlive the observation set ----
@@ -308,6 +311,7 @@ struct bhmm_ctx {
         bhmm::DevBuf<double> wpar;
         bhmm::DevBuf<int32_t> seg_traj, seg_len, seg_traj0;
         bhmm::DevBuf<int64_t> seg_t0;
+        bhmm::DevBuf<int32_t> tile_seg;  // 65..128 states: segment of every tile row, [16 * ds.score_ntiles]
     } score;
 
     // ---- pinned host buffers ----

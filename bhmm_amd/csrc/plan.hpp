@@ -1,5 +1,6 @@
 // plan.hpp -- host-side planning of the time decomposition: chunk tables of the N <= 8 family
-// (bhmm_amd.hip) and segment tables of the 9..64-state family (wide_api.hip).  Pure C++ (no HIP), so
+// (bhmm_amd.hip), segment tables of the 9..64-state family (wide_api.hip), the plans of bhmm_score
+// (score_api.hip).  Pure C++ (no HIP), so
 // the same code runs under -fsanitize=address,undefined in the CPU sanitizer build
 // (oracle/Makefile `asan`); the .hip files only allocate and upload what these functions return.
 #pragma once
@@ -150,6 +151,21 @@ inline int64_t score_seglen(int64_t total, int np, int num_simd, int64_t asked)
         return (asked + 3) & ~(int64_t)3;
     const int64_t want = 2 * (int64_t)num_simd * (64 / np);
     return (std::max<int64_t>((total + want - 1) / want, 2048) + 3) & ~(int64_t)3;
+}
+
+// Segment length of the scoring plan for 65..128 states (score_api.hip: plan_segments with it, mult 1, then
+// plan_tiles).  A function of the observation set's size and the device only, like score_seglen.  asked > 0: the
+// caller's length (option score_seglen).  Automatic: enough tiles of 16 segments for one workgroup per compute
+// unit for ONE model (num_simd / 4 tiles; more models bring their own workgroups), but at least 256 steps: a
+// quickly mixing model forgets its start within some tens of steps, and a segment of four times that keeps the
+// warm-up, which is paid per segment, a minor share of the steps.
+constexpr int64_t SCORE_TILE_MIN_SEGLEN = 256;
+inline int64_t score_tile_seglen(int64_t total, int num_simd, int64_t asked)
+{
+    if (asked > 0)
+        return (asked + 3) & ~(int64_t)3;
+    const int64_t want = 16 * std::max<int64_t>(num_simd / 4, 1);
+    return (std::max<int64_t>((total + want - 1) / want, SCORE_TILE_MIN_SEGLEN) + 3) & ~(int64_t)3;
 }
 
 // Tiles of the row-batched kernels (tile_kernels.hpp): 16 segments per workgroup, which runs as long

@@ -14,7 +14,14 @@
 // from k_wide_probe (or score_W); the same protocol: a failed model runs again alone with twice the warm-up,
 // on the kernel that sums every step, then takes the exact serial recursion.
 //
-// Explicit pobs, more than 64 states and a context on the any-N family always take the exact path.
+// 65 to 128 states, gaussian or discrete: k_score_tile (score_tile_kernels.hpp) on the fp64 matrix cores, sixteen
+// segments per workgroup, over a segment plan and a tile table that again belong to scoring alone
+// (score_tile_plan; plan::score_tile_seglen, option score_seglen).  W per model from two passes of the kernel
+// itself (tile_calibrate) or the option score_W; the protocol is the same, but a model that left the number range
+// of the lazily scaled kernel goes straight to the exact serial recursion (there is no tile kernel that sums
+// every step).
+//
+// Explicit pobs and more than 128 states always take the exact path.
 //
 // Nothing here reads or writes the E-step's state (ds.* but the score plan's own fields, carried vectors,
 // warm-up lengths, d_Bt, the E-step's segment plans, the timing events, the pinned landing zones): the
@@ -33,8 +40,14 @@
 #include "plan.hpp"
 #include "score_kernels.hpp"
 #include "score_wide_kernels.hpp"
+#include "score_tile_launch.hpp"
 
 namespace bhmm {
+
+SCORE_TILE_LAUNCH_DECL(extern, 5)
+SCORE_TILE_LAUNCH_DECL(extern, 6)
+SCORE_TILE_LAUNCH_DECL(extern, 7)
+SCORE_TILE_LAUNCH_DECL(extern, 8)
 
 namespace {
 
@@ -528,6 +541,248 @@ int run_wide(bhmm_ctx *c, int S, const double *A, const double *pi, const double
                                  : Wide<NP, EMIT_DISC>::run(c, S, A, pi, par0, par1, logL);
 }
 
+// ---- 65..128 states ----------------------------------------------------------------------------
+
+constexpr int SCORE_TILE_W0 = 32;            // the two warm-ups the calibration runs at
+constexpr int SCORE_TILE_W1 = 64;
+constexpr double SCORE_TILE_DEV_OK = 3e-13;  // boundary deviation that needs no longer warm-up (tile_gen.hip)
+constexpr double SCORE_TILE_MARGIN = 1.25;   // safety factor on the extrapolated decay (tile_gen.hip)
+constexpr int SCORE_TILE_W_SLOW = 1024;      // no decay between the two warm-ups: this one, the check decides
+constexpr int SCORE_TILE_W_MAX = 1 << 20;
+
+// the segment plan and the tile table of scoring on this observation set: made once (and again when
+// score_seglen changes), never after a check
+int score_tile_plan(bhmm_ctx *c)
+{
+    auto &d = c->ds;
+    auto &b = c->score;
+    if (d.score_nseg > 0 && d.score_seglen_opt == c->opt.score_seglen)
+        return BHMM_OK;
+    plan::SegPlan sp; // (plan.hpp: pure host code)
+    plan::plan_segments(c->offsets, c->K, plan::score_tile_seglen(c->total, c->num_simd, c->opt.score_seglen), 1, sp);
+    std::vector<int32_t> tile_seg;
+    plan::plan_tiles(sp, c->offsets, false, tile_seg);
+    const size_t ns = sp.traj.size();
+    int rc;
+    if ((rc = b.seg_traj.ensure(ns)) || (rc = b.seg_len.ensure(ns)) || (rc = b.seg_t0.ensure(ns)) ||
+        (rc = b.seg_traj0.ensure(c->K + 1)) || (rc = b.tile_seg.ensure(std::max<size_t>(tile_seg.size(), 16))))
+        return rc;
+    BHMM_HIP(hipMemcpyAsync(b.seg_traj.p, sp.traj.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.seg_len.p, sp.len.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.seg_t0.p, sp.t0.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.seg_traj0.p, sp.traj0.data(), (c->K + 1) * sizeof(int32_t), hipMemcpyHostToDevice,
+                            c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.tile_seg.p, tile_seg.data(), tile_seg.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                            c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream)); // (sp and tile_seg are temporaries)
+    d.score_nseg = (int)ns;
+    d.score_ntiles = (int)(tile_seg.size() / 16);
+    d.score_ntraj = 0;
+    for (int k = 0; k < c->K; ++k)
+        d.score_ntraj += c->offsets[k + 1] > c->offsets[k];
+    d.score_seglen_opt = c->opt.score_seglen;
+    return BHMM_OK;
+}
+
+template <int KIND>
+struct Tile {
+    // what a pass left per model
+    struct Verdict {
+        unsigned int range, fails; // rows outside the lazy scaling's range; boundaries that did not verify
+        float dev;                 // largest boundary deviation
+    };
+
+    // one launch sequence for models [0, Sb) of the table on the device.  logLk_h == nullptr: boundary vectors and
+    // their check only (calibration)
+    static int pass(bhmm_ctx *c, int Sb, const ScoreTileModel *dm, double *logLk_h, Verdict *v)
+    {
+        auto &b = c->score;
+        const int K = c->K, nseg = c->ds.score_nseg, n = c->n;
+        Segs sg;
+        sg.traj = b.seg_traj.p;
+        sg.t0 = b.seg_t0.p;
+        sg.len = b.seg_len.p;
+        sg.nseg = nseg;
+        sg.W = 0; // (per model: in its table entry)
+        const TilePlan tp{b.tile_seg.p, c->ds.score_ntiles};
+        BHMM_HIP(hipMemsetAsync(b.fails.p, 0, (size_t)Sb * SCORE_TILE_FLAGS * sizeof(unsigned int), c->stream));
+        int rc = n <= 80   ? score_tile_launch<5, KIND>(c, Sb, dm, sg, tp, b.fails.p)
+                 : n <= 96  ? score_tile_launch<6, KIND>(c, Sb, dm, sg, tp, b.fails.p)
+                 : n <= 112 ? score_tile_launch<7, KIND>(c, Sb, dm, sg, tp, b.fails.p)
+                            : score_tile_launch<8, KIND>(c, Sb, dm, sg, tp, b.fails.p);
+        if (rc)
+            return rc;
+        if (nseg > c->ds.score_ntraj)
+            BHMM_HIP(launch(k_score_tile_check, dim3((nseg + 15) / 16, Sb), dim3(256), 0, c->stream, sg, n, b.aentry.p,
+                            b.aexit.p, SCORE_TOL, b.fails.p));
+        if (logLk_h)
+            BHMM_HIP(launch(k_score_logl, dim3(K, Sb), dim3(64), 0, c->stream, b.seg_traj0.p, K, nseg, b.logLc.p,
+                            b.logLk.p));
+        std::vector<unsigned int> f((size_t)Sb * SCORE_TILE_FLAGS);
+        BHMM_HIP(hipMemcpyAsync(f.data(), b.fails.p, f.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        if (logLk_h)
+            BHMM_HIP(hipMemcpyAsync(logLk_h, b.logLk.p, (size_t)Sb * K * sizeof(double), hipMemcpyDeviceToHost,
+                                    c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+        for (int s = 0; s < Sb; ++s) {
+            v[s].range = f[SCORE_TILE_FLAGS * s];
+            v[s].fails = f[SCORE_TILE_FLAGS * s + 1];
+            memcpy(&v[s].dev, &f[SCORE_TILE_FLAGS * s + 2], sizeof(float));
+        }
+        return BHMM_OK;
+    }
+
+    static int upload(bhmm_ctx *c, int Sb, ScoreTileModel *dm, std::vector<ScoreTileModel> &m, const std::vector<int> &W)
+    {
+        for (int s = 0; s < Sb; ++s)
+            m[s].W = W[s];
+        BHMM_HIP(hipMemcpyAsync(dm, m.data(), Sb * sizeof(ScoreTileModel), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream)); // (m changes between passes)
+        return BHMM_OK;
+    }
+
+    // Warm-up of every model of the batch, the way tile_gen.hip calibrates the E-step's: the kernel itself at two
+    // warm-ups, the largest boundary deviation of each, and the geometric decay between the two (the filter
+    // forgets its start vector) extrapolated to 1e-13, times SCORE_TILE_MARGIN.  A function of the model, the
+    // observation set and the plan: every model is measured on its own counters.
+    static int calibrate(bhmm_ctx *c, int Sb, ScoreTileModel *dm, std::vector<ScoreTileModel> &m, std::vector<int> &W)
+    {
+        std::vector<Verdict> v0(Sb), v1(Sb);
+        int rc;
+        W.assign(Sb, SCORE_TILE_W0);
+        if ((rc = upload(c, Sb, dm, m, W)) || (rc = pass(c, Sb, dm, nullptr, v0.data())))
+            return rc;
+        auto good = [](const Verdict &v) { return v.fails == 0 && (double)v.dev <= SCORE_TILE_DEV_OK; };
+        bool all = true;
+        for (int s = 0; s < Sb; ++s)
+            all = all && (good(v0[s]) || v0[s].range != 0);
+        if (all)
+            return BHMM_OK;
+        std::vector<int> W1(Sb, SCORE_TILE_W1);
+        if ((rc = upload(c, Sb, dm, m, W1)) || (rc = pass(c, Sb, dm, nullptr, v1.data())))
+            return rc;
+        for (int s = 0; s < Sb; ++s) {
+            if (good(v0[s]) || v0[s].range != 0)
+                continue; // (outside the range: the pass that follows sends the model to the serial recursion)
+            const double d0 = std::max((double)v0[s].dev, 1e-300), d1 = std::max((double)v1[s].dev, 1e-300);
+            if (good(v1[s])) {
+                W[s] = SCORE_TILE_W1;
+            } else if (d1 < 0.5 * d0) {
+                const double rate = log(d0 / d1) / (double)(SCORE_TILE_W1 - SCORE_TILE_W0); // per step
+                const double w = SCORE_TILE_W1 + SCORE_TILE_MARGIN * log(d1 / 1e-13) / rate;
+                W[s] = (int)std::min<double>((std::ceil(w) + 7.0) / 8.0, SCORE_TILE_W_MAX / 8) * 8;
+            } else {
+                W[s] = SCORE_TILE_W_SLOW;
+            }
+        }
+        return BHMM_OK;
+    }
+
+    static int run(bhmm_ctx *c, int S, const double *A, const double *pi, const double *par0, const double *par1,
+                   double *logL)
+    {
+        auto &b = c->score;
+        const int K = c->K, M = c->M, n = c->n;
+        int rc;
+        if ((rc = score_tile_plan(c)))
+            return rc;
+        if (c->ds.score_ntiles == 0) // (no trajectory has a step)
+            return score_serial(c, S, A, pi, par0, par1, logL);
+        const int nseg = c->last.score_segments = c->ds.score_nseg;
+        const bool segmented = nseg > c->ds.score_ntraj;
+        // models per launch: at most SCORE_MAX_MODELS, and boundary vectors of at most 1 GiB
+        const size_t per_model = (size_t)std::max(nseg, 1) * (2 * n + 1) * sizeof(double);
+        const int Sb_max = (int)std::max<size_t>(1, std::min<size_t>(SCORE_MAX_MODELS, ((size_t)1 << 30) / per_model));
+        // parameter block of a model: wide_model's layout, then B^T
+        const size_t nB = KIND == EMIT_DISC ? (size_t)n * M : 0, np = (size_t)n * n + 7 * n + nB;
+        if ((rc = b.logLc.ensure((size_t)Sb_max * nseg)) || (rc = b.aentry.ensure((size_t)Sb_max * nseg * n)) ||
+            (rc = b.aexit.ensure((size_t)Sb_max * nseg * n)) || (rc = b.logLk.ensure((size_t)Sb_max * K)) ||
+            (rc = b.fails.ensure((size_t)Sb_max * SCORE_TILE_FLAGS)) ||
+            (rc = b.models.ensure((size_t)Sb_max * sizeof(ScoreTileModel))) || (rc = b.wpar.ensure(Sb_max * np)))
+            return rc;
+        ScoreTileModel *dm = reinterpret_cast<ScoreTileModel *>(b.models.p);
+        std::vector<Verdict> v(Sb_max);
+        for (int s0 = 0; s0 < S; s0 += Sb_max) {
+            const int Sb = std::min(Sb_max, S - s0);
+            std::vector<double> h(Sb * np, 0.0);
+            std::vector<ScoreTileModel> m(Sb);
+            for (int s = 0; s < Sb; ++s) {
+                const int g = s0 + s;
+                double *hp = h.data() + s * np;
+                const double *dp = b.wpar.p + s * np;
+                memcpy(hp, A + (size_t)g * n * n, sizeof(double) * n * n);
+                memcpy(hp + (size_t)n * n, pi + (size_t)g * n, sizeof(double) * n);
+                WideModel &w = m[s].w;
+                w.A = dp;
+                w.pi = dp + (size_t)n * n;
+                w.mu = w.pi + n;
+                w.isig = w.mu + n;
+                w.cnorm = w.isig + n;
+                w.sigma = w.cnorm + n;
+                w.ga = w.sigma + n;
+                w.gb = w.ga + n;
+                w.gmg = 0.0;
+                w.B = nullptr; // (the kernel reads B^T)
+                w.n = n;
+                w.M = M;
+                m[s].Bt = nullptr;
+                m[s].W = 0;
+                double *q = hp + (size_t)n * n + n;
+                if (KIND == EMIT_GAUSS) {
+                    const double *mu = par0 + (size_t)g * n, *sg = par1 + (size_t)g * n;
+                    for (int i = 0; i < n; ++i) {
+                        q[i] = mu[i];
+                        q[n + i] = 1.0 / sg[i];
+                        q[2 * n + i] = 1.0 / (sqrt(2.0 * M_PI) * sg[i]);
+                        q[3 * n + i] = sg[i];
+                    }
+                    gauss_pdf_constants(n, n, sg, q + 4 * n, q + 5 * n, &w.gmg);
+                } else {
+                    const double *B = par0 + (size_t)g * nB;
+                    double *hBt = q + 6 * n;
+                    for (int i = 0; i < n; ++i)
+                        for (int o = 0; o < M; ++o)
+                            hBt[(size_t)o * n + i] = B[(size_t)i * M + o];
+                    m[s].Bt = w.gb + n;
+                }
+            }
+            BHMM_HIP(hipMemcpyAsync(b.wpar.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            BHMM_HIP(hipStreamSynchronize(c->stream)); // (h is a temporary)
+            // W: multiples of four (the refresh of the scaling); no boundary at all, no warm-up to measure
+            std::vector<int> W(Sb, segmented ? (c->opt.score_W + 3) & ~3 : 0);
+            if (segmented && c->opt.score_W <= 0 && (rc = calibrate(c, Sb, dm, m, W)))
+                return rc;
+            if (segmented)
+                c->last.score_W_max = std::max(c->last.score_W_max, *std::max_element(W.begin(), W.end()));
+            double *out = logL + (size_t)s0 * K;
+            if ((rc = upload(c, Sb, dm, m, W)) || (rc = pass(c, Sb, dm, out, v.data())))
+                return rc;
+            for (int s = 0; s < Sb; ++s) {
+                if (v[s].range == 0 && v[s].fails == 0)
+                    continue;
+                bool serial = v[s].range != 0; // outside the lazy scaling's range: the exact recursion at once
+                if (!serial) {
+                    // boundaries that did not verify: that model alone with twice the warm-up, then the exact path
+                    ++c->last.score_fallbacks;
+                    std::vector<ScoreTileModel> one(1, m[s]);
+                    Verdict v2;
+                    if ((rc = upload(c, 1, dm + s, one, std::vector<int>(1, (int)std::min<int64_t>(2 * (int64_t)W[s], SCORE_TILE_W_MAX)))) ||
+                        (rc = pass(c, 1, dm + s, out + (size_t)s * K, &v2)))
+                        return rc;
+                    serial = v2.range != 0 || v2.fails != 0;
+                }
+                const int g = s0 + s;
+                if (serial && (rc = score_serial(c, 1, A + (size_t)g * n * n, pi + (size_t)g * n,
+                                                 par0 + (size_t)g * (KIND == EMIT_DISC ? nB : (size_t)n),
+                                                 KIND == EMIT_GAUSS ? par1 + (size_t)g * n : nullptr,
+                                                 out + (size_t)s * K)))
+                    return rc;
+            }
+        }
+        return BHMM_OK;
+    }
+};
+
 } // namespace
 } // namespace bhmm
 
@@ -547,8 +802,12 @@ int bhmm_score(bhmm_ctx *c, int nmodels, const double *A, const double *pi, cons
         return rc;
     const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
     const bool fast = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;
-    c->last.score_path = fast ? 1 : (c->wide && emis ? 2 : 0);
+    const bool tile = c->gen && c->n <= 128 && emis; // 65..128 states
+    c->last.score_path = fast ? 1 : (c->wide && emis ? 2 : (tile ? 3 : 0));
     c->last.score_segments = c->last.score_W_max = 0;
+    if (tile)
+        return c->kind == EMIT_GAUSS ? Tile<EMIT_GAUSS>::run(c, nmodels, A, pi, par0, par1, logL)
+                                     : Tile<EMIT_DISC>::run(c, nmodels, A, pi, par0, par1, logL);
     if (c->last.score_path == 2) // 9..64 states: lanes per segment in c->N
         return c->N == 16   ? run_wide<16>(c, nmodels, A, pi, par0, par1, logL)
                : c->N == 32 ? run_wide<32>(c, nmodels, A, pi, par0, par1, logL)

@@ -271,7 +271,8 @@ class Engine(object):
         probability zero under a model scores -inf there.  Forward pass only; leaves the state that
         later E-steps, Viterbi and sampling calls use untouched.  Gaussian and discrete models run parallel
         over time: up to 8 states over the chunk plan, 9 to 64 states over a segment plan of its own (option
-        score_seglen; get_option("score_path") is 2 there, "score_segments" the plan's size); more than 64
+        score_seglen; get_option("score_path") is 2 there, "score_segments" the plan's size), 65 to 128 states
+        the same on the matrix cores (score_path 3) -- up to 128 states run parallel over time; more than 128
         states and explicit pobs take the exact serial recursion (score_path 0)."""
         if self.kind is None:
             raise ValueError("no observations loaded")

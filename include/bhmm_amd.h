@@ -168,8 +168,11 @@ int bhmm_get_gamma(bhmm_ctx *ctx, int k, double *gamma);
    with verified warm-up boundaries (options score_W, score_layout, score_fallbacks).  9 to 64 states
    (gaussian, discrete): parallel over time segments of a plan of its own, same verification and fallbacks
    (options score_seglen: segment length, 0 = automatic; score_lazy; read-only score_segments, score_W_max
-   and score_path: 0 serial, 1 chunk kernels, 2 segment kernel).  Otherwise (more than 64 states, explicit
-   pobs) the exact serial recursion, one workgroup per trajectory and model. */
+   and score_path: 0 serial, 1 chunk kernels, 2 segment kernel, 3 matrix-core kernel).  65 to 128 states
+   (gaussian, discrete): the same on the fp64 matrix cores, sixteen segments per workgroup (score_path 3;
+   score_seglen, score_W, score_segments, score_W_max, score_fallbacks as above) -- so up to 128 states run
+   parallel over time.  Otherwise (more than 128 states, explicit pobs) the exact serial recursion, one
+   workgroup per trajectory and model. */
 int bhmm_score(bhmm_ctx *ctx, int nmodels, const double *A, const double *pi,
                const double *par0, const double *par1, double *logL);
 

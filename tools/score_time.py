@@ -5,9 +5,11 @@ For configs[2] (8-state discrete, M = 64, 1024 x 1e6) and configs[1] (8-state ga
 one Engine.score call with S = 1, 8 and 64 models for each kernel layout (option score_layout), and the same
 S models as S E-steps.  For the 9..64-state setups -- configs[3] (64-state gaussian, 128 x 1e5: the model,
 observations and seed of bench.py's configs[3] block) and a 16- and a 32-state gaussian setup of the same size -- the
-same per scaling of the segmented kernel (option score_lazy; on a library without the option: as it is).  Prints one
-JSON object per measurement, with the minimum and maximum over the repetitions.  Options: --only c2|c1|c3|g16|g32
-(one config), --reps R, --label TEXT (a "build" field in every line: which library was timed), --score-only (S = 1 and 8 score calls alone: the workload of a rocprofv3 pass)."""
+same per scaling of the segmented kernel (option score_lazy; on a library without the option: as it is).  For the
+65..128-state setups g65 and g128 -- the shapes and the model construction of bench.py's secondary_gen (128 x 1e4
+gaussian, 65 and 128 states) -- the same once (there is one scaling); these two also append their lines to
+profiles/score/score_time.json.  Prints one JSON object per measurement, with the minimum and maximum over the
+repetitions.  Options: --only c2|c1|c3|g16|g32|g65|g128 (one config), --reps R, --label TEXT (a "build" field in every line: which library was timed), --score-only (S = 1 and 8 score calls alone: the workload of a rocprofv3 pass)."""
 import argparse
 import json
 import os
@@ -77,6 +79,34 @@ def g32_setup():
     return wide_setup(32, 32, "32-state gaussian 128 x 1e5")
 
 
+def gen_setup(n):
+    """bench.py's secondary_gen at n states: 128 x 1e4 gaussian, 64 candidate models around the generating one"""
+    rng = np.random.default_rng(n)
+    K, T = 128, 10000
+    A = metastable_matrix(n, rng)
+    pi = stationary(A)
+    mu, sig = np.linspace(-5, 5, n), np.linspace(0.5, 2.0, n)
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(n)
+    obs = torch.randn(K * T, dtype=torch.float64, device="cuda:0", generator=g) * 3.0
+    torch.cuda.synchronize()
+    eng = Engine(0)
+    eng.set_observations_device("gaussian", obs.data_ptr(), np.arange(K + 1, dtype=np.int64) * T, n)
+    models = [(0.9 * A + 0.1 / n, pi, mu + 0.05, sig)]     # secondary_gen's model first
+    for s in range(1, 64):
+        w = 0.85 + 0.1 * s / 63
+        models.append((w * A + (1 - w) / n, pi, mu + 0.2 * ((s * 37) % 64) / 63, sig))
+    return "%d-state gaussian 128 x 1e4" % n, eng, models, obs, K * T
+
+
+def g65_setup():
+    return gen_setup(65)
+
+
+def g128_setup():
+    return gen_setup(128)
+
+
 def opt(eng, name):
     try:
         return eng.get_option(name)
@@ -84,9 +114,11 @@ def opt(eng, name):
         return None
 
 
-def wide_main(args, setup):
+def wide_main(args, setup, one_scaling=False, keep=None):
     name, eng, models, obs, steps = setup()
     lazies = [int(x) for x in args.lazy.split(",")] if opt(eng, "score_lazy") is not None else [None]
+    if one_scaling:
+        lazies = [None]
     if args.score_only:
         for S in (1, 8):
             eng.score(models[:S])
@@ -101,14 +133,19 @@ def wide_main(args, setup):
             if lazy is not None:
                 eng.set_option("score_lazy", lazy)
             ts = timed_all(lambda: eng.score(ms), reps)
-            print(json.dumps(dict(build=args.label, config=name, lazy=lazy, S=S, reps=reps, score_ms_per_model=np.mean(ts) / S,
-                                  score_ms_per_model_min=min(ts) / S, score_ms_per_model_max=max(ts) / S,
-                                  estep_ms_per_model=np.mean(te) / S, estep_ms_per_model_min=min(te) / S,
-                                  estep_ms_per_model_max=max(te) / S,
-                                  timesteps_models_per_s=steps * S / (1e-3 * np.mean(ts)),
-                                  score_path=opt(eng, "score_path"), score_segments=opt(eng, "score_segments"),
-                                  score_W_max=opt(eng, "score_W_max"),
-                                  score_fallbacks=opt(eng, "score_fallbacks"))), flush=True)
+            line = json.dumps(dict(build=args.label, config=name, lazy=lazy, S=S, reps=reps, score_ms_per_model=np.mean(ts) / S,
+                                   score_ms_per_model_min=min(ts) / S, score_ms_per_model_max=max(ts) / S,
+                                   estep_ms_per_model=np.mean(te) / S, estep_ms_per_model_min=min(te) / S,
+                                   estep_ms_per_model_max=max(te) / S,
+                                   timesteps_models_per_s=steps * S / (1e-3 * np.mean(ts)),
+                                   score_path=opt(eng, "score_path"), score_segments=opt(eng, "score_segments"),
+                                   score_W_max=opt(eng, "score_W_max"),
+                                   score_fallbacks=opt(eng, "score_fallbacks")))
+            print(line, flush=True)
+            if keep:
+                os.makedirs(os.path.dirname(keep), exist_ok=True)
+                with open(keep, "a") as f:
+                    f.write(line + "\n")
     eng.close()
     del obs
     torch.cuda.empty_cache()
@@ -150,17 +187,22 @@ def c1_setup():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=["c2", "c1", "c3", "g16", "g32"])
+    ap.add_argument("--only", choices=["c2", "c1", "c3", "g16", "g32", "g65", "g128"])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--score-only", action="store_true")
     ap.add_argument("--layouts", default="1,2", help="score_layout values to time (1: lane per chunk, 2: N/2 lanes)")
     ap.add_argument("--label", default=None, help="written as \"build\" into every line (e.g. the commit timed)")
     ap.add_argument("--lazy", default="1,0", help="score_lazy values to time at 9..64 states (1: refresh every "
                                                    "fourth step, 0: sum every step)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "score", "score_time.json"),
+                    help="file the g65 / g128 lines are appended to")
     args = ap.parse_args()
     for key, setup in (("c3", c3_setup), ("g16", g16_setup), ("g32", g32_setup)):
         if not args.only or key == args.only:
             wide_main(args, setup)
+    for key, setup in (("g65", g65_setup), ("g128", g128_setup)):
+        if not args.only or key == args.only:
+            wide_main(args, setup, one_scaling=True, keep=args.out)
     for key, setup in (("c2", c2_setup), ("c1", c1_setup)):
         if args.only and key != args.only:
             continue
