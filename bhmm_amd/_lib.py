@@ -73,6 +73,8 @@ SIGNATURES = {
     "bhmm_get_gamma": (ctypes.c_int, [c_void_p, ctypes.c_int, c_double_p]),
     "bhmm_score": (ctypes.c_int, [c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p,
                                   c_double_p]),
+    "bhmm_posterior_decode": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                             c_void_p, ctypes.c_int, c_void_p]),
     "bhmm_viterbi_batch": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,
                                           c_double_p, c_int32_p]),
     "bhmm_viterbi_batch_u8": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,

@@ -175,3 +175,37 @@ def score(observations, models, lag=1, per_trajectory=False, **engine_kwargs):
     finally:
         eng.close()
     return logL if per_trajectory else logL.sum(axis=1)
+
+
+def posterior_decode(observations, model, lag=1, confidence=False, **engine_kwargs):
+    """Posterior (maximum-posterior-marginal) decoding of `observations` under one HMM
+    (bhmm_posterior_decode): per trajectory the state of largest posterior marginal gamma_t(i) at every
+    step (the lowest index on exactly equal gamma), as uint8 arrays (int32 above 256 states); with
+    `confidence` also max_i gamma_t(i) as float32 arrays, returned as (paths, conf).  lag > 1 decodes the
+    lagged views (lag_observations), one result per view.  Gaussian and discrete models of up to 8 states
+    are decoded by one fused kernel that stores no gamma; more states run an E-step that stores gamma.
+    engine_kwargs: device (default 0)."""
+    from .engine import Engine
+    from .estimators.maximum_likelihood import model_tuple
+    if not isinstance(model, HMM):
+        raise TypeError("model must be an HMM object")
+    if len(observations) == 0:
+        raise ValueError("no observations")
+    output = model.output_model.model_type
+    nstates = model.nstates
+    nsymbols = model.output_model.nsymbols if output == 'discrete' else 0
+    device = engine_kwargs.pop('device', 0)
+    if engine_kwargs:
+        raise TypeError("unexpected keyword arguments: %s" % ", ".join(sorted(engine_kwargs)))
+    if lag > 1:
+        observations = lag_observations(observations, lag)
+    eng = Engine(device)
+    try:
+        if output == 'discrete':
+            obs = [np.asarray(o) for o in observations]
+            eng.set_observations('discrete', obs, nstates, nsymbols=nsymbols)
+        else:
+            eng.set_observations(output, [np.asarray(o, dtype=np.float64) for o in observations], nstates)
+        return eng.posterior_decode(*model_tuple(model), confidence=confidence)
+    finally:
+        eng.close()

@@ -1534,7 +1534,13 @@ int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
         c->opt.score_seglen = ((int)value + 3) & ~3;
     } else if (n == "score_lazy") // ... first pass on the lazily scaled kernel (default) or summing every step
         c->opt.score_lazy = value != 0.0;
-    else
+    else if (n == "post_W") // bhmm_posterior_decode only: fixed warm-up (0: measured); no E-step state changes
+        c->opt.post_W = std::max(0, (int)value);
+    else if (n == "post_ws_mb") { // ... budget of its alpha-row workspace in MiB (0: unbounded)
+        if (!(value >= 0.0) || value > (double)(1 << 30))
+            return invalid_arg("post_ws_mb outside [0, 2^30]");
+        c->opt.post_ws_mb = (int)value;
+    } else
         return invalid_arg("unknown or read-only option: " + n);
     return BHMM_OK;
 }
@@ -1649,6 +1655,14 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->last.score_segments;
     else if (n == "score_W_max") // ... longest warm-up of its first pass at 9..128 states (0: no boundary, other paths)
         *value = c->last.score_W_max;
+    else if (n == "post_W")
+        *value = c->opt.post_W;
+    else if (n == "post_ws_mb")
+        *value = c->opt.post_ws_mb;
+    else if (n == "post_fallbacks") // bhmm_posterior_decode: calls whose boundaries did not verify at the first warm-up
+        *value = c->last.post_fallbacks;
+    else if (n == "post_path") // ... first pass of the last call: 1 fused kernel (up to 8 states), 0 E-step + gamma rows
+        *value = c->last.post_path;
     else if (n == "score_path") // ... first pass of the last call: 0 serial kernel, 1 chunk kernels (N <= 8), 2 k_score_wide, 3 k_score_tile
         *value = c->last.score_path;
     else

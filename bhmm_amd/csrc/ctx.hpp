@@ -104,6 +104,8 @@ struct bhmm_ctx {
         int score_layout = 1;            // bhmm_score, N <= 8: 1 = one lane per chunk (default), 2 = N/2 lanes per chunk
         int score_seglen = 0;            // bhmm_score, 9..128 states: segment length of its plan (option score_seglen; 0: automatic)
         bool score_lazy = true;          // ... first pass on the lazily scaled kernel (option score_lazy; 0: sum every step)
+        int post_W = 0;                  // bhmm_posterior_decode: warm-up fixed by the caller (option post_W; 0: measured)
+        int post_ws_mb = 8192;           // ... budget of its alpha-row workspace in MiB (option post_ws_mb; 0: unbounded)
     } opt;
 
     // ---- loaded problem ----
@@ -207,6 +209,8 @@ struct bhmm_ctx {
                                          // 3 k_score_tile (65..128 states)
         int score_segments = 0;          // ... segments of the score plan it ran on (0: no such plan)
         int score_W_max = 0;             // ... longest warm-up of its first pass at 9..128 states (0: no boundary, other paths)
+        int post_fallbacks = 0;          // bhmm_posterior_decode: calls whose boundaries did not verify at the first warm-up
+        int post_path = 0;               // ... first pass of the last call: 1 fused (k_post_sweep), 0 generic (E-step + gamma rows)
     } last;
 
     // ---- not reset by bhmm_ctx_set_observations: they outlive the observation set ----
@@ -313,6 +317,16 @@ struct bhmm_ctx {
         bhmm::DevBuf<int64_t> seg_t0;
         bhmm::DevBuf<int32_t> tile_seg;  // 65..128 states: segment of every tile row, [16 * ds.score_ntiles]
     } score;
+    // bhmm_posterior_decode (post_api.hip): its own buffers -- model, B^T, alpha-row workspace of one range of
+    // chunk groups, boundary vectors of both directions, failure counter, probe curve, and the results on the
+    // device (path: bytes or int32; conf); nothing else reads them
+    struct PostBufs {
+        bhmm::DevBuf<char> model, probe, path;
+        bhmm::DevBuf<double> Bt, ws, aentry, aexit, bassumed, bout;
+        bhmm::DevBuf<uint8_t> dead;
+        bhmm::DevBuf<float> conf;
+        bhmm::DevBuf<unsigned int> fails;
+    } post;
 
     // ---- pinned host buffers ----
     unsigned int *h_specres = nullptr; // pinned

@@ -1,0 +1,286 @@
+// post_api.hip -- bhmm_posterior_decode: for every step of every loaded trajectory the state of largest
+// posterior marginal, argmax_i gamma_t(i), and optionally that marginal.  Kernels in post_kernels.hpp;
+// DESIGN.md section 14.
+//
+// Up to 8 states, gaussian or discrete (the fused path, post_path 1): k_post_sweep over the E-step's chunk
+// plan, forward and backward in one launch per range of chunk groups, the alpha rows in a workspace of
+// at most post_ws_mb (the host loops over ranges of groups; every lane's arithmetic is its own, so the result
+// does not depend on the budget), then k_post_check over the boundary vectors of both directions.  The warm-up
+// comes from the forgetting probe of the E-step (k_forget_probe, the larger of its two directions) or the
+// option post_W.  Boundaries that do not verify: counted in post_fallbacks, the call runs again with twice
+// the warm-up, and if they fail again it takes the generic path.
+//
+// Everything else (9 states and more, explicit pobs; post_path 0): bhmm_estep with BHMM_FLAG_STORE_GAMMA
+// through its own entry point and protocol, then k_post_gamma_rm / k_post_gamma_ci over the stored rows.
+// That IS an E-step for the context's state (statistics, carried boundaries, timers, stored gamma), exactly
+// like a caller's own.
+//
+// The fused path reads or writes nothing of the E-step's state (ds.*, carried vectors, warm-up lengths,
+// d_Bt, the timing events, the pinned landing zones): its buffers are c->post.*, the only other fields
+// touched are opt.post_* (read) and last.post_*.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "host_common.hpp"
+#include "host_internal.hpp"
+#include "launch.hpp"
+#include "model_check.hpp"
+#include "post_kernels.hpp"
+
+namespace bhmm {
+namespace {
+
+constexpr double POST_TOL = 1e-11;         // boundary check: componentwise relative (the E-step's spec_tol default)
+constexpr int POST_W_UNPROBED = 288;       // warm-up when the trajectories are too short to probe (the E-step's)
+constexpr size_t POST_LDS_BT = 16 * 1024;  // B^T staged in LDS up to this size
+
+// the results on the device to the caller: the paths as deliver_paths does, the confidences after them
+int deliver(bhmm_ctx *c, void *path, int path_u8, float *conf)
+{
+    auto &b = c->post;
+    if (conf)
+        BHMM_HIP(hipMemcpyAsync(conf, b.conf.p, (size_t)c->total * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return deliver_paths(c, path, path_u8 ? 1 : 0, b.path.p);
+}
+
+template <int N, int KIND>
+struct Fused {
+    // warm-up from the forgetting curve: the probe's reading as bhmm_score takes it (chains within 1e-13
+    // from then on, + 15 %, doubled), here the larger of the forward and the backward direction.  0 where
+    // the trajectories are too short to probe
+    static int probe(bhmm_ctx *c, const Model<N> &m, const double *dBt, int *W)
+    {
+        *W = 0;
+        const int64_t maxT = longest_traj(c);
+        const int Wmax = (int)std::min<int64_t>(1024, maxT / 2) / 4 * 4;
+        if (Wmax < 32)
+            return BHMM_OK;
+        std::vector<int> longk;
+        for (int k = 0; k < c->K; ++k)
+            if (c->offsets[k + 1] - c->offsets[k] >= Wmax)
+                longk.push_back(k);
+        const int P = 256;
+        std::vector<int64_t> starts(P);
+        for (int i = 0; i < P; ++i) {
+            const int k = longk[i % longk.size()];
+            const int64_t room = c->offsets[k + 1] - c->offsets[k] - Wmax + 1;
+            const int64_t rep = i / (int64_t)longk.size(), reps = (P + longk.size() - 1) / longk.size();
+            starts[i] = c->offsets[k] + (room - 1) * rep / std::max<int64_t>(reps - 1, 1);
+        }
+        const size_t curve_words = 2 * (size_t)Wmax; // forward | backward
+        int rc;
+        if ((rc = c->post.probe.ensure(P * sizeof(int64_t) + curve_words * sizeof(unsigned int))))
+            return rc;
+        int64_t *d_starts = reinterpret_cast<int64_t *>(c->post.probe.p);
+        unsigned int *d_curve = reinterpret_cast<unsigned int *>(d_starts + P);
+        BHMM_HIP(hipMemcpyAsync(d_starts, starts.data(), P * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipMemsetAsync(d_curve, 0, curve_words * sizeof(unsigned int), c->stream));
+        BHMM_HIP(launch(k_forget_probe<N, KIND>, dim3((2 * P + 63) / 64), dim3(64), 0, c->stream, m, c->d_obs_rm.p,
+                        KIND == EMIT_DISC ? dBt : nullptr, d_starts, P, Wmax, d_curve));
+        std::vector<float> curve(curve_words);
+        BHMM_HIP(hipMemcpyAsync(curve.data(), d_curve, curve.size() * sizeof(float), hipMemcpyDeviceToHost,
+                                c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+        const float target = (float)(0.01 * POST_TOL);
+        int last = -1;
+        for (int dir = 0; dir < 2; ++dir)
+            for (int w = 0; w < Wmax; ++w)
+                if (curve[(size_t)dir * Wmax + w] >= target)
+                    last = std::max(last, w);
+        const int w = (int)std::ceil(1.15 * (last + 2));
+        *W = 2 * std::min(std::max(16, (w + 3) / 4 * 4), Wmax);
+        return BHMM_OK;
+    }
+
+    // the sweep over every range of chunk groups and the check; *fails: boundaries out of tolerance
+    template <typename PT>
+    static int pass(bhmm_ctx *c, const Model<N> *dm, int W, const double *dBt, bool want_conf, unsigned int *fails)
+    {
+        auto &b = c->post;
+        const int G = c->G, groups = c->Gp / 64;
+        const Chunks ch = chunks_of(c);
+        const size_t lds_bt = (size_t)c->M * score_bt_stride(N) * sizeof(double);
+        const bool bt_lds = KIND == EMIT_DISC && lds_bt <= POST_LDS_BT;
+        // alpha rows of one group, and how many groups the budget holds (at least one)
+        const size_t per_group = (size_t)c->Lmax * N * 64 * sizeof(double);
+        const size_t budget = (size_t)c->opt.post_ws_mb << 20;
+        const int per_range =
+            budget == 0 ? groups : (int)std::min<size_t>(groups, std::max<size_t>(1, budget / per_group));
+        int rc;
+        if ((rc = b.ws.ensure((size_t)per_range * c->Lmax * N * 64)))
+            return rc;
+        BHMM_HIP(hipMemsetAsync(b.fails.p, 0, sizeof(unsigned int), c->stream));
+        auto *kern = bt_lds ? k_post_sweep<N, KIND, true, PT> : k_post_sweep<N, KIND, false, PT>;
+        for (int g0 = 0; g0 < groups; g0 += per_range)
+            BHMM_HIP(launch(kern, dim3(std::min(per_range, groups - g0)), dim3(64), bt_lds ? lds_bt : 0, c->stream, dm,
+                            W, ch, G, g0, c->d_offsets.p, c->d_obs_ci.p, c->d_obs_rm.p, dBt, c->M, b.ws.p,
+                            reinterpret_cast<PT *>(b.path.p), want_conf ? b.conf.p : nullptr, b.aentry.p, b.aexit.p,
+                            b.bassumed.p, b.bout.p, b.dead.p));
+        if (G > 1)
+            BHMM_HIP(launch(k_post_check<N>, dim3((G + 255) / 256), dim3(256), 0, c->stream, ch, G, b.aentry.p,
+                            b.aexit.p, b.bassumed.p, b.bout.p, b.dead.p, POST_TOL, b.fails.p));
+        BHMM_HIP(hipMemcpyAsync(fails, b.fails.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+        return BHMM_OK;
+    }
+
+    // *verified: the outputs in c->post.path / conf stand
+    static int run(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                   int path_u8, bool want_conf, bool *verified)
+    {
+        auto &b = c->post;
+        const int M = c->M, n = c->n;
+        *verified = false;
+        int rc;
+        if ((rc = b.model.ensure(sizeof(Model<N>))) || (rc = b.aentry.ensure((size_t)c->Gp * N)) ||
+            (rc = b.aexit.ensure((size_t)c->Gp * N)) || (rc = b.bassumed.ensure((size_t)c->Gp * N)) ||
+            (rc = b.bout.ensure((size_t)c->Gp * N)) || (rc = b.dead.ensure(c->Gp)) || (rc = b.fails.ensure(1)) ||
+            (KIND == EMIT_DISC && (rc = b.Bt.ensure((size_t)M * N))))
+            return rc;
+        Model<N> m;
+        fill_model<N>(m, n, KIND, M, A, pi, par0, par1);
+        Model<N> *dm = reinterpret_cast<Model<N> *>(b.model.p);
+        std::vector<double> bt;
+        if (KIND == EMIT_DISC) {
+            bt.resize((size_t)M * N);
+            for (int i = 0; i < n; ++i)
+                for (int o = 0; o < M; ++o)
+                    bt[(size_t)o * N + i] = par0[(size_t)i * M + o];
+            BHMM_HIP(hipMemcpyAsync(b.Bt.p, bt.data(), bt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        }
+        BHMM_HIP(hipMemcpyAsync(dm, &m, sizeof(Model<N>), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream)); // (m and bt are temporaries)
+        int W = c->opt.post_W;
+        if (W <= 0) {
+            if ((rc = probe(c, m, b.Bt.p, &W)))
+                return rc;
+            W = W > 0 ? W : POST_W_UNPROBED;
+        }
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            unsigned int fails = 0;
+            rc = path_u8 ? pass<uint8_t>(c, dm, W, b.Bt.p, want_conf, &fails)
+                         : pass<int32_t>(c, dm, W, b.Bt.p, want_conf, &fails);
+            if (rc)
+                return rc;
+            if (fails == 0) {
+                *verified = true;
+                return BHMM_OK;
+            }
+            if (attempt == 0)
+                ++c->last.post_fallbacks; // boundaries that did not verify at the first warm-up
+            W = (int)std::min<int64_t>(2 * (int64_t)W, 1 << 30);
+        }
+        return BHMM_OK;
+    }
+};
+
+template <int N>
+int run_n(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, int path_u8,
+          bool want_conf, bool *verified)
+{
+    return c->kind == EMIT_GAUSS ? Fused<N, EMIT_GAUSS>::run(c, A, pi, par0, par1, path_u8, want_conf, verified)
+                                 : Fused<N, EMIT_DISC>::run(c, A, pi, par0, par1, path_u8, want_conf, verified);
+}
+
+// the generic path: an E-step that stores gamma, then argmax / max over the rows in the layout the
+// kernel family of this context stores them in
+template <typename PT>
+int gamma_decode(bhmm_ctx *c, bool want_conf)
+{
+    auto &b = c->post;
+    PT *path = reinterpret_cast<PT *>(b.path.p);
+    float *conf = want_conf ? b.conf.p : nullptr;
+    if (c->total == 0)
+        return BHMM_OK;
+    if (c->wide || c->gen) { // trajectory-major rows of n
+        BHMM_HIP(launch(k_post_gamma_rm<PT>, dim3((unsigned)((c->total + 255) / 256)), dim3(256), 0, c->stream,
+                        c->d_gamma_ci.p, c->n, c->total, path, conf));
+        return BHMM_OK;
+    }
+    const Chunks ch = chunks_of(c); // (the plan the E-step ended on)
+    const dim3 grid((c->G + 255) / 256), block(256);
+    if (c->N == 2)
+        BHMM_HIP(launch(k_post_gamma_ci<2, PT>, grid, block, 0, c->stream, ch, c->G, c->d_gamma_ci.p, c->n, path, conf));
+    else if (c->N == 4)
+        BHMM_HIP(launch(k_post_gamma_ci<4, PT>, grid, block, 0, c->stream, ch, c->G, c->d_gamma_ci.p, c->n, path, conf));
+    else
+        BHMM_HIP(launch(k_post_gamma_ci<8, PT>, grid, block, 0, c->stream, ch, c->G, c->d_gamma_ci.p, c->n, path, conf));
+    return BHMM_OK;
+}
+
+int generic(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, int path_u8,
+            bool want_conf)
+{
+    int rc;
+    if ((rc = bhmm_estep(c, A, pi, par0, par1, nullptr, BHMM_FLAG_STORE_GAMMA)) ||
+        (rc = bhmm_estep_fetch(c, nullptr, nullptr))) // (waits; a non-finite log-likelihood is its error)
+        return rc;
+    return path_u8 ? gamma_decode<uint8_t>(c, want_conf) : gamma_decode<int32_t>(c, want_conf);
+}
+
+} // namespace
+} // namespace bhmm
+
+using namespace bhmm;
+
+extern "C" {
+
+int bhmm_posterior_decode(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                          void *path, int path_u8, float *conf)
+{
+    int rc = enter_model_call(c, A && pi && path, "A / pi / path == NULL", true, par0, par1);
+    if (rc)
+        return rc;
+    if (path_u8 && c->n > 256)
+        return invalid_arg("bhmm_posterior_decode: one byte per step holds at most 256 states (use the int32 form)");
+    if ((rc = check_models(c, "bhmm_posterior_decode", 1, A, pi, par0, par1)))
+        return rc;
+    auto &b = c->post;
+    if ((rc = b.path.ensure(std::max<size_t>((size_t)c->total * (path_u8 ? 1 : sizeof(int32_t)), 8))) ||
+        (conf && (rc = b.conf.ensure(std::max<size_t>(c->total, 1)))))
+        return rc;
+    const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
+    const bool fused = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;
+    c->last.post_path = fused ? 1 : 0;
+    bool verified = false;
+    if (fused) {
+        switch (c->n) {
+        case 1:
+            rc = run_n<1>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            break;
+        case 2:
+            rc = run_n<2>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            break;
+        case 3:
+            rc = run_n<3>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            break;
+        case 4:
+            rc = run_n<4>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            break;
+        case 5:
+            rc = run_n<5>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            break;
+        case 6:
+            rc = run_n<6>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            break;
+        case 7:
+            rc = run_n<7>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            break;
+        default:
+            rc = run_n<8>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            break;
+        }
+        if (rc)
+            return rc;
+    }
+    if (!verified && (rc = generic(c, A, pi, par0, par1, path_u8, conf != nullptr)))
+        return rc;
+    return deliver(c, path, path_u8, conf);
+}
+
+} // extern "C"

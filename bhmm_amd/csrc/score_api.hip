@@ -37,6 +37,7 @@
 #include "host_common.hpp"
 #include "host_internal.hpp"
 #include "launch.hpp"
+#include "model_check.hpp"
 #include "plan.hpp"
 #include "score_kernels.hpp"
 #include "score_wide_kernels.hpp"
@@ -54,52 +55,7 @@ namespace {
 constexpr double SCORE_TOL = 1e-11;         // boundary check: componentwise relative (the E-step's spec_tol default)
 constexpr int SCORE_W_UNPROBED = 288;       // warm-up when the trajectories are too short to probe (the E-step's)
 constexpr size_t SCORE_LDS_BT = 16 * 1024;  // B^T of a model staged in LDS up to this size
-constexpr double SCORE_STOCH_TOL = 1e-8;    // rows of A, pi and B must sum to 1 within this
 constexpr double SCORE_WIDE_MARGIN = 1.5;   // 9..64 states: warm-up over the probe's reading (wide_probe_run's factor)
-
-int check_prob_rows(const double *p, int rows, int cols, int s, const char *what)
-{
-    for (int r = 0; r < rows; ++r) {
-        double sum = 0.0;
-        for (int j = 0; j < cols; ++j) {
-            const double v = p[(size_t)r * cols + j];
-            if (!std::isfinite(v) || v < 0.0)
-                return invalid_arg("bhmm_score: model " + std::to_string(s) + ": " + what +
-                                   " has a negative or non-finite entry");
-            sum += v;
-        }
-        if (!(fabs(sum - 1.0) <= SCORE_STOCH_TOL))
-            return invalid_arg("bhmm_score: model " + std::to_string(s) + ": " + what +
-                               (rows > 1 ? " row " + std::to_string(r) : std::string()) + " sums to " +
-                               std::to_string(sum) + ", not 1");
-    }
-    return BHMM_OK;
-}
-
-int check_models(const bhmm_ctx *c, int S, const double *A, const double *pi, const double *par0,
-                 const double *par1)
-{
-    const int n = c->n;
-    int rc;
-    for (int s = 0; s < S; ++s) {
-        if ((rc = check_prob_rows(A + (size_t)s * n * n, n, n, s, "A")) ||
-            (rc = check_prob_rows(pi + (size_t)s * n, 1, n, s, "pi")))
-            return rc;
-        if (c->kind == EMIT_GAUSS) {
-            for (int i = 0; i < n; ++i) {
-                const double mu = par0[(size_t)s * n + i], sg = par1[(size_t)s * n + i];
-                if (!std::isfinite(mu) || !std::isfinite(sg) || !(sg > 0.0) ||
-                    !std::isfinite(1.0 / (sqrt(2.0 * M_PI) * sg)))
-                    return invalid_arg("bhmm_score: model " + std::to_string(s) +
-                                       ": means must be finite and sigmas positive and finite");
-            }
-        } else if (c->kind == EMIT_DISC) {
-            if ((rc = check_prob_rows(par0 + (size_t)s * n * c->M, n, c->M, s, "B")))
-                return rc;
-        }
-    }
-    return BHMM_OK;
-}
 
 // per (trajectory, model) log-likelihood on the exact serial recursion for models [0, S) of the stacked
 // arrays; out[s * K + k]
@@ -798,7 +754,7 @@ int bhmm_score(bhmm_ctx *c, int nmodels, const double *A, const double *pi, cons
         return rc;
     if (nmodels < 1)
         return invalid_arg("bhmm_score: nmodels must be >= 1");
-    if ((rc = check_models(c, nmodels, A, pi, par0, par1)))
+    if ((rc = check_models(c, "bhmm_score", nmodels, A, pi, par0, par1)))
         return rc;
     const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
     const bool fast = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;

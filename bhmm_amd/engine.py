@@ -282,6 +282,51 @@ class Engine(object):
                                       _lib.dp(logL)))
         return logL
 
+    # -- posterior decoding ----------------------------------------------------------------
+    def posterior_decode(self, A, pi, par0=None, par1=None, confidence=False, out=None):
+        """Posterior (maximum-posterior-marginal) decoding (bhmm_posterior_decode): for every step the
+        state of largest gamma_t(i) -- the lowest index on exactly equal gamma -- and, with `confidence`,
+        that largest gamma.  Returns a list of per-trajectory uint8 views (int32 above 256 states) like
+        viterbi, or (paths, conf) with per-trajectory float32 views.  out: None, or a C-contiguous numpy
+        array of sum(T_k) elements of that path dtype which receives the concatenated paths (the views
+        then point into it).  Up to 8 states (gaussian, discrete) one fused kernel decodes without storing
+        gamma and leaves the state of E-step, Viterbi, sampling and scoring calls untouched
+        (get_option("post_path") == 1; options post_W, post_ws_mb, read-only post_fallbacks); 9 states
+        and more and explicit pobs run an E-step that stores gamma and count as one (post_path 0)."""
+        if self.kind is None:
+            raise ValueError("no observations loaded")
+        n, M = self.nstates, self.nsymbols
+        if np.shape(A) != (n, n) or np.shape(pi) != (n,):
+            raise ValueError("A must be (%d, %d) and pi (%d,)" % (n, n, n))
+        if self.kind == 'gaussian':
+            if par0 is None or par1 is None:
+                raise ValueError("gaussian emissions need means and sigmas")
+            if np.shape(par0) != (n,) or np.shape(par1) != (n,):
+                raise ValueError("means and sigmas must be (%d,)" % n)
+        elif self.kind == 'discrete':
+            if par0 is None:
+                raise ValueError("discrete emissions need B")
+            if np.shape(par0) != (n, M):
+                raise ValueError("B must be (%d, %d)" % (n, M))
+        total = int(self.offsets[-1])
+        dtype = np.uint8 if n <= 256 else np.int32
+        if out is None:
+            out = np.empty(total, dtype=dtype)
+        elif (not isinstance(out, np.ndarray) or out.dtype != dtype or out.ndim != 1 or out.size != total
+              or not out.flags.c_contiguous):
+            raise ValueError("out must be a C-contiguous %s array of sum(T_k) = %d elements"
+                             % (np.dtype(dtype).name, total))
+        conf = np.empty(total, dtype=np.float32) if confidence else None
+        A, pi, p0, p1 = self._model_ptrs(A, pi, par0, par1)
+        _lib.check(self._L.bhmm_posterior_decode(
+            self._h, A, pi, p0, p1, ctypes.c_void_p(out.ctypes.data), 1 if dtype == np.uint8 else 0,
+            ctypes.c_void_p(conf.ctypes.data) if confidence else None))
+        K = len(self.lengths)
+        paths = [out[self.offsets[k]:self.offsets[k + 1]] for k in range(K)]
+        if not confidence:
+            return paths
+        return paths, [conf[self.offsets[k]:self.offsets[k + 1]] for k in range(K)]
+
     # -- paths ---------------------------------------------------------------------------
     def viterbi(self, A, pi, par0=None, par1=None):
         A, pi, p0, p1 = self._model_ptrs(A, pi, par0, par1)

@@ -371,6 +371,26 @@ class MaximumLikelihoodEstimator(object):
                 paths[k] = pth
         return paths
 
+    def posterior_decode(self, confidence=False):
+        """Posterior (maximum-posterior-marginal) decoding of the estimator's observations under the
+        current (fitted) hmm (Engine.posterior_decode): a list in the caller's trajectory order of the
+        state of largest gamma_t(i) per step, uint8 (int32 above 256 states); with `confidence`
+        (paths, conf), conf the float32 arrays of max_i gamma_t(i).  With a process_group every rank
+        decodes the trajectories it holds and the entries of the others are None (local_trajectories
+        lists the ones filled); there is no collective.  Up to 8 states the EM state of the engine stays
+        untouched; more states run one more E-step that stores gamma."""
+        par0, par1 = self._hmm.output_model.parameters()
+        paths, conf = [None] * self._nobs, [None] * self._nobs
+        if self._mine:
+            res = self._engine.posterior_decode(self._hmm.transition_matrix, self._hmm.initial_distribution,
+                                                par0, par1, confidence=confidence)
+            lp, lc = res if confidence else (res, None)
+            for j, k in enumerate(self._mine):
+                paths[k] = lp[j]
+                if confidence:
+                    conf[k] = lc[j]
+        return (paths, conf) if confidence else paths
+
     def score(self, models=None):
         """Total log-likelihood of the estimator's observations under each model (forward pass
         only, Engine.score): `models` is one HMM, a list of HMMs or (A, pi, par0, par1) tuples, or

@@ -14,7 +14,7 @@ from .. import _lib
 from ..util import config
 
 __all__ = ['set_implementation', 'forward', 'backward', 'state_probabilities', 'state_counts',
-           'transition_counts', 'viterbi', 'sample_path']
+           'transition_counts', 'viterbi', 'sample_path', 'posterior_decode']
 
 __IMPL_HIP__ = 2
 __impl__ = __IMPL_HIP__
@@ -174,3 +174,28 @@ def sample_path(alpha, A, pobs, T=None, seed=None, u=None):
     a_, A_ = _lib.f64(alpha[:T]), _lib.f64(A)
     _lib.check(L.bhmm_sample_path(_lib.ip(path), _lib.dp(a_), _lib.dp(A_), _lib.dp(u_), N, T))
     return path
+
+
+def posterior_decode(A, pobs, pi, confidence=False):
+    """Posterior (maximum-posterior-marginal) decoding of one trajectory given its pobs rows (no twin in
+    the reference, which offers state_probabilities and leaves the argmax to the caller): path[t] =
+    argmax_i gamma_t(i), the lowest index on exactly equal gamma, as uint8 (int32 above 256 states); with
+    `confidence` also max_i gamma_t(i) as float32, returned as (path, conf).  Explicit pobs take the
+    generic path of bhmm_posterior_decode: one E-step that stores gamma, then a kernel over its rows."""
+    _check_dtype()
+    A_, p_, pi_ = _lib.f64(A), _lib.f64(pobs), _lib.f64(pi)
+    N = A_.shape[0] if A_.ndim == 2 else -1
+    if A_.ndim != 2 or A_.shape != (N, N) or pi_.shape != (N,) or p_.ndim != 2 or p_.shape[1] != N:
+        raise ValueError('A must be (N, N), pi (N,) and pobs (T, N)')
+    if p_.shape[0] < 1:
+        raise ValueError('pobs has no rows')
+    from ..engine import Engine
+    eng = Engine(0)
+    try:
+        eng.set_observations('explicit', [p_], N)
+        res = eng.posterior_decode(A_, pi_, confidence=confidence)
+    finally:
+        eng.close()
+    if confidence:
+        return res[0][0], res[1][0]
+    return res[0]

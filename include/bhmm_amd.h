@@ -176,6 +176,26 @@ int bhmm_get_gamma(bhmm_ctx *ctx, int k, double *gamma);
 int bhmm_score(bhmm_ctx *ctx, int nmodels, const double *A, const double *pi,
                const double *par0, const double *par1, double *logL);
 
+/* Posterior (maximum-posterior-marginal) decoding of every loaded trajectory under ONE model (A, pi,
+   par0, par1 as for bhmm_viterbi_batch): path[t] = argmax_i gamma_t(i), on exactly equal gamma the lowest
+   index; conf[t] = max_i gamma_t(i) as float, or nothing when conf == NULL.  path and conf are host buffers
+   concatenated over the trajectories like the observations; path holds int32_t, or with path_u8 != 0 one
+   byte per step (more than 256 states: BHMM_ERR_INVALID).  The model is validated as by bhmm_score
+   (BHMM_ERR_INVALID); synchronous.
+   Up to 8 states (gaussian, discrete): one fused forward-backward kernel over the chunk plan with verified
+   warm-up boundaries in both directions; no gamma row is stored and every state that E-step, Viterbi,
+   sampling and scoring calls use stays untouched.  Options: post_W (warm-up in steps, 0 = measured),
+   post_ws_mb (budget of the alpha-row workspace in MiB, default 8192, 0 = unbounded: the call loops over
+   ranges of chunk groups, the result does not depend on it); read-only post_fallbacks (calls whose
+   boundaries did not verify at the first warm-up: they run again with twice the warm-up, then take the
+   generic path) and post_path (first pass of the last call: 1 fused, 0 generic).
+   Generic path (9 states and more, explicit pobs): a bhmm_estep with BHMM_FLAG_STORE_GAMMA followed by a
+   kernel over the stored rows.  It counts as an E-step for the context (last statistics, carried
+   boundaries, timers, stored gamma) exactly like the caller's own, needs total * N * 8 bytes for gamma
+   (BHMM_ERR_NO_MEM if they are not there) and returns BHMM_ERR_NONFINITE where bhmm_estep_fetch would. */
+int bhmm_posterior_decode(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0,
+                          const double *par1, void *path, int path_u8, float *conf);
+
 /* Viterbi paths of all trajectories (maximum_likelihood.py:332-352).  paths is a host
  * buffer of sum_k T_k int32, trajectory-concatenated like obs. */
 int bhmm_viterbi_batch(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0,
