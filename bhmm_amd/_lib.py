@@ -30,6 +30,9 @@ EMIT_EXPLICIT = 2
 FLAG_STORE_GAMMA = 1
 FLAG_SINGLE = 2        # the caller accepts a single-precision E-step (up to 8 states; else fp64)
 
+MARG_F32 = 1           # bhmm_posterior_marginals: rows of float
+MARG_DEVICE = 2        # ... out is a device pointer
+
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -75,6 +78,8 @@ SIGNATURES = {
                                   c_double_p]),
     "bhmm_posterior_decode": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                              c_void_p, ctypes.c_int, c_void_p]),
+    "bhmm_posterior_marginals": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                c_double_p, ctypes.c_int, c_void_p, ctypes.c_int]),
     "bhmm_viterbi_batch": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,
                                           c_double_p, c_int32_p]),
     "bhmm_viterbi_batch_u8": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,

@@ -209,3 +209,43 @@ def posterior_decode(observations, model, lag=1, confidence=False, **engine_kwar
         return eng.posterior_decode(*model_tuple(model), confidence=confidence)
     finally:
         eng.close()
+
+
+def posterior_marginals(observations, model, lag=1, weights=None, dtype=np.float64, **engine_kwargs):
+    """Posterior state probabilities of `observations` under one HMM (bhmm_posterior_marginals): per
+    trajectory a (T_k, nstates) array of gamma_t(i) -- what the reference's estimator hands out as
+    hidden_state_probabilities, for any model and without an EM run -- or with `weights` ((nstates, Q),
+    1 <= Q <= 8: set memberships, state means) the (T_k, Q) array gamma @ weights.  dtype float64 or float32.
+    The arrays are views into one array.  lag > 1 works on the lagged views (lag_observations), one result
+    per view.  Gaussian and discrete models of up to 8 states run one fused kernel that stores no gamma beyond
+    the result; more states run an E-step that stores gamma.  engine_kwargs: device (default 0)."""
+    from .engine import Engine
+    from .estimators.maximum_likelihood import model_tuple
+    if not isinstance(model, HMM):
+        raise TypeError("model must be an HMM object")
+    if len(observations) == 0:
+        raise ValueError("no observations")
+    output = model.output_model.model_type
+    nstates = model.nstates
+    nsymbols = model.output_model.nsymbols if output == 'discrete' else 0
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError("dtype must be float64 or float32")
+    if weights is not None:
+        w = np.asarray(weights)
+        if w.ndim != 2 or w.shape[0] != nstates or not 1 <= w.shape[1] <= 8:
+            raise ValueError("weights must be (%d, Q) with 1 <= Q <= 8" % nstates)
+    device = engine_kwargs.pop('device', 0)
+    if engine_kwargs:
+        raise TypeError("unexpected keyword arguments: %s" % ", ".join(sorted(engine_kwargs)))
+    if lag > 1:
+        observations = lag_observations(observations, lag)
+    eng = Engine(device)
+    try:
+        if output == 'discrete':
+            obs = [np.asarray(o) for o in observations]
+            eng.set_observations('discrete', obs, nstates, nsymbols=nsymbols)
+        else:
+            eng.set_observations(output, [np.asarray(o, dtype=np.float64) for o in observations], nstates)
+        return eng.posterior_marginals(*model_tuple(model), weights=weights, dtype=dtype)
+    finally:
+        eng.close()

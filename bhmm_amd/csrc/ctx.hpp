@@ -106,6 +106,8 @@ struct bhmm_ctx {
         bool score_lazy = true;          // ... first pass on the lazily scaled kernel (option score_lazy; 0: sum every step)
         int post_W = 0;                  // bhmm_posterior_decode: warm-up fixed by the caller (option post_W; 0: measured)
         int post_ws_mb = 8192;           // ... budget of its alpha-row workspace in MiB (option post_ws_mb; 0: unbounded)
+        int marg_W = 0;                  // bhmm_posterior_marginals: warm-up fixed by the caller (option marg_W; 0: measured)
+        int marg_ws_mb = 8192;           // ... budget of its alpha-row workspace in MiB (option marg_ws_mb; 0: unbounded)
     } opt;
 
     // ---- loaded problem ----
@@ -211,6 +213,8 @@ struct bhmm_ctx {
         int score_W_max = 0;             // ... longest warm-up of its first pass at 9..128 states (0: no boundary, other paths)
         int post_fallbacks = 0;          // bhmm_posterior_decode: calls whose boundaries did not verify at the first warm-up
         int post_path = 0;               // ... first pass of the last call: 1 fused (k_post_sweep), 0 generic (E-step + gamma rows)
+        int marg_fallbacks = 0;          // bhmm_posterior_marginals: calls whose boundaries did not verify at the first warm-up
+        int marg_path = 0;               // ... first pass of the last call: 1 fused (k_marg_sweep), 0 generic (E-step + gamma rows)
     } last;
 
     // ---- not reset by bhmm_ctx_set_observations: they outlive the observation set ----
@@ -327,6 +331,14 @@ struct bhmm_ctx {
         bhmm::DevBuf<float> conf;
         bhmm::DevBuf<unsigned int> fails;
     } post;
+    // bhmm_posterior_marginals (marg_api.hip): its own buffers -- as PostBufs, the projection matrix V, and the
+    // result staged on the device when the caller's buffer is on the host (out); nothing else reads them
+    struct MargBufs {
+        bhmm::DevBuf<char> model, probe, out;
+        bhmm::DevBuf<double> Bt, ws, aentry, aexit, bassumed, bout, V;
+        bhmm::DevBuf<uint8_t> dead;
+        bhmm::DevBuf<unsigned int> fails;
+    } marg;
 
     // ---- pinned host buffers ----
     unsigned int *h_specres = nullptr; // pinned

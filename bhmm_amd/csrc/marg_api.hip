@@ -1,0 +1,282 @@
+// marg_api.hip -- bhmm_posterior_marginals: the posterior probability of every hidden state at every step of
+// every loaded trajectory, gamma_t(i), or its projection on up to 8 columns, as trajectory-major rows in
+// double or float, in a host buffer or left in a device buffer of the caller.  Kernels in marg_kernels.hpp;
+// DESIGN.md section 15.
+//
+// Up to 8 states, gaussian or discrete (the fused path, marg_path 1): k_marg_sweep -- the sweep of k_post_sweep
+// (restated as marg_sweep_lane, marg_kernels.hpp) with the emit policy MargRow -- over the E-step's chunk plan,
+// the alpha rows in a workspace of at most marg_ws_mb, then k_post_check over the boundary vectors of both directions.
+// Warm-up from the forgetting probe or the option marg_W.  Boundaries that do not verify: counted in
+// marg_fallbacks, the call runs again with twice the warm-up, and if they fail again it takes the generic path.
+//
+// Everything else (9 states and more, explicit pobs; marg_path 0): bhmm_estep with BHMM_FLAG_STORE_GAMMA
+// through its own entry point and protocol, then k_marg_rows_rm / k_marg_rows_ci over the stored rows.  That IS
+// an E-step for the context's state (statistics, carried boundaries, timers, stored gamma), exactly like a
+// caller's own.
+//
+// The fused path reads or writes nothing of the E-step's state and nothing of c->post.*: its buffers are
+// c->marg.*, the only other fields touched are opt.marg_* (read) and last.marg_*.  A host result is staged in
+// c->marg.out and crosses the link in ONE copy (a pageable buffer of 8 MiB or more is pinned for it).
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "host_common.hpp"
+#include "host_internal.hpp"
+#include "launch.hpp"
+#include "marg_kernels.hpp"
+#include "model_check.hpp"
+#include "post_host.hpp"
+
+namespace bhmm {
+namespace {
+
+struct Out {          // where the rows go on the device, and what they are
+    void *dev;        // [total][Qp] of double / float
+    const double *V;  // device copy of the projection, or nullptr
+    int Q;            // its columns (0: none)
+    int Qp;           // values per row
+    bool f32;
+};
+
+template <int N, int KIND>
+struct Fused {
+    // the sweep over every range of chunk groups and the check; *fails: boundaries out of tolerance
+    template <typename OT, bool PROJ>
+    static int pass(bhmm_ctx *c, const Model<N> *dm, int W, const double *dBt, const Out &o, unsigned int *fails)
+    {
+        auto &b = c->marg;
+        const int G = c->G, groups = c->Gp / 64;
+        const Chunks ch = chunks_of(c);
+        const size_t lds_bt = (size_t)c->M * score_bt_stride(N) * sizeof(double);
+        const bool bt_lds = KIND == EMIT_DISC && lds_bt <= POST_LDS_BT;
+        // alpha rows of one group, and how many groups the budget holds (at least one)
+        const size_t per_group = (size_t)c->Lmax * N * 64 * sizeof(double);
+        const size_t budget = (size_t)c->opt.marg_ws_mb << 20;
+        const int per_range =
+            budget == 0 ? groups : (int)std::min<size_t>(groups, std::max<size_t>(1, budget / per_group));
+        int rc;
+        if ((rc = b.ws.ensure((size_t)per_range * c->Lmax * N * 64)))
+            return rc;
+        BHMM_HIP(hipMemsetAsync(b.fails.p, 0, sizeof(unsigned int), c->stream));
+        auto *kern = bt_lds ? k_marg_sweep<N, KIND, true, OT, PROJ> : k_marg_sweep<N, KIND, false, OT, PROJ>;
+        for (int g0 = 0; g0 < groups; g0 += per_range)
+            BHMM_HIP(launch(kern, dim3(std::min(per_range, groups - g0)), dim3(64), bt_lds ? lds_bt : 0, c->stream, dm,
+                            W, ch, G, g0, c->d_offsets.p, c->d_obs_ci.p, c->d_obs_rm.p, dBt, c->M, b.ws.p,
+                            static_cast<OT *>(o.dev), o.V, o.Q, b.aentry.p, b.aexit.p, b.bassumed.p, b.bout.p,
+                            b.dead.p));
+        if (G > 1)
+            BHMM_HIP(launch(k_post_check<N>, dim3((G + 255) / 256), dim3(256), 0, c->stream, ch, G, b.aentry.p,
+                            b.aexit.p, b.bassumed.p, b.bout.p, b.dead.p, POST_TOL, b.fails.p));
+        BHMM_HIP(hipMemcpyAsync(fails, b.fails.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+        return BHMM_OK;
+    }
+
+    // *verified: the rows in o.dev stand
+    static int run(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                   const Out &o, bool *verified)
+    {
+        auto &b = c->marg;
+        const int M = c->M, n = c->n;
+        *verified = false;
+        int rc;
+        if ((rc = b.model.ensure(sizeof(Model<N>))) || (rc = b.aentry.ensure((size_t)c->Gp * N)) ||
+            (rc = b.aexit.ensure((size_t)c->Gp * N)) || (rc = b.bassumed.ensure((size_t)c->Gp * N)) ||
+            (rc = b.bout.ensure((size_t)c->Gp * N)) || (rc = b.dead.ensure(c->Gp)) || (rc = b.fails.ensure(1)) ||
+            (KIND == EMIT_DISC && (rc = b.Bt.ensure((size_t)M * N))))
+            return rc;
+        Model<N> m;
+        fill_model<N>(m, n, KIND, M, A, pi, par0, par1);
+        Model<N> *dm = reinterpret_cast<Model<N> *>(b.model.p);
+        std::vector<double> bt;
+        if (KIND == EMIT_DISC) {
+            bt.resize((size_t)M * N);
+            for (int i = 0; i < n; ++i)
+                for (int s = 0; s < M; ++s)
+                    bt[(size_t)s * N + i] = par0[(size_t)i * M + s];
+            BHMM_HIP(hipMemcpyAsync(b.Bt.p, bt.data(), bt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        }
+        BHMM_HIP(hipMemcpyAsync(dm, &m, sizeof(Model<N>), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream)); // (m and bt are temporaries)
+        int W = c->opt.marg_W;
+        if (W <= 0) {
+            if ((rc = post_probe<N, KIND>(c, b.probe, m, b.Bt.p, &W)))
+                return rc;
+            W = W > 0 ? W : POST_W_UNPROBED;
+        }
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            unsigned int fails = 0;
+            if (o.Q > 0)
+                rc = o.f32 ? pass<float, true>(c, dm, W, b.Bt.p, o, &fails)
+                           : pass<double, true>(c, dm, W, b.Bt.p, o, &fails);
+            else
+                rc = o.f32 ? pass<float, false>(c, dm, W, b.Bt.p, o, &fails)
+                           : pass<double, false>(c, dm, W, b.Bt.p, o, &fails);
+            if (rc)
+                return rc;
+            if (fails == 0) {
+                *verified = true;
+                return BHMM_OK;
+            }
+            if (attempt == 0)
+                ++c->last.marg_fallbacks; // boundaries that did not verify at the first warm-up
+            W = (int)std::min<int64_t>(2 * (int64_t)W, 1 << 30);
+        }
+        return BHMM_OK;
+    }
+};
+
+template <int N>
+int run_n(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, const Out &o,
+          bool *verified)
+{
+    return c->kind == EMIT_GAUSS ? Fused<N, EMIT_GAUSS>::run(c, A, pi, par0, par1, o, verified)
+                                 : Fused<N, EMIT_DISC>::run(c, A, pi, par0, par1, o, verified);
+}
+
+// the generic path: an E-step that stores gamma, then one kernel that converts / projects the rows in the
+// layout the kernel family of this context stores them in
+template <typename OT>
+int gamma_rows(bhmm_ctx *c, const Out &o)
+{
+    OT *out = static_cast<OT *>(o.dev);
+    if (c->total == 0)
+        return BHMM_OK;
+    if (c->wide || c->gen) { // trajectory-major rows of n
+        const int64_t threads = o.Q > 0 ? c->total : c->total * c->n;
+        BHMM_HIP(launch(k_marg_rows_rm<OT>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, c->stream,
+                        c->d_gamma_ci.p, c->n, c->total, o.V, o.Q, out));
+        return BHMM_OK;
+    }
+    const Chunks ch = chunks_of(c); // (the plan the E-step ended on)
+    const dim3 grid((c->G + 255) / 256), block(256);
+    if (c->N == 2)
+        BHMM_HIP(launch(k_marg_rows_ci<2, OT>, grid, block, 0, c->stream, ch, c->G, c->d_gamma_ci.p, c->n, o.V, o.Q, out));
+    else if (c->N == 4)
+        BHMM_HIP(launch(k_marg_rows_ci<4, OT>, grid, block, 0, c->stream, ch, c->G, c->d_gamma_ci.p, c->n, o.V, o.Q, out));
+    else
+        BHMM_HIP(launch(k_marg_rows_ci<8, OT>, grid, block, 0, c->stream, ch, c->G, c->d_gamma_ci.p, c->n, o.V, o.Q, out));
+    return BHMM_OK;
+}
+
+int generic(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, const Out &o)
+{
+    int rc;
+    if ((rc = bhmm_estep(c, A, pi, par0, par1, nullptr, BHMM_FLAG_STORE_GAMMA)) ||
+        (rc = bhmm_estep_fetch(c, nullptr, nullptr))) // (waits; a non-finite log-likelihood is its error)
+        return rc;
+    return o.f32 ? gamma_rows<float>(c, o) : gamma_rows<double>(c, o);
+}
+
+// the staged rows to the caller's host buffer in one copy, as deliver_paths does it: a pageable buffer of
+// 8 MiB or more is pinned for the transfer, one the caller pinned is used as it is
+int deliver(bhmm_ctx *c, void *host, const void *dev, size_t bytes)
+{
+    if (bytes == 0)
+        return BHMM_OK;
+    hipPointerAttribute_t attr;
+    const bool caller_pinned = hipPointerGetAttributes(&attr, host) == hipSuccess && attr.type == hipMemoryTypeHost;
+    (void)hipGetLastError();
+    const bool pinned = !caller_pinned && bytes >= ((size_t)8 << 20) &&
+                        hipHostRegister(host, bytes, hipHostRegisterDefault) == hipSuccess;
+    if (!pinned)
+        (void)hipGetLastError();
+    hipError_t ce = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (ce == hipSuccess)
+        ce = hipStreamSynchronize(c->stream);
+    if (pinned)
+        (void)hipHostUnregister(host);
+    BHMM_HIP(ce);
+    return BHMM_OK;
+}
+
+} // namespace
+} // namespace bhmm
+
+using namespace bhmm;
+
+extern "C" {
+
+int bhmm_posterior_marginals(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                             const double *V, int Q, void *out, int flags)
+{
+    int rc = enter_model_call(c, A && pi && out, "A / pi / out == NULL", true, par0, par1);
+    if (rc)
+        return rc;
+    if (flags & ~(BHMM_MARG_F32 | BHMM_MARG_DEVICE))
+        return invalid_arg("bhmm_posterior_marginals: unknown flag");
+    if ((V == nullptr) != (Q == 0) || Q < 0 || Q > MARG_QMAX)
+        return invalid_arg("bhmm_posterior_marginals: V with 1 <= Q <= 8 columns, or V == NULL and Q == 0");
+    const bool on_dev = (flags & BHMM_MARG_DEVICE) != 0;
+    if (on_dev && (reinterpret_cast<uintptr_t>(out) & 15))
+        return invalid_arg("bhmm_posterior_marginals: a device buffer must be aligned to 16 bytes");
+    for (int e = 0; e < c->n * Q; ++e)
+        if (!std::isfinite(V[e]))
+            return invalid_arg("bhmm_posterior_marginals: V has a non-finite entry");
+    if ((rc = check_models(c, "bhmm_posterior_marginals", 1, A, pi, par0, par1)))
+        return rc;
+    auto &b = c->marg;
+    Out o;
+    o.f32 = (flags & BHMM_MARG_F32) != 0;
+    o.Q = Q;
+    o.Qp = Q > 0 ? Q : c->n;
+    o.V = nullptr;
+    const size_t bytes = (size_t)c->total * o.Qp * (o.f32 ? sizeof(float) : sizeof(double));
+    if (!on_dev && (rc = b.out.ensure(std::max<size_t>(bytes, 16)))) // (BHMM_ERR_NO_MEM: nothing is truncated)
+        return rc;
+    o.dev = on_dev ? out : static_cast<void *>(b.out.p);
+    if (Q > 0) {
+        if ((rc = b.V.ensure((size_t)std::max(c->n, 8) * MARG_QMAX)))
+            return rc;
+        BHMM_HIP(hipMemcpyAsync(b.V.p, V, (size_t)c->n * Q * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream)); // (V may be a temporary of the caller's)
+        o.V = b.V.p;
+    }
+    const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
+    const bool fused = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;
+    c->last.marg_path = fused ? 1 : 0;
+    bool verified = false;
+    if (fused) {
+        switch (c->n) {
+        case 1:
+            rc = run_n<1>(c, A, pi, par0, par1, o, &verified);
+            break;
+        case 2:
+            rc = run_n<2>(c, A, pi, par0, par1, o, &verified);
+            break;
+        case 3:
+            rc = run_n<3>(c, A, pi, par0, par1, o, &verified);
+            break;
+        case 4:
+            rc = run_n<4>(c, A, pi, par0, par1, o, &verified);
+            break;
+        case 5:
+            rc = run_n<5>(c, A, pi, par0, par1, o, &verified);
+            break;
+        case 6:
+            rc = run_n<6>(c, A, pi, par0, par1, o, &verified);
+            break;
+        case 7:
+            rc = run_n<7>(c, A, pi, par0, par1, o, &verified);
+            break;
+        default:
+            rc = run_n<8>(c, A, pi, par0, par1, o, &verified);
+            break;
+        }
+        if (rc)
+            return rc;
+    }
+    if (!verified && (rc = generic(c, A, pi, par0, par1, o)))
+        return rc;
+    if (on_dev) { // the rows are where the caller wants them, ordered on the context's stream
+        return BHMM_OK;
+    }
+    return deliver(c, out, o.dev, bytes);
+}
+
+} // extern "C"

@@ -30,14 +30,11 @@
 #include "host_internal.hpp"
 #include "launch.hpp"
 #include "model_check.hpp"
+#include "post_host.hpp"
 #include "post_kernels.hpp"
 
 namespace bhmm {
 namespace {
-
-constexpr double POST_TOL = 1e-11;         // boundary check: componentwise relative (the E-step's spec_tol default)
-constexpr int POST_W_UNPROBED = 288;       // warm-up when the trajectories are too short to probe (the E-step's)
-constexpr size_t POST_LDS_BT = 16 * 1024;  // B^T staged in LDS up to this size
 
 // the results on the device to the caller: the paths as deliver_paths does, the confidences after them
 int deliver(bhmm_ctx *c, void *path, int path_u8, float *conf)
@@ -50,53 +47,6 @@ int deliver(bhmm_ctx *c, void *path, int path_u8, float *conf)
 
 template <int N, int KIND>
 struct Fused {
-    // warm-up from the forgetting curve: the probe's reading as bhmm_score takes it (chains within 1e-13
-    // from then on, + 15 %, doubled), here the larger of the forward and the backward direction.  0 where
-    // the trajectories are too short to probe
-    static int probe(bhmm_ctx *c, const Model<N> &m, const double *dBt, int *W)
-    {
-        *W = 0;
-        const int64_t maxT = longest_traj(c);
-        const int Wmax = (int)std::min<int64_t>(1024, maxT / 2) / 4 * 4;
-        if (Wmax < 32)
-            return BHMM_OK;
-        std::vector<int> longk;
-        for (int k = 0; k < c->K; ++k)
-            if (c->offsets[k + 1] - c->offsets[k] >= Wmax)
-                longk.push_back(k);
-        const int P = 256;
-        std::vector<int64_t> starts(P);
-        for (int i = 0; i < P; ++i) {
-            const int k = longk[i % longk.size()];
-            const int64_t room = c->offsets[k + 1] - c->offsets[k] - Wmax + 1;
-            const int64_t rep = i / (int64_t)longk.size(), reps = (P + longk.size() - 1) / longk.size();
-            starts[i] = c->offsets[k] + (room - 1) * rep / std::max<int64_t>(reps - 1, 1);
-        }
-        const size_t curve_words = 2 * (size_t)Wmax; // forward | backward
-        int rc;
-        if ((rc = c->post.probe.ensure(P * sizeof(int64_t) + curve_words * sizeof(unsigned int))))
-            return rc;
-        int64_t *d_starts = reinterpret_cast<int64_t *>(c->post.probe.p);
-        unsigned int *d_curve = reinterpret_cast<unsigned int *>(d_starts + P);
-        BHMM_HIP(hipMemcpyAsync(d_starts, starts.data(), P * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        BHMM_HIP(hipMemsetAsync(d_curve, 0, curve_words * sizeof(unsigned int), c->stream));
-        BHMM_HIP(launch(k_forget_probe<N, KIND>, dim3((2 * P + 63) / 64), dim3(64), 0, c->stream, m, c->d_obs_rm.p,
-                        KIND == EMIT_DISC ? dBt : nullptr, d_starts, P, Wmax, d_curve));
-        std::vector<float> curve(curve_words);
-        BHMM_HIP(hipMemcpyAsync(curve.data(), d_curve, curve.size() * sizeof(float), hipMemcpyDeviceToHost,
-                                c->stream));
-        BHMM_HIP(hipStreamSynchronize(c->stream));
-        const float target = (float)(0.01 * POST_TOL);
-        int last = -1;
-        for (int dir = 0; dir < 2; ++dir)
-            for (int w = 0; w < Wmax; ++w)
-                if (curve[(size_t)dir * Wmax + w] >= target)
-                    last = std::max(last, w);
-        const int w = (int)std::ceil(1.15 * (last + 2));
-        *W = 2 * std::min(std::max(16, (w + 3) / 4 * 4), Wmax);
-        return BHMM_OK;
-    }
-
     // the sweep over every range of chunk groups and the check; *fails: boundaries out of tolerance
     template <typename PT>
     static int pass(bhmm_ctx *c, const Model<N> *dm, int W, const double *dBt, bool want_conf, unsigned int *fails)
@@ -157,7 +107,7 @@ struct Fused {
         BHMM_HIP(hipStreamSynchronize(c->stream)); // (m and bt are temporaries)
         int W = c->opt.post_W;
         if (W <= 0) {
-            if ((rc = probe(c, m, b.Bt.p, &W)))
+            if ((rc = post_probe<N, KIND>(c, b.probe, m, b.Bt.p, &W)))
                 return rc;
             W = W > 0 ? W : POST_W_UNPROBED;
         }

@@ -282,17 +282,8 @@ class Engine(object):
                                       _lib.dp(logL)))
         return logL
 
-    # -- posterior decoding ----------------------------------------------------------------
-    def posterior_decode(self, A, pi, par0=None, par1=None, confidence=False, out=None):
-        """Posterior (maximum-posterior-marginal) decoding (bhmm_posterior_decode): for every step the
-        state of largest gamma_t(i) -- the lowest index on exactly equal gamma -- and, with `confidence`,
-        that largest gamma.  Returns a list of per-trajectory uint8 views (int32 above 256 states) like
-        viterbi, or (paths, conf) with per-trajectory float32 views.  out: None, or a C-contiguous numpy
-        array of sum(T_k) elements of that path dtype which receives the concatenated paths (the views
-        then point into it).  Up to 8 states (gaussian, discrete) one fused kernel decodes without storing
-        gamma and leaves the state of E-step, Viterbi, sampling and scoring calls untouched
-        (get_option("post_path") == 1; options post_W, post_ws_mb, read-only post_fallbacks); 9 states
-        and more and explicit pobs run an E-step that stores gamma and count as one (post_path 0)."""
+    def _check_model(self, A, pi, par0, par1):
+        """Shapes of one model against the loaded observations, before any native call."""
         if self.kind is None:
             raise ValueError("no observations loaded")
         n, M = self.nstates, self.nsymbols
@@ -308,6 +299,22 @@ class Engine(object):
                 raise ValueError("discrete emissions need B")
             if np.shape(par0) != (n, M):
                 raise ValueError("B must be (%d, %d)" % (n, M))
+
+    # -- posterior decoding ----------------------------------------------------------------
+    def posterior_decode(self, A, pi, par0=None, par1=None, confidence=False, out=None):
+        """Posterior (maximum-posterior-marginal) decoding (bhmm_posterior_decode): for every step the
+        state of largest gamma_t(i) -- the lowest index on exactly equal gamma -- and, with `confidence`,
+        that largest gamma.  Returns a list of per-trajectory uint8 views (int32 above 256 states) like
+        viterbi, or (paths, conf) with per-trajectory float32 views.  out: None, or a C-contiguous numpy
+        array of sum(T_k) elements of that path dtype which receives the concatenated paths (the views
+        then point into it).  Up to 8 states (gaussian, discrete) one fused kernel decodes without storing
+        gamma and leaves the state of E-step, Viterbi, sampling and scoring calls untouched
+        (get_option("post_path") == 1; options post_W, post_ws_mb, read-only post_fallbacks); 9 states
+        and more and explicit pobs run an E-step that stores gamma and count as one (post_path 0)."""
+        if self.kind is None:
+            raise ValueError("no observations loaded")
+        n = self.nstates
+        self._check_model(A, pi, par0, par1)
         total = int(self.offsets[-1])
         dtype = np.uint8 if n <= 256 else np.int32
         if out is None:
@@ -326,6 +333,67 @@ class Engine(object):
         if not confidence:
             return paths
         return paths, [conf[self.offsets[k]:self.offsets[k + 1]] for k in range(K)]
+
+    # -- posterior state probabilities ---------------------------------------------------
+    def posterior_marginals(self, A, pi, par0=None, par1=None, weights=None, dtype=np.float64, out=None):
+        """Posterior state probabilities gamma_t(i) of every step of every loaded trajectory under one model
+        (bhmm_posterior_marginals).  Returns a list of per-trajectory views (T_k, Q') into ONE array of
+        sum(T_k) rows: Q' = nstates, or with `weights` (an (nstates, Q) matrix, 1 <= Q <= 8) Q' = Q and the
+        rows are gamma_t @ weights, accumulated over the states in ascending order in fp64.  dtype: float64
+        or float32 (the rounded float64 result).  out: None (a numpy array is allocated), a C-contiguous numpy
+        array of that dtype and sum(T_k) * Q' elements, an object with data_ptr() / is_cuda (a torch tensor: on
+        this engine's GPU the kernels write it directly and nothing crosses the link, pinned host memory is
+        copied at link rate), or an integer device address on this engine's GPU, aligned to 16 bytes (as
+        estep_launch takes stats_dev; then None is returned).  Rows left on the device are complete in the
+        order of the engine's stream (sync()).  Up to 8 states (gaussian, discrete) one fused kernel leaves
+        the state of every other call untouched (get_option("marg_path") == 1; options marg_W, marg_ws_mb,
+        read-only marg_fallbacks); 9 states and more and explicit pobs run an E-step that stores gamma and
+        count as one (marg_path 0)."""
+        self._check_model(A, pi, par0, par1)
+        n = self.nstates
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError("dtype must be float64 or float32, not %s" % dtype.name)
+        V, Q = None, 0
+        if weights is not None:
+            V = np.ascontiguousarray(weights, dtype=np.float64)
+            if V.ndim != 2 or V.shape[0] != n or not 1 <= V.shape[1] <= 8:
+                raise ValueError("weights must be (%d, Q) with 1 <= Q <= 8, not %r" % (n, np.shape(weights)))
+            if not np.all(np.isfinite(V)):
+                raise ValueError("weights has a non-finite entry")
+            Q = V.shape[1]
+        Qp = Q if Q else n
+        total = int(self.offsets[-1])
+        flags = _lib.MARG_F32 if dtype == np.float32 else 0
+        rows = None
+        if out is None:
+            out = np.empty((total, Qp), dtype=dtype)
+        if isinstance(out, np.ndarray):
+            if out.dtype != dtype or out.size != total * Qp or not out.flags.c_contiguous:
+                raise ValueError("out must be a C-contiguous %s array of sum(T_k) * %d = %d elements"
+                                 % (dtype.name, Qp, total * Qp))
+            ptr, rows = out.ctypes.data, out.reshape(total, Qp)
+        elif hasattr(out, 'data_ptr'):
+            if out.numel() != total * Qp or out.element_size() != dtype.itemsize or not out.is_contiguous() \
+                    or not out.is_floating_point():
+                raise ValueError("out must be a contiguous %s tensor of sum(T_k) * %d = %d elements"
+                                 % (dtype.name, Qp, total * Qp))
+            if out.is_cuda:
+                if out.device.index != self.device:
+                    raise ValueError("out lives on another GPU than this engine")
+                flags |= _lib.MARG_DEVICE
+            ptr, rows = out.data_ptr(), out.view(total, Qp)
+        else:
+            ptr = int(out)
+            flags |= _lib.MARG_DEVICE
+        if (flags & _lib.MARG_DEVICE) and ptr % 16:
+            raise ValueError("a device buffer must be aligned to 16 bytes")
+        A, pi, p0, p1 = self._model_ptrs(A, pi, par0, par1)
+        _lib.check(self._L.bhmm_posterior_marginals(self._h, A, pi, p0, p1, _lib.dp(V), Q,
+                                                    ctypes.c_void_p(int(ptr)), flags))
+        if rows is None:
+            return None
+        return [rows[self.offsets[k]:self.offsets[k + 1]] for k in range(len(self.lengths))]
 
     # -- paths ---------------------------------------------------------------------------
     def viterbi(self, A, pi, par0=None, par1=None):

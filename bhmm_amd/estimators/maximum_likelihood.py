@@ -139,6 +139,7 @@ class MaximumLikelihoodEstimator(object):
         self._store_gamma = store_gamma
         self._gammas = None
         self._last = None
+        self._estep_model = None     # (A, pi, par0, par1) of the last E-step, copies
         self._mstep = None
         hidden.set_implementation(config.kernel)
         self._hmm.output_model.set_implementation(config.kernel)
@@ -198,14 +199,33 @@ class MaximumLikelihoodEstimator(object):
 
     @property
     def hidden_state_probabilities(self):
-        """gamma per trajectory (T_k, N), fetched from the device on demand (construct the
-        estimator with store_gamma=True).  With several ranks only the local trajectories are
-        filled, the others are None."""
+        """gamma per trajectory (T_k, N) under the model of the last E-step -- the model before the last
+        M-step, as in the reference (maximum_likelihood.py:207-209).  With store_gamma=True the rows every
+        E-step stored are fetched from the device; otherwise they are computed on demand in one call
+        (posterior_marginals), which costs the EM run nothing.  With several ranks only the local
+        trajectories are filled, the others are None."""
         if not self._store_gamma:
-            raise RuntimeError('construct the estimator with store_gamma=True to keep gamma')
+            return self.posterior_marginals()
         out = [None] * self._nobs
         for j, k in enumerate(self._mine):
             out[k] = self._engine.gamma(j)
+        return out
+
+    def posterior_marginals(self, weights=None, dtype=np.float64):
+        """Posterior state probabilities of the estimator's observations under the parameters of the last
+        E-step (Engine.posterior_marginals): a list in the caller's trajectory order of (T_k, N) arrays, or
+        with `weights` ((N, Q), 1 <= Q <= 8) of (T_k, Q) arrays gamma @ weights; dtype float64 or float32.
+        With a process_group every rank fills the trajectories it holds and the entries of the others are
+        None (local_trajectories lists the ones filled); there is no collective.  Up to 8 states the EM state
+        of the engine stays untouched; more states run one more E-step that stores gamma."""
+        if self._estep_model is None:
+            raise RuntimeError('no E-step has run yet: call fit() or em_step() first')
+        out = [None] * self._nobs
+        if self._mine:
+            A, pi, par0, par1 = self._estep_model
+            rows = self._engine.posterior_marginals(A, pi, par0, par1, weights=weights, dtype=dtype)
+            for j, k in enumerate(self._mine):
+                out[k] = rows[j]
         return out
 
     @property
@@ -244,6 +264,8 @@ class MaximumLikelihoodEstimator(object):
         par0, par1 = om.parameters()
         eng, comm = self._engine, self._comm
         A, pi = self._hmm.transition_matrix, self._hmm.initial_distribution
+        # kept for hidden_state_probabilities: gamma is that of the model BEFORE the following M-step
+        self._estep_model = tuple(None if x is None else np.array(x, dtype=np.float64) for x in (A, pi, par0, par1))
         kw = {'single': True} if single else {}
         if not comm.active and hasattr(eng, 'estep_fetch_packed'):
             # (the per-trajectory log-likelihoods stay on the device: the EM loop needs their sum,

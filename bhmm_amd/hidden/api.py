@@ -14,7 +14,7 @@ from .. import _lib
 from ..util import config
 
 __all__ = ['set_implementation', 'forward', 'backward', 'state_probabilities', 'state_counts',
-           'transition_counts', 'viterbi', 'sample_path', 'posterior_decode']
+           'transition_counts', 'viterbi', 'sample_path', 'posterior_decode', 'posterior_marginals']
 
 __IMPL_HIP__ = 2
 __impl__ = __IMPL_HIP__
@@ -199,3 +199,30 @@ def posterior_decode(A, pobs, pi, confidence=False):
     if confidence:
         return res[0][0], res[1][0]
     return res[0]
+
+
+def posterior_marginals(A, pobs, pi, weights=None, dtype=np.float64):
+    """Posterior state probabilities of one trajectory given its pobs rows, in one call: the (T, N) array the
+    reference obtains from forward, backward and state_probabilities (hidden/api.py:65-188), or with `weights`
+    ((N, Q), 1 <= Q <= 8) the (T, Q) array gamma @ weights; dtype float64 or float32.  Explicit pobs take the
+    generic path of bhmm_posterior_marginals: one E-step that stores gamma, then a kernel over its rows."""
+    _check_dtype()
+    A_, p_, pi_ = _lib.f64(A), _lib.f64(pobs), _lib.f64(pi)
+    N = A_.shape[0] if A_.ndim == 2 else -1
+    if A_.ndim != 2 or A_.shape != (N, N) or pi_.shape != (N,) or p_.ndim != 2 or p_.shape[1] != N:
+        raise ValueError('A must be (N, N), pi (N,) and pobs (T, N)')
+    if p_.shape[0] < 1:
+        raise ValueError('pobs has no rows')
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError('dtype must be float64 or float32')
+    if weights is not None:
+        w = np.asarray(weights)
+        if w.ndim != 2 or w.shape[0] != N or not 1 <= w.shape[1] <= 8:
+            raise ValueError('weights must be (N, Q) with 1 <= Q <= 8')
+    from ..engine import Engine
+    eng = Engine(0)
+    try:
+        eng.set_observations('explicit', [p_], N)
+        return eng.posterior_marginals(A_, pi_, weights=weights, dtype=dtype)[0]
+    finally:
+        eng.close()

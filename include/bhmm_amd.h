@@ -156,7 +156,8 @@ int bhmm_estep(bhmm_ctx *ctx, const double *A, const double *pi, const double *p
  * place; later fetches of the same launch do not look at the buffer's counts again. */
 int bhmm_estep_fetch(bhmm_ctx *ctx, double *stats, double *logL_k);
 /* After an E-step run with BHMM_FLAG_STORE_GAMMA: copy gamma of trajectory k, (T_k,N)
- * row-major, to the host. */
+ * row-major, to the host.  (All trajectories at once, in float or projected, for any model and without
+ * an E-step: bhmm_posterior_marginals.) */
 int bhmm_get_gamma(bhmm_ctx *ctx, int k, double *gamma);
 
 /* log-likelihood of every loaded trajectory under each of nmodels models, stacked:
@@ -195,6 +196,37 @@ int bhmm_score(bhmm_ctx *ctx, int nmodels, const double *A, const double *pi,
    (BHMM_ERR_NO_MEM if they are not there) and returns BHMM_ERR_NONFINITE where bhmm_estep_fetch would. */
 int bhmm_posterior_decode(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0,
                           const double *par1, void *path, int path_u8, float *conf);
+
+/* Posterior state probabilities of every step of every loaded trajectory under ONE model (A, pi, par0, par1 as
+   for bhmm_posterior_decode; validated the same way): the quantity bhmm_posterior_decode takes the argmax of.
+   out is trajectory-major, out[(offset_k + t) * Q' + q]:
+     V == NULL, Q == 0 : Q' = N, the row is gamma_t(0 .. N-1) and sums to one;
+     V[N*Q] row-major, 1 <= Q <= 8 : Q' = Q, the row is sum_i gamma_t(i) * V[i*Q + q], accumulated over i in
+       ASCENDING order in fp64 (fused multiply-add) -- set memberships, state means, any few columns.
+   flags: BHMM_MARG_F32    rows of float instead of double (the conversion is the last operation: the float
+                           result is the rounded double result);
+          BHMM_MARG_DEVICE out is a device pointer on the context's device, aligned to 16 bytes: the kernels
+                           write it directly, nothing is copied, and the rows are complete in the order of
+                           the context's stream (bhmm_ctx_sync, or work enqueued on bhmm_ctx_stream).
+   Without BHMM_MARG_DEVICE out is a host buffer of total * Q' values: the rows are staged on the device
+   (BHMM_ERR_NO_MEM if they do not fit; nothing is truncated) and cross the link in ONE copy -- pass pinned
+   memory for the full link rate, a pageable buffer of 8 MiB or more is pinned for the duration of the copy --
+   and the call is synchronous.
+   Up to 8 states (gaussian, discrete): the fused forward-backward sweep of bhmm_posterior_decode with the
+   normalised row (or its projection) as last stage, the same verified warm-up boundaries and retry protocol;
+   nothing of the state that E-step, Viterbi, sampling, scoring and decoding calls use is read or written and no
+   gamma row is kept beyond out.  Options: marg_W (warm-up in steps, 0 = measured), marg_ws_mb (budget of the
+   alpha-row workspace in MiB, default 8192, 0 = unbounded; the result does not depend on it); read-only
+   marg_fallbacks (calls whose boundaries did not verify at the first warm-up: they run again with twice the
+   warm-up, then take the generic path) and marg_path (first pass of the last call: 1 fused, 0 generic).
+   Generic path (9 states and more, explicit pobs): a bhmm_estep with BHMM_FLAG_STORE_GAMMA followed by one
+   kernel over the stored rows.  It counts as an E-step for the context (last statistics, carried boundaries,
+   timers, stored gamma) exactly like the caller's own, needs total * N * 8 bytes for gamma besides the staged
+   result and returns BHMM_ERR_NONFINITE where bhmm_estep_fetch would. */
+#define BHMM_MARG_F32 1
+#define BHMM_MARG_DEVICE 2
+int bhmm_posterior_marginals(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0,
+                             const double *par1, const double *V, int Q, void *out, int flags);
 
 /* Viterbi paths of all trajectories (maximum_likelihood.py:332-352).  paths is a host
  * buffer of sum_k T_k int32, trajectory-concatenated like obs. */
