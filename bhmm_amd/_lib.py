@@ -32,6 +32,8 @@ FLAG_SINGLE = 2        # the caller accepts a single-precision E-step (up to 8 s
 
 MARG_F32 = 1           # bhmm_posterior_marginals: rows of float
 MARG_DEVICE = 2        # ... out is a device pointer
+FILT_F32 = 1           # bhmm_filter: both outputs of float
+FILT_DEVICE = 2        # ... both outputs are device pointers
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -80,6 +82,8 @@ SIGNATURES = {
                                              c_void_p, ctypes.c_int, c_void_p]),
     "bhmm_posterior_marginals": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                                 c_double_p, ctypes.c_int, c_void_p, ctypes.c_int]),
+    "bhmm_filter": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int,
+                                   c_void_p, c_void_p, ctypes.c_int]),
     "bhmm_viterbi_batch": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,
                                           c_double_p, c_int32_p]),
     "bhmm_viterbi_batch_u8": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,

@@ -249,3 +249,47 @@ def posterior_marginals(observations, model, lag=1, weights=None, dtype=np.float
         return eng.posterior_marginals(*model_tuple(model), weights=weights, dtype=dtype)
     finally:
         eng.close()
+
+
+def filter_states(observations, model, lag=1, weights=None, dtype=np.float64, probabilities=True, increments=True,
+                  **engine_kwargs):
+    """Filtered state probabilities and per-step likelihood of `observations` under one HMM (bhmm_filter):
+    (rows, logc) with per trajectory a (T_k, nstates) array of P(s_t = i | o_0 .. o_t) -- or with `weights`
+    ((nstates, Q), 1 <= Q <= 8) the (T_k, Q) array of their projection -- and a (T_k,) array of
+    log p(o_t | o_0 .. o_{t-1}), whose sum is the log-likelihood; None for the one not asked for.  dtype float64
+    or float32.  The arrays are views into one array each.  lag > 1 works on the lagged views
+    (lag_observations), one result per view.  Gaussian and discrete models of up to 8 states run parallel over
+    time; more states run the serial recursion per trajectory.  engine_kwargs: device (default 0)."""
+    from .engine import Engine
+    from .estimators.maximum_likelihood import model_tuple
+    if not isinstance(model, HMM):
+        raise TypeError("model must be an HMM object")
+    if len(observations) == 0:
+        raise ValueError("no observations")
+    output = model.output_model.model_type
+    nstates = model.nstates
+    nsymbols = model.output_model.nsymbols if output == 'discrete' else 0
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError("dtype must be float64 or float32")
+    if not probabilities and not increments:
+        raise ValueError("neither probabilities nor increments asked for")
+    if weights is not None:
+        w = np.asarray(weights)
+        if w.ndim != 2 or w.shape[0] != nstates or not 1 <= w.shape[1] <= 8:
+            raise ValueError("weights must be (%d, Q) with 1 <= Q <= 8" % nstates)
+    device = engine_kwargs.pop('device', 0)
+    if engine_kwargs:
+        raise TypeError("unexpected keyword arguments: %s" % ", ".join(sorted(engine_kwargs)))
+    if lag > 1:
+        observations = lag_observations(observations, lag)
+    eng = Engine(device)
+    try:
+        if output == 'discrete':
+            obs = [np.asarray(o) for o in observations]
+            eng.set_observations('discrete', obs, nstates, nsymbols=nsymbols)
+        else:
+            eng.set_observations(output, [np.asarray(o, dtype=np.float64) for o in observations], nstates)
+        return eng.filter_states(*model_tuple(model), weights=weights, dtype=dtype, probabilities=probabilities,
+                                 increments=increments)
+    finally:
+        eng.close()

@@ -1546,7 +1546,9 @@ int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
         if (!(value >= 0.0) || value > (double)(1 << 30))
             return invalid_arg("marg_ws_mb outside [0, 2^30]");
         c->opt.marg_ws_mb = (int)value;
-    } else
+    } else if (n == "filter_W") // bhmm_filter only: fixed warm-up (0: measured); no E-step state changes
+        c->opt.filter_W = std::max(0, (int)value);
+    else
         return invalid_arg("unknown or read-only option: " + n);
     return BHMM_OK;
 }
@@ -1677,6 +1679,12 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->last.marg_fallbacks;
     else if (n == "marg_path") // ... first pass of the last call: 1 fused kernel (up to 8 states), 0 E-step + gamma rows
         *value = c->last.marg_path;
+    else if (n == "filter_W")
+        *value = c->opt.filter_W;
+    else if (n == "filter_fallbacks") // bhmm_filter: calls whose boundaries did not verify at the first warm-up
+        *value = c->last.filter_fallbacks;
+    else if (n == "filter_path") // ... first pass of the last call: 1 fused kernel (up to 8 states), 0 serial kernel
+        *value = c->last.filter_path;
     else if (n == "score_path") // ... first pass of the last call: 0 serial kernel, 1 chunk kernels (N <= 8), 2 k_score_wide, 3 k_score_tile
         *value = c->last.score_path;
     else

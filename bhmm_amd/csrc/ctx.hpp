@@ -108,6 +108,7 @@ struct bhmm_ctx {
         int post_ws_mb = 8192;           // ... budget of its alpha-row workspace in MiB (option post_ws_mb; 0: unbounded)
         int marg_W = 0;                  // bhmm_posterior_marginals: warm-up fixed by the caller (option marg_W; 0: measured)
         int marg_ws_mb = 8192;           // ... budget of its alpha-row workspace in MiB (option marg_ws_mb; 0: unbounded)
+        int filter_W = 0;                // bhmm_filter: warm-up fixed by the caller (option filter_W; 0: measured)
     } opt;
 
     // ---- loaded problem ----
@@ -215,6 +216,8 @@ struct bhmm_ctx {
         int post_path = 0;               // ... first pass of the last call: 1 fused (k_post_sweep), 0 generic (E-step + gamma rows)
         int marg_fallbacks = 0;          // bhmm_posterior_marginals: calls whose boundaries did not verify at the first warm-up
         int marg_path = 0;               // ... first pass of the last call: 1 fused (k_marg_sweep), 0 generic (E-step + gamma rows)
+        int filter_fallbacks = 0;        // bhmm_filter: calls whose boundaries did not verify at the first warm-up
+        int filter_path = 0;             // ... first pass of the last call: 1 fused (k_filter_sweep), 0 serial (k_filter_serial)
     } last;
 
     // ---- not reset by bhmm_ctx_set_observations: they outlive the observation set ----
@@ -339,6 +342,17 @@ struct bhmm_ctx {
         bhmm::DevBuf<uint8_t> dead;
         bhmm::DevBuf<unsigned int> fails;
     } marg;
+    // bhmm_filter (filter_api.hip): its own buffers -- model, B^T, boundary vectors, the chunks whose exit vector
+    // is all zero and per trajectory the first of them, failure counter, probe curve, the projection matrix V, the
+    // parameters of the serial path, and the two results staged on the device when the caller's buffers are on
+    // the host (rows, logc); nothing else reads them
+    struct FiltBufs {
+        bhmm::DevBuf<char> model, probe, rows, logc;
+        bhmm::DevBuf<double> Bt, aentry, aexit, V, par;
+        bhmm::DevBuf<uint8_t> dead;
+        bhmm::DevBuf<int32_t> first_dead;
+        bhmm::DevBuf<unsigned int> fails;
+    } filt;
 
     // ---- pinned host buffers ----
     unsigned int *h_specres = nullptr; // pinned

@@ -1,0 +1,351 @@
+// filter_api.hip -- bhmm_filter: the filtered state probabilities P(s_t = i | o_0 .. o_t) of every step of every
+// loaded trajectory (or their projection on up to 8 columns) and the one-step predictive log-densities
+// log p(o_t | o_0 .. o_{t-1}), in double or float, in host buffers or left in device buffers of the caller.
+// Kernels in filter_kernels.hpp; DESIGN.md section 16.
+//
+// Up to 8 states, gaussian or discrete (the fused path, filter_path 1): k_filter_sweep -- the forward sweep of
+// k_score_fwd with the row and the increment as last stage -- over the E-step's chunk plan, then
+// k_filter_first_dead (per trajectory the first chunk whose exit vector is all zero), k_filter_check over the
+// boundary vectors up to there and k_filter_bury (zero rows and -inf in every chunk after it).  Warm-up from the
+// forward reading of the forgetting probe, as bhmm_score takes it, or the option filter_W.  Boundaries that do
+// not verify: counted in filter_fallbacks, the call runs again with twice the warm-up, and if they fail again it
+// takes the serial path.
+//
+// Everything else (9 states and more, explicit pobs; filter_path 0): k_filter_serial, one workgroup per
+// trajectory.
+//
+// Nothing here reads or writes the state other calls use: the buffers are c->filt.*, the only other fields
+// touched are opt.filter_W (read) and last.filter_*.  Host results are staged in c->filt.rows / c->filt.logc and
+// cross the link in ONE copy each, after the boundaries verified (a pageable buffer of 8 MiB or more is pinned
+// for it).
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "filter_kernels.hpp"
+#include "host_common.hpp"
+#include "host_internal.hpp"
+#include "launch.hpp"
+#include "model_check.hpp"
+
+namespace bhmm {
+namespace {
+
+constexpr double FILTER_TOL = 1e-11;         // boundary check: componentwise relative (bhmm_score's)
+constexpr int FILTER_W_UNPROBED = 288;       // warm-up when the trajectories are too short to probe (bhmm_score's)
+constexpr size_t FILTER_LDS_BT = 16 * 1024;  // B^T staged in LDS up to this size
+
+struct Out {          // where the results go on the device, and what they are
+    void *rows;       // [total][Qp] of double / float, or nullptr
+    void *logc;       // [total] of double / float, or nullptr
+    const double *V;  // device copy of the projection, or nullptr
+    int Q;            // its columns (0: none)
+    int Qp;           // values per row
+    bool f32;
+};
+
+// warm-up from the forgetting curve, the reading bhmm_score takes (score_api.hip, Fast::probe): forward chains
+// within 0.01 of the check's tolerance from then on, + 15 %, doubled.  0 where the trajectories are too short to
+// probe
+template <int N, int KIND>
+int filter_probe(bhmm_ctx *c, const Model<N> &m, const double *dBt, int *W)
+{
+    *W = 0;
+    const int64_t maxT = longest_traj(c);
+    const int Wmax = (int)std::min<int64_t>(1024, maxT / 2) / 4 * 4;
+    if (Wmax < 32)
+        return BHMM_OK;
+    std::vector<int> longk;
+    for (int k = 0; k < c->K; ++k)
+        if (c->offsets[k + 1] - c->offsets[k] >= Wmax)
+            longk.push_back(k);
+    const int P = 256;
+    std::vector<int64_t> starts(P);
+    for (int i = 0; i < P; ++i) {
+        const int k = longk[i % longk.size()];
+        const int64_t room = c->offsets[k + 1] - c->offsets[k] - Wmax + 1;
+        const int64_t rep = i / (int64_t)longk.size(), reps = (P + longk.size() - 1) / longk.size();
+        starts[i] = c->offsets[k] + (room - 1) * rep / std::max<int64_t>(reps - 1, 1);
+    }
+    const size_t curve_words = 2 * (size_t)Wmax; // forward | backward (the kernel's layout)
+    int rc;
+    if ((rc = c->filt.probe.ensure(P * sizeof(int64_t) + curve_words * sizeof(unsigned int))))
+        return rc;
+    int64_t *d_starts = reinterpret_cast<int64_t *>(c->filt.probe.p);
+    unsigned int *d_curve = reinterpret_cast<unsigned int *>(d_starts + P);
+    BHMM_HIP(hipMemcpyAsync(d_starts, starts.data(), P * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemsetAsync(d_curve, 0, curve_words * sizeof(unsigned int), c->stream));
+    BHMM_HIP(launch(k_forget_probe<N, KIND>, dim3((2 * P + 63) / 64), dim3(64), 0, c->stream, m, c->d_obs_rm.p,
+                    KIND == EMIT_DISC ? dBt : nullptr, d_starts, P, Wmax, d_curve));
+    std::vector<float> curve(Wmax); // the forward direction: the first Wmax entries
+    BHMM_HIP(hipMemcpyAsync(curve.data(), d_curve, curve.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream));
+    const float target = (float)(0.01 * FILTER_TOL);
+    int last = -1;
+    for (int w = 0; w < Wmax; ++w)
+        if (curve[w] >= target)
+            last = w;
+    const int w = (int)std::ceil(1.15 * (last + 2));
+    *W = 2 * std::min(std::max(16, (w + 3) / 4 * 4), Wmax);
+    return BHMM_OK;
+}
+
+template <int N, int KIND>
+struct Fused {
+    template <typename OT, bool PROJ, bool WANT_LOGC>
+    static auto kernel(bool bt_lds)
+    {
+        return bt_lds ? k_filter_sweep<N, KIND, true, OT, PROJ, WANT_LOGC>
+                      : k_filter_sweep<N, KIND, false, OT, PROJ, WANT_LOGC>;
+    }
+
+    // the sweep, the first dead chunk of every trajectory, the check and the fix-up; *fails: boundaries out of
+    // tolerance
+    template <typename OT>
+    static int pass(bhmm_ctx *c, const Model<N> *dm, int W, const double *dBt, const Out &o, unsigned int *fails)
+    {
+        auto &b = c->filt;
+        const int G = c->G, groups = c->Gp / 64;
+        const Chunks ch = chunks_of(c);
+        const size_t lds_bt = (size_t)c->M * score_bt_stride(N) * sizeof(double);
+        const bool bt_lds = KIND == EMIT_DISC && lds_bt <= FILTER_LDS_BT;
+        const bool proj = o.Q > 0 && o.rows != nullptr;
+        BHMM_HIP(hipMemsetAsync(b.fails.p, 0, sizeof(unsigned int), c->stream));
+        auto *kern = proj ? (o.logc ? kernel<OT, true, true>(bt_lds) : kernel<OT, true, false>(bt_lds))
+                          : (o.logc ? kernel<OT, false, true>(bt_lds) : kernel<OT, false, false>(bt_lds));
+        BHMM_HIP(launch(kern, dim3(groups), dim3(64), bt_lds ? lds_bt : 0, c->stream, dm, W, ch, G, c->d_obs_ci.p,
+                        c->d_obs_rm.p, dBt, c->M, static_cast<OT *>(o.rows), o.V, o.Q, static_cast<OT *>(o.logc),
+                        b.aentry.p, b.aexit.p, b.dead.p));
+        if (G > 1) { // (one chunk: no boundary, nothing after a dead chunk)
+            BHMM_HIP(launch(k_filter_first_dead, dim3(c->K), dim3(64), 0, c->stream, c->d_traj_c0.p, b.dead.p,
+                            b.first_dead.p));
+            BHMM_HIP(launch(k_filter_check<N>, dim3((G + 255) / 256), dim3(256), 0, c->stream, ch, G, b.aentry.p,
+                            b.aexit.p, b.first_dead.p, FILTER_TOL, b.fails.p));
+            BHMM_HIP(launch(k_filter_bury<OT>, dim3((G + 255) / 256), dim3(256), 0, c->stream, ch, G, b.first_dead.p,
+                            static_cast<OT *>(o.rows), o.Qp, static_cast<OT *>(o.logc)));
+        }
+        BHMM_HIP(hipMemcpyAsync(fails, b.fails.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+        return BHMM_OK;
+    }
+
+    // *verified: the results in o stand
+    static int run(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                   const Out &o, bool *verified)
+    {
+        auto &b = c->filt;
+        const int M = c->M, n = c->n;
+        *verified = false;
+        int rc;
+        if ((rc = b.model.ensure(sizeof(Model<N>))) || (rc = b.aentry.ensure((size_t)c->Gp * N)) ||
+            (rc = b.aexit.ensure((size_t)c->Gp * N)) || (rc = b.dead.ensure(c->Gp)) ||
+            (rc = b.first_dead.ensure(std::max(c->K, 1))) || (rc = b.fails.ensure(1)) ||
+            (KIND == EMIT_DISC && (rc = b.Bt.ensure((size_t)M * N))))
+            return rc;
+        Model<N> m;
+        fill_model<N>(m, n, KIND, M, A, pi, par0, par1);
+        Model<N> *dm = reinterpret_cast<Model<N> *>(b.model.p);
+        std::vector<double> bt;
+        if (KIND == EMIT_DISC) {
+            bt.resize((size_t)M * N);
+            for (int i = 0; i < n; ++i)
+                for (int s = 0; s < M; ++s)
+                    bt[(size_t)s * N + i] = par0[(size_t)i * M + s];
+            BHMM_HIP(hipMemcpyAsync(b.Bt.p, bt.data(), bt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        }
+        BHMM_HIP(hipMemcpyAsync(dm, &m, sizeof(Model<N>), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream)); // (m and bt are temporaries)
+        int W = c->opt.filter_W;
+        if (W <= 0) {
+            if ((rc = filter_probe<N, KIND>(c, m, b.Bt.p, &W)))
+                return rc;
+            W = W > 0 ? W : FILTER_W_UNPROBED;
+        }
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            unsigned int fails = 0;
+            rc = o.f32 ? pass<float>(c, dm, W, b.Bt.p, o, &fails) : pass<double>(c, dm, W, b.Bt.p, o, &fails);
+            if (rc)
+                return rc;
+            if (fails == 0) {
+                *verified = true;
+                return BHMM_OK;
+            }
+            if (attempt == 0)
+                ++c->last.filter_fallbacks; // boundaries that did not verify at the first warm-up
+            W = (int)std::min<int64_t>(2 * (int64_t)W, 1 << 30);
+        }
+        return BHMM_OK;
+    }
+};
+
+template <int N>
+int run_n(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, const Out &o,
+          bool *verified)
+{
+    return c->kind == EMIT_GAUSS ? Fused<N, EMIT_GAUSS>::run(c, A, pi, par0, par1, o, verified)
+                                 : Fused<N, EMIT_DISC>::run(c, A, pi, par0, par1, o, verified);
+}
+
+// the serial path: parallel over trajectories only
+template <typename OT>
+int serial(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, const Out &o)
+{
+    const int n = c->n, K = c->K;
+    if (n > SCORE_SERIAL_R * 1024)
+        return invalid_arg("bhmm_filter: more than 4096 states");
+    const size_t np0 = c->kind == EMIT_GAUSS ? (size_t)n : (c->kind == EMIT_DISC ? (size_t)n * c->M : 0);
+    const size_t np1 = c->kind == EMIT_GAUSS ? (size_t)n : 0;
+    auto &b = c->filt;
+    int rc;
+    if ((rc = b.par.ensure((size_t)n * n + n + np0 + np1)))
+        return rc;
+    double *dA = b.par.p, *dpi = dA + (size_t)n * n, *dp0 = dpi + n, *dp1 = dp0 + np0;
+    BHMM_HIP(hipMemcpyAsync(dA, A, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(dpi, pi, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (np0)
+        BHMM_HIP(hipMemcpyAsync(dp0, par0, np0 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (np1)
+        BHMM_HIP(hipMemcpyAsync(dp1, par1, np1 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream)); // (the caller's arrays may be temporaries)
+    if (K == 0)
+        return BHMM_OK;
+    const int bd = std::min(1024, (n + 63) / 64 * 64);
+    const size_t lds = ((size_t)n + 16) * sizeof(double);
+    OT *rows = static_cast<OT *>(o.rows), *logc = static_cast<OT *>(o.logc);
+    const void *obs = c->d_obs_rm.p;
+    hipError_t e;
+    if (c->kind == EMIT_GAUSS)
+        e = launch(k_filter_serial<EMIT_GAUSS, OT>, dim3(K), dim3(bd), lds, c->stream, n, c->M, c->d_offsets.p, obs, dA,
+                   dpi, dp0, dp1, o.V, o.Q, rows, logc);
+    else if (c->kind == EMIT_DISC)
+        e = launch(k_filter_serial<EMIT_DISC, OT>, dim3(K), dim3(bd), lds, c->stream, n, c->M, c->d_offsets.p, obs, dA,
+                   dpi, dp0, nullptr, o.V, o.Q, rows, logc);
+    else
+        e = launch(k_filter_serial<EMIT_EXPL, OT>, dim3(K), dim3(bd), lds, c->stream, n, c->M, c->d_offsets.p, obs, dA,
+                   dpi, nullptr, nullptr, o.V, o.Q, rows, logc);
+    BHMM_HIP(e);
+    return BHMM_OK;
+}
+
+// a staged result to the caller's host buffer in one copy: a pageable buffer of 8 MiB or more is pinned for the
+// transfer, one the caller pinned is used as it is
+int deliver(bhmm_ctx *c, void *host, const void *dev, size_t bytes)
+{
+    if (bytes == 0)
+        return BHMM_OK;
+    hipPointerAttribute_t attr;
+    const bool caller_pinned = hipPointerGetAttributes(&attr, host) == hipSuccess && attr.type == hipMemoryTypeHost;
+    (void)hipGetLastError();
+    const bool pinned = !caller_pinned && bytes >= ((size_t)8 << 20) &&
+                        hipHostRegister(host, bytes, hipHostRegisterDefault) == hipSuccess;
+    if (!pinned)
+        (void)hipGetLastError();
+    hipError_t ce = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (ce == hipSuccess)
+        ce = hipStreamSynchronize(c->stream);
+    if (pinned)
+        (void)hipHostUnregister(host);
+    BHMM_HIP(ce);
+    return BHMM_OK;
+}
+
+} // namespace
+} // namespace bhmm
+
+using namespace bhmm;
+
+extern "C" {
+
+int bhmm_filter(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                const double *V, int Q, void *rows, void *logc, int flags)
+{
+    int rc = enter_model_call(c, A && pi && (rows || logc), "A / pi == NULL, or rows and logc both NULL", true, par0,
+                              par1);
+    if (rc)
+        return rc;
+    if (flags & ~(BHMM_FILT_F32 | BHMM_FILT_DEVICE))
+        return invalid_arg("bhmm_filter: unknown flag");
+    if ((V == nullptr) != (Q == 0) || Q < 0 || Q > MARG_QMAX)
+        return invalid_arg("bhmm_filter: V with 1 <= Q <= 8 columns, or V == NULL and Q == 0");
+    const bool on_dev = (flags & BHMM_FILT_DEVICE) != 0;
+    if (on_dev && ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(logc)) & 15))
+        return invalid_arg("bhmm_filter: a device buffer must be aligned to 16 bytes");
+    for (int e = 0; e < c->n * Q; ++e)
+        if (!std::isfinite(V[e]))
+            return invalid_arg("bhmm_filter: V has a non-finite entry");
+    if ((rc = check_models(c, "bhmm_filter", 1, A, pi, par0, par1)))
+        return rc;
+    auto &b = c->filt;
+    Out o;
+    o.f32 = (flags & BHMM_FILT_F32) != 0;
+    o.Q = Q;
+    o.Qp = Q > 0 ? Q : c->n;
+    o.V = nullptr;
+    const size_t esz = o.f32 ? sizeof(float) : sizeof(double);
+    const size_t rows_bytes = rows ? (size_t)c->total * o.Qp * esz : 0, logc_bytes = logc ? (size_t)c->total * esz : 0;
+    if (!on_dev) { // (BHMM_ERR_NO_MEM: nothing is truncated)
+        if (rows && (rc = b.rows.ensure(std::max<size_t>(rows_bytes, 16))))
+            return rc;
+        if (logc && (rc = b.logc.ensure(std::max<size_t>(logc_bytes, 16))))
+            return rc;
+    }
+    o.rows = !rows ? nullptr : (on_dev ? rows : static_cast<void *>(b.rows.p));
+    o.logc = !logc ? nullptr : (on_dev ? logc : static_cast<void *>(b.logc.p));
+    if (Q > 0 && rows) {
+        if ((rc = b.V.ensure((size_t)c->n * Q)))
+            return rc;
+        BHMM_HIP(hipMemcpyAsync(b.V.p, V, (size_t)c->n * Q * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream)); // (V may be a temporary of the caller's)
+        o.V = b.V.p;
+    }
+    const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
+    const bool fused = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;
+    c->last.filter_path = fused ? 1 : 0;
+    bool verified = false;
+    if (fused) {
+        switch (c->n) {
+        case 1:
+            rc = run_n<1>(c, A, pi, par0, par1, o, &verified);
+            break;
+        case 2:
+            rc = run_n<2>(c, A, pi, par0, par1, o, &verified);
+            break;
+        case 3:
+            rc = run_n<3>(c, A, pi, par0, par1, o, &verified);
+            break;
+        case 4:
+            rc = run_n<4>(c, A, pi, par0, par1, o, &verified);
+            break;
+        case 5:
+            rc = run_n<5>(c, A, pi, par0, par1, o, &verified);
+            break;
+        case 6:
+            rc = run_n<6>(c, A, pi, par0, par1, o, &verified);
+            break;
+        case 7:
+            rc = run_n<7>(c, A, pi, par0, par1, o, &verified);
+            break;
+        default:
+            rc = run_n<8>(c, A, pi, par0, par1, o, &verified);
+            break;
+        }
+        if (rc)
+            return rc;
+    }
+    if (!verified && (rc = o.f32 ? serial<float>(c, A, pi, par0, par1, o) : serial<double>(c, A, pi, par0, par1, o)))
+        return rc;
+    if (on_dev) // the results are where the caller wants them, ordered on the context's stream
+        return BHMM_OK;
+    if (rows && (rc = deliver(c, rows, o.rows, rows_bytes)))
+        return rc;
+    if (logc && (rc = deliver(c, logc, o.logc, logc_bytes)))
+        return rc;
+    BHMM_HIP(hipStreamSynchronize(c->stream)); // (synchronous also when there was nothing to copy)
+    return BHMM_OK;
+}
+
+} // extern "C"

@@ -395,6 +395,89 @@ class Engine(object):
             return None
         return [rows[self.offsets[k]:self.offsets[k + 1]] for k in range(len(self.lengths))]
 
+    # -- filtered state probabilities ----------------------------------------------------
+    def _filter_out(self, out, what, total, width, dtype):
+        """(address, 2-d view or None, on this engine's GPU) of one output of filter_states"""
+        if out is None:
+            out = np.empty((total, width) if what == 'out' else total, dtype=dtype)
+        shape = (total, width) if what == 'out' else (total,)
+        if isinstance(out, np.ndarray):
+            if out.dtype != dtype or out.size != total * width or not out.flags.c_contiguous:
+                raise ValueError("%s must be a C-contiguous %s array of %d elements" % (what, dtype.name, total * width))
+            return out.ctypes.data, out.reshape(shape), False
+        if hasattr(out, 'data_ptr'):
+            if out.numel() != total * width or out.element_size() != dtype.itemsize or not out.is_contiguous() \
+                    or not out.is_floating_point():
+                raise ValueError("%s must be a contiguous %s tensor of %d elements" % (what, dtype.name, total * width))
+            if out.is_cuda and out.device.index != self.device:
+                raise ValueError("%s lives on another GPU than this engine" % what)
+            return out.data_ptr(), out.view(*shape), bool(out.is_cuda)
+        return int(out), None, True
+
+    def filter_states(self, A, pi, par0=None, par1=None, weights=None, dtype=np.float64, probabilities=True,
+                      increments=True, out=None, out_increments=None):
+        """Filtered state probabilities P(s_t = i | o_0 .. o_t) of every step of every loaded trajectory under one
+        model, and the one-step predictive log-densities log p(o_t | o_0 .. o_{t-1}) whose sum is the
+        log-likelihood (bhmm_filter).  Returns (rows, logc): rows a list of per-trajectory views (T_k, Q') into
+        ONE array of sum(T_k) rows -- Q' = nstates, or with `weights` (an (nstates, Q) matrix, 1 <= Q <= 8)
+        Q' = Q and the rows are alpha^_t @ weights, accumulated over the states in ascending order in fp64 --
+        and logc a list of per-trajectory views (T_k,) into one array; None for the one not asked for
+        (probabilities / increments; at least one).  logc[k][0] = log sum_i pi_i p_0(i).  From the first step of
+        probability zero on, the rows of a trajectory are zero and its logc -inf.  dtype: float64 or float32
+        (the rounded float64 result), for both.  out / out_increments: None (numpy arrays are allocated), a
+        C-contiguous numpy array of that dtype, an object with data_ptr() / is_cuda (a torch tensor), or an
+        integer device address on this engine's GPU aligned to 16 bytes (then None stands in the result); both
+        on the host or both on this engine's GPU.  Results left on the device are complete in the order of the
+        engine's stream (sync()).  Up to 8 states (gaussian, discrete) one chunk-parallel forward sweep with
+        verified boundaries (get_option("filter_path") == 1; option filter_W, read-only filter_fallbacks); 9
+        states and more and explicit pobs run the serial recursion, one workgroup per trajectory (filter_path
+        0).  No other call's state is touched."""
+        self._check_model(A, pi, par0, par1)
+        n = self.nstates
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError("dtype must be float64 or float32, not %s" % dtype.name)
+        if not probabilities and not increments:
+            raise ValueError("neither probabilities nor increments asked for")
+        if (not probabilities and out is not None) or (not increments and out_increments is not None):
+            raise ValueError("a buffer was passed for an output that is not asked for")
+        V, Q = None, 0
+        if weights is not None:
+            V = np.ascontiguousarray(weights, dtype=np.float64)
+            if V.ndim != 2 or V.shape[0] != n or not 1 <= V.shape[1] <= 8:
+                raise ValueError("weights must be (%d, Q) with 1 <= Q <= 8, not %r" % (n, np.shape(weights)))
+            if not np.all(np.isfinite(V)):
+                raise ValueError("weights has a non-finite entry")
+            Q = V.shape[1]
+        Qp = Q if Q else n
+        total = int(self.offsets[-1])
+        rptr = lptr = 0
+        rows = logc = None
+        where = []
+        if probabilities:
+            rptr, rows, dev = self._filter_out(out, 'out', total, Qp, dtype)
+            where.append(dev)
+        if increments:
+            lptr, logc, dev = self._filter_out(out_increments, 'out_increments', total, 1, dtype)
+            where.append(dev)
+        if len(set(where)) > 1:
+            raise ValueError("out and out_increments must both be on the host or both on this engine's GPU")
+        flags = _lib.FILT_F32 if dtype == np.float32 else 0
+        if where[0]:
+            flags |= _lib.FILT_DEVICE
+            if rptr % 16 or lptr % 16:
+                raise ValueError("a device buffer must be aligned to 16 bytes")
+        A, pi, p0, p1 = self._model_ptrs(A, pi, par0, par1)
+        _lib.check(self._L.bhmm_filter(self._h, A, pi, p0, p1, _lib.dp(V) if probabilities else None,
+                                       Q if probabilities else 0, ctypes.c_void_p(int(rptr)) if probabilities else None,
+                                       ctypes.c_void_p(int(lptr)) if increments else None, flags))
+        K = len(self.lengths)
+        if rows is not None:
+            rows = [rows[self.offsets[k]:self.offsets[k + 1]] for k in range(K)]
+        if logc is not None:
+            logc = [logc[self.offsets[k]:self.offsets[k + 1]] for k in range(K)]
+        return rows, logc
+
     # -- paths ---------------------------------------------------------------------------
     def viterbi(self, A, pi, par0=None, par1=None):
         A, pi, p0, p1 = self._model_ptrs(A, pi, par0, par1)

@@ -228,6 +228,31 @@ class MaximumLikelihoodEstimator(object):
                 out[k] = rows[j]
         return out
 
+    def filter_states(self, weights=None, dtype=np.float64, probabilities=True, increments=True):
+        """Filtered state probabilities and per-step likelihood of the estimator's observations under the
+        parameters of the last E-step (Engine.filter_states): (rows, logc), each a list in the caller's
+        trajectory order -- (T_k, N) arrays, or with `weights` ((N, Q), 1 <= Q <= 8) (T_k, Q) arrays, and (T_k,)
+        arrays of log p(o_t | o_0 .. o_{t-1}) -- or None when not asked for; dtype float64 or float32.  With a
+        process_group every rank fills the trajectories it holds and the entries of the others are None
+        (local_trajectories lists the ones filled); there is no collective.  The EM state of the engine stays
+        untouched."""
+        if self._estep_model is None:
+            raise RuntimeError('no E-step has run yet: call fit() or em_step() first')
+        if not probabilities and not increments:
+            raise ValueError('neither probabilities nor increments asked for')
+        rows = [None] * self._nobs if probabilities else None
+        logc = [None] * self._nobs if increments else None
+        if self._mine:
+            A, pi, par0, par1 = self._estep_model
+            r, l = self._engine.filter_states(A, pi, par0, par1, weights=weights, dtype=dtype,
+                                              probabilities=probabilities, increments=increments)
+            for j, k in enumerate(self._mine):
+                if probabilities:
+                    rows[k] = r[j]
+                if increments:
+                    logc[k] = l[j]
+        return rows, logc
+
     @property
     def local_trajectories(self):
         """Indices of the trajectories this rank holds (all of them in a single process)."""

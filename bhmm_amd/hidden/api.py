@@ -14,7 +14,8 @@ from .. import _lib
 from ..util import config
 
 __all__ = ['set_implementation', 'forward', 'backward', 'state_probabilities', 'state_counts',
-           'transition_counts', 'viterbi', 'sample_path', 'posterior_decode', 'posterior_marginals']
+           'transition_counts', 'viterbi', 'sample_path', 'posterior_decode', 'posterior_marginals',
+           'filter_states']
 
 __IMPL_HIP__ = 2
 __impl__ = __IMPL_HIP__
@@ -226,3 +227,35 @@ def posterior_marginals(A, pobs, pi, weights=None, dtype=np.float64):
         return eng.posterior_marginals(A_, pi_, weights=weights, dtype=dtype)[0]
     finally:
         eng.close()
+
+
+def filter_states(A, pobs, pi, weights=None, dtype=np.float64, probabilities=True, increments=True):
+    """Filtered state probabilities and per-step likelihood of one trajectory given its pobs rows, in one call:
+    (rows, logc) with the (T, N) array the reference's forward returns as alpha -- or with `weights` ((N, Q),
+    1 <= Q <= 8) the (T, Q) array alpha @ weights -- and the (T,) array log p(o_t | o_0 .. o_{t-1}), whose sum is
+    forward's log-likelihood; None for the one not asked for.  dtype float64 or float32.  Explicit pobs take the
+    serial path of bhmm_filter."""
+    _check_dtype()
+    A_, p_, pi_ = _lib.f64(A), _lib.f64(pobs), _lib.f64(pi)
+    N = A_.shape[0] if A_.ndim == 2 else -1
+    if A_.ndim != 2 or A_.shape != (N, N) or pi_.shape != (N,) or p_.ndim != 2 or p_.shape[1] != N:
+        raise ValueError('A must be (N, N), pi (N,) and pobs (T, N)')
+    if p_.shape[0] < 1:
+        raise ValueError('pobs has no rows')
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError('dtype must be float64 or float32')
+    if not probabilities and not increments:
+        raise ValueError('neither probabilities nor increments asked for')
+    if weights is not None:
+        w = np.asarray(weights)
+        if w.ndim != 2 or w.shape[0] != N or not 1 <= w.shape[1] <= 8:
+            raise ValueError('weights must be (N, Q) with 1 <= Q <= 8')
+    from ..engine import Engine
+    eng = Engine(0)
+    try:
+        eng.set_observations('explicit', [p_], N)
+        rows, logc = eng.filter_states(A_, pi_, weights=weights, dtype=dtype, probabilities=probabilities,
+                                       increments=increments)
+    finally:
+        eng.close()
+    return (rows[0] if rows is not None else None), (logc[0] if logc is not None else None)

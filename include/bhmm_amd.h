@@ -228,6 +228,37 @@ int bhmm_posterior_decode(bhmm_ctx *ctx, const double *A, const double *pi, cons
 int bhmm_posterior_marginals(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0,
                              const double *par1, const double *V, int Q, void *out, int flags);
 
+/* Filtered state probabilities and one-step predictive log-densities of every step of every loaded trajectory
+   under ONE model (A, pi, par0, par1 as for bhmm_posterior_marginals; validated the same way): the forward pass
+   of bhmm_score with its rows handed out.
+     rows[(offset_k + t) * Q' + q], trajectory-major as bhmm_posterior_marginals writes them:
+       V == NULL, Q == 0 : Q' = N, the row is P(s_t = . | o_0 .. o_t) and sums to one;
+       V[N*Q] row-major, 1 <= Q <= 8 : Q' = Q, the row is sum_i P(s_t = i | o_0 .. o_t) * V[i*Q + q], accumulated
+         over i in ASCENDING order in fp64 (fused multiply-add);
+     logc[offset_k + t] = log p(o_t | o_0 .. o_{t-1}); logc[offset_k] = log sum_i pi_i p_0(i) (pi is not
+       normalised, as in the reference's forward); their sum over a trajectory is its log-likelihood.
+   Either output may be NULL, not both.  From the first step of a trajectory whose probability is zero on, its
+   rows are zero and its logc -inf; the steps before are the ordinary ones.  Gaussian emissions follow
+   bhmm_score: an all-zero emission row or a NaN observation counts as a row of ones.
+   flags: BHMM_FILT_F32    both outputs are float (the conversion is the last operation);
+          BHMM_FILT_DEVICE both outputs are device pointers on the context's device, aligned to 16 bytes: the
+                           kernels write them directly and they are complete in the order of the context's
+                           stream.
+   Without BHMM_FILT_DEVICE the outputs are host buffers: they are staged on the device (BHMM_ERR_NO_MEM if they
+   do not fit; nothing is truncated), each crosses the link in ONE copy after the boundaries verified -- a
+   pageable buffer of 8 MiB or more is pinned for the duration of its copy -- and the call is synchronous.
+   Up to 8 states (gaussian, discrete): one forward sweep over the chunk plan with verified warm-up boundaries
+   (filter_path 1).  Options: filter_W (warm-up in steps, 0 = measured); read-only filter_fallbacks (calls whose
+   boundaries did not verify at the first warm-up: they run again with twice the warm-up, then take the serial
+   path) and filter_path (first pass of the last call: 1 fused, 0 serial).  9 states and more and explicit pobs:
+   the serial recursion, one workgroup per trajectory (filter_path 0; at most 4096 states).
+   Nothing of the state that E-step, Viterbi, sampling, scoring, decoding and marginals calls use is read or
+   written. */
+#define BHMM_FILT_F32 1
+#define BHMM_FILT_DEVICE 2
+int bhmm_filter(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0, const double *par1,
+                const double *V, int Q, void *rows, void *logc, int flags);
+
 /* Viterbi paths of all trajectories (maximum_likelihood.py:332-352).  paths is a host
  * buffer of sum_k T_k int32, trajectory-concatenated like obs. */
 int bhmm_viterbi_batch(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0,
