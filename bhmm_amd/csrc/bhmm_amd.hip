@@ -1548,7 +1548,15 @@ int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
         c->opt.marg_ws_mb = (int)value;
     } else if (n == "filter_W") // bhmm_filter only: fixed warm-up (0: measured); no E-step state changes
         c->opt.filter_W = std::max(0, (int)value);
-    else
+    else if (n == "filter_seglen") { // ... 9..64 states: segment length of its plan from the next call on (0: automatic)
+        if (!(value >= 0 && value <= (1 << 30)))
+            return invalid_arg("filter_seglen outside [0, 2^30]");
+        c->opt.filter_seglen = ((int)value + 3) & ~3;
+    } else if (n == "filter_parallel") { // ... the time-parallel path: 0 never, 1 always when eligible, -1 automatic
+        if (value != 0.0 && value != 1.0 && value != -1.0)
+            return invalid_arg("filter_parallel must be -1, 0 or 1");
+        c->opt.filter_parallel = (int)value;
+    } else
         return invalid_arg("unknown or read-only option: " + n);
     return BHMM_OK;
 }
@@ -1683,8 +1691,16 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->opt.filter_W;
     else if (n == "filter_fallbacks") // bhmm_filter: calls whose boundaries did not verify at the first warm-up
         *value = c->last.filter_fallbacks;
-    else if (n == "filter_path") // ... first pass of the last call: 1 fused kernel (up to 8 states), 0 serial kernel
+    else if (n == "filter_path") // ... first pass of the last call: 2 k_filter_wide (9..64 states), 1 fused kernel (up to 8 states), 0 serial kernel
         *value = c->last.filter_path;
+    else if (n == "filter_seglen")
+        *value = c->opt.filter_seglen;
+    else if (n == "filter_parallel")
+        *value = c->opt.filter_parallel;
+    else if (n == "filter_segments") // ... segments of the filter plan the last call ran on (0: another path)
+        *value = c->last.filter_segments;
+    else if (n == "filter_wide_min_total") // ... steps from which filter_parallel = -1 takes the time-parallel path
+        *value = (double)FILTER_WIDE_MIN_TOTAL;
     else if (n == "score_path") // ... first pass of the last call: 0 serial kernel, 1 chunk kernels (N <= 8), 2 k_score_wide, 3 k_score_tile
         *value = c->last.score_path;
     else

@@ -109,6 +109,9 @@ struct bhmm_ctx {
         int marg_W = 0;                  // bhmm_posterior_marginals: warm-up fixed by the caller (option marg_W; 0: measured)
         int marg_ws_mb = 8192;           // ... budget of its alpha-row workspace in MiB (option marg_ws_mb; 0: unbounded)
         int filter_W = 0;                // bhmm_filter: warm-up fixed by the caller (option filter_W; 0: measured)
+        int filter_seglen = 0;           // bhmm_filter, 9..64 states: segment length of its plan (option filter_seglen; 0: automatic)
+        int filter_parallel = -1;        // ... the time-parallel path: 0 never, 1 always when eligible, -1 automatic
+                                         // (eligible and at least FILTER_WIDE_MIN_TOTAL steps; option filter_parallel)
     } opt;
 
     // ---- loaded problem ----
@@ -180,6 +183,11 @@ struct bhmm_ctx {
         int score_ntraj = 0;             // ... trajectories with at least one step (nseg == ntraj: no boundary)
         int score_seglen_opt = 0;        // ... opt.score_seglen it was made for
         int score_ntiles = 0;            // ... 65..128 states: tiles of 16 segments (k_score_tile)
+        // bhmm_filter, 9..64 states: its own segment plan (tables in filt.seg_*), made at the first eligible filter
+        // call on these observations from the offsets, the state count and the device alone -- never after a check
+        int filt_nseg = 0;               // segments of the plan (0: not made yet)
+        int filt_ntraj = 0;              // ... trajectories with at least one step (nseg == ntraj: no boundary)
+        int filt_seglen_opt = 0;         // ... opt.filter_seglen it was made for
     } ds;
 
     // ---- counters and diagnostics of the last calls (bhmm_ctx_get_option) ----
@@ -217,7 +225,9 @@ struct bhmm_ctx {
         int marg_fallbacks = 0;          // bhmm_posterior_marginals: calls whose boundaries did not verify at the first warm-up
         int marg_path = 0;               // ... first pass of the last call: 1 fused (k_marg_sweep), 0 generic (E-step + gamma rows)
         int filter_fallbacks = 0;        // bhmm_filter: calls whose boundaries did not verify at the first warm-up
-        int filter_path = 0;             // ... first pass of the last call: 1 fused (k_filter_sweep), 0 serial (k_filter_serial)
+        int filter_path = 0;             // ... first pass of the last call: 2 time segments (k_filter_wide, 9..64 states),
+                                         // 1 fused (k_filter_sweep, up to 8 states), 0 serial (k_filter_serial)
+        int filter_segments = 0;         // ... segments of the filter plan it ran on (0: no such plan)
     } last;
 
     // ---- not reset by bhmm_ctx_set_observations: they outlive the observation set ----
@@ -345,13 +355,17 @@ struct bhmm_ctx {
     // bhmm_filter (filter_api.hip): its own buffers -- model, B^T, boundary vectors, the chunks whose exit vector
     // is all zero and per trajectory the first of them, failure counter, probe curve, the projection matrix V, the
     // parameters of the serial path, and the two results staged on the device when the caller's buffers are on
-    // the host (rows, logc); nothing else reads them
+    // the host (rows, logc); 9..64 states: the model's parameter block and the tables of the plan ds.filt_nseg
+    // counts (dead / first_dead then count segments); nothing else reads them
     struct FiltBufs {
         bhmm::DevBuf<char> model, probe, rows, logc;
         bhmm::DevBuf<double> Bt, aentry, aexit, V, par;
         bhmm::DevBuf<uint8_t> dead;
         bhmm::DevBuf<int32_t> first_dead;
         bhmm::DevBuf<unsigned int> fails;
+        bhmm::DevBuf<double> wpar;
+        bhmm::DevBuf<int32_t> seg_traj, seg_len, seg_traj0;
+        bhmm::DevBuf<int64_t> seg_t0;
     } filt;
 
     // ---- pinned host buffers ----

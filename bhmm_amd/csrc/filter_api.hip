@@ -11,11 +11,19 @@
 // not verify: counted in filter_fallbacks, the call runs again with twice the warm-up, and if they fail again it
 // takes the serial path.
 //
-// Everything else (9 states and more, explicit pobs; filter_path 0): k_filter_serial, one workgroup per
-// trajectory.
+// 9 to 64 states, gaussian or discrete (the time-parallel path, filter_path 2): k_filter_wide
+// (filter_wide_kernels.hpp; compiled in filter_wide.hip) -- the forward sweep of k_score_wide that sums every
+// step, with the row and the increment as last stage -- over a segment plan that belongs to filtering alone
+// (filter_plan: a function of the offsets, the state count and the device; option filter_seglen), then
+// k_filter_first_dead, k_filter_seg_check and k_filter_seg_bury.  W from the forward chains of k_wide_probe as
+// bhmm_score reads them, or filter_W; the same protocol.  Taken when the option filter_parallel is 1, or -1 (the
+// default) and the set has at least FILTER_WIDE_MIN_TOTAL steps (host_internal.hpp).
 //
-// Nothing here reads or writes the state other calls use: the buffers are c->filt.*, the only other fields
-// touched are opt.filter_W (read) and last.filter_*.  Host results are staged in c->filt.rows / c->filt.logc and
+// Everything else (65 states and more, explicit pobs, filter_parallel 0 or a small set; filter_path 0):
+// k_filter_serial, one workgroup per trajectory.
+//
+// Nothing here reads or writes the state other calls use: the buffers are c->filt.*, the plan's sizes
+// ds.filt_*, the only other fields touched are opt.filter_* (read) and last.filter_*.  Host results are staged in c->filt.rows / c->filt.logc and
 // cross the link in ONE copy each, after the boundaries verified (a pageable buffer of 8 MiB or more is pinned
 // for it).
 #include <math.h>
@@ -27,10 +35,12 @@
 #include <vector>
 
 #include "filter_kernels.hpp"
+#include "filter_wide_launch.hpp"
 #include "host_common.hpp"
 #include "host_internal.hpp"
 #include "launch.hpp"
 #include "model_check.hpp"
+#include "plan.hpp"
 
 namespace bhmm {
 namespace {
@@ -38,6 +48,7 @@ namespace {
 constexpr double FILTER_TOL = 1e-11;         // boundary check: componentwise relative (bhmm_score's)
 constexpr int FILTER_W_UNPROBED = 288;       // warm-up when the trajectories are too short to probe (bhmm_score's)
 constexpr size_t FILTER_LDS_BT = 16 * 1024;  // B^T staged in LDS up to this size
+constexpr double FILTER_WIDE_MARGIN = 1.5;   // 9..64 states: warm-up over the probe's reading (bhmm_score's factor)
 
 struct Out {          // where the results go on the device, and what they are
     void *rows;       // [total][Qp] of double / float, or nullptr
@@ -190,6 +201,212 @@ int run_n(bhmm_ctx *c, const double *A, const double *pi, const double *par0, co
                                  : Fused<N, EMIT_DISC>::run(c, A, pi, par0, par1, o, verified);
 }
 
+// ---- 9..64 states ------------------------------------------------------------------------------
+
+// the segment plan of filtering on this observation set: made at the first eligible call (and again when
+// filter_seglen changes), never after a check.  Not the score plan and not the E-step's
+int filter_plan(bhmm_ctx *c)
+{
+    auto &d = c->ds;
+    auto &b = c->filt;
+    if (d.filt_nseg > 0 && d.filt_seglen_opt == c->opt.filter_seglen)
+        return BHMM_OK;
+    plan::SegPlan sp; // (plan.hpp: pure host code)
+    plan::plan_segments(c->offsets, c->K, plan::score_seglen(c->total, c->N, c->num_simd, c->opt.filter_seglen), 1,
+                        sp);
+    const size_t ns = sp.traj.size();
+    int rc;
+    if ((rc = b.seg_traj.ensure(ns)) || (rc = b.seg_len.ensure(ns)) || (rc = b.seg_t0.ensure(ns)) ||
+        (rc = b.seg_traj0.ensure(c->K + 1)))
+        return rc;
+    BHMM_HIP(hipMemcpyAsync(b.seg_traj.p, sp.traj.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.seg_len.p, sp.len.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.seg_t0.p, sp.t0.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.seg_traj0.p, sp.traj0.data(), (c->K + 1) * sizeof(int32_t), hipMemcpyHostToDevice,
+                            c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream)); // (sp is a temporary)
+    d.filt_nseg = (int)ns;
+    d.filt_ntraj = 0;
+    for (int k = 0; k < c->K; ++k)
+        d.filt_ntraj += c->offsets[k + 1] > c->offsets[k];
+    d.filt_seglen_opt = c->opt.filter_seglen;
+    return BHMM_OK;
+}
+
+struct WideFilt {
+    // warm-up: k_wide_probe's forward chains, read as bhmm_score reads them (score_api.hip, Wide::probe) --
+    // chains within 1e-13 from then on, times 1.5, rounded up to 8
+    static int probe(bhmm_ctx *c, const WideModel &m, int *W)
+    {
+        *W = FILTER_W_UNPROBED;
+        const int Wmax = (int)std::min<int64_t>(8192, longest_traj(c) / 2) / 8 * 8;
+        if (Wmax < 64)
+            return BHMM_OK; // (trajectories of fewer than 128 steps)
+        std::vector<int> longk;
+        for (int k = 0; k < c->K; ++k)
+            if (c->offsets[k + 1] - c->offsets[k] >= Wmax)
+                longk.push_back(k);
+        const int P = 256;
+        std::vector<int64_t> starts(P);
+        for (int i = 0; i < P; ++i) {
+            const int k = longk[i % longk.size()];
+            const int64_t room = c->offsets[k + 1] - c->offsets[k] - Wmax + 1;
+            const int64_t rep = i / (int64_t)longk.size(), reps = (P + longk.size() - 1) / longk.size();
+            starts[i] = c->offsets[k] + (room - 1) * rep / std::max<int64_t>(reps - 1, 1);
+        }
+        const size_t curve_words = 2 * (size_t)Wmax; // (the kernel's layout: forward | backward, the latter stays zero)
+        int rc;
+        if ((rc = c->filt.probe.ensure(P * sizeof(int64_t) + curve_words * sizeof(unsigned int))))
+            return rc;
+        int64_t *d_starts = reinterpret_cast<int64_t *>(c->filt.probe.p);
+        unsigned int *d_curve = reinterpret_cast<unsigned int *>(d_starts + P);
+        BHMM_HIP(hipMemcpyAsync(d_starts, starts.data(), P * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipMemsetAsync(d_curve, 0, curve_words * sizeof(unsigned int), c->stream));
+        if ((rc = filter_wide_probe_launch(c, c->N, m, d_starts, P, Wmax, d_curve)))
+            return rc;
+        std::vector<float> curve(Wmax); // the forward direction: the first Wmax entries
+        BHMM_HIP(hipMemcpyAsync(curve.data(), d_curve, curve.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+        int last = -1;
+        for (int w = 0; w < Wmax; ++w)
+            if (curve[w] >= 1e-13f)
+                last = w;
+        const int w = (int)std::ceil(FILTER_WIDE_MARGIN * (last + 2));
+        *W = std::min(std::max(16, (w + 7) / 8 * 8), Wmax); // (not forgotten within Wmax: Wmax, the check decides)
+        return BHMM_OK;
+    }
+
+    // the sweep, the first dead segment of every trajectory, the check and the fix-up; *fails: boundaries out of
+    // tolerance
+    static int pass(bhmm_ctx *c, const ScoreWideModel *dm, int W, const Out &o, unsigned int *fails)
+    {
+        auto &b = c->filt;
+        const int nseg = c->ds.filt_nseg;
+        FilterWideArgs a;
+        a.dm = dm;
+        a.W = W;
+        a.sg.traj = b.seg_traj.p;
+        a.sg.t0 = b.seg_t0.p;
+        a.sg.len = b.seg_len.p;
+        a.sg.nseg = nseg;
+        a.sg.W = W;
+        a.rows = o.rows;
+        a.logc = o.logc;
+        a.V = o.V;
+        a.Q = o.Q;
+        a.f32 = o.f32;
+        a.aentry = b.aentry.p;
+        a.aexit = b.aexit.p;
+        a.dead = b.dead.p;
+        *fails = 0;
+        int rc;
+        if ((rc = filter_wide_launch(c, c->N, a)))
+            return rc;
+        if (nseg > c->ds.filt_ntraj) { // (no boundary: the exact recursion, nothing after a dead segment)
+            const FiltSegs fs{b.seg_traj.p, b.seg_t0.p, b.seg_len.p, c->d_offsets.p, nseg};
+            BHMM_HIP(hipMemsetAsync(b.fails.p, 0, sizeof(unsigned int), c->stream));
+            BHMM_HIP(launch(k_filter_first_dead, dim3(c->K), dim3(64), 0, c->stream, b.seg_traj0.p, b.dead.p,
+                            b.first_dead.p));
+            BHMM_HIP(launch(k_filter_seg_check, dim3((nseg + 255) / 256), dim3(256), 0, c->stream, fs, c->n, b.aentry.p,
+                            b.aexit.p, b.first_dead.p, FILTER_TOL, b.fails.p));
+            if (o.f32)
+                BHMM_HIP(launch(k_filter_seg_bury<float>, dim3(nseg), dim3(64), 0, c->stream, fs, b.first_dead.p,
+                                static_cast<float *>(o.rows), o.Qp, static_cast<float *>(o.logc)));
+            else
+                BHMM_HIP(launch(k_filter_seg_bury<double>, dim3(nseg), dim3(64), 0, c->stream, fs, b.first_dead.p,
+                                static_cast<double *>(o.rows), o.Qp, static_cast<double *>(o.logc)));
+            BHMM_HIP(hipMemcpyAsync(fails, b.fails.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        }
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+        return BHMM_OK;
+    }
+
+    // *verified: the results in o stand
+    static int run(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                   const Out &o, bool *verified)
+    {
+        auto &b = c->filt;
+        const int M = c->M, n = c->n, K = c->K;
+        *verified = false;
+        int rc;
+        if ((rc = filter_plan(c)))
+            return rc;
+        const int nseg = c->last.filter_segments = c->ds.filt_nseg;
+        const bool segmented = nseg > c->ds.filt_ntraj;
+        // parameter block of the model: wide_model's layout, then B and B^T (bhmm_score's)
+        const bool disc = c->kind == EMIT_DISC;
+        const size_t nB = disc ? (size_t)n * M : 0, np = (size_t)n * n + 7 * n + 2 * nB;
+        if ((rc = b.model.ensure(sizeof(ScoreWideModel))) || (rc = b.wpar.ensure(np)) ||
+            (rc = b.aentry.ensure((size_t)std::max(nseg, 1) * n)) || (rc = b.aexit.ensure((size_t)std::max(nseg, 1) * n)) ||
+            (rc = b.dead.ensure(std::max(nseg, 1))) || (rc = b.first_dead.ensure(std::max(K, 1))) ||
+            (rc = b.fails.ensure(1)))
+            return rc;
+        if (nseg == 0) { // (no trajectory has a step: nothing to write)
+            *verified = true;
+            return BHMM_OK;
+        }
+        std::vector<double> h(np, 0.0);
+        ScoreWideModel m;
+        const double *dp = b.wpar.p;
+        memcpy(h.data(), A, sizeof(double) * n * n);
+        memcpy(h.data() + (size_t)n * n, pi, sizeof(double) * n);
+        WideModel &w = m.w;
+        w.A = dp;
+        w.pi = dp + (size_t)n * n;
+        w.mu = w.pi + n;
+        w.isig = w.mu + n;
+        w.cnorm = w.isig + n;
+        w.sigma = w.cnorm + n;
+        w.ga = w.sigma + n;
+        w.gb = w.ga + n;
+        w.gmg = 0.0;
+        w.B = nullptr;
+        w.n = n;
+        w.M = M;
+        m.Bt = nullptr;
+        double *q = h.data() + (size_t)n * n + n;
+        if (!disc) {
+            for (int i = 0; i < n; ++i) {
+                q[i] = par0[i];
+                q[n + i] = 1.0 / par1[i];
+                q[2 * n + i] = 1.0 / (sqrt(2.0 * M_PI) * par1[i]);
+                q[3 * n + i] = par1[i];
+            }
+            gauss_pdf_constants(n, n, par1, q + 4 * n, q + 5 * n, &w.gmg);
+        } else {
+            double *hB = q + 6 * n, *hBt = hB + nB;
+            memcpy(hB, par0, sizeof(double) * nB);
+            for (int i = 0; i < n; ++i)
+                for (int s = 0; s < M; ++s)
+                    hBt[(size_t)s * n + i] = par0[(size_t)i * M + s];
+            w.B = w.gb + n;
+            m.Bt = w.B + nB;
+        }
+        ScoreWideModel *dm = reinterpret_cast<ScoreWideModel *>(b.model.p);
+        BHMM_HIP(hipMemcpyAsync(b.wpar.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipMemcpyAsync(dm, &m, sizeof(ScoreWideModel), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream)); // (h and m are temporaries)
+        // a plan without a boundary runs the exact recursion: no probe, no check
+        int W = (c->opt.filter_W + 7) / 8 * 8;
+        if (segmented && c->opt.filter_W <= 0 && (rc = probe(c, m.w, &W)))
+            return rc;
+        W = std::max(W, 8);
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            unsigned int fails = 0;
+            if ((rc = pass(c, dm, W, o, &fails)))
+                return rc;
+            if (fails == 0) {
+                *verified = true;
+                return BHMM_OK;
+            }
+            if (attempt == 0)
+                ++c->last.filter_fallbacks; // boundaries that did not verify at the first warm-up
+            W = (int)std::min<int64_t>(2 * (int64_t)W, 1 << 30);
+        }
+        return BHMM_OK;
+    }
+};
+
 // the serial path: parallel over trajectories only
 template <typename OT>
 int serial(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, const Out &o)
@@ -304,9 +521,16 @@ int bhmm_filter(bhmm_ctx *c, const double *A, const double *pi, const double *pa
     }
     const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
     const bool fused = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;
-    c->last.filter_path = fused ? 1 : 0;
+    // 9..64 states (lanes per segment in c->N): always, never, or from FILTER_WIDE_MIN_TOTAL steps on
+    const bool wide = c->wide && emis && c->n <= 64 && c->opt.filter_parallel != 0 &&
+                      (c->opt.filter_parallel == 1 || c->total >= FILTER_WIDE_MIN_TOTAL);
+    c->last.filter_path = fused ? 1 : (wide ? 2 : 0);
+    c->last.filter_segments = 0;
     bool verified = false;
-    if (fused) {
+    if (wide) {
+        if ((rc = WideFilt::run(c, A, pi, par0, par1, o, &verified)))
+            return rc;
+    } else if (fused) {
         switch (c->n) {
         case 1:
             rc = run_n<1>(c, A, pi, par0, par1, o, &verified);

@@ -20,6 +20,8 @@
 //                   probability zero warms up from the uniform vector and emits rows that are not zero: per
 //                   trajectory the first chunk whose exit vector is all zero, then every LATER chunk of that
 //                   trajectory is overwritten with zero rows and -inf.
+//   k_filter_seg_check / k_filter_seg_bury   the same two rules over the segment plan of the 9..64-state path
+//                   (k_filter_wide, filter_wide_kernels.hpp); k_filter_first_dead serves both plans.
 //   k_filter_serial the exact path: one workgroup per trajectory, the serial recursion of k_score_serial with the
 //                   states spread over the threads; writes the normalised row (or its projection) and log c_t
 //                   every step.  Any n and explicit pobs; for N <= 8 the fallback after two failed checks.
@@ -239,6 +241,68 @@ __global__ __launch_bounds__(256) void k_filter_bury(const Chunks ch, int G, con
         if (logc)
             logc[goff + s] = (OT)-INFINITY;
     }
+}
+
+// ---- the same two rules over a segment plan (9..64 states, k_filter_wide in filter_wide_kernels.hpp) ---------
+// k_filter_first_dead serves both plans as it is (traj_c0: the plan's first segment of each trajectory).
+struct FiltSegs {
+    const int32_t *traj; // trajectory of the segment
+    const int64_t *t0;   // first step inside the trajectory
+    const int32_t *len;
+    const int64_t *off;  // [K + 1] trajectory offsets
+    int nseg;
+};
+
+// k_filter_check on segment records of n doubles: one lane per boundary (the segments of a trajectory are
+// consecutive, so the predecessor of a segment with t0 != 0 is s - 1)
+[[maybe_unused]] static __global__ __launch_bounds__(256) void k_filter_seg_check(const FiltSegs sg, int n,
+                                                                                const double *__restrict__ a_entry,
+                                                                                const double *__restrict__ a_exit,
+                                                                                const int32_t *__restrict__ first_dead,
+                                                                                double tol, unsigned int *fails)
+{
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= sg.nseg || sg.len[s] <= 0 || sg.t0[s] == 0)
+        return;
+    if (s > first_dead[sg.traj[s]])
+        return;
+    const double *x = a_entry + s * n, *y = a_exit + (s - 1) * n;
+    double sx = 0.0, sy = 0.0;
+    for (int j = 0; j < n; ++j) {
+        sx += x[j];
+        sy += y[j];
+    }
+    double dev = 0.0;
+    if (!(sx > 0.0) || !(sy > 0.0)) {
+        dev = 1.0;
+    } else {
+        for (int j = 0; j < n; ++j) {
+            const double xs = x[j] / sx, ys = y[j] / sy;
+            const double d = fabs(xs - ys);
+            const double rel = (ys > 1e-280) ? d / ys : (d > 1e-280 ? 1.0 : 0.0);
+            dev = fmax(dev, rel == rel ? rel : 1.0);
+        }
+    }
+    if (!(dev <= tol))
+        atomicAdd(fails, 1u);
+}
+
+// k_filter_bury over segments: one wavefront per segment (a segment is thousands of steps long)
+template <typename OT>
+__global__ __launch_bounds__(64) void k_filter_seg_bury(const FiltSegs sg, const int32_t *__restrict__ first_dead,
+                                                        OT *__restrict__ rows, int Qp, OT *__restrict__ logc)
+{
+    const int s = blockIdx.x;
+    const int len = sg.len[s];
+    if (len <= 0 || s <= first_dead[sg.traj[s]])
+        return;
+    const int64_t g0 = sg.off[sg.traj[s]] + sg.t0[s];
+    if (rows)
+        for (int64_t e = threadIdx.x; e < (int64_t)len * Qp; e += 64)
+            rows[g0 * Qp + e] = (OT)0.0;
+    if (logc)
+        for (int e = threadIdx.x; e < len; e += 64)
+            logc[g0 + e] = (OT)-INFINITY;
 }
 
 // ---- exact path ----------------------------------------------------------------------------

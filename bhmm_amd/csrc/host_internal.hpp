@@ -42,6 +42,15 @@ int specres_read(bhmm_ctx *c, int words = 4, bool wait = true);
 int estep_f32(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
               double *stats_dev, int flags, bool *done);
 
+// ---- filter_api.hip (bhmm_filter) ----
+// Steps of an observation set from which a call at 9..64 states takes the time-parallel path by itself (option
+// filter_parallel = -1; read-only option filter_wide_min_total).  To be the break-even against k_filter_serial of
+// the scan in DESIGN.md section 16 (tools/filter_time.py --only scan, profiles/filter/filter_time.json), rounded up
+// to a power of two and not below 32768: tests/test_filter_gpu.py::test_parity_serial pins the serial kernel for a
+// default call on 23734 steps.  The scan puts the break-even below 4096 steps (64 states: 28.4 ms against 2.4 ms
+// there), so this is the floor, not the break-even; lowering it also owns that test.
+constexpr int64_t FILTER_WIDE_MIN_TOTAL = 32768;
+
 // ---- wide_api.hip (9..64 states) ----
 int wide_alloc(bhmm_ctx *c);
 int wide_model(bhmm_ctx *c, int kind, const double *A, const double *pi, const double *par0, const double *par1,

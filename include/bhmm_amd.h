@@ -234,7 +234,7 @@ int bhmm_posterior_marginals(bhmm_ctx *ctx, const double *A, const double *pi, c
      rows[(offset_k + t) * Q' + q], trajectory-major as bhmm_posterior_marginals writes them:
        V == NULL, Q == 0 : Q' = N, the row is P(s_t = . | o_0 .. o_t) and sums to one;
        V[N*Q] row-major, 1 <= Q <= 8 : Q' = Q, the row is sum_i P(s_t = i | o_0 .. o_t) * V[i*Q + q], accumulated
-         over i in ASCENDING order in fp64 (fused multiply-add);
+         over i in ASCENDING order in fp64 (fused multiply-add; filter_path 2: see below);
      logc[offset_k + t] = log p(o_t | o_0 .. o_{t-1}); logc[offset_k] = log sum_i pi_i p_0(i) (pi is not
        normalised, as in the reference's forward); their sum over a trajectory is its log-likelihood.
    Either output may be NULL, not both.  From the first step of a trajectory whose probability is zero on, its
@@ -248,10 +248,18 @@ int bhmm_posterior_marginals(bhmm_ctx *ctx, const double *A, const double *pi, c
    do not fit; nothing is truncated), each crosses the link in ONE copy after the boundaries verified -- a
    pageable buffer of 8 MiB or more is pinned for the duration of its copy -- and the call is synchronous.
    Up to 8 states (gaussian, discrete): one forward sweep over the chunk plan with verified warm-up boundaries
-   (filter_path 1).  Options: filter_W (warm-up in steps, 0 = measured); read-only filter_fallbacks (calls whose
-   boundaries did not verify at the first warm-up: they run again with twice the warm-up, then take the serial
-   path) and filter_path (first pass of the last call: 1 fused, 0 serial).  9 states and more and explicit pobs:
-   the serial recursion, one workgroup per trajectory (filter_path 0; at most 4096 states).
+   (filter_path 1).  9 to 64 states (gaussian, discrete): the time-parallel sweep k_filter_wide over a segment
+   plan that belongs to filtering alone, with the same verified warm-up boundaries (filter_path 2) -- taken when
+   the option filter_parallel is 1, or -1 (the default) and the loaded set has at least filter_wide_min_total
+   steps; on this path the columns of a projection are summed over i by a fixed tree, not in ascending order.
+   Everything else (65 states and more, explicit pobs, filter_parallel 0, smaller sets): the serial recursion, one
+   workgroup per trajectory (filter_path 0; at most 4096 states).
+   Options: filter_W (warm-up in steps, 0 = measured); filter_seglen (9 to 64 states: segment length of the plan
+   from the next call on, rounded up to a multiple of four; 0 = automatic); filter_parallel (-1, 0, 1: above);
+   read-only filter_fallbacks (calls whose boundaries did not verify at the first warm-up: they run again with
+   twice the warm-up, then take the serial path), filter_path (first pass of the last call: 2 time segments,
+   1 fused, 0 serial), filter_segments (segments of the plan the last call ran on; 0: another path) and
+   filter_wide_min_total.
    Nothing of the state that E-step, Viterbi, sampling, scoring, decoding and marginals calls use is read or
    written. */
 #define BHMM_FILT_F32 1

@@ -10,8 +10,14 @@ device, logc alone left on the device and a Q = 1 projection (the state index) l
   (b) Engine.posterior_marginals in the same output form: it does strictly more work;
   (c) the route a user had before this call: pobs on the host and hidden.forward per trajectory, timed on the
       first --fwd trajectories and scaled to the set ("forward_route_trajectories" says how many ran).
+Blocks c3 | g32 | g16 (the shapes of tools/score_time.py: 128 x 1e5 gaussian at 64, 32 and 16 states) time the
+time-parallel path for 9 to 64 states (k_filter_wide, filter_parallel = 1) in four forms -- float64 to the host,
+float32 to the device, logc alone to the device, a Q = 1 projection to the device -- against the same build with
+filter_parallel = 0 (k_filter_serial, which is also what the commit before this path ran), Engine.score with one
+model (the floor) and posterior_marginals in the same form.  Block scan: one long 64-state trajectory of 4096,
+16384, 65536 and 262144 steps under filter_parallel 0 and 1 -- the break-even behind FILTER_WIDE_MIN_TOTAL.
 One JSON object per configuration, printed and appended to profiles/filter/filter_time.json.  Options: --only
-c1|c2, --reps R, --sub N, --fwd N, --label TEXT (a "build" field in every line), --filter-only (the device forms
+c1|c2|c3|g32|g16|scan, --reps R, --sub N, --fwd N, --label TEXT (a "build" field in every line), --filter-only (the device forms
 alone: the workload of a rocprofv3 --kernel-trace --stats pass)."""
 import argparse
 import json
@@ -25,7 +31,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from score_time import c1_setup, c2_setup  # noqa: E402
+from score_time import c1_setup, c2_setup, c3_setup, g16_setup, g32_setup  # noqa: E402
 from bhmm_amd.engine import Engine  # noqa: E402
 
 
@@ -81,9 +87,98 @@ def forward_route(kind, obs_host, model, count):
         hidden.forward(A, om.p_obs(obs_host[k]), pi)
 
 
+def wide_forms(eng, model, V, reps, line, prefix):
+    """the four forms of the 9..64-state blocks under the engine's current filter_parallel"""
+    n, total = eng.nstates, int(eng.offsets[-1])
+    h64, l64 = np.empty((total, n)), np.empty(total)
+    line.update(stats(prefix + "_f64_host", timed_all(lambda: eng.filter_states(*model, out=h64, out_increments=l64),
+                                                      reps)))
+    del h64, l64
+    t32 = torch.empty((total, n), dtype=torch.float32, device="cuda:0")
+    l32 = torch.empty(total, dtype=torch.float32, device="cuda:0")
+    line.update(stats(prefix + "_f32_dev", timed_all(
+        lambda: eng.filter_states(*model, dtype=np.float32, out=t32, out_increments=l32), reps)))
+    del t32
+    line.update(stats(prefix + "_logc_dev", timed_all(
+        lambda: eng.filter_states(*model, dtype=np.float32, probabilities=False, out_increments=l32), reps)))
+    tq = torch.empty((total, 1), dtype=torch.float32, device="cuda:0")
+    line.update(stats(prefix + "_q1_dev", timed_all(
+        lambda: eng.filter_states(*model, weights=V, dtype=np.float32, out=tq, out_increments=l32), reps)))
+    line[prefix + "_path"] = eng.get_option("filter_path")
+    line[prefix + "_fallbacks"] = eng.get_option("filter_fallbacks")
+    line[prefix + "_segments"] = eng.get_option("filter_segments")
+    del tq, l32
+    torch.cuda.empty_cache()
+
+
+def wide_block(args, setup):
+    name, eng, models, obs, total = setup()
+    model = models[0]
+    n = eng.nstates
+    V = np.arange(n, dtype=float)[:, None]
+    line = dict(build=args.label, config=name, trajectories=len(eng.lengths), steps=total, reps=args.reps)
+    eng.set_option("filter_parallel", 1)
+    if args.filter_only:
+        wide_forms(eng, model, V, 1, line, "wide")
+        eng.close()
+        return
+    wide_forms(eng, model, V, args.reps, line, "wide")
+    eng.set_option("filter_parallel", 0)
+    wide_forms(eng, model, V, args.reps, line, "serial")
+    line.update(stats("score_one_model", timed_all(lambda: eng.score([model]), args.reps)))
+    t32 = torch.empty((total, n), dtype=torch.float32, device="cuda:0")
+    line.update(stats("marg_f32_dev", timed_all(lambda: eng.posterior_marginals(*model, dtype=np.float32, out=t32),
+                                                args.reps)))
+    del t32
+    tq = torch.empty((total, 1), dtype=torch.float32, device="cuda:0")
+    line.update(stats("marg_q1_dev", timed_all(
+        lambda: eng.posterior_marginals(*model, weights=V, dtype=np.float32, out=tq), args.reps)))
+    del tq
+    h64 = np.empty((total, n))
+    line.update(stats("marg_f64_host", timed_all(lambda: eng.posterior_marginals(*model, out=h64), args.reps)))
+    del h64
+    for form in ("f64_host", "f32_dev", "logc_dev", "q1_dev"):
+        line["serial_over_wide_" + form] = line["serial_%s_ms" % form] / line["wide_%s_ms" % form]
+    line["wide_f32_dev_over_score"] = line["wide_f32_dev_ms"] / line["score_one_model_ms"]
+    line["wide_f32_dev_over_marg"] = line["wide_f32_dev_ms"] / line["marg_f32_dev_ms"]
+    emit(args, line)
+    eng.close()
+
+
+def scan_block(args):
+    """one long 64-state trajectory (a prefix of configs[3]'s observations), float32 rows and logc to the device"""
+    name, eng, models, obs, _ = c3_setup()
+    model, n = models[0], eng.nstates
+    eng.close()
+    for total in (4096, 16384, 65536, 262144):
+        eng = Engine(0)
+        eng.set_observations_device("gaussian", obs.data_ptr(), np.array([0, total], dtype=np.int64), n)
+        t32 = torch.empty((total, n), dtype=torch.float32, device="cuda:0")
+        l32 = torch.empty(total, dtype=torch.float32, device="cuda:0")
+        line = dict(build=args.label, config="scan: 64-state gaussian, one trajectory", steps=total, reps=args.reps)
+        for par, key in ((0, "serial"), (1, "wide")):
+            eng.set_option("filter_parallel", par)
+            line.update(stats(key + "_f32_dev", timed_all(
+                lambda: eng.filter_states(*model, dtype=np.float32, out=t32, out_increments=l32), args.reps)))
+            line[key + "_path"] = eng.get_option("filter_path")
+        line["wide_segments"] = eng.get_option("filter_segments")
+        line["serial_over_wide"] = line["serial_f32_dev_ms"] / line["wide_f32_dev_ms"]
+        emit(args, line)
+        eng.close()
+        del t32, l32
+
+
+def emit(args, line):
+    text = json.dumps(line)
+    print(text, flush=True)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=["c1", "c2"])
+    ap.add_argument("--only", choices=["c1", "c2", "c3", "g32", "g16", "scan"])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sub", type=int, default=32, help="trajectories of configs[2] that are filtered")
     ap.add_argument("--fwd", type=int, default=2, help="trajectories the hidden.forward route is timed on")
@@ -91,6 +186,13 @@ def main():
     ap.add_argument("--filter-only", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "filter", "filter_time.json"))
     args = ap.parse_args()
+    for key, setup in (("c3", c3_setup), ("g32", g32_setup), ("g16", g16_setup)):
+        if args.only == key:        # (the 9..64-state blocks run on request only: the serial side takes seconds)
+            wide_block(args, setup)
+    if args.only == "scan":
+        scan_block(args)
+    if args.only in ("c3", "g32", "g16", "scan"):
+        return
     for key, setup in (("c1", c1_setup), ("c2", c2_setup)):
         if args.only and key != args.only:
             continue
@@ -135,11 +237,7 @@ def main():
         line["filter_f32_dev_over_score"] = line["filter_f32_dev_ms"] / line["score_one_model_ms"]
         line["filter_f32_dev_over_marg"] = line["filter_f32_dev_ms"] / line["marg_f32_dev_ms"]
         line["forward_route_over_filter_f64_host"] = line["forward_route_ms_scaled"] / line["filter_f64_host_ms"]
-        text = json.dumps(line)
-        print(text, flush=True)
-        os.makedirs(os.path.dirname(args.out), exist_ok=True)
-        with open(args.out, "a") as f:
-            f.write(text + "\n")
+        emit(args, line)
         eng.close()
         del obs
         torch.cuda.empty_cache()
