@@ -1556,6 +1556,10 @@ int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
         if (value != 0.0 && value != 1.0 && value != -1.0)
             return invalid_arg("filter_parallel must be -1, 0 or 1");
         c->opt.filter_parallel = (int)value;
+    } else if (n == "filter_tile") { // ... 65..128 states, the matrix-core path: 0 never, 1 always when eligible, -1 automatic
+        if (value != 0.0 && value != 1.0 && value != -1.0)
+            return invalid_arg("filter_tile must be -1, 0 or 1");
+        c->opt.filter_tile = (int)value;
     } else
         return invalid_arg("unknown or read-only option: " + n);
     return BHMM_OK;
@@ -1691,7 +1695,7 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->opt.filter_W;
     else if (n == "filter_fallbacks") // bhmm_filter: calls whose boundaries did not verify at the first warm-up
         *value = c->last.filter_fallbacks;
-    else if (n == "filter_path") // ... first pass of the last call: 2 k_filter_wide (9..64 states), 1 fused kernel (up to 8 states), 0 serial kernel
+    else if (n == "filter_path") // ... first pass of the last call: 3 k_filter_tile (65..128 states), 2 k_filter_wide (9..64 states), 1 fused kernel (up to 8 states), 0 serial kernel
         *value = c->last.filter_path;
     else if (n == "filter_seglen")
         *value = c->opt.filter_seglen;
@@ -1701,6 +1705,12 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->last.filter_segments;
     else if (n == "filter_wide_min_total") // ... steps from which filter_parallel = -1 takes the time-parallel path
         *value = (double)FILTER_WIDE_MIN_TOTAL;
+    else if (n == "filter_tile")
+        *value = c->opt.filter_tile;
+    else if (n == "filter_tile_min_total") // ... steps from which filter_tile = -1 takes the matrix-core path (65..128 states)
+        *value = (double)FILTER_TILE_MIN_TOTAL;
+    else if (n == "filter_redone") // ... trajectories of the last call that path did again on the serial kernel
+        *value = c->last.filter_redone;
     else if (n == "score_path") // ... first pass of the last call: 0 serial kernel, 1 chunk kernels (N <= 8), 2 k_score_wide, 3 k_score_tile
         *value = c->last.score_path;
     else

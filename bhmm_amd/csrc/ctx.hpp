@@ -112,6 +112,8 @@ struct bhmm_ctx {
         int filter_seglen = 0;           // bhmm_filter, 9..64 states: segment length of its plan (option filter_seglen; 0: automatic)
         int filter_parallel = -1;        // ... the time-parallel path: 0 never, 1 always when eligible, -1 automatic
                                          // (eligible and at least FILTER_WIDE_MIN_TOTAL steps; option filter_parallel)
+        int filter_tile = -1;            // ... 65..128 states, the matrix-core path (k_filter_tile): 0 never, 1 always when
+                                         // eligible, -1 automatic (at least FILTER_TILE_MIN_TOTAL steps; option filter_tile)
     } opt;
 
     // ---- loaded problem ----
@@ -188,6 +190,12 @@ struct bhmm_ctx {
         int filt_nseg = 0;               // segments of the plan (0: not made yet)
         int filt_ntraj = 0;              // ... trajectories with at least one step (nseg == ntraj: no boundary)
         int filt_seglen_opt = 0;         // ... opt.filter_seglen it was made for
+        // bhmm_filter, 65..128 states: the segment plan and tile table of k_filter_tile (tables in filt.tseg_* and
+        // filt.tile_seg), made the same way; neither the score plan nor the plan above
+        int filt_tile_nseg = 0;          // segments of the plan (0: not made yet)
+        int filt_tile_ntraj = 0;         // ... trajectories with at least one step (nseg == ntraj: no boundary)
+        int filt_tile_ntiles = 0;        // ... tiles of 16 segments
+        int filt_tile_seglen_opt = 0;    // ... opt.filter_seglen it was made for
     } ds;
 
     // ---- counters and diagnostics of the last calls (bhmm_ctx_get_option) ----
@@ -225,9 +233,12 @@ struct bhmm_ctx {
         int marg_fallbacks = 0;          // bhmm_posterior_marginals: calls whose boundaries did not verify at the first warm-up
         int marg_path = 0;               // ... first pass of the last call: 1 fused (k_marg_sweep), 0 generic (E-step + gamma rows)
         int filter_fallbacks = 0;        // bhmm_filter: calls whose boundaries did not verify at the first warm-up
-        int filter_path = 0;             // ... first pass of the last call: 2 time segments (k_filter_wide, 9..64 states),
-                                         // 1 fused (k_filter_sweep, up to 8 states), 0 serial (k_filter_serial)
+        int filter_path = 0;             // ... first pass of the last call: 3 matrix cores (k_filter_tile, 65..128 states),
+                                         // 2 time segments (k_filter_wide, 9..64 states), 1 fused (k_filter_sweep, up to
+                                         // 8 states), 0 serial (k_filter_serial)
         int filter_segments = 0;         // ... segments of the filter plan it ran on (0: no such plan)
+        int filter_redone = 0;           // ... filter_path 3: trajectories of the last call done again on k_filter_serial
+                                         // because a segment left the range of k_filter_tile (option filter_redone)
     } last;
 
     // ---- not reset by bhmm_ctx_set_observations: they outlive the observation set ----
@@ -356,7 +367,9 @@ struct bhmm_ctx {
     // is all zero and per trajectory the first of them, failure counter, probe curve, the projection matrix V, the
     // parameters of the serial path, and the two results staged on the device when the caller's buffers are on
     // the host (rows, logc); 9..64 states: the model's parameter block and the tables of the plan ds.filt_nseg
-    // counts (dead / first_dead then count segments); nothing else reads them
+    // counts (dead / first_dead then count segments); 65..128 states: the tables of the plan ds.filt_tile_nseg
+    // counts (tseg_*, tile_seg), dead is then the range flag of every segment, redo the trajectories to do again and
+    // fails the words of k_filter_tile_check / k_filter_tile_redo; nothing else reads them
     struct FiltBufs {
         bhmm::DevBuf<char> model, probe, rows, logc;
         bhmm::DevBuf<double> Bt, aentry, aexit, V, par;
@@ -366,6 +379,9 @@ struct bhmm_ctx {
         bhmm::DevBuf<double> wpar;
         bhmm::DevBuf<int32_t> seg_traj, seg_len, seg_traj0;
         bhmm::DevBuf<int64_t> seg_t0;
+        bhmm::DevBuf<int32_t> tseg_traj, tseg_len, tseg_traj0, tile_seg;
+        bhmm::DevBuf<int64_t> tseg_t0;
+        bhmm::DevBuf<uint8_t> redo;
     } filt;
 
     // ---- pinned host buffers ----

@@ -19,10 +19,22 @@
 // bhmm_score reads them, or filter_W; the same protocol.  Taken when the option filter_parallel is 1, or -1 (the
 // default) and the set has at least FILTER_WIDE_MIN_TOTAL steps (host_internal.hpp).
 //
-// Everything else (65 states and more, explicit pobs, filter_parallel 0 or a small set; filter_path 0):
-// k_filter_serial, one workgroup per trajectory.
+// 65 to 128 states, gaussian or discrete, loaded observations (the matrix-core path, filter_path 3): k_filter_tile
+// (filter_tile_kernels.hpp; compiled in filter_tile_nt.hip, one unit per column-tile count) -- k_score_tile for one
+// model with the row and the increment as last stage -- over a segment plan and tile table of its own
+// (filter_tile_plan: plan::score_tile_seglen with filter_seglen, plan::plan_tiles).  W by the rule of bhmm_score's
+// Tile::calibrate: two passes of the kernel without outputs at W = 32 and 64, the decay of the largest boundary
+// deviation extrapolated (score_tile_extrapolate), or filter_W.  The kernel flags every segment that left its number
+// range (probability zero, an outlier, a NaN observation): k_filter_tile_redo marks their trajectories, which
+// k_filter_serial does again, whole, behind the pass on the same stream (counted in filter_redone); their boundaries
+// are not checked (k_filter_tile_check).  Boundaries that do not verify: the same protocol as above.  Taken when
+// filter_parallel is not 0 and the option filter_tile is 1, or -1 (the default) and the set has at least
+// FILTER_TILE_MIN_TOTAL steps.
 //
-// Nothing here reads or writes the state other calls use: the buffers are c->filt.*, the plan's sizes
+// Everything else (more than 128 states, explicit pobs, filter_parallel / filter_tile 0 or a small set;
+// filter_path 0): k_filter_serial, one workgroup per trajectory.
+//
+// Nothing here reads or writes the state other calls use: the buffers are c->filt.*, the plans' sizes
 // ds.filt_*, the only other fields touched are opt.filter_* (read) and last.filter_*.  Host results are staged in c->filt.rows / c->filt.logc and
 // cross the link in ONE copy each, after the boundaries verified (a pageable buffer of 8 MiB or more is pinned
 // for it).
@@ -35,6 +47,7 @@
 #include <vector>
 
 #include "filter_kernels.hpp"
+#include "filter_tile_launch.hpp"
 #include "filter_wide_launch.hpp"
 #include "host_common.hpp"
 #include "host_internal.hpp"
@@ -43,6 +56,10 @@
 #include "plan.hpp"
 
 namespace bhmm {
+FILTER_TILE_LAUNCH_DECL(extern, 5)
+FILTER_TILE_LAUNCH_DECL(extern, 6)
+FILTER_TILE_LAUNCH_DECL(extern, 7)
+FILTER_TILE_LAUNCH_DECL(extern, 8)
 namespace {
 
 constexpr double FILTER_TOL = 1e-11;         // boundary check: componentwise relative (bhmm_score's)
@@ -408,8 +425,10 @@ struct WideFilt {
 };
 
 // the serial path: parallel over trajectories only
+// (only: nullptr, or one byte per trajectory on the device -- the marked ones alone)
 template <typename OT>
-int serial(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, const Out &o)
+int serial(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, const Out &o,
+           const uint8_t *only = nullptr)
 {
     const int n = c->n, K = c->K;
     if (n > SCORE_SERIAL_R * 1024)
@@ -437,16 +456,213 @@ int serial(bhmm_ctx *c, const double *A, const double *pi, const double *par0, c
     hipError_t e;
     if (c->kind == EMIT_GAUSS)
         e = launch(k_filter_serial<EMIT_GAUSS, OT>, dim3(K), dim3(bd), lds, c->stream, n, c->M, c->d_offsets.p, obs, dA,
-                   dpi, dp0, dp1, o.V, o.Q, rows, logc);
+                   dpi, dp0, dp1, o.V, o.Q, rows, logc, only);
     else if (c->kind == EMIT_DISC)
         e = launch(k_filter_serial<EMIT_DISC, OT>, dim3(K), dim3(bd), lds, c->stream, n, c->M, c->d_offsets.p, obs, dA,
-                   dpi, dp0, nullptr, o.V, o.Q, rows, logc);
+                   dpi, dp0, nullptr, o.V, o.Q, rows, logc, only);
     else
         e = launch(k_filter_serial<EMIT_EXPL, OT>, dim3(K), dim3(bd), lds, c->stream, n, c->M, c->d_offsets.p, obs, dA,
-                   dpi, nullptr, nullptr, o.V, o.Q, rows, logc);
+                   dpi, nullptr, nullptr, o.V, o.Q, rows, logc, only);
     BHMM_HIP(e);
     return BHMM_OK;
 }
+
+// ---- 65..128 states ----------------------------------------------------------------------------
+
+// the segment plan and the tile table of k_filter_tile on this observation set: made at the first eligible call
+// (and again when filter_seglen changes), never after a check.  Neither the score plan nor the plan above
+int filter_tile_plan(bhmm_ctx *c)
+{
+    auto &d = c->ds;
+    auto &b = c->filt;
+    if (d.filt_tile_nseg > 0 && d.filt_tile_seglen_opt == c->opt.filter_seglen)
+        return BHMM_OK;
+    plan::SegPlan sp; // (plan.hpp: pure host code)
+    plan::plan_segments(c->offsets, c->K, plan::score_tile_seglen(c->total, c->num_simd, c->opt.filter_seglen), 1, sp);
+    std::vector<int32_t> tile_seg;
+    plan::plan_tiles(sp, c->offsets, false, tile_seg);
+    const size_t ns = sp.traj.size();
+    int rc;
+    if ((rc = b.tseg_traj.ensure(std::max<size_t>(ns, 1))) || (rc = b.tseg_len.ensure(std::max<size_t>(ns, 1))) ||
+        (rc = b.tseg_t0.ensure(std::max<size_t>(ns, 1))) || (rc = b.tseg_traj0.ensure(c->K + 1)) ||
+        (rc = b.tile_seg.ensure(std::max<size_t>(tile_seg.size(), 16))))
+        return rc;
+    BHMM_HIP(hipMemcpyAsync(b.tseg_traj.p, sp.traj.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.tseg_len.p, sp.len.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.tseg_t0.p, sp.t0.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.tseg_traj0.p, sp.traj0.data(), (c->K + 1) * sizeof(int32_t), hipMemcpyHostToDevice,
+                            c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.tile_seg.p, tile_seg.data(), tile_seg.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                            c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream)); // (sp and tile_seg are temporaries)
+    d.filt_tile_nseg = (int)ns;
+    d.filt_tile_ntiles = (int)(tile_seg.size() / 16);
+    d.filt_tile_ntraj = 0;
+    for (int k = 0; k < c->K; ++k)
+        d.filt_tile_ntraj += c->offsets[k + 1] > c->offsets[k];
+    d.filt_tile_seglen_opt = c->opt.filter_seglen;
+    return BHMM_OK;
+}
+
+template <int KIND>
+struct TileFilt {
+    // what a pass left
+    struct Verdict {
+        unsigned int fails;  // boundaries out of tolerance (those of trajectories marked for redo are not looked at)
+        float dev;           // largest boundary deviation
+        unsigned int redone; // trajectories with a segment outside the kernel's range
+    };
+
+    // the kernel at warm-up W, the trajectories to do again and the boundary check.  o == nullptr: boundary vectors
+    // only (calibration)
+    static int pass(bhmm_ctx *c, ScoreTileModel *dm, ScoreTileModel &m, int W, const Out *o, Verdict *v)
+    {
+        auto &b = c->filt;
+        const int n = c->n, nseg = c->ds.filt_tile_nseg;
+        m.W = W;
+        BHMM_HIP(hipMemcpyAsync(dm, &m, sizeof(ScoreTileModel), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream)); // (m changes between passes)
+        FilterTileArgs a;
+        a.dm = dm;
+        a.sg.traj = b.tseg_traj.p;
+        a.sg.t0 = b.tseg_t0.p;
+        a.sg.len = b.tseg_len.p;
+        a.sg.nseg = nseg;
+        a.sg.W = W;
+        a.tp = TilePlan{b.tile_seg.p, c->ds.filt_tile_ntiles};
+        a.rows = o ? o->rows : nullptr;
+        a.logc = o ? o->logc : nullptr;
+        a.V = o ? o->V : nullptr;
+        a.Q = o ? o->Q : 0;
+        a.f32 = o ? o->f32 : false;
+        a.aentry = b.aentry.p;
+        a.aexit = b.aexit.p;
+        a.seg_flag = b.dead.p;
+        BHMM_HIP(hipMemsetAsync(b.fails.p, 0, FILTER_TILE_WORDS * sizeof(unsigned int), c->stream));
+        int rc = n <= 80   ? filter_tile_launch<5, KIND>(c, a)
+                 : n <= 96  ? filter_tile_launch<6, KIND>(c, a)
+                 : n <= 112 ? filter_tile_launch<7, KIND>(c, a)
+                            : filter_tile_launch<8, KIND>(c, a);
+        if (rc)
+            return rc;
+        BHMM_HIP(launch(k_filter_tile_redo, dim3(c->K), dim3(64), 0, c->stream, b.tseg_traj0.p, b.dead.p, b.redo.p,
+                        b.fails.p));
+        if (nseg > c->ds.filt_tile_ntraj) // (no boundary: the exact recursion)
+            BHMM_HIP(launch(k_filter_tile_check, dim3((nseg + 15) / 16), dim3(256), 0, c->stream, a.sg, n, b.aentry.p,
+                            b.aexit.p, b.redo.p, FILTER_TOL, b.fails.p));
+        unsigned int f[FILTER_TILE_WORDS];
+        BHMM_HIP(hipMemcpyAsync(f, b.fails.p, sizeof(f), hipMemcpyDeviceToHost, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+        v->fails = f[FILTER_TILE_FAILS];
+        memcpy(&v->dev, &f[FILTER_TILE_DEV], sizeof(float));
+        v->redone = f[FILTER_TILE_REDONE];
+        return BHMM_OK;
+    }
+
+    // warm-up by the rule of bhmm_score's Tile::calibrate (score_api.hip): the kernel itself, without outputs, at
+    // two warm-ups; the largest boundary deviation of each; the decay between them extrapolated
+    static int calibrate(bhmm_ctx *c, ScoreTileModel *dm, ScoreTileModel &m, int *W)
+    {
+        auto good = [](const Verdict &v) { return v.fails == 0 && (double)v.dev <= SCORE_TILE_DEV_OK; };
+        Verdict v0, v1;
+        int rc;
+        *W = SCORE_TILE_W0;
+        if ((rc = pass(c, dm, m, SCORE_TILE_W0, nullptr, &v0)) || good(v0))
+            return rc;
+        if ((rc = pass(c, dm, m, SCORE_TILE_W1, nullptr, &v1)))
+            return rc;
+        *W = good(v1) ? SCORE_TILE_W1 : score_tile_extrapolate((double)v0.dev, (double)v1.dev);
+        return BHMM_OK;
+    }
+
+    // *verified: the results in o stand
+    static int run(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                   const Out &o, bool *verified)
+    {
+        auto &b = c->filt;
+        const int M = c->M, n = c->n, K = c->K;
+        *verified = false;
+        int rc;
+        if ((rc = filter_tile_plan(c)))
+            return rc;
+        const int nseg = c->last.filter_segments = c->ds.filt_tile_nseg;
+        const bool segmented = nseg > c->ds.filt_tile_ntraj;
+        // parameter block of the model: wide_model's layout, then B^T (bhmm_score's)
+        const size_t nB = KIND == EMIT_DISC ? (size_t)n * M : 0, np = (size_t)n * n + 7 * n + nB;
+        if ((rc = b.model.ensure(sizeof(ScoreTileModel))) || (rc = b.wpar.ensure(np)) ||
+            (rc = b.aentry.ensure((size_t)std::max(nseg, 1) * n)) || (rc = b.aexit.ensure((size_t)std::max(nseg, 1) * n)) ||
+            (rc = b.dead.ensure(std::max(nseg, 1))) || (rc = b.redo.ensure(std::max(K, 1))) ||
+            (rc = b.fails.ensure(FILTER_TILE_WORDS)))
+            return rc;
+        if (nseg == 0) { // (no trajectory has a step: nothing to write)
+            *verified = true;
+            return BHMM_OK;
+        }
+        std::vector<double> h(np, 0.0);
+        ScoreTileModel m;
+        const double *dp = b.wpar.p;
+        memcpy(h.data(), A, sizeof(double) * n * n);
+        memcpy(h.data() + (size_t)n * n, pi, sizeof(double) * n);
+        WideModel &w = m.w;
+        w.A = dp;
+        w.pi = dp + (size_t)n * n;
+        w.mu = w.pi + n;
+        w.isig = w.mu + n;
+        w.cnorm = w.isig + n;
+        w.sigma = w.cnorm + n;
+        w.ga = w.sigma + n;
+        w.gb = w.ga + n;
+        w.gmg = 0.0;
+        w.B = nullptr; // (the kernel reads B^T)
+        w.n = n;
+        w.M = M;
+        m.Bt = nullptr;
+        m.W = 0;
+        double *q = h.data() + (size_t)n * n + n;
+        if (KIND == EMIT_GAUSS) {
+            for (int i = 0; i < n; ++i) {
+                q[i] = par0[i];
+                q[n + i] = 1.0 / par1[i];
+                q[2 * n + i] = 1.0 / (sqrt(2.0 * M_PI) * par1[i]);
+                q[3 * n + i] = par1[i];
+            }
+            gauss_pdf_constants(n, n, par1, q + 4 * n, q + 5 * n, &w.gmg);
+        } else {
+            double *hBt = q + 6 * n;
+            for (int i = 0; i < n; ++i)
+                for (int s = 0; s < M; ++s)
+                    hBt[(size_t)s * n + i] = par0[(size_t)i * M + s];
+            m.Bt = w.gb + n;
+        }
+        ScoreTileModel *dm = reinterpret_cast<ScoreTileModel *>(b.model.p);
+        BHMM_HIP(hipMemcpyAsync(b.wpar.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream)); // (h is a temporary)
+        // W: multiples of four (the refresh of the scaling).  A plan without a boundary runs the exact recursion: no
+        // calibration, no check
+        int W = segmented ? (c->opt.filter_W + 3) & ~3 : 0;
+        if (segmented && c->opt.filter_W <= 0 && (rc = calibrate(c, dm, m, &W)))
+            return rc;
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            Verdict v;
+            if ((rc = pass(c, dm, m, W, &o, &v)))
+                return rc;
+            if (v.fails == 0) {
+                // the trajectories with a segment outside the kernel's range again, whole, on the serial kernel:
+                // behind the pass, on the same stream
+                c->last.filter_redone = (int)v.redone;
+                if (v.redone != 0 && (rc = o.f32 ? serial<float>(c, A, pi, par0, par1, o, b.redo.p)
+                                                 : serial<double>(c, A, pi, par0, par1, o, b.redo.p)))
+                    return rc;
+                *verified = true;
+                return BHMM_OK;
+            }
+            if (attempt == 0)
+                ++c->last.filter_fallbacks; // boundaries that did not verify at the first warm-up
+            W = (int)std::min<int64_t>(2 * (int64_t)W, SCORE_TILE_W_MAX);
+        }
+        return BHMM_OK;
+    }
+};
 
 // a staged result to the caller's host buffer in one copy: a pageable buffer of 8 MiB or more is pinned for the
 // transfer, one the caller pinned is used as it is
@@ -524,10 +740,19 @@ int bhmm_filter(bhmm_ctx *c, const double *A, const double *pi, const double *pa
     // 9..64 states (lanes per segment in c->N): always, never, or from FILTER_WIDE_MIN_TOTAL steps on
     const bool wide = c->wide && emis && c->n <= 64 && c->opt.filter_parallel != 0 &&
                       (c->opt.filter_parallel == 1 || c->total >= FILTER_WIDE_MIN_TOTAL);
-    c->last.filter_path = fused ? 1 : (wide ? 2 : 0);
+    // 65..128 states on loaded observations (as bhmm_score decides): always, never, or from FILTER_TILE_MIN_TOTAL
+    // steps on
+    const bool tile = c->gen && c->n <= 128 && emis && c->opt.filter_parallel != 0 && c->opt.filter_tile != 0 &&
+                      (c->opt.filter_tile == 1 || c->total >= FILTER_TILE_MIN_TOTAL);
+    c->last.filter_path = fused ? 1 : (wide ? 2 : (tile ? 3 : 0));
     c->last.filter_segments = 0;
+    c->last.filter_redone = 0;
     bool verified = false;
-    if (wide) {
+    if (tile) {
+        if ((rc = c->kind == EMIT_GAUSS ? TileFilt<EMIT_GAUSS>::run(c, A, pi, par0, par1, o, &verified)
+                                        : TileFilt<EMIT_DISC>::run(c, A, pi, par0, par1, o, &verified)))
+            return rc;
+    } else if (wide) {
         if ((rc = WideFilt::run(c, A, pi, par0, par1, o, &verified)))
             return rc;
     } else if (fused) {

@@ -24,7 +24,8 @@
 //                   (k_filter_wide, filter_wide_kernels.hpp); k_filter_first_dead serves both plans.
 //   k_filter_serial the exact path: one workgroup per trajectory, the serial recursion of k_score_serial with the
 //                   states spread over the threads; writes the normalised row (or its projection) and log c_t
-//                   every step.  Any n and explicit pobs; for N <= 8 the fallback after two failed checks.
+//                   every step.  Any n and explicit pobs; for N <= 8 the fallback after two failed checks.  With a
+//                   table `only`: the marked trajectories alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -308,17 +309,22 @@ __global__ __launch_bounds__(64) void k_filter_seg_bury(const FiltSegs sg, const
 // ---- exact path ----------------------------------------------------------------------------
 // grid K, blockDim a multiple of 64 with n <= SCORE_SERIAL_R * blockDim; LDS: n + 16 doubles.  Model: A [n][n],
 // pi [n], par0 [n] (gaussian mu) / [n][M] (discrete B), par1 [n] (gaussian sigma).  Explicit pobs: obs_rm holds
-// n doubles per step, read as given.  rows: [total][Q > 0 ? Q : n] or nullptr; logc: [total] or nullptr
+// n doubles per step, read as given.  rows: [total][Q > 0 ? Q : n] or nullptr; logc: [total] or nullptr.
+// only: nullptr (every trajectory), or one byte per trajectory -- a workgroup whose trajectory is not marked returns
+// at once (filter_path 3: the trajectories with a segment outside the range of k_filter_tile)
 template <int KIND, typename OT>
 __global__ __launch_bounds__(1024) void k_filter_serial(int n, int M, const int64_t *__restrict__ offsets,
                                                         const void *__restrict__ obs_rm, const double *__restrict__ A,
                                                         const double *__restrict__ pi, const double *__restrict__ par0,
                                                         const double *__restrict__ par1, const double *__restrict__ V,
-                                                        int Q, OT *__restrict__ rows, OT *__restrict__ logc)
+                                                        int Q, OT *__restrict__ rows, OT *__restrict__ logc,
+                                                        const uint8_t *__restrict__ only)
 {
     extern __shared__ double sh[];
     double *alpha = sh, *red = sh + n;
     const int k = blockIdx.x;
+    if (only != nullptr && only[k] == 0) // (uniform over the workgroup)
+        return;
     const int64_t base = offsets[k], T = offsets[k + 1] - base;
     const int bd = blockDim.x, tid = threadIdx.x;
     const int Qp = Q > 0 ? Q : n;

@@ -1,6 +1,7 @@
 // host_internal.hpp -- functions one translation unit of libbhmm_amd.so calls in another.  Every defining
 // unit includes this header as well, so the compiler checks each declaration against its definition.
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 #include <functional>
@@ -42,6 +43,29 @@ int specres_read(bhmm_ctx *c, int words = 4, bool wait = true);
 int estep_f32(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
               double *stats_dev, int flags, bool *done);
 
+// ---- score_api.hip / filter_api.hip: calibration of the warm-up at 65..128 states (Tile::calibrate, TileFilt) ----
+constexpr int SCORE_TILE_W0 = 32;            // the two warm-ups the calibration runs at
+constexpr int SCORE_TILE_W1 = 64;
+constexpr double SCORE_TILE_DEV_OK = 3e-13;  // boundary deviation that needs no longer warm-up (tile_gen.hip)
+constexpr double SCORE_TILE_DEV_GOAL = 1e-13; // the deviation the decay is extrapolated to
+constexpr double SCORE_TILE_MARGIN = 1.25;   // safety factor on the extrapolated decay (tile_gen.hip)
+constexpr int SCORE_TILE_W_SLOW = 1024;      // no decay between the two warm-ups: this one, the check decides
+constexpr int SCORE_TILE_W_MAX = 1 << 20;
+// the warm-up from the largest boundary deviations d0, d1 of the passes at SCORE_TILE_W0 and SCORE_TILE_W1 (d1 not
+// good enough as it is): the geometric decay between the two extrapolated to SCORE_TILE_DEV_GOAL, times the
+// margin, rounded up to 8
+inline int score_tile_extrapolate(double d0, double d1)
+{
+    d0 = d0 > 1e-300 ? d0 : 1e-300;
+    d1 = d1 > 1e-300 ? d1 : 1e-300;
+    if (!(d1 < 0.5 * d0))
+        return SCORE_TILE_W_SLOW;
+    const double rate = log(d0 / d1) / (double)(SCORE_TILE_W1 - SCORE_TILE_W0); // per step
+    const double w = SCORE_TILE_W1 + SCORE_TILE_MARGIN * log(d1 / SCORE_TILE_DEV_GOAL) / rate;
+    const double w8 = (ceil(w) + 7.0) / 8.0;
+    return (int)(w8 < SCORE_TILE_W_MAX / 8 ? w8 : SCORE_TILE_W_MAX / 8) * 8;
+}
+
 // ---- filter_api.hip (bhmm_filter) ----
 // Steps of an observation set from which a call at 9..64 states takes the time-parallel path by itself (option
 // filter_parallel = -1; read-only option filter_wide_min_total).  To be the break-even against k_filter_serial of
@@ -50,6 +74,12 @@ int estep_f32(bhmm_ctx *c, const double *A, const double *pi, const double *par0
 // default call on 23734 steps.  The scan puts the break-even below 4096 steps (64 states: 28.4 ms against 2.4 ms
 // there), so this is the floor, not the break-even; lowering it also owns that test.
 constexpr int64_t FILTER_WIDE_MIN_TOTAL = 32768;
+// The same for 65..128 states (k_filter_tile, option filter_tile = -1; read-only option filter_tile_min_total): the
+// break-even against k_filter_serial at 128 states (tools/filter_time.py --only tile, the scan in DESIGN.md section
+// 16), rounded up to a power of two and not below 32768: tests/test_filter_gpu.py::test_parity_serial pins the
+// serial kernel for a default call at 100 states on 23734 steps.  The scan puts the break-even below 4096 steps
+// (128 states: 50.0 ms against 2.5 ms there), so this is the floor, not the break-even.
+constexpr int64_t FILTER_TILE_MIN_TOTAL = 32768;
 
 // ---- wide_api.hip (9..64 states) ----
 int wide_alloc(bhmm_ctx *c);

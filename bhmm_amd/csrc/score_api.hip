@@ -499,12 +499,7 @@ int run_wide(bhmm_ctx *c, int S, const double *A, const double *pi, const double
 
 // ---- 65..128 states ----------------------------------------------------------------------------
 
-constexpr int SCORE_TILE_W0 = 32;            // the two warm-ups the calibration runs at
-constexpr int SCORE_TILE_W1 = 64;
-constexpr double SCORE_TILE_DEV_OK = 3e-13;  // boundary deviation that needs no longer warm-up (tile_gen.hip)
-constexpr double SCORE_TILE_MARGIN = 1.25;   // safety factor on the extrapolated decay (tile_gen.hip)
-constexpr int SCORE_TILE_W_SLOW = 1024;      // no decay between the two warm-ups: this one, the check decides
-constexpr int SCORE_TILE_W_MAX = 1 << 20;
+// (SCORE_TILE_W0 .. SCORE_TILE_W_MAX, the constants of the calibration: host_internal.hpp, shared with bhmm_filter)
 
 // the segment plan and the tile table of scoring on this observation set: made once (and again when
 // score_seglen changes), never after a check
@@ -599,8 +594,9 @@ struct Tile {
 
     // Warm-up of every model of the batch, the way tile_gen.hip calibrates the E-step's: the kernel itself at two
     // warm-ups, the largest boundary deviation of each, and the geometric decay between the two (the filter
-    // forgets its start vector) extrapolated to 1e-13, times SCORE_TILE_MARGIN.  A function of the model, the
-    // observation set and the plan: every model is measured on its own counters.
+    // forgets its start vector) extrapolated to 1e-13, times SCORE_TILE_MARGIN (score_tile_extrapolate in
+    // host_internal.hpp).  A function of the model, the observation set and the plan: every model is measured on
+    // its own counters.
     static int calibrate(bhmm_ctx *c, int Sb, ScoreTileModel *dm, std::vector<ScoreTileModel> &m, std::vector<int> &W)
     {
         std::vector<Verdict> v0(Sb), v1(Sb);
@@ -620,16 +616,7 @@ struct Tile {
         for (int s = 0; s < Sb; ++s) {
             if (good(v0[s]) || v0[s].range != 0)
                 continue; // (outside the range: the pass that follows sends the model to the serial recursion)
-            const double d0 = std::max((double)v0[s].dev, 1e-300), d1 = std::max((double)v1[s].dev, 1e-300);
-            if (good(v1[s])) {
-                W[s] = SCORE_TILE_W1;
-            } else if (d1 < 0.5 * d0) {
-                const double rate = log(d0 / d1) / (double)(SCORE_TILE_W1 - SCORE_TILE_W0); // per step
-                const double w = SCORE_TILE_W1 + SCORE_TILE_MARGIN * log(d1 / 1e-13) / rate;
-                W[s] = (int)std::min<double>((std::ceil(w) + 7.0) / 8.0, SCORE_TILE_W_MAX / 8) * 8;
-            } else {
-                W[s] = SCORE_TILE_W_SLOW;
-            }
+            W[s] = good(v1[s]) ? SCORE_TILE_W1 : score_tile_extrapolate((double)v0[s].dev, (double)v1[s].dev);
         }
         return BHMM_OK;
     }

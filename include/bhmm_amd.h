@@ -234,7 +234,7 @@ int bhmm_posterior_marginals(bhmm_ctx *ctx, const double *A, const double *pi, c
      rows[(offset_k + t) * Q' + q], trajectory-major as bhmm_posterior_marginals writes them:
        V == NULL, Q == 0 : Q' = N, the row is P(s_t = . | o_0 .. o_t) and sums to one;
        V[N*Q] row-major, 1 <= Q <= 8 : Q' = Q, the row is sum_i P(s_t = i | o_0 .. o_t) * V[i*Q + q], accumulated
-         over i in ASCENDING order in fp64 (fused multiply-add; filter_path 2: see below);
+         over i in ASCENDING order in fp64 (fused multiply-add; filter_path 2 and 3: see below);
      logc[offset_k + t] = log p(o_t | o_0 .. o_{t-1}); logc[offset_k] = log sum_i pi_i p_0(i) (pi is not
        normalised, as in the reference's forward); their sum over a trajectory is its log-likelihood.
    Either output may be NULL, not both.  From the first step of a trajectory whose probability is zero on, its
@@ -252,14 +252,23 @@ int bhmm_posterior_marginals(bhmm_ctx *ctx, const double *A, const double *pi, c
    plan that belongs to filtering alone, with the same verified warm-up boundaries (filter_path 2) -- taken when
    the option filter_parallel is 1, or -1 (the default) and the loaded set has at least filter_wide_min_total
    steps; on this path the columns of a projection are summed over i by a fixed tree, not in ascending order.
-   Everything else (65 states and more, explicit pobs, filter_parallel 0, smaller sets): the serial recursion, one
-   workgroup per trajectory (filter_path 0; at most 4096 states).
-   Options: filter_W (warm-up in steps, 0 = measured); filter_seglen (9 to 64 states: segment length of the plan
+   65 to 128 states (gaussian, discrete, loaded observations): the same recursion on the fp64 matrix cores,
+   k_filter_tile, over a segment plan and tile table of its own (filter_path 3) -- taken when filter_parallel is
+   not 0 and the option filter_tile is 1, or -1 (the default) and the loaded set has at least
+   filter_tile_min_total steps.  A trajectory with a segment that leaves the number range of that kernel
+   (probability zero, an outlier whose densities all underflow, a NaN observation) is done again, whole, by the
+   serial recursion, the others stand (filter_redone counts them); the columns of a projection are summed by a
+   fixed tree here too.
+   Everything else (more than 128 states, explicit pobs, filter_parallel or filter_tile 0, smaller sets): the
+   serial recursion, one workgroup per trajectory (filter_path 0; at most 4096 states).
+   Options: filter_W (warm-up in steps, 0 = measured); filter_seglen (9 to 128 states: segment length of the plan
    from the next call on, rounded up to a multiple of four; 0 = automatic); filter_parallel (-1, 0, 1: above);
+   filter_tile (-1, 0, 1: above);
    read-only filter_fallbacks (calls whose boundaries did not verify at the first warm-up: they run again with
-   twice the warm-up, then take the serial path), filter_path (first pass of the last call: 2 time segments,
-   1 fused, 0 serial), filter_segments (segments of the plan the last call ran on; 0: another path) and
-   filter_wide_min_total.
+   twice the warm-up, then take the serial path), filter_path (first pass of the last call: 3 matrix cores,
+   2 time segments, 1 fused, 0 serial), filter_segments (segments of the plan the last call ran on; 0: another
+   path), filter_redone (filter_path 3: trajectories of the last call done again on the serial recursion),
+   filter_wide_min_total and filter_tile_min_total.
    Nothing of the state that E-step, Viterbi, sampling, scoring, decoding and marginals calls use is read or
    written. */
 #define BHMM_FILT_F32 1

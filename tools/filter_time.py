@@ -16,8 +16,14 @@ float32 to the device, logc alone to the device, a Q = 1 projection to the devic
 filter_parallel = 0 (k_filter_serial, which is also what the commit before this path ran), Engine.score with one
 model (the floor) and posterior_marginals in the same form.  Block scan: one long 64-state trajectory of 4096,
 16384, 65536 and 262144 steps under filter_parallel 0 and 1 -- the break-even behind FILTER_WIDE_MIN_TOTAL.
+Block tile (the matrix-core path for 65 to 128 states, k_filter_tile): 128 states, 128 x 1e4 gaussian (the shape of
+tools/score_time.py's g128) and 100 states discrete, M = 64, on the same 128 x 1e4 steps, in the four forms of the
+c3 block under filter_tile 1 against 0 (k_filter_serial, which is also what the commit before this path ran), with
+Engine.score with one model as the floor; then the scan behind FILTER_TILE_MIN_TOTAL: the first 4096 .. 1.28e6
+steps of the 128-state set as trajectories of 1e4 steps (one shorter one for 4096), float32 rows and logc to the
+device, filter_tile 1 against 0.
 One JSON object per configuration, printed and appended to profiles/filter/filter_time.json.  Options: --only
-c1|c2|c3|g32|g16|scan, --reps R, --sub N, --fwd N, --label TEXT (a "build" field in every line), --filter-only (the device forms
+c1|c2|c3|g32|g16|scan|tile, --reps R, --sub N, --fwd N, --label TEXT (a "build" field in every line), --filter-only (the device forms
 alone: the workload of a rocprofv3 --kernel-trace --stats pass)."""
 import argparse
 import json
@@ -31,7 +37,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from score_time import c1_setup, c2_setup, c3_setup, g16_setup, g32_setup  # noqa: E402
+from score_time import c1_setup, c2_setup, c3_setup, g16_setup, g32_setup, g128_setup  # noqa: E402
 from bhmm_amd.engine import Engine  # noqa: E402
 
 
@@ -168,6 +174,70 @@ def scan_block(args):
         del t32, l32
 
 
+def tile_forms_block(args, name, eng, model, total):
+    """the four forms under filter_tile 1 and 0, Engine.score with one model as the floor"""
+    n = eng.nstates
+    V = np.arange(n, dtype=float)[:, None]
+    line = dict(build=args.label, config=name, trajectories=len(eng.lengths), steps=total, reps=args.reps)
+    eng.set_option("filter_tile", 1)
+    if args.filter_only:
+        wide_forms(eng, model, V, 1, line, "tile")
+        return
+    wide_forms(eng, model, V, args.reps, line, "tile")
+    line["tile_redone"] = eng.get_option("filter_redone")
+    eng.set_option("filter_tile", 0)
+    wide_forms(eng, model, V, args.reps, line, "serial")
+    line.update(stats("score_one_model", timed_all(lambda: eng.score([model]), args.reps)))
+    line["score_path"] = eng.get_option("score_path")
+    for form in ("f64_host", "f32_dev", "logc_dev", "q1_dev"):
+        line["serial_over_tile_" + form] = line["serial_%s_ms" % form] / line["tile_%s_ms" % form]
+    line["tile_logc_dev_over_score"] = line["tile_logc_dev_ms"] / line["score_one_model_ms"]
+    line["tile_f32_dev_over_score"] = line["tile_f32_dev_ms"] / line["score_one_model_ms"]
+    emit(args, line)
+
+
+def tile_block(args):
+    name, eng, models, obs, total = g128_setup()
+    model, n = models[0], eng.nstates
+    tile_forms_block(args, name, eng, model, total)
+    eng.close()
+    # 100 states, discrete, M = 64, the same number of steps
+    rng = np.random.default_rng(100)
+    K, T, nd, M = 128, 10000, 100, 64
+    A = rng.random((nd, nd)) + 0.05 + 5.0 * np.eye(nd)
+    A /= A.sum(axis=1)[:, None]
+    B = rng.random((nd, M)) + 0.01
+    B /= B.sum(axis=1)[:, None]
+    sym = torch.randint(0, M, (K * T,), dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
+    eng = Engine(0)
+    eng.set_observations_device("discrete", sym.data_ptr(), np.arange(K + 1, dtype=np.int64) * T, nd, nsymbols=M)
+    tile_forms_block(args, "100-state discrete M = 64, 128 x 1e4", eng, (A, np.full(nd, 1.0 / nd), B, None), K * T)
+    eng.close()
+    del sym
+    if args.filter_only:
+        return
+    # the break-even behind FILTER_TILE_MIN_TOTAL
+    for steps in (4096, 8192, 16384, 32768, 65536, 131072, 320000, 1280000):
+        off = np.array(sorted(set(list(range(0, steps, T)) + [steps])), dtype=np.int64)
+        eng = Engine(0)
+        eng.set_observations_device("gaussian", obs.data_ptr(), off, n)
+        t32 = torch.empty((steps, n), dtype=torch.float32, device="cuda:0")
+        l32 = torch.empty(steps, dtype=torch.float32, device="cuda:0")
+        line = dict(build=args.label, config="tile scan: 128-state gaussian, trajectories of 1e4 steps", steps=steps,
+                    trajectories=len(off) - 1, reps=args.reps)
+        for opt, key in ((0, "serial"), (1, "tile")):
+            eng.set_option("filter_tile", opt)
+            line.update(stats(key + "_f32_dev", timed_all(
+                lambda: eng.filter_states(*model, dtype=np.float32, out=t32, out_increments=l32), args.reps)))
+            line[key + "_path"] = eng.get_option("filter_path")
+        line["tile_segments"] = eng.get_option("filter_segments")
+        line["serial_over_tile"] = line["serial_f32_dev_ms"] / line["tile_f32_dev_ms"]
+        emit(args, line)
+        eng.close()
+        del t32, l32
+
+
 def emit(args, line):
     text = json.dumps(line)
     print(text, flush=True)
@@ -178,7 +248,7 @@ def emit(args, line):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=["c1", "c2", "c3", "g32", "g16", "scan"])
+    ap.add_argument("--only", choices=["c1", "c2", "c3", "g32", "g16", "scan", "tile"])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sub", type=int, default=32, help="trajectories of configs[2] that are filtered")
     ap.add_argument("--fwd", type=int, default=2, help="trajectories the hidden.forward route is timed on")
@@ -191,7 +261,9 @@ def main():
             wide_block(args, setup)
     if args.only == "scan":
         scan_block(args)
-    if args.only in ("c3", "g32", "g16", "scan"):
+    if args.only == "tile":
+        tile_block(args)
+    if args.only in ("c3", "g32", "g16", "scan", "tile"):
         return
     for key, setup in (("c1", c1_setup), ("c2", c2_setup)):
         if args.only and key != args.only:
