@@ -13,6 +13,7 @@
 #include "host_common.hpp"
 #include "host_internal.hpp"
 #include "plan.hpp"
+#include "seg_host.hpp"
 #include "estep_sweep.hpp"
 
 namespace bhmm {
@@ -341,45 +342,19 @@ struct Runner {
         if (!(target > 0.0))
             target = 0.01 * c->opt.spec_tol; // (default: 1e-13)
         *W_out = 0;
-        const int64_t maxT = longest_traj(c);
-        const int Wmax = (int)std::min<int64_t>(1024, maxT / 2) / 4 * 4;
-        if (Wmax < 32)
+        const int Wmax = plan::probe_wmax(longest_traj(c));
+        if (Wmax == 0)
             return BHMM_OK;
-        std::vector<int> longk;
-        for (int k = 0; k < c->K; ++k)
-            if (c->offsets[k + 1] - c->offsets[k] >= Wmax)
-                longk.push_back(k);
-        const int S = 256;
-        std::vector<int64_t> starts(S);
-        for (int i = 0; i < S; ++i) {
-            const int k = longk[i % longk.size()];
-            const int64_t room = c->offsets[k + 1] - c->offsets[k] - Wmax + 1;
-            const int64_t rep = i / (int64_t)longk.size(), reps = (S + longk.size() - 1) / longk.size();
-            starts[i] = c->offsets[k] + (room - 1) * rep / std::max<int64_t>(reps - 1, 1);
-        }
-        const size_t bytes = S * sizeof(int64_t) + 2 * (size_t)Wmax * sizeof(unsigned int);
+        Probe pr;
         int rc;
-        if ((rc = c->d_probe.ensure(bytes)))
+        if ((rc = probe_stage(c, c->d_probe, Wmax, 1, pr)))
             return rc;
-        int64_t *d_starts = reinterpret_cast<int64_t *>(c->d_probe.p);
-        unsigned int *d_curve = reinterpret_cast<unsigned int *>(d_starts + S);
-        BHMM_HIP(hipMemcpyAsync(d_starts, starts.data(), S * sizeof(int64_t), hipMemcpyHostToDevice,
-                                c->stream));
-        BHMM_HIP(hipMemsetAsync(d_curve, 0, 2 * (size_t)Wmax * sizeof(unsigned int), c->stream));
-        BHMM_HIP(launch(k_forget_probe<N, KIND>, dim3((2 * S + 63) / 64), dim3(64), 0, c->stream, m, c->d_obs_rm.p,
-                        c->d_Bt.p, d_starts, S, Wmax, d_curve));
-        std::vector<float> curve(2 * (size_t)Wmax);
-        BHMM_HIP(hipMemcpyAsync(curve.data(), d_curve, curve.size() * sizeof(float),
-                                hipMemcpyDeviceToHost, c->stream));
-        BHMM_HIP(hipStreamSynchronize(c->stream)); // starts / curve are temporaries
-        int last = -1;
-        for (int w = 0; w < Wmax; ++w)
-            if (std::max(curve[w], curve[Wmax + w]) >= (float)target)
-                last = w;
-        int W = last + 2; // steps needed to get below the target and stay there
-        W = (int)std::ceil(1.15 * W);
-        W = std::max(16, (W + 3) / 4 * 4);
-        *W_out = std::min(W, Wmax);
+        BHMM_HIP(launch(k_forget_probe<N, KIND>, dim3((2 * PROBE_P + 63) / 64), dim3(64), 0, c->stream, m,
+                        c->d_obs_rm.p, c->d_Bt.p, pr.d_starts, PROBE_P, Wmax, pr.d_curve));
+        std::vector<float> curve;
+        if ((rc = probe_read(c, pr, curve)))
+            return rc;
+        *W_out = plan::warmup_of(plan::curve_last(curve.data(), Wmax, (float)target, true), Wmax);
         return BHMM_OK;
     }
 

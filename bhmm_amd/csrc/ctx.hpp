@@ -64,6 +64,15 @@ struct DevBuf {
     }
 };
 
+// Device tables of one segment plan of a forward-only pass (bhmm_score, bhmm_filter; made and uploaded by
+// make_seg_tables, seg_host.hpp): trajectory, length and start of every segment, the first segment of every
+// trajectory [K + 1] and, at 65..128 states, the segment of every tile row [16 * tiles]
+struct SegTables {
+    DevBuf<int32_t> seg_traj, seg_len, seg_traj0;
+    DevBuf<int64_t> seg_t0;
+    DevBuf<int32_t> tile_seg;
+};
+
 } // namespace bhmm
 
 // The fields are grouped by lifetime: `opt` holds what the caller sets (bhmm_ctx_set_option, environment at
@@ -178,20 +187,20 @@ struct bhmm_ctx {
         int tile_W_good = 0;             // ... the last warm-up that verified
         int f32_W = 0;                   // fp32 E-step (estep_f32.hip): warm-up read off the forgetting curve at
                                          // 0.01 f32_tol (0: not measured yet), doubled after a failed check
-        // bhmm_score, 9..128 states: its own segment plan (tables in score.seg_*; 65..128 states: and the tile table
-        // score.tile_seg), made at the first score call on these observations from the offsets, the state count and
+        // bhmm_score, 9..128 states: its own segment plan (tables in score.seg; 65..128 states: and the tile table
+        // score.seg.tile_seg), made at the first score call on these observations from the offsets, the state count and
         // the device alone -- never re-made after a check
         int score_nseg = 0;              // segments of the plan (0: not made yet)
         int score_ntraj = 0;             // ... trajectories with at least one step (nseg == ntraj: no boundary)
         int score_seglen_opt = 0;        // ... opt.score_seglen it was made for
         int score_ntiles = 0;            // ... 65..128 states: tiles of 16 segments (k_score_tile)
-        // bhmm_filter, 9..64 states: its own segment plan (tables in filt.seg_*), made at the first eligible filter
+        // bhmm_filter, 9..64 states: its own segment plan (tables in filt.seg), made at the first eligible filter
         // call on these observations from the offsets, the state count and the device alone -- never after a check
         int filt_nseg = 0;               // segments of the plan (0: not made yet)
         int filt_ntraj = 0;              // ... trajectories with at least one step (nseg == ntraj: no boundary)
         int filt_seglen_opt = 0;         // ... opt.filter_seglen it was made for
-        // bhmm_filter, 65..128 states: the segment plan and tile table of k_filter_tile (tables in filt.tseg_* and
-        // filt.tile_seg), made the same way; neither the score plan nor the plan above
+        // bhmm_filter, 65..128 states: the segment plan and tile table of k_filter_tile (tables in filt.tseg, with its
+        // tile_seg), made the same way; neither the score plan nor the plan above
         int filt_tile_nseg = 0;          // segments of the plan (0: not made yet)
         int filt_tile_ntraj = 0;         // ... trajectories with at least one step (nseg == ntraj: no boundary)
         int filt_tile_ntiles = 0;        // ... tiles of 16 segments
@@ -339,11 +348,10 @@ struct bhmm_ctx {
         bhmm::DevBuf<double> Bt, logLc, aentry, aexit, logLk, par;
         bhmm::DevBuf<int32_t> W;
         bhmm::DevBuf<unsigned int> fails;
-        // 9..64 states: parameter blocks of the batch's models, tables of the plan ds.score_nseg counts
+        // 9..128 states: parameter blocks of the batch's models, tables of the plan ds.score_nseg counts (65..128
+        // states: with the tile table, [16 * ds.score_ntiles])
         bhmm::DevBuf<double> wpar;
-        bhmm::DevBuf<int32_t> seg_traj, seg_len, seg_traj0;
-        bhmm::DevBuf<int64_t> seg_t0;
-        bhmm::DevBuf<int32_t> tile_seg;  // 65..128 states: segment of every tile row, [16 * ds.score_ntiles]
+        bhmm::SegTables seg;
     } score;
     // bhmm_posterior_decode (post_api.hip): its own buffers -- model, B^T, alpha-row workspace of one range of
     // chunk groups, boundary vectors of both directions, failure counter, probe curve, and the results on the
@@ -367,8 +375,8 @@ struct bhmm_ctx {
     // is all zero and per trajectory the first of them, failure counter, probe curve, the projection matrix V, the
     // parameters of the serial path, and the two results staged on the device when the caller's buffers are on
     // the host (rows, logc); 9..64 states: the model's parameter block and the tables of the plan ds.filt_nseg
-    // counts (dead / first_dead then count segments); 65..128 states: the tables of the plan ds.filt_tile_nseg
-    // counts (tseg_*, tile_seg), dead is then the range flag of every segment, redo the trajectories to do again and
+    // counts (seg; dead / first_dead then count segments); 65..128 states: the tables of the plan ds.filt_tile_nseg
+    // counts (tseg), dead is then the range flag of every segment, redo the trajectories to do again and
     // fails the words of k_filter_tile_check / k_filter_tile_redo; nothing else reads them
     struct FiltBufs {
         bhmm::DevBuf<char> model, probe, rows, logc;
@@ -377,10 +385,7 @@ struct bhmm_ctx {
         bhmm::DevBuf<int32_t> first_dead;
         bhmm::DevBuf<unsigned int> fails;
         bhmm::DevBuf<double> wpar;
-        bhmm::DevBuf<int32_t> seg_traj, seg_len, seg_traj0;
-        bhmm::DevBuf<int64_t> seg_t0;
-        bhmm::DevBuf<int32_t> tseg_traj, tseg_len, tseg_traj0, tile_seg;
-        bhmm::DevBuf<int64_t> tseg_t0;
+        bhmm::SegTables seg, tseg;
         bhmm::DevBuf<uint8_t> redo;
     } filt;
 

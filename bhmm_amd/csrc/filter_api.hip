@@ -34,6 +34,12 @@
 // Everything else (more than 128 states, explicit pobs, filter_parallel / filter_tile 0 or a small set;
 // filter_path 0): k_filter_serial, one workgroup per trajectory.
 //
+// The three verified paths run one protocol (two_attempts): a pass at the measured warm-up, and after boundaries
+// that did not verify one more at twice that.  What they share with bhmm_score and the posterior calls is in
+// seg_host.hpp (device side) and plan.hpp (arithmetic): the constants of the protocol, the probe's sample positions,
+// staging and reading, the parameter block of a WideModel (fill_wide_block) and the making of a plan's tables
+// (make_seg_tables into c->filt.seg at 9..64 states, c->filt.tseg at 65..128).
+//
 // Nothing here reads or writes the state other calls use: the buffers are c->filt.*, the plans' sizes
 // ds.filt_*, the only other fields touched are opt.filter_* (read) and last.filter_*.  Host results are staged in c->filt.rows / c->filt.logc and
 // cross the link in ONE copy each, after the boundaries verified (a pageable buffer of 8 MiB or more is pinned
@@ -54,6 +60,7 @@
 #include "launch.hpp"
 #include "model_check.hpp"
 #include "plan.hpp"
+#include "seg_host.hpp"
 
 namespace bhmm {
 FILTER_TILE_LAUNCH_DECL(extern, 5)
@@ -62,10 +69,8 @@ FILTER_TILE_LAUNCH_DECL(extern, 7)
 FILTER_TILE_LAUNCH_DECL(extern, 8)
 namespace {
 
-constexpr double FILTER_TOL = 1e-11;         // boundary check: componentwise relative (bhmm_score's)
-constexpr int FILTER_W_UNPROBED = 288;       // warm-up when the trajectories are too short to probe (bhmm_score's)
-constexpr size_t FILTER_LDS_BT = 16 * 1024;  // B^T staged in LDS up to this size
-constexpr double FILTER_WIDE_MARGIN = 1.5;   // 9..64 states: warm-up over the probe's reading (bhmm_score's factor)
+// (BOUNDARY_TOL, W_UNPROBED, LDS_BT_MAX, the probe and the plan: seg_host.hpp, shared with bhmm_score and the
+// posterior calls)
 
 struct Out {          // where the results go on the device, and what they are
     void *rows;       // [total][Qp] of double / float, or nullptr
@@ -83,42 +88,41 @@ template <int N, int KIND>
 int filter_probe(bhmm_ctx *c, const Model<N> &m, const double *dBt, int *W)
 {
     *W = 0;
-    const int64_t maxT = longest_traj(c);
-    const int Wmax = (int)std::min<int64_t>(1024, maxT / 2) / 4 * 4;
-    if (Wmax < 32)
+    const int Wmax = plan::probe_wmax(longest_traj(c));
+    if (Wmax == 0)
         return BHMM_OK;
-    std::vector<int> longk;
-    for (int k = 0; k < c->K; ++k)
-        if (c->offsets[k + 1] - c->offsets[k] >= Wmax)
-            longk.push_back(k);
-    const int P = 256;
-    std::vector<int64_t> starts(P);
-    for (int i = 0; i < P; ++i) {
-        const int k = longk[i % longk.size()];
-        const int64_t room = c->offsets[k + 1] - c->offsets[k] - Wmax + 1;
-        const int64_t rep = i / (int64_t)longk.size(), reps = (P + longk.size() - 1) / longk.size();
-        starts[i] = c->offsets[k] + (room - 1) * rep / std::max<int64_t>(reps - 1, 1);
-    }
-    const size_t curve_words = 2 * (size_t)Wmax; // forward | backward (the kernel's layout)
+    Probe pr;
     int rc;
-    if ((rc = c->filt.probe.ensure(P * sizeof(int64_t) + curve_words * sizeof(unsigned int))))
+    if ((rc = probe_stage(c, c->filt.probe, Wmax, 1, pr)))
         return rc;
-    int64_t *d_starts = reinterpret_cast<int64_t *>(c->filt.probe.p);
-    unsigned int *d_curve = reinterpret_cast<unsigned int *>(d_starts + P);
-    BHMM_HIP(hipMemcpyAsync(d_starts, starts.data(), P * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemsetAsync(d_curve, 0, curve_words * sizeof(unsigned int), c->stream));
-    BHMM_HIP(launch(k_forget_probe<N, KIND>, dim3((2 * P + 63) / 64), dim3(64), 0, c->stream, m, c->d_obs_rm.p,
-                    KIND == EMIT_DISC ? dBt : nullptr, d_starts, P, Wmax, d_curve));
-    std::vector<float> curve(Wmax); // the forward direction: the first Wmax entries
-    BHMM_HIP(hipMemcpyAsync(curve.data(), d_curve, curve.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    BHMM_HIP(hipStreamSynchronize(c->stream));
-    const float target = (float)(0.01 * FILTER_TOL);
-    int last = -1;
-    for (int w = 0; w < Wmax; ++w)
-        if (curve[w] >= target)
-            last = w;
-    const int w = (int)std::ceil(1.15 * (last + 2));
-    *W = 2 * std::min(std::max(16, (w + 3) / 4 * 4), Wmax);
+    BHMM_HIP(launch(k_forget_probe<N, KIND>, dim3((2 * PROBE_P + 63) / 64), dim3(64), 0, c->stream, m, c->d_obs_rm.p,
+                    KIND == EMIT_DISC ? dBt : nullptr, pr.d_starts, PROBE_P, Wmax, pr.d_curve));
+    std::vector<float> curve;
+    if ((rc = probe_read(c, pr, curve)))
+        return rc;
+    *W = 2 * plan::warmup_of(plan::curve_last(curve.data(), Wmax, (float)(0.01 * BOUNDARY_TOL), false), Wmax);
+    return BHMM_OK;
+}
+
+// The protocol of a verified pass: `pass` at warm-up W (its boundaries out of tolerance to *fails); none -> the
+// results stand (*verified); else the call counts one fallback and runs once more with twice the warm-up, at most
+// Wcap.  *verified false: the caller takes the serial path
+template <class Pass>
+int two_attempts(bhmm_ctx *c, int W, int Wcap, Pass pass, bool *verified)
+{
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        unsigned int fails = 0;
+        int rc;
+        if ((rc = pass(W, &fails)))
+            return rc;
+        if (fails == 0) {
+            *verified = true;
+            return BHMM_OK;
+        }
+        if (attempt == 0)
+            ++c->last.filter_fallbacks; // boundaries that did not verify at the first warm-up
+        W = (int)std::min<int64_t>(2 * (int64_t)W, Wcap);
+    }
     return BHMM_OK;
 }
 
@@ -140,7 +144,7 @@ struct Fused {
         const int G = c->G, groups = c->Gp / 64;
         const Chunks ch = chunks_of(c);
         const size_t lds_bt = (size_t)c->M * score_bt_stride(N) * sizeof(double);
-        const bool bt_lds = KIND == EMIT_DISC && lds_bt <= FILTER_LDS_BT;
+        const bool bt_lds = KIND == EMIT_DISC && lds_bt <= LDS_BT_MAX;
         const bool proj = o.Q > 0 && o.rows != nullptr;
         BHMM_HIP(hipMemsetAsync(b.fails.p, 0, sizeof(unsigned int), c->stream));
         auto *kern = proj ? (o.logc ? kernel<OT, true, true>(bt_lds) : kernel<OT, true, false>(bt_lds))
@@ -152,7 +156,7 @@ struct Fused {
             BHMM_HIP(launch(k_filter_first_dead, dim3(c->K), dim3(64), 0, c->stream, c->d_traj_c0.p, b.dead.p,
                             b.first_dead.p));
             BHMM_HIP(launch(k_filter_check<N>, dim3((G + 255) / 256), dim3(256), 0, c->stream, ch, G, b.aentry.p,
-                            b.aexit.p, b.first_dead.p, FILTER_TOL, b.fails.p));
+                            b.aexit.p, b.first_dead.p, BOUNDARY_TOL, b.fails.p));
             BHMM_HIP(launch(k_filter_bury<OT>, dim3((G + 255) / 256), dim3(256), 0, c->stream, ch, G, b.first_dead.p,
                             static_cast<OT *>(o.rows), o.Qp, static_cast<OT *>(o.logc)));
         }
@@ -191,22 +195,14 @@ struct Fused {
         if (W <= 0) {
             if ((rc = filter_probe<N, KIND>(c, m, b.Bt.p, &W)))
                 return rc;
-            W = W > 0 ? W : FILTER_W_UNPROBED;
+            W = W > 0 ? W : W_UNPROBED;
         }
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            unsigned int fails = 0;
-            rc = o.f32 ? pass<float>(c, dm, W, b.Bt.p, o, &fails) : pass<double>(c, dm, W, b.Bt.p, o, &fails);
-            if (rc)
-                return rc;
-            if (fails == 0) {
-                *verified = true;
-                return BHMM_OK;
-            }
-            if (attempt == 0)
-                ++c->last.filter_fallbacks; // boundaries that did not verify at the first warm-up
-            W = (int)std::min<int64_t>(2 * (int64_t)W, 1 << 30);
-        }
-        return BHMM_OK;
+        return two_attempts(
+            c, W, 1 << 30,
+            [&](int w, unsigned int *fails) {
+                return o.f32 ? pass<float>(c, dm, w, b.Bt.p, o, fails) : pass<double>(c, dm, w, b.Bt.p, o, fails);
+            },
+            verified);
     }
 };
 
@@ -225,27 +221,12 @@ int run_n(bhmm_ctx *c, const double *A, const double *pi, const double *par0, co
 int filter_plan(bhmm_ctx *c)
 {
     auto &d = c->ds;
-    auto &b = c->filt;
     if (d.filt_nseg > 0 && d.filt_seglen_opt == c->opt.filter_seglen)
         return BHMM_OK;
-    plan::SegPlan sp; // (plan.hpp: pure host code)
-    plan::plan_segments(c->offsets, c->K, plan::score_seglen(c->total, c->N, c->num_simd, c->opt.filter_seglen), 1,
-                        sp);
-    const size_t ns = sp.traj.size();
-    int rc;
-    if ((rc = b.seg_traj.ensure(ns)) || (rc = b.seg_len.ensure(ns)) || (rc = b.seg_t0.ensure(ns)) ||
-        (rc = b.seg_traj0.ensure(c->K + 1)))
+    int rc, ntiles;
+    if ((rc = make_seg_tables(c, c->filt.seg, plan::score_seglen(c->total, c->N, c->num_simd, c->opt.filter_seglen),
+                              false, &d.filt_nseg, &d.filt_ntraj, &ntiles)))
         return rc;
-    BHMM_HIP(hipMemcpyAsync(b.seg_traj.p, sp.traj.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemcpyAsync(b.seg_len.p, sp.len.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemcpyAsync(b.seg_t0.p, sp.t0.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemcpyAsync(b.seg_traj0.p, sp.traj0.data(), (c->K + 1) * sizeof(int32_t), hipMemcpyHostToDevice,
-                            c->stream));
-    BHMM_HIP(hipStreamSynchronize(c->stream)); // (sp is a temporary)
-    d.filt_nseg = (int)ns;
-    d.filt_ntraj = 0;
-    for (int k = 0; k < c->K; ++k)
-        d.filt_ntraj += c->offsets[k + 1] > c->offsets[k];
     d.filt_seglen_opt = c->opt.filter_seglen;
     return BHMM_OK;
 }
@@ -255,41 +236,20 @@ struct WideFilt {
     // chains within 1e-13 from then on, times 1.5, rounded up to 8
     static int probe(bhmm_ctx *c, const WideModel &m, int *W)
     {
-        *W = FILTER_W_UNPROBED;
-        const int Wmax = (int)std::min<int64_t>(8192, longest_traj(c) / 2) / 8 * 8;
-        if (Wmax < 64)
-            return BHMM_OK; // (trajectories of fewer than 128 steps)
-        std::vector<int> longk;
-        for (int k = 0; k < c->K; ++k)
-            if (c->offsets[k + 1] - c->offsets[k] >= Wmax)
-                longk.push_back(k);
-        const int P = 256;
-        std::vector<int64_t> starts(P);
-        for (int i = 0; i < P; ++i) {
-            const int k = longk[i % longk.size()];
-            const int64_t room = c->offsets[k + 1] - c->offsets[k] - Wmax + 1;
-            const int64_t rep = i / (int64_t)longk.size(), reps = (P + longk.size() - 1) / longk.size();
-            starts[i] = c->offsets[k] + (room - 1) * rep / std::max<int64_t>(reps - 1, 1);
-        }
-        const size_t curve_words = 2 * (size_t)Wmax; // (the kernel's layout: forward | backward, the latter stays zero)
+        *W = W_UNPROBED;
+        const int Wmax = plan::probe_wmax_wide(longest_traj(c));
+        if (Wmax == 0)
+            return BHMM_OK;
+        Probe pr;
         int rc;
-        if ((rc = c->filt.probe.ensure(P * sizeof(int64_t) + curve_words * sizeof(unsigned int))))
+        if ((rc = probe_stage(c, c->filt.probe, Wmax, 1, pr)) ||
+            (rc = filter_wide_probe_launch(c, c->N, m, pr.d_starts, PROBE_P, Wmax, pr.d_curve)))
             return rc;
-        int64_t *d_starts = reinterpret_cast<int64_t *>(c->filt.probe.p);
-        unsigned int *d_curve = reinterpret_cast<unsigned int *>(d_starts + P);
-        BHMM_HIP(hipMemcpyAsync(d_starts, starts.data(), P * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        BHMM_HIP(hipMemsetAsync(d_curve, 0, curve_words * sizeof(unsigned int), c->stream));
-        if ((rc = filter_wide_probe_launch(c, c->N, m, d_starts, P, Wmax, d_curve)))
+        std::vector<float> curve; // (the kernel's layout: forward | backward, the latter stays zero)
+        if ((rc = probe_read(c, pr, curve)))
             return rc;
-        std::vector<float> curve(Wmax); // the forward direction: the first Wmax entries
-        BHMM_HIP(hipMemcpyAsync(curve.data(), d_curve, curve.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        BHMM_HIP(hipStreamSynchronize(c->stream));
-        int last = -1;
-        for (int w = 0; w < Wmax; ++w)
-            if (curve[w] >= 1e-13f)
-                last = w;
-        const int w = (int)std::ceil(FILTER_WIDE_MARGIN * (last + 2));
-        *W = std::min(std::max(16, (w + 7) / 8 * 8), Wmax); // (not forgotten within Wmax: Wmax, the check decides)
+        // (not forgotten within Wmax: Wmax, the check decides)
+        *W = std::min(plan::warmup_wide_of(plan::curve_last(curve.data(), Wmax, 1e-13f, false)), Wmax);
         return BHMM_OK;
     }
 
@@ -302,11 +262,7 @@ struct WideFilt {
         FilterWideArgs a;
         a.dm = dm;
         a.W = W;
-        a.sg.traj = b.seg_traj.p;
-        a.sg.t0 = b.seg_t0.p;
-        a.sg.len = b.seg_len.p;
-        a.sg.nseg = nseg;
-        a.sg.W = W;
+        a.sg = segs_of_tables<Segs>(b.seg, nseg, W);
         a.rows = o.rows;
         a.logc = o.logc;
         a.V = o.V;
@@ -320,12 +276,12 @@ struct WideFilt {
         if ((rc = filter_wide_launch(c, c->N, a)))
             return rc;
         if (nseg > c->ds.filt_ntraj) { // (no boundary: the exact recursion, nothing after a dead segment)
-            const FiltSegs fs{b.seg_traj.p, b.seg_t0.p, b.seg_len.p, c->d_offsets.p, nseg};
+            const FiltSegs fs{b.seg.seg_traj.p, b.seg.seg_t0.p, b.seg.seg_len.p, c->d_offsets.p, nseg};
             BHMM_HIP(hipMemsetAsync(b.fails.p, 0, sizeof(unsigned int), c->stream));
-            BHMM_HIP(launch(k_filter_first_dead, dim3(c->K), dim3(64), 0, c->stream, b.seg_traj0.p, b.dead.p,
+            BHMM_HIP(launch(k_filter_first_dead, dim3(c->K), dim3(64), 0, c->stream, b.seg.seg_traj0.p, b.dead.p,
                             b.first_dead.p));
             BHMM_HIP(launch(k_filter_seg_check, dim3((nseg + 255) / 256), dim3(256), 0, c->stream, fs, c->n, b.aentry.p,
-                            b.aexit.p, b.first_dead.p, FILTER_TOL, b.fails.p));
+                            b.aexit.p, b.first_dead.p, BOUNDARY_TOL, b.fails.p));
             if (o.f32)
                 BHMM_HIP(launch(k_filter_seg_bury<float>, dim3(nseg), dim3(64), 0, c->stream, fs, b.first_dead.p,
                                 static_cast<float *>(o.rows), o.Qp, static_cast<float *>(o.logc)));
@@ -350,9 +306,8 @@ struct WideFilt {
             return rc;
         const int nseg = c->last.filter_segments = c->ds.filt_nseg;
         const bool segmented = nseg > c->ds.filt_ntraj;
-        // parameter block of the model: wide_model's layout, then B and B^T (bhmm_score's)
         const bool disc = c->kind == EMIT_DISC;
-        const size_t nB = disc ? (size_t)n * M : 0, np = (size_t)n * n + 7 * n + 2 * nB;
+        const size_t np = wide_block_size(n, M, disc, true);
         if ((rc = b.model.ensure(sizeof(ScoreWideModel))) || (rc = b.wpar.ensure(np)) ||
             (rc = b.aentry.ensure((size_t)std::max(nseg, 1) * n)) || (rc = b.aexit.ensure((size_t)std::max(nseg, 1) * n)) ||
             (rc = b.dead.ensure(std::max(nseg, 1))) || (rc = b.first_dead.ensure(std::max(K, 1))) ||
@@ -364,41 +319,7 @@ struct WideFilt {
         }
         std::vector<double> h(np, 0.0);
         ScoreWideModel m;
-        const double *dp = b.wpar.p;
-        memcpy(h.data(), A, sizeof(double) * n * n);
-        memcpy(h.data() + (size_t)n * n, pi, sizeof(double) * n);
-        WideModel &w = m.w;
-        w.A = dp;
-        w.pi = dp + (size_t)n * n;
-        w.mu = w.pi + n;
-        w.isig = w.mu + n;
-        w.cnorm = w.isig + n;
-        w.sigma = w.cnorm + n;
-        w.ga = w.sigma + n;
-        w.gb = w.ga + n;
-        w.gmg = 0.0;
-        w.B = nullptr;
-        w.n = n;
-        w.M = M;
-        m.Bt = nullptr;
-        double *q = h.data() + (size_t)n * n + n;
-        if (!disc) {
-            for (int i = 0; i < n; ++i) {
-                q[i] = par0[i];
-                q[n + i] = 1.0 / par1[i];
-                q[2 * n + i] = 1.0 / (sqrt(2.0 * M_PI) * par1[i]);
-                q[3 * n + i] = par1[i];
-            }
-            gauss_pdf_constants(n, n, par1, q + 4 * n, q + 5 * n, &w.gmg);
-        } else {
-            double *hB = q + 6 * n, *hBt = hB + nB;
-            memcpy(hB, par0, sizeof(double) * nB);
-            for (int i = 0; i < n; ++i)
-                for (int s = 0; s < M; ++s)
-                    hBt[(size_t)s * n + i] = par0[(size_t)i * M + s];
-            w.B = w.gb + n;
-            m.Bt = w.B + nB;
-        }
+        m.Bt = fill_wide_block(n, M, disc, true, A, pi, par0, par1, h.data(), b.wpar.p, m.w);
         ScoreWideModel *dm = reinterpret_cast<ScoreWideModel *>(b.model.p);
         BHMM_HIP(hipMemcpyAsync(b.wpar.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
         BHMM_HIP(hipMemcpyAsync(dm, &m, sizeof(ScoreWideModel), hipMemcpyHostToDevice, c->stream));
@@ -408,19 +329,8 @@ struct WideFilt {
         if (segmented && c->opt.filter_W <= 0 && (rc = probe(c, m.w, &W)))
             return rc;
         W = std::max(W, 8);
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            unsigned int fails = 0;
-            if ((rc = pass(c, dm, W, o, &fails)))
-                return rc;
-            if (fails == 0) {
-                *verified = true;
-                return BHMM_OK;
-            }
-            if (attempt == 0)
-                ++c->last.filter_fallbacks; // boundaries that did not verify at the first warm-up
-            W = (int)std::min<int64_t>(2 * (int64_t)W, 1 << 30);
-        }
-        return BHMM_OK;
+        return two_attempts(c, W, 1 << 30, [&](int w, unsigned int *fails) { return pass(c, dm, w, o, fails); },
+                            verified);
     }
 };
 
@@ -474,32 +384,12 @@ int serial(bhmm_ctx *c, const double *A, const double *pi, const double *par0, c
 int filter_tile_plan(bhmm_ctx *c)
 {
     auto &d = c->ds;
-    auto &b = c->filt;
     if (d.filt_tile_nseg > 0 && d.filt_tile_seglen_opt == c->opt.filter_seglen)
         return BHMM_OK;
-    plan::SegPlan sp; // (plan.hpp: pure host code)
-    plan::plan_segments(c->offsets, c->K, plan::score_tile_seglen(c->total, c->num_simd, c->opt.filter_seglen), 1, sp);
-    std::vector<int32_t> tile_seg;
-    plan::plan_tiles(sp, c->offsets, false, tile_seg);
-    const size_t ns = sp.traj.size();
     int rc;
-    if ((rc = b.tseg_traj.ensure(std::max<size_t>(ns, 1))) || (rc = b.tseg_len.ensure(std::max<size_t>(ns, 1))) ||
-        (rc = b.tseg_t0.ensure(std::max<size_t>(ns, 1))) || (rc = b.tseg_traj0.ensure(c->K + 1)) ||
-        (rc = b.tile_seg.ensure(std::max<size_t>(tile_seg.size(), 16))))
+    if ((rc = make_seg_tables(c, c->filt.tseg, plan::score_tile_seglen(c->total, c->num_simd, c->opt.filter_seglen),
+                              true, &d.filt_tile_nseg, &d.filt_tile_ntraj, &d.filt_tile_ntiles)))
         return rc;
-    BHMM_HIP(hipMemcpyAsync(b.tseg_traj.p, sp.traj.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemcpyAsync(b.tseg_len.p, sp.len.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemcpyAsync(b.tseg_t0.p, sp.t0.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemcpyAsync(b.tseg_traj0.p, sp.traj0.data(), (c->K + 1) * sizeof(int32_t), hipMemcpyHostToDevice,
-                            c->stream));
-    BHMM_HIP(hipMemcpyAsync(b.tile_seg.p, tile_seg.data(), tile_seg.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                            c->stream));
-    BHMM_HIP(hipStreamSynchronize(c->stream)); // (sp and tile_seg are temporaries)
-    d.filt_tile_nseg = (int)ns;
-    d.filt_tile_ntiles = (int)(tile_seg.size() / 16);
-    d.filt_tile_ntraj = 0;
-    for (int k = 0; k < c->K; ++k)
-        d.filt_tile_ntraj += c->offsets[k + 1] > c->offsets[k];
     d.filt_tile_seglen_opt = c->opt.filter_seglen;
     return BHMM_OK;
 }
@@ -524,12 +414,8 @@ struct TileFilt {
         BHMM_HIP(hipStreamSynchronize(c->stream)); // (m changes between passes)
         FilterTileArgs a;
         a.dm = dm;
-        a.sg.traj = b.tseg_traj.p;
-        a.sg.t0 = b.tseg_t0.p;
-        a.sg.len = b.tseg_len.p;
-        a.sg.nseg = nseg;
-        a.sg.W = W;
-        a.tp = TilePlan{b.tile_seg.p, c->ds.filt_tile_ntiles};
+        a.sg = segs_of_tables<Segs>(b.tseg, nseg, W);
+        a.tp = TilePlan{b.tseg.tile_seg.p, c->ds.filt_tile_ntiles};
         a.rows = o ? o->rows : nullptr;
         a.logc = o ? o->logc : nullptr;
         a.V = o ? o->V : nullptr;
@@ -545,11 +431,11 @@ struct TileFilt {
                             : filter_tile_launch<8, KIND>(c, a);
         if (rc)
             return rc;
-        BHMM_HIP(launch(k_filter_tile_redo, dim3(c->K), dim3(64), 0, c->stream, b.tseg_traj0.p, b.dead.p, b.redo.p,
+        BHMM_HIP(launch(k_filter_tile_redo, dim3(c->K), dim3(64), 0, c->stream, b.tseg.seg_traj0.p, b.dead.p, b.redo.p,
                         b.fails.p));
         if (nseg > c->ds.filt_tile_ntraj) // (no boundary: the exact recursion)
             BHMM_HIP(launch(k_filter_tile_check, dim3((nseg + 15) / 16), dim3(256), 0, c->stream, a.sg, n, b.aentry.p,
-                            b.aexit.p, b.redo.p, FILTER_TOL, b.fails.p));
+                            b.aexit.p, b.redo.p, BOUNDARY_TOL, b.fails.p));
         unsigned int f[FILTER_TILE_WORDS];
         BHMM_HIP(hipMemcpyAsync(f, b.fails.p, sizeof(f), hipMemcpyDeviceToHost, c->stream));
         BHMM_HIP(hipStreamSynchronize(c->stream));
@@ -587,8 +473,8 @@ struct TileFilt {
             return rc;
         const int nseg = c->last.filter_segments = c->ds.filt_tile_nseg;
         const bool segmented = nseg > c->ds.filt_tile_ntraj;
-        // parameter block of the model: wide_model's layout, then B^T (bhmm_score's)
-        const size_t nB = KIND == EMIT_DISC ? (size_t)n * M : 0, np = (size_t)n * n + 7 * n + nB;
+        constexpr bool disc = KIND == EMIT_DISC;
+        const size_t np = wide_block_size(n, M, disc, false); // (the kernel reads B^T)
         if ((rc = b.model.ensure(sizeof(ScoreTileModel))) || (rc = b.wpar.ensure(np)) ||
             (rc = b.aentry.ensure((size_t)std::max(nseg, 1) * n)) || (rc = b.aexit.ensure((size_t)std::max(nseg, 1) * n)) ||
             (rc = b.dead.ensure(std::max(nseg, 1))) || (rc = b.redo.ensure(std::max(K, 1))) ||
@@ -600,40 +486,8 @@ struct TileFilt {
         }
         std::vector<double> h(np, 0.0);
         ScoreTileModel m;
-        const double *dp = b.wpar.p;
-        memcpy(h.data(), A, sizeof(double) * n * n);
-        memcpy(h.data() + (size_t)n * n, pi, sizeof(double) * n);
-        WideModel &w = m.w;
-        w.A = dp;
-        w.pi = dp + (size_t)n * n;
-        w.mu = w.pi + n;
-        w.isig = w.mu + n;
-        w.cnorm = w.isig + n;
-        w.sigma = w.cnorm + n;
-        w.ga = w.sigma + n;
-        w.gb = w.ga + n;
-        w.gmg = 0.0;
-        w.B = nullptr; // (the kernel reads B^T)
-        w.n = n;
-        w.M = M;
-        m.Bt = nullptr;
+        m.Bt = fill_wide_block(n, M, disc, false, A, pi, par0, par1, h.data(), b.wpar.p, m.w);
         m.W = 0;
-        double *q = h.data() + (size_t)n * n + n;
-        if (KIND == EMIT_GAUSS) {
-            for (int i = 0; i < n; ++i) {
-                q[i] = par0[i];
-                q[n + i] = 1.0 / par1[i];
-                q[2 * n + i] = 1.0 / (sqrt(2.0 * M_PI) * par1[i]);
-                q[3 * n + i] = par1[i];
-            }
-            gauss_pdf_constants(n, n, par1, q + 4 * n, q + 5 * n, &w.gmg);
-        } else {
-            double *hBt = q + 6 * n;
-            for (int i = 0; i < n; ++i)
-                for (int s = 0; s < M; ++s)
-                    hBt[(size_t)s * n + i] = par0[(size_t)i * M + s];
-            m.Bt = w.gb + n;
-        }
         ScoreTileModel *dm = reinterpret_cast<ScoreTileModel *>(b.model.p);
         BHMM_HIP(hipMemcpyAsync(b.wpar.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
         BHMM_HIP(hipStreamSynchronize(c->stream)); // (h is a temporary)
@@ -642,25 +496,22 @@ struct TileFilt {
         int W = segmented ? (c->opt.filter_W + 3) & ~3 : 0;
         if (segmented && c->opt.filter_W <= 0 && (rc = calibrate(c, dm, m, &W)))
             return rc;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            Verdict v;
-            if ((rc = pass(c, dm, m, W, &o, &v)))
-                return rc;
-            if (v.fails == 0) {
+        return two_attempts(
+            c, W, SCORE_TILE_W_MAX,
+            [&](int w, unsigned int *fails) {
+                Verdict v;
+                int rc2;
+                if ((rc2 = pass(c, dm, m, w, &o, &v)) || (*fails = v.fails) != 0)
+                    return rc2;
                 // the trajectories with a segment outside the kernel's range again, whole, on the serial kernel:
                 // behind the pass, on the same stream
                 c->last.filter_redone = (int)v.redone;
-                if (v.redone != 0 && (rc = o.f32 ? serial<float>(c, A, pi, par0, par1, o, b.redo.p)
-                                                 : serial<double>(c, A, pi, par0, par1, o, b.redo.p)))
-                    return rc;
-                *verified = true;
-                return BHMM_OK;
-            }
-            if (attempt == 0)
-                ++c->last.filter_fallbacks; // boundaries that did not verify at the first warm-up
-            W = (int)std::min<int64_t>(2 * (int64_t)W, SCORE_TILE_W_MAX);
-        }
-        return BHMM_OK;
+                if (v.redone == 0)
+                    return BHMM_OK;
+                return o.f32 ? serial<float>(c, A, pi, par0, par1, o, b.redo.p)
+                             : serial<double>(c, A, pi, par0, par1, o, b.redo.p);
+            },
+            verified);
     }
 };
 

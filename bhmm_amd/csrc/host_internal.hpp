@@ -1,5 +1,7 @@
 // host_internal.hpp -- functions one translation unit of libbhmm_amd.so calls in another.  Every defining
 // unit includes this header as well, so the compiler checks each declaration against its definition.
+// (Inline host code several units share -- the protocol constants, the probe's staging, the parameter block of a
+// WideModel, the upload of a forward-only pass's plan -- is in seg_host.hpp; its arithmetic in plan.hpp.)
 #pragma once
 #include <math.h>
 #include <stdint.h>

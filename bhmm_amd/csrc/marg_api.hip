@@ -53,7 +53,7 @@ struct Fused {
         const int G = c->G, groups = c->Gp / 64;
         const Chunks ch = chunks_of(c);
         const size_t lds_bt = (size_t)c->M * score_bt_stride(N) * sizeof(double);
-        const bool bt_lds = KIND == EMIT_DISC && lds_bt <= POST_LDS_BT;
+        const bool bt_lds = KIND == EMIT_DISC && lds_bt <= LDS_BT_MAX;
         // alpha rows of one group, and how many groups the budget holds (at least one)
         const size_t per_group = (size_t)c->Lmax * N * 64 * sizeof(double);
         const size_t budget = (size_t)c->opt.marg_ws_mb << 20;
@@ -71,7 +71,7 @@ struct Fused {
                             b.dead.p));
         if (G > 1)
             BHMM_HIP(launch(k_post_check<N>, dim3((G + 255) / 256), dim3(256), 0, c->stream, ch, G, b.aentry.p,
-                            b.aexit.p, b.bassumed.p, b.bout.p, b.dead.p, POST_TOL, b.fails.p));
+                            b.aexit.p, b.bassumed.p, b.bout.p, b.dead.p, BOUNDARY_TOL, b.fails.p));
         BHMM_HIP(hipMemcpyAsync(fails, b.fails.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
         BHMM_HIP(hipStreamSynchronize(c->stream));
         return BHMM_OK;
@@ -107,7 +107,7 @@ struct Fused {
         if (W <= 0) {
             if ((rc = post_probe<N, KIND>(c, b.probe, m, b.Bt.p, &W)))
                 return rc;
-            W = W > 0 ? W : POST_W_UNPROBED;
+            W = W > 0 ? W : W_UNPROBED;
         }
         for (int attempt = 0; attempt < 2; ++attempt) {
             unsigned int fails = 0;

@@ -1,6 +1,8 @@
 // plan.hpp -- host-side planning of the time decomposition: chunk tables of the N <= 8 family
-// (bhmm_amd.hip), segment tables of the 9..64-state family (wide_api.hip), the plans of bhmm_score
-// (score_api.hip).  Pure C++ (no HIP), so
+// (bhmm_amd.hip), segment tables of the 9..64-state family (wide_api.hip), the plan of a forward-only pass
+// (bhmm_score, bhmm_filter: plan_pass, uploaded by seg_host.hpp), and the forgetting probe every family
+// warms up by: where it samples (probe_starts) and how its curve is read (curve_last, warmup_of,
+// warmup_wide_of).  Pure C++ (no HIP), so
 // the same code runs under -fsanitize=address,undefined in the CPU sanitizer build
 // (oracle/Makefile `asan`); the .hip files only allocate and upload what these functions return.
 #pragma once
@@ -8,6 +10,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 namespace bhmm {
@@ -140,7 +143,7 @@ inline void plan_segments(const std::vector<int64_t> &offsets, int K, int64_t se
     s.traj0[K] = (int32_t)s.traj.size();
 }
 
-// Segment length of the scoring plan for 9..64 states (score_api.hip: plan_segments with it, mult 1).  A
+// Segment length of the scoring plan for 9..64 states (score_api.hip: plan_pass with it; bhmm_filter's too).  A
 // function of the observation set's size, the lane-group width np (16, 32, 64) and the device only: a score
 // must not depend on what earlier calls found out.  asked > 0: the caller's length (option score_seglen).
 // Automatic: two wavefronts per SIMD for ONE model (the kernel's registers allow two at np = 64; more models
@@ -153,8 +156,8 @@ inline int64_t score_seglen(int64_t total, int np, int num_simd, int64_t asked)
     return (std::max<int64_t>((total + want - 1) / want, 2048) + 3) & ~(int64_t)3;
 }
 
-// Segment length of the scoring plan for 65..128 states (score_api.hip: plan_segments with it, mult 1, then
-// plan_tiles).  A function of the observation set's size and the device only, like score_seglen.  asked > 0: the
+// Segment length of the scoring plan for 65..128 states (score_api.hip: plan_pass with it and tiles; bhmm_filter's
+// too).  A function of the observation set's size and the device only, like score_seglen.  asked > 0: the
 // caller's length (option score_seglen).  Automatic: enough tiles of 16 segments for one workgroup per compute
 // unit for ONE model (num_simd / 4 tiles; more models bring their own workgroups), but at least 256 steps: a
 // quickly mixing model forgets its start within some tens of steps, and a segment of four times that keeps the
@@ -192,6 +195,87 @@ inline void plan_tiles(const SegPlan &s, const std::vector<int64_t> &offsets, bo
         tile_seg.resize(base + (order.size() + 15) / 16 * 16, -1);
         std::copy(order.begin(), order.end(), tile_seg.begin() + base);
     }
+}
+
+// The plan of a forward-only pass over segments of at most seglen steps (bhmm_score and bhmm_filter at 9..128
+// states; seg_host.hpp uploads it): plan_segments with mult 1, with `tiles` the tile table of the forward
+// direction, and the number of trajectories with at least one step (as many segments: no boundary).
+struct PassPlan {
+    SegPlan seg;
+    std::vector<int32_t> tile_seg; // [16 * tiles], empty without `tiles`
+    int ntraj = 0;
+};
+inline void plan_pass(const std::vector<int64_t> &offsets, int K, int64_t seglen, bool tiles, PassPlan &p)
+{
+    plan_segments(offsets, K, seglen, 1, p.seg);
+    p.tile_seg.clear();
+    if (tiles)
+        plan_tiles(p.seg, offsets, false, p.tile_seg);
+    p.ntraj = 0;
+    for (int k = 0; k < K; ++k)
+        p.ntraj += offsets[k + 1] > offsets[k];
+}
+
+// ---- the forgetting probe (k_forget_probe up to 8 states, k_wide_probe at 9..64) ----
+// It runs two differently started chains over Wmax steps from P sample positions and leaves, per direction and
+// step, the largest deviation between them: curve[w] forward, curve[Wmax + w] backward.
+
+// Longest warm-up the probe measures: half the longest trajectory, at most 1024 steps in multiples of 4 (up to 8
+// states) or 8192 in multiples of 8 (9..64 states).  0: the trajectories are too short to probe.
+inline int probe_wmax(int64_t maxT)
+{
+    const int Wmax = (int)std::min<int64_t>(1024, maxT / 2) / 4 * 4;
+    return Wmax < 32 ? 0 : Wmax;
+}
+inline int probe_wmax_wide(int64_t maxT)
+{
+    const int Wmax = (int)std::min<int64_t>(8192, maxT / 2) / 8 * 8;
+    return Wmax < 64 ? 0 : Wmax; // (trajectories of fewer than 128 steps)
+}
+
+// The P sample positions (in time steps, like the offsets): the trajectories of at least Wmax steps in turn, each
+// visited `reps` times at starts spread evenly over the room that leaves Wmax steps to its end.  Wmax from
+// probe_wmax / probe_wmax_wide, not 0: at least one trajectory is that long.
+inline void probe_starts(const std::vector<int64_t> &offsets, int K, int Wmax, int P, std::vector<int64_t> &starts)
+{
+    std::vector<int> longk;
+    for (int k = 0; k < K; ++k)
+        if (offsets[k + 1] - offsets[k] >= Wmax)
+            longk.push_back(k);
+    starts.resize(P);
+    for (int i = 0; i < P; ++i) {
+        const int k = longk[i % longk.size()];
+        const int64_t room = offsets[k + 1] - offsets[k] - Wmax + 1;
+        const int64_t rep = i / (int64_t)longk.size(), reps = (P + longk.size() - 1) / longk.size();
+        starts[i] = offsets[k] + (room - 1) * rep / std::max<int64_t>(reps - 1, 1);
+    }
+}
+
+// The last step at which the chains are still `target` apart (-1: never), in the forward direction or in the
+// worse of the two.
+inline int curve_last(const float *curve, int Wmax, float target, bool both)
+{
+    int last = -1;
+    for (int w = 0; w < Wmax; ++w)
+        if (curve[w] >= target || (both && curve[Wmax + w] >= target))
+            last = w;
+    return last;
+}
+
+// Warm-up from that reading, last + 2 steps to get below the target and stay there.  Up to 8 states: + 15 %, a
+// multiple of 4, at least 16, at most Wmax.  9..64 states: times PROBE_WIDE_MARGIN -- the check looks at every
+// boundary, the probe at P positions, and the worst boundary lags the worst sample (measured: 1.3 x in warm-up
+// steps) --, a multiple of 8, at least 16; what a reading near Wmax means is the caller's decision.
+constexpr double PROBE_WIDE_MARGIN = 1.5;
+inline int warmup_of(int last, int Wmax)
+{
+    const int w = (int)std::ceil(1.15 * (last + 2));
+    return std::min(std::max(16, (w + 3) / 4 * 4), Wmax);
+}
+inline int warmup_wide_of(int last)
+{
+    const int w = (int)std::ceil(PROBE_WIDE_MARGIN * (last + 2));
+    return std::max(16, (w + 7) / 8 * 8);
 }
 
 // For every segment of the plan with `seglen`: the start of a segment of the twice-as-fine plan

@@ -10,18 +10,22 @@
 //
 // 9 to 64 states, gaussian or discrete: k_score_wide (score_wide_kernels.hpp) over a segment plan that belongs
 // to scoring alone (score_plan: a function of the offsets, the state count and the device; option
-// score_seglen), all models of a batch in one launch, then k_score_wide_check and k_score_logl.  W per model
+// score_seglen; tables in c->score.seg), all models of a batch in one launch, then k_score_wide_check and k_score_logl.  W per model
 // from k_wide_probe (or score_W); the same protocol: a failed model runs again alone with twice the warm-up,
 // on the kernel that sums every step, then takes the exact serial recursion.
 //
 // 65 to 128 states, gaussian or discrete: k_score_tile (score_tile_kernels.hpp) on the fp64 matrix cores, sixteen
 // segments per workgroup, over a segment plan and a tile table that again belong to scoring alone
-// (score_tile_plan; plan::score_tile_seglen, option score_seglen).  W per model from two passes of the kernel
+// (score_plan with tiles; plan::score_tile_seglen, option score_seglen).  W per model from two passes of the kernel
 // itself (tile_calibrate) or the option score_W; the protocol is the same, but a model that left the number range
 // of the lazily scaled kernel goes straight to the exact serial recursion (there is no tile kernel that sums
 // every step).
 //
 // Explicit pobs and more than 128 states always take the exact path.
+//
+// What the paths share with bhmm_filter and the posterior calls is in seg_host.hpp (device side) and plan.hpp
+// (arithmetic): the constants of the protocol, the probe's sample positions, staging and reading, the parameter
+// block of a WideModel (fill_wide_block) and the making of a plan's tables (make_seg_tables).
 //
 // Nothing here reads or writes the E-step's state (ds.* but the score plan's own fields, carried vectors,
 // warm-up lengths, d_Bt, the E-step's segment plans, the timing events, the pinned landing zones): the
@@ -42,6 +46,7 @@
 #include "score_kernels.hpp"
 #include "score_wide_kernels.hpp"
 #include "score_tile_launch.hpp"
+#include "seg_host.hpp"
 
 namespace bhmm {
 
@@ -52,10 +57,8 @@ SCORE_TILE_LAUNCH_DECL(extern, 8)
 
 namespace {
 
-constexpr double SCORE_TOL = 1e-11;         // boundary check: componentwise relative (the E-step's spec_tol default)
-constexpr int SCORE_W_UNPROBED = 288;       // warm-up when the trajectories are too short to probe (the E-step's)
-constexpr size_t SCORE_LDS_BT = 16 * 1024;  // B^T of a model staged in LDS up to this size
-constexpr double SCORE_WIDE_MARGIN = 1.5;   // 9..64 states: warm-up over the probe's reading (wide_probe_run's factor)
+// (BOUNDARY_TOL, W_UNPROBED, LDS_BT_MAX, the probe and the plan: seg_host.hpp, shared with bhmm_filter and the
+// posterior calls)
 
 // per (trajectory, model) log-likelihood on the exact serial recursion for models [0, S) of the stacked
 // arrays; out[s * K + k]
@@ -108,57 +111,32 @@ int score_serial(bhmm_ctx *c, int S, const double *A, const double *pi, const do
 // N: the kernel's state count (the real one for the lane-per-chunk layout, 2 / 4 / 8 padded for PAIR)
 template <int N, int KIND, bool PAIR>
 struct Fast {
-    // warm-up of every model of the batch from the forgetting curve: the E-step's probe_warmup reading (forward
-    // chains within 1e-13 from then on, + 15 %), doubled -- the E-step lengthens its warm-up after a failed
+    // warm-up of every model of the batch from the forgetting curve: the E-step's reading (plan::warmup_of) of the
+    // forward chains (within 1e-13 from then on, + 15 %), doubled -- the E-step lengthens its warm-up after a failed
     // check and keeps it for the observation set, a score call keeps nothing (1024 x 1e6 steps, slowly mixing
     // models: the plain reading failed the check for three models of four, twice that passed).  W[s] = 0 where
     // the trajectories are too short to probe
     static int probe(bhmm_ctx *c, int Sb, const std::vector<Model<N>> &m, const double *dBt, std::vector<int> &W)
     {
         W.assign(Sb, 0);
-        const int64_t maxT = longest_traj(c);
-        const int Wmax = (int)std::min<int64_t>(1024, maxT / 2) / 4 * 4;
-        if (Wmax < 32)
+        const int Wmax = plan::probe_wmax(longest_traj(c));
+        if (Wmax == 0)
             return BHMM_OK;
-        std::vector<int> longk;
-        for (int k = 0; k < c->K; ++k)
-            if (c->offsets[k + 1] - c->offsets[k] >= Wmax)
-                longk.push_back(k);
-        const int P = 256;
-        std::vector<int64_t> starts(P);
-        for (int i = 0; i < P; ++i) {
-            const int k = longk[i % longk.size()];
-            const int64_t room = c->offsets[k + 1] - c->offsets[k] - Wmax + 1;
-            const int64_t rep = i / (int64_t)longk.size(), reps = (P + longk.size() - 1) / longk.size();
-            starts[i] = c->offsets[k] + (room - 1) * rep / std::max<int64_t>(reps - 1, 1);
-        }
-        const size_t curve_words = 2 * (size_t)Wmax;
-        const size_t bytes = P * sizeof(int64_t) + (size_t)Sb * curve_words * sizeof(unsigned int);
+        Probe pr;
         int rc;
-        if ((rc = c->score.probe.ensure(bytes)))
+        if ((rc = probe_stage(c, c->score.probe, Wmax, Sb, pr)))
             return rc;
-        int64_t *d_starts = reinterpret_cast<int64_t *>(c->score.probe.p);
-        unsigned int *d_curve = reinterpret_cast<unsigned int *>(d_starts + P);
-        BHMM_HIP(hipMemcpyAsync(d_starts, starts.data(), P * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        BHMM_HIP(hipMemsetAsync(d_curve, 0, (size_t)Sb * curve_words * sizeof(unsigned int), c->stream));
+        const size_t curve_words = 2 * (size_t)Wmax;
         for (int s = 0; s < Sb; ++s)
-            BHMM_HIP(launch(k_forget_probe<N, KIND>, dim3((2 * P + 63) / 64), dim3(64), 0, c->stream, m[s],
-                            c->d_obs_rm.p, KIND == EMIT_DISC ? dBt + (size_t)s * c->M * N : nullptr, d_starts, P,
-                            Wmax, d_curve + s * curve_words));
-        std::vector<float> curve((size_t)Sb * curve_words);
-        BHMM_HIP(hipMemcpyAsync(curve.data(), d_curve, curve.size() * sizeof(float), hipMemcpyDeviceToHost,
-                                c->stream));
-        BHMM_HIP(hipStreamSynchronize(c->stream));
-        const float target = (float)(0.01 * SCORE_TOL);
-        for (int s = 0; s < Sb; ++s) {
-            const float *cv = curve.data() + s * curve_words; // forward direction: the first Wmax entries
-            int last = -1;
-            for (int w = 0; w < Wmax; ++w)
-                if (cv[w] >= target)
-                    last = w;
-            int w = (int)std::ceil(1.15 * (last + 2));
-            W[s] = 2 * std::min(std::max(16, (w + 3) / 4 * 4), Wmax);
-        }
+            BHMM_HIP(launch(k_forget_probe<N, KIND>, dim3((2 * PROBE_P + 63) / 64), dim3(64), 0, c->stream, m[s],
+                            c->d_obs_rm.p, KIND == EMIT_DISC ? dBt + (size_t)s * c->M * N : nullptr, pr.d_starts,
+                            PROBE_P, Wmax, pr.d_curve + s * curve_words));
+        std::vector<float> curve;
+        if ((rc = probe_read(c, pr, curve)))
+            return rc;
+        const float target = (float)(0.01 * BOUNDARY_TOL);
+        for (int s = 0; s < Sb; ++s) // (the forward direction)
+            W[s] = 2 * plan::warmup_of(plan::curve_last(curve.data() + s * curve_words, Wmax, target, false), Wmax);
         return BHMM_OK;
     }
 
@@ -170,7 +148,7 @@ struct Fast {
         const int K = c->K, G = c->G, Gp = c->Gp;
         const Chunks ch = chunks_of(c);
         const size_t lds_bt = (size_t)c->M * score_bt_stride(N) * sizeof(double);
-        const bool bt_lds = KIND == EMIT_DISC && lds_bt <= SCORE_LDS_BT;
+        const bool bt_lds = KIND == EMIT_DISC && lds_bt <= LDS_BT_MAX;
         BHMM_HIP(hipMemsetAsync(b.fails.p, 0, Sb * sizeof(unsigned int), c->stream));
         const dim3 grid(Gp / 64, Sb);
         const dim3 block(PAIR ? 32 * N : 64);
@@ -184,7 +162,7 @@ struct Fast {
                         c->d_obs_rm.p, dBt, c->M, b.logLc.p, b.aentry.p, b.aexit.p));
         if (G > 1)
             BHMM_HIP(launch(k_score_check<N>, dim3((G + 255) / 256, Sb), dim3(256), 0, c->stream, ch, G, Gp, b.logLc.p,
-                            b.aentry.p, b.aexit.p, SCORE_TOL, b.fails.p));
+                            b.aentry.p, b.aexit.p, BOUNDARY_TOL, b.fails.p));
         BHMM_HIP(launch(k_score_logl, dim3(K, Sb), dim3(64), 0, c->stream, c->d_traj_c0.p, K, Gp, b.logLc.p,
                         b.logLk.p));
         BHMM_HIP(hipMemcpyAsync(fails_h, b.fails.p, Sb * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
@@ -236,7 +214,7 @@ struct Fast {
                 if ((rc = probe(c, Sb, m, b.Bt.p, W)))
                     return rc;
                 for (int &w : W)
-                    w = w > 0 ? w : SCORE_W_UNPROBED;
+                    w = w > 0 ? w : W_UNPROBED;
             }
             BHMM_HIP(hipMemcpyAsync(b.W.p, W.data(), Sb * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
             double *out = logL + (size_t)s0 * K;
@@ -272,86 +250,53 @@ int run_n(bhmm_ctx *c, int S, const double *A, const double *pi, const double *p
                                  : Fast<N, EMIT_DISC, PAIR>::run(c, S, A, pi, par0, par1, logL);
 }
 
-// ---- 9..64 states ------------------------------------------------------------------------------
+// ---- 9..128 states: the plan ----------------------------------------------------------------------
 
 // the segment plan of scoring on this observation set: made once (and again when score_seglen changes),
-// never after a check
-int score_plan(bhmm_ctx *c)
+// never after a check.  tiles: 65..128 states, plan::score_tile_seglen and the tile table of k_score_tile
+int score_plan(bhmm_ctx *c, bool tiles)
 {
     auto &d = c->ds;
-    auto &b = c->score;
     if (d.score_nseg > 0 && d.score_seglen_opt == c->opt.score_seglen)
         return BHMM_OK;
-    plan::SegPlan sp; // (plan.hpp: pure host code)
-    plan::plan_segments(c->offsets, c->K, plan::score_seglen(c->total, c->N, c->num_simd, c->opt.score_seglen), 1,
-                        sp);
-    const size_t ns = sp.traj.size();
+    const int64_t seglen = tiles ? plan::score_tile_seglen(c->total, c->num_simd, c->opt.score_seglen)
+                                 : plan::score_seglen(c->total, c->N, c->num_simd, c->opt.score_seglen);
     int rc;
-    if ((rc = b.seg_traj.ensure(ns)) || (rc = b.seg_len.ensure(ns)) || (rc = b.seg_t0.ensure(ns)) ||
-        (rc = b.seg_traj0.ensure(c->K + 1)))
+    if ((rc = make_seg_tables(c, c->score.seg, seglen, tiles, &d.score_nseg, &d.score_ntraj, &d.score_ntiles)))
         return rc;
-    BHMM_HIP(hipMemcpyAsync(b.seg_traj.p, sp.traj.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemcpyAsync(b.seg_len.p, sp.len.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemcpyAsync(b.seg_t0.p, sp.t0.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemcpyAsync(b.seg_traj0.p, sp.traj0.data(), (c->K + 1) * sizeof(int32_t), hipMemcpyHostToDevice,
-                            c->stream));
-    BHMM_HIP(hipStreamSynchronize(c->stream)); // (sp is a temporary)
-    d.score_nseg = (int)ns;
-    d.score_ntraj = 0;
-    for (int k = 0; k < c->K; ++k)
-        d.score_ntraj += c->offsets[k + 1] > c->offsets[k];
     d.score_seglen_opt = c->opt.score_seglen;
     return BHMM_OK;
 }
+
+// ---- 9..64 states ------------------------------------------------------------------------------
 
 template <int NP, int KIND>
 struct Wide {
     static constexpr int GP = 64 / NP;
 
     // warm-up of every model of the batch: k_wide_probe once per model (its forward chains only: the first
-    // P / GP workgroups), read like wide_probe_run -- chains within 1e-13 from then on, times 1.5
+    // PROBE_P / GP workgroups), read like wide_probe_run (plan::warmup_wide_of) -- chains within 1e-13 from then on,
+    // times 1.5 -- and capped at the longest warm-up the probe measures
     static int probe(bhmm_ctx *c, int Sb, const std::vector<ScoreWideModel> &m, std::vector<int> &W)
     {
-        W.assign(Sb, SCORE_W_UNPROBED);
-        const int Wmax = (int)std::min<int64_t>(8192, longest_traj(c) / 2) / 8 * 8;
-        if (Wmax < 64)
-            return BHMM_OK; // (trajectories of fewer than 128 steps)
-        std::vector<int> longk;
-        for (int k = 0; k < c->K; ++k)
-            if (c->offsets[k + 1] - c->offsets[k] >= Wmax)
-                longk.push_back(k);
-        const int P = 256;
-        std::vector<int64_t> starts(P);
-        for (int i = 0; i < P; ++i) {
-            const int k = longk[i % longk.size()];
-            const int64_t room = c->offsets[k + 1] - c->offsets[k] - Wmax + 1;
-            const int64_t rep = i / (int64_t)longk.size(), reps = (P + longk.size() - 1) / longk.size();
-            starts[i] = c->offsets[k] + (room - 1) * rep / std::max<int64_t>(reps - 1, 1);
-        }
-        const size_t curve_words = 2 * (size_t)Wmax; // (the kernel's layout: forward | backward, the latter stays zero)
+        W.assign(Sb, W_UNPROBED);
+        const int Wmax = plan::probe_wmax_wide(longest_traj(c));
+        if (Wmax == 0)
+            return BHMM_OK;
+        Probe pr;
         int rc;
-        if ((rc = c->score.probe.ensure(P * sizeof(int64_t) + (size_t)Sb * curve_words * sizeof(unsigned int))))
+        if ((rc = probe_stage(c, c->score.probe, Wmax, Sb, pr)))
             return rc;
-        int64_t *d_starts = reinterpret_cast<int64_t *>(c->score.probe.p);
-        unsigned int *d_curve = reinterpret_cast<unsigned int *>(d_starts + P);
-        BHMM_HIP(hipMemcpyAsync(d_starts, starts.data(), P * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        BHMM_HIP(hipMemsetAsync(d_curve, 0, (size_t)Sb * curve_words * sizeof(unsigned int), c->stream));
+        const size_t curve_words = 2 * (size_t)Wmax; // (the kernel's layout: forward | backward, the latter stays zero)
         for (int s = 0; s < Sb; ++s)
-            BHMM_HIP(launch(k_wide_probe<NP, KIND>, dim3(P / GP), dim3(64), 0, c->stream, m[s].w, c->d_obs_rm.p,
-                            d_starts, P, Wmax, d_curve + s * curve_words));
-        std::vector<float> curve((size_t)Sb * curve_words);
-        BHMM_HIP(hipMemcpyAsync(curve.data(), d_curve, curve.size() * sizeof(float), hipMemcpyDeviceToHost,
-                                c->stream));
-        BHMM_HIP(hipStreamSynchronize(c->stream));
-        for (int s = 0; s < Sb; ++s) {
-            const float *cv = curve.data() + s * curve_words;
-            int last = -1;
-            for (int w = 0; w < Wmax; ++w)
-                if (cv[w] >= 1e-13f)
-                    last = w;
-            const int w = (int)std::ceil(SCORE_WIDE_MARGIN * (last + 2));
-            W[s] = std::min(std::max(16, (w + 7) / 8 * 8), Wmax); // (not forgotten within Wmax: Wmax, the check decides)
-        }
+            BHMM_HIP(launch(k_wide_probe<NP, KIND>, dim3(PROBE_P / GP), dim3(64), 0, c->stream, m[s].w, c->d_obs_rm.p,
+                            pr.d_starts, PROBE_P, Wmax, pr.d_curve + s * curve_words));
+        std::vector<float> curve;
+        if ((rc = probe_read(c, pr, curve)))
+            return rc;
+        for (int s = 0; s < Sb; ++s) // (not forgotten within Wmax: Wmax, the check decides)
+            W[s] = std::min(plan::warmup_wide_of(plan::curve_last(curve.data() + s * curve_words, Wmax, 1e-13f, false)),
+                            Wmax);
         return BHMM_OK;
     }
 
@@ -361,14 +306,9 @@ struct Wide {
     {
         auto &b = c->score;
         const int K = c->K, nseg = c->ds.score_nseg;
-        Segs sg;
-        sg.traj = b.seg_traj.p;
-        sg.t0 = b.seg_t0.p;
-        sg.len = b.seg_len.p;
-        sg.nseg = nseg;
-        sg.W = 0; // (per model: dW)
+        const Segs sg = segs_of_tables<Segs>(b.seg, nseg, 0); // (W per model: dW)
         const size_t lds_bt = (size_t)c->M * NP * sizeof(double);
-        const bool bt_lds = KIND == EMIT_DISC && lds_bt <= SCORE_LDS_BT;
+        const bool bt_lds = KIND == EMIT_DISC && lds_bt <= LDS_BT_MAX;
         BHMM_HIP(hipMemsetAsync(b.fails.p, 0, Sb * sizeof(unsigned int), c->stream));
         constexpr bool D = KIND == EMIT_DISC; // (gaussian: one instantiation per scaling)
         auto *kern = lazy ? (bt_lds ? k_score_wide<NP, KIND, true, D> : k_score_wide<NP, KIND, true, false>)
@@ -377,8 +317,8 @@ struct Wide {
                         c->d_offsets.p, sg, c->d_obs_rm.p, b.logLc.p, b.aentry.p, b.aexit.p, b.fails.p));
         if (nseg > c->ds.score_ntraj)
             BHMM_HIP(launch(k_score_wide_check, dim3((nseg + 15) / 16, Sb), dim3(256), 0, c->stream, sg, c->n,
-                            b.logLc.p, b.aentry.p, b.aexit.p, SCORE_TOL, b.fails.p));
-        BHMM_HIP(launch(k_score_logl, dim3(K, Sb), dim3(64), 0, c->stream, b.seg_traj0.p, K, nseg, b.logLc.p,
+                            b.logLc.p, b.aentry.p, b.aexit.p, BOUNDARY_TOL, b.fails.p));
+        BHMM_HIP(launch(k_score_logl, dim3(K, Sb), dim3(64), 0, c->stream, b.seg.seg_traj0.p, K, nseg, b.logLc.p,
                         b.logLk.p));
         BHMM_HIP(hipMemcpyAsync(fails_h, b.fails.p, Sb * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
         BHMM_HIP(hipMemcpyAsync(logLk_h, b.logLk.p, (size_t)Sb * K * sizeof(double), hipMemcpyDeviceToHost,
@@ -393,14 +333,14 @@ struct Wide {
         auto &b = c->score;
         const int K = c->K, M = c->M, n = c->n;
         int rc;
-        if ((rc = score_plan(c)))
+        if ((rc = score_plan(c, false)))
             return rc;
         const int nseg = c->last.score_segments = c->ds.score_nseg;
         // models per launch: at most SCORE_MAX_MODELS, and boundary vectors of at most 1 GiB
         const size_t per_model = (size_t)nseg * (2 * n + 1) * sizeof(double);
         const int Sb_max = (int)std::max<size_t>(1, std::min<size_t>(SCORE_MAX_MODELS, ((size_t)1 << 30) / per_model));
-        // parameter block of a model: wide_model's layout, then B and B^T
-        const size_t nB = KIND == EMIT_DISC ? (size_t)n * M : 0, np = (size_t)n * n + 7 * n + 2 * nB;
+        constexpr bool disc = KIND == EMIT_DISC;
+        const size_t nB = disc ? (size_t)n * M : 0, np = wide_block_size(n, M, disc, true);
         if ((rc = b.logLc.ensure((size_t)Sb_max * nseg)) || (rc = b.aentry.ensure((size_t)Sb_max * nseg * n)) ||
             (rc = b.aexit.ensure((size_t)Sb_max * nseg * n)) || (rc = b.logLk.ensure((size_t)Sb_max * K)) ||
             (rc = b.fails.ensure(Sb_max)) || (rc = b.W.ensure(Sb_max)) ||
@@ -414,44 +354,9 @@ struct Wide {
             std::vector<ScoreWideModel> m(Sb);
             for (int s = 0; s < Sb; ++s) {
                 const int g = s0 + s;
-                double *hp = h.data() + s * np;
-                const double *dp = b.wpar.p + s * np;
-                memcpy(hp, A + (size_t)g * n * n, sizeof(double) * n * n);
-                memcpy(hp + (size_t)n * n, pi + (size_t)g * n, sizeof(double) * n);
-                WideModel &w = m[s].w;
-                w.A = dp;
-                w.pi = dp + (size_t)n * n;
-                w.mu = w.pi + n;
-                w.isig = w.mu + n;
-                w.cnorm = w.isig + n;
-                w.sigma = w.cnorm + n;
-                w.ga = w.sigma + n;
-                w.gb = w.ga + n;
-                w.gmg = 0.0;
-                w.B = nullptr;
-                w.n = n;
-                w.M = M;
-                m[s].Bt = nullptr;
-                double *q = hp + (size_t)n * n + n;
-                if (KIND == EMIT_GAUSS) {
-                    const double *mu = par0 + (size_t)g * n, *sg = par1 + (size_t)g * n;
-                    for (int i = 0; i < n; ++i) {
-                        q[i] = mu[i];
-                        q[n + i] = 1.0 / sg[i];
-                        q[2 * n + i] = 1.0 / (sqrt(2.0 * M_PI) * sg[i]);
-                        q[3 * n + i] = sg[i];
-                    }
-                    gauss_pdf_constants(n, n, sg, q + 4 * n, q + 5 * n, &w.gmg);
-                } else {
-                    const double *B = par0 + (size_t)g * nB;
-                    double *hB = q + 6 * n, *hBt = hB + nB;
-                    memcpy(hB, B, sizeof(double) * nB);
-                    for (int i = 0; i < n; ++i)
-                        for (int o = 0; o < M; ++o)
-                            hBt[(size_t)o * n + i] = B[(size_t)i * M + o];
-                    w.B = w.gb + n;
-                    m[s].Bt = w.B + nB;
-                }
+                m[s].Bt = fill_wide_block(n, M, disc, true, A + (size_t)g * n * n, pi + (size_t)g * n,
+                                          par0 + (size_t)g * (disc ? nB : (size_t)n), disc ? nullptr : par1 + (size_t)g * n,
+                                          h.data() + s * np, b.wpar.p + s * np, m[s].w);
             }
             BHMM_HIP(hipMemcpyAsync(b.wpar.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
             BHMM_HIP(hipMemcpyAsync(dm, m.data(), Sb * sizeof(ScoreWideModel), hipMemcpyHostToDevice, c->stream));
@@ -501,40 +406,6 @@ int run_wide(bhmm_ctx *c, int S, const double *A, const double *pi, const double
 
 // (SCORE_TILE_W0 .. SCORE_TILE_W_MAX, the constants of the calibration: host_internal.hpp, shared with bhmm_filter)
 
-// the segment plan and the tile table of scoring on this observation set: made once (and again when
-// score_seglen changes), never after a check
-int score_tile_plan(bhmm_ctx *c)
-{
-    auto &d = c->ds;
-    auto &b = c->score;
-    if (d.score_nseg > 0 && d.score_seglen_opt == c->opt.score_seglen)
-        return BHMM_OK;
-    plan::SegPlan sp; // (plan.hpp: pure host code)
-    plan::plan_segments(c->offsets, c->K, plan::score_tile_seglen(c->total, c->num_simd, c->opt.score_seglen), 1, sp);
-    std::vector<int32_t> tile_seg;
-    plan::plan_tiles(sp, c->offsets, false, tile_seg);
-    const size_t ns = sp.traj.size();
-    int rc;
-    if ((rc = b.seg_traj.ensure(ns)) || (rc = b.seg_len.ensure(ns)) || (rc = b.seg_t0.ensure(ns)) ||
-        (rc = b.seg_traj0.ensure(c->K + 1)) || (rc = b.tile_seg.ensure(std::max<size_t>(tile_seg.size(), 16))))
-        return rc;
-    BHMM_HIP(hipMemcpyAsync(b.seg_traj.p, sp.traj.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemcpyAsync(b.seg_len.p, sp.len.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemcpyAsync(b.seg_t0.p, sp.t0.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemcpyAsync(b.seg_traj0.p, sp.traj0.data(), (c->K + 1) * sizeof(int32_t), hipMemcpyHostToDevice,
-                            c->stream));
-    BHMM_HIP(hipMemcpyAsync(b.tile_seg.p, tile_seg.data(), tile_seg.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                            c->stream));
-    BHMM_HIP(hipStreamSynchronize(c->stream)); // (sp and tile_seg are temporaries)
-    d.score_nseg = (int)ns;
-    d.score_ntiles = (int)(tile_seg.size() / 16);
-    d.score_ntraj = 0;
-    for (int k = 0; k < c->K; ++k)
-        d.score_ntraj += c->offsets[k + 1] > c->offsets[k];
-    d.score_seglen_opt = c->opt.score_seglen;
-    return BHMM_OK;
-}
-
 template <int KIND>
 struct Tile {
     // what a pass left per model
@@ -549,13 +420,8 @@ struct Tile {
     {
         auto &b = c->score;
         const int K = c->K, nseg = c->ds.score_nseg, n = c->n;
-        Segs sg;
-        sg.traj = b.seg_traj.p;
-        sg.t0 = b.seg_t0.p;
-        sg.len = b.seg_len.p;
-        sg.nseg = nseg;
-        sg.W = 0; // (per model: in its table entry)
-        const TilePlan tp{b.tile_seg.p, c->ds.score_ntiles};
+        const Segs sg = segs_of_tables<Segs>(b.seg, nseg, 0); // (W per model: in its table entry)
+        const TilePlan tp{b.seg.tile_seg.p, c->ds.score_ntiles};
         BHMM_HIP(hipMemsetAsync(b.fails.p, 0, (size_t)Sb * SCORE_TILE_FLAGS * sizeof(unsigned int), c->stream));
         int rc = n <= 80   ? score_tile_launch<5, KIND>(c, Sb, dm, sg, tp, b.fails.p)
                  : n <= 96  ? score_tile_launch<6, KIND>(c, Sb, dm, sg, tp, b.fails.p)
@@ -565,9 +431,9 @@ struct Tile {
             return rc;
         if (nseg > c->ds.score_ntraj)
             BHMM_HIP(launch(k_score_tile_check, dim3((nseg + 15) / 16, Sb), dim3(256), 0, c->stream, sg, n, b.aentry.p,
-                            b.aexit.p, SCORE_TOL, b.fails.p));
+                            b.aexit.p, BOUNDARY_TOL, b.fails.p));
         if (logLk_h)
-            BHMM_HIP(launch(k_score_logl, dim3(K, Sb), dim3(64), 0, c->stream, b.seg_traj0.p, K, nseg, b.logLc.p,
+            BHMM_HIP(launch(k_score_logl, dim3(K, Sb), dim3(64), 0, c->stream, b.seg.seg_traj0.p, K, nseg, b.logLc.p,
                             b.logLk.p));
         std::vector<unsigned int> f((size_t)Sb * SCORE_TILE_FLAGS);
         BHMM_HIP(hipMemcpyAsync(f.data(), b.fails.p, f.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
@@ -627,7 +493,7 @@ struct Tile {
         auto &b = c->score;
         const int K = c->K, M = c->M, n = c->n;
         int rc;
-        if ((rc = score_tile_plan(c)))
+        if ((rc = score_plan(c, true)))
             return rc;
         if (c->ds.score_ntiles == 0) // (no trajectory has a step)
             return score_serial(c, S, A, pi, par0, par1, logL);
@@ -636,8 +502,8 @@ struct Tile {
         // models per launch: at most SCORE_MAX_MODELS, and boundary vectors of at most 1 GiB
         const size_t per_model = (size_t)std::max(nseg, 1) * (2 * n + 1) * sizeof(double);
         const int Sb_max = (int)std::max<size_t>(1, std::min<size_t>(SCORE_MAX_MODELS, ((size_t)1 << 30) / per_model));
-        // parameter block of a model: wide_model's layout, then B^T
-        const size_t nB = KIND == EMIT_DISC ? (size_t)n * M : 0, np = (size_t)n * n + 7 * n + nB;
+        constexpr bool disc = KIND == EMIT_DISC;
+        const size_t nB = disc ? (size_t)n * M : 0, np = wide_block_size(n, M, disc, false); // (the kernel reads B^T)
         if ((rc = b.logLc.ensure((size_t)Sb_max * nseg)) || (rc = b.aentry.ensure((size_t)Sb_max * nseg * n)) ||
             (rc = b.aexit.ensure((size_t)Sb_max * nseg * n)) || (rc = b.logLk.ensure((size_t)Sb_max * K)) ||
             (rc = b.fails.ensure((size_t)Sb_max * SCORE_TILE_FLAGS)) ||
@@ -651,43 +517,10 @@ struct Tile {
             std::vector<ScoreTileModel> m(Sb);
             for (int s = 0; s < Sb; ++s) {
                 const int g = s0 + s;
-                double *hp = h.data() + s * np;
-                const double *dp = b.wpar.p + s * np;
-                memcpy(hp, A + (size_t)g * n * n, sizeof(double) * n * n);
-                memcpy(hp + (size_t)n * n, pi + (size_t)g * n, sizeof(double) * n);
-                WideModel &w = m[s].w;
-                w.A = dp;
-                w.pi = dp + (size_t)n * n;
-                w.mu = w.pi + n;
-                w.isig = w.mu + n;
-                w.cnorm = w.isig + n;
-                w.sigma = w.cnorm + n;
-                w.ga = w.sigma + n;
-                w.gb = w.ga + n;
-                w.gmg = 0.0;
-                w.B = nullptr; // (the kernel reads B^T)
-                w.n = n;
-                w.M = M;
-                m[s].Bt = nullptr;
+                m[s].Bt = fill_wide_block(n, M, disc, false, A + (size_t)g * n * n, pi + (size_t)g * n,
+                                          par0 + (size_t)g * (disc ? nB : (size_t)n), disc ? nullptr : par1 + (size_t)g * n,
+                                          h.data() + s * np, b.wpar.p + s * np, m[s].w);
                 m[s].W = 0;
-                double *q = hp + (size_t)n * n + n;
-                if (KIND == EMIT_GAUSS) {
-                    const double *mu = par0 + (size_t)g * n, *sg = par1 + (size_t)g * n;
-                    for (int i = 0; i < n; ++i) {
-                        q[i] = mu[i];
-                        q[n + i] = 1.0 / sg[i];
-                        q[2 * n + i] = 1.0 / (sqrt(2.0 * M_PI) * sg[i]);
-                        q[3 * n + i] = sg[i];
-                    }
-                    gauss_pdf_constants(n, n, sg, q + 4 * n, q + 5 * n, &w.gmg);
-                } else {
-                    const double *B = par0 + (size_t)g * nB;
-                    double *hBt = q + 6 * n;
-                    for (int i = 0; i < n; ++i)
-                        for (int o = 0; o < M; ++o)
-                            hBt[(size_t)o * n + i] = B[(size_t)i * M + o];
-                    m[s].Bt = w.gb + n;
-                }
             }
             BHMM_HIP(hipMemcpyAsync(b.wpar.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
             BHMM_HIP(hipStreamSynchronize(c->stream)); // (h is a temporary)

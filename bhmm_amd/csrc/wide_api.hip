@@ -12,6 +12,7 @@
 #include "host_internal.hpp"
 #include "launch.hpp"
 #include "plan.hpp"
+#include "seg_host.hpp"
 #include "wide_kernels.hpp"
 #include "tile_kernels.hpp"
 
@@ -24,37 +25,14 @@ int wide_model(bhmm_ctx *c, int kind, const double *A, const double *pi, const d
                WideModel &m)
 {
     const int n = c->n;
-    std::vector<double> h((size_t)n * n + 7 * n, 0.0);
-    memcpy(h.data(), A, sizeof(double) * n * n);
-    double *hp = h.data() + (size_t)n * n;
-    for (int i = 0; i < n; ++i) {
-        hp[i] = pi ? pi[i] : 0.0;
-        if (kind == EMIT_GAUSS) {
-            hp[n + i] = par0[i];
-            hp[2 * n + i] = 1.0 / par1[i];
-            hp[3 * n + i] = 1.0 / (sqrt(2.0 * M_PI) * par1[i]);
-            hp[4 * n + i] = par1[i];
-        }
-    }
-    m.gmg = 0.0;
-    if (kind == EMIT_GAUSS)
-        gauss_pdf_constants(n, n, par1, hp + 5 * n, hp + 6 * n, &m.gmg);
+    std::vector<double> h(wide_block_size(n, c->M, false, false), 0.0);
     int rc = c->d_wmodel.ensure(h.size());
     if (rc)
         return rc;
+    // (the part of the block every family has; B stays in d_Brm, where the path kernels read it too)
+    fill_wide_common(n, c->M, kind == EMIT_GAUSS, A, pi, par0, par1, h.data(), c->d_wmodel.p, m);
     BHMM_HIP(hipMemcpyAsync(c->d_wmodel.p, h.data(), h.size() * sizeof(double),
                             hipMemcpyHostToDevice, c->stream));
-    m.A = c->d_wmodel.p;
-    m.pi = m.A + (size_t)n * n;
-    m.mu = m.pi + n;
-    m.isig = m.mu + n;
-    m.cnorm = m.isig + n;
-    m.sigma = m.cnorm + n;
-    m.ga = m.sigma + n;
-    m.gb = m.ga + n;
-    m.n = n;
-    m.M = c->M;
-    m.B = nullptr;
     if (kind == EMIT_DISC) {
         if ((rc = c->d_Brm.ensure((size_t)n * c->M)))
             return rc;
@@ -374,48 +352,25 @@ template <int NP, int KIND>
 static int wide_probe_run(bhmm_ctx *c, const WideModel &m, int *W_out)
 {
     *W_out = 0;
-    const int Wmax = (int)std::min<int64_t>(8192, longest_traj(c) / 2) / 8 * 8;
-    if (Wmax < 64)
+    const int Wmax = plan::probe_wmax_wide(longest_traj(c));
+    if (Wmax == 0)
         return BHMM_OK;
-    std::vector<int> longk;
-    for (int k = 0; k < c->K; ++k)
-        if (c->offsets[k + 1] - c->offsets[k] >= Wmax)
-            longk.push_back(k);
-    const int S = 256;
-    std::vector<int64_t> starts(S);
-    for (int i = 0; i < S; ++i) { // positions relative to the first observation of the context
-        const int k = longk[i % longk.size()];
-        const int64_t room = c->offsets[k + 1] - c->offsets[k] - Wmax + 1;
-        const int64_t rep = i / (int64_t)longk.size(), reps = (S + longk.size() - 1) / longk.size();
-        starts[i] = c->offsets[k] + (room - 1) * rep / std::max<int64_t>(reps - 1, 1);
-    }
-    const size_t bytes = S * sizeof(int64_t) + 2 * (size_t)Wmax * sizeof(unsigned int);
+    Probe pr; // (positions relative to the first observation of the context)
     int rc;
-    if ((rc = c->d_probe.ensure(bytes)))
+    if ((rc = probe_stage(c, c->d_probe, Wmax, 1, pr)))
         return rc;
-    int64_t *d_starts = reinterpret_cast<int64_t *>(c->d_probe.p);
-    unsigned int *d_curve = reinterpret_cast<unsigned int *>(d_starts + S);
-    BHMM_HIP(hipMemcpyAsync(d_starts, starts.data(), S * sizeof(int64_t), hipMemcpyHostToDevice,
-                            c->stream));
-    BHMM_HIP(hipMemsetAsync(d_curve, 0, 2 * (size_t)Wmax * sizeof(unsigned int), c->stream));
     constexpr int GP = 64 / NP;
-    BHMM_HIP(launch(k_wide_probe<NP, KIND>, dim3((2 * S + GP - 1) / GP), dim3(64), 0, c->stream, m, c->d_obs_rm.p,
-                    d_starts, S, Wmax, d_curve));
-    std::vector<float> curve(2 * (size_t)Wmax);
-    BHMM_HIP(hipMemcpyAsync(curve.data(), d_curve, curve.size() * sizeof(float), hipMemcpyDeviceToHost,
-                            c->stream));
-    BHMM_HIP(hipStreamSynchronize(c->stream)); // starts / curve are temporaries
-    int last = -1;
-    for (int w = 0; w < Wmax; ++w)
-        if (std::max(curve[w], curve[Wmax + w]) >= 1e-13f)
-            last = w;
+    BHMM_HIP(launch(k_wide_probe<NP, KIND>, dim3((2 * PROBE_P + GP - 1) / GP), dim3(64), 0, c->stream, m,
+                    c->d_obs_rm.p, pr.d_starts, PROBE_P, Wmax, pr.d_curve));
+    std::vector<float> curve;
+    if ((rc = probe_read(c, pr, curve)))
+        return rc;
+    const int last = plan::curve_last(curve.data(), Wmax, 1e-13f, true);
     if (last + 2 >= Wmax)
         return BHMM_OK; // not forgotten within Wmax: no statement
-    // the boundary check looks at every segment boundary, the probe at S positions: the worst
-    // boundary lags the worst sample (measured: 1.3x in warm-up steps); an E-step that fails the
-    // check costs eight good ones, a longer warm-up a few per cent
-    int W = (int)std::ceil(1.5 * (last + 2));
-    *W_out = std::max(16, (W + 7) / 8 * 8);
+    // (the margin over the reading: plan::PROBE_WIDE_MARGIN -- an E-step that fails the check costs eight good
+    // ones, a longer warm-up a few per cent)
+    *W_out = plan::warmup_wide_of(last);
     return BHMM_OK;
 }
 

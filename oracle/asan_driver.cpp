@@ -136,6 +136,41 @@ static void check_seg_plan(const std::vector<int64_t> &off, int K, int64_t segle
     }
 }
 
+// the plan of a forward-only pass and the sample positions of the forgetting probe on the same offsets
+static void check_pass_and_probe(const std::vector<int64_t> &off, int K, int64_t seglen)
+{
+    for (int tiles = 0; tiles < 2; ++tiles) {
+        bhmm::plan::PassPlan p;
+        bhmm::plan::plan_pass(off, K, seglen, tiles != 0, p);
+        int ntraj = 0;
+        for (int k = 0; k < K; ++k)
+            ntraj += off[k + 1] > off[k];
+        CHECK(p.ntraj == ntraj && (int)p.seg.traj.size() >= ntraj);
+        CHECK(p.tile_seg.size() % 16 == 0 && (tiles != 0 || p.tile_seg.empty()));
+    }
+    int64_t maxT = 0;
+    for (int k = 0; k < K; ++k)
+        maxT = std::max(maxT, off[k + 1] - off[k]);
+    for (int Wmax : {bhmm::plan::probe_wmax(maxT), bhmm::plan::probe_wmax_wide(maxT)}) {
+        if (Wmax == 0)
+            continue;
+        std::vector<int64_t> starts;
+        bhmm::plan::probe_starts(off, K, Wmax, 256, starts);
+        CHECK(starts.size() == 256);
+        for (int64_t s : starts) {
+            const int k = (int)(std::upper_bound(off.begin(), off.end(), s) - off.begin()) - 1;
+            CHECK(k >= 0 && k < K && s + Wmax <= off[k + 1]);
+        }
+        std::vector<float> curve(2 * (size_t)Wmax, 0.f);
+        CHECK(bhmm::plan::curve_last(curve.data(), Wmax, 1e-13f, true) == -1);
+        curve[2 * (size_t)Wmax - 1] = 1.f;
+        CHECK(bhmm::plan::curve_last(curve.data(), Wmax, 1e-13f, false) == -1);
+        CHECK(bhmm::plan::curve_last(curve.data(), Wmax, 1e-13f, true) == Wmax - 1);
+        CHECK(bhmm::plan::warmup_of(Wmax - 1, Wmax) == Wmax && bhmm::plan::warmup_of(-1, Wmax) == 16);
+        CHECK(bhmm::plan::warmup_wide_of(-1) == 16 && bhmm::plan::warmup_wide_of(Wmax - 1) % 8 == 0);
+    }
+}
+
 static void planners()
 {
     // ragged lengths incl. T = 1, T = 0 (skipped), one long trajectory
@@ -150,6 +185,8 @@ static void planners()
         for (int64_t seglen : {(int64_t)0, (int64_t)4, (int64_t)100, (int64_t)4096, (int64_t)1 << 40})
             for (int mult : {1, 2})
                 check_seg_plan(off, (int)lens.size(), seglen, mult);
+        for (int64_t seglen : {(int64_t)4, (int64_t)4096})
+            check_pass_and_probe(off, (int)lens.size(), seglen);
     }
     // 1e5 short trajectories
     {
@@ -161,6 +198,7 @@ static void planners()
         check_chunk_plan(off, K, 2, 16, true);
         check_seg_plan(off, K, 16, 1);
         check_seg_plan(off, K, 0, 1);
+        check_pass_and_probe(off, K, 16);
     }
     // very long chunks: the tripled / doubled plan and the re-plan back to the default count
     {
