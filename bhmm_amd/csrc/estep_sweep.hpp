@@ -596,7 +596,8 @@ struct Carry {
                                    // not capture must round like one that does
 };
 
-template <int N, int KIND, bool SPEC, bool GAMMA, bool CAREFUL, int PHASE, bool BIGM = false>
+template <int N, int KIND, bool SPEC, bool GAMMA, bool CAREFUL, int PHASE, bool BIGM = false,
+          bool TABSG = false>
 __device__ __forceinline__ void estep_body(
     const Model<N> &m, const Chunks &ch, const void *obs_ci, const void *obs_rm,
     const int64_t *toff,   // [K+1] trajectory offsets (time steps)
@@ -621,6 +622,10 @@ __device__ __forceinline__ void estep_body(
     constexpr bool FWDONLY = PHASE == PH_FWDROWS;
     constexpr bool HAS_BWD = PHASE == PH_ALL || PHASE == PH_P2;
     static_assert(SPEC || PHASE == PH_ALL, "the split phases are speculative-only");
+    // TABSG: the state counts are the column sums of the workgroup's symbol table (both accumulate
+    // the same gamma), taken once in the epilogue instead of two additions per step and lane
+    static_assert(!TABSG || (KIND == EMIT_DISC && PHASE == PH_P2 && !CAREFUL && !BIGM),
+                  "only the branch-free backward launch of the discrete kind with LDS tables");
     // PH_P1: workgroup b and b + gridDim/2 share record group b (forward / backward warm-up)
     const int bidx = PHASE == PH_P1 ? (int)(blockIdx.x % (gridDim.x / 2)) : (int)blockIdx.x;
     const bool role_f = PHASE != PH_P1 || blockIdx.x < gridDim.x / 2;
@@ -1030,12 +1035,25 @@ __device__ __forceinline__ void estep_body(
         // at every step of the chunk, only the powers of two removed from alpha (ea, recorded by
         // PH_P1) and from beta (Eb) differ: PH_P2 takes one reciprocal per chunk (rS0, at the
         // last step, where alpha carries the exponent ebase) and scales it, 1/S = rS0 2^(ea + Eb -
-        // ebase), instead of a sum over the group and a reciprocal per step.  The single steps and
-        // the other instantiations sum and divide as before.
+        // ebase), instead of a sum over the group and a reciprocal per step.  The factor goes ONCE
+        // onto the stored alpha row a quad (pair) starts from (prescaled): the rebuild is linear and
+        // beta is rescaled only at the last step of a quad (pair), so the rows rebuilt from it are
+        // alpha / S too -- the xi weights w as they stand, and their products with A (p o beta) are
+        // gamma.  The single steps and the other instantiations sum and divide as before.
         constexpr bool EXPO = PHASE == PH_P2 && !CAREFUL;
         double rS0 = 0.0;
         int Eb = 0;
         const int ebase = EXPO ? ea_ci[g] : 0;
+        // EXPO: the stored row times 1 / S; the largest alpha / S of the rows of a quad (pair) goes to
+        // wmax there, once per stored row
+        [[maybe_unused]] auto prescaled = [&](const double2 &alo, int ea, double (&al)[2]) {
+            const double c = ldexp(rS0, ea + Eb - ebase);
+            al[0] = alo.x * c;
+            al[1] = alo.y * c;
+        };
+        [[maybe_unused]] auto wcheck = [&](const double (&w)[2]) {
+            wmax = max(max(wmax, __double2hiint(w[0])), __double2hiint(w[1]));
+        };
         {
 #ifdef ESTEP_CLOCKPROBE
             pr3 = wall_clock64();
@@ -1051,7 +1069,8 @@ __device__ __forceinline__ void estep_body(
         auto consume = [&](const ObsIn &in, const double (&d)[2], double2 *gdst) {
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
-                sg[b] += gam[b];
+                if constexpr (!TABSG)
+                    sg[b] += gam[b];
                 if constexpr (KIND == EMIT_GAUSS) {
                     const double gd = gam[b] * d[b];
                     sd[b] += gd;
@@ -1126,7 +1145,8 @@ __device__ __forceinline__ void estep_body(
         // steps s and s-1 from the stored row alpha_{s-2}: alpha_{s-1} = (alpha_{s-2} A) o p_{s-1}
         // up to a scale, which gamma and xi do not see
         // second half of a backward step, from the gathered p o beta: beta_{s-1}, gamma_{s-1}, xi
-        auto bfinish = [&](const double (&bf)[N], const double2 &apv, int ea, auto sc) {
+        // (EXPO: apv is alpha_{s-1} / S, see prescaled)
+        auto bfinish = [&](const double (&bf)[N], const double2 &apv, auto sc) {
             double r[2];
             r[0] = Ar[0][0] * bf[0];
             r[1] = Ar[1][0] * bf[0];
@@ -1136,16 +1156,19 @@ __device__ __forceinline__ void estep_body(
                 r[1] = fma(Ar[1][j], bf[j], r[1]);
             }
             const double q0 = apv.x * r[0], q1 = apv.y * r[1];
-            double rS;
-            if constexpr (EXPO)
-                rS = ldexp(rS0, ea + Eb - ebase);
-            else
-                rS = fast_rcp(grp_sum<H>(q0 + q1));
-            gam[0] = q0 * rS;
-            gam[1] = q1 * rS;
-            const double w0 = apv.x * rS, w1 = apv.y * rS;
-            if constexpr (!CAREFUL)
-                wmax = max(wmax, max(__double2hiint(w0), __double2hiint(w1)));
+            double w0 = apv.x, w1 = apv.y;
+            if constexpr (EXPO) {
+                gam[0] = q0;
+                gam[1] = q1;
+            } else {
+                const double rS = fast_rcp(grp_sum<H>(q0 + q1));
+                gam[0] = q0 * rS;
+                gam[1] = q1 * rS;
+                w0 *= rS;
+                w1 *= rS;
+                if constexpr (!CAREFUL)
+                    wmax = max(wmax, max(__double2hiint(w0), __double2hiint(w1)));
+            }
 #pragma unroll
             for (int j = 0; j < N; ++j) {
                 Cacc[0][j] = fma(w0, bf[j], Cacc[0][j]);
@@ -1170,7 +1193,7 @@ __device__ __forceinline__ void estep_body(
         auto bpair = [&](const ObsIn &hi, const ObsIn &lo, const double2 &alo, int ea,
                          double2 *gdst, auto sc_hi, auto sc_lo) {
             double p_hi[2], d_hi[2], p_lo[2], d_lo[2], sv[2], ah[2];
-            const double al[2] = {alo.x, alo.y};
+            double al[2] = {alo.x, alo.y};
             // (per-step-checked kernels, every emission kind: the rebuilt alpha row is RESCALED.  Left
             // at the magnitude of its emission row -- explicit rows of 1e-222 -- its product with
             // A (p o beta) underflowed to zero, S = 0, gamma and the counts NaN: found by the explicit
@@ -1186,6 +1209,10 @@ __device__ __forceinline__ void estep_body(
                 bcore(lo, p_lo, d_lo, alo, gdst - RS, sc_lo);
             } else {
                 double afl[N], bf[N];
+                if constexpr (EXPO) {
+                    prescaled(alo, ea, al);
+                    wcheck(al);
+                }
                 gather(al, afl); // (1) alpha_{s-2}, for the rebuild
                 sched_fence();
                 emit_raw<N, KIND, CAREFUL>(m, gmask, nreal, hi, Bt, q, em, p_hi, d_hi);
@@ -1201,13 +1228,15 @@ __device__ __forceinline__ void estep_body(
                 sched_fence();
                 ah[0] = sv[0] * p_lo[0];
                 ah[1] = sv[1] * p_lo[1];
-                bfinish(bf, make_double2(ah[0], ah[1]), ea, sc_hi);
+                if constexpr (EXPO)
+                    wcheck(ah);
+                bfinish(bf, make_double2(ah[0], ah[1]), sc_hi);
                 consume(lo, d_lo, gdst - RS);
                 {
                     const double bb[2] = {p_lo[0] * b2[0], p_lo[1] * b2[1]};
                     gather(bb, bf); // (3) p o beta of step s-1
                 }
-                bfinish(bf, alo, ea, sc_lo);
+                bfinish(bf, make_double2(al[0], al[1]), sc_lo);
             }
         };
         // Four steps s .. s-3 from the stored row alpha_{s-4} (ESTEP_CK_OF == 4): the three rows in
@@ -1218,7 +1247,7 @@ __device__ __forceinline__ void estep_body(
                                           auto sc3, auto sc2, auto sc1, auto sc0) {
             double p3[2], d3[2], p2[2], d2[2], p1[2], d1[2], p0[2], d0[2], sv[2];
             double a1[2], a2[2], a3[2], af[N], bf[N];
-            const double al[2] = {alo.x, alo.y};
+            double al[2] = {alo.x, alo.y};
             if constexpr (CAREFUL) {
                 // per-step-checked kernels: every rebuilt row is RESCALED (three steps of emission
                 // probabilities of 1e-150 took the unscaled rows to zero, S = 0, gamma and the counts
@@ -1244,6 +1273,8 @@ __device__ __forceinline__ void estep_body(
                 (void)bf;
                 return;
             }
+            if constexpr (EXPO)
+                prescaled(alo, ea, al);
             gather(al, af); // alpha_{s-4}
             sched_fence();
             emit_raw<N, KIND, CAREFUL>(m, gmask, nreal, x0, Bt, q, em, p0, d0);
@@ -1264,17 +1295,23 @@ __device__ __forceinline__ void estep_body(
             fwd_dot<N>(af, Ac, sv);
             a3[0] = sv[0] * p2[0]; // alpha_{s-1}
             a3[1] = sv[1] * p2[1];
+            if constexpr (EXPO) {
+                wcheck(al);
+                wcheck(a1);
+                wcheck(a2);
+                wcheck(a3);
+            }
             auto back = [&](const ObsIn &in, const double (&p)[2], const double (&d)[2],
                             const double2 &apv, double2 *gd, auto sc) {
                 consume(in, d, gd);
                 const double bb[2] = {p[0] * b2[0], p[1] * b2[1]};
                 gather(bb, bf);
-                bfinish(bf, apv, ea, sc);
+                bfinish(bf, apv, sc);
             };
             back(x3, p3, d3, make_double2(a3[0], a3[1]), gdst, sc3);
             back(x2, p2, d2, make_double2(a2[0], a2[1]), gdst - RS, sc2);
             back(x1, p1, d1, make_double2(a1[0], a1[1]), gdst - 2 * RS, sc1);
-            back(x0, p0, d0, alo, gdst - 3 * RS, sc0);
+            back(x0, p0, d0, make_double2(al[0], al[1]), gdst - 3 * RS, sc0);
         };
         // the observation of step 0 is needed last: fetch it now
         const ObsIn in0 = ObsCursor<N, KIND>(obs_ci, rec0, cl, q).at(0);
@@ -1459,7 +1496,20 @@ __device__ __forceinline__ void estep_body(
             // that does not come out at its length (an intermediate product in the denormal range
             // that the scale tracking did not see, anything non-finite) is reported like a tiny
             // vector: the host repeats the E-step with the per-step-checked kernels.
-            const double mass = grp_sum<H>(sg[0] + sg[1]);
+            // (TABSG keeps no gamma sums: every backward step's gamma_{s-1} is the row sums of its xi
+            // contribution, gamma_{s-1}[i] = w[i] sum_j A[i][j] (p o beta)[j], so the same mass is read
+            // off the xi accumulators; the first gamma of the chunk is normalised by construction and
+            // a chunk that does not start its trajectory takes one more backward step)
+            double mass;
+            if constexpr (TABSG) {
+                double mc = 0.0;
+#pragma unroll
+                for (int j = 0; j < N; ++j)
+                    mc = fma(Ar[0][j], Cacc[0][j], fma(Ar[1][j], Cacc[1][j], mc));
+                mass = grp_sum<H>(mc) + (first ? 1.0 : 0.0);
+            } else {
+                mass = grp_sum<H>(sg[0] + sg[1]);
+            }
             if (!(fabs(mass - (double)len) <= 1e-8 * (double)len))
                 hmin = 0;
             // ... and a state that carries weight although its (A (p o beta)) entry is below 2^-910
@@ -1512,9 +1562,11 @@ __device__ __forceinline__ void estep_body(
                 if (lane < H)
                     mine[(2 * q + b) * N + G::slot(j, q)] = v;
             }
-            const double v = chunk_sum(sg[b]);
-            if (lane < H)
-                mine[SL::NC + 2 * q + b] = v;
+            if constexpr (!TABSG) {
+                const double v = chunk_sum(sg[b]);
+                if (lane < H)
+                    mine[SL::NC + 2 * q + b] = v;
+            }
             if constexpr (KIND == EMIT_GAUSS) {
                 const double v1 = chunk_sum(sd[b]);
                 const double v2 = chunk_sum(sdd[b]);
@@ -1530,6 +1582,19 @@ __device__ __forceinline__ void estep_body(
 #pragma unroll
             for (int w = 1; w < NW; ++w)
                 v += red[w * SL::S + i];
+            if constexpr (TABSG) {
+                // state count = column sum of the workgroup's symbol counts, in the fixed order
+                // symbol by symbol of the very sums that go to disc_partials below
+                if (i >= SL::NC && i < SL::NC + N) {
+                    v = 0.0;
+                    for (int o = 0; o < Mlds; ++o) {
+                        double t = dstat0[o * N + (i - SL::NC)];
+                        for (int w = 1; w < dcopies; ++w)
+                            t += dstat0[w * (m.M * N) + o * N + (i - SL::NC)];
+                        v += t;
+                    }
+                }
+            }
             partials[(int64_t)blockIdx.x * SL::S + i] = v;
         }
         if constexpr (KIND == EMIT_DISC)
@@ -1563,6 +1628,13 @@ __global__ __launch_bounds__(32 * N)
         if (m.bt_global) { // alphabet beyond the LDS: tables in global memory (uniform branch)
             estep_body<N, KIND, SPEC, GAMMA, CAREFUL, PHASE, true>(ESTEP_PASS);
             return;
+        }
+        // one count table per wavefront (bit-reproducible sums): the state counts come from the tables
+        if constexpr (PHASE == PH_P2 && !CAREFUL) {
+            if (m.dcopies == (32 * N + 63) / 64) {
+                estep_body<N, KIND, SPEC, GAMMA, CAREFUL, PHASE, false, true>(ESTEP_PASS);
+                return;
+            }
         }
     }
     estep_body<N, KIND, SPEC, GAMMA, CAREFUL, PHASE>(ESTEP_PASS);
