@@ -98,6 +98,9 @@ static int stats_size(const bhmm_ctx *c);
 // symbols whose tables live in the LDS of the sweep kernels: all of them, or none (big alphabets)
 static int lds_symbols(const bhmm_ctx *c) { return c->bt_global ? 0 : c->M; }
 static int64_t ci_records(const bhmm_ctx *c) { return (int64_t)(c->Gp / 64) * c->Lmax; }
+// the unconditional refills of the sweeps (estep_sweep.hpp) stay inside the guards of the buffers they read
+static_assert(SWEEP_REACH_BACK <= (int)bhmm_ctx::SWEEP_GUARD_BACK && SWEEP_REACH_FRONT <= (int)bhmm_ctx::SWEEP_GUARD_FRONT,
+              "a deeper prefetch needs wider guards around d_obs_ci, d_ws and d_ea (ctx.hpp)");
 
 int replan_coarse(bhmm_ctx *c, bool half = false, int chunk = 0); // (defined with bhmm_ctx_set_observations)
 int replan_for_warmup(bhmm_ctx *c);
@@ -1617,6 +1620,8 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->opt.carry_enabled ? 1.0 : 0.0;
     else if (n == "carry_W") // warm-up steps of the last E-step's carried starts (0: full warm-ups)
         *value = c->last.carry_last_W;
+    else if (n == "carry_cap") // where the last E-step's backward sweep was split for the capture (0: not split)
+        *value = c->ds.carry_cap;
     else if (n == "carry_ok")
         *value = c->last.carry_ok;
     else if (n == "carry_fail")

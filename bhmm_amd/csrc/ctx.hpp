@@ -25,7 +25,14 @@ template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    // Guard elements in front of p[0] and behind p[n - 1], inside the allocation (both multiples of
+    // 16 bytes).  The sweeps of k_estep refill their prefetch registers unconditionally: a chunk's last
+    // iteration loads a few CI records before its first (backward) or behind its last (forward) one.
+    // Nothing consumes those values, but the addresses must be mapped (SWEEP_GUARD_* below).
+    const size_t front = 0, back = 0;
+    T *base = nullptr; // what hipMalloc returned: p - front
     DevBuf() = default;
+    DevBuf(size_t front_, size_t back_) : front(front_), back(back_) {}
     DevBuf(const DevBuf &) = delete; // (owns its allocation)
     DevBuf &operator=(const DevBuf &) = delete;
     ~DevBuf() { release(); } // (bhmm_ctx_destroy deletes the context on its own device: nothing is left behind)
@@ -33,33 +40,33 @@ struct DevBuf {
     {
         if (count <= n)
             return BHMM_OK;
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), count * sizeof(T));
+        release();
+        const size_t total = front + count + back;
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&base), total * sizeof(T));
         if (e != hipSuccess) {
-            set_error(std::string("hipMalloc of ") + std::to_string(count * sizeof(T)) +
+            base = nullptr;
+            set_error(std::string("hipMalloc of ") + std::to_string(total * sizeof(T)) +
                       " bytes failed: " + hipGetErrorString(e));
             (void)hipGetLastError();
             return BHMM_ERR_NO_MEM;
         }
+        p = base + front;
         n = count;
         // debugging aid: BHMM_AMD_POISON=1 fills every fresh allocation with 0xFF bytes (NaN doubles,
         // -1 integers), so that a kernel that reads what nothing wrote shows up at once instead of
         // depending on what the allocator handed out
         static const bool poison = getenv("BHMM_AMD_POISON") != nullptr;
         if (poison) { // (the fill runs on the null stream; the context's streams do not wait for it by themselves)
-            (void)hipMemset(p, 0xFF, count * sizeof(T));
+            (void)hipMemset(base, 0xFF, total * sizeof(T));
             (void)hipDeviceSynchronize();
         }
         return BHMM_OK;
     }
     void release()
     {
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
+        if (base)
+            (void)hipFree(base);
+        base = p = nullptr;
         n = 0;
     }
 };
@@ -287,11 +294,18 @@ struct bhmm_ctx {
     // ---- device buffers (kept across observation sets: DevBuf::ensure only grows them) ----
     bhmm::DevBuf<int32_t> d_ctraj, d_clen, d_traj_c0;
     bhmm::DevBuf<int64_t> d_ct0, d_cgoff;
-    bhmm::DevBuf<char> d_obs_ci;     // CI observations (double / int32 / N doubles)
+    // Guards of the buffers k_estep prefetches from (DevBuf::front / back), in CI records of the largest
+    // kind (8 states): the backward sweeps reach up to 8 records before a chunk's first one (observations,
+    // alpha rows, their exponents), the forward sweep up to 2 * ESTEP_PF_F = 8 records behind its last one
+    // (observations only).  An explicit-emission record is 8 * 64 doubles like an alpha row.
+    static constexpr size_t SWEEP_GUARD_FRONT = 8, SWEEP_GUARD_BACK = 8, SWEEP_REC_DOUBLES = 8 * 64;
+    bhmm::DevBuf<char> d_obs_ci{SWEEP_GUARD_FRONT * SWEEP_REC_DOUBLES * sizeof(double),
+                                SWEEP_GUARD_BACK * SWEEP_REC_DOUBLES * sizeof(double)}; // CI observations (double / int32 / N doubles)
     bhmm::DevBuf<char> d_obs_rm;     // trajectory-major observations (Viterbi / sampling)
     bhmm::DevBuf<double> d_Bt;       // [M][N] transposed emission matrix
     bhmm::DevBuf<double> d_M;        // chunk transfer matrices
-    bhmm::DevBuf<double> d_aentry, d_bexit, d_ws, d_gamma_ci;
+    bhmm::DevBuf<double> d_aentry, d_bexit, d_gamma_ci;
+    bhmm::DevBuf<double> d_ws{SWEEP_GUARD_FRONT * SWEEP_REC_DOUBLES, 0}; // CI workspace: alpha / beta rows
     bhmm::DevBuf<float> d_ws32;      // Gibbs step: CI alpha rows rounded to fp32 (forward-only pass)
     bhmm::DevBuf<double> d_logLc, d_logLk, d_gamma0, d_partials, d_dpartials, d_stats;
     bhmm::DevBuf<char> d_scratch;    // paths, uniforms, pointer tables ...
@@ -308,7 +322,9 @@ struct bhmm_ctx {
     bhmm::DevBuf<double> d_carry_a, d_carry_b;
     bhmm::DevBuf<int32_t> d_carry_da, d_carry_db;
     bhmm::DevBuf<unsigned int> d_specres;
-    bhmm::DevBuf<int32_t> d_ea;       // exponents of the stored alpha rows (k_estep PH_P1 -> PH_P2)
+    // exponents of the stored alpha rows (k_estep PH_P1 -> PH_P2): [Gp] per chunk, then CI rows of 64; the
+    // guard in front keeps SWEEP_GUARD_FRONT rows before the first one mapped however small Gp is
+    bhmm::DevBuf<int32_t> d_ea{SWEEP_GUARD_FRONT * 64, 0};
     bhmm::DevBuf<double> d_tail;      // same layout as h_raw, written by k_tail (one D2H copy)
     bhmm::DevBuf<double> d_fold;      // partial statistics folded 128 rows at a time (k_fold_rows)
     bhmm::DevBuf<double> d_tbpart;    // k_tail: per trajectory block [sum logL | sum gamma_0 (N)]

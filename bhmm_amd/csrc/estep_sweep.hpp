@@ -558,6 +558,13 @@ __device__ __forceinline__ void beta_step(const G &gather, const ObsIn &in, int 
 #ifndef ESTEP_PF_B
 #define ESTEP_PF_B 2 // ... backward sweep (observations + alpha)
 #endif
+// How far the unconditional refills of the main loops read outside a chunk, in CI records (nothing
+// consumes them; the buffers carry guards of at least this size, checked where they are allocated):
+// behind its last record the forward loop refills both sets of ESTEP_PF_F once more; before its first
+// record the backward quad loop refills two quads of four and the stored row four before them, the pair
+// loop one pair and its row, the uncheckpointed loop one set of ESTEP_PF_B and its rows.
+constexpr int SWEEP_REACH_BACK = 2 * ESTEP_PF_F;
+constexpr int SWEEP_REACH_FRONT = (2 * 4 > ESTEP_PF_B) ? 2 * 4 : ESTEP_PF_B;
 #ifndef ESTEP_CKPT
 #define ESTEP_CKPT 1 // keep every second alpha row in HBM, rebuild the others
 #endif
@@ -876,20 +883,38 @@ __device__ __forceinline__ void estep_body(
                 single(po, pw, (s % CKS) == 0);
                 ++s;
             }
-            // groups of 2 PF steps (two register sets, each loaded PF..2PF-1 steps before its
-            // use), then the remaining 0 .. 2PF-1 steps one by one
+            // groups of 2 PF steps (two register sets, each refilled right after its last use, PF+1
+            // .. 2PF steps before its next one), then the remaining 0 .. 2PF-1 steps one by one.
+            // Both refills are unconditional and both sets are loaded before the loop: a wavefront's
+            // vector-memory operations retire in issue order, so the wait in front of a set's first
+            // use covers whatever was issued before that set's loads -- with a refill inside a
+            // branch, or the y loads at the top of the iteration, that took in the loads just issued
+            // or the row stores of the last few steps (profiles/prefetch_waits/isa_waits.md).  The
+            // last group reads up to 2 PF records behind the chunk, which nothing consumes: records
+            // of the same or the next record group, or the guard behind the observations
+            // (DevBuf::back).
             const int tail = (len - s) % (2 * PF);
             int rem = len - s - tail;
             if (rem > 0) {
                 ObsIn x[PF], y[PF];
                 double2 ox[PF], oy[PF];
+                // (in the order of their use, each behind a fence: the wait counts of the loop hold on
+                // the way in as well, and the compiler, left alone, issues these loads last one first)
 #pragma unroll
-                for (int j = 0; j < PF; ++j)
+                for (int j = 0; j < PF; ++j) {
                     x[j] = po.at(j);
-                for (; rem > 0; rem -= 2 * PF) {
+                    sched_fence();
+                }
 #pragma unroll
-                    for (int j = 0; j < PF; ++j)
-                        y[j] = po.at(PF + j);
+                for (int j = 0; j < PF; ++j) {
+                    y[j] = po.at(PF + j);
+                    sched_fence();
+                }
+                // one group of 2 PF steps.  It stands twice: once in front of the loop and once as the
+                // loop body, so that the loop is entered with the same operations in flight as it is
+                // repeated with -- the wait counts of the loop body are then not bounded by a path into
+                // it on which no stores follow the loads of the x set
+                auto group = [&]() __attribute__((always_inline)) {
                     unrolled<PF>([&](auto j) {
                         fstep(x[j], ox[j], sc_at<j>());
                         if constexpr (FWDONLY) {
@@ -902,11 +927,9 @@ __device__ __forceinline__ void estep_body(
                                 pe[j * 64] = eP;
                         }
                     });
-                    if (rem > 2 * PF) {
 #pragma unroll
-                        for (int j = 0; j < PF; ++j)
-                            x[j] = po.at(2 * PF + j);
-                    }
+                    for (int j = 0; j < PF; ++j)
+                        x[j] = po.at(2 * PF + j);
                     unrolled<PF>([&](auto j) {
                         fstep(y[j], oy[j], sc_at<PF + j>());
                         if constexpr (FWDONLY) {
@@ -917,6 +940,9 @@ __device__ __forceinline__ void estep_body(
                                 pe[(PF + j) * 64] = eP;
                         }
                     });
+#pragma unroll
+                    for (int j = 0; j < PF; ++j)
+                        y[j] = po.at(3 * PF + j);
                     if constexpr (CKPT) {
                         // the backward sweep reads the last (len-1) % (2 CKS) + 1 rows directly: if
                         // the single steps below do not cover them, all rows of the last group are kept
@@ -937,7 +963,10 @@ __device__ __forceinline__ void estep_body(
                         pw32 += 2 * PF * RS32;
                         s += 2 * PF;
                     }
-                }
+                };
+                group();
+                for (rem -= 2 * PF; rem > 0; rem -= 2 * PF)
+                    group();
             }
             for (int i = tail; i > 0; --i) // step len - i
                 single(po, pw, ((len - i) % CKS) == 0);
@@ -1336,11 +1365,33 @@ __device__ __forceinline__ void estep_body(
                 if (rem > 0) {
                     const int32_t *pea = ea_rows + (rec0 + rem) * 64 + cl;
                     ObsIn x[4], y[4];
-                    double2 xa = pa[-4 * RS], ya;
-                    int xe = EXPO ? pea[-4 * 64] : 0, ye = 0;
+                    double2 xa, ya;
+                    int xe = 0, ye = 0;
+                    // both sets before the loop, in the order of their use and each load behind a
+                    // fence, so that the wait counts of the loop hold on the way in as well (left
+                    // alone the compiler issues them last one first)
+                    if constexpr (EXPO) {
+                        xe = pea[-4 * 64];
+                        sched_fence();
+                    }
+                    xa = pa[-4 * RS];
+                    sched_fence();
 #pragma unroll
-                    for (int j = 0; j < 4; ++j)
+                    for (int j = 3; j >= 0; --j) {
                         x[j] = po.at(-j);
+                        sched_fence();
+                    }
+                    if constexpr (EXPO) {
+                        ye = pea[-8 * 64];
+                        sched_fence();
+                    }
+                    ya = pa[-8 * RS];
+                    sched_fence();
+#pragma unroll
+                    for (int j = 3; j >= 0; --j) {
+                        y[j] = po.at(-4 - j);
+                        sched_fence();
+                    }
                     // (PH_P2 with a capture request: the same loop runs in two stretches, down to
                     // `cap` remaining steps and then to the end; in between b2 -- beta at my local
                     // step cap, cap + 1 steps after the last step of the chunk before me -- is
@@ -1351,24 +1402,30 @@ __device__ __forceinline__ void estep_body(
 #pragma clang loop unroll(disable)
                     for (int stretch = 0; stretch < 2; ++stretch) {
                     for (; rem > stop; rem -= 8) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            y[j] = po.at(-4 - j);
-                        ya = pa[-8 * RS];
-                        if constexpr (EXPO)
-                            ye = pea[-8 * 64];
                         bquad(x[0], x[1], x[2], x[3], xa, xe, pg, sc_at<0>(), sc_at<1>(), sc_at<2>(),
                               sc_at<3>());
-                        if (rem > 8) {
+                        // Each set is refilled right after its last use, unconditionally.  A wavefront's
+                        // vector-memory operations retire in issue order and a wait names how many may
+                        // stay outstanding: with the refill of x inside `if (rem > 8)` the wait in front
+                        // of the y quad had to hold on the path around it and came out as vmcnt(0) -- the
+                        // six loads just issued, a full memory latency every eight steps
+                        // (profiles/prefetch_waits/isa_waits.md).  The last iteration reads up to eight
+                        // records before the chunk's first one, which nothing consumes: the previous
+                        // record group's, or the guards in front of the buffers (DevBuf::front).
 #pragma unroll
-                            for (int j = 0; j < 4; ++j)
-                                x[j] = po.at(-8 - j);
-                            xa = pa[-12 * RS];
-                            if constexpr (EXPO)
-                                xe = pea[-12 * 64];
-                        }
+                        for (int j = 0; j < 4; ++j)
+                            x[j] = po.at(-8 - j);
+                        xa = pa[-12 * RS];
+                        if constexpr (EXPO)
+                            xe = pea[-12 * 64];
                         bquad(y[0], y[1], y[2], y[3], ya, ye, pg - 4 * RS, sc_at<0>(), sc_at<1>(),
                               sc_at<2>(), sc_at<3>());
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            y[j] = po.at(-12 - j);
+                        ya = pa[-16 * RS];
+                        if constexpr (EXPO)
+                            ye = pea[-16 * 64];
                         po.move(-8);
                         pa -= 8 * RS;
                         pg -= 8 * RS;
@@ -1411,13 +1468,11 @@ __device__ __forceinline__ void estep_body(
                         if constexpr (EXPO)
                             ye = pea[-4 * 64];
                         bpair(xh, xl, xa, xe, pg, sc_at<0>(), sc_at<1>());
-                        if (rem > 4) {
-                            xh = po.at(-4);
-                            xl = po.at(-5);
-                            xa = pa[-6 * RS];
-                            if constexpr (EXPO)
-                                xe = pea[-6 * 64];
-                        }
+                        xh = po.at(-4); // (unconditional, see the quad loop)
+                        xl = po.at(-5);
+                        xa = pa[-6 * RS];
+                        if constexpr (EXPO)
+                            xe = pea[-6 * 64];
                         bpair(yh, yl, ya, ye, pg - 2 * RS, sc_at<2>(), sc_at<3>());
                         po.move(-4);
                         pa -= 4 * RS;
@@ -1459,12 +1514,10 @@ __device__ __forceinline__ void estep_body(
                             v[j] = pa[-(PF + j + 1) * RS];
                         }
                         unrolled<PF>([&](auto j) { bstep(x[j], u[j], pg - j * RS, sc_at<j>()); });
-                        if (rem > 2 * PF) {
 #pragma unroll
-                            for (int j = 0; j < PF; ++j) {
-                                x[j] = po.at(-(2 * PF + j));
-                                u[j] = pa[-(2 * PF + j + 1) * RS];
-                            }
+                        for (int j = 0; j < PF; ++j) { // (unconditional, see the quad loop)
+                            x[j] = po.at(-(2 * PF + j));
+                            u[j] = pa[-(2 * PF + j + 1) * RS];
                         }
                         unrolled<PF>([&](auto j) {
                             bstep(y[j], v[j], pg - (PF + j) * RS, sc_at<PF + j>());

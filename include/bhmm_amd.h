@@ -341,6 +341,8 @@ int bhmm_sample_paths_dev(bhmm_ctx *ctx, const double *A, const double *pi, cons
  *   "carry_W", "carry_ok", "carry_fail"  (read-only) warm-up steps of the last E-step's carried
  *                        starts (0: full warm-ups), E-steps that verified on carried starts /
  *                        had to be repeated
+ *   "carry_cap"          (read-only) local step at which the last E-step's backward sweep was split
+ *                        to capture beta for the next one (0: one stretch, nothing captured)
  *   "spec_ok", "spec_fail"  (read-only) E-steps whose boundaries verified / fell back
  *   "spec_last_dev" (read-only) largest relative boundary deviation of the last check
  *   "f32_used"      (read-only) 1 if the last E-step ran in fp32 end to end (BHMM_FLAG_SINGLE)
