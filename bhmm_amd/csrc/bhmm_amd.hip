@@ -1538,6 +1538,20 @@ int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
         if (value != 0.0 && value != 1.0 && value != -1.0)
             return invalid_arg("filter_tile must be -1, 0 or 1");
         c->opt.filter_tile = (int)value;
+    } else if (n == "smooth_wide") { // posterior calls, 9..64 states: the time-segmented path: 0 never, 1 always when eligible, -1 automatic
+        if (value != 0.0 && value != 1.0 && value != -1.0)
+            return invalid_arg("smooth_wide must be -1, 0 or 1");
+        c->opt.smooth_wide = (int)value;
+    } else if (n == "smooth_seglen") { // ... segment length of its plan from the next call on (0: automatic)
+        if (!(value >= 0 && value <= (1 << 30)))
+            return invalid_arg("smooth_seglen outside [0, 2^30]");
+        c->opt.smooth_seglen = ((int)value + 3) & ~3;
+    } else if (n == "smooth_W") // ... fixed warm-up (0: measured); no E-step state changes
+        c->opt.smooth_W = std::max(0, (int)std::min(value, (double)(1 << 30)));
+    else if (n == "smooth_ws_mb") { // ... budget of its alpha-row workspace in MiB (0: unbounded)
+        if (!(value >= 0.0) || value > (double)(1 << 30))
+            return invalid_arg("smooth_ws_mb outside [0, 2^30]");
+        c->opt.smooth_ws_mb = (int)value;
     } else
         return invalid_arg("unknown or read-only option: " + n);
     return BHMM_OK;
@@ -1661,7 +1675,7 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->opt.post_ws_mb;
     else if (n == "post_fallbacks") // bhmm_posterior_decode: calls whose boundaries did not verify at the first warm-up
         *value = c->last.post_fallbacks;
-    else if (n == "post_path") // ... first pass of the last call: 1 fused kernel (up to 8 states), 0 E-step + gamma rows
+    else if (n == "post_path") // ... first pass of the last call: 2 time segments (9..64 states), 1 fused kernel (up to 8 states), 0 E-step + gamma rows
         *value = c->last.post_path;
     else if (n == "marg_W")
         *value = c->opt.marg_W;
@@ -1669,7 +1683,7 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->opt.marg_ws_mb;
     else if (n == "marg_fallbacks") // bhmm_posterior_marginals: calls whose boundaries did not verify at the first warm-up
         *value = c->last.marg_fallbacks;
-    else if (n == "marg_path") // ... first pass of the last call: 1 fused kernel (up to 8 states), 0 E-step + gamma rows
+    else if (n == "marg_path") // ... first pass of the last call: 2 time segments (9..64 states), 1 fused kernel (up to 8 states), 0 E-step + gamma rows
         *value = c->last.marg_path;
     else if (n == "filter_W")
         *value = c->opt.filter_W;
@@ -1691,6 +1705,18 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = (double)FILTER_TILE_MIN_TOTAL;
     else if (n == "filter_redone") // ... trajectories of the last call that path did again on the serial kernel
         *value = c->last.filter_redone;
+    else if (n == "smooth_wide")
+        *value = c->opt.smooth_wide;
+    else if (n == "smooth_seglen")
+        *value = c->opt.smooth_seglen;
+    else if (n == "smooth_W")
+        *value = c->opt.smooth_W;
+    else if (n == "smooth_ws_mb")
+        *value = c->opt.smooth_ws_mb;
+    else if (n == "smooth_segments") // posterior calls: segments of the smoothing plan the last call ran on (0: another path)
+        *value = c->last.smooth_segments;
+    else if (n == "smooth_wide_min_total") // ... steps below which smooth_wide = -1 never takes the time-segmented path
+        *value = (double)SMOOTH_WIDE_MIN_TOTAL;
     else if (n == "score_path") // ... first pass of the last call: 0 serial kernel, 1 chunk kernels (N <= 8), 2 k_score_wide, 3 k_score_tile
         *value = c->last.score_path;
     else

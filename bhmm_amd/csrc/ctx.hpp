@@ -130,6 +130,12 @@ struct bhmm_ctx {
                                          // (eligible and at least FILTER_WIDE_MIN_TOTAL steps; option filter_parallel)
         int filter_tile = -1;            // ... 65..128 states, the matrix-core path (k_filter_tile): 0 never, 1 always when
                                          // eligible, -1 automatic (at least FILTER_TILE_MIN_TOTAL steps; option filter_tile)
+        int smooth_wide = -1;            // bhmm_posterior_decode / bhmm_posterior_marginals, 9..64 states: the time-segmented
+                                         // path (k_filter_wide + k_smooth_wide_bwd): 0 never, 1 always when eligible, -1
+                                         // automatic (smooth_wide_auto, smooth_wide_launch.hpp; option smooth_wide)
+        int smooth_seglen = 0;           // ... segment length of its plan (option smooth_seglen; 0: automatic)
+        int smooth_W = 0;                // ... warm-up fixed by the caller (option smooth_W; 0: measured)
+        int smooth_ws_mb = 8192;         // ... budget of its alpha-row workspace in MiB (option smooth_ws_mb; 0: unbounded)
     } opt;
 
     // ---- loaded problem ----
@@ -212,6 +218,11 @@ struct bhmm_ctx {
         int filt_tile_ntraj = 0;         // ... trajectories with at least one step (nseg == ntraj: no boundary)
         int filt_tile_ntiles = 0;        // ... tiles of 16 segments
         int filt_tile_seglen_opt = 0;    // ... opt.filter_seglen it was made for
+        // posterior calls, 9..64 states: the segment plan of the smoothing pass (tables in smooth.seg, host copies
+        // smooth.seg_len / seg_g0), made the same way; none of the plans above
+        int smooth_nseg = 0;             // segments of the plan (0: not made yet)
+        int smooth_ntraj = 0;            // ... trajectories with at least one step (nseg == ntraj: no boundary)
+        int smooth_seglen_opt = 0;       // ... opt.smooth_seglen it was made for
     } ds;
 
     // ---- counters and diagnostics of the last calls (bhmm_ctx_get_option) ----
@@ -245,9 +256,12 @@ struct bhmm_ctx {
         int score_segments = 0;          // ... segments of the score plan it ran on (0: no such plan)
         int score_W_max = 0;             // ... longest warm-up of its first pass at 9..128 states (0: no boundary, other paths)
         int post_fallbacks = 0;          // bhmm_posterior_decode: calls whose boundaries did not verify at the first warm-up
-        int post_path = 0;               // ... first pass of the last call: 1 fused (k_post_sweep), 0 generic (E-step + gamma rows)
+        int post_path = 0;               // ... first pass of the last call: 2 time segments (k_smooth_wide_bwd, 9..64 states),
+                                         // 1 fused (k_post_sweep), 0 generic (E-step + gamma rows)
         int marg_fallbacks = 0;          // bhmm_posterior_marginals: calls whose boundaries did not verify at the first warm-up
-        int marg_path = 0;               // ... first pass of the last call: 1 fused (k_marg_sweep), 0 generic (E-step + gamma rows)
+        int marg_path = 0;               // ... first pass of the last call: 2 time segments (k_smooth_wide_bwd, 9..64 states),
+                                         // 1 fused (k_marg_sweep), 0 generic (E-step + gamma rows)
+        int smooth_segments = 0;         // segments of the smoothing plan the last posterior call ran on (0: another path)
         int filter_fallbacks = 0;        // bhmm_filter: calls whose boundaries did not verify at the first warm-up
         int filter_path = 0;             // ... first pass of the last call: 3 matrix cores (k_filter_tile, 65..128 states),
                                          // 2 time segments (k_filter_wide, 9..64 states), 1 fused (k_filter_sweep, up to
@@ -404,6 +418,21 @@ struct bhmm_ctx {
         bhmm::SegTables seg, tseg;
         bhmm::DevBuf<uint8_t> redo;
     } filt;
+    // the time-segmented path of the two posterior calls at 9..64 states (smooth_wide.hip): its own buffers -- model,
+    // parameter block, probe curve, the tables of the plan ds.smooth_nseg counts with host copies of every segment's
+    // length and first global step (the ranges of the budgeted workspace are cut on the host), the filtered rows of
+    // one range of segments (ws), entry / exit vectors of both directions, the segments whose forward sum became
+    // zero (dead) and those the backward kernel flagged (trouble), and the words [boundaries out of tolerance |
+    // largest deviation | flagged segments] (fails); nothing else reads them
+    struct SmoothBufs {
+        bhmm::DevBuf<char> model, probe;
+        bhmm::DevBuf<double> wpar, ws, aentry, aexit, bexit, bentry;
+        bhmm::DevBuf<uint8_t> dead, trouble;
+        bhmm::DevBuf<unsigned int> fails;
+        bhmm::SegTables seg;
+        std::vector<int32_t> seg_len;
+        std::vector<int64_t> seg_g0;
+    } smooth;
 
     // ---- pinned host buffers ----
     unsigned int *h_specres = nullptr; // pinned

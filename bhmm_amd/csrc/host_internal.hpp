@@ -83,6 +83,13 @@ constexpr int64_t FILTER_WIDE_MIN_TOTAL = 32768;
 // (128 states: 50.0 ms against 2.5 ms there), so this is the floor, not the break-even.
 constexpr int64_t FILTER_TILE_MIN_TOTAL = 32768;
 
+// ---- smooth_wide.hip (bhmm_posterior_decode / bhmm_posterior_marginals at 9..64 states) ----
+// Steps of an observation set below which the option smooth_wide = -1 never takes the time-segmented path (read-only
+// option smooth_wide_min_total): a power of two, not below 32768 -- the existing tests pin the generic path for a
+// default call on 23734 steps.  Above it the automatic rule is per lane-group class and call form, from the
+// measurements of DESIGN.md section 17 (smooth_wide_auto, smooth_wide_launch.hpp): no cell is on today.
+constexpr int64_t SMOOTH_WIDE_MIN_TOTAL = 32768;
+
 // ---- wide_api.hip (9..64 states) ----
 int wide_alloc(bhmm_ctx *c);
 int wide_model(bhmm_ctx *c, int kind, const double *A, const double *pi, const double *par0, const double *par1,

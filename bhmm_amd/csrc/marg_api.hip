@@ -9,7 +9,15 @@
 // Warm-up from the forgetting probe or the option marg_W.  Boundaries that do not verify: counted in
 // marg_fallbacks, the call runs again with twice the warm-up, and if they fail again it takes the generic path.
 //
-// Everything else (9 states and more, explicit pobs; marg_path 0): bhmm_estep with BHMM_FLAG_STORE_GAMMA
+// 9 to 64 states, gaussian or discrete (the time-segmented path, marg_path 2; smooth_wide.hip):
+// k_filter_wide leaves the filtered rows of a range of segments in a workspace of at most smooth_ws_mb,
+// k_smooth_wide_bwd walks the same segments back and writes the rows or their projection (summed by the DPP tree of
+// wgroup_sum, not in ascending state order); both directions are checked, the same protocol.  A segment of
+// probability zero or a NaN observation: the generic path answers.  Taken when the option smooth_wide is 1, or -1
+// (the default) where smooth_wide_auto allows it and the set has at least SMOOTH_WIDE_MIN_TOTAL steps.  It touches
+// c->smooth.* alone and writes to c->marg.out or the caller's device buffer.
+//
+// Everything else (9 states and more unless the path above is taken, explicit pobs; marg_path 0): bhmm_estep with BHMM_FLAG_STORE_GAMMA
 // through its own entry point and protocol, then k_marg_rows_rm / k_marg_rows_ci over the stored rows.  That IS
 // an E-step for the context's state (statistics, carried boundaries, timers, stored gamma), exactly like a
 // caller's own.
@@ -31,6 +39,7 @@
 #include "marg_kernels.hpp"
 #include "model_check.hpp"
 #include "post_host.hpp"
+#include "smooth_wide_launch.hpp"
 
 namespace bhmm {
 namespace {
@@ -239,9 +248,22 @@ int bhmm_posterior_marginals(bhmm_ctx *c, const double *A, const double *pi, con
     }
     const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
     const bool fused = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;
-    c->last.marg_path = fused ? 1 : 0;
+    const int form = Q > 0 ? SMOOTH_FORM_PROJ : SMOOTH_FORM_ROWS;
+    const bool segs = smooth_wide_takes(c, form);
+    c->last.marg_path = fused ? 1 : (segs ? 2 : 0);
+    c->last.smooth_segments = 0;
     bool verified = false;
-    if (fused) {
+    if (segs) {
+        SmoothWideOut so;
+        so.form = form;
+        so.out = o.dev;
+        so.narrow = o.f32;
+        so.conf = nullptr;
+        so.V = o.V;
+        so.Q = Q;
+        if ((rc = smooth_wide_run(c, A, pi, par0, par1, so, &c->last.marg_fallbacks, &verified)))
+            return rc;
+    } else if (fused) {
         switch (c->n) {
         case 1:
             rc = run_n<1>(c, A, pi, par0, par1, o, &verified);

@@ -216,6 +216,40 @@ inline void plan_pass(const std::vector<int64_t> &offsets, int K, int64_t seglen
         p.ntraj += offsets[k + 1] > offsets[k];
 }
 
+// ---- ranges of segments for a budgeted workspace (the posterior calls at 9..64 states, smooth_wide.hip) ----
+// The filtered rows of a segment live in a workspace of `row_bytes` per step between the forward and the backward
+// launch.  smooth_ranges cuts the plan's segments (lengths `len`, in plan order) into ranges [s0, s1) of consecutive
+// whole segments whose steps fit `budget` bytes (0: unbounded, one range).  A range starts at a multiple of `group`
+// (the segments of one wavefront, 64 / np) and holds whole groups -- so the workgroups of a range are those of the
+// whole launch -- and at least one, however small the budget; only the last range may end on a partial group.
+struct SegRange {
+    int s0 = 0, s1 = 0;
+    int64_t steps = 0;
+};
+inline void smooth_ranges(const std::vector<int32_t> &len, int group, int64_t row_bytes, int64_t budget,
+                          std::vector<SegRange> &out)
+{
+    out.clear();
+    const int nseg = (int)len.size();
+    int s = 0;
+    while (s < nseg) {
+        SegRange r;
+        r.s0 = s;
+        while (s < nseg) {
+            const int e = std::min(nseg, s + group);
+            int64_t add = 0;
+            for (int q = s; q < e; ++q)
+                add += len[q];
+            if (budget > 0 && s > r.s0 && (r.steps + add) * row_bytes > budget)
+                break;
+            r.steps += add;
+            s = e;
+        }
+        r.s1 = s;
+        out.push_back(r);
+    }
+}
+
 // ---- the forgetting probe (k_forget_probe up to 8 states, k_wide_probe at 9..64) ----
 // It runs two differently started chains over Wmax steps from P sample positions and leaves, per direction and
 // step, the largest deviation between them: curve[w] forward, curve[Wmax + w] backward.

@@ -10,7 +10,14 @@
 // option post_W.  Boundaries that do not verify: counted in post_fallbacks, the call runs again with twice
 // the warm-up, and if they fail again it takes the generic path.
 //
-// Everything else (9 states and more, explicit pobs; post_path 0): bhmm_estep with BHMM_FLAG_STORE_GAMMA
+// 9 to 64 states, gaussian or discrete (the time-segmented path, post_path 2; smooth_wide.hip):
+// k_filter_wide leaves the filtered rows of a range of segments in a workspace of at most smooth_ws_mb,
+// k_smooth_wide_bwd walks the same segments back and decodes; both directions are checked, the same protocol.  A
+// segment of probability zero or a NaN observation: the generic path answers.  Taken when the option smooth_wide is
+// 1, or -1 (the default) where smooth_wide_auto allows it and the set has at least SMOOTH_WIDE_MIN_TOTAL steps.  It
+// touches c->smooth.* alone and delivers through c->post.path / conf.
+//
+// Everything else (9 states and more unless the path above is taken, explicit pobs; post_path 0): bhmm_estep with BHMM_FLAG_STORE_GAMMA
 // through its own entry point and protocol, then k_post_gamma_rm / k_post_gamma_ci over the stored rows.
 // That IS an E-step for the context's state (statistics, carried boundaries, timers, stored gamma), exactly
 // like a caller's own.
@@ -32,6 +39,7 @@
 #include "model_check.hpp"
 #include "post_host.hpp"
 #include "post_kernels.hpp"
+#include "smooth_wide_launch.hpp"
 
 namespace bhmm {
 namespace {
@@ -196,9 +204,22 @@ int bhmm_posterior_decode(bhmm_ctx *c, const double *A, const double *pi, const 
         return rc;
     const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
     const bool fused = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;
-    c->last.post_path = fused ? 1 : 0;
+    const int form = conf ? SMOOTH_FORM_DECODE_CONF : SMOOTH_FORM_DECODE;
+    const bool segs = smooth_wide_takes(c, form);
+    c->last.post_path = fused ? 1 : (segs ? 2 : 0);
+    c->last.smooth_segments = 0;
     bool verified = false;
-    if (fused) {
+    if (segs) {
+        SmoothWideOut o;
+        o.form = form;
+        o.out = b.path.p;
+        o.narrow = path_u8 != 0;
+        o.conf = conf ? b.conf.p : nullptr;
+        o.V = nullptr;
+        o.Q = 0;
+        if ((rc = smooth_wide_run(c, A, pi, par0, par1, o, &c->last.post_fallbacks, &verified)))
+            return rc;
+    } else if (fused) {
         switch (c->n) {
         case 1:
             rc = run_n<1>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);

@@ -309,8 +309,13 @@ class Engine(object):
         array of sum(T_k) elements of that path dtype which receives the concatenated paths (the views
         then point into it).  Up to 8 states (gaussian, discrete) one fused kernel decodes without storing
         gamma and leaves the state of E-step, Viterbi, sampling and scoring calls untouched
-        (get_option("post_path") == 1; options post_W, post_ws_mb, read-only post_fallbacks); 9 states
-        and more and explicit pobs run an E-step that stores gamma and count as one (post_path 0)."""
+        (get_option("post_path") == 1; options post_W, post_ws_mb, read-only post_fallbacks).  9 to 64
+        states (gaussian, discrete) can run over time segments instead -- k_filter_wide forward,
+        k_smooth_wide_bwd backward, a workspace of at most smooth_ws_mb MiB, no gamma stored, no other
+        call's state touched (post_path 2): set_option("smooth_wide", 1); the default -1 takes it only
+        where it was measured faster than the E-step route (no class: it wins at 128 x 1e5 steps, loses at 128 x 1e4, so -1 acts as 0); options smooth_seglen, smooth_W, smooth_ws_mb, read-only smooth_segments and
+        smooth_wide_min_total.  Everything else (9 states and more otherwise, explicit pobs) runs an
+        E-step that stores gamma and counts as one (post_path 0)."""
         if self.kind is None:
             raise ValueError("no observations loaded")
         n = self.nstates
@@ -347,8 +352,11 @@ class Engine(object):
         estep_launch takes stats_dev; then None is returned).  Rows left on the device are complete in the
         order of the engine's stream (sync()).  Up to 8 states (gaussian, discrete) one fused kernel leaves
         the state of every other call untouched (get_option("marg_path") == 1; options marg_W, marg_ws_mb,
-        read-only marg_fallbacks); 9 states and more and explicit pobs run an E-step that stores gamma and
-        count as one (marg_path 0)."""
+        read-only marg_fallbacks).  9 to 64 states (gaussian, discrete) can run over time segments instead
+        (marg_path 2, as posterior_decode: set_option("smooth_wide", 1); the default -1 takes it only
+        where it was measured faster at every size, no class); there a projection is summed over the states by a fixed tree over the lanes, not in
+        ascending order.  Everything else (9 states and more otherwise, explicit pobs) runs an E-step that
+        stores gamma and counts as one (marg_path 0)."""
         self._check_model(A, pi, par0, par1)
         n = self.nstates
         dtype = np.dtype(dtype)
