@@ -1542,6 +1542,10 @@ int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
         if (value != 0.0 && value != 1.0 && value != -1.0)
             return invalid_arg("smooth_wide must be -1, 0 or 1");
         c->opt.smooth_wide = (int)value;
+    } else if (n == "smooth_tile") { // ... 65..128 states, the matrix-core path: 0 never, 1 always when eligible, -1 automatic
+        if (value != -1 && value != 0 && value != 1)
+            return invalid_arg("smooth_tile must be -1, 0 or 1");
+        c->opt.smooth_tile = (int)value;
     } else if (n == "smooth_seglen") { // ... segment length of its plan from the next call on (0: automatic)
         if (!(value >= 0 && value <= (1 << 30)))
             return invalid_arg("smooth_seglen outside [0, 2^30]");
@@ -1707,6 +1711,10 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->last.filter_redone;
     else if (n == "smooth_wide")
         *value = c->opt.smooth_wide;
+    else if (n == "smooth_tile")
+        *value = c->opt.smooth_tile;
+    else if (n == "smooth_tile_min_total") // ... steps below which smooth_tile = -1 never takes the matrix-core path (65..128 states)
+        *value = (double)SMOOTH_TILE_MIN_TOTAL;
     else if (n == "smooth_seglen")
         *value = c->opt.smooth_seglen;
     else if (n == "smooth_W")

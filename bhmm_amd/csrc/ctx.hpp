@@ -133,9 +133,12 @@ struct bhmm_ctx {
         int smooth_wide = -1;            // bhmm_posterior_decode / bhmm_posterior_marginals, 9..64 states: the time-segmented
                                          // path (k_filter_wide + k_smooth_wide_bwd): 0 never, 1 always when eligible, -1
                                          // automatic (smooth_wide_auto, smooth_wide_launch.hpp; option smooth_wide)
-        int smooth_seglen = 0;           // ... segment length of its plan (option smooth_seglen; 0: automatic)
+        int smooth_tile = -1;            // ... 65..128 states, the matrix-core path (k_filter_tile + k_smooth_tile_bwd): 0 never,
+                                         // 1 always when eligible, -1 automatic (smooth_tile_auto, smooth_tile_api.hpp; option
+                                         // smooth_tile)
+        int smooth_seglen = 0;           // ... both paths: segment length of the plan (option smooth_seglen; 0: automatic)
         int smooth_W = 0;                // ... warm-up fixed by the caller (option smooth_W; 0: measured)
-        int smooth_ws_mb = 8192;         // ... budget of its alpha-row workspace in MiB (option smooth_ws_mb; 0: unbounded)
+        int smooth_ws_mb = 8192;         // ... budget of the alpha-row workspace in MiB (option smooth_ws_mb; 0: unbounded)
     } opt;
 
     // ---- loaded problem ----
@@ -223,6 +226,13 @@ struct bhmm_ctx {
         int smooth_nseg = 0;             // segments of the plan (0: not made yet)
         int smooth_ntraj = 0;            // ... trajectories with at least one step (nseg == ntraj: no boundary)
         int smooth_seglen_opt = 0;       // ... opt.smooth_seglen it was made for
+        // posterior calls, 65..128 states: the segment plan of the matrix-core smoothing pass (tables in smooth_tile.seg,
+        // the ranges of the budgeted workspace and their tile tables in smooth_tile.ranges / seg.tile_seg / tile_segb),
+        // made the same way; none of the plans above
+        int smooth_tile_nseg = 0;        // segments of the plan (0: not made yet)
+        int smooth_tile_ntraj = 0;       // ... trajectories with at least one step (nseg == ntraj: no boundary)
+        int smooth_tile_seglen_opt = 0;  // ... opt.smooth_seglen it was made for
+        int smooth_tile_ws_mb_opt = 0;   // ... opt.smooth_ws_mb its ranges were cut for
     } ds;
 
     // ---- counters and diagnostics of the last calls (bhmm_ctx_get_option) ----
@@ -256,11 +266,13 @@ struct bhmm_ctx {
         int score_segments = 0;          // ... segments of the score plan it ran on (0: no such plan)
         int score_W_max = 0;             // ... longest warm-up of its first pass at 9..128 states (0: no boundary, other paths)
         int post_fallbacks = 0;          // bhmm_posterior_decode: calls whose boundaries did not verify at the first warm-up
-        int post_path = 0;               // ... first pass of the last call: 2 time segments (k_smooth_wide_bwd, 9..64 states),
-                                         // 1 fused (k_post_sweep), 0 generic (E-step + gamma rows)
+        int post_path = 0;               // ... first pass of the last call: 3 matrix cores (k_smooth_tile_bwd, 65..128 states),
+                                         // 2 time segments (k_smooth_wide_bwd, 9..64 states), 1 fused (k_post_sweep), 0 generic
+                                         // (E-step + gamma rows)
         int marg_fallbacks = 0;          // bhmm_posterior_marginals: calls whose boundaries did not verify at the first warm-up
-        int marg_path = 0;               // ... first pass of the last call: 2 time segments (k_smooth_wide_bwd, 9..64 states),
-                                         // 1 fused (k_marg_sweep), 0 generic (E-step + gamma rows)
+        int marg_path = 0;               // ... first pass of the last call: 3 matrix cores (k_smooth_tile_bwd, 65..128 states),
+                                         // 2 time segments (k_smooth_wide_bwd, 9..64 states), 1 fused (k_marg_sweep), 0 generic
+                                         // (E-step + gamma rows)
         int smooth_segments = 0;         // segments of the smoothing plan the last posterior call ran on (0: another path)
         int filter_fallbacks = 0;        // bhmm_filter: calls whose boundaries did not verify at the first warm-up
         int filter_path = 0;             // ... first pass of the last call: 3 matrix cores (k_filter_tile, 65..128 states),
@@ -433,6 +445,22 @@ struct bhmm_ctx {
         std::vector<int32_t> seg_len;
         std::vector<int64_t> seg_g0;
     } smooth;
+    // the matrix-core path of the two posterior calls at 65..128 states (smooth_tile.hip): its own buffers -- the
+    // model's table entry and parameter block (B^T for discrete), the tables of the plan ds.smooth_tile_nseg counts
+    // (seg; seg.tile_seg holds the forward tiles of every range, tile_segb the backward ones) with the ranges of the
+    // budgeted workspace and every segment's first global step on the host, the filtered rows of one range (ws),
+    // entry / exit vectors of both directions, the range flags of both directions (fflag: k_filter_tile's, dead
+    // segments included; bflag: k_smooth_tile_bwd's) and the words of a pass (SMT_*); nothing else reads them
+    struct SmoothTileBufs {
+        bhmm::DevBuf<char> model;
+        bhmm::DevBuf<double> wpar, ws, aentry, aexit, bexit, bentry;
+        bhmm::DevBuf<uint8_t> fflag, bflag;
+        bhmm::DevBuf<unsigned int> words;
+        bhmm::SegTables seg;
+        bhmm::DevBuf<int32_t> tile_segb;
+        std::vector<int32_t> r_s0, r_s1, r_f0, r_nf, r_b0, r_nb; // per range (plan::TileRange)
+        std::vector<int64_t> r_steps, r_g0;                       // ... its steps and its first global step
+    } smooth_tile;
 
     // ---- pinned host buffers ----
     unsigned int *h_specres = nullptr; // pinned

@@ -90,6 +90,13 @@ constexpr int64_t FILTER_TILE_MIN_TOTAL = 32768;
 // measurements of DESIGN.md section 17 (smooth_wide_auto, smooth_wide_launch.hpp): no cell is on today.
 constexpr int64_t SMOOTH_WIDE_MIN_TOTAL = 32768;
 
+// ---- smooth_tile.hip (bhmm_posterior_decode / bhmm_posterior_marginals at 65..128 states) ----
+// Steps of an observation set below which the option smooth_tile = -1 never takes the matrix-core path (read-only
+// option smooth_tile_min_total): a power of two, not below 32768 -- the existing tests pin the generic path for a
+// default call at 100 states on 23734 steps.  Above it the automatic rule is per call form, from the measurements
+// of DESIGN.md section 18 (smooth_tile_auto, smooth_tile_api.hpp).
+constexpr int64_t SMOOTH_TILE_MIN_TOTAL = 32768;
+
 // ---- wide_api.hip (9..64 states) ----
 int wide_alloc(bhmm_ctx *c);
 int wide_model(bhmm_ctx *c, int kind, const double *A, const double *pi, const double *par0, const double *par1,

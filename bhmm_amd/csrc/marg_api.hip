@@ -17,7 +17,15 @@
 // (the default) where smooth_wide_auto allows it and the set has at least SMOOTH_WIDE_MIN_TOTAL steps.  It touches
 // c->smooth.* alone and writes to c->marg.out or the caller's device buffer.
 //
-// Everything else (9 states and more unless the path above is taken, explicit pobs; marg_path 0): bhmm_estep with BHMM_FLAG_STORE_GAMMA
+// 65 to 128 states, gaussian or discrete (the matrix-core path, marg_path 3; smooth_tile.hip):
+// k_filter_tile forward into a workspace of at most smooth_ws_mb, k_smooth_tile_bwd backward on the matrix cores,
+// which writes the rows or their projection (summed by the tree of row16_sum, not in ascending state order); both
+// directions are checked, the same protocol.  A segment either kernel flags: the generic path answers for the whole
+// call.  Taken when the option smooth_tile is 1, or -1 (the default) where smooth_tile_auto allows it and the set
+// has at least SMOOTH_TILE_MIN_TOTAL steps.  It touches c->smooth_tile.* alone and writes to c->marg.out or the
+// caller's device buffer.
+//
+// Everything else (9 states and more unless a path above is taken, explicit pobs; marg_path 0): bhmm_estep with BHMM_FLAG_STORE_GAMMA
 // through its own entry point and protocol, then k_marg_rows_rm / k_marg_rows_ci over the stored rows.  That IS
 // an E-step for the context's state (statistics, carried boundaries, timers, stored gamma), exactly like a
 // caller's own.
@@ -39,6 +47,7 @@
 #include "marg_kernels.hpp"
 #include "model_check.hpp"
 #include "post_host.hpp"
+#include "smooth_tile_api.hpp"
 #include "smooth_wide_launch.hpp"
 
 namespace bhmm {
@@ -249,11 +258,11 @@ int bhmm_posterior_marginals(bhmm_ctx *c, const double *A, const double *pi, con
     const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
     const bool fused = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;
     const int form = Q > 0 ? SMOOTH_FORM_PROJ : SMOOTH_FORM_ROWS;
-    const bool segs = smooth_wide_takes(c, form);
-    c->last.marg_path = fused ? 1 : (segs ? 2 : 0);
+    const bool segs = smooth_wide_takes(c, form), tile = smooth_tile_takes(c, form);
+    c->last.marg_path = fused ? 1 : (segs ? 2 : (tile ? 3 : 0));
     c->last.smooth_segments = 0;
     bool verified = false;
-    if (segs) {
+    if (segs || tile) {
         SmoothWideOut so;
         so.form = form;
         so.out = o.dev;
@@ -261,7 +270,8 @@ int bhmm_posterior_marginals(bhmm_ctx *c, const double *A, const double *pi, con
         so.conf = nullptr;
         so.V = o.V;
         so.Q = Q;
-        if ((rc = smooth_wide_run(c, A, pi, par0, par1, so, &c->last.marg_fallbacks, &verified)))
+        if ((rc = tile ? smooth_tile_run(c, A, pi, par0, par1, so, &c->last.marg_fallbacks, &verified)
+                       : smooth_wide_run(c, A, pi, par0, par1, so, &c->last.marg_fallbacks, &verified)))
             return rc;
     } else if (fused) {
         switch (c->n) {

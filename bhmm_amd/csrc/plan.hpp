@@ -1,6 +1,7 @@
 // plan.hpp -- host-side planning of the time decomposition: chunk tables of the N <= 8 family
 // (bhmm_amd.hip), segment tables of the 9..64-state family (wide_api.hip), the plan of a forward-only pass
-// (bhmm_score, bhmm_filter: plan_pass, uploaded by seg_host.hpp), and the forgetting probe every family
+// (bhmm_score, bhmm_filter: plan_pass, uploaded by seg_host.hpp), the ranges of a budgeted workspace of the posterior
+// calls (smooth_ranges, smooth_tile_ranges), and the forgetting probe every family
 // warms up by: where it samples (probe_starts) and how its curve is read (curve_last, warmup_of,
 // warmup_wide_of).  Pure C++ (no HIP), so
 // the same code runs under -fsanitize=address,undefined in the CPU sanitizer build
@@ -247,6 +248,49 @@ inline void smooth_ranges(const std::vector<int32_t> &len, int group, int64_t ro
         }
         r.s1 = s;
         out.push_back(r);
+    }
+}
+
+// ---- the same at 65..128 states (smooth_tile.hip): ranges with tile tables of their own ----
+// A tile's sixteen segments are picked by length, not by position, and the forward and the backward tile tables
+// differ (plan_tiles puts different segments in the edge class), so the cut comes first: smooth_ranges with group 1
+// over the plan's segments in plan order (consecutive global steps), whole segments that fit `budget` bytes, at least
+// one per range.  Then every range gets a forward and a backward tile table over its segments alone (plan_tiles on
+// the range's sub-plan).  The tables are concatenated in tile_f / tile_b and name segments of the WHOLE plan; a
+// range's tiles are [f0, f0 + nf) and [b0, b0 + nb).  Budget 0 or one that fits: one range, the whole plan.
+struct TileRange {
+    int s0 = 0, s1 = 0;
+    int64_t steps = 0;
+    int f0 = 0, nf = 0, b0 = 0, nb = 0;
+};
+inline void smooth_tile_ranges(const SegPlan &s, const std::vector<int64_t> &offsets, int64_t row_bytes, int64_t budget,
+                               std::vector<TileRange> &out, std::vector<int32_t> &tile_f, std::vector<int32_t> &tile_b)
+{
+    out.clear();
+    tile_f.clear();
+    tile_b.clear();
+    std::vector<SegRange> cut;
+    smooth_ranges(s.len, 1, row_bytes, budget, cut);
+    for (const SegRange &r : cut) {
+        SegPlan sub;
+        sub.traj.assign(s.traj.begin() + r.s0, s.traj.begin() + r.s1);
+        sub.len.assign(s.len.begin() + r.s0, s.len.begin() + r.s1);
+        sub.t0.assign(s.t0.begin() + r.s0, s.t0.begin() + r.s1);
+        TileRange t;
+        t.s0 = r.s0;
+        t.s1 = r.s1;
+        t.steps = r.steps;
+        std::vector<int32_t> tiles;
+        for (int dir = 0; dir < 2; ++dir) {
+            std::vector<int32_t> &all = dir ? tile_b : tile_f;
+            plan_tiles(sub, offsets, dir != 0, tiles);
+            for (int32_t &e : tiles)
+                e = e < 0 ? -1 : e + r.s0;
+            (dir ? t.b0 : t.f0) = (int)(all.size() / 16);
+            (dir ? t.nb : t.nf) = (int)(tiles.size() / 16);
+            all.insert(all.end(), tiles.begin(), tiles.end());
+        }
+        out.push_back(t);
     }
 }
 

@@ -17,7 +17,15 @@
 // 1, or -1 (the default) where smooth_wide_auto allows it and the set has at least SMOOTH_WIDE_MIN_TOTAL steps.  It
 // touches c->smooth.* alone and delivers through c->post.path / conf.
 //
-// Everything else (9 states and more unless the path above is taken, explicit pobs; post_path 0): bhmm_estep with BHMM_FLAG_STORE_GAMMA
+// 65 to 128 states, gaussian or discrete (the matrix-core path, post_path 3; smooth_tile.hip):
+// k_filter_tile leaves the filtered rows of a range of segments in a workspace of at most smooth_ws_mb,
+// k_smooth_tile_bwd walks the same segments back on the matrix cores and decodes; both directions are checked, the
+// same protocol.  A segment either kernel flags (probability zero, an outlier, a NaN observation): the generic path
+// answers for the whole call.  Taken when the option smooth_tile is 1, or -1 (the default) where smooth_tile_auto
+// allows it and the set has at least SMOOTH_TILE_MIN_TOTAL steps.  It touches c->smooth_tile.* alone and delivers
+// through c->post.path / conf.
+//
+// Everything else (9 states and more unless a path above is taken, explicit pobs; post_path 0): bhmm_estep with BHMM_FLAG_STORE_GAMMA
 // through its own entry point and protocol, then k_post_gamma_rm / k_post_gamma_ci over the stored rows.
 // That IS an E-step for the context's state (statistics, carried boundaries, timers, stored gamma), exactly
 // like a caller's own.
@@ -39,6 +47,7 @@
 #include "model_check.hpp"
 #include "post_host.hpp"
 #include "post_kernels.hpp"
+#include "smooth_tile_api.hpp"
 #include "smooth_wide_launch.hpp"
 
 namespace bhmm {
@@ -205,11 +214,11 @@ int bhmm_posterior_decode(bhmm_ctx *c, const double *A, const double *pi, const 
     const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
     const bool fused = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;
     const int form = conf ? SMOOTH_FORM_DECODE_CONF : SMOOTH_FORM_DECODE;
-    const bool segs = smooth_wide_takes(c, form);
-    c->last.post_path = fused ? 1 : (segs ? 2 : 0);
+    const bool segs = smooth_wide_takes(c, form), tile = smooth_tile_takes(c, form);
+    c->last.post_path = fused ? 1 : (segs ? 2 : (tile ? 3 : 0));
     c->last.smooth_segments = 0;
     bool verified = false;
-    if (segs) {
+    if (segs || tile) {
         SmoothWideOut o;
         o.form = form;
         o.out = b.path.p;
@@ -217,7 +226,8 @@ int bhmm_posterior_decode(bhmm_ctx *c, const double *A, const double *pi, const 
         o.conf = conf ? b.conf.p : nullptr;
         o.V = nullptr;
         o.Q = 0;
-        if ((rc = smooth_wide_run(c, A, pi, par0, par1, o, &c->last.post_fallbacks, &verified)))
+        if ((rc = tile ? smooth_tile_run(c, A, pi, par0, par1, o, &c->last.post_fallbacks, &verified)
+                       : smooth_wide_run(c, A, pi, par0, par1, o, &c->last.post_fallbacks, &verified)))
             return rc;
     } else if (fused) {
         switch (c->n) {

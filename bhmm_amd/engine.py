@@ -314,7 +314,13 @@ class Engine(object):
         k_smooth_wide_bwd backward, a workspace of at most smooth_ws_mb MiB, no gamma stored, no other
         call's state touched (post_path 2): set_option("smooth_wide", 1); the default -1 takes it only
         where it was measured faster than the E-step route (no class: it wins at 128 x 1e5 steps, loses at 128 x 1e4, so -1 acts as 0); options smooth_seglen, smooth_W, smooth_ws_mb, read-only smooth_segments and
-        smooth_wide_min_total.  Everything else (9 states and more otherwise, explicit pobs) runs an
+        smooth_wide_min_total.  65 to 128 states (gaussian, discrete) can run on the fp64 matrix cores
+        -- k_filter_tile forward, k_smooth_tile_bwd backward, the same workspace budget, no gamma stored,
+        no other call's state touched (post_path 3): set_option("smooth_tile", 1); the default -1 takes it
+        only for the call forms measured faster than the E-step route in every shape (DESIGN.md section
+        18); one segment outside the kernels' number range (probability zero, an outlier, a NaN
+        observation) sends the whole call to the E-step route; the same options, read-only
+        smooth_tile_min_total.  Everything else (9 states and more otherwise, explicit pobs) runs an
         E-step that stores gamma and counts as one (post_path 0)."""
         if self.kind is None:
             raise ValueError("no observations loaded")
@@ -355,7 +361,9 @@ class Engine(object):
         read-only marg_fallbacks).  9 to 64 states (gaussian, discrete) can run over time segments instead
         (marg_path 2, as posterior_decode: set_option("smooth_wide", 1); the default -1 takes it only
         where it was measured faster at every size, no class); there a projection is summed over the states by a fixed tree over the lanes, not in
-        ascending order.  Everything else (9 states and more otherwise, explicit pobs) runs an E-step that
+        ascending order.  65 to 128 states (gaussian, discrete) can run on the fp64 matrix cores (marg_path 3,
+        as posterior_decode: set_option("smooth_tile", 1)); a projection is summed by a fixed tree over
+        sixteen lanes there.  Everything else (9 states and more otherwise, explicit pobs) runs an E-step that
         stores gamma and counts as one (marg_path 0)."""
         self._check_model(A, pi, par0, par1)
         n = self.nstates

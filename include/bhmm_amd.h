@@ -189,7 +189,7 @@ int bhmm_score(bhmm_ctx *ctx, int nmodels, const double *A, const double *pi,
    post_ws_mb (budget of the alpha-row workspace in MiB, default 8192, 0 = unbounded: the call loops over
    ranges of chunk groups, the result does not depend on it); read-only post_fallbacks (calls whose
    boundaries did not verify at the first warm-up: they run again with twice the warm-up, then take the
-   generic path) and post_path (first pass of the last call: 2 time segments, 1 fused, 0 generic).
+   generic path) and post_path (first pass of the last call: 3 matrix cores, 2 time segments, 1 fused, 0 generic).
    9 to 64 states (gaussian, discrete), the time-segmented path (post_path 2): k_filter_wide leaves the filtered
    rows of the segments of a plan of its own in a workspace, k_smooth_wide_bwd walks the same segments back and
    decodes; warm-up boundaries of both directions verified, the same retry protocol (post_fallbacks).  No gamma
@@ -201,7 +201,17 @@ int bhmm_score(bhmm_ctx *ctx, int nmodels, const double *A, const double *pi,
    steps, 0 = measured), smooth_ws_mb (budget of the workspace in MiB, default 8192, 0 = unbounded: the call
    loops over ranges of whole segments, the result does not depend on it); read-only smooth_segments (segments of
    the plan the last call ran on; 0: another path) and smooth_wide_min_total.
-   Generic path (9 states and more unless the path above is taken, explicit pobs): a bhmm_estep with BHMM_FLAG_STORE_GAMMA followed by a
+   65 to 128 states (gaussian, discrete), the matrix-core path (post_path 3): k_filter_tile leaves the filtered rows
+   of a range of segments in the workspace, k_smooth_tile_bwd walks the same segments back on the fp64 matrix cores
+   (sixteen segments per workgroup) and decodes; boundaries of both directions verified, the same retry protocol
+   (post_fallbacks); nothing of another call's state is read or written.  A segment either kernel flags (probability
+   zero, an outlier, a NaN observation) sends the whole call to the generic path (nothing counted).  Options:
+   smooth_tile (1: always when eligible, 0: never, -1, the default: automatic -- only from smooth_tile_min_total
+   steps on and only for the call forms measured faster than the generic path in every shape, DESIGN.md section
+   18), smooth_seglen, smooth_W (rounded up to a multiple of four) and smooth_ws_mb as above -- here the ranges of
+   whole segments also decide which segments share a tile; results are bitwise reproducible at a fixed budget,
+   across budgets that is not promised; read-only smooth_segments and smooth_tile_min_total.
+   Generic path (9 states and more unless a path above is taken, explicit pobs): a bhmm_estep with BHMM_FLAG_STORE_GAMMA followed by a
    kernel over the stored rows.  It counts as an E-step for the context (last statistics, carried
    boundaries, timers, stored gamma) exactly like the caller's own, needs total * N * 8 bytes for gamma
    (BHMM_ERR_NO_MEM if they are not there) and returns BHMM_ERR_NONFINITE where bhmm_estep_fetch would. */
@@ -229,8 +239,8 @@ int bhmm_posterior_decode(bhmm_ctx *ctx, const double *A, const double *pi, cons
    gamma row is kept beyond out.  Options: marg_W (warm-up in steps, 0 = measured), marg_ws_mb (budget of the
    alpha-row workspace in MiB, default 8192, 0 = unbounded; the result does not depend on it); read-only
    marg_fallbacks (calls whose boundaries did not verify at the first warm-up: they run again with twice the
-   warm-up, then take the generic path) and marg_path (first pass of the last call: 2 time segments, 1 fused,
-   0 generic).
+   warm-up, then take the generic path) and marg_path (first pass of the last call: 3 matrix cores, 2 time
+   segments, 1 fused, 0 generic).
    9 to 64 states (gaussian, discrete), the time-segmented path (marg_path 2): k_filter_wide forward and
    k_smooth_wide_bwd backward over the segments of a plan of its own, as for bhmm_posterior_decode, with the
    normalised row or its projection as last stage; a projection is summed over the states by a fixed tree over
@@ -240,7 +250,13 @@ int bhmm_posterior_decode(bhmm_ctx *ctx, const double *A, const double *pi, cons
    (1: always when eligible, 0: never, -1, the default: automatic -- only from smooth_wide_min_total steps on and only for the lane-group classes and call forms
    measured faster than the generic path, which is none: it wins at 128 x 1e5 steps but loses at 128 x 1e4, DESIGN.md section 17, so -1 behaves like 0), smooth_seglen, smooth_W,
    smooth_ws_mb (as for bhmm_posterior_decode); read-only smooth_segments and smooth_wide_min_total.
-   Generic path (9 states and more unless the path above is taken, explicit pobs): a bhmm_estep with BHMM_FLAG_STORE_GAMMA followed by one
+   65 to 128 states (gaussian, discrete), the matrix-core path (marg_path 3): k_filter_tile forward and
+   k_smooth_tile_bwd backward, as for bhmm_posterior_decode, with the normalised row or its projection as last stage;
+   a projection is summed over the states by a fixed tree over sixteen lanes, NOT in ascending order (the same bound
+   holds).  Verified in both directions, the same retry protocol (marg_fallbacks); a flagged segment: the generic
+   path answers for the whole call.  Options: smooth_tile, smooth_seglen, smooth_W, smooth_ws_mb (as for
+   bhmm_posterior_decode); read-only smooth_segments and smooth_tile_min_total.
+   Generic path (9 states and more unless a path above is taken, explicit pobs): a bhmm_estep with BHMM_FLAG_STORE_GAMMA followed by one
    kernel over the stored rows.  It counts as an E-step for the context (last statistics, carried boundaries,
    timers, stored gamma) exactly like the caller's own, needs total * N * 8 bytes for gamma besides the staged
    result and returns BHMM_ERR_NONFINITE where bhmm_estep_fetch would. */
