@@ -34,6 +34,7 @@ MARG_F32 = 1           # bhmm_posterior_marginals: rows of float
 MARG_DEVICE = 2        # ... out is a device pointer
 FILT_F32 = 1           # bhmm_filter: both outputs of float
 FILT_DEVICE = 2        # ... both outputs are device pointers
+DWELL_COLS = 5         # bhmm_path_runs / bhmm_decode_runs: columns of the dwell table (BHMM_DWELL_COLS)
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -88,6 +89,11 @@ SIGNATURES = {
                                           c_double_p, c_int32_p]),
     "bhmm_viterbi_batch_u8": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,
                                              c_double_p, c_void_p, ctypes.c_int]),
+    "bhmm_path_runs": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, c_int64_p, c_int64_p,
+                                      c_int64_p]),
+    "bhmm_decode_runs": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int,
+                                        c_int64_p, c_int64_p, c_int64_p]),
+    "bhmm_runs_fetch": (ctypes.c_int, [c_void_p, c_int64_p, c_int64_p, c_int32_p]),
     "bhmm_ctx_path_stats_size": (ctypes.c_int, [c_void_p]),
     "bhmm_ctx_set_stream_offsets": (ctypes.c_int, [c_void_p, c_int64_p]),
     "bhmm_sample_paths_dev": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,

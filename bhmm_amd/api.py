@@ -211,6 +211,43 @@ def posterior_decode(observations, model, lag=1, confidence=False, **engine_kwar
         eng.close()
 
 
+def decode_segments(observations, model, lag=1, method='viterbi', stats=False, **engine_kwargs):
+    """Dwell segments of `observations` decoded under one HMM (bhmm_decode_runs): the path of method 'viterbi'
+    (the most probable path) or 'posterior' (the state of largest posterior marginal per step) collapsed on the
+    GPU into runs of equal states -- per run its state, its first step inside the trajectory and its length --
+    without the per-step path crossing the link.  Returns a PathRuns (bhmm_amd.engine): offsets (K + 1), start,
+    length and state concatenated over the trajectories, trajectory(k) for the three views of one; with `stats`
+    also dwell ((nstates, 5): runs, steps, longest run, censored runs, censored steps per state) and jumps
+    ((nstates, nstates) run pairs i -> j).  lag > 1 decodes the lagged views (lag_observations), one trajectory
+    per view.  Up to 256 states.  engine_kwargs: device (default 0)."""
+    from .engine import Engine
+    from .estimators.maximum_likelihood import model_tuple
+    if not isinstance(model, HMM):
+        raise TypeError("model must be an HMM object")
+    if method not in ('viterbi', 'posterior'):
+        raise ValueError("method must be 'viterbi' or 'posterior', not %r" % (method,))
+    if len(observations) == 0:
+        raise ValueError("no observations")
+    output = model.output_model.model_type
+    nstates = model.nstates
+    nsymbols = model.output_model.nsymbols if output == 'discrete' else 0
+    device = engine_kwargs.pop('device', 0)
+    if engine_kwargs:
+        raise TypeError("unexpected keyword arguments: %s" % ", ".join(sorted(engine_kwargs)))
+    if lag > 1:
+        observations = lag_observations(observations, lag)
+    eng = Engine(device)
+    try:
+        if output == 'discrete':
+            obs = [np.asarray(o) for o in observations]
+            eng.set_observations('discrete', obs, nstates, nsymbols=nsymbols)
+        else:
+            eng.set_observations(output, [np.asarray(o, dtype=np.float64) for o in observations], nstates)
+        return eng.decode_runs(*model_tuple(model), method=method, stats=stats)
+    finally:
+        eng.close()
+
+
 def posterior_marginals(observations, model, lag=1, weights=None, dtype=np.float64, **engine_kwargs):
     """Posterior state probabilities of `observations` under one HMM (bhmm_posterior_marginals): per
     trajectory a (T_k, nstates) array of gamma_t(i) -- what the reference's estimator hands out as

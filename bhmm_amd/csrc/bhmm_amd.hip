@@ -13,6 +13,7 @@
 #include "host_common.hpp"
 #include "host_internal.hpp"
 #include "plan.hpp"
+#include "runs_host.hpp"
 #include "seg_host.hpp"
 #include "estep_sweep.hpp"
 
@@ -1727,6 +1728,14 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = (double)SMOOTH_WIDE_MIN_TOTAL;
     else if (n == "score_path") // ... first pass of the last call: 0 serial kernel, 1 chunk kernels (N <= 8), 2 k_score_wide, 3 k_score_tile
         *value = c->last.score_path;
+    else if (n == "runs_tile") // bhmm_path_runs / bhmm_decode_runs: steps of the path per workgroup
+        *value = runs::TILE;
+    else if (n == "runs_lane") // ... per lane
+        *value = runs::LANE;
+    else if (n == "runs_count") // ... runs of the last call on these observations
+        *value = (double)c->ds.runs_count;
+    else if (n == "runs_ms") // ... device time of its count, scan and scatter passes
+        *value = c->last.runs_ms;
     else
         return invalid_arg("unknown option: " + n);
     return BHMM_OK;

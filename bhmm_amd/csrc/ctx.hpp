@@ -233,6 +233,11 @@ struct bhmm_ctx {
         int smooth_tile_ntraj = 0;       // ... trajectories with at least one step (nseg == ntraj: no boundary)
         int smooth_tile_seglen_opt = 0;  // ... opt.smooth_seglen it was made for
         int smooth_tile_ws_mb_opt = 0;   // ... opt.smooth_ws_mb its ranges were cut for
+        // bhmm_path_runs / bhmm_decode_runs (runs_api.hip): the runs of the last call on these observations sit in
+        // runs.start / length / state (bhmm_runs_fetch)
+        bool runs_tiles_ready = false;   // ... runs.tile_traj holds the trajectory of every tile's first step for these offsets
+        bool runs_valid = false;
+        int64_t runs_count = 0;          // ... how many (option runs_count)
     } ds;
 
     // ---- counters and diagnostics of the last calls (bhmm_ctx_get_option) ----
@@ -281,6 +286,7 @@ struct bhmm_ctx {
         int filter_segments = 0;         // ... segments of the filter plan it ran on (0: no such plan)
         int filter_redone = 0;           // ... filter_path 3: trajectories of the last call done again on k_filter_serial
                                          // because a segment left the range of k_filter_tile (option filter_redone)
+        float runs_ms = 0.f;             // bhmm_path_runs / bhmm_decode_runs: device time of count, scan and scatter
     } last;
 
     // ---- not reset by bhmm_ctx_set_observations: they outlive the observation set ----
@@ -461,6 +467,29 @@ struct bhmm_ctx {
         std::vector<int32_t> r_s0, r_s1, r_f0, r_nf, r_b0, r_nb; // per range (plan::TileRange)
         std::vector<int64_t> r_steps, r_g0;                       // ... its steps and its first global step
     } smooth_tile;
+    // bhmm_path_runs / bhmm_decode_runs (runs_api.hip): its own buffers -- the path where the call has to hold it (a
+    // host path staged, the Viterbi path of bhmm_decode_runs), the trajectory of every tile's first step (made once per
+    // observation set, ds.runs_tiles_ready), run count and exclusive offset of every tile, the sums
+    // of the scan's blocks (the last entry: R), the status word, the first run of every trajectory, the runs
+    // (start, length, state: sized from R; valid while ds.runs_valid), the statistics tables [n * 5 | n * n] and
+    // the events of runs_ms (count + scan, scatter + finish); nothing else reads them
+    struct RunsBufs {
+        bhmm::DevBuf<char> path;
+        bhmm::DevBuf<int32_t> tile_traj, tile_cnt, state;
+        bhmm::DevBuf<int64_t> tile_off, blk, run_off, start, length;
+        bhmm::DevBuf<unsigned long long> tables;
+        bhmm::DevBuf<unsigned int> status;
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        RunsBufs() = default;
+        RunsBufs(const RunsBufs &) = delete;
+        RunsBufs &operator=(const RunsBufs &) = delete;
+        ~RunsBufs()
+        {
+            for (hipEvent_t e : ev)
+                if (e)
+                    (void)hipEventDestroy(e);
+        }
+    } runs;
 
     // ---- pinned host buffers ----
     unsigned int *h_specres = nullptr; // pinned

@@ -83,6 +83,14 @@ constexpr int64_t FILTER_WIDE_MIN_TOTAL = 32768;
 // (128 states: 50.0 ms against 2.5 ms there), so this is the floor, not the break-even.
 constexpr int64_t FILTER_TILE_MIN_TOTAL = 32768;
 
+// ---- post_api.hip (bhmm_posterior_decode) ----
+// Everything bhmm_posterior_decode does before its results leave the device: the checks (given: the caller's pointer
+// arguments are there), the path the call takes and its fallbacks; the decoded path is then in c->post.path (one
+// byte per step with path_u8, else int32) and, with want_conf, the confidences in c->post.conf, complete in the
+// order of the context's stream.  bhmm_decode_runs compacts that path instead of delivering it.
+int post_decode_device(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                       bool given, int path_u8, bool want_conf);
+
 // ---- smooth_wide.hip (bhmm_posterior_decode / bhmm_posterior_marginals at 9..64 states) ----
 // Steps of an observation set below which the option smooth_wide = -1 never takes the time-segmented path (read-only
 // option smooth_wide_min_total): a power of two, not below 32768 -- the existing tests pin the generic path for a

@@ -191,16 +191,13 @@ int generic(bhmm_ctx *c, const double *A, const double *pi, const double *par0, 
 }
 
 } // namespace
-} // namespace bhmm
 
-using namespace bhmm;
-
-extern "C" {
-
-int bhmm_posterior_decode(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
-                          void *path, int path_u8, float *conf)
+// decode into c->post.path / conf (host_internal.hpp); bhmm_posterior_decode delivers them, bhmm_decode_runs
+// compacts the path on the device
+int post_decode_device(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                       bool given, int path_u8, bool conf)
 {
-    int rc = enter_model_call(c, A && pi && path, "A / pi / path == NULL", true, par0, par1);
+    int rc = enter_model_call(c, given, "A / pi / path == NULL", true, par0, par1);
     if (rc)
         return rc;
     if (path_u8 && c->n > 256)
@@ -232,34 +229,48 @@ int bhmm_posterior_decode(bhmm_ctx *c, const double *A, const double *pi, const 
     } else if (fused) {
         switch (c->n) {
         case 1:
-            rc = run_n<1>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            rc = run_n<1>(c, A, pi, par0, par1, path_u8, conf, &verified);
             break;
         case 2:
-            rc = run_n<2>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            rc = run_n<2>(c, A, pi, par0, par1, path_u8, conf, &verified);
             break;
         case 3:
-            rc = run_n<3>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            rc = run_n<3>(c, A, pi, par0, par1, path_u8, conf, &verified);
             break;
         case 4:
-            rc = run_n<4>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            rc = run_n<4>(c, A, pi, par0, par1, path_u8, conf, &verified);
             break;
         case 5:
-            rc = run_n<5>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            rc = run_n<5>(c, A, pi, par0, par1, path_u8, conf, &verified);
             break;
         case 6:
-            rc = run_n<6>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            rc = run_n<6>(c, A, pi, par0, par1, path_u8, conf, &verified);
             break;
         case 7:
-            rc = run_n<7>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            rc = run_n<7>(c, A, pi, par0, par1, path_u8, conf, &verified);
             break;
         default:
-            rc = run_n<8>(c, A, pi, par0, par1, path_u8, conf != nullptr, &verified);
+            rc = run_n<8>(c, A, pi, par0, par1, path_u8, conf, &verified);
             break;
         }
         if (rc)
             return rc;
     }
-    if (!verified && (rc = generic(c, A, pi, par0, par1, path_u8, conf != nullptr)))
+    if (!verified && (rc = generic(c, A, pi, par0, par1, path_u8, conf)))
+        return rc;
+    return BHMM_OK;
+}
+
+} // namespace bhmm
+
+using namespace bhmm;
+
+extern "C" {
+
+int bhmm_posterior_decode(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                          void *path, int path_u8, float *conf)
+{
+    if (int rc = post_decode_device(c, A, pi, par0, par1, A && pi && path, path_u8, conf != nullptr))
         return rc;
     return deliver(c, path, path_u8, conf);
 }

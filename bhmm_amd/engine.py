@@ -33,6 +33,47 @@ class EStepResult(object):
             self.symbol_counts = packed[o:o + n * M].reshape(n, M).copy(); o += n * M
 
 
+class PathRuns(object):
+    """Dwell segments (runs) of a decoded path (Engine.path_runs, Engine.decode_runs): a run is a maximal stretch
+    of equal states inside one trajectory.  offsets (K + 1, int64): the runs of trajectory k are
+    offsets[k]:offsets[k + 1] of start (int64, step index inside the trajectory), length (int64) and state (int32),
+    which are concatenated over the trajectories; an empty trajectory has none.  With statistics, dwell is
+    (nstates, 5) int64 -- per state the number of runs, the steps in them, the longest run, the runs that touch the
+    first or the last step of their trajectory (censored) and the steps in those -- and jumps (nstates, nstates)
+    int64 the number of adjacent run pairs i -> j inside one trajectory (zero diagonal); else both are None."""
+
+    DWELL_COLUMNS = ('runs', 'steps', 'longest', 'censored_runs', 'censored_steps')
+
+    def __init__(self, offsets, start, length, state, dwell=None, jumps=None):
+        self.offsets = offsets
+        self.start = start
+        self.length = length
+        self.state = state
+        self.dwell = dwell
+        self.jumps = jumps
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    @property
+    def count(self):
+        """Number of runs."""
+        return int(self.offsets[-1])
+
+    def trajectory(self, k):
+        """(start, length, state) of the runs of trajectory k: three views."""
+        K = len(self.offsets) - 1
+        k = int(k)
+        if not -K <= k < K:
+            raise IndexError("trajectory %d of %d" % (k, K))
+        k %= K
+        a, b = int(self.offsets[k]), int(self.offsets[k + 1])
+        return self.start[a:b], self.length[a:b], self.state[a:b]
+
+
+_METHODS = {'viterbi': 0, 'posterior': 1}
+
+
 _KINDS = {'gaussian': _lib.EMIT_GAUSSIAN, 'discrete': _lib.EMIT_DISCRETE,
           'explicit': _lib.EMIT_EXPLICIT}
 
@@ -524,6 +565,88 @@ class Engine(object):
             ptr = out.data_ptr()
         _lib.check(self._L.bhmm_viterbi_batch_u8(self._h, A, pi, p0, p1, ctypes.c_void_p(int(ptr)), on_dev))
         return out
+
+    # -- dwell segments of a path ----------------------------------------------------------
+    def _runs_result(self, call, stats):
+        """Run one of the two runs calls (call(run_off, dwell, jumps) -> status) and fetch its runs."""
+        n, K = self.nstates, len(self.lengths)
+        off = np.empty(K + 1, dtype=np.int64)
+        dwell = np.zeros((n, _lib.DWELL_COLS), dtype=np.int64) if stats else None
+        jumps = np.zeros((n, n), dtype=np.int64) if stats else None
+        _lib.check(call(_lib.lp(off), _lib.lp(dwell), _lib.lp(jumps)))
+        R = int(off[K])
+        start, length = np.empty(R, dtype=np.int64), np.empty(R, dtype=np.int64)
+        state = np.empty(R, dtype=np.int32)
+        _lib.check(self._L.bhmm_runs_fetch(self._h, _lib.lp(start), _lib.lp(length), _lib.ip(state)))
+        return PathRuns(off, start, length, state, dwell, jumps)
+
+    def path_runs(self, paths, stats=False):
+        """Dwell segments of a GIVEN path, compacted on the device (bhmm_path_runs): `paths` holds one state per
+        step of every loaded trajectory, concatenated like the observations -- what viterbi_u8 and
+        posterior_decode(out=...) write.  A C-contiguous numpy uint8 or int32 array of sum(T_k) elements (staged on
+        the device), or an object with data_ptr() / is_cuda of one or four bytes per element (a torch uint8 / int32
+        tensor: on this engine's GPU it is read in place and must be aligned to 16 bytes; host memory is staged).
+        uint8 needs nstates <= 256.  A state outside [0, nstates) raises ValueError.  Returns a PathRuns; with
+        `stats` its dwell and jumps tables are filled.  Only the runs cross the link (get_option("runs_count"),
+        "runs_ms": device time of the compaction; read-only "runs_tile", "runs_lane")."""
+        if self.kind is None:
+            raise ValueError("no observations loaded")
+        total = int(self.offsets[-1])
+        on_dev = 0
+        if isinstance(paths, np.ndarray):
+            if paths.dtype not in (np.dtype(np.uint8), np.dtype(np.int32)):
+                raise ValueError("paths must be uint8 or int32, not %s" % paths.dtype.name)
+            if paths.ndim != 1 or paths.size != total or not paths.flags.c_contiguous:
+                raise ValueError("paths must be a C-contiguous array of sum(T_k) = %d elements" % total)
+            u8 = paths.dtype == np.uint8
+            ptr = paths.ctypes.data
+        elif hasattr(paths, 'data_ptr'):
+            if paths.element_size() not in (1, 4) or paths.is_floating_point():
+                raise ValueError("paths must be a uint8 or int32 tensor")
+            if paths.numel() != total or not paths.is_contiguous():
+                raise ValueError("paths must be a contiguous tensor of sum(T_k) = %d elements" % total)
+            u8 = paths.element_size() == 1
+            ptr = paths.data_ptr()
+            if paths.is_cuda:
+                if paths.device.index != self.device:
+                    raise ValueError("paths lives on another GPU than this engine")
+                if ptr % 16:
+                    raise ValueError("a device path must be aligned to 16 bytes")
+                on_dev = 1
+        else:
+            raise ValueError("paths must be a numpy array or an object with data_ptr() / is_cuda")
+        if u8 and self.nstates > 256:
+            raise ValueError("one byte per step holds at most 256 states (pass an int32 path)")
+        return self._runs_result(
+            lambda off, dwell, jumps: self._L.bhmm_path_runs(self._h, ctypes.c_void_p(int(ptr)), 1 if u8 else 0,
+                                                             on_dev, off, dwell, jumps), stats)
+
+    def decode_runs(self, A, pi, par0=None, par1=None, method='viterbi', stats=False):
+        """Decode every loaded trajectory under one model and return the dwell segments of the decoded path
+        (bhmm_decode_runs): method 'viterbi' runs what viterbi_u8 runs into a device buffer, 'posterior' what
+        posterior_decode runs up to its copy to the host -- the same kernels, options and side effects on the
+        engine -- and the path is compacted on the device: it never crosses the link.  Up to 256 states (more:
+        decode with viterbi / posterior_decode and call path_runs on the int32 path).  Returns a PathRuns; with
+        `stats` its dwell and jumps tables are filled."""
+        if method not in _METHODS:
+            raise ValueError("method must be 'viterbi' or 'posterior', not %r" % (method,))
+        self._check_model(A, pi, par0, par1)
+        if self.nstates > 256:
+            raise ValueError("decode_runs handles up to 256 states (decode, then path_runs on the int32 path)")
+        A, pi, p0, p1 = self._model_ptrs(A, pi, par0, par1)
+        return self._runs_result(
+            lambda off, dwell, jumps: self._L.bhmm_decode_runs(self._h, A, pi, p0, p1, _METHODS[method], off, dwell,
+                                                               jumps), stats)
+
+    def runs_fetch(self):
+        """(start, length, state) of the runs the last path_runs / decode_runs call on these observations left on
+        the device (bhmm_runs_fetch); ValueError before any."""
+        _lib.check(self._L.bhmm_runs_fetch(self._h, None, None, None))   # (no runs: raises)
+        R = int(self.get_option("runs_count"))
+        start, length = np.empty(R, dtype=np.int64), np.empty(R, dtype=np.int64)
+        state = np.empty(R, dtype=np.int32)
+        _lib.check(self._L.bhmm_runs_fetch(self._h, _lib.lp(start), _lib.lp(length), _lib.ip(state)))
+        return start, length, state
 
     def set_stream_offsets(self, soff):
         """Position of each loaded trajectory in the device random stream (include/bhmm_amd.h):

@@ -438,6 +438,32 @@ class MaximumLikelihoodEstimator(object):
                     conf[k] = lc[j]
         return (paths, conf) if confidence else paths
 
+    def hidden_state_segments(self, method='viterbi', stats=False):
+        """Dwell segments of the estimator's observations decoded under the current (fitted) hmm
+        (Engine.decode_runs): method 'viterbi' or 'posterior'; the path is collapsed into runs of equal states on
+        the GPU and never crosses the link.  Returns a list in the caller's trajectory order of (start, length,
+        state) per trajectory -- the first step of every run inside the trajectory (int64), its length (int64) and
+        its state (int32) -- or with `stats` (segments, dwell, jumps): dwell (nstates, 5) int64 per state the runs,
+        the steps in them, the longest run, the censored runs (they touch the first or last step of their
+        trajectory) and their steps; jumps (nstates, nstates) int64 the run pairs i -> j.  With a process_group
+        every rank decodes the trajectories it holds and the entries of the others are None (local_trajectories
+        lists the ones filled); there is no collective, so dwell and jumps are those of the LOCAL trajectories
+        only (sum them over the ranks for the whole set; the longest run is a maximum).  Up to 256 states."""
+        if method not in ('viterbi', 'posterior'):
+            raise ValueError("method must be 'viterbi' or 'posterior', not %r" % (method,))
+        par0, par1 = self._hmm.output_model.parameters()
+        segs = [None] * self._nobs
+        n = self._hmm.nstates
+        dwell, jumps = np.zeros((n, 5), dtype=np.int64), np.zeros((n, n), dtype=np.int64)
+        if self._mine:
+            res = self._engine.decode_runs(self._hmm.transition_matrix, self._hmm.initial_distribution, par0, par1,
+                                           method=method, stats=stats)
+            for j, k in enumerate(self._mine):
+                segs[k] = res.trajectory(j)
+            if stats:
+                dwell, jumps = res.dwell, res.jumps
+        return (segs, dwell, jumps) if stats else segs
+
     def score(self, models=None):
         """Total log-likelihood of the estimator's observations under each model (forward pass
         only, Engine.score): `models` is one HMM, a list of HMMs or (A, pi, par0, par1) tuples, or

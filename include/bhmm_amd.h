@@ -329,6 +329,40 @@ int bhmm_viterbi_batch(bhmm_ctx *ctx, const double *A, const double *pi, const d
 int bhmm_viterbi_batch_u8(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0,
                           const double *par1, uint8_t *paths, int paths_on_device);
 
+/* Dwell segments (runs) of a decoded path, compacted on the device.  A run is a maximal
+ * stretch of equal states inside one trajectory: a new run begins at step t if t is the first step of its
+ * trajectory or path[t] != path[t - 1].  The trajectories are those of the context's offsets (the views of a lagged
+ * set count as trajectories).  Of a path of sum_k T_k steps only the runs cross the link:
+ *   run_off[K + 1] (host, required): run_off[k] is the index of the first run of trajectory k, run_off[K] = R the
+ *     number of runs; an empty trajectory has run_off[k + 1] == run_off[k];
+ *   dwell[N * BHMM_DWELL_COLS] (host, or NULL), per state i: the number of runs in the state, the steps in them, the
+ *     longest run, the runs that touch the first or the last step of their trajectory (censored: their true dwell
+ *     time is not known) and the steps in those;
+ *   jumps[N * N] (host, or NULL): jumps[i * N + j] adjacent run pairs i -> j inside one trajectory (zero diagonal);
+ *   the runs themselves stay on the device until bhmm_runs_fetch copies them: start (step index inside the
+ *     trajectory, int64), length (int64), state (int32), each of R entries, trajectory after trajectory.
+ * Integer work throughout: the results do not depend on the order of anything.
+ * bhmm_path_runs takes a GIVEN path, flat and trajectory-concatenated as the decoders write it: path_u8 != 0 one
+ * byte per step, else int32; paths_on_device == 0: a host buffer, staged on the device; != 0: a device buffer on the
+ * context's device, aligned to 16 bytes (BHMM_ERR_INVALID otherwise), read in place.  A state outside [0, N) gives
+ * BHMM_ERR_INVALID: the count pass flags it before anything is indexed by it, and no run is delivered.
+ * bhmm_decode_runs decodes under one model and compacts without the path crossing the link: method 0 runs what
+ * bhmm_viterbi_batch_u8 with paths_on_device != 0 runs, into a buffer of the context; method 1 what
+ * bhmm_posterior_decode runs up to the copy to the host -- the same kernels, options, counters and side effects on
+ * the context as those calls.  One byte per step: more than 256 states give BHMM_ERR_INVALID (decode with the
+ * calls above and hand the int32 path to bhmm_path_runs).
+ * The run buffers are sized from R after the count pass; BHMM_ERR_NO_MEM if they do not fit (nothing is delivered
+ * then).  The runs belong to the observation set: bhmm_ctx_set_observations discards them, and bhmm_runs_fetch
+ * before a successful call of the two above gives BHMM_ERR_INVALID.  bhmm_runs_fetch: any pointer may be NULL.
+ * Read-only options: runs_tile (steps per workgroup), runs_lane (steps per lane), runs_count (R of the last call),
+ * runs_ms (device time of its count, scan and scatter passes). */
+#define BHMM_DWELL_COLS 5
+int bhmm_path_runs(bhmm_ctx *ctx, const void *paths, int path_u8, int paths_on_device, int64_t *run_off,
+                   int64_t *dwell, int64_t *jumps);
+int bhmm_decode_runs(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0, const double *par1,
+                     int method, int64_t *run_off, int64_t *dwell, int64_t *jumps);
+int bhmm_runs_fetch(bhmm_ctx *ctx, int64_t *start, int64_t *length, int32_t *state);
+
 /* Gibbs hidden-path step (bayesian_sampling.py:283-331): forward pass + backward sampling
  * of every trajectory.  Uniforms come either from u (host, concatenated like obs; u[t]
  * used at step t) or, when u == NULL, from a counter-based generator seeded with `seed`.
