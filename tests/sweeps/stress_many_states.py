@@ -4,6 +4,7 @@ shape sweep does not reach: 9..64 states (lane-per-state kernels, wide_kernels.h
 also the matrix-core kernels of big_kernels.hpp) -- gaussian / discrete, ragged trajectories (lengths 1, 2, ... included),
 sparse transition matrices, zero entries in pi, far-away observations.  E-step statistics against the
 oracle (logL 1e-10, counts 1e-8), Viterbi and sampled paths (given the uniforms) bit for bit.
+513 to 4096 states are not drawn here: tests/test_many_states_gpu.py covers them at fixed state counts.
 Prints one line per failure and a summary; exit code 1 on failure."""
 import os, sys
 R = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
