@@ -879,9 +879,7 @@ static int alloc_work(bhmm_ctx *c)
 static int upload_Bt(bhmm_ctx *c, const double *B)
 {
     std::vector<double> bt((size_t)c->M * c->N, 0.0);
-    for (int i = 0; i < c->n; ++i)
-        for (int o = 0; o < c->M; ++o)
-            bt[(size_t)o * c->N + i] = B[(size_t)i * c->M + o];
+    fill_Bt_padded(c->n, c->N, c->M, B, bt.data());
     BHMM_HIP(hipMemcpyAsync(c->d_Bt.p, bt.data(), bt.size() * sizeof(double),
                             hipMemcpyHostToDevice, c->stream));
     BHMM_HIP(hipStreamSynchronize(c->stream)); // bt is a temporary

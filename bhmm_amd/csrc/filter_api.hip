@@ -34,16 +34,17 @@
 // Everything else (more than 128 states, explicit pobs, filter_parallel / filter_tile 0 or a small set;
 // filter_path 0): k_filter_serial, one workgroup per trajectory.
 //
-// The three verified paths run one protocol (two_attempts): a pass at the measured warm-up, and after boundaries
-// that did not verify one more at twice that.  What they share with bhmm_score and the posterior calls is in
-// seg_host.hpp (device side) and plan.hpp (arithmetic): the constants of the protocol, the probe's sample positions,
-// staging and reading, the parameter block of a WideModel (fill_wide_block) and the making of a plan's tables
-// (make_seg_tables into c->filt.seg at 9..64 states, c->filt.tseg at 65..128).
+// The three verified paths run one protocol (plan::two_attempts, plan.hpp): a pass at the measured warm-up, and after
+// boundaries that did not verify one more at twice that.  What they share with bhmm_score and the posterior calls is
+// in plan.hpp (arithmetic, protocol), seg_host.hpp (device side) and fused_host.hpp (up to 8 states): the constants of
+// the protocol, the probe's sample positions, staging and reading, the model upload and the warm-up of the fused path
+// (upload_fused_model, fused_probe), the parameter block of a WideModel (fill_wide_block), the making of a plan's
+// tables (make_seg_tables into c->filt.seg at 9..64 states, c->filt.tseg at 65..128) and the staging of the serial
+// path's parameters (stage_serial_models).
 //
 // Nothing here reads or writes the state other calls use: the buffers are c->filt.*, the plans' sizes
 // ds.filt_*, the only other fields touched are opt.filter_* (read) and last.filter_*.  Host results are staged in c->filt.rows / c->filt.logc and
-// cross the link in ONE copy each, after the boundaries verified (a pageable buffer of 8 MiB or more is pinned
-// for it).
+// cross the link in ONE copy each, after the boundaries verified (copy_to_host_pinned, host_internal.hpp).
 #include <math.h>
 #include <string.h>
 
@@ -55,6 +56,7 @@
 #include "filter_kernels.hpp"
 #include "filter_tile_launch.hpp"
 #include "filter_wide_launch.hpp"
+#include "fused_host.hpp"
 #include "host_common.hpp"
 #include "host_internal.hpp"
 #include "launch.hpp"
@@ -70,7 +72,7 @@ FILTER_TILE_LAUNCH_DECL(extern, 8)
 namespace {
 
 // (BOUNDARY_TOL, W_UNPROBED, LDS_BT_MAX, the probe and the plan: seg_host.hpp, shared with bhmm_score and the
-// posterior calls)
+// posterior calls; the protocol: plan.hpp)
 
 struct Out {          // where the results go on the device, and what they are
     void *rows;       // [total][Qp] of double / float, or nullptr
@@ -81,51 +83,6 @@ struct Out {          // where the results go on the device, and what they are
     bool f32;
 };
 
-// warm-up from the forgetting curve, the reading bhmm_score takes (score_api.hip, Fast::probe): forward chains
-// within 0.01 of the check's tolerance from then on, + 15 %, doubled.  0 where the trajectories are too short to
-// probe
-template <int N, int KIND>
-int filter_probe(bhmm_ctx *c, const Model<N> &m, const double *dBt, int *W)
-{
-    *W = 0;
-    const int Wmax = plan::probe_wmax(longest_traj(c));
-    if (Wmax == 0)
-        return BHMM_OK;
-    Probe pr;
-    int rc;
-    if ((rc = probe_stage(c, c->filt.probe, Wmax, 1, pr)))
-        return rc;
-    BHMM_HIP(launch(k_forget_probe<N, KIND>, dim3((2 * PROBE_P + 63) / 64), dim3(64), 0, c->stream, m, c->d_obs_rm.p,
-                    KIND == EMIT_DISC ? dBt : nullptr, pr.d_starts, PROBE_P, Wmax, pr.d_curve));
-    std::vector<float> curve;
-    if ((rc = probe_read(c, pr, curve)))
-        return rc;
-    *W = 2 * plan::warmup_of(plan::curve_last(curve.data(), Wmax, (float)(0.01 * BOUNDARY_TOL), false), Wmax);
-    return BHMM_OK;
-}
-
-// The protocol of a verified pass: `pass` at warm-up W (its boundaries out of tolerance to *fails); none -> the
-// results stand (*verified); else the call counts one fallback and runs once more with twice the warm-up, at most
-// Wcap.  *verified false: the caller takes the serial path
-template <class Pass>
-int two_attempts(bhmm_ctx *c, int W, int Wcap, Pass pass, bool *verified)
-{
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        unsigned int fails = 0;
-        int rc;
-        if ((rc = pass(W, &fails)))
-            return rc;
-        if (fails == 0) {
-            *verified = true;
-            return BHMM_OK;
-        }
-        if (attempt == 0)
-            ++c->last.filter_fallbacks; // boundaries that did not verify at the first warm-up
-        W = (int)std::min<int64_t>(2 * (int64_t)W, Wcap);
-    }
-    return BHMM_OK;
-}
-
 template <int N, int KIND>
 struct Fused {
     template <typename OT, bool PROJ, bool WANT_LOGC>
@@ -135,11 +92,12 @@ struct Fused {
                       : k_filter_sweep<N, KIND, false, OT, PROJ, WANT_LOGC>;
     }
 
-    // the sweep, the first dead chunk of every trajectory, the check and the fix-up; *fails: boundaries out of
-    // tolerance
+    // the sweep, the first dead chunk of every trajectory, the check and the fix-up; *v: failed with boundaries out
+    // of tolerance
     template <typename OT>
-    static int pass(bhmm_ctx *c, const Model<N> *dm, int W, const double *dBt, const Out &o, unsigned int *fails)
+    static int pass(bhmm_ctx *c, const Model<N> *dm, int W, const double *dBt, const Out &o, plan::Verdict *v)
     {
+        unsigned int fails = 0;
         auto &b = c->filt;
         const int G = c->G, groups = c->Gp / 64;
         const Chunks ch = chunks_of(c);
@@ -160,8 +118,9 @@ struct Fused {
             BHMM_HIP(launch(k_filter_bury<OT>, dim3((G + 255) / 256), dim3(256), 0, c->stream, ch, G, b.first_dead.p,
                             static_cast<OT *>(o.rows), o.Qp, static_cast<OT *>(o.logc)));
         }
-        BHMM_HIP(hipMemcpyAsync(fails, b.fails.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        BHMM_HIP(hipMemcpyAsync(&fails, b.fails.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
         BHMM_HIP(hipStreamSynchronize(c->stream));
+        *v = plan::verdict_of(fails);
         return BHMM_OK;
     }
 
@@ -170,37 +129,22 @@ struct Fused {
                    const Out &o, bool *verified)
     {
         auto &b = c->filt;
-        const int M = c->M, n = c->n;
         *verified = false;
-        int rc;
-        if ((rc = b.model.ensure(sizeof(Model<N>))) || (rc = b.aentry.ensure((size_t)c->Gp * N)) ||
-            (rc = b.aexit.ensure((size_t)c->Gp * N)) || (rc = b.dead.ensure(c->Gp)) ||
-            (rc = b.first_dead.ensure(std::max(c->K, 1))) || (rc = b.fails.ensure(1)) ||
-            (KIND == EMIT_DISC && (rc = b.Bt.ensure((size_t)M * N))))
-            return rc;
         Model<N> m;
-        fill_model<N>(m, n, KIND, M, A, pi, par0, par1);
-        Model<N> *dm = reinterpret_cast<Model<N> *>(b.model.p);
-        std::vector<double> bt;
-        if (KIND == EMIT_DISC) {
-            bt.resize((size_t)M * N);
-            for (int i = 0; i < n; ++i)
-                for (int s = 0; s < M; ++s)
-                    bt[(size_t)s * N + i] = par0[(size_t)i * M + s];
-            BHMM_HIP(hipMemcpyAsync(b.Bt.p, bt.data(), bt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        }
-        BHMM_HIP(hipMemcpyAsync(dm, &m, sizeof(Model<N>), hipMemcpyHostToDevice, c->stream));
-        BHMM_HIP(hipStreamSynchronize(c->stream)); // (m and bt are temporaries)
+        int rc;
+        if ((rc = b.aentry.ensure((size_t)c->Gp * N)) || (rc = b.aexit.ensure((size_t)c->Gp * N)) ||
+            (rc = b.dead.ensure(c->Gp)) || (rc = b.first_dead.ensure(std::max(c->K, 1))) || (rc = b.fails.ensure(1)) ||
+            (rc = upload_fused_model<N, KIND>(c, b.model, b.Bt, A, pi, par0, par1, m)))
+            return rc;
+        const Model<N> *dm = reinterpret_cast<const Model<N> *>(b.model.p);
+        // the forward reading of the forgetting probe, as bhmm_score takes it
         int W = c->opt.filter_W;
-        if (W <= 0) {
-            if ((rc = filter_probe<N, KIND>(c, m, b.Bt.p, &W)))
-                return rc;
-            W = W > 0 ? W : W_UNPROBED;
-        }
-        return two_attempts(
-            c, W, 1 << 30,
-            [&](int w, unsigned int *fails) {
-                return o.f32 ? pass<float>(c, dm, w, b.Bt.p, o, fails) : pass<double>(c, dm, w, b.Bt.p, o, fails);
+        if (W <= 0 && (rc = fused_probe<N, KIND>(c, b.probe, m, b.Bt.p, false, &W)))
+            return rc;
+        return plan::two_attempts(
+            W, 1 << 30, &c->last.filter_fallbacks,
+            [&](int w, plan::Verdict *v) {
+                return o.f32 ? pass<float>(c, dm, w, b.Bt.p, o, v) : pass<double>(c, dm, w, b.Bt.p, o, v);
             },
             verified);
     }
@@ -253,10 +197,11 @@ struct WideFilt {
         return BHMM_OK;
     }
 
-    // the sweep, the first dead segment of every trajectory, the check and the fix-up; *fails: boundaries out of
-    // tolerance
-    static int pass(bhmm_ctx *c, const ScoreWideModel *dm, int W, const Out &o, unsigned int *fails)
+    // the sweep, the first dead segment of every trajectory, the check and the fix-up; *v: failed with boundaries out
+    // of tolerance
+    static int pass(bhmm_ctx *c, const ScoreWideModel *dm, int W, const Out &o, plan::Verdict *v)
     {
+        unsigned int fails = 0;
         auto &b = c->filt;
         const int nseg = c->ds.filt_nseg;
         FilterWideArgs a;
@@ -271,7 +216,6 @@ struct WideFilt {
         a.aentry = b.aentry.p;
         a.aexit = b.aexit.p;
         a.dead = b.dead.p;
-        *fails = 0;
         int rc;
         if ((rc = filter_wide_launch(c, c->N, a)))
             return rc;
@@ -288,9 +232,10 @@ struct WideFilt {
             else
                 BHMM_HIP(launch(k_filter_seg_bury<double>, dim3(nseg), dim3(64), 0, c->stream, fs, b.first_dead.p,
                                 static_cast<double *>(o.rows), o.Qp, static_cast<double *>(o.logc)));
-            BHMM_HIP(hipMemcpyAsync(fails, b.fails.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+            BHMM_HIP(hipMemcpyAsync(&fails, b.fails.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
         }
         BHMM_HIP(hipStreamSynchronize(c->stream));
+        *v = plan::verdict_of(fails);
         return BHMM_OK;
     }
 
@@ -329,8 +274,8 @@ struct WideFilt {
         if (segmented && c->opt.filter_W <= 0 && (rc = probe(c, m.w, &W)))
             return rc;
         W = std::max(W, 8);
-        return two_attempts(c, W, 1 << 30, [&](int w, unsigned int *fails) { return pass(c, dm, w, o, fails); },
-                            verified);
+        return plan::two_attempts(W, 1 << 30, &c->last.filter_fallbacks,
+                                  [&](int w, plan::Verdict *v) { return pass(c, dm, w, o, v); }, verified);
     }
 };
 
@@ -343,37 +288,20 @@ int serial(bhmm_ctx *c, const double *A, const double *pi, const double *par0, c
     const int n = c->n, K = c->K;
     if (n > SCORE_SERIAL_R * 1024)
         return invalid_arg("bhmm_filter: more than 4096 states");
-    const size_t np0 = c->kind == EMIT_GAUSS ? (size_t)n : (c->kind == EMIT_DISC ? (size_t)n * c->M : 0);
-    const size_t np1 = c->kind == EMIT_GAUSS ? (size_t)n : 0;
-    auto &b = c->filt;
+    StackedModels d;
     int rc;
-    if ((rc = b.par.ensure((size_t)n * n + n + np0 + np1)))
+    if ((rc = stage_serial_models(c, c->filt.par, 1, StackedModels(c, A, pi, par0, par1), d)))
         return rc;
-    double *dA = b.par.p, *dpi = dA + (size_t)n * n, *dp0 = dpi + n, *dp1 = dp0 + np0;
-    BHMM_HIP(hipMemcpyAsync(dA, A, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemcpyAsync(dpi, pi, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (np0)
-        BHMM_HIP(hipMemcpyAsync(dp0, par0, np0 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (np1)
-        BHMM_HIP(hipMemcpyAsync(dp1, par1, np1 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     BHMM_HIP(hipStreamSynchronize(c->stream)); // (the caller's arrays may be temporaries)
     if (K == 0)
         return BHMM_OK;
     const int bd = std::min(1024, (n + 63) / 64 * 64);
     const size_t lds = ((size_t)n + 16) * sizeof(double);
-    OT *rows = static_cast<OT *>(o.rows), *logc = static_cast<OT *>(o.logc);
-    const void *obs = c->d_obs_rm.p;
-    hipError_t e;
-    if (c->kind == EMIT_GAUSS)
-        e = launch(k_filter_serial<EMIT_GAUSS, OT>, dim3(K), dim3(bd), lds, c->stream, n, c->M, c->d_offsets.p, obs, dA,
-                   dpi, dp0, dp1, o.V, o.Q, rows, logc, only);
-    else if (c->kind == EMIT_DISC)
-        e = launch(k_filter_serial<EMIT_DISC, OT>, dim3(K), dim3(bd), lds, c->stream, n, c->M, c->d_offsets.p, obs, dA,
-                   dpi, dp0, nullptr, o.V, o.Q, rows, logc, only);
-    else
-        e = launch(k_filter_serial<EMIT_EXPL, OT>, dim3(K), dim3(bd), lds, c->stream, n, c->M, c->d_offsets.p, obs, dA,
-                   dpi, nullptr, nullptr, o.V, o.Q, rows, logc, only);
-    BHMM_HIP(e);
+    BHMM_HIP(dispatch_kind(c->kind, [&](auto KIND) {
+        return launch(k_filter_serial<decltype(KIND)::value, OT>, dim3(K), dim3(bd), lds, c->stream, n, c->M,
+                      c->d_offsets.p, c->d_obs_rm.p, d.A, d.pi, d.par0, d.par1, o.V, o.Q, static_cast<OT *>(o.rows),
+                      static_cast<OT *>(o.logc), only);
+    }));
     return BHMM_OK;
 }
 
@@ -496,12 +424,12 @@ struct TileFilt {
         int W = segmented ? (c->opt.filter_W + 3) & ~3 : 0;
         if (segmented && c->opt.filter_W <= 0 && (rc = calibrate(c, dm, m, &W)))
             return rc;
-        return two_attempts(
-            c, W, SCORE_TILE_W_MAX,
-            [&](int w, unsigned int *fails) {
+        return plan::two_attempts(
+            W, SCORE_TILE_W_MAX, &c->last.filter_fallbacks,
+            [&](int w, plan::Verdict *pv) {
                 Verdict v;
                 int rc2;
-                if ((rc2 = pass(c, dm, m, w, &o, &v)) || (*fails = v.fails) != 0)
+                if ((rc2 = pass(c, dm, m, w, &o, &v)) || (*pv = plan::verdict_of(v.fails)) != plan::Verdict::verified)
                     return rc2;
                 // the trajectories with a segment outside the kernel's range again, whole, on the serial kernel:
                 // behind the pass, on the same stream
@@ -515,26 +443,10 @@ struct TileFilt {
     }
 };
 
-// a staged result to the caller's host buffer in one copy: a pageable buffer of 8 MiB or more is pinned for the
-// transfer, one the caller pinned is used as it is
+// a staged result to the caller's host buffer in one copy
 int deliver(bhmm_ctx *c, void *host, const void *dev, size_t bytes)
 {
-    if (bytes == 0)
-        return BHMM_OK;
-    hipPointerAttribute_t attr;
-    const bool caller_pinned = hipPointerGetAttributes(&attr, host) == hipSuccess && attr.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    const bool pinned = !caller_pinned && bytes >= ((size_t)8 << 20) &&
-                        hipHostRegister(host, bytes, hipHostRegisterDefault) == hipSuccess;
-    if (!pinned)
-        (void)hipGetLastError();
-    hipError_t ce = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (ce == hipSuccess)
-        ce = hipStreamSynchronize(c->stream);
-    if (pinned)
-        (void)hipHostUnregister(host);
-    BHMM_HIP(ce);
-    return BHMM_OK;
+    return bytes == 0 ? BHMM_OK : copy_to_host_pinned(c, host, dev, bytes);
 }
 
 } // namespace
@@ -587,7 +499,7 @@ int bhmm_filter(bhmm_ctx *c, const double *A, const double *pi, const double *pa
         o.V = b.V.p;
     }
     const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
-    const bool fused = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;
+    const bool fused = fused_takes(c);
     // 9..64 states (lanes per segment in c->N): always, never, or from FILTER_WIDE_MIN_TOTAL steps on
     const bool wide = c->wide && emis && c->n <= 64 && c->opt.filter_parallel != 0 &&
                       (c->opt.filter_parallel == 1 || c->total >= FILTER_WIDE_MIN_TOTAL);
@@ -607,32 +519,7 @@ int bhmm_filter(bhmm_ctx *c, const double *A, const double *pi, const double *pa
         if ((rc = WideFilt::run(c, A, pi, par0, par1, o, &verified)))
             return rc;
     } else if (fused) {
-        switch (c->n) {
-        case 1:
-            rc = run_n<1>(c, A, pi, par0, par1, o, &verified);
-            break;
-        case 2:
-            rc = run_n<2>(c, A, pi, par0, par1, o, &verified);
-            break;
-        case 3:
-            rc = run_n<3>(c, A, pi, par0, par1, o, &verified);
-            break;
-        case 4:
-            rc = run_n<4>(c, A, pi, par0, par1, o, &verified);
-            break;
-        case 5:
-            rc = run_n<5>(c, A, pi, par0, par1, o, &verified);
-            break;
-        case 6:
-            rc = run_n<6>(c, A, pi, par0, par1, o, &verified);
-            break;
-        case 7:
-            rc = run_n<7>(c, A, pi, par0, par1, o, &verified);
-            break;
-        default:
-            rc = run_n<8>(c, A, pi, par0, par1, o, &verified);
-            break;
-        }
+        rc = dispatch_n(c->n, [&](auto N) { return run_n<decltype(N)::value>(c, A, pi, par0, par1, o, &verified); });
         if (rc)
             return rc;
     }

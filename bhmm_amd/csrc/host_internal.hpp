@@ -1,7 +1,8 @@
 // host_internal.hpp -- functions one translation unit of libbhmm_amd.so calls in another.  Every defining
 // unit includes this header as well, so the compiler checks each declaration against its definition.
 // (Inline host code several units share -- the protocol constants, the probe's staging, the parameter block of a
-// WideModel, the upload of a forward-only pass's plan -- is in seg_host.hpp; its arithmetic in plan.hpp.)
+// WideModel, the upload of a forward-only pass's plan -- is in seg_host.hpp, the scaffold of the paths for up to 8
+// states in fused_host.hpp; the arithmetic and the acceptance protocol in plan.hpp.)
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -10,6 +11,7 @@
 #include <string>
 
 #include "ctx.hpp"
+#include "plan.hpp"
 
 namespace bhmm {
 
@@ -52,7 +54,7 @@ constexpr double SCORE_TILE_DEV_OK = 3e-13;  // boundary deviation that needs no
 constexpr double SCORE_TILE_DEV_GOAL = 1e-13; // the deviation the decay is extrapolated to
 constexpr double SCORE_TILE_MARGIN = 1.25;   // safety factor on the extrapolated decay (tile_gen.hip)
 constexpr int SCORE_TILE_W_SLOW = 1024;      // no decay between the two warm-ups: this one, the check decides
-constexpr int SCORE_TILE_W_MAX = 1 << 20;
+using plan::SCORE_TILE_W_MAX;                // (plan.hpp, beside the protocol it caps)
 // the warm-up from the largest boundary deviations d0, d1 of the passes at SCORE_TILE_W0 and SCORE_TILE_W1 (d1 not
 // good enough as it is): the geometric decay between the two extrapolated to SCORE_TILE_DEV_GOAL, times the
 // margin, rounded up to 8
@@ -125,6 +127,11 @@ int wide_path_plan(bhmm_ctx *c, int which, int64_t seglen, Segs &sg);
 // buffer, 2: one byte per step in a device buffer, written there already); completes the call's stream.  A
 // pageable host buffer of 8 MiB or more is registered for the copy.
 int deliver_paths(bhmm_ctx *c, void *paths_out, int out_fmt, const void *dev_paths);
+// `bytes` from the device to a host buffer in one copy, complete on return (deliver_paths, bhmm_filter,
+// bhmm_posterior_marginals, bhmm_runs_fetch).  A pageable buffer of 8 MiB or more is registered for the transfer (a
+// pageable destination goes through the runtime's staging buffers at a fraction of the link rate); one the caller
+// pinned already (hipHostMalloc / hipHostRegister, torch pin_memory) is used as it is
+int copy_to_host_pinned(bhmm_ctx *c, void *dst, const void *src, size_t bytes);
 // The acceptance protocol of a segment-parallel Viterbi pass on one plan: the first pass is
 // accepted when every boundary is bit-identical to its predecessor's vector, or -- vall kept -- when every
 // boundary is within SEG_VIT_TOL (after mending the far ones) and every decision on the path clears the margin;

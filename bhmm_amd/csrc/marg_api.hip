@@ -7,7 +7,9 @@
 // (restated as marg_sweep_lane, marg_kernels.hpp) with the emit policy MargRow -- over the E-step's chunk plan,
 // the alpha rows in a workspace of at most marg_ws_mb, then k_post_check over the boundary vectors of both directions.
 // Warm-up from the forgetting probe or the option marg_W.  Boundaries that do not verify: counted in
-// marg_fallbacks, the call runs again with twice the warm-up, and if they fail again it takes the generic path.
+// marg_fallbacks, the call runs again with twice the warm-up, and if they fail again it takes the generic path
+// (plan::two_attempts, plan.hpp; the model upload, the probe and the dispatch on the state count are
+// fused_host.hpp's, shared with bhmm_score, bhmm_filter and bhmm_posterior_decode).
 //
 // 9 to 64 states, gaussian or discrete (the time-segmented path, marg_path 2; smooth_wide.hip):
 // k_filter_wide leaves the filtered rows of a range of segments in a workspace of at most smooth_ws_mb,
@@ -32,7 +34,7 @@
 //
 // The fused path reads or writes nothing of the E-step's state and nothing of c->post.*: its buffers are
 // c->marg.*, the only other fields touched are opt.marg_* (read) and last.marg_*.  A host result is staged in
-// c->marg.out and crosses the link in ONE copy (a pageable buffer of 8 MiB or more is pinned for it).
+// c->marg.out and crosses the link in ONE copy (copy_to_host_pinned, host_internal.hpp).
 #include <math.h>
 #include <string.h>
 
@@ -41,12 +43,12 @@
 #include <string>
 #include <vector>
 
+#include "fused_host.hpp"
 #include "host_common.hpp"
 #include "host_internal.hpp"
 #include "launch.hpp"
 #include "marg_kernels.hpp"
 #include "model_check.hpp"
-#include "post_host.hpp"
 #include "smooth_tile_api.hpp"
 #include "smooth_wide_launch.hpp"
 
@@ -63,10 +65,11 @@ struct Out {          // where the rows go on the device, and what they are
 
 template <int N, int KIND>
 struct Fused {
-    // the sweep over every range of chunk groups and the check; *fails: boundaries out of tolerance
+    // the sweep over every range of chunk groups and the check; *v: failed with boundaries out of tolerance
     template <typename OT, bool PROJ>
-    static int pass(bhmm_ctx *c, const Model<N> *dm, int W, const double *dBt, const Out &o, unsigned int *fails)
+    static int pass(bhmm_ctx *c, const Model<N> *dm, int W, const double *dBt, const Out &o, plan::Verdict *v)
     {
+        unsigned int fails = 0;
         auto &b = c->marg;
         const int G = c->G, groups = c->Gp / 64;
         const Chunks ch = chunks_of(c);
@@ -90,8 +93,9 @@ struct Fused {
         if (G > 1)
             BHMM_HIP(launch(k_post_check<N>, dim3((G + 255) / 256), dim3(256), 0, c->stream, ch, G, b.aentry.p,
                             b.aexit.p, b.bassumed.p, b.bout.p, b.dead.p, BOUNDARY_TOL, b.fails.p));
-        BHMM_HIP(hipMemcpyAsync(fails, b.fails.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        BHMM_HIP(hipMemcpyAsync(&fails, b.fails.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
         BHMM_HIP(hipStreamSynchronize(c->stream));
+        *v = plan::verdict_of(fails);
         return BHMM_OK;
     }
 
@@ -100,52 +104,27 @@ struct Fused {
                    const Out &o, bool *verified)
     {
         auto &b = c->marg;
-        const int M = c->M, n = c->n;
         *verified = false;
-        int rc;
-        if ((rc = b.model.ensure(sizeof(Model<N>))) || (rc = b.aentry.ensure((size_t)c->Gp * N)) ||
-            (rc = b.aexit.ensure((size_t)c->Gp * N)) || (rc = b.bassumed.ensure((size_t)c->Gp * N)) ||
-            (rc = b.bout.ensure((size_t)c->Gp * N)) || (rc = b.dead.ensure(c->Gp)) || (rc = b.fails.ensure(1)) ||
-            (KIND == EMIT_DISC && (rc = b.Bt.ensure((size_t)M * N))))
-            return rc;
         Model<N> m;
-        fill_model<N>(m, n, KIND, M, A, pi, par0, par1);
-        Model<N> *dm = reinterpret_cast<Model<N> *>(b.model.p);
-        std::vector<double> bt;
-        if (KIND == EMIT_DISC) {
-            bt.resize((size_t)M * N);
-            for (int i = 0; i < n; ++i)
-                for (int s = 0; s < M; ++s)
-                    bt[(size_t)s * N + i] = par0[(size_t)i * M + s];
-            BHMM_HIP(hipMemcpyAsync(b.Bt.p, bt.data(), bt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        }
-        BHMM_HIP(hipMemcpyAsync(dm, &m, sizeof(Model<N>), hipMemcpyHostToDevice, c->stream));
-        BHMM_HIP(hipStreamSynchronize(c->stream)); // (m and bt are temporaries)
+        int rc;
+        if ((rc = b.aentry.ensure((size_t)c->Gp * N)) || (rc = b.aexit.ensure((size_t)c->Gp * N)) ||
+            (rc = b.bassumed.ensure((size_t)c->Gp * N)) || (rc = b.bout.ensure((size_t)c->Gp * N)) ||
+            (rc = b.dead.ensure(c->Gp)) || (rc = b.fails.ensure(1)) ||
+            (rc = upload_fused_model<N, KIND>(c, b.model, b.Bt, A, pi, par0, par1, m)))
+            return rc;
+        const Model<N> *dm = reinterpret_cast<const Model<N> *>(b.model.p);
+        // the larger of the two directions of the forgetting probe
         int W = c->opt.marg_W;
-        if (W <= 0) {
-            if ((rc = post_probe<N, KIND>(c, b.probe, m, b.Bt.p, &W)))
-                return rc;
-            W = W > 0 ? W : W_UNPROBED;
-        }
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            unsigned int fails = 0;
-            if (o.Q > 0)
-                rc = o.f32 ? pass<float, true>(c, dm, W, b.Bt.p, o, &fails)
-                           : pass<double, true>(c, dm, W, b.Bt.p, o, &fails);
-            else
-                rc = o.f32 ? pass<float, false>(c, dm, W, b.Bt.p, o, &fails)
-                           : pass<double, false>(c, dm, W, b.Bt.p, o, &fails);
-            if (rc)
-                return rc;
-            if (fails == 0) {
-                *verified = true;
-                return BHMM_OK;
-            }
-            if (attempt == 0)
-                ++c->last.marg_fallbacks; // boundaries that did not verify at the first warm-up
-            W = (int)std::min<int64_t>(2 * (int64_t)W, 1 << 30);
-        }
-        return BHMM_OK;
+        if (W <= 0 && (rc = fused_probe<N, KIND>(c, b.probe, m, b.Bt.p, true, &W)))
+            return rc;
+        return plan::two_attempts(
+            W, 1 << 30, &c->last.marg_fallbacks,
+            [&](int w, plan::Verdict *v) {
+                if (o.Q > 0)
+                    return o.f32 ? pass<float, true>(c, dm, w, b.Bt.p, o, v) : pass<double, true>(c, dm, w, b.Bt.p, o, v);
+                return o.f32 ? pass<float, false>(c, dm, w, b.Bt.p, o, v) : pass<double, false>(c, dm, w, b.Bt.p, o, v);
+            },
+            verified);
     }
 };
 
@@ -191,26 +170,10 @@ int generic(bhmm_ctx *c, const double *A, const double *pi, const double *par0, 
     return o.f32 ? gamma_rows<float>(c, o) : gamma_rows<double>(c, o);
 }
 
-// the staged rows to the caller's host buffer in one copy, as deliver_paths does it: a pageable buffer of
-// 8 MiB or more is pinned for the transfer, one the caller pinned is used as it is
+// the staged rows to the caller's host buffer in one copy
 int deliver(bhmm_ctx *c, void *host, const void *dev, size_t bytes)
 {
-    if (bytes == 0)
-        return BHMM_OK;
-    hipPointerAttribute_t attr;
-    const bool caller_pinned = hipPointerGetAttributes(&attr, host) == hipSuccess && attr.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    const bool pinned = !caller_pinned && bytes >= ((size_t)8 << 20) &&
-                        hipHostRegister(host, bytes, hipHostRegisterDefault) == hipSuccess;
-    if (!pinned)
-        (void)hipGetLastError();
-    hipError_t ce = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (ce == hipSuccess)
-        ce = hipStreamSynchronize(c->stream);
-    if (pinned)
-        (void)hipHostUnregister(host);
-    BHMM_HIP(ce);
-    return BHMM_OK;
+    return bytes == 0 ? BHMM_OK : copy_to_host_pinned(c, host, dev, bytes);
 }
 
 } // namespace
@@ -255,8 +218,7 @@ int bhmm_posterior_marginals(bhmm_ctx *c, const double *A, const double *pi, con
         BHMM_HIP(hipStreamSynchronize(c->stream)); // (V may be a temporary of the caller's)
         o.V = b.V.p;
     }
-    const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
-    const bool fused = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;
+    const bool fused = fused_takes(c);
     const int form = Q > 0 ? SMOOTH_FORM_PROJ : SMOOTH_FORM_ROWS;
     const bool segs = smooth_wide_takes(c, form), tile = smooth_tile_takes(c, form);
     c->last.marg_path = fused ? 1 : (segs ? 2 : (tile ? 3 : 0));
@@ -274,32 +236,7 @@ int bhmm_posterior_marginals(bhmm_ctx *c, const double *A, const double *pi, con
                        : smooth_wide_run(c, A, pi, par0, par1, so, &c->last.marg_fallbacks, &verified)))
             return rc;
     } else if (fused) {
-        switch (c->n) {
-        case 1:
-            rc = run_n<1>(c, A, pi, par0, par1, o, &verified);
-            break;
-        case 2:
-            rc = run_n<2>(c, A, pi, par0, par1, o, &verified);
-            break;
-        case 3:
-            rc = run_n<3>(c, A, pi, par0, par1, o, &verified);
-            break;
-        case 4:
-            rc = run_n<4>(c, A, pi, par0, par1, o, &verified);
-            break;
-        case 5:
-            rc = run_n<5>(c, A, pi, par0, par1, o, &verified);
-            break;
-        case 6:
-            rc = run_n<6>(c, A, pi, par0, par1, o, &verified);
-            break;
-        case 7:
-            rc = run_n<7>(c, A, pi, par0, par1, o, &verified);
-            break;
-        default:
-            rc = run_n<8>(c, A, pi, par0, par1, o, &verified);
-            break;
-        }
+        rc = dispatch_n(c->n, [&](auto N) { return run_n<decltype(N)::value>(c, A, pi, par0, par1, o, &verified); });
         if (rc)
             return rc;
     }

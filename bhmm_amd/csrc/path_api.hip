@@ -355,23 +355,24 @@ int deliver_paths(bhmm_ctx *c, void *paths_out, int out_fmt, const void *dev_pat
         BHMM_HIP(hipStreamSynchronize(c->stream));
         return BHMM_OK;
     }
-    // large results into a pageable buffer: pin it for the transfer (a pageable destination goes
-    // through the runtime's staging buffers at a fraction of the link rate); a buffer the caller
-    // pinned already (hipHostMalloc / hipHostRegister, torch pin_memory) is used as it is
-    const size_t pbytes = (size_t)c->total * (out_fmt == 0 ? sizeof(int32_t) : sizeof(uint8_t));
+    return copy_to_host_pinned(c, paths_out, dev_paths,
+                               (size_t)c->total * (out_fmt == 0 ? sizeof(int32_t) : sizeof(uint8_t)));
+}
+
+int copy_to_host_pinned(bhmm_ctx *c, void *dst, const void *src, size_t bytes)
+{
     hipPointerAttribute_t attr;
-    bool caller_pinned = hipPointerGetAttributes(&attr, paths_out) == hipSuccess &&
-                         attr.type == hipMemoryTypeHost;
+    const bool caller_pinned = hipPointerGetAttributes(&attr, dst) == hipSuccess && attr.type == hipMemoryTypeHost;
     (void)hipGetLastError();
-    const bool pinned = !caller_pinned && pbytes >= ((size_t)8 << 20) &&
-                        hipHostRegister(paths_out, pbytes, hipHostRegisterDefault) == hipSuccess;
+    const bool pinned = !caller_pinned && bytes >= ((size_t)8 << 20) &&
+                        hipHostRegister(dst, bytes, hipHostRegisterDefault) == hipSuccess;
     if (!pinned)
         (void)hipGetLastError();
-    hipError_t ce = hipMemcpyAsync(paths_out, dev_paths, pbytes, hipMemcpyDeviceToHost, c->stream);
+    hipError_t ce = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream);
     if (ce == hipSuccess)
         ce = hipStreamSynchronize(c->stream);
     if (pinned)
-        (void)hipHostUnregister(paths_out);
+        (void)hipHostUnregister(dst);
     BHMM_HIP(ce);
     return BHMM_OK;
 }

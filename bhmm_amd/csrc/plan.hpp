@@ -3,7 +3,7 @@
 // (bhmm_score, bhmm_filter: plan_pass, uploaded by seg_host.hpp), the ranges of a budgeted workspace of the posterior
 // calls (smooth_ranges, smooth_tile_ranges), and the forgetting probe every family
 // warms up by: where it samples (probe_starts) and how its curve is read (curve_last, warmup_of,
-// warmup_wide_of).  Pure C++ (no HIP), so
+// warmup_wide_of), and the acceptance protocol of a verified pass (two_attempts, doubled).  Pure C++ (no HIP), so
 // the same code runs under -fsanitize=address,undefined in the CPU sanitizer build
 // (oracle/Makefile `asan`); the .hip files only allocate and upload what these functions return.
 #pragma once
@@ -354,6 +354,45 @@ inline int warmup_wide_of(int last)
 {
     const int w = (int)std::ceil(PROBE_WIDE_MARGIN * (last + 2));
     return std::max(16, (w + 7) / 8 * 8);
+}
+
+// ---- the acceptance protocol of a verified pass (bhmm_filter, bhmm_posterior_decode, bhmm_posterior_marginals) ----
+// `pass(W, &v)` runs the kernels at warm-up W and returns a BHMM code (non-zero: returned at once); v says what its
+// boundary check found.  verified: the results stand (*verified).  failed: the call counts one fallback -- once,
+// after the first pass -- and runs once more at doubled(W, Wcap); failed again: *verified stays false and the
+// caller takes its last-resort path.  abandon (a segment outside the kernels' number range): the same ending at
+// once, and nothing is counted.  bhmm_score runs the protocol per model of a batch (score_api.hip: retry_failed)
+// and takes only the doubling from here.
+//
+// What the callers do NOT share is how they round the W they start from; unifying it would change results:
+//   up to 8 states (filter, decode, marginals; score)  the option or the probe's reading as it is; cap 1 << 30
+//   9..64 states, filter                 (filter_W + 7) / 8 * 8 (not clamped before rounding), then max(W, 8); 1 << 30
+//   9..64 states, decode / marginals     smooth_W rounded up to 8 in 64 bits and clamped to 1 << 30, then max(W, 8);
+//                                        1 << 30; may abandon
+//   9..64 states, score                  (score_W + 3) & ~3 per model; 1 << 30
+//   65..128 states, filter / score       (W + 3) & ~3, or 0 for a plan without a boundary; cap SCORE_TILE_W_MAX
+//   65..128 states, decode / marginals   the same, clamped to SCORE_TILE_W_MAX before the pass; may abandon
+constexpr int SCORE_TILE_W_MAX = 1 << 20; // longest warm-up of the matrix-core passes at 65..128 states
+enum class Verdict { verified, failed, abandon };
+inline Verdict verdict_of(unsigned int fails) { return fails == 0 ? Verdict::verified : Verdict::failed; } // of a count
+inline int doubled(int W, int64_t cap) { return (int)std::min<int64_t>(2 * (int64_t)W, cap); }
+template <class Pass>
+int two_attempts(int W, int Wcap, int *fallbacks, Pass pass, bool *verified)
+{
+    *verified = false;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        Verdict v = Verdict::failed;
+        if (const int rc = pass(W, &v))
+            return rc;
+        if (v != Verdict::failed) {
+            *verified = v == Verdict::verified;
+            return 0; // (BHMM_OK)
+        }
+        if (attempt == 0)
+            ++*fallbacks; // boundaries that did not verify at the first warm-up
+        W = doubled(W, Wcap);
+    }
+    return 0;
 }
 
 // For every segment of the plan with `seglen`: the start of a segment of the twice-as-fine plan

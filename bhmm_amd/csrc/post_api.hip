@@ -8,7 +8,9 @@
 // does not depend on the budget), then k_post_check over the boundary vectors of both directions.  The warm-up
 // comes from the forgetting probe of the E-step (k_forget_probe, the larger of its two directions) or the
 // option post_W.  Boundaries that do not verify: counted in post_fallbacks, the call runs again with twice
-// the warm-up, and if they fail again it takes the generic path.
+// the warm-up, and if they fail again it takes the generic path (plan::two_attempts, plan.hpp; the model upload,
+// the probe and the dispatch on the state count are fused_host.hpp's, shared with bhmm_score, bhmm_filter and
+// bhmm_posterior_marginals).
 //
 // 9 to 64 states, gaussian or discrete (the time-segmented path, post_path 2; smooth_wide.hip):
 // k_filter_wide leaves the filtered rows of a range of segments in a workspace of at most smooth_ws_mb,
@@ -41,11 +43,11 @@
 #include <string>
 #include <vector>
 
+#include "fused_host.hpp"
 #include "host_common.hpp"
 #include "host_internal.hpp"
 #include "launch.hpp"
 #include "model_check.hpp"
-#include "post_host.hpp"
 #include "post_kernels.hpp"
 #include "smooth_tile_api.hpp"
 #include "smooth_wide_launch.hpp"
@@ -64,10 +66,11 @@ int deliver(bhmm_ctx *c, void *path, int path_u8, float *conf)
 
 template <int N, int KIND>
 struct Fused {
-    // the sweep over every range of chunk groups and the check; *fails: boundaries out of tolerance
+    // the sweep over every range of chunk groups and the check; *v: failed with boundaries out of tolerance
     template <typename PT>
-    static int pass(bhmm_ctx *c, const Model<N> *dm, int W, const double *dBt, bool want_conf, unsigned int *fails)
+    static int pass(bhmm_ctx *c, const Model<N> *dm, int W, const double *dBt, bool want_conf, plan::Verdict *v)
     {
+        unsigned int fails = 0;
         auto &b = c->post;
         const int G = c->G, groups = c->Gp / 64;
         const Chunks ch = chunks_of(c);
@@ -91,8 +94,9 @@ struct Fused {
         if (G > 1)
             BHMM_HIP(launch(k_post_check<N>, dim3((G + 255) / 256), dim3(256), 0, c->stream, ch, G, b.aentry.p,
                             b.aexit.p, b.bassumed.p, b.bout.p, b.dead.p, BOUNDARY_TOL, b.fails.p));
-        BHMM_HIP(hipMemcpyAsync(fails, b.fails.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        BHMM_HIP(hipMemcpyAsync(&fails, b.fails.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
         BHMM_HIP(hipStreamSynchronize(c->stream));
+        *v = plan::verdict_of(fails);
         return BHMM_OK;
     }
 
@@ -101,48 +105,26 @@ struct Fused {
                    int path_u8, bool want_conf, bool *verified)
     {
         auto &b = c->post;
-        const int M = c->M, n = c->n;
         *verified = false;
-        int rc;
-        if ((rc = b.model.ensure(sizeof(Model<N>))) || (rc = b.aentry.ensure((size_t)c->Gp * N)) ||
-            (rc = b.aexit.ensure((size_t)c->Gp * N)) || (rc = b.bassumed.ensure((size_t)c->Gp * N)) ||
-            (rc = b.bout.ensure((size_t)c->Gp * N)) || (rc = b.dead.ensure(c->Gp)) || (rc = b.fails.ensure(1)) ||
-            (KIND == EMIT_DISC && (rc = b.Bt.ensure((size_t)M * N))))
-            return rc;
         Model<N> m;
-        fill_model<N>(m, n, KIND, M, A, pi, par0, par1);
-        Model<N> *dm = reinterpret_cast<Model<N> *>(b.model.p);
-        std::vector<double> bt;
-        if (KIND == EMIT_DISC) {
-            bt.resize((size_t)M * N);
-            for (int i = 0; i < n; ++i)
-                for (int o = 0; o < M; ++o)
-                    bt[(size_t)o * N + i] = par0[(size_t)i * M + o];
-            BHMM_HIP(hipMemcpyAsync(b.Bt.p, bt.data(), bt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        }
-        BHMM_HIP(hipMemcpyAsync(dm, &m, sizeof(Model<N>), hipMemcpyHostToDevice, c->stream));
-        BHMM_HIP(hipStreamSynchronize(c->stream)); // (m and bt are temporaries)
+        int rc;
+        if ((rc = b.aentry.ensure((size_t)c->Gp * N)) || (rc = b.aexit.ensure((size_t)c->Gp * N)) ||
+            (rc = b.bassumed.ensure((size_t)c->Gp * N)) || (rc = b.bout.ensure((size_t)c->Gp * N)) ||
+            (rc = b.dead.ensure(c->Gp)) || (rc = b.fails.ensure(1)) ||
+            (rc = upload_fused_model<N, KIND>(c, b.model, b.Bt, A, pi, par0, par1, m)))
+            return rc;
+        const Model<N> *dm = reinterpret_cast<const Model<N> *>(b.model.p);
+        // the larger of the two directions of the forgetting probe
         int W = c->opt.post_W;
-        if (W <= 0) {
-            if ((rc = post_probe<N, KIND>(c, b.probe, m, b.Bt.p, &W)))
-                return rc;
-            W = W > 0 ? W : W_UNPROBED;
-        }
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            unsigned int fails = 0;
-            rc = path_u8 ? pass<uint8_t>(c, dm, W, b.Bt.p, want_conf, &fails)
-                         : pass<int32_t>(c, dm, W, b.Bt.p, want_conf, &fails);
-            if (rc)
-                return rc;
-            if (fails == 0) {
-                *verified = true;
-                return BHMM_OK;
-            }
-            if (attempt == 0)
-                ++c->last.post_fallbacks; // boundaries that did not verify at the first warm-up
-            W = (int)std::min<int64_t>(2 * (int64_t)W, 1 << 30);
-        }
-        return BHMM_OK;
+        if (W <= 0 && (rc = fused_probe<N, KIND>(c, b.probe, m, b.Bt.p, true, &W)))
+            return rc;
+        return plan::two_attempts(
+            W, 1 << 30, &c->last.post_fallbacks,
+            [&](int w, plan::Verdict *v) {
+                return path_u8 ? pass<uint8_t>(c, dm, w, b.Bt.p, want_conf, v)
+                               : pass<int32_t>(c, dm, w, b.Bt.p, want_conf, v);
+            },
+            verified);
     }
 };
 
@@ -208,8 +190,7 @@ int post_decode_device(bhmm_ctx *c, const double *A, const double *pi, const dou
     if ((rc = b.path.ensure(std::max<size_t>((size_t)c->total * (path_u8 ? 1 : sizeof(int32_t)), 8))) ||
         (conf && (rc = b.conf.ensure(std::max<size_t>(c->total, 1)))))
         return rc;
-    const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
-    const bool fused = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;
+    const bool fused = fused_takes(c);
     const int form = conf ? SMOOTH_FORM_DECODE_CONF : SMOOTH_FORM_DECODE;
     const bool segs = smooth_wide_takes(c, form), tile = smooth_tile_takes(c, form);
     c->last.post_path = fused ? 1 : (segs ? 2 : (tile ? 3 : 0));
@@ -227,32 +208,9 @@ int post_decode_device(bhmm_ctx *c, const double *A, const double *pi, const dou
                        : smooth_wide_run(c, A, pi, par0, par1, o, &c->last.post_fallbacks, &verified)))
             return rc;
     } else if (fused) {
-        switch (c->n) {
-        case 1:
-            rc = run_n<1>(c, A, pi, par0, par1, path_u8, conf, &verified);
-            break;
-        case 2:
-            rc = run_n<2>(c, A, pi, par0, par1, path_u8, conf, &verified);
-            break;
-        case 3:
-            rc = run_n<3>(c, A, pi, par0, par1, path_u8, conf, &verified);
-            break;
-        case 4:
-            rc = run_n<4>(c, A, pi, par0, par1, path_u8, conf, &verified);
-            break;
-        case 5:
-            rc = run_n<5>(c, A, pi, par0, par1, path_u8, conf, &verified);
-            break;
-        case 6:
-            rc = run_n<6>(c, A, pi, par0, par1, path_u8, conf, &verified);
-            break;
-        case 7:
-            rc = run_n<7>(c, A, pi, par0, par1, path_u8, conf, &verified);
-            break;
-        default:
-            rc = run_n<8>(c, A, pi, par0, par1, path_u8, conf, &verified);
-            break;
-        }
+        rc = dispatch_n(c->n, [&](auto N) {
+            return run_n<decltype(N)::value>(c, A, pi, par0, par1, path_u8, conf, &verified);
+        });
         if (rc)
             return rc;
     }

@@ -25,26 +25,6 @@ namespace {
 
 using namespace runs;
 
-// `bytes` from the device to a host buffer, complete on return; a pageable buffer of 8 MiB or more is pinned for the
-// copy, as deliver_paths does
-int to_host(bhmm_ctx *c, void *dst, const void *src, size_t bytes)
-{
-    hipPointerAttribute_t attr;
-    const bool caller_pinned = hipPointerGetAttributes(&attr, dst) == hipSuccess && attr.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    const bool pinned = !caller_pinned && bytes >= ((size_t)8 << 20) &&
-                        hipHostRegister(dst, bytes, hipHostRegisterDefault) == hipSuccess;
-    if (!pinned)
-        (void)hipGetLastError();
-    hipError_t ce = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (ce == hipSuccess)
-        ce = hipStreamSynchronize(c->stream);
-    if (pinned)
-        (void)hipHostUnregister(dst);
-    BHMM_HIP(ce);
-    return BHMM_OK;
-}
-
 template <typename PT>
 int compact_t(bhmm_ctx *c, const PT *path, int64_t *run_off, int64_t *dwell, int64_t *jumps)
 {
@@ -197,9 +177,9 @@ int bhmm_runs_fetch(bhmm_ctx *c, int64_t *start, int64_t *length, int32_t *state
     BHMM_HIP(hipSetDevice(c->device));
     const size_t R = (size_t)c->ds.runs_count;
     int rc;
-    if ((start && (rc = to_host(c, start, c->runs.start.p, R * sizeof(int64_t)))) ||
-        (length && (rc = to_host(c, length, c->runs.length.p, R * sizeof(int64_t)))) ||
-        (state && (rc = to_host(c, state, c->runs.state.p, R * sizeof(int32_t)))))
+    if ((start && (rc = copy_to_host_pinned(c, start, c->runs.start.p, R * sizeof(int64_t)))) ||
+        (length && (rc = copy_to_host_pinned(c, length, c->runs.length.p, R * sizeof(int64_t)))) ||
+        (state && (rc = copy_to_host_pinned(c, state, c->runs.state.p, R * sizeof(int32_t)))))
         return rc;
     return BHMM_OK;
 }

@@ -23,9 +23,12 @@
 //
 // Explicit pobs and more than 128 states always take the exact path.
 //
-// What the paths share with bhmm_filter and the posterior calls is in seg_host.hpp (device side) and plan.hpp
-// (arithmetic): the constants of the protocol, the probe's sample positions, staging and reading, the parameter
-// block of a WideModel (fill_wide_block) and the making of a plan's tables (make_seg_tables).
+// The three paths run the protocol per model through one loop (retry_alone) over one view of the caller's stacked
+// arrays (StackedModels).  What they share with bhmm_filter and the posterior calls is in plan.hpp (arithmetic, the
+// doubling of a warm-up), seg_host.hpp (device side) and fused_host.hpp (up to 8 states): the constants of the
+// protocol, the probe's sample positions, staging and reading, the padded B^T and the warm-up of the fused path
+// (fill_Bt_padded, fused_probe_models), the parameter block of a WideModel (fill_wide_block), the making of a plan's
+// tables (make_seg_tables) and the staging of the serial recursion's parameters (stage_serial_models).
 //
 // Nothing here reads or writes the E-step's state (ds.* but the score plan's own fields, carried vectors,
 // warm-up lengths, d_Bt, the E-step's segment plans, the timing events, the pinned landing zones): the
@@ -38,6 +41,7 @@
 #include <string>
 #include <vector>
 
+#include "fused_host.hpp"
 #include "host_common.hpp"
 #include "host_internal.hpp"
 #include "launch.hpp"
@@ -62,45 +66,22 @@ namespace {
 
 // per (trajectory, model) log-likelihood on the exact serial recursion for models [0, S) of the stacked
 // arrays; out[s * K + k]
-int score_serial(bhmm_ctx *c, int S, const double *A, const double *pi, const double *par0, const double *par1,
-                 double *out)
+int score_serial(bhmm_ctx *c, int S, const StackedModels &h, double *out)
 {
     const int n = c->n, K = c->K;
-    const size_t np0 = c->kind == EMIT_GAUSS ? (size_t)n : (c->kind == EMIT_DISC ? (size_t)n * c->M : 0);
-    const size_t np1 = c->kind == EMIT_GAUSS ? (size_t)n : 0;
-    const size_t per = (size_t)n * n + n + np0 + np1;
     const int bd = std::min(1024, (n + 63) / 64 * 64);
     const size_t lds = ((size_t)n + 16) * sizeof(double);
     auto &b = c->score;
     int rc;
     for (int s0 = 0; s0 < S; s0 += SCORE_MAX_MODELS) {
         const int Sb = std::min(SCORE_MAX_MODELS, S - s0);
-        if ((rc = b.par.ensure(per * Sb)) || (rc = b.logLk.ensure((size_t)Sb * K)))
+        StackedModels d;
+        if ((rc = b.logLk.ensure((size_t)Sb * K)) || (rc = stage_serial_models(c, b.par, Sb, h.at(s0), d)))
             return rc;
-        double *dA = b.par.p, *dpi = dA + (size_t)Sb * n * n, *dp0 = dpi + (size_t)Sb * n, *dp1 = dp0 + Sb * np0;
-        BHMM_HIP(hipMemcpyAsync(dA, A + (size_t)s0 * n * n, (size_t)Sb * n * n * sizeof(double),
-                                hipMemcpyHostToDevice, c->stream));
-        BHMM_HIP(hipMemcpyAsync(dpi, pi + (size_t)s0 * n, (size_t)Sb * n * sizeof(double), hipMemcpyHostToDevice,
-                                c->stream));
-        if (np0)
-            BHMM_HIP(hipMemcpyAsync(dp0, par0 + s0 * np0, Sb * np0 * sizeof(double), hipMemcpyHostToDevice,
-                                    c->stream));
-        if (np1)
-            BHMM_HIP(hipMemcpyAsync(dp1, par1 + s0 * np1, Sb * np1 * sizeof(double), hipMemcpyHostToDevice,
-                                    c->stream));
-        const dim3 grid(K, Sb);
-        const void *obs = c->d_obs_rm.p;
-        hipError_t e;
-        if (c->kind == EMIT_GAUSS)
-            e = launch(k_score_serial<EMIT_GAUSS>, grid, dim3(bd), lds, c->stream, n, c->M, K, c->d_offsets.p, obs,
-                       dA, dpi, dp0, dp1, b.logLk.p);
-        else if (c->kind == EMIT_DISC)
-            e = launch(k_score_serial<EMIT_DISC>, grid, dim3(bd), lds, c->stream, n, c->M, K, c->d_offsets.p, obs,
-                       dA, dpi, dp0, nullptr, b.logLk.p);
-        else
-            e = launch(k_score_serial<EMIT_EXPL>, grid, dim3(bd), lds, c->stream, n, c->M, K, c->d_offsets.p, obs,
-                       dA, dpi, nullptr, nullptr, b.logLk.p);
-        BHMM_HIP(e);
+        BHMM_HIP(dispatch_kind(c->kind, [&](auto KIND) {
+            return launch(k_score_serial<decltype(KIND)::value>, dim3(K, Sb), dim3(bd), lds, c->stream, n, c->M, K,
+                          c->d_offsets.p, c->d_obs_rm.p, d.A, d.pi, d.par0, d.par1, b.logLk.p);
+        }));
         BHMM_HIP(hipMemcpyAsync(out + (size_t)s0 * K, b.logLk.p, (size_t)Sb * K * sizeof(double),
                                 hipMemcpyDeviceToHost, c->stream));
         BHMM_HIP(hipStreamSynchronize(c->stream)); // (the parameter buffer is reused by the next batch)
@@ -108,38 +89,38 @@ int score_serial(bhmm_ctx *c, int S, const double *A, const double *pi, const do
     return BHMM_OK;
 }
 
+// models per launch: at most SCORE_MAX_MODELS, and boundary vectors (`rows` chunks or segments of n states, entry and
+// exit, and a log-normaliser each) of at most 1 GiB
+int models_per_launch(int rows, int n)
+{
+    const size_t per_model = (size_t)std::max(rows, 1) * (2 * n + 1) * sizeof(double);
+    return (int)std::max<size_t>(1, std::min<size_t>(SCORE_MAX_MODELS, ((size_t)1 << 30) / per_model));
+}
+
+// The protocol per model of a batch (h, out: the batch's models and results): a model whose first pass left
+// boundaries that did not verify (first(s): failed) counts one fallback and runs again alone, second(s, &v), with
+// twice the warm-up; one that fails again, or that left the kernel's number range (abandon), takes the exact serial
+// recursion
+template <class First, class Second>
+int retry_alone(bhmm_ctx *c, int Sb, const StackedModels &h, double *out, First first, Second second)
+{
+    int rc;
+    for (int s = 0; s < Sb; ++s) {
+        plan::Verdict v = first(s);
+        if (v == plan::Verdict::failed) {
+            ++c->last.score_fallbacks;
+            if ((rc = second(s, &v)))
+                return rc;
+        }
+        if (v != plan::Verdict::verified && (rc = score_serial(c, 1, h.at(s), out + (size_t)s * c->K)))
+            return rc;
+    }
+    return BHMM_OK;
+}
+
 // N: the kernel's state count (the real one for the lane-per-chunk layout, 2 / 4 / 8 padded for PAIR)
 template <int N, int KIND, bool PAIR>
 struct Fast {
-    // warm-up of every model of the batch from the forgetting curve: the E-step's reading (plan::warmup_of) of the
-    // forward chains (within 1e-13 from then on, + 15 %), doubled -- the E-step lengthens its warm-up after a failed
-    // check and keeps it for the observation set, a score call keeps nothing (1024 x 1e6 steps, slowly mixing
-    // models: the plain reading failed the check for three models of four, twice that passed).  W[s] = 0 where
-    // the trajectories are too short to probe
-    static int probe(bhmm_ctx *c, int Sb, const std::vector<Model<N>> &m, const double *dBt, std::vector<int> &W)
-    {
-        W.assign(Sb, 0);
-        const int Wmax = plan::probe_wmax(longest_traj(c));
-        if (Wmax == 0)
-            return BHMM_OK;
-        Probe pr;
-        int rc;
-        if ((rc = probe_stage(c, c->score.probe, Wmax, Sb, pr)))
-            return rc;
-        const size_t curve_words = 2 * (size_t)Wmax;
-        for (int s = 0; s < Sb; ++s)
-            BHMM_HIP(launch(k_forget_probe<N, KIND>, dim3((2 * PROBE_P + 63) / 64), dim3(64), 0, c->stream, m[s],
-                            c->d_obs_rm.p, KIND == EMIT_DISC ? dBt + (size_t)s * c->M * N : nullptr, pr.d_starts,
-                            PROBE_P, Wmax, pr.d_curve + s * curve_words));
-        std::vector<float> curve;
-        if ((rc = probe_read(c, pr, curve)))
-            return rc;
-        const float target = (float)(0.01 * BOUNDARY_TOL);
-        for (int s = 0; s < Sb; ++s) // (the forward direction)
-            W[s] = 2 * plan::warmup_of(plan::curve_last(curve.data() + s * curve_words, Wmax, target, false), Wmax);
-        return BHMM_OK;
-    }
-
     // one launch sequence for models [0, Sb) of the tables on the device; logLk and the failure counters to the host
     static int pass(bhmm_ctx *c, int Sb, const Model<N> *dm, const int32_t *dW, const double *dBt, double *logLk_h,
                     unsigned int *fails_h)
@@ -172,14 +153,11 @@ struct Fast {
         return BHMM_OK;
     }
 
-    static int run(bhmm_ctx *c, int S, const double *A, const double *pi, const double *par0, const double *par1,
-                   double *logL)
+    static int run(bhmm_ctx *c, int S, const StackedModels &h, double *logL)
     {
         auto &b = c->score;
         const int K = c->K, M = c->M, n = c->n;
-        // models per launch: at most SCORE_MAX_MODELS, and boundary vectors of at most 1 GiB
-        const size_t per_model = (size_t)c->Gp * (2 * N + 1) * sizeof(double);
-        const int Sb_max = (int)std::max<size_t>(1, std::min<size_t>(SCORE_MAX_MODELS, ((size_t)1 << 30) / per_model));
+        const int Sb_max = models_per_launch(c->Gp, N);
         int rc;
         if ((rc = b.logLc.ensure((size_t)Sb_max * c->Gp)) || (rc = b.aentry.ensure((size_t)Sb_max * c->Gp * N)) ||
             (rc = b.aexit.ensure((size_t)Sb_max * c->Gp * N)) || (rc = b.logLk.ensure((size_t)Sb_max * K)) ||
@@ -192,62 +170,50 @@ struct Fast {
         for (int s0 = 0; s0 < S; s0 += Sb_max) {
             const int Sb = std::min(Sb_max, S - s0);
             std::vector<Model<N>> m(Sb);
+            std::vector<double> bt(KIND == EMIT_DISC ? (size_t)Sb * M * N : 0, 0.0); // (padded states: zero)
             for (int s = 0; s < Sb; ++s) {
-                const int g = s0 + s;
-                fill_model<N>(m[s], n, KIND, M, A + (size_t)g * n * n, pi + (size_t)g * n,
-                              KIND == EMIT_DISC ? par0 + (size_t)g * n * M : par0 + (size_t)g * n,
-                              KIND == EMIT_GAUSS ? par1 + (size_t)g * n : nullptr);
+                const StackedModels g = h.at(s0 + s);
+                fill_model<N>(m[s], n, KIND, M, g.A, g.pi, g.par0, g.par1);
+                if (KIND == EMIT_DISC)
+                    fill_Bt_padded(n, N, M, g.par0, bt.data() + (size_t)s * M * N);
             }
             if (KIND == EMIT_DISC) {
-                std::vector<double> bt((size_t)Sb * M * N, 0.0); // (padded states: zero)
-                for (int s = 0; s < Sb; ++s)
-                    for (int i = 0; i < n; ++i)
-                        for (int o = 0; o < M; ++o)
-                            bt[((size_t)s * M + o) * N + i] = par0[((size_t)(s0 + s) * n + i) * M + o];
                 BHMM_HIP(hipMemcpyAsync(b.Bt.p, bt.data(), bt.size() * sizeof(double), hipMemcpyHostToDevice,
                                         c->stream));
-                BHMM_HIP(hipStreamSynchronize(c->stream)); // (bt is a temporary)
+                BHMM_HIP(hipStreamSynchronize(c->stream));
             }
             BHMM_HIP(hipMemcpyAsync(dm, m.data(), Sb * sizeof(Model<N>), hipMemcpyHostToDevice, c->stream));
+            // every model has a warm-up of its own: the forward reading of its forgetting curve
             std::vector<int> W(Sb, c->opt.score_W);
-            if (c->opt.score_W <= 0) {
-                if ((rc = probe(c, Sb, m, b.Bt.p, W)))
-                    return rc;
-                for (int &w : W)
-                    w = w > 0 ? w : W_UNPROBED;
-            }
+            if (c->opt.score_W <= 0 &&
+                (rc = fused_probe_models<N, KIND>(c, b.probe, Sb, m.data(), b.Bt.p, false, W.data())))
+                return rc;
             BHMM_HIP(hipMemcpyAsync(b.W.p, W.data(), Sb * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
             double *out = logL + (size_t)s0 * K;
-            if ((rc = pass(c, Sb, dm, b.W.p, b.Bt.p, out, fails.data())))
+            if ((rc = pass(c, Sb, dm, b.W.p, b.Bt.p, out, fails.data())) ||
+                (rc = retry_alone(
+                     c, Sb, h.at(s0), out, [&](int s) { return plan::verdict_of(fails[s]); },
+                     [&](int s, plan::Verdict *v) {
+                         const int W2 = plan::doubled(W[s], 1 << 30);
+                         BHMM_HIP(hipMemcpyAsync(b.W.p + s, &W2, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+                         unsigned int f2 = 0;
+                         const int rc2 = pass(c, 1, dm + s, b.W.p + s,
+                                              KIND == EMIT_DISC ? b.Bt.p + (size_t)s * M * N : nullptr,
+                                              out + (size_t)s * K, &f2);
+                         *v = plan::verdict_of(f2);
+                         return rc2;
+                     })))
                 return rc;
-            // boundaries that did not verify: that model alone with twice the warm-up, then the exact path
-            for (int s = 0; s < Sb; ++s) {
-                if (fails[s] == 0)
-                    continue;
-                ++c->last.score_fallbacks;
-                const int W2 = (int)std::min<int64_t>(2 * (int64_t)W[s], 1 << 30);
-                BHMM_HIP(hipMemcpyAsync(b.W.p + s, &W2, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-                unsigned int f2 = 0;
-                if ((rc = pass(c, 1, dm + s, b.W.p + s, KIND == EMIT_DISC ? b.Bt.p + (size_t)s * M * N : nullptr,
-                               out + (size_t)s * K, &f2)))
-                    return rc;
-                if (f2 != 0 && (rc = score_serial(c, 1, A + (size_t)(s0 + s) * n * n, pi + (size_t)(s0 + s) * n,
-                                                  par0 ? par0 + (size_t)(s0 + s) * n * (KIND == EMIT_DISC ? M : 1)
-                                                       : nullptr,
-                                                  KIND == EMIT_GAUSS ? par1 + (size_t)(s0 + s) * n : nullptr,
-                                                  out + (size_t)s * K)))
-                    return rc;
-            }
         }
         return BHMM_OK;
     }
 };
 
 template <int N, bool PAIR>
-int run_n(bhmm_ctx *c, int S, const double *A, const double *pi, const double *par0, const double *par1, double *logL)
+int run_n(bhmm_ctx *c, int S, const StackedModels &h, double *logL)
 {
-    return c->kind == EMIT_GAUSS ? Fast<N, EMIT_GAUSS, PAIR>::run(c, S, A, pi, par0, par1, logL)
-                                 : Fast<N, EMIT_DISC, PAIR>::run(c, S, A, pi, par0, par1, logL);
+    return c->kind == EMIT_GAUSS ? Fast<N, EMIT_GAUSS, PAIR>::run(c, S, h, logL)
+                                 : Fast<N, EMIT_DISC, PAIR>::run(c, S, h, logL);
 }
 
 // ---- 9..128 states: the plan ----------------------------------------------------------------------
@@ -327,8 +293,7 @@ struct Wide {
         return BHMM_OK;
     }
 
-    static int run(bhmm_ctx *c, int S, const double *A, const double *pi, const double *par0, const double *par1,
-                   double *logL)
+    static int run(bhmm_ctx *c, int S, const StackedModels &h, double *logL)
     {
         auto &b = c->score;
         const int K = c->K, M = c->M, n = c->n;
@@ -336,11 +301,9 @@ struct Wide {
         if ((rc = score_plan(c, false)))
             return rc;
         const int nseg = c->last.score_segments = c->ds.score_nseg;
-        // models per launch: at most SCORE_MAX_MODELS, and boundary vectors of at most 1 GiB
-        const size_t per_model = (size_t)nseg * (2 * n + 1) * sizeof(double);
-        const int Sb_max = (int)std::max<size_t>(1, std::min<size_t>(SCORE_MAX_MODELS, ((size_t)1 << 30) / per_model));
+        const int Sb_max = models_per_launch(nseg, n);
         constexpr bool disc = KIND == EMIT_DISC;
-        const size_t nB = disc ? (size_t)n * M : 0, np = wide_block_size(n, M, disc, true);
+        const size_t np = wide_block_size(n, M, disc, true);
         if ((rc = b.logLc.ensure((size_t)Sb_max * nseg)) || (rc = b.aentry.ensure((size_t)Sb_max * nseg * n)) ||
             (rc = b.aexit.ensure((size_t)Sb_max * nseg * n)) || (rc = b.logLk.ensure((size_t)Sb_max * K)) ||
             (rc = b.fails.ensure(Sb_max)) || (rc = b.W.ensure(Sb_max)) ||
@@ -350,17 +313,16 @@ struct Wide {
         std::vector<unsigned int> fails(Sb_max);
         for (int s0 = 0; s0 < S; s0 += Sb_max) {
             const int Sb = std::min(Sb_max, S - s0);
-            std::vector<double> h(Sb * np, 0.0);
+            std::vector<double> hp(Sb * np, 0.0);
             std::vector<ScoreWideModel> m(Sb);
             for (int s = 0; s < Sb; ++s) {
-                const int g = s0 + s;
-                m[s].Bt = fill_wide_block(n, M, disc, true, A + (size_t)g * n * n, pi + (size_t)g * n,
-                                          par0 + (size_t)g * (disc ? nB : (size_t)n), disc ? nullptr : par1 + (size_t)g * n,
-                                          h.data() + s * np, b.wpar.p + s * np, m[s].w);
+                const StackedModels g = h.at(s0 + s);
+                m[s].Bt = fill_wide_block(n, M, disc, true, g.A, g.pi, g.par0, g.par1, hp.data() + s * np,
+                                          b.wpar.p + s * np, m[s].w);
             }
-            BHMM_HIP(hipMemcpyAsync(b.wpar.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            BHMM_HIP(hipMemcpyAsync(b.wpar.p, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
             BHMM_HIP(hipMemcpyAsync(dm, m.data(), Sb * sizeof(ScoreWideModel), hipMemcpyHostToDevice, c->stream));
-            BHMM_HIP(hipStreamSynchronize(c->stream)); // (h and m are temporaries; the probe takes m by value)
+            BHMM_HIP(hipStreamSynchronize(c->stream)); // (hp and m are temporaries; the probe takes m by value)
             // W: multiples of four (the lazy refresh); no boundary at all, no warm-up to measure
             std::vector<int> W(Sb, (c->opt.score_W + 3) & ~3);
             if (c->opt.score_W <= 0 && nseg > c->ds.score_ntraj && (rc = probe(c, Sb, m, W)))
@@ -369,37 +331,29 @@ struct Wide {
                 c->last.score_W_max = std::max(c->last.score_W_max, *std::max_element(W.begin(), W.end()));
             BHMM_HIP(hipMemcpyAsync(b.W.p, W.data(), Sb * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
             double *out = logL + (size_t)s0 * K;
-            if ((rc = pass(c, Sb, dm, b.W.p, c->opt.score_lazy, out, fails.data())))
+            // (a vector outside the lazy kernel's range counts as a boundary that did not verify: the second pass is
+            // the kernel that sums every step)
+            if ((rc = pass(c, Sb, dm, b.W.p, c->opt.score_lazy, out, fails.data())) ||
+                (rc = retry_alone(
+                     c, Sb, h.at(s0), out, [&](int s) { return plan::verdict_of(fails[s]); },
+                     [&](int s, plan::Verdict *v) {
+                         const int W2 = plan::doubled(W[s], 1 << 30);
+                         BHMM_HIP(hipMemcpyAsync(b.W.p + s, &W2, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+                         unsigned int f2 = 0;
+                         const int rc2 = pass(c, 1, dm + s, b.W.p + s, false, out + (size_t)s * K, &f2);
+                         *v = plan::verdict_of(f2);
+                         return rc2;
+                     })))
                 return rc;
-            // boundaries that did not verify, a vector outside the lazy kernel's range: that model alone with twice
-            // the warm-up on the kernel that sums every step, then the exact path
-            for (int s = 0; s < Sb; ++s) {
-                if (fails[s] == 0)
-                    continue;
-                ++c->last.score_fallbacks;
-                const int W2 = (int)std::min<int64_t>(2 * (int64_t)W[s], 1 << 30);
-                BHMM_HIP(hipMemcpyAsync(b.W.p + s, &W2, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-                unsigned int f2 = 0;
-                if ((rc = pass(c, 1, dm + s, b.W.p + s, false, out + (size_t)s * K, &f2)))
-                    return rc;
-                const int g = s0 + s;
-                if (f2 != 0 && (rc = score_serial(c, 1, A + (size_t)g * n * n, pi + (size_t)g * n,
-                                                  par0 + (size_t)g * (KIND == EMIT_DISC ? nB : (size_t)n),
-                                                  KIND == EMIT_GAUSS ? par1 + (size_t)g * n : nullptr,
-                                                  out + (size_t)s * K)))
-                    return rc;
-            }
         }
         return BHMM_OK;
     }
 };
 
 template <int NP>
-int run_wide(bhmm_ctx *c, int S, const double *A, const double *pi, const double *par0, const double *par1,
-             double *logL)
+int run_wide(bhmm_ctx *c, int S, const StackedModels &h, double *logL)
 {
-    return c->kind == EMIT_GAUSS ? Wide<NP, EMIT_GAUSS>::run(c, S, A, pi, par0, par1, logL)
-                                 : Wide<NP, EMIT_DISC>::run(c, S, A, pi, par0, par1, logL);
+    return c->kind == EMIT_GAUSS ? Wide<NP, EMIT_GAUSS>::run(c, S, h, logL) : Wide<NP, EMIT_DISC>::run(c, S, h, logL);
 }
 
 // ---- 65..128 states ----------------------------------------------------------------------------
@@ -487,8 +441,7 @@ struct Tile {
         return BHMM_OK;
     }
 
-    static int run(bhmm_ctx *c, int S, const double *A, const double *pi, const double *par0, const double *par1,
-                   double *logL)
+    static int run(bhmm_ctx *c, int S, const StackedModels &h, double *logL)
     {
         auto &b = c->score;
         const int K = c->K, M = c->M, n = c->n;
@@ -496,14 +449,12 @@ struct Tile {
         if ((rc = score_plan(c, true)))
             return rc;
         if (c->ds.score_ntiles == 0) // (no trajectory has a step)
-            return score_serial(c, S, A, pi, par0, par1, logL);
+            return score_serial(c, S, h, logL);
         const int nseg = c->last.score_segments = c->ds.score_nseg;
         const bool segmented = nseg > c->ds.score_ntraj;
-        // models per launch: at most SCORE_MAX_MODELS, and boundary vectors of at most 1 GiB
-        const size_t per_model = (size_t)std::max(nseg, 1) * (2 * n + 1) * sizeof(double);
-        const int Sb_max = (int)std::max<size_t>(1, std::min<size_t>(SCORE_MAX_MODELS, ((size_t)1 << 30) / per_model));
+        const int Sb_max = models_per_launch(nseg, n);
         constexpr bool disc = KIND == EMIT_DISC;
-        const size_t nB = disc ? (size_t)n * M : 0, np = wide_block_size(n, M, disc, false); // (the kernel reads B^T)
+        const size_t np = wide_block_size(n, M, disc, false); // (the kernel reads B^T)
         if ((rc = b.logLc.ensure((size_t)Sb_max * nseg)) || (rc = b.aentry.ensure((size_t)Sb_max * nseg * n)) ||
             (rc = b.aexit.ensure((size_t)Sb_max * nseg * n)) || (rc = b.logLk.ensure((size_t)Sb_max * K)) ||
             (rc = b.fails.ensure((size_t)Sb_max * SCORE_TILE_FLAGS)) ||
@@ -513,17 +464,16 @@ struct Tile {
         std::vector<Verdict> v(Sb_max);
         for (int s0 = 0; s0 < S; s0 += Sb_max) {
             const int Sb = std::min(Sb_max, S - s0);
-            std::vector<double> h(Sb * np, 0.0);
+            std::vector<double> hp(Sb * np, 0.0);
             std::vector<ScoreTileModel> m(Sb);
             for (int s = 0; s < Sb; ++s) {
-                const int g = s0 + s;
-                m[s].Bt = fill_wide_block(n, M, disc, false, A + (size_t)g * n * n, pi + (size_t)g * n,
-                                          par0 + (size_t)g * (disc ? nB : (size_t)n), disc ? nullptr : par1 + (size_t)g * n,
-                                          h.data() + s * np, b.wpar.p + s * np, m[s].w);
+                const StackedModels g = h.at(s0 + s);
+                m[s].Bt = fill_wide_block(n, M, disc, false, g.A, g.pi, g.par0, g.par1, hp.data() + s * np,
+                                          b.wpar.p + s * np, m[s].w);
                 m[s].W = 0;
             }
-            BHMM_HIP(hipMemcpyAsync(b.wpar.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-            BHMM_HIP(hipStreamSynchronize(c->stream)); // (h is a temporary)
+            BHMM_HIP(hipMemcpyAsync(b.wpar.p, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            BHMM_HIP(hipStreamSynchronize(c->stream)); // (hp is a temporary)
             // W: multiples of four (the refresh of the scaling); no boundary at all, no warm-up to measure
             std::vector<int> W(Sb, segmented ? (c->opt.score_W + 3) & ~3 : 0);
             if (segmented && c->opt.score_W <= 0 && (rc = calibrate(c, Sb, dm, m, W)))
@@ -531,29 +481,23 @@ struct Tile {
             if (segmented)
                 c->last.score_W_max = std::max(c->last.score_W_max, *std::max_element(W.begin(), W.end()));
             double *out = logL + (size_t)s0 * K;
-            if ((rc = upload(c, Sb, dm, m, W)) || (rc = pass(c, Sb, dm, out, v.data())))
+            // (outside the lazy scaling's range: the exact recursion at once -- there is no tile kernel that sums every
+            // step)
+            auto verdict = [](const Verdict &r) { return r.range != 0 ? plan::Verdict::abandon : plan::verdict_of(r.fails); };
+            if ((rc = upload(c, Sb, dm, m, W)) || (rc = pass(c, Sb, dm, out, v.data())) ||
+                (rc = retry_alone(
+                     c, Sb, h.at(s0), out, [&](int s) { return verdict(v[s]); },
+                     [&](int s, plan::Verdict *pv) {
+                         std::vector<ScoreTileModel> one(1, m[s]);
+                         Verdict v2 = {};
+                         int rc2;
+                         if ((rc2 = upload(c, 1, dm + s, one, std::vector<int>(1, plan::doubled(W[s], SCORE_TILE_W_MAX)))) ||
+                             (rc2 = pass(c, 1, dm + s, out + (size_t)s * K, &v2)))
+                             return rc2;
+                         *pv = v2.range != 0 ? plan::Verdict::failed : plan::verdict_of(v2.fails);
+                         return BHMM_OK;
+                     })))
                 return rc;
-            for (int s = 0; s < Sb; ++s) {
-                if (v[s].range == 0 && v[s].fails == 0)
-                    continue;
-                bool serial = v[s].range != 0; // outside the lazy scaling's range: the exact recursion at once
-                if (!serial) {
-                    // boundaries that did not verify: that model alone with twice the warm-up, then the exact path
-                    ++c->last.score_fallbacks;
-                    std::vector<ScoreTileModel> one(1, m[s]);
-                    Verdict v2;
-                    if ((rc = upload(c, 1, dm + s, one, std::vector<int>(1, (int)std::min<int64_t>(2 * (int64_t)W[s], SCORE_TILE_W_MAX)))) ||
-                        (rc = pass(c, 1, dm + s, out + (size_t)s * K, &v2)))
-                        return rc;
-                    serial = v2.range != 0 || v2.fails != 0;
-                }
-                const int g = s0 + s;
-                if (serial && (rc = score_serial(c, 1, A + (size_t)g * n * n, pi + (size_t)g * n,
-                                                 par0 + (size_t)g * (KIND == EMIT_DISC ? nB : (size_t)n),
-                                                 KIND == EMIT_GAUSS ? par1 + (size_t)g * n : nullptr,
-                                                 out + (size_t)s * K)))
-                    return rc;
-            }
         }
         return BHMM_OK;
     }
@@ -577,45 +521,29 @@ int bhmm_score(bhmm_ctx *c, int nmodels, const double *A, const double *pi, cons
     if ((rc = check_models(c, "bhmm_score", nmodels, A, pi, par0, par1)))
         return rc;
     const bool emis = c->kind == EMIT_GAUSS || c->kind == EMIT_DISC;
-    const bool fast = !c->wide && !c->gen && c->n <= 8 && emis && c->G > 0;
+    const bool fast = fused_takes(c);
     const bool tile = c->gen && c->n <= 128 && emis; // 65..128 states
     c->last.score_path = fast ? 1 : (c->wide && emis ? 2 : (tile ? 3 : 0));
     c->last.score_segments = c->last.score_W_max = 0;
+    const StackedModels h(c, A, pi, par0, par1);
     if (tile)
-        return c->kind == EMIT_GAUSS ? Tile<EMIT_GAUSS>::run(c, nmodels, A, pi, par0, par1, logL)
-                                     : Tile<EMIT_DISC>::run(c, nmodels, A, pi, par0, par1, logL);
+        return c->kind == EMIT_GAUSS ? Tile<EMIT_GAUSS>::run(c, nmodels, h, logL)
+                                     : Tile<EMIT_DISC>::run(c, nmodels, h, logL);
     if (c->last.score_path == 2) // 9..64 states: lanes per segment in c->N
-        return c->N == 16   ? run_wide<16>(c, nmodels, A, pi, par0, par1, logL)
-               : c->N == 32 ? run_wide<32>(c, nmodels, A, pi, par0, par1, logL)
-                            : run_wide<64>(c, nmodels, A, pi, par0, par1, logL);
+        return c->N == 16   ? run_wide<16>(c, nmodels, h, logL)
+               : c->N == 32 ? run_wide<32>(c, nmodels, h, logL)
+                            : run_wide<64>(c, nmodels, h, logL);
     if (!fast)
-        return score_serial(c, nmodels, A, pi, par0, par1, logL);
+        return score_serial(c, nmodels, h, logL);
     if (c->opt.score_layout == 1) // one lane per chunk, the real state count
-        switch (c->n) {
-        case 1:
-            return run_n<1, false>(c, nmodels, A, pi, par0, par1, logL);
-        case 2:
-            return run_n<2, false>(c, nmodels, A, pi, par0, par1, logL);
-        case 3:
-            return run_n<3, false>(c, nmodels, A, pi, par0, par1, logL);
-        case 4:
-            return run_n<4, false>(c, nmodels, A, pi, par0, par1, logL);
-        case 5:
-            return run_n<5, false>(c, nmodels, A, pi, par0, par1, logL);
-        case 6:
-            return run_n<6, false>(c, nmodels, A, pi, par0, par1, logL);
-        case 7:
-            return run_n<7, false>(c, nmodels, A, pi, par0, par1, logL);
-        default:
-            return run_n<8, false>(c, nmodels, A, pi, par0, par1, logL);
-        }
+        return dispatch_n(c->n, [&](auto N) { return run_n<decltype(N)::value, false>(c, nmodels, h, logL); });
     switch (c->N) { // N/2 lanes per chunk (P1's layout), padded state count
     case 2:
-        return run_n<2, true>(c, nmodels, A, pi, par0, par1, logL);
+        return run_n<2, true>(c, nmodels, h, logL);
     case 4:
-        return run_n<4, true>(c, nmodels, A, pi, par0, par1, logL);
+        return run_n<4, true>(c, nmodels, h, logL);
     default:
-        return run_n<8, true>(c, nmodels, A, pi, par0, par1, logL);
+        return run_n<8, true>(c, nmodels, h, logL);
     }
 }
 

@@ -1,11 +1,14 @@
 // seg_host.hpp -- host scaffolding the verified time-parallel passes share (the E-step's probes, bhmm_score,
 // bhmm_filter, bhmm_posterior_decode, bhmm_posterior_marginals): the constants of their protocol, the staging of
-// the forgetting probe around each caller's kernel launch, the parameter block of a WideModel, and the upload of a
-// forward-only pass's segment plan.  The arithmetic is plan.hpp's (pure host code); this header touches the device.
+// the forgetting probe around each caller's kernel launch, the padded B^T of the kernels for up to 8 states, the
+// parameter block of a WideModel, the upload of a forward-only pass's segment plan, and the staging of the exact
+// serial recursions' parameters.  What only the paths for up to 8 states share is in fused_host.hpp.  The arithmetic
+// and the acceptance protocol are plan.hpp's (pure host code); this header touches the device.
 #pragma once
 #include <math.h>
 #include <string.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "host_common.hpp"
@@ -49,6 +52,15 @@ inline int probe_read(bhmm_ctx *c, const Probe &p, std::vector<float> &curve)
     BHMM_HIP(hipMemcpyAsync(curve.data(), p.d_curve, p.words * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     BHMM_HIP(hipStreamSynchronize(c->stream));
     return BHMM_OK;
+}
+
+// ---- B^T of a discrete model for the kernels up to 8 states ----
+// bt[M][N] (zeroed by the caller: the padded states stay zero) from B[n][M]
+inline void fill_Bt_padded(int n, int N, int M, const double *B, double *bt)
+{
+    for (int i = 0; i < n; ++i)
+        for (int o = 0; o < M; ++o)
+            bt[(size_t)o * N + i] = B[(size_t)i * M + o];
 }
 
 // ---- the parameter block of a WideModel (wide_kernels.hpp) ----
@@ -149,6 +161,55 @@ SEGS segs_of_tables(const SegTables &t, int nseg, int W)
     sg.nseg = nseg;
     sg.W = W;
     return sg;
+}
+
+// ---- the exact serial recursions (k_score_serial, k_filter_serial) ----
+// The caller's stacked arrays of S models as the kernels read them, [A | pi | par0 | par1] in buf, copied on the
+// context's stream (no wait); what the emission kind does not have is nullptr.  view.at(g): model g of them
+struct StackedModels {
+    const double *A = nullptr, *pi = nullptr, *par0 = nullptr, *par1 = nullptr;
+    size_t n = 0, np0 = 0, np1 = 0; // values per model of pi, par0 and par1
+    StackedModels() = default;
+    StackedModels(const bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1)
+        : A(A), pi(pi), n(c->n), np0(c->kind == EMIT_GAUSS ? n : (c->kind == EMIT_DISC ? n * c->M : 0)),
+          np1(c->kind == EMIT_GAUSS ? n : 0)
+    {
+        this->par0 = np0 ? par0 : nullptr;
+        this->par1 = np1 ? par1 : nullptr;
+    }
+    StackedModels at(size_t g) const
+    {
+        StackedModels v = *this;
+        v.A += g * n * n, v.pi += g * n;
+        v.par0 = par0 ? par0 + g * np0 : nullptr;
+        v.par1 = par1 ? par1 + g * np1 : nullptr;
+        return v;
+    }
+};
+inline int stage_serial_models(bhmm_ctx *c, DevBuf<double> &buf, size_t S, const StackedModels &h, StackedModels &d)
+{
+    if (int rc = buf.ensure(S * (h.n * h.n + h.n + h.np0 + h.np1)))
+        return rc;
+    d = h;
+    double *dA = buf.p, *dpi = dA + S * h.n * h.n, *dp0 = dpi + S * h.n, *dp1 = dp0 + S * h.np0;
+    BHMM_HIP(hipMemcpyAsync(dA, h.A, S * h.n * h.n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(dpi, h.pi, S * h.n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (h.np0)
+        BHMM_HIP(hipMemcpyAsync(dp0, h.par0, S * h.np0 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (h.np1)
+        BHMM_HIP(hipMemcpyAsync(dp1, h.par1, S * h.np1 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    d.A = dA, d.pi = dpi, d.par0 = h.np0 ? dp0 : nullptr, d.par1 = h.np1 ? dp1 : nullptr;
+    return BHMM_OK;
+}
+// f(std::integral_constant<int, KIND>()) for one of the three emission kinds
+template <class F>
+auto dispatch_kind(int kind, F f)
+{
+    if (kind == EMIT_GAUSS)
+        return f(std::integral_constant<int, EMIT_GAUSS>());
+    if (kind == EMIT_DISC)
+        return f(std::integral_constant<int, EMIT_DISC>());
+    return f(std::integral_constant<int, EMIT_EXPL>());
 }
 
 } // namespace bhmm

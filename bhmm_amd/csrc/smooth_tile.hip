@@ -1,6 +1,7 @@
 // smooth_tile.hip -- the matrix-core path of bhmm_posterior_decode and bhmm_posterior_marginals for 65..128 states
 // (post_path / marg_path 3): the plan, the ranges of the budgeted workspace, the warm-up and
-// the protocol.  The kernels compile in smooth_tile_nt.hip and filter_tile_nt.hip.
+// the pass the protocol (plan::two_attempts, plan.hpp) runs.  The kernels compile in smooth_tile_nt.hip and
+// filter_tile_nt.hip.
 //
 // Forward half: k_filter_tile<NT, KIND, FULL, double, false, false> (filter_tile_nt.hip, not changed) through
 // filter_tile_launch, with rows = the workspace, no projection, no logc.  Backward half: k_smooth_tile_bwd over the
@@ -243,21 +244,17 @@ struct TileSmooth {
         int W = segmented ? (int)std::min<int64_t>(((int64_t)c->opt.smooth_W + 3) & ~(int64_t)3, SCORE_TILE_W_MAX) : 0;
         if (segmented && c->opt.smooth_W <= 0 && (rc = calibrate(c, dm, m, &W)))
             return rc;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            Verdict v;
-            if ((rc = pass(c, dm, m, W, &o, &v)))
-                return rc;
-            if (v.flagged != 0) // probability zero, an outlier, a NaN observation: the generic path gives its answer
-                return BHMM_OK; // (or its error); nothing is counted
-            if (v.fails == 0) {
-                *verified = true;
-                return BHMM_OK;
-            }
-            if (attempt == 0)
-                ++*fallbacks; // boundaries that did not verify at the first warm-up
-            W = (int)std::min<int64_t>(2 * (int64_t)W, SCORE_TILE_W_MAX);
-        }
-        return BHMM_OK;
+        return plan::two_attempts(
+            W, SCORE_TILE_W_MAX, fallbacks,
+            [&](int w, plan::Verdict *pv) {
+                Verdict v = {};
+                const int rc2 = pass(c, dm, m, w, &o, &v);
+                // probability zero, an outlier, a NaN observation: the generic path gives its answer (or its error);
+                // nothing is counted
+                *pv = v.flagged != 0 ? plan::Verdict::abandon : plan::verdict_of(v.fails);
+                return rc2;
+            },
+            verified);
     }
 };
 

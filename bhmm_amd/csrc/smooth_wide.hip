@@ -2,7 +2,8 @@
 // (post_path / marg_path 2) in a translation unit of its own: the 54 instantiations of
 // k_smooth_wide_bwd (16 / 32 / 64 lanes per segment x gaussian / discrete with B^T in LDS / discrete with B^T read
 // ahead x decode to bytes / decode to int32 / rows double / rows float / projection double / projection float), the
-// forgetting probe of the family in both directions, the plan, the warm-up and the protocol.
+// forgetting probe of the family in both directions, the plan, the warm-up and the pass the protocol
+// (plan::two_attempts, plan.hpp) runs.
 //
 // Forward half: k_filter_wide (filter_wide.hip, not changed) through filter_wide_launch, with rows = the workspace
 // in double, no projection, no logc.  Backward half: k_smooth_wide_bwd over the same segments.  The workspace holds
@@ -237,21 +238,17 @@ int smooth_wide_run(bhmm_ctx *c, const double *A, const double *pi, const double
     if (segmented && c->opt.smooth_W <= 0 && (rc = probe(c, m.w, &W)))
         return rc;
     W = std::max(W, 8);
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        unsigned int words[SMOOTH_WORDS] = {0, 0, 0};
-        if ((rc = pass(c, dm, W, o, words)))
-            return rc;
-        if (words[SMOOTH_FLAGGED] != 0) // probability zero, a NaN observation, a sum outside the range: the generic
-            return BHMM_OK;             // path gives its answer (or its error); nothing is counted
-        if (words[SMOOTH_FAILS] == 0) {
-            *verified = true;
-            return BHMM_OK;
-        }
-        if (attempt == 0)
-            ++*fallbacks; // boundaries that did not verify at the first warm-up
-        W = (int)std::min<int64_t>(2 * (int64_t)W, 1 << 30);
-    }
-    return BHMM_OK;
+    return plan::two_attempts(
+        W, 1 << 30, fallbacks,
+        [&](int w, plan::Verdict *v) {
+            unsigned int words[SMOOTH_WORDS] = {0, 0, 0};
+            const int rc2 = pass(c, dm, w, o, words);
+            // probability zero, a NaN observation, a sum outside the range: the generic path gives its answer (or its
+            // error); nothing is counted
+            *v = words[SMOOTH_FLAGGED] != 0 ? plan::Verdict::abandon : plan::verdict_of(words[SMOOTH_FAILS]);
+            return rc2;
+        },
+        verified);
 }
 
 } // namespace bhmm
