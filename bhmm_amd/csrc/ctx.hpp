@@ -312,7 +312,6 @@ struct bhmm_ctx {
     int tail_slot = 0;               // verdict word set of the next E-step
     bool tail_ready = false;         // d_tail allocated and its verdict words cleared
     bool ev_lean = false;            // last E-step recorded only ev[2..4]
-    bool draw_force_exact = false;   // the call in flight is the repeat on exact alpha rows
     int wide_retry = 0;              // time-segmented attempts of the E-step call in flight that did not verify
     bool gamma_wanted = false;       // the E-step in flight stores gamma (a re-plan must re-size the rows)
     bool prefetched = false;         // stats + logL_k of the last E-step already sit in h_pinned

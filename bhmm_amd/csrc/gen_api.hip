@@ -399,23 +399,6 @@ int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double 
     int rc = wide_model(c, c->kind, A, pi, par0, par1, m);
     if (rc)
         return rc;
-    // alpha rows in d_alpha_rm: from the tile forward pass over time segments where it verifies
-    // (65..128 states; the draw normalises alpha_t[i] A[i][s_{t+1}] itself, any factor per row cancels),
-    // else from the serial recursion
-    // (the repeat of a call in which a watched draw did not stand, draw_verify.hpp: the serial recursion)
-    bool fwd_seg = false;
-    if (!c->draw_force_exact && (rc = tile_gen_forward_draw(c, m, &fwd_seg)))
-        return rc;
-    c->last.draw_fwd_segmented = fwd_seg;
-    if (!fwd_seg) {
-        c->last.draw_alpha_dev = 0.0;
-        if ((rc = gen_forward(c, A, pi, par0, par1)))
-            return rc;
-    }
-    // rows of a segmented pass: draws within 64 x the deviation its boundary check measured are recorded
-    DrawWatch watch;
-    if ((rc = draw_watch_prepare(c, fwd_seg ? 64.0 * std::max(c->last.draw_alpha_dev, 1e-16) : 0.0, watch, nullptr)))
-        return rc;
     const int n = c->n, K = c->K;
     const size_t nstat = (size_t)n * n + n;
     const size_t esz = c->kind == EMIT_GAUSS ? 3 * (size_t)n : (c->kind == EMIT_DISC ? (size_t)n * c->M : 0);
@@ -437,100 +420,43 @@ int gen_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double 
                                 c->stream));
     }
     BHMM_HIP(hipMemsetAsync(cnt, 0, (nstat + nsym) * sizeof(unsigned long long), c->stream));
-    BHMM_HIP(hipMemsetAsync(status, 0, sizeof(int), c->stream));
-    // up to 512 states: the draw over time segments (k_gen_sample_seg), coupled through the per-step
-    // uniforms; segments that did not continue their successor's state are drawn again until none is left
-    c->last.smp_segmented = false;
-    bool seg_done = false;
-    if (c->opt.spec_enabled && n <= 512) {
-        const int64_t want = (int64_t)c->opt.smp_seg_per_simd * c->num_simd;
-        const int64_t seglen = std::max<int64_t>((c->total + want - 1) / want, 64);
-        Segs sg;
-        if ((rc = wide_path_plan(c, 1, seglen, sg)))
-            return rc;
-        if (sg.nseg > K) {
-            if (c->ds.smp_W <= 0)
-                c->ds.smp_W = 64;
-            sg.W = c->ds.smp_W;
-            if ((rc = gen_transposed(c, m)) || (rc = c->d_sentry.ensure((size_t)sg.nseg)) ||
-                (rc = c->d_sexit.ensure((size_t)sg.nseg)) || (rc = c->d_vflag.ensure((size_t)sg.nseg)) ||
-                (rc = ensure_specres(c)))
-                return rc;
-            const dim3 sgrid((sg.nseg + 3) / 4), sblk(256);
-            // (first round, then the rounds that draw the flagged segments again)
-            auto *kfirst = n <= 128   ? k_gen_sample_seg<2, false>
-                           : n <= 256 ? k_gen_sample_seg<4, false>
-                                      : k_gen_sample_seg<8, false>;
-            auto *kfix = n <= 128   ? k_gen_sample_seg<2, true>
-                         : n <= 256 ? k_gen_sample_seg<4, true>
-                                    : k_gen_sample_seg<8, true>;
-            const int max_rounds = 16;
-            int round = 0;
-            for (; round <= max_rounds; ++round) {
-                if ((rc = specres_reset(c)))
-                    return rc;
-                lds_poison(c->stream);
-                BHMM_HIP(launch(round == 0 ? kfirst : kfix, sgrid, sblk, 0, c->stream, m, c->d_gAt.p, c->d_offsets.p, sg,
-                                c->d_alpha_rm.p, udev, seed, c->d_soff.p, path, status, c->d_sentry.p, c->d_sexit.p,
-                                c->d_vflag.p, watch));
-                BHMM_HIP(launch(k_wide_smp_check, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg, c->d_sentry.p,
-                                c->d_sexit.p, c->d_vflag.p, c->d_specres.p));
-                if ((rc = specres_read(c, 4, false)))
-                    return rc;
-                BHMM_HIP(hipMemcpyAsync(&c->h_specres[0], status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-                BHMM_HIP(hipStreamSynchronize(c->stream));
-                if (round == 0)
-                    c->last.smp_seg_mismatch = (int)c->h_specres[3];
-                if (c->h_specres[3] == 0)
-                    break;
-            }
-            c->last.smp_seg_rounds = round;
-            // (a draw that found no state may belong to a segment that was drawn again afterwards:
-            // the serial kernel decides such a call)
-            seg_done = c->h_specres[3] == 0 && c->h_specres[0] == 0;
-            if (!seg_done)
-                BHMM_HIP(hipMemsetAsync(status, 0, sizeof(int), c->stream));
-            if ((int64_t)c->last.smp_seg_mismatch * 10 > sg.nseg && c->ds.smp_W < 4096)
-                c->ds.smp_W *= 2;
-            c->last.smp_segmented = seg_done;
-        }
-    }
-    size_t sm = gen_smem(n, 2, 4);
-    if (!seg_done && fwd_seg) { // (the serial draw has no watch: it reads rows of the serial recursion)
-        if ((rc = gen_forward(c, A, pi, par0, par1)))
-            return rc;
-        c->last.draw_fwd_segmented = false;
+    // up to 512 states: the draw over time segments (k_gen_sample_seg), by the protocol of seg_draw (path_api.hip)
+    SegDraw f;
+    // alpha rows in d_alpha_rm: from the tile forward pass over time segments where it verifies
+    // (65..128 states; the draw normalises alpha_t[i] A[i][s_{t+1}] itself, any factor per row cancels),
+    // else from the serial recursion
+    f.forward = [&](bool exact) -> int {
+        bool fwd_seg = false;
+        int r;
+        if (!exact && (r = tile_gen_forward_draw(c, m, &fwd_seg)))
+            return r;
+        c->last.draw_fwd_segmented = fwd_seg;
+        if (fwd_seg)
+            return BHMM_OK;
         c->last.draw_alpha_dev = 0.0;
-    }
-    if (seg_done && watch.count) {
-        // watched draws are decided again on the serial recursion over a long window; if one does not stand, the
-        // whole call again on the rows of the serial recursion
-        unsigned int nwatched = 0;
-        BHMM_HIP(hipMemcpyAsync(&nwatched, watch.count, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-        BHMM_HIP(hipStreamSynchronize(c->stream));
-        if (nwatched) {
-            bool ok = false;
-            if ((rc = draw_verify_run(c, A, pi, par0, par1, nwatched, watch.tol, 8 * (int64_t)std::max(c->ds.spec_W, 64), &ok)))
-                return rc;
-            if (!ok) {
-                const unsigned int ev = c->last.draw_events, ck = c->last.draw_checked;
-                c->draw_force_exact = true;
-                rc = gen_sample_run(c, A, pi, par0, par1, u, seed, paths, counts, n0, emis, stats_dev);
-                c->draw_force_exact = false;
-                c->last.draw_events = ev;
-                c->last.draw_checked = ck;
-                c->last.draw_redone = 1;
-                return rc;
-            }
-        }
-    }
-    if (!seg_done) {
+        return gen_forward(c, A, pi, par0, par1);
+    };
+    f.prepare = [&](const Segs &) { return gen_transposed(c, m); };
+    f.pass = [&](bool fix, const Segs &sg, const DrawWatch &watch) -> int {
+        auto *k = n <= 128   ? (fix ? k_gen_sample_seg<2, true> : k_gen_sample_seg<2, false>)
+                  : n <= 256 ? (fix ? k_gen_sample_seg<4, true> : k_gen_sample_seg<4, false>)
+                             : (fix ? k_gen_sample_seg<8, true> : k_gen_sample_seg<8, false>);
+        BHMM_HIP(launch(k, dim3((sg.nseg + 3) / 4), dim3(256), 0, c->stream, m, c->d_gAt.p, c->d_offsets.p, sg,
+                        c->d_alpha_rm.p, udev, seed, c->d_soff.p, path, status, c->d_sentry.p, c->d_sexit.p, c->d_vflag.p,
+                        watch));
+        return BHMM_OK;
+    };
+    f.serial = [&]() -> int {
+        size_t sm = gen_smem(n, 2, 4);
         const bool alds = gen_a_in_lds(n, sm);
         sm += alds ? gen_a_bytes(n) : 0;
         auto *ks = alds ? k_gen_sample<true> : k_gen_sample<false>;
         BHMM_HIP(launch(ks, dim3(K), dim3(GEN_TPB), sm, c->stream, m, c->d_offsets.p, K, c->d_alpha_rm.p, udev, seed,
                         c->d_soff.p, path, status));
-    }
+        return BHMM_OK;
+    };
+    if ((rc = seg_draw(c, f, A, pi, par0, par1, n <= 512, (int64_t)c->opt.smp_seg_per_simd * c->num_simd, status)))
+        return rc;
     int hstatus = 0;
     BHMM_HIP(hipMemcpyAsync(&hstatus, status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     BHMM_HIP(hipStreamSynchronize(c->stream));

@@ -156,6 +156,36 @@ int seg_viterbi(bhmm_ctx *c, const SegViterbi &f, const Segs &sg, int64_t seglen
 int draw_watch_prepare(bhmm_ctx *c, double tol, DrawWatch &w, unsigned int *count_slot);
 int draw_verify_run(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
                     unsigned int count, double thr, int64_t Wlong, bool *ok);
+// "Watched draws are decided again", for every family: draw_verify_run over a window of 8 x max(spec_W, 64) steps.
+// If a decision does not stand, `repeat` -- the caller's draw on exact alpha rows, which records nothing -- runs,
+// draw_events and draw_checked stay those of the first draw, draw_redone = 1 and *repeated (its code is returned).
+int draw_decide_again(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                      unsigned int count, double thr, const std::function<int()> &repeat, bool *repeated);
+// The protocol around the segment-parallel backward draw (wide_sample_run, gen_sample_run) on plan 1 of
+// wide_path_plan: alpha rows from forward(false); a watch of 64 x the deviation a segmented forward pass measured
+// (none on exact rows); *status_dev cleared; then -- segments_allowed, spec_enabled and more segments than
+// trajectories at plan::draw_seglen(total, want_segments) -- the first round and up to plan::DRAW_MAX_ROUNDS fix-up
+// rounds, each: reset, poison, pass, k_wide_smp_check, read; else, or if they do not accept, the serial kernel; the
+// watched draws of an accepted draw decided again (draw_decide_again), the repeat being a second trip through all
+// of this with forward(true).  A hook's BHMM_* code is returned at once.  Two invariants:
+//   1. The serial draw never reads speculative rows: if the segmented draw is not accepted and the rows came from a
+//      segmented forward pass, forward(true) runs first, draw_fwd_segmented and draw_alpha_dev are cleared and the
+//      draws the abandoned rounds recorded are ignored (draw_events stays 0).
+//   2. The segmented draw counts as done only if the last round left no mismatching segment AND no round set
+//      *status_dev (a draw that found no state may belong to a segment drawn again later); otherwise *status_dev is
+//      cleared on the stream before the serial kernel.
+// Sets smp_segmented, smp_seg_mismatch (the first round's count), smp_seg_rounds (the round that ended the loop,
+// DRAW_MAX_ROUNDS + 1: they ran out), draw_events, draw_checked, draw_redone, draw_fwd_segmented and
+// draw_alpha_dev of c->last (both zeroed on exact rows), and ds.smp_W (plan::draw_next_warmup, accepted or not).
+struct SegDraw {
+    std::function<int(bool exact)> forward;   // alpha rows into d_alpha_rm (exact: the serial recursion); leaves
+                                              // last.draw_fwd_segmented / draw_alpha_dev
+    std::function<int(const Segs &)> prepare; // what the family's pass needs beyond the driver's buffers (may be empty)
+    std::function<int(bool fix, const Segs &, const DrawWatch &)> pass; // the segment kernel (fix: a fix-up round)
+    std::function<int()> serial;              // the serial draw kernel
+};
+int seg_draw(bhmm_ctx *c, const SegDraw &f, const double *A, const double *pi, const double *par0, const double *par1,
+             bool segments_allowed, int64_t want_segments, int *status_dev);
 
 // ---- gen_api.hip (more than 64 states) ----
 int gen_alloc(bhmm_ctx *c);

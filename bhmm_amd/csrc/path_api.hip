@@ -80,6 +80,24 @@ int draw_verify_run(bhmm_ctx *c, const double *A, const double *pi, const double
     return BHMM_OK;
 }
 
+int draw_decide_again(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+                      unsigned int count, double thr, const std::function<int()> &repeat, bool *repeated)
+{
+    *repeated = false;
+    bool ok = false;
+    int rc = draw_verify_run(c, A, pi, par0, par1, count, thr, 8 * (int64_t)std::max(c->ds.spec_W, 64), &ok);
+    if (rc || ok)
+        return rc;
+    // a decision does not stand: the whole draw again on exact rows; the counters keep what THIS draw recorded
+    const unsigned int ev = c->last.draw_events, ck = c->last.draw_checked;
+    *repeated = true;
+    rc = repeat();
+    c->last.draw_events = ev;
+    c->last.draw_checked = ck;
+    c->last.draw_redone = 1;
+    return rc;
+}
+
 namespace {
 
 struct Tmp { // scoped raw device allocations for the context-free entry points
@@ -275,19 +293,15 @@ int sample_run(bhmm_ctx *c, const double *A, const double *pi, const double *par
     if (nwatched) {
         // draws inside 64 x the deviation the boundary check measured: decided again on the serial recursion
         // over a long window; if one does not stand, the whole call again on the transfer-matrix rows
-        bool ok = false;
+        bool repeated = false;
         const double thr = c->opt.draw_watch_tol > 0.0 ? c->opt.draw_watch_tol
                                                    : 64.0 * std::max((double)c->last.spec_last_dev, 1e-16);
-        if ((rc = draw_verify_run(c, A, pi, par0, par1, nwatched, thr, 8 * (int64_t)std::max(c->ds.spec_W, 64), &ok)))
+        rc = draw_decide_again(
+            c, A, pi, par0, par1, nwatched, thr,
+            [&] { return sample_run<N>(c, A, pi, par0, par1, u, seed, paths, counts, n0, emis, stats_dev, false, true); },
+            &repeated);
+        if (rc || repeated)
             return rc;
-        if (!ok) {
-            const unsigned int ev = c->last.draw_events, ck = c->last.draw_checked;
-            rc = sample_run<N>(c, A, pi, par0, par1, u, seed, paths, counts, n0, emis, stats_dev, false, true);
-            c->last.draw_events = ev;
-            c->last.draw_checked = ck;
-            c->last.draw_redone = 1;
-            return rc;
-        }
     }
     if (hstatus) {
         set_error("random choice found no state: alpha/A not normalisable (_hidden.c:299-304)");
@@ -468,6 +482,97 @@ int seg_viterbi(bhmm_ctx *c, const SegViterbi &f, const Segs &sg, int64_t seglen
     if (res->accepted && !walked && (rc = f.walks()))
         return rc;
     return BHMM_OK;
+}
+
+// The draws are coupled through the per-step uniforms: a segment that did not continue its successor's state is
+// drawn again from that state until it meets its own earlier path, so an accepted draw is the serial kernel's.
+int seg_draw(bhmm_ctx *c, const SegDraw &f, const double *A, const double *pi, const double *par0, const double *par1,
+             bool segments_allowed, int64_t want_segments, int *status_dev)
+{
+    // one trip: rows, watch, draw.  *nwatched: draws an accepted segmented draw recorded, to be decided again
+    auto trip = [&](bool exact, DrawWatch &watch, unsigned int *nwatched) -> int {
+        *nwatched = 0;
+        int rc;
+        if ((rc = f.forward(exact)))
+            return rc;
+        if (exact) {
+            c->last.draw_fwd_segmented = false;
+            c->last.draw_alpha_dev = 0.0;
+        }
+        // rows of a segmented pass: draws within 64 x the deviation its boundary check measured are recorded
+        if ((rc = draw_watch_prepare(c, c->last.draw_fwd_segmented ? 64.0 * std::max(c->last.draw_alpha_dev, 1e-16) : 0.0,
+                                     watch, nullptr)))
+            return rc;
+        BHMM_HIP(hipMemsetAsync(status_dev, 0, sizeof(int), c->stream));
+        c->last.smp_segmented = false;
+        bool seg_done = false;
+        Segs sg;
+        if (segments_allowed && c->opt.spec_enabled) {
+            if ((rc = wide_path_plan(c, 1, plan::draw_seglen(c->total, want_segments), sg)))
+                return rc;
+            seg_done = sg.nseg > c->K; // (else one segment per trajectory: the serial kernel)
+        }
+        if (seg_done) {
+            if (c->ds.smp_W <= 0)
+                c->ds.smp_W = plan::DRAW_W_START;
+            sg.W = c->ds.smp_W;
+            if ((f.prepare && (rc = f.prepare(sg))) || (rc = c->d_sentry.ensure((size_t)sg.nseg)) ||
+                (rc = c->d_sexit.ensure((size_t)sg.nseg)) || (rc = c->d_vflag.ensure((size_t)sg.nseg)) ||
+                (rc = ensure_specres(c)))
+                return rc;
+            const unsigned int *h = c->h_specres;
+            int round = 0;
+            for (; round <= plan::DRAW_MAX_ROUNDS; ++round) {
+                if ((rc = specres_reset(c)))
+                    return rc;
+                lds_poison(c->stream);
+                if ((rc = f.pass(round > 0, sg, watch)))
+                    return rc;
+                BHMM_HIP(launch(k_wide_smp_check, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg, c->d_sentry.p,
+                                c->d_sexit.p, c->d_vflag.p, c->d_specres.p));
+                if ((rc = specres_read(c, 4, false)))
+                    return rc;
+                BHMM_HIP(hipMemcpyAsync(&c->h_specres[0], status_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+                BHMM_HIP(hipStreamSynchronize(c->stream));
+                if (round == 0)
+                    c->last.smp_seg_mismatch = (int)h[3];
+                if (h[3] == 0)
+                    break;
+            }
+            c->last.smp_seg_rounds = round;
+            // (a draw that found no state may belong to a segment that was drawn again afterwards:
+            // the serial kernel decides such a call)
+            seg_done = h[3] == 0 && h[0] == 0;
+            if (!seg_done)
+                BHMM_HIP(hipMemsetAsync(status_dev, 0, sizeof(int), c->stream));
+            c->ds.smp_W = plan::draw_next_warmup(c->ds.smp_W, c->last.smp_seg_mismatch, sg.nseg);
+            c->last.smp_segmented = seg_done;
+        }
+        if (!seg_done) {
+            if (c->last.draw_fwd_segmented) { // (the serial draw has no watch: it reads rows of the serial recursion)
+                if ((rc = f.forward(true)))
+                    return rc;
+                c->last.draw_fwd_segmented = false;
+                c->last.draw_alpha_dev = 0.0;
+            }
+            return f.serial();
+        }
+        if (watch.count) {
+            BHMM_HIP(hipMemcpyAsync(nwatched, watch.count, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+            BHMM_HIP(hipStreamSynchronize(c->stream));
+        }
+        return BHMM_OK;
+    };
+    DrawWatch watch;
+    unsigned int nwatched = 0;
+    const int rc = trip(false, watch, &nwatched);
+    if (rc || !nwatched)
+        return rc;
+    // watched draws are decided again on the serial recursion over a long window; if one does not stand, the
+    // second trip: the whole draw on the rows of the serial recursion (no watch, nothing to decide again)
+    bool repeated = false;
+    return draw_decide_again(c, A, pi, par0, par1, nwatched, watch.tol, [&] { return trip(true, watch, &nwatched); },
+                             &repeated);
 }
 
 namespace {
@@ -829,23 +934,11 @@ int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double
                     const double *par1, const double *u, uint64_t seed, int32_t *paths,
                     int64_t *counts, int64_t *n0, double *emis, double *stats_dev)
 {
-    // alpha (row-major, any scale per row) in d_alpha_rm; the repeat of a call in which a watched draw did not
-    // stand (draw_verify.hpp) takes the serial recursion
-    int rc = c->draw_force_exact ? wide_forward(c, A, pi, par0, par1) : wide_forward_draw(c, A, pi, par0, par1);
+    WideModel m; // (the forward passes upload the same block again: m stays valid)
+    int rc = wide_model(c, c->kind, A, pi, par0, par1, m);
     if (rc)
         return rc;
-    if (c->draw_force_exact) {
-        c->last.draw_fwd_segmented = false;
-        c->last.draw_alpha_dev = 0.0;
-    }
-    WideModel m;
-    if ((rc = wide_model(c, c->kind, A, pi, par0, par1, m)))
-        return rc;
     const int K = c->K, n = c->n, NP = c->N, GP = 64 / NP;
-    // rows of a segmented pass: draws within 64 x the deviation its boundary check measured are recorded
-    DrawWatch watch;
-    if ((rc = draw_watch_prepare(c, c->last.draw_fwd_segmented ? 64.0 * std::max(c->last.draw_alpha_dev, 1e-16) : 0.0, watch, nullptr)))
-        return rc;
     const size_t nstat = (size_t)n * n + n;
     const size_t esz = c->kind == EMIT_GAUSS ? 3 * (size_t)n
                                              : (c->kind == EMIT_DISC ? (size_t)n * c->M : 0);
@@ -866,98 +959,32 @@ int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double
                                 c->stream));
     }
     BHMM_HIP(hipMemsetAsync(cnt, 0, nstat * sizeof(unsigned long long), c->stream));
-    BHMM_HIP(hipMemsetAsync(status, 0, sizeof(int), c->stream));
     if (esz)
         BHMM_HIP(hipMemsetAsync(ered, 0, esz * sizeof(double), c->stream));
-    const dim3 grid((K + GP - 1) / GP), blk(64);
     const int64_t *off = c->d_offsets.p;
     // parallel over time segments where that fills more of the device than the trajectories do
-    // (k_wide_sample_seg): the draws are coupled through the per-step uniforms, segments that did not
-    // continue their successor's state are drawn again until none is left
-    c->last.smp_segmented = false;
-    bool seg_done = false;
-    if (c->opt.spec_enabled) {
-        const int64_t want = (int64_t)c->opt.smp_seg_per_simd * c->num_simd * GP;
-        const int64_t seglen = std::max<int64_t>((c->total + want - 1) / want, 64);
-        Segs sg;
-        if ((rc = wide_path_plan(c, 1, seglen, sg)))
-            return rc;
-        if (sg.nseg > K) {
-            if (c->ds.smp_W <= 0)
-                c->ds.smp_W = 64;
-            sg.W = c->ds.smp_W;
-            if ((rc = c->d_sentry.ensure((size_t)sg.nseg)) || (rc = c->d_sexit.ensure((size_t)sg.nseg)) ||
-                (rc = c->d_vflag.ensure((size_t)sg.nseg)) || (rc = ensure_specres(c)))
-                return rc;
-            const dim3 sgrid((sg.nseg + GP * WVS_WPB - 1) / (GP * WVS_WPB)), sblk(64 * WVS_WPB);
-            auto *kfirst = NP == 16   ? k_wide_sample_seg<16, false>
-                           : NP == 32 ? k_wide_sample_seg<32, false>
-                                      : k_wide_sample_seg<64, false>;
-            auto *kfix = NP == 16   ? k_wide_sample_seg<16, true>
-                         : NP == 32 ? k_wide_sample_seg<32, true>
-                                    : k_wide_sample_seg<64, true>;
-            const int max_rounds = 16;
-            int round = 0;
-            for (; round <= max_rounds; ++round) {
-                if ((rc = specres_reset(c)))
-                    return rc;
-                lds_poison(c->stream);
-                BHMM_HIP(launch(round == 0 ? kfirst : kfix, sgrid, sblk, 0, c->stream, m, off, sg, c->d_alpha_rm.p, udev, seed,
-                                path, status, c->d_soff.p, c->d_sentry.p, c->d_sexit.p, c->d_vflag.p, watch));
-                BHMM_HIP(launch(k_wide_smp_check, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg, c->d_sentry.p,
-                                c->d_sexit.p, c->d_vflag.p, c->d_specres.p));
-                if ((rc = specres_read(c, 4, false)))
-                    return rc;
-                BHMM_HIP(hipMemcpyAsync(&c->h_specres[0], status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-                BHMM_HIP(hipStreamSynchronize(c->stream));
-                if (round == 0)
-                    c->last.smp_seg_mismatch = (int)c->h_specres[3];
-                if (c->h_specres[3] == 0)
-                    break;
-            }
-            c->last.smp_seg_rounds = round;
-            // (a draw that found no state may belong to a segment that was drawn again afterwards:
-            // the serial kernel decides such a call)
-            seg_done = c->h_specres[3] == 0 && c->h_specres[0] == 0;
-            if (!seg_done)
-                BHMM_HIP(hipMemsetAsync(status, 0, sizeof(int), c->stream));
-            // more than a tenth of the segments left to the fix-up: a longer warm-up next time
-            if ((int64_t)c->last.smp_seg_mismatch * 10 > sg.nseg && c->ds.smp_W < 4096)
-                c->ds.smp_W *= 2;
-            c->last.smp_segmented = seg_done;
-        }
-    }
-    if (!seg_done) {
-        if (c->last.draw_fwd_segmented) { // (the serial draw has no watch: it reads rows of the serial recursion)
-            if ((rc = wide_forward(c, A, pi, par0, par1)))
-                return rc;
-            c->last.draw_fwd_segmented = false;
-            c->last.draw_alpha_dev = 0.0;
-        }
+    // (k_wide_sample_seg), by the protocol of seg_draw; alpha (row-major, any scale per row) in d_alpha_rm
+    SegDraw f;
+    f.forward = [&](bool exact) {
+        return exact ? wide_forward(c, A, pi, par0, par1) : wide_forward_draw(c, A, pi, par0, par1);
+    };
+    f.pass = [&](bool fix, const Segs &sg, const DrawWatch &watch) -> int {
+        const dim3 sgrid((sg.nseg + GP * WVS_WPB - 1) / (GP * WVS_WPB)), sblk(64 * WVS_WPB);
+        auto *k = NP == 16   ? (fix ? k_wide_sample_seg<16, true> : k_wide_sample_seg<16, false>)
+                  : NP == 32 ? (fix ? k_wide_sample_seg<32, true> : k_wide_sample_seg<32, false>)
+                             : (fix ? k_wide_sample_seg<64, true> : k_wide_sample_seg<64, false>);
+        BHMM_HIP(launch(k, sgrid, sblk, 0, c->stream, m, off, sg, c->d_alpha_rm.p, udev, seed, path, status, c->d_soff.p,
+                        c->d_sentry.p, c->d_sexit.p, c->d_vflag.p, watch));
+        return BHMM_OK;
+    };
+    f.serial = [&]() -> int {
         auto *ks = NP == 16 ? k_wide_sample_path<16> : NP == 32 ? k_wide_sample_path<32> : k_wide_sample_path<64>;
-        BHMM_HIP(launch(ks, grid, blk, 0, c->stream, m, off, K, c->d_alpha_rm.p, udev, seed, path, status, c->d_soff.p));
-    } else if (watch.count) {
-        // watched draws are decided again on the serial recursion over a long window; if one does not stand, the
-        // whole call again on the rows of the serial recursion
-        unsigned int nwatched = 0;
-        BHMM_HIP(hipMemcpyAsync(&nwatched, watch.count, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-        BHMM_HIP(hipStreamSynchronize(c->stream));
-        if (nwatched) {
-            bool ok = false;
-            if ((rc = draw_verify_run(c, A, pi, par0, par1, nwatched, watch.tol, 8 * (int64_t)std::max(c->ds.spec_W, 64), &ok)))
-                return rc;
-            if (!ok) {
-                const unsigned int ev = c->last.draw_events, ck = c->last.draw_checked;
-                c->draw_force_exact = true;
-                rc = wide_sample_run(c, A, pi, par0, par1, u, seed, paths, counts, n0, emis, stats_dev);
-                c->draw_force_exact = false;
-                c->last.draw_events = ev;
-                c->last.draw_checked = ck;
-                c->last.draw_redone = 1;
-                return rc;
-            }
-        }
-    }
+        BHMM_HIP(launch(ks, dim3((K + GP - 1) / GP), dim3(64), 0, c->stream, m, off, K, c->d_alpha_rm.p, udev, seed, path,
+                        status, c->d_soff.p));
+        return BHMM_OK;
+    };
+    if ((rc = seg_draw(c, f, A, pi, par0, par1, true, (int64_t)c->opt.smp_seg_per_simd * c->num_simd * GP, status)))
+        return rc;
     if (counts || n0 || emis || stats_dev) {
         // the per-trajectory emission table in LDS, or -- alphabets too large for it -- in epart itself
         const bool gtab = c->kind == EMIT_DISC &&

@@ -3,7 +3,8 @@
 // (bhmm_score, bhmm_filter: plan_pass, uploaded by seg_host.hpp), the ranges of a budgeted workspace of the posterior
 // calls (smooth_ranges, smooth_tile_ranges), and the forgetting probe every family
 // warms up by: where it samples (probe_starts) and how its curve is read (curve_last, warmup_of,
-// warmup_wide_of), and the acceptance protocol of a verified pass (two_attempts, doubled).  Pure C++ (no HIP), so
+// warmup_wide_of), the acceptance protocol of a verified pass (two_attempts, doubled), and the integer rules of the
+// segment-parallel backward draw (draw_seglen, draw_next_warmup).  Pure C++ (no HIP), so
 // the same code runs under -fsanitize=address,undefined in the CPU sanitizer build
 // (oracle/Makefile `asan`); the .hip files only allocate and upload what these functions return.
 #pragma once
@@ -394,6 +395,19 @@ int two_attempts(int W, int Wcap, int *fallbacks, Pass pass, bool *verified)
     }
     return 0;
 }
+
+// ---- the integer rules of the segment-parallel backward draw (path_api.hip: seg_draw) ----
+// Every warm-up is exact (segments that did not continue their successor's state are drawn again), so these only
+// trade warm-up steps against fix-up rounds.  Segment length: `want` (>= 1) segments over the observation set's
+// `total` steps, none shorter than DRAW_SEGLEN_MIN.  Warm-up: DRAW_W_START on new observations; the next call's
+// is twice as long while the first round left more than a tenth of the `nseg` segments to the fix-up, up to
+// DRAW_W_MAX.  DRAW_MAX_ROUNDS fix-up rounds, then the serial kernel.
+constexpr int64_t DRAW_SEGLEN_MIN = 64;
+constexpr int DRAW_W_START = 64;
+constexpr int DRAW_W_MAX = 4096;
+constexpr int DRAW_MAX_ROUNDS = 16;
+inline int64_t draw_seglen(int64_t total, int64_t want) { return std::max((total + want - 1) / want, DRAW_SEGLEN_MIN); }
+inline int draw_next_warmup(int W, int64_t mismatch, int64_t nseg) { return mismatch * 10 > nseg && W < DRAW_W_MAX ? 2 * W : W; }
 
 // For every segment of the plan with `seglen`: the start of a segment of the twice-as-fine plan
 // strictly inside it (-1: none).  Cuts the trajectories exactly like plan_segments(.., 1).

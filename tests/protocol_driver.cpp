@@ -8,6 +8,10 @@
 //     prints "call W" per call of the pass, then "counter C", "verified 0|1" and "rc R"
 //   protocol_driver doubled W CAP      prints "doubled D"
 //   protocol_driver cap                prints "tile SCORE_TILE_W_MAX"
+// and the integer rules of the segment-parallel backward draw (draw_seglen, draw_next_warmup):
+//   protocol_driver draw                                prints the four constants
+//   protocol_driver draw_seglen TOTAL WANT              prints "seglen L"
+//   protocol_driver draw_next_warmup W MISMATCH NSEG    prints "warmup W'"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -34,6 +38,19 @@ int main(int argc, char **argv)
     }
     if (mode == "doubled" && argc == 4) {
         printf("doubled %d\n", doubled(atoi(argv[2]), cap_of(argv[3])));
+        return 0;
+    }
+    if (mode == "draw") {
+        printf("seglen_min %lld\nstart %d\nmax %d\nrounds %d\n", (long long)DRAW_SEGLEN_MIN, DRAW_W_START, DRAW_W_MAX,
+               DRAW_MAX_ROUNDS);
+        return 0;
+    }
+    if (mode == "draw_seglen" && argc == 4) {
+        printf("seglen %lld\n", (long long)draw_seglen(atoll(argv[2]), atoll(argv[3])));
+        return 0;
+    }
+    if (mode == "draw_next_warmup" && argc == 5) {
+        printf("warmup %d\n", draw_next_warmup(atoi(argv[2]), atoll(argv[3]), atoll(argv[4])));
         return 0;
     }
     if (mode != "run" || argc != 6)

@@ -1,7 +1,8 @@
 """CPU: the acceptance protocol every verified pass of bhmm_filter, bhmm_posterior_decode and
 bhmm_posterior_marginals runs (csrc/plan.hpp: two_attempts), and the doubling of a warm-up bhmm_score shares with it
 (doubled).  tests/protocol_driver.cpp runs two_attempts with a scripted pass and prints the warm-up of every call, the
-fallback counter, `verified` and the return code; every expectation is an exact integer."""
+fallback counter, `verified` and the return code; every expectation is an exact integer.  The same driver prints
+the integer rules of the segment-parallel backward draw (draw_seglen, draw_next_warmup; path_api.hip: seg_draw)."""
 import os
 import shutil
 import subprocess
@@ -79,3 +80,44 @@ def test_caps(driver):
     assert _out(driver, "doubled", 786432, "tile") == ["doubled %d" % SCORE_TILE_W_MAX]
     assert _out(driver, "doubled", 0, "tile") == ["doubled 0"]
     assert _out(driver, "doubled", 288, CAP) == ["doubled 576"]
+
+
+def _seglen(driver, total, want):
+    return int(_out(driver, "draw_seglen", total, want)[0].split()[1])
+
+
+def _next_warmup(driver, W, mismatch, nseg):
+    return int(_out(driver, "draw_next_warmup", W, mismatch, nseg)[0].split()[1])
+
+
+def test_draw_constants(driver):
+    assert _out(driver, "draw") == ["seglen_min 64", "start 64", "max 4096", "rounds 16"]
+
+
+def test_draw_segment_length(driver):
+    """max(ceil(total / want), 64)"""
+    want = 2048
+    for total in (0, 1, want, want + 1, 64 * want):
+        assert _seglen(driver, total, want) == 64                    # the floor
+    assert _seglen(driver, 64 * want + 1, want) == 65                # rounds up
+    assert _seglen(driver, 100 * want, want) == 100
+    assert _seglen(driver, 100 * want + 1, want) == 101
+    assert _seglen(driver, 1 << 31, 1024) == 1 << 21                 # a 2^31-step total
+    assert _seglen(driver, (1 << 31) + 1, 1024) == (1 << 21) + 1
+    assert _seglen(driver, 1 << 31, 1) == 1 << 31                    # (a length no int holds)
+    assert _seglen(driver, 1, 1) == 64 and _seglen(driver, 65, 1) == 65
+
+
+def test_draw_next_warmup(driver):
+    """twice the warm-up while more than a tenth of the segments were left to the fix-up, up to 4096"""
+    assert _next_warmup(driver, 64, 0, 147) == 64
+    assert _next_warmup(driver, 64, 10, 100) == 64                   # exactly a tenth: not more than a tenth
+    assert _next_warmup(driver, 64, 11, 100) == 128
+    assert _next_warmup(driver, 64, 1, 9) == 128
+    assert _next_warmup(driver, 2048, 50, 100) == 4096
+    assert _next_warmup(driver, 4096, 50, 100) == 4096               # stays
+    assert _next_warmup(driver, 4096, 100, 100) == 4096
+    # mismatch * 10 does not fit an int: 3e9 > 2^31 - 1 segments doubles, 2147483640 does not
+    assert _next_warmup(driver, 64, 300000000, 2147483647) == 128
+    assert _next_warmup(driver, 64, 214748364, 2147483647) == 64
+    assert _next_warmup(driver, 64, 214748365, 2147483647) == 128
