@@ -32,6 +32,8 @@ FLAG_SINGLE = 2        # the caller accepts a single-precision E-step (up to 8 s
 
 MARG_F32 = 1           # bhmm_posterior_marginals: rows of float
 MARG_DEVICE = 2        # ... out is a device pointer
+PAIR_F32 = 1           # bhmm_posterior_transitions: rows of float
+PAIR_DEVICE = 2        # ... out is a device pointer
 FILT_F32 = 1           # bhmm_filter: both outputs of float
 FILT_DEVICE = 2        # ... both outputs are device pointers
 DWELL_COLS = 5         # bhmm_path_runs / bhmm_decode_runs: columns of the dwell table (BHMM_DWELL_COLS)
@@ -83,6 +85,11 @@ SIGNATURES = {
                                              c_void_p, ctypes.c_int, c_void_p]),
     "bhmm_posterior_marginals": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                                 c_double_p, ctypes.c_int, c_void_p, ctypes.c_int]),
+    "bhmm_posterior_transitions": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                  c_double_p, ctypes.c_int, c_void_p, ctypes.c_int]),
+    "bhmm_pair_set_option": (ctypes.c_int, [c_void_p, ctypes.c_char_p, ctypes.c_double]),
+    "bhmm_pair_get_option": (ctypes.c_int, [c_void_p, ctypes.c_char_p, c_double_p]),
+    "bhmm_pair_release": (ctypes.c_int, [c_void_p]),
     "bhmm_filter": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int,
                                    c_void_p, c_void_p, ctypes.c_int]),
     "bhmm_viterbi_batch": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,

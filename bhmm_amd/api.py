@@ -288,6 +288,49 @@ def posterior_marginals(observations, model, lag=1, weights=None, dtype=np.float
         eng.close()
 
 
+def posterior_transitions(observations, model, lag=1, weights=None, dtype=np.float64, **engine_kwargs):
+    """Pair posteriors of `observations` under one HMM (bhmm_posterior_transitions): per trajectory the
+    probability of a jump at every step, P(s_t != s_t+1 | O), as an array of length T_k - 1 -- where the jumps
+    are and how sure the model is of them -- or with `weights` ((nstates, nstates, Q), 1 <= Q <= 8: unit pair
+    matrices for the expected A -> B events, any few pair weightings) the (T_k - 1, Q) array
+    sum_ij xi_t(i, j) weights[i, j, q].  dtype float64 or float32.  The arrays are views into one array.  lag > 1
+    works on the lagged views (lag_observations), one result per view.  Gaussian and discrete models of up to 8
+    states run one fused kernel; more states run filter_states and posterior_marginals on the device, each on the path
+    it picks itself, and a kernel over their rows.  engine_kwargs: device (default 0)."""
+    from .engine import Engine
+    from .estimators.maximum_likelihood import model_tuple
+    if not isinstance(model, HMM):
+        raise TypeError("model must be an HMM object")
+    if len(observations) == 0:
+        raise ValueError("no observations")
+    output = model.output_model.model_type
+    nstates = model.nstates
+    nsymbols = model.output_model.nsymbols if output == 'discrete' else 0
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError("dtype must be float64 or float32")
+    if weights is not None:
+        w = np.asarray(weights)
+        if w.ndim != 3 or w.shape[:2] != (nstates, nstates) or not 1 <= w.shape[2] <= 8:
+            raise ValueError("weights must be (%d, %d, Q) with 1 <= Q <= 8" % (nstates, nstates))
+        if not np.all(np.isfinite(np.asarray(w, dtype=np.float64))):
+            raise ValueError("weights has a non-finite entry")
+    device = engine_kwargs.pop('device', 0)
+    if engine_kwargs:
+        raise TypeError("unexpected keyword arguments: %s" % ", ".join(sorted(engine_kwargs)))
+    if lag > 1:
+        observations = lag_observations(observations, lag)
+    eng = Engine(device)
+    try:
+        if output == 'discrete':
+            obs = [np.asarray(o) for o in observations]
+            eng.set_observations('discrete', obs, nstates, nsymbols=nsymbols)
+        else:
+            eng.set_observations(output, [np.asarray(o, dtype=np.float64) for o in observations], nstates)
+        return eng.posterior_transitions(*model_tuple(model), weights=weights, dtype=dtype)
+    finally:
+        eng.close()
+
+
 def filter_states(observations, model, lag=1, weights=None, dtype=np.float64, probabilities=True, increments=True,
                   **engine_kwargs):
     """Filtered state probabilities and per-step likelihood of `observations` under one HMM (bhmm_filter):

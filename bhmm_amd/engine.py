@@ -98,6 +98,9 @@ class Engine(object):
 
     def close(self):
         if getattr(self, "_h", None):
+            if getattr(self, "_pair_used", False):      # (the state posterior_transitions keeps beside the context)
+                self._L.bhmm_pair_release(self._h)
+                self._pair_used = False
             self._L.bhmm_ctx_destroy(self._h)
             self._h = None
 
@@ -201,10 +204,17 @@ class Engine(object):
         return self._L.bhmm_ctx_stream(self._h)
 
     def set_option(self, name, value):
+        if name.startswith("pair_"):        # posterior_transitions keeps its options itself (bhmm_pair_set_option)
+            self._pair_used = True
+            _lib.check(self._L.bhmm_pair_set_option(self._h, name.encode(), float(value)))
+            return
         _lib.check(self._L.bhmm_ctx_set_option(self._h, name.encode(), float(value)))
 
     def get_option(self, name):
         v = ctypes.c_double(0.0)
+        if name.startswith("pair_"):        # (reading keeps nothing beside the context)
+            _lib.check(self._L.bhmm_pair_get_option(self._h, name.encode(), ctypes.byref(v)))
+            return v.value
         _lib.check(self._L.bhmm_ctx_get_option(self._h, name.encode(), ctypes.byref(v)))
         return v.value
 
@@ -451,6 +461,72 @@ class Engine(object):
         if rows is None:
             return None
         return [rows[self.offsets[k]:self.offsets[k + 1]] for k in range(len(self.lengths))]
+
+    # -- pair posteriors -------------------------------------------------------------------
+    def posterior_transitions(self, A, pi, par0=None, par1=None, weights=None, dtype=np.float64, out=None):
+        """Pair posteriors xi_t(i, j) = P(s_t = i, s_t+1 = j | O) of every transition t -> t+1 of every loaded
+        trajectory under one model (bhmm_posterior_transitions), in one of two forms.  weights=None, the jump
+        form: a list of 1-d arrays of length T_k - 1, P(s_t != s_t+1 | O) -- the soft counterpart of the run
+        boundaries decode_runs returns.  weights of shape (nstates, nstates, Q), 1 <= Q <= 8, the projected
+        form: a list of (T_k - 1, Q) arrays, sum_ij xi_t(i, j) weights[i, j, q], accumulated with i the outer
+        and j the inner loop in ascending order in fp64 (the jump form is bitwise the projection on the
+        off-diagonal 0/1 mask).  The arrays are views into ONE array of sum(T_k) rows in which the last row of
+        every trajectory is zero; the views leave that row out.  dtype: float64 or float32 (the rounded float64
+        result).  out: as for posterior_marginals -- None, a C-contiguous numpy array of that dtype and
+        sum(T_k) * Q' elements (Q' = 1 or Q), an object with data_ptr() / is_cuda (a torch tensor), or an
+        integer device address on this engine's GPU aligned to 16 bytes (then None is returned).  Rows left on
+        the device are complete in the order of the engine's stream (sync()).  Up to 8 states (gaussian,
+        discrete) one fused kernel leaves the state of every other call untouched (get_option("pair_path") == 1;
+        options pair_W, pair_ws_mb, pair_fused, read-only pair_fallbacks).  Everything else (9 states and more,
+        explicit pobs, pair_fused 0) runs filter_states and posterior_marginals on the device and one kernel
+        over their rows (pair_path 0), and counts as those two calls."""
+        self._check_model(A, pi, par0, par1)
+        n = self.nstates
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError("dtype must be float64 or float32, not %s" % dtype.name)
+        W, Q = None, 0
+        if weights is not None:
+            W = np.ascontiguousarray(weights, dtype=np.float64)
+            if W.ndim != 3 or W.shape[0] != n or W.shape[1] != n or not 1 <= W.shape[2] <= 8:
+                raise ValueError("weights must be (%d, %d, Q) with 1 <= Q <= 8, not %r" % (n, n, np.shape(weights)))
+            if not np.all(np.isfinite(W)):
+                raise ValueError("weights has a non-finite entry")
+            Q = W.shape[2]
+        Qp = Q if Q else 1
+        total = int(self.offsets[-1])
+        flags = _lib.PAIR_F32 if dtype == np.float32 else 0
+        rows = None
+        if out is None:
+            out = np.empty((total, Qp), dtype=dtype)
+        if isinstance(out, np.ndarray):
+            if out.dtype != dtype or out.size != total * Qp or not out.flags.c_contiguous:
+                raise ValueError("out must be a C-contiguous %s array of sum(T_k) * %d = %d elements"
+                                 % (dtype.name, Qp, total * Qp))
+            ptr, rows = out.ctypes.data, out.reshape(total, Qp)
+        elif hasattr(out, 'data_ptr'):
+            if out.numel() != total * Qp or out.element_size() != dtype.itemsize or not out.is_contiguous() \
+                    or not out.is_floating_point():
+                raise ValueError("out must be a contiguous %s tensor of sum(T_k) * %d = %d elements"
+                                 % (dtype.name, Qp, total * Qp))
+            if out.is_cuda:
+                if out.device.index != self.device:
+                    raise ValueError("out lives on another GPU than this engine")
+                flags |= _lib.PAIR_DEVICE
+            ptr, rows = out.data_ptr(), out.view(total, Qp)
+        else:
+            ptr = int(out)
+            flags |= _lib.PAIR_DEVICE
+        if (flags & _lib.PAIR_DEVICE) and ptr % 16:
+            raise ValueError("a device buffer must be aligned to 16 bytes")
+        A, pi, p0, p1 = self._model_ptrs(A, pi, par0, par1)
+        self._pair_used = True
+        _lib.check(self._L.bhmm_posterior_transitions(self._h, A, pi, p0, p1, _lib.dp(W), Q,
+                                                      ctypes.c_void_p(int(ptr)), flags))
+        if rows is None:
+            return None
+        views = [rows[self.offsets[k]:max(self.offsets[k + 1] - 1, self.offsets[k])] for k in range(len(self.lengths))]
+        return views if Q else [v[:, 0] for v in views]
 
     # -- filtered state probabilities ----------------------------------------------------
     def _filter_out(self, out, what, total, width, dtype):

@@ -228,6 +228,25 @@ class MaximumLikelihoodEstimator(object):
                 out[k] = rows[j]
         return out
 
+    def posterior_transitions(self, weights=None, dtype=np.float64):
+        """Pair posteriors of the estimator's observations under the parameters of the last E-step
+        (Engine.posterior_transitions): a list in the caller's trajectory order of arrays of length T_k - 1,
+        P(s_t != s_t+1 | O), or with `weights` ((N, N, Q), 1 <= Q <= 8) of (T_k - 1, Q) arrays
+        sum_ij xi_t(i, j) weights[i, j, q]; dtype float64 or float32.  With a process_group every rank fills
+        the trajectories it holds and the entries of the others are None (local_trajectories lists the ones
+        filled); there is no collective.  Up to 8 states the EM state of the engine stays untouched; more
+        states run filter_states and posterior_marginals on the device -- an E-step where posterior_marginals runs one
+        (its generic path), nothing of the EM state where it takes a path of its own -- and a kernel over their rows."""
+        if self._estep_model is None:
+            raise RuntimeError('no E-step has run yet: call fit() or em_step() first')
+        out = [None] * self._nobs
+        if self._mine:
+            A, pi, par0, par1 = self._estep_model
+            rows = self._engine.posterior_transitions(A, pi, par0, par1, weights=weights, dtype=dtype)
+            for j, k in enumerate(self._mine):
+                out[k] = rows[j]
+        return out
+
     def filter_states(self, weights=None, dtype=np.float64, probabilities=True, increments=True):
         """Filtered state probabilities and per-step likelihood of the estimator's observations under the
         parameters of the last E-step (Engine.filter_states): (rows, logc), each a list in the caller's

@@ -15,7 +15,7 @@ from ..util import config
 
 __all__ = ['set_implementation', 'forward', 'backward', 'state_probabilities', 'state_counts',
            'transition_counts', 'viterbi', 'sample_path', 'posterior_decode', 'posterior_marginals',
-           'filter_states']
+           'posterior_transitions', 'filter_states']
 
 __IMPL_HIP__ = 2
 __impl__ = __IMPL_HIP__
@@ -225,6 +225,36 @@ def posterior_marginals(A, pobs, pi, weights=None, dtype=np.float64):
     try:
         eng.set_observations('explicit', [p_], N)
         return eng.posterior_marginals(A_, pi_, weights=weights, dtype=dtype)[0]
+    finally:
+        eng.close()
+
+
+def posterior_transitions(A, pobs, pi, weights=None, dtype=np.float64):
+    """Pair posteriors of one trajectory given its pobs rows, in one call: the array of length T - 1 of
+    P(s_t != s_t+1 | O), or with `weights` ((N, N, Q), 1 <= Q <= 8) the (T - 1, Q) array
+    sum_ij xi_t(i, j) weights[i, j, q] -- per step what the reference sums over time in transition_counts
+    (hidden/api.py:213-249); dtype float64 or float32.  Explicit pobs take the generic path of
+    bhmm_posterior_transitions: a filter call and a marginals call on the device, then a kernel over their rows."""
+    _check_dtype()
+    A_, p_, pi_ = _lib.f64(A), _lib.f64(pobs), _lib.f64(pi)
+    N = A_.shape[0] if A_.ndim == 2 else -1
+    if A_.ndim != 2 or A_.shape != (N, N) or pi_.shape != (N,) or p_.ndim != 2 or p_.shape[1] != N:
+        raise ValueError('A must be (N, N), pi (N,) and pobs (T, N)')
+    if p_.shape[0] < 1:
+        raise ValueError('pobs has no rows')
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError('dtype must be float64 or float32')
+    if weights is not None:
+        w = np.asarray(weights)
+        if w.ndim != 3 or w.shape[:2] != (N, N) or not 1 <= w.shape[2] <= 8:
+            raise ValueError('weights must be (N, N, Q) with 1 <= Q <= 8')
+        if not np.all(np.isfinite(np.asarray(w, dtype=np.float64))):
+            raise ValueError('weights has a non-finite entry')
+    from ..engine import Engine
+    eng = Engine(0)
+    try:
+        eng.set_observations('explicit', [p_], N)
+        return eng.posterior_transitions(A_, pi_, weights=weights, dtype=dtype)[0]
     finally:
         eng.close()
 

@@ -265,6 +265,60 @@ int bhmm_posterior_decode(bhmm_ctx *ctx, const double *A, const double *pi, cons
 int bhmm_posterior_marginals(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0,
                              const double *par1, const double *V, int Q, void *out, int flags);
 
+/* Pair posteriors of every step of every loaded trajectory under ONE model (A, pi, par0, par1 as for
+   bhmm_posterior_marginals; validated the same way): xi_t(i,j) = P(s_t = i, s_t+1 = j | O) of the transition
+   t -> t+1, the quantity whose sum over t is the count matrix of the E-step, in one of two forms.
+   out is trajectory-major, out[(offset_k + t) * Q' + q], total rows; row t belongs to the pair (t, t+1) and the
+   last row of every trajectory, t = T_k - 1, is written as zeros:
+     W == NULL, Q == 0 (the jump form): Q' = 1, the row is P(s_t != s_t+1 | O) = sum_{i != j} xi_t(i,j);
+     W[N*N*Q] row-major (W[(i*N + j)*Q + q]), 1 <= Q <= 8 (the projected form): Q' = Q, the row is
+       sum_i sum_j xi_t(i,j) * W[i][j][q].
+   The unnormalised pairs x_ij are accumulated in fp64 with i the OUTER and j the INNER loop, both in ASCENDING
+   order (fused multiply-add), and normalised by ONE multiplication with the reciprocal of sum_ij x_ij (summed in
+   the same order).  The jump form is by definition, and bitwise, the projection on the off-diagonal 0/1 mask with
+   Q = 1 -- the same order, the diagonal terms added as zero; it only leaves out the loads of W.  Full N x N rows
+   are not handed out (N * N * 8 bytes per step): eight pair columns per call.
+   flags: BHMM_PAIR_F32    rows of float instead of double (the conversion is the last operation: the float
+                           result is the rounded double result);
+          BHMM_PAIR_DEVICE out is a device pointer on the context's device, aligned to 16 bytes: the kernels
+                           write it directly, nothing is copied, and the rows are complete in the order of
+                           the context's stream (bhmm_ctx_sync, or work enqueued on bhmm_ctx_stream).
+   Without BHMM_PAIR_DEVICE out is a host buffer of total * Q' values: the rows are staged on the device
+   (BHMM_ERR_NO_MEM if they do not fit; nothing is truncated) and cross the link in ONE copy, and the call is
+   synchronous.  A trajectory of probability zero is out of contract: its rows are whatever
+   bhmm_posterior_marginals would give (NaN).
+   Up to 8 states (gaussian, discrete), the fused path (pair_path 1): the forward-backward sweep of
+   bhmm_posterior_marginals with the pair row hanging off the backward sweep -- alpha_t(i) A_ij p_t+1(j) beta_t+1(j)
+   from the stored alpha row and the vector the backward step forms anyway -- the same verified warm-up boundaries
+   and retry protocol; the pair that straddles a chunk edge rests on the verified entry vector of the later chunk.
+   Nothing of the state that E-step, Viterbi, sampling, scoring, decoding, marginals and filter calls use is read or
+   written; the context itself is not changed either: the call keeps its buffers, options and counters in a
+   state of its own beside the context, made at the first call or option and released by bhmm_pair_release.
+   Options, set and read by bhmm_pair_set_option / bhmm_pair_get_option (not by bhmm_ctx_set_option): pair_W
+   (warm-up in steps, 0 = measured), pair_ws_mb (budget of the alpha-row workspace in MiB, default 8192,
+   0 = unbounded; the result does not depend on it), pair_fused (default 1; 0: never take the fused path);
+   read-only pair_fallbacks (calls whose boundaries did not verify at the first warm-up: they run again with twice
+   the warm-up, then take the generic path) and pair_path (first pass of the last call: 1 fused, 0 generic).
+   Generic path (9 states and more, explicit pobs, pair_fused 0, fused calls that did not verify): with f_t the
+   filtered row, xi_t(i,j) = f_t(i) A_ij gamma_t+1(j) / pred_j, pred_j = sum_i f_t(i) A_ij (a term with pred_j == 0
+   is zero) -- a bhmm_filter and a bhmm_posterior_marginals through their own entry points, each on the path it
+   picks for the class, fp64 rows of both kept on the device (2 * total * N * 8 bytes, BHMM_ERR_NO_MEM if they do
+   not fit), then one kernel over the steps, O(N * N) each.  It counts as whatever those two calls count as for the
+   context: at 9 states and more (unless bhmm_posterior_marginals takes a path of its own) an E-step. */
+#define BHMM_PAIR_F32 1
+#define BHMM_PAIR_DEVICE 2
+int bhmm_posterior_transitions(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0,
+                               const double *par1, const double *W, int Q, void *out, int flags);
+/* The options of bhmm_posterior_transitions (names above; BHMM_ERR_INVALID for an unknown or read-only one), and
+   the release of the state it keeps for ctx: call it before bhmm_ctx_destroy on every context that made a pair
+   call or set a pair option (it waits for the device; a context without such a state: no-op; reading an option of
+   such a context gives the default and keeps nothing).  bhmm_ctx_destroy does NOT release it: without this call the
+   state's device buffers stay allocated until the process ends.  A state left behind is never used for another
+   context: one found under the address of a context with another device or stream is dropped first. */
+int bhmm_pair_set_option(bhmm_ctx *ctx, const char *name, double value);
+int bhmm_pair_get_option(bhmm_ctx *ctx, const char *name, double *value);
+int bhmm_pair_release(bhmm_ctx *ctx);
+
 /* Filtered state probabilities and one-step predictive log-densities of every step of every loaded trajectory
    under ONE model (A, pi, par0, par1 as for bhmm_posterior_marginals; validated the same way): the forward pass
    of bhmm_score with its rows handed out.
