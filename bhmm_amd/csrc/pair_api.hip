@@ -14,7 +14,10 @@
 //
 // Everything else (9 states and more, explicit pobs, pair_fused 0, a fused call that did not verify; pair_path 0):
 // bhmm_filter and bhmm_posterior_marginals through their public entry points, each leaving fp64 rows in a device
-// buffer of the call's own state, then k_pair_rows over the steps with a device copy of A.  That IS a filter call and a
+// buffer of the call's own state, then the row kernel over the steps: k_pair_rows with a device copy of A (one thread
+// per step), or k_pair_tile (pair_tile_kernels.hpp, up to 128 states: 16 steps a matrix-core tile, the matrices in its
+// operand order formed here and kept like A and W) -- option pair_rows 0 / 1, -1 by class; read-only
+// pair_rows_kernel says which one the last generic pass ran; pair_path is 0 for both.  That IS a filter call and a
 // marginals call for the context's state, exactly like a caller's own: where bhmm_posterior_marginals takes its
 // generic path (9 states and more unless its time-segmented or matrix-core path is on, explicit pobs) that is an
 // E-step; on its paths 1 to 3 it touches no other call's state.
@@ -145,10 +148,26 @@ int run_n(bhmm_ctx *c, const double *A, const double *pi, const double *par0, co
                                  : Fused<N, EMIT_DISC>::run(c, A, pi, par0, par1, b, o, verified);
 }
 
+// pair_rows -1: k_pair_tile where it was faster than k_pair_rows in EVERY shape measured for the class (DESIGN.md
+// section 21: 16, 32, 64 states and 100, 128 states, jump form, Q = 2 and Q = 8), the rule of smooth_wide / smooth_tile
+constexpr bool PAIR_TILE_AUTO_WIDE = true; // 9 .. 64 states
+constexpr bool PAIR_TILE_AUTO_TILE = true; // 65 .. 128 states
+
+bool tile_takes(const bhmm_ctx *c, const PairState &b)
+{
+    if (c->n > PAIR_TILE_MAX_N || b.opt_rows == 0)
+        return false;
+    if (b.opt_rows > 0)
+        return true;
+    return c->n > 64 ? PAIR_TILE_AUTO_TILE : c->n > 8 ? PAIR_TILE_AUTO_WIDE : false;
+}
+
 // the generic path: filtered rows and posterior rows by the calls that hand them out, then one kernel over the steps
 int generic(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, PairState &b,
             const PairOut &o)
 {
+    const bool tile = tile_takes(c, b);
+    b.rows_kernel = tile ? 1 : 0;
     if (c->total == 0)
         return BHMM_OK;
     const size_t rows = (size_t)c->total * c->n;
@@ -165,6 +184,22 @@ int generic(bhmm_ctx *c, const double *A, const double *pi, const double *par0, 
     if ((rc = bhmm_filter(c, A, pi, par0, par1, nullptr, 0, b.filt.p, nullptr, BHMM_FILT_DEVICE)) ||
         (rc = bhmm_posterior_marginals(c, A, pi, par0, par1, nullptr, 0, b.gam.p, BHMM_MARG_DEVICE)))
         return rc;
+    if (tile) {
+        // the matrices in operand order, formed again from A and the padded W of this call: the same A, W, Q and
+        // form as the last time give the same vector, and then nothing is uploaded or waited for
+        std::vector<double> ops;
+        pair_tile_operands(A, o.Q > 0 ? b.W_host.data() : nullptr, c->n, o.Q, ops);
+        const bool regrown = ops.size() > b.Bop.n;
+        if ((rc = b.Bop.ensure(ops.size())))
+            return rc;
+        if (regrown || ops != b.Bop_host) {
+            BHMM_HIP(hipStreamSynchronize(c->stream)); // (an earlier upload may still read the kept copy)
+            b.Bop_host.swap(ops); // (kept: the copy may still be read when this call returns)
+            BHMM_HIP(hipMemcpyAsync(b.Bop.p, b.Bop_host.data(), b.Bop_host.size() * sizeof(double),
+                                    hipMemcpyHostToDevice, c->stream));
+        }
+        return pair_tile_rows(c, b, o); // (pair_tile.hip)
+    }
     const dim3 grid((unsigned)((c->total + 63) / 64)), block(64);
     if (o.f32)
         BHMM_HIP(launch(k_pair_rows<float>, grid, block, 0, c->stream, b.filt.p, b.gam.p, b.A.p, c->n, c->total, c->K,
@@ -257,7 +292,11 @@ int bhmm_pair_set_option(bhmm_ctx *c, const char *name, double value)
         b.opt_ws_mb = (int)value;
     } else if (n == "pair_fused") // 0: never the fused path (the generic route answers every call)
         b.opt_fused = value != 0.0;
-    else
+    else if (n == "pair_rows") { // row kernel of the generic path: 0 k_pair_rows, 1 k_pair_tile (n <= 128), -1 by class
+        if (value != -1.0 && value != 0.0 && value != 1.0)
+            return invalid_arg("pair_rows is -1, 0 or 1");
+        b.opt_rows = (int)value;
+    } else
         return invalid_arg("unknown or read-only option: " + n);
     return BHMM_OK;
 }
@@ -280,6 +319,10 @@ int bhmm_pair_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = b.fallbacks;
     else if (n == "pair_path") // first pass of the last call: 1 fused kernel, 0 filter + marginals + pair rows
         *value = b.path;
+    else if (n == "pair_rows")
+        *value = b.opt_rows;
+    else if (n == "pair_rows_kernel") // row kernel of the last generic pass: 0 k_pair_rows, 1 k_pair_tile
+        *value = b.rows_kernel;
     else
         return invalid_arg("unknown option: " + n);
     return BHMM_OK;

@@ -479,7 +479,12 @@ class Engine(object):
         discrete) one fused kernel leaves the state of every other call untouched (get_option("pair_path") == 1;
         options pair_W, pair_ws_mb, pair_fused, read-only pair_fallbacks).  Everything else (9 states and more,
         explicit pobs, pair_fused 0) runs filter_states and posterior_marginals on the device and one kernel
-        over their rows (pair_path 0), and counts as those two calls."""
+        over their rows (pair_path 0), and counts as those two calls.  That row kernel is k_pair_rows (one thread
+        per step, the order above) or, up to 128 states, k_pair_tile on the fp64 matrix cores (16 steps a tile;
+        it sums in a fixed tree order, is repeatable bitwise and is held to the same bound against the oracle, not
+        to bitwise equality with k_pair_rows): set_option("pair_rows", 0 / 1) forces one or the other (1: every
+        kind up to 128 states), the default -1 takes k_pair_tile at 9 to 128 states, where it was measured
+        faster in every shape; get_option("pair_rows_kernel") says which one the last generic pass ran."""
         self._check_model(A, pi, par0, par1)
         n = self.nstates
         dtype = np.dtype(dtype)

@@ -304,7 +304,20 @@ int bhmm_posterior_marginals(bhmm_ctx *ctx, const double *A, const double *pi, c
    is zero) -- a bhmm_filter and a bhmm_posterior_marginals through their own entry points, each on the path it
    picks for the class, fp64 rows of both kept on the device (2 * total * N * 8 bytes, BHMM_ERR_NO_MEM if they do
    not fit), then one kernel over the steps, O(N * N) each.  It counts as whatever those two calls count as for the
-   context: at 9 states and more (unless bhmm_posterior_marginals takes a path of its own) an E-step. */
+   context: at 9 states and more (unless bhmm_posterior_marginals takes a path of its own) an E-step.
+   That kernel over the steps is one of two row kernels.  k_pair_rows, any N, one thread per step, accumulates in the
+   order stated above.  k_pair_tile, N <= 128, takes 16 steps as one tile on the matrix cores: pred = f_t A and
+   u_q = f_t (A o W_q) as one fp64 product (for the jump form A with its diagonal zeroed), then
+   sum_j u_q(j) r_j / sum_j pred_j r_j with r_j = gamma_t+1(j) / pred_j (0 where pred_j == 0).  It sums in a fixed tree
+   order (the matrix core's over i, then column tiles ascending and a butterfly over j; no atomics, repeated calls
+   are bitwise equal, a row does not depend on its neighbours, float is the rounded double) and is held to the same
+   bound against the oracle, not to bitwise equality with k_pair_rows (the jump form is still bitwise the projection
+   on the mask: both give the same matrix).  Option pair_rows: 0 always k_pair_rows; 1 k_pair_tile whenever
+   N <= 128 (every kind, explicit pobs and N <= 8 included), k_pair_rows above; -1 (default) k_pair_tile in the
+   classes where it was measured faster in every shape (9 to 64 and 65 to 128 states: both), k_pair_rows up to 8
+   states and above 128.
+   Read-only pair_rows_kernel: the row kernel of the last generic pass, 0 k_pair_rows, 1 k_pair_tile.  pair_path is 0
+   for the generic path whichever row kernel runs. */
 #define BHMM_PAIR_F32 1
 #define BHMM_PAIR_DEVICE 2
 int bhmm_posterior_transitions(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0,
