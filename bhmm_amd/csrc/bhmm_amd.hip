@@ -1028,71 +1028,18 @@ int bhmm_ctx_destroy(bhmm_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream)
         (void)hipStreamSynchronize(c->stream);
-    c->d_soff.release();
-    c->d_ws32.release();
-    c->d_ctraj.release();
-    c->d_clen.release();
-    c->d_traj_c0.release();
-    c->d_ct0.release();
-    c->d_cgoff.release();
-    c->d_obs_ci.release();
-    c->d_obs_rm.release();
-    c->d_Bt.release();
-    c->d_M.release();
-    c->d_aentry.release();
-    c->d_bexit.release();
-    c->d_ws.release();
-    c->d_gamma_ci.release();
-    c->d_logLc.release();
-    c->d_logLk.release();
-    c->d_gamma0.release();
-    c->d_partials.release();
-    c->d_dpartials.release();
-    c->d_stats.release();
-    c->d_scratch.release();
-    c->d_scratch2.release();
-    c->d_offsets.release();
-    c->d_Brm.release();
-    c->d_alpha_rm.release();
-    c->d_wmodel.release();
-    c->d_grp_c0.release();
-    c->d_grp_c1.release();
-    c->d_grp_traj0.release();
-    c->d_P.release();
-    c->d_agrp.release();
-    c->d_bgrp.release();
-    c->d_aexit.release();
-    c->d_bentry.release();
-    for (int w = 0; w < 3; ++w) {
-        c->d_wseg_traj[w].release();
-        c->d_wseg_len[w].release();
-        c->d_wseg_traj0[w].release();
-        c->d_wseg_t0[w].release();
-        c->d_wseg_fmid.release();
-    }
-    c->d_wlogLseg.release();
-    c->d_waentry.release();
-    c->d_waexit.release();
-    c->d_wbexit.release();
-    c->d_wbentry.release();
-    c->d_specres.release();
     if (c->h_specres)
         (void)hipHostFree(c->h_specres);
     if (c->h_small)
         (void)hipHostFree(c->h_small);
     if (c->h_raw)
         (void)hipHostFree(c->h_raw);
-    c->d_tail.release();
-    c->d_fold.release();
-    c->d_tbpart.release();
-    c->d_ea.release();
-    c->d_probe.release();
     for (auto &ev : c->ev)
         if (ev)
             (void)hipEventDestroy(ev);
     if (c->own_stream && c->stream)
         (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c; // (every DevBuf frees its allocation)
     return BHMM_OK;
 }
 
@@ -1523,6 +1470,18 @@ int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
         if (!(value >= 0.0) || value > (double)(1 << 30))
             return invalid_arg("marg_ws_mb outside [0, 2^30]");
         c->opt.marg_ws_mb = (int)value;
+    } else if (n == "pair_W") // bhmm_posterior_transitions only: fixed warm-up (0: measured); no E-step state changes
+        c->opt.pair_W = std::max(0, (int)value);
+    else if (n == "pair_ws_mb") { // ... budget of its alpha-row workspace in MiB (0: unbounded)
+        if (!(value >= 0.0) || value > (double)(1 << 30))
+            return invalid_arg("pair_ws_mb outside [0, 2^30]");
+        c->opt.pair_ws_mb = (int)value;
+    } else if (n == "pair_fused") // ... 0: never the fused path (the generic route answers every call)
+        c->opt.pair_fused = value != 0.0;
+    else if (n == "pair_rows") { // ... row kernel of the generic path: 0 k_pair_rows, 1 k_pair_tile (n <= 128), -1 by class
+        if (value != -1.0 && value != 0.0 && value != 1.0)
+            return invalid_arg("pair_rows is -1, 0 or 1");
+        c->opt.pair_rows = (int)value;
     } else if (n == "filter_W") // bhmm_filter only: fixed warm-up (0: measured); no E-step state changes
         c->opt.filter_W = std::max(0, (int)value);
     else if (n == "filter_seglen") { // ... 9..64 states: segment length of its plan from the next call on (0: automatic)
@@ -1688,6 +1647,20 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->last.marg_fallbacks;
     else if (n == "marg_path") // ... first pass of the last call: 2 time segments (9..64 states), 1 fused kernel (up to 8 states), 0 E-step + gamma rows
         *value = c->last.marg_path;
+    else if (n == "pair_W")
+        *value = c->opt.pair_W;
+    else if (n == "pair_ws_mb")
+        *value = c->opt.pair_ws_mb;
+    else if (n == "pair_fused")
+        *value = c->opt.pair_fused ? 1.0 : 0.0;
+    else if (n == "pair_rows")
+        *value = c->opt.pair_rows;
+    else if (n == "pair_fallbacks") // bhmm_posterior_transitions: calls whose boundaries did not verify at the first warm-up
+        *value = c->last.pair_fallbacks;
+    else if (n == "pair_path") // ... first pass of the last call: 1 fused kernel, 0 filter + marginals + pair rows
+        *value = c->last.pair_path;
+    else if (n == "pair_rows_kernel") // ... row kernel of the last generic pass: 0 k_pair_rows, 1 k_pair_tile
+        *value = c->last.pair_rows_kernel;
     else if (n == "filter_W")
         *value = c->opt.filter_W;
     else if (n == "filter_fallbacks") // bhmm_filter: calls whose boundaries did not verify at the first warm-up

@@ -80,6 +80,17 @@ struct SegTables {
     DevBuf<int32_t> tile_seg;
 };
 
+// What one two-sided sweep over the E-step's chunk plan needs for up to 8 states (sweep_host.hpp; the fused paths of
+// bhmm_posterior_decode, bhmm_posterior_marginals and bhmm_posterior_transitions, one of these each): model, probe
+// curve, B^T, alpha-row workspace of one range of chunk groups, boundary vectors of both directions, the chunks
+// whose exit vector is all zero, failure counter
+struct SweepBufs {
+    DevBuf<char> model, probe;
+    DevBuf<double> Bt, ws, aentry, aexit, bassumed, bout;
+    DevBuf<uint8_t> dead;
+    DevBuf<unsigned int> fails;
+};
+
 } // namespace bhmm
 
 // The fields are grouped by lifetime: `opt` holds what the caller sets (bhmm_ctx_set_option, environment at
@@ -124,6 +135,11 @@ struct bhmm_ctx {
         int post_ws_mb = 8192;           // ... budget of its alpha-row workspace in MiB (option post_ws_mb; 0: unbounded)
         int marg_W = 0;                  // bhmm_posterior_marginals: warm-up fixed by the caller (option marg_W; 0: measured)
         int marg_ws_mb = 8192;           // ... budget of its alpha-row workspace in MiB (option marg_ws_mb; 0: unbounded)
+        int pair_W = 0;                  // bhmm_posterior_transitions: warm-up fixed by the caller (option pair_W; 0: measured)
+        int pair_ws_mb = 8192;           // ... budget of its alpha-row workspace in MiB (option pair_ws_mb; 0: unbounded)
+        bool pair_fused = true;          // ... option pair_fused: 0 never takes the fused path
+        int pair_rows = -1;              // ... row kernel of its generic path: 0 k_pair_rows, 1 k_pair_tile up to 128 states,
+                                         // -1 by class (tile_takes, pair_api.hip; option pair_rows)
         int filter_W = 0;                // bhmm_filter: warm-up fixed by the caller (option filter_W; 0: measured)
         int filter_seglen = 0;           // bhmm_filter, 9..64 states: segment length of its plan (option filter_seglen; 0: automatic)
         int filter_parallel = -1;        // ... the time-parallel path: 0 never, 1 always when eligible, -1 automatic
@@ -278,6 +294,10 @@ struct bhmm_ctx {
         int marg_path = 0;               // ... first pass of the last call: 3 matrix cores (k_smooth_tile_bwd, 65..128 states),
                                          // 2 time segments (k_smooth_wide_bwd, 9..64 states), 1 fused (k_marg_sweep), 0 generic
                                          // (E-step + gamma rows)
+        int pair_fallbacks = 0;          // bhmm_posterior_transitions: calls whose boundaries did not verify at the first warm-up
+        int pair_path = 0;               // ... first pass of the last call: 1 fused (k_pair_sweep), 0 generic (filter +
+                                         // marginals + pair rows)
+        int pair_rows_kernel = 0;        // ... row kernel of the last generic pass: 0 k_pair_rows, 1 k_pair_tile
         int smooth_segments = 0;         // segments of the smoothing plan the last posterior call ran on (0: another path)
         int filter_fallbacks = 0;        // bhmm_filter: calls whose boundaries did not verify at the first warm-up
         int filter_path = 0;             // ... first pass of the last call: 3 matrix cores (k_filter_tile, 65..128 states),
@@ -400,24 +420,30 @@ struct bhmm_ctx {
         bhmm::DevBuf<double> wpar;
         bhmm::SegTables seg;
     } score;
-    // bhmm_posterior_decode (post_api.hip): its own buffers -- model, B^T, alpha-row workspace of one range of
-    // chunk groups, boundary vectors of both directions, failure counter, probe curve, and the results on the
-    // device (path: bytes or int32; conf); nothing else reads them
-    struct PostBufs {
-        bhmm::DevBuf<char> model, probe, path;
-        bhmm::DevBuf<double> Bt, ws, aentry, aexit, bassumed, bout;
-        bhmm::DevBuf<uint8_t> dead;
+    // bhmm_posterior_decode (post_api.hip): its own buffers -- a SweepBufs and the results on the device (path:
+    // bytes or int32; conf); nothing else reads them
+    struct PostBufs : bhmm::SweepBufs {
+        bhmm::DevBuf<char> path;
         bhmm::DevBuf<float> conf;
-        bhmm::DevBuf<unsigned int> fails;
     } post;
-    // bhmm_posterior_marginals (marg_api.hip): its own buffers -- as PostBufs, the projection matrix V, and the
+    // bhmm_posterior_marginals (marg_api.hip): its own buffers -- a SweepBufs, the projection matrix V, and the
     // result staged on the device when the caller's buffer is on the host (out); nothing else reads them
-    struct MargBufs {
-        bhmm::DevBuf<char> model, probe, out;
-        bhmm::DevBuf<double> Bt, ws, aentry, aexit, bassumed, bout, V;
-        bhmm::DevBuf<uint8_t> dead;
-        bhmm::DevBuf<unsigned int> fails;
+    struct MargBufs : bhmm::SweepBufs {
+        bhmm::DevBuf<char> out;
+        bhmm::DevBuf<double> V;
     } marg;
+    // bhmm_posterior_transitions (pair_api.hip): its own buffers -- a SweepBufs, the pair weights W [n][n][PAIR_QMAX]
+    // (padded), the result staged on the device when the caller's buffer is on the host (out), and for the generic
+    // path the filtered rows (filt) and posterior rows (gam) of every step, [total][n] doubles each, a device copy of
+    // the transition matrix (A) and the matrices [A | M_1 | ...] of k_pair_tile in its operand order (Bop,
+    // pair_tile_kernels.hpp).  W_host / A_host / Bop_host: what W, A and Bop on the device hold (upload_if_changed,
+    // pair_api.hip: an unchanged matrix is not uploaded again; Bop is formed on the host at every call that takes that
+    // kernel, so a change of A, W, Q or of the form rebuilds it and nothing else does); nothing else reads them
+    struct PairBufs : bhmm::SweepBufs {
+        bhmm::DevBuf<char> out;
+        bhmm::DevBuf<double> W, filt, gam, A, Bop;
+        std::vector<double> W_host, A_host, Bop_host;
+    } pair;
     // bhmm_filter (filter_api.hip): its own buffers -- model, B^T, boundary vectors, the chunks whose exit vector
     // is all zero and per trajectory the first of them, failure counter, probe curve, the projection matrix V, the
     // parameters of the serial path, and the two results staged on the device when the caller's buffers are on

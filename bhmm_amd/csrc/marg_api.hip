@@ -8,8 +8,9 @@
 // the alpha rows in a workspace of at most marg_ws_mb, then k_post_check over the boundary vectors of both directions.
 // Warm-up from the forgetting probe or the option marg_W.  Boundaries that do not verify: counted in
 // marg_fallbacks, the call runs again with twice the warm-up, and if they fail again it takes the generic path
-// (plan::two_attempts, plan.hpp; the model upload, the probe and the dispatch on the state count are
-// fused_host.hpp's, shared with bhmm_score, bhmm_filter and bhmm_posterior_decode).
+// (plan::two_attempts, plan.hpp; the pass and the run around it are sweep_host.hpp's, shared with
+// bhmm_posterior_decode and bhmm_posterior_transitions; the model upload, the probe and the dispatch on the state
+// count are fused_host.hpp's, shared with bhmm_score and bhmm_filter too).
 //
 // 9 to 64 states, gaussian or discrete (the time-segmented path, marg_path 2; smooth_wide.hip):
 // k_filter_wide leaves the filtered rows of a range of segments in a workspace of at most smooth_ws_mb,
@@ -43,7 +44,6 @@
 #include <string>
 #include <vector>
 
-#include "fused_host.hpp"
 #include "host_common.hpp"
 #include "host_internal.hpp"
 #include "launch.hpp"
@@ -51,6 +51,7 @@
 #include "model_check.hpp"
 #include "smooth_tile_api.hpp"
 #include "smooth_wide_launch.hpp"
+#include "sweep_host.hpp"
 
 namespace bhmm {
 namespace {
@@ -63,77 +64,37 @@ struct Out {          // where the rows go on the device, and what they are
     bool f32;
 };
 
-template <int N, int KIND>
-struct Fused {
-    // the sweep over every range of chunk groups and the check; *v: failed with boundaries out of tolerance
-    template <typename OT, bool PROJ>
-    static int pass(bhmm_ctx *c, const Model<N> *dm, int W, const double *dBt, const Out &o, plan::Verdict *v)
-    {
-        unsigned int fails = 0;
-        auto &b = c->marg;
-        const int G = c->G, groups = c->Gp / 64;
-        const Chunks ch = chunks_of(c);
-        const size_t lds_bt = (size_t)c->M * score_bt_stride(N) * sizeof(double);
-        const bool bt_lds = KIND == EMIT_DISC && lds_bt <= LDS_BT_MAX;
-        // alpha rows of one group, and how many groups the budget holds (at least one)
-        const size_t per_group = (size_t)c->Lmax * N * 64 * sizeof(double);
-        const size_t budget = (size_t)c->opt.marg_ws_mb << 20;
-        const int per_range =
-            budget == 0 ? groups : (int)std::min<size_t>(groups, std::max<size_t>(1, budget / per_group));
-        int rc;
-        if ((rc = b.ws.ensure((size_t)per_range * c->Lmax * N * 64)))
-            return rc;
-        BHMM_HIP(hipMemsetAsync(b.fails.p, 0, sizeof(unsigned int), c->stream));
-        auto *kern = bt_lds ? k_marg_sweep<N, KIND, true, OT, PROJ> : k_marg_sweep<N, KIND, false, OT, PROJ>;
-        for (int g0 = 0; g0 < groups; g0 += per_range)
-            BHMM_HIP(launch(kern, dim3(std::min(per_range, groups - g0)), dim3(64), bt_lds ? lds_bt : 0, c->stream, dm,
-                            W, ch, G, g0, c->d_offsets.p, c->d_obs_ci.p, c->d_obs_rm.p, dBt, c->M, b.ws.p,
-                            static_cast<OT *>(o.dev), o.V, o.Q, b.aentry.p, b.aexit.p, b.bassumed.p, b.bout.p,
-                            b.dead.p));
-        if (G > 1)
-            BHMM_HIP(launch(k_post_check<N>, dim3((G + 255) / 256), dim3(256), 0, c->stream, ch, G, b.aentry.p,
-                            b.aexit.p, b.bassumed.p, b.bout.p, b.dead.p, BOUNDARY_TOL, b.fails.p));
-        BHMM_HIP(hipMemcpyAsync(&fails, b.fails.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-        BHMM_HIP(hipStreamSynchronize(c->stream));
-        *v = plan::verdict_of(fails);
-        return BHMM_OK;
-    }
+template <int N, int KIND, typename OT, bool PROJ>
+int pass_as(bhmm_ctx *c, const Model<N> *dm, int W, const Out &o, plan::Verdict *v)
+{
+    auto &b = c->marg;
+    return sweep_pass<N, KIND>(c, b, c->opt.marg_ws_mb, dm, W, b.Bt.p, k_marg_sweep<N, KIND, true, OT, PROJ>,
+                               k_marg_sweep<N, KIND, false, OT, PROJ>, v, static_cast<OT *>(o.dev), o.V, o.Q);
+}
 
-    // *verified: the rows in o.dev stand
-    static int run(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
-                   const Out &o, bool *verified)
-    {
-        auto &b = c->marg;
-        *verified = false;
-        Model<N> m;
-        int rc;
-        if ((rc = b.aentry.ensure((size_t)c->Gp * N)) || (rc = b.aexit.ensure((size_t)c->Gp * N)) ||
-            (rc = b.bassumed.ensure((size_t)c->Gp * N)) || (rc = b.bout.ensure((size_t)c->Gp * N)) ||
-            (rc = b.dead.ensure(c->Gp)) || (rc = b.fails.ensure(1)) ||
-            (rc = upload_fused_model<N, KIND>(c, b.model, b.Bt, A, pi, par0, par1, m)))
-            return rc;
-        const Model<N> *dm = reinterpret_cast<const Model<N> *>(b.model.p);
-        // the larger of the two directions of the forgetting probe
-        int W = c->opt.marg_W;
-        if (W <= 0 && (rc = fused_probe<N, KIND>(c, b.probe, m, b.Bt.p, true, &W)))
-            return rc;
-        return plan::two_attempts(
-            W, 1 << 30, &c->last.marg_fallbacks,
-            [&](int w, plan::Verdict *v) {
-                if (o.Q > 0)
-                    return o.f32 ? pass<float, true>(c, dm, w, b.Bt.p, o, v) : pass<double, true>(c, dm, w, b.Bt.p, o, v);
-                return o.f32 ? pass<float, false>(c, dm, w, b.Bt.p, o, v) : pass<double, false>(c, dm, w, b.Bt.p, o, v);
-            },
-            verified);
-    }
-};
+// the fused path; *verified: the rows in o.dev stand
+template <int N, int KIND>
+int run_fused(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, const Out &o,
+              bool *verified)
+{
+    return sweep_run<N, KIND>(
+        c, c->marg, A, pi, par0, par1, c->opt.marg_W, &c->last.marg_fallbacks,
+        [&](const Model<N> *dm, int w, plan::Verdict *v) {
+            if (o.Q > 0)
+                return o.f32 ? pass_as<N, KIND, float, true>(c, dm, w, o, v)
+                             : pass_as<N, KIND, double, true>(c, dm, w, o, v);
+            return o.f32 ? pass_as<N, KIND, float, false>(c, dm, w, o, v)
+                         : pass_as<N, KIND, double, false>(c, dm, w, o, v);
+        },
+        verified);
+}
 
 template <int N>
 int run_n(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, const Out &o,
           bool *verified)
 {
-    return c->kind == EMIT_GAUSS ? Fused<N, EMIT_GAUSS>::run(c, A, pi, par0, par1, o, verified)
-                                 : Fused<N, EMIT_DISC>::run(c, A, pi, par0, par1, o, verified);
+    return c->kind == EMIT_GAUSS ? run_fused<N, EMIT_GAUSS>(c, A, pi, par0, par1, o, verified)
+                                 : run_fused<N, EMIT_DISC>(c, A, pi, par0, par1, o, verified);
 }
 
 // the generic path: an E-step that stores gamma, then one kernel that converts / projects the rows in the

@@ -8,13 +8,13 @@
 // alpha rows in a workspace of at most pair_ws_mb, then k_post_check over the boundary vectors of both directions.
 // Warm-up from the forgetting probe or the option pair_W.  Boundaries that do not verify: counted in
 // pair_fallbacks, the call runs again with twice the warm-up, and if they fail again it takes the generic path
-// (plan::two_attempts, plan.hpp; the model upload, the probe and the dispatch on the state count are
+// (plan::two_attempts, plan.hpp; the run around the pass is sweep_host.hpp's, the dispatch on the state count
 // fused_host.hpp's; the kernels and one pass over them are compiled per state count, pair_sweep_n.hip).  The option
 // pair_fused = 0 never takes this path.
 //
 // Everything else (9 states and more, explicit pobs, pair_fused 0, a fused call that did not verify; pair_path 0):
 // bhmm_filter and bhmm_posterior_marginals through their public entry points, each leaving fp64 rows in a device
-// buffer of the call's own state, then the row kernel over the steps: k_pair_rows with a device copy of A (one thread
+// buffer of c->pair, then the row kernel over the steps: k_pair_rows with a device copy of A (one thread
 // per step), or k_pair_tile (pair_tile_kernels.hpp, up to 128 states: 16 steps a matrix-core tile, the matrices in its
 // operand order formed here and kept like A and W) -- option pair_rows 0 / 1, -1 by class; read-only
 // pair_rows_kernel says which one the last generic pass ran; pair_path is 0 for both.  That IS a filter call and a
@@ -22,33 +22,27 @@
 // generic path (9 states and more unless its time-segmented or matrix-core path is on, explicit pobs) that is an
 // E-step; on its paths 1 to 3 it touches no other call's state.
 //
-// The call's buffers, options and counters are a PairState (pair_launch.hpp) that this unit keeps BESIDE the context,
-// one per context in a table keyed by its address, made at the first call or the first option SET and released by
-// bhmm_pair_release (which the owner of the context calls before bhmm_ctx_destroy) -- not a group in ctx.hpp: the
-// context and every other unit are then exactly what they were before this call existed.  The options are therefore
-// set and read by bhmm_pair_set_option / bhmm_pair_get_option, not by the tables of bhmm_ctx_set_option.  A state
-// that was never released and is found again under the address of a NEW context (another device or stream) is
-// discarded before use, its buffers freed on the device they were made on; the table itself is never destroyed, so
-// nothing is freed after the HIP runtime has gone at process exit.  The fused
-// path reads or writes nothing of the context beyond the plan, the observations and the stream.  A host result is
-// staged in the state's out buffer and crosses the link in ONE copy (copy_to_host_pinned, host_internal.hpp).
+// The call's buffers are the group c->pair (ctx.hpp), its options opt.pair_* and its counters last.pair_*, like every
+// other call's: set and read by bhmm_ctx_set_option / bhmm_ctx_get_option, kept across bhmm_ctx_set_observations,
+// freed by bhmm_ctx_destroy.  bhmm_pair_set_option / bhmm_pair_get_option forward the names that begin with pair_
+// to those two; bhmm_pair_release frees the group early and puts the seven values back to their defaults.  The fused
+// path reads or writes nothing of the context beyond that, the plan, the observations and the stream.  A host result
+// is staged in c->pair.out and crosses the link in ONE copy (copy_to_host_pinned, host_internal.hpp).
 #include <math.h>
 #include <string.h>
 
 #include <algorithm>
 #include <cmath>
-#include <memory>
-#include <mutex>
+#include <new>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
-#include "fused_host.hpp"
 #include "host_common.hpp"
 #include "host_internal.hpp"
 #include "launch.hpp"
 #include "model_check.hpp"
 #include "pair_launch.hpp"
+#include "sweep_host.hpp"
 
 namespace bhmm {
 PAIR_PASS_DECL(extern, 1)
@@ -61,91 +55,40 @@ PAIR_PASS_DECL(extern, 7)
 PAIR_PASS_DECL(extern, 8)
 namespace {
 
-// the state of every context that has made a pair call or set a pair option.  The table is allocated once and
-// never destroyed: a static destructor would free device buffers after the HIP runtime
-using PairTable = std::unordered_map<const bhmm_ctx *, std::unique_ptr<PairState>>;
-std::mutex g_pair_mutex;
-PairTable &pair_table()
-{
-    static PairTable *table = new PairTable();
-    return *table;
-}
-
-// frees the buffers of a state on the device they were allocated on, then makes c's device current again
-void drop_state(std::unique_ptr<PairState> gone, const bhmm_ctx *c)
-{
-    if (!gone)
-        return;
-    if (gone->device >= 0)
-        (void)hipSetDevice(gone->device);
-    (void)hipDeviceSynchronize();
-    gone.reset();
-    (void)hipSetDevice(c->device);
-    (void)hipGetLastError();
-}
-
-// the state of c; nullptr if it has none and create is false.  A state left by a context that is gone is dropped
-PairState *pair_state(const bhmm_ctx *c, bool create)
-{
-    std::unique_ptr<PairState> stale;
-    PairState *found = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_pair_mutex);
-        PairTable &t = pair_table();
-        auto it = t.find(c);
-        if (it != t.end() && (it->second->device != c->device || it->second->stream != c->stream)) {
-            stale = std::move(it->second);
-            t.erase(it);
-            it = t.end();
-        }
-        if (it != t.end()) {
-            found = it->second.get();
-        } else if (create) {
-            auto &slot = t[c];
-            slot.reset(new PairState());
-            slot->device = c->device;
-            slot->stream = c->stream;
-            found = slot.get();
-        }
-    }
-    drop_state(std::move(stale), c);
-    return found;
-}
-
+// the fused path; *verified: the rows in o.dev stand
 template <int N, int KIND>
-struct Fused {
-    // *verified: the rows in o.dev stand
-    static int run(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
-                   PairState &b, const PairOut &o, bool *verified)
-    {
-        *verified = false;
-        Model<N> m;
-        int rc;
-        if ((rc = b.aentry.ensure((size_t)c->Gp * N)) || (rc = b.aexit.ensure((size_t)c->Gp * N)) ||
-            (rc = b.bassumed.ensure((size_t)c->Gp * N)) || (rc = b.bout.ensure((size_t)c->Gp * N)) ||
-            (rc = b.dead.ensure(c->Gp)) || (rc = b.fails.ensure(1)) ||
-            (rc = upload_fused_model<N, KIND>(c, b.model, b.Bt, A, pi, par0, par1, m)))
-            return rc;
-        const Model<N> *dm = reinterpret_cast<const Model<N> *>(b.model.p);
-        // the larger of the two directions of the forgetting probe
-        int W = b.opt_W;
-        if (W <= 0 && (rc = fused_probe<N, KIND>(c, b.probe, m, b.Bt.p, true, &W)))
-            return rc;
-        return plan::two_attempts(
-            W, 1 << 30, &b.fallbacks,
-            [&](int w, plan::Verdict *v) {
-                return pair_pass<N, KIND>(c, b, dm, w, b.Bt.p, o, v); // (pair_sweep_n.hip)
-            },
-            verified);
-    }
-};
+int run_fused(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1,
+              const PairOut &o, bool *verified)
+{
+    return sweep_run<N, KIND>(
+        c, c->pair, A, pi, par0, par1, c->opt.pair_W, &c->last.pair_fallbacks,
+        [&](const Model<N> *dm, int w, plan::Verdict *v) {
+            return pair_pass<N, KIND>(c, dm, w, o, v); // (pair_sweep_n.hip)
+        },
+        verified);
+}
 
 template <int N>
-int run_n(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, PairState &b,
-          const PairOut &o, bool *verified)
+int run_n(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, const PairOut &o,
+          bool *verified)
 {
-    return c->kind == EMIT_GAUSS ? Fused<N, EMIT_GAUSS>::run(c, A, pi, par0, par1, b, o, verified)
-                                 : Fused<N, EMIT_DISC>::run(c, A, pi, par0, par1, b, o, verified);
+    return c->kind == EMIT_GAUSS ? run_fused<N, EMIT_GAUSS>(c, A, pi, par0, par1, o, verified)
+                                 : run_fused<N, EMIT_DISC>(c, A, pi, par0, par1, o, verified);
+}
+
+// `count` doubles of `fresh` into dev, kept is what dev holds: uploaded only where they differ from the kept copy or
+// the buffer was regrown, so repeated calls with the same matrix upload nothing and wait for nothing
+int upload_if_changed(bhmm_ctx *c, DevBuf<double> &dev, std::vector<double> &kept, const double *fresh, size_t count)
+{
+    const bool regrown = count > dev.n;
+    if (int rc = dev.ensure(count))
+        return rc;
+    if (regrown || kept.size() != count || !std::equal(kept.begin(), kept.end(), fresh)) {
+        BHMM_HIP(hipStreamSynchronize(c->stream)); // (an earlier upload may still read the kept copy)
+        kept.assign(fresh, fresh + count); // (kept: the copy may still be read when this call returns)
+        BHMM_HIP(hipMemcpyAsync(dev.p, kept.data(), count * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    return BHMM_OK;
 }
 
 // pair_rows -1: k_pair_tile where it was faster than k_pair_rows in EVERY shape measured for the class (DESIGN.md
@@ -153,34 +96,28 @@ int run_n(bhmm_ctx *c, const double *A, const double *pi, const double *par0, co
 constexpr bool PAIR_TILE_AUTO_WIDE = true; // 9 .. 64 states
 constexpr bool PAIR_TILE_AUTO_TILE = true; // 65 .. 128 states
 
-bool tile_takes(const bhmm_ctx *c, const PairState &b)
+bool tile_takes(const bhmm_ctx *c)
 {
-    if (c->n > PAIR_TILE_MAX_N || b.opt_rows == 0)
+    if (c->n > PAIR_TILE_MAX_N || c->opt.pair_rows == 0)
         return false;
-    if (b.opt_rows > 0)
+    if (c->opt.pair_rows > 0)
         return true;
     return c->n > 64 ? PAIR_TILE_AUTO_TILE : c->n > 8 ? PAIR_TILE_AUTO_WIDE : false;
 }
 
 // the generic path: filtered rows and posterior rows by the calls that hand them out, then one kernel over the steps
-int generic(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, PairState &b,
-            const PairOut &o)
+int generic(bhmm_ctx *c, const double *A, const double *pi, const double *par0, const double *par1, const PairOut &o)
 {
-    const bool tile = tile_takes(c, b);
-    b.rows_kernel = tile ? 1 : 0;
+    auto &b = c->pair;
+    const bool tile = tile_takes(c);
+    c->last.pair_rows_kernel = tile ? 1 : 0;
     if (c->total == 0)
         return BHMM_OK;
     const size_t rows = (size_t)c->total * c->n;
     int rc;
     if ((rc = b.filt.ensure(std::max<size_t>(rows, 2))) || (rc = b.gam.ensure(std::max<size_t>(rows, 2))) ||
-        (rc = b.A.ensure((size_t)c->n * c->n)))
+        (rc = upload_if_changed(c, b.A, b.A_host, A, (size_t)c->n * c->n)))
         return rc;
-    if (b.A_host.size() != (size_t)c->n * c->n || !std::equal(b.A_host.begin(), b.A_host.end(), A)) {
-        BHMM_HIP(hipStreamSynchronize(c->stream)); // (an earlier upload may still read the kept copy)
-        b.A_host.assign(A, A + (size_t)c->n * c->n); // (kept: the copy may still be read when this call returns)
-        BHMM_HIP(hipMemcpyAsync(b.A.p, b.A_host.data(), b.A_host.size() * sizeof(double), hipMemcpyHostToDevice,
-                                c->stream));
-    }
     if ((rc = bhmm_filter(c, A, pi, par0, par1, nullptr, 0, b.filt.p, nullptr, BHMM_FILT_DEVICE)) ||
         (rc = bhmm_posterior_marginals(c, A, pi, par0, par1, nullptr, 0, b.gam.p, BHMM_MARG_DEVICE)))
         return rc;
@@ -189,16 +126,9 @@ int generic(bhmm_ctx *c, const double *A, const double *pi, const double *par0, 
         // form as the last time give the same vector, and then nothing is uploaded or waited for
         std::vector<double> ops;
         pair_tile_operands(A, o.Q > 0 ? b.W_host.data() : nullptr, c->n, o.Q, ops);
-        const bool regrown = ops.size() > b.Bop.n;
-        if ((rc = b.Bop.ensure(ops.size())))
+        if ((rc = upload_if_changed(c, b.Bop, b.Bop_host, ops.data(), ops.size())))
             return rc;
-        if (regrown || ops != b.Bop_host) {
-            BHMM_HIP(hipStreamSynchronize(c->stream)); // (an earlier upload may still read the kept copy)
-            b.Bop_host.swap(ops); // (kept: the copy may still be read when this call returns)
-            BHMM_HIP(hipMemcpyAsync(b.Bop.p, b.Bop_host.data(), b.Bop_host.size() * sizeof(double),
-                                    hipMemcpyHostToDevice, c->stream));
-        }
-        return pair_tile_rows(c, b, o); // (pair_tile.hip)
+        return pair_tile_rows(c, o); // (pair_tile.hip)
     }
     const dim3 grid((unsigned)((c->total + 63) / 64)), block(64);
     if (o.f32)
@@ -236,7 +166,7 @@ int bhmm_posterior_transitions(bhmm_ctx *c, const double *A, const double *pi, c
             return invalid_arg("bhmm_posterior_transitions: W has a non-finite entry");
     if ((rc = check_models(c, "bhmm_posterior_transitions", 1, A, pi, par0, par1)))
         return rc;
-    PairState &b = *pair_state(c, true);
+    auto &b = c->pair;
     PairOut o;
     o.f32 = (flags & BHMM_PAIR_F32) != 0;
     o.Q = Q;
@@ -252,97 +182,63 @@ int bhmm_posterior_transitions(bhmm_ctx *c, const double *A, const double *pi, c
         std::vector<double> padded(pairs * PAIR_QMAX, 0.0);
         for (size_t e = 0; e < pairs; ++e)
             std::copy(W + e * Q, W + (e + 1) * Q, padded.begin() + e * PAIR_QMAX);
-        const bool regrown = padded.size() > b.W.n;
-        if ((rc = b.W.ensure(padded.size())))
+        if ((rc = upload_if_changed(c, b.W, b.W_host, padded.data(), padded.size())))
             return rc;
-        if (regrown || padded != b.W_host) { // (repeated calls with the same weights upload nothing)
-            BHMM_HIP(hipStreamSynchronize(c->stream)); // (an earlier upload may still read the kept copy)
-            b.W_host.swap(padded); // (kept: the copy may still be read when this call returns)
-            BHMM_HIP(hipMemcpyAsync(b.W.p, b.W_host.data(), b.W_host.size() * sizeof(double), hipMemcpyHostToDevice,
-                                    c->stream));
-        }
         o.W = b.W.p;
     }
-    const bool fused = fused_takes(c) && b.opt_fused;
-    b.path = fused ? 1 : 0;
+    const bool fused = fused_takes(c) && c->opt.pair_fused;
+    c->last.pair_path = fused ? 1 : 0;
     bool verified = false;
     if (fused) {
-        rc = dispatch_n(c->n, [&](auto N) { return run_n<decltype(N)::value>(c, A, pi, par0, par1, b, o, &verified); });
+        rc = dispatch_n(c->n, [&](auto N) { return run_n<decltype(N)::value>(c, A, pi, par0, par1, o, &verified); });
         if (rc)
             return rc;
     }
-    if (!verified && (rc = generic(c, A, pi, par0, par1, b, o)))
+    if (!verified && (rc = generic(c, A, pi, par0, par1, o)))
         return rc;
     if (on_dev) // the rows are where the caller wants them, ordered on the context's stream
         return BHMM_OK;
     return bytes == 0 ? BHMM_OK : copy_to_host_pinned(c, out, o.dev, bytes);
 }
 
+// the names of this call's options and counters, by the context's own functions (bhmm_amd.hip)
 int bhmm_pair_set_option(bhmm_ctx *c, const char *name, double value)
 {
     if (!c || !name)
         return invalid_arg("bhmm_pair_set_option: ctx / name == NULL");
-    const std::string n(name);
-    PairState &b = *pair_state(c, true);
-    if (n == "pair_W") // fixed warm-up (0: measured)
-        b.opt_W = std::max(0, (int)value);
-    else if (n == "pair_ws_mb") { // budget of the alpha-row workspace in MiB (0: unbounded)
-        if (!(value >= 0.0) || value > (double)(1 << 30))
-            return invalid_arg("pair_ws_mb outside [0, 2^30]");
-        b.opt_ws_mb = (int)value;
-    } else if (n == "pair_fused") // 0: never the fused path (the generic route answers every call)
-        b.opt_fused = value != 0.0;
-    else if (n == "pair_rows") { // row kernel of the generic path: 0 k_pair_rows, 1 k_pair_tile (n <= 128), -1 by class
-        if (value != -1.0 && value != 0.0 && value != 1.0)
-            return invalid_arg("pair_rows is -1, 0 or 1");
-        b.opt_rows = (int)value;
-    } else
-        return invalid_arg("unknown or read-only option: " + n);
-    return BHMM_OK;
+    if (strncmp(name, "pair_", 5) != 0)
+        return invalid_arg(std::string("unknown or read-only option: ") + name);
+    return bhmm_ctx_set_option(c, name, value);
 }
 
 int bhmm_pair_get_option(bhmm_ctx *c, const char *name, double *value)
 {
     if (!c || !name || !value)
         return invalid_arg("bhmm_pair_get_option: ctx / name / value == NULL");
-    const std::string n(name);
-    const PairState fresh; // (a context that made no pair call and set no option: the defaults, nothing is kept)
-    const PairState *have = pair_state(c, false);
-    const PairState &b = have ? *have : fresh;
-    if (n == "pair_W")
-        *value = b.opt_W;
-    else if (n == "pair_ws_mb")
-        *value = b.opt_ws_mb;
-    else if (n == "pair_fused")
-        *value = b.opt_fused ? 1.0 : 0.0;
-    else if (n == "pair_fallbacks") // calls whose boundaries did not verify at the first warm-up
-        *value = b.fallbacks;
-    else if (n == "pair_path") // first pass of the last call: 1 fused kernel, 0 filter + marginals + pair rows
-        *value = b.path;
-    else if (n == "pair_rows")
-        *value = b.opt_rows;
-    else if (n == "pair_rows_kernel") // row kernel of the last generic pass: 0 k_pair_rows, 1 k_pair_tile
-        *value = b.rows_kernel;
-    else
-        return invalid_arg("unknown option: " + n);
-    return BHMM_OK;
+    if (strncmp(name, "pair_", 5) != 0)
+        return invalid_arg(std::string("unknown option: ") + name);
+    return bhmm_ctx_get_option(c, name, value);
 }
 
+// frees c->pair and puts opt.pair_* / last.pair_* back to their defaults: the next call works as on a fresh context
 int bhmm_pair_release(bhmm_ctx *c)
 {
     if (!c)
         return BHMM_OK;
-    std::unique_ptr<PairState> gone;
-    {
-        std::lock_guard<std::mutex> lock(g_pair_mutex);
-        PairTable &t = pair_table();
-        auto it = t.find(c);
-        if (it == t.end())
-            return BHMM_OK;
-        gone = std::move(it->second);
-        t.erase(it);
-    }
-    drop_state(std::move(gone), c); // (waits for the device, frees the buffers where they were made)
+    BHMM_HIP(hipSetDevice(c->device));
+    BHMM_HIP(hipStreamSynchronize(c->stream)); // (a kernel or an upload may still use the buffers and the kept copies)
+    using PairBufs = bhmm_ctx::PairBufs;
+    c->pair.~PairBufs();
+    new (&c->pair) PairBufs();
+    const bhmm_ctx::Options opt;
+    c->opt.pair_W = opt.pair_W;
+    c->opt.pair_ws_mb = opt.pair_ws_mb;
+    c->opt.pair_fused = opt.pair_fused;
+    c->opt.pair_rows = opt.pair_rows;
+    const bhmm_ctx::LastCall last;
+    c->last.pair_fallbacks = last.pair_fallbacks;
+    c->last.pair_path = last.pair_path;
+    c->last.pair_rows_kernel = last.pair_rows_kernel;
     return BHMM_OK;
 }
 

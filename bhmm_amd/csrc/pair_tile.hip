@@ -1,6 +1,6 @@
 // pair_tile.hip -- k_pair_tile (pair_tile_kernels.hpp): its sixteen instantiations (1 .. 8 column tiles, double /
 // float), the matrices [A | M_1 | ...] in the kernel's operand order, and the launch over the rows that the generic
-// path of bhmm_posterior_transitions (pair_api.hip) has left in b.filt / b.gam.  DESIGN.md section 21.
+// path of bhmm_posterior_transitions (pair_api.hip) has left in c->pair.filt / gam.  DESIGN.md section 21.
 #include <algorithm>
 
 #include "pair_launch.hpp"
@@ -10,19 +10,20 @@ namespace bhmm {
 namespace {
 
 template <int NT, typename OT>
-int rows_as(bhmm_ctx *c, PairState &b, const PairOut &o, int nm)
+int rows_as(bhmm_ctx *c, const PairOut &o, int nm)
 {
     const int64_t tiles = (c->total + 15) / 16; // one per wavefront
     const dim3 grid((unsigned)((tiles + PAIR_TILE_WAVES - 1) / PAIR_TILE_WAVES)), block(64 * PAIR_TILE_WAVES);
+    const auto &b = c->pair;
     BHMM_HIP(launch(k_pair_tile<NT, OT>, grid, block, 0, c->stream, b.filt.p, b.gam.p, b.Bop.p, nm, c->n, c->total,
                     c->K, c->d_offsets.p, static_cast<OT *>(o.dev)));
     return BHMM_OK;
 }
 
 template <int NT>
-int rows_nt(bhmm_ctx *c, PairState &b, const PairOut &o, int nm)
+int rows_nt(bhmm_ctx *c, const PairOut &o, int nm)
 {
-    return o.f32 ? rows_as<NT, float>(c, b, o, nm) : rows_as<NT, double>(c, b, o, nm);
+    return o.f32 ? rows_as<NT, float>(c, o, nm) : rows_as<NT, double>(c, o, nm);
 }
 
 } // namespace
@@ -43,18 +44,18 @@ void pair_tile_operands(const double *A, const double *Wpad, int n, int Q, std::
             }
 }
 
-int pair_tile_rows(bhmm_ctx *c, PairState &b, const PairOut &o)
+int pair_tile_rows(bhmm_ctx *c, const PairOut &o)
 {
     const int nm = pair_tile_matrices(o.Q);
     switch ((c->n + 15) / 16) {
-    case 1: return rows_nt<1>(c, b, o, nm);
-    case 2: return rows_nt<2>(c, b, o, nm);
-    case 3: return rows_nt<3>(c, b, o, nm);
-    case 4: return rows_nt<4>(c, b, o, nm);
-    case 5: return rows_nt<5>(c, b, o, nm);
-    case 6: return rows_nt<6>(c, b, o, nm);
-    case 7: return rows_nt<7>(c, b, o, nm);
-    case 8: return rows_nt<8>(c, b, o, nm);
+    case 1: return rows_nt<1>(c, o, nm);
+    case 2: return rows_nt<2>(c, o, nm);
+    case 3: return rows_nt<3>(c, o, nm);
+    case 4: return rows_nt<4>(c, o, nm);
+    case 5: return rows_nt<5>(c, o, nm);
+    case 6: return rows_nt<6>(c, o, nm);
+    case 7: return rows_nt<7>(c, o, nm);
+    case 8: return rows_nt<8>(c, o, nm);
     }
     return invalid_arg("pair_tile_rows: more than 128 states");
 }

@@ -98,9 +98,6 @@ class Engine(object):
 
     def close(self):
         if getattr(self, "_h", None):
-            if getattr(self, "_pair_used", False):      # (the state posterior_transitions keeps beside the context)
-                self._L.bhmm_pair_release(self._h)
-                self._pair_used = False
             self._L.bhmm_ctx_destroy(self._h)
             self._h = None
 
@@ -204,17 +201,10 @@ class Engine(object):
         return self._L.bhmm_ctx_stream(self._h)
 
     def set_option(self, name, value):
-        if name.startswith("pair_"):        # posterior_transitions keeps its options itself (bhmm_pair_set_option)
-            self._pair_used = True
-            _lib.check(self._L.bhmm_pair_set_option(self._h, name.encode(), float(value)))
-            return
         _lib.check(self._L.bhmm_ctx_set_option(self._h, name.encode(), float(value)))
 
     def get_option(self, name):
         v = ctypes.c_double(0.0)
-        if name.startswith("pair_"):        # (reading keeps nothing beside the context)
-            _lib.check(self._L.bhmm_pair_get_option(self._h, name.encode(), ctypes.byref(v)))
-            return v.value
         _lib.check(self._L.bhmm_ctx_get_option(self._h, name.encode(), ctypes.byref(v)))
         return v.value
 
@@ -525,7 +515,6 @@ class Engine(object):
         if (flags & _lib.PAIR_DEVICE) and ptr % 16:
             raise ValueError("a device buffer must be aligned to 16 bytes")
         A, pi, p0, p1 = self._model_ptrs(A, pi, par0, par1)
-        self._pair_used = True
         _lib.check(self._L.bhmm_posterior_transitions(self._h, A, pi, p0, p1, _lib.dp(W), Q,
                                                       ctypes.c_void_p(int(ptr)), flags))
         if rows is None:

@@ -292,9 +292,9 @@ int bhmm_posterior_marginals(bhmm_ctx *ctx, const double *A, const double *pi, c
    from the stored alpha row and the vector the backward step forms anyway -- the same verified warm-up boundaries
    and retry protocol; the pair that straddles a chunk edge rests on the verified entry vector of the later chunk.
    Nothing of the state that E-step, Viterbi, sampling, scoring, decoding, marginals and filter calls use is read or
-   written; the context itself is not changed either: the call keeps its buffers, options and counters in a
-   state of its own beside the context, made at the first call or option and released by bhmm_pair_release.
-   Options, set and read by bhmm_pair_set_option / bhmm_pair_get_option (not by bhmm_ctx_set_option): pair_W
+   written: the call keeps its buffers in a group of its own in the context, freed by bhmm_ctx_destroy.
+   Options, set and read by bhmm_ctx_set_option / bhmm_ctx_get_option like every other call's (they survive
+   bhmm_ctx_set_observations; bhmm_pair_set_option / bhmm_pair_get_option below are the same two doors): pair_W
    (warm-up in steps, 0 = measured), pair_ws_mb (budget of the alpha-row workspace in MiB, default 8192,
    0 = unbounded; the result does not depend on it), pair_fused (default 1; 0: never take the fused path);
    read-only pair_fallbacks (calls whose boundaries did not verify at the first warm-up: they run again with twice
@@ -322,12 +322,11 @@ int bhmm_posterior_marginals(bhmm_ctx *ctx, const double *A, const double *pi, c
 #define BHMM_PAIR_DEVICE 2
 int bhmm_posterior_transitions(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0,
                                const double *par1, const double *W, int Q, void *out, int flags);
-/* The options of bhmm_posterior_transitions (names above; BHMM_ERR_INVALID for an unknown or read-only one), and
-   the release of the state it keeps for ctx: call it before bhmm_ctx_destroy on every context that made a pair
-   call or set a pair option (it waits for the device; a context without such a state: no-op; reading an option of
-   such a context gives the default and keeps nothing).  bhmm_ctx_destroy does NOT release it: without this call the
-   state's device buffers stay allocated until the process ends.  A state left behind is never used for another
-   context: one found under the address of a context with another device or stream is dropped first. */
+/* Kept from the first release of bhmm_posterior_transitions.  bhmm_pair_set_option / bhmm_pair_get_option forward a
+   name that begins with pair_ to bhmm_ctx_set_option / bhmm_ctx_get_option (BHMM_ERR_INVALID for any other name, and
+   for an unknown or read-only one).  bhmm_pair_release frees the buffers the call keeps in ctx early (it waits for
+   the context's stream) and puts the pair_ options and counters back to their defaults; the next call works as on a
+   fresh context.  It is NOT needed before bhmm_ctx_destroy, which frees everything. */
 int bhmm_pair_set_option(bhmm_ctx *ctx, const char *name, double value);
 int bhmm_pair_get_option(bhmm_ctx *ctx, const char *name, double *value);
 int bhmm_pair_release(bhmm_ctx *ctx);

@@ -501,3 +501,142 @@ def test_full_size_configs1():
     sel = [0, 85, K - 1]
     _check_jump(oracle_rows("gaussian", [obs[k] for k in sel], model), [views[k].cpu().numpy() for k in sel],
                 np.float32, n, "configs[1]")
+
+
+# ---- 9. the call's state is the context's --------------------------------------------------------------
+PAIR_DEFAULTS = {"pair_fused": 1.0, "pair_W": 0.0, "pair_ws_mb": 8192.0, "pair_rows": -1.0, "pair_fallbacks": 0.0,
+                 "pair_path": 0.0, "pair_rows_kernel": 0.0}
+
+
+def _raw_get(L, h, door, name):
+    """(status, value) of one option through bhmm_ctx_get_option or bhmm_pair_get_option"""
+    v = ctypes.c_double(-12345.0)
+    rc = getattr(L, door)(h, name.encode(), ctypes.byref(v))
+    return rc, v.value
+
+
+def _pair_options(L, h):
+    out = {}
+    for name in PAIR_DEFAULTS:
+        by_ctx, by_pair = _raw_get(L, h, "bhmm_ctx_get_option", name), _raw_get(L, h, "bhmm_pair_get_option", name)
+        assert by_ctx[0] == 0 and by_ctx == by_pair, name
+        out[name] = by_ctx[1]
+    return out
+
+
+def test_state_dies_with_the_context():
+    """options set on a context that is destroyed without bhmm_pair_release reach no later context, whichever
+    address it is made at"""
+    from bhmm_amd import _lib
+    L = _lib.load()
+    for _ in range(4):
+        h = ctypes.c_void_p()
+        assert L.bhmm_ctx_create(ctypes.byref(h), 0, None) == 0
+        for name, value in (("pair_fused", 0.0), ("pair_W", 7.0), ("pair_rows", 0.0)):
+            assert L.bhmm_ctx_set_option(h, name.encode(), value) == 0
+        assert _raw_get(L, h, "bhmm_pair_get_option", "pair_W") == (0, 7.0)
+        assert L.bhmm_ctx_destroy(h) == 0
+    h = ctypes.c_void_p()
+    assert L.bhmm_ctx_create(ctypes.byref(h), 0, None) == 0
+    try:
+        assert _pair_options(L, h) == PAIR_DEFAULTS
+    finally:
+        L.bhmm_ctx_destroy(h)
+
+
+def test_options_by_both_doors():
+    from bhmm_amd import _lib
+    rng = np.random.default_rng(31)
+    n = 3
+    eng = _engine()
+    eng.set_observations("gaussian", _rand_obs("gaussian", n, 0, [50], rng), n)
+    L, h = eng._L, eng._h
+    doors = ("bhmm_ctx", "bhmm_pair")
+    values = {"pair_W": 11.0, "pair_ws_mb": 3.0, "pair_fused": 0.0, "pair_rows": 1.0}
+    for setter, getter in (doors, doors[::-1]):
+        for name, value in values.items():
+            assert getattr(L, setter + "_set_option")(h, name.encode(), value) == 0, (setter, name)
+            assert _raw_get(L, h, getter + "_get_option", name) == (0, value), (getter, name)
+            assert eng.get_option(name) == value
+        values = {"pair_W": 0.0, "pair_ws_mb": 0.0, "pair_fused": 1.0, "pair_rows": 0.0}   # (second round: other values)
+    before = _pair_options(L, h)
+    for door in doors:
+        assert getattr(L, door + "_set_option")(h, b"pair_path", 1.0) == _lib.ERR_INVALID           # read-only
+        assert b"unknown or read-only option" in L.bhmm_last_error()
+        assert getattr(L, door + "_set_option")(h, b"pair_nonsense", 1.0) == _lib.ERR_INVALID
+        assert _raw_get(L, h, door + "_get_option", "pair_nonsense")[0] == _lib.ERR_INVALID
+        assert getattr(L, door + "_set_option")(h, b"pair_rows", 2.0) == _lib.ERR_INVALID           # out of range
+        assert b"pair_rows is -1, 0 or 1" in L.bhmm_last_error()
+        assert getattr(L, door + "_set_option")(h, b"pair_ws_mb", -1.0) == _lib.ERR_INVALID         # negative
+        assert b"pair_ws_mb outside [0, 2^30]" in L.bhmm_last_error()
+    # the pair doors take the names of this call alone
+    assert L.bhmm_pair_set_option(h, b"post_W", 5.0) == _lib.ERR_INVALID
+    assert _raw_get(L, h, "bhmm_pair_get_option", "post_W")[0] == _lib.ERR_INVALID
+    assert eng.get_option("post_W") == 0
+    assert _pair_options(L, h) == before
+    eng.close()
+
+
+def test_release_then_go_on():
+    eng = _engine()
+
+    def calls():
+        out = []
+        for n, opts in ((3, {"pair_W": 40, "pair_ws_mb": 1}), (12, {"pair_rows": 1})):
+            r = np.random.default_rng(100 + n)
+            obs = _rand_obs("gaussian", n, 0, [300, 1, 77], r)
+            model, W = _rand_model("gaussian", n, 0, r, stay=2.0), _weights(n, 3, r)
+            eng.set_observations("gaussian", obs, n, chunk=64)
+            for name, value in opts.items():
+                eng.set_option(name, value)
+            out.append(_cat(eng.posterior_transitions(*model, weights=W)))
+            assert eng.get_option("pair_path") == (1 if n == 3 else 0)
+            assert eng.get_option("pair_rows_kernel") == (1 if n == 12 else 0)
+        return out
+
+    before = calls()
+    assert _pair_options(eng._L, eng._h) != PAIR_DEFAULTS
+    assert eng._L.bhmm_pair_release(eng._h) == 0
+    assert _pair_options(eng._L, eng._h) == PAIR_DEFAULTS
+    after = calls()
+    assert eng._L.bhmm_pair_release(eng._h) == 0
+    assert eng._L.bhmm_pair_release(eng._h) == 0            # (nothing left: still fine)
+    eng.close()
+    for a, b in zip(before, after):
+        assert a.size and np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("rows", [0, 1])
+def test_kept_copies(rows):
+    """A, W and the operand matrices are uploaded only where they differ from the kept host copy: every call of a
+    sequence on ONE engine gives bitwise what a fresh engine gives for that call alone"""
+    rng = np.random.default_rng(33)
+    n, big = 12, 20
+    obs = _rand_obs("gaussian", n, 0, [40, 1, 2, 17], rng)
+    obs_big = _rand_obs("gaussian", big, 0, [40, 1, 2, 17], rng)
+    m1, m2 = _rand_model("gaussian", n, 0, rng, stay=2.0), _rand_model("gaussian", n, 0, rng, stay=1.0)
+    m2 = (m2[0],) + m1[1:]                                   # (A2 with the rest of model 1: A alone changes)
+    m3 = _rand_model("gaussian", big, 0, rng, stay=2.0)
+    W1, W2, W3 = _weights(n, 4, rng), _weights(n, 4, rng), _weights(big, 4, rng)
+    steps = [(obs, m1, W1), (obs, m1, W1), (obs, m1, W2), (obs, m2, W2), (obs, m2, None),
+             (obs, m2, np.ascontiguousarray(W1[:, :, :2])), (obs_big, m3, W3)]
+
+    def run(eng, o, model, W):
+        if eng.nstates != len(model[1]):
+            eng.set_observations("gaussian", o, len(model[1]))
+        return _cat(eng.posterior_transitions(*model, weights=W))
+
+    def fresh():
+        eng = _engine()
+        eng.set_option("pair_rows", rows)
+        return eng
+
+    one = fresh()
+    got = [run(one, *s) for s in steps]
+    assert one.get_option("pair_path") == 0 and one.get_option("pair_rows_kernel") == rows
+    one.close()
+    for i, s in enumerate(steps):
+        eng = fresh()
+        want = run(eng, *s)
+        eng.close()
+        assert want.size and np.array_equal(got[i], want), "step %d" % i
