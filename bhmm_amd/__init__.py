@@ -17,7 +17,7 @@ from .estimators.maximum_likelihood import MaximumLikelihoodEstimator  # noqa: F
 from .estimators.bayesian_sampling import BayesianHMMSampler  # noqa: F401
 from .api import (estimate_hmm, bayesian_hmm, lag_observations, gaussian_hmm,  # noqa: F401
                   discrete_hmm, init_hmm, init_gaussian_hmm, init_discrete_hmm, score, posterior_decode,
-                  posterior_marginals, posterior_transitions, filter_states, decode_segments)
+                  posterior_marginals, posterior_transitions, filter_states, decode_segments, path_logprob)
 from .engine import PathRuns  # noqa: F401
 
 MLHMM = MaximumLikelihoodEstimator          # bhmm/__init__.py:36

@@ -101,6 +101,10 @@ SIGNATURES = {
     "bhmm_decode_runs": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int,
                                         c_int64_p, c_int64_p, c_int64_p]),
     "bhmm_runs_fetch": (ctypes.c_int, [c_void_p, c_int64_p, c_int64_p, c_int32_p]),
+    "bhmm_path_logprob": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p,
+                                         c_double_p, c_double_p, c_double_p, c_double_p]),
+    "bhmm_decode_logprob": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int,
+                                           c_double_p]),
     "bhmm_ctx_path_stats_size": (ctypes.c_int, [c_void_p]),
     "bhmm_ctx_set_stream_offsets": (ctypes.c_int, [c_void_p, c_int64_p]),
     "bhmm_sample_paths_dev": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,

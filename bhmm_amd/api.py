@@ -248,6 +248,88 @@ def decode_segments(observations, model, lag=1, method='viterbi', stats=False, *
         eng.close()
 
 
+def path_logprob(observations, models, paths=None, method='viterbi', lag=1, **engine_kwargs):
+    """Joint log-probability log p(s, O | model) of hidden paths of `observations`, per trajectory
+    (bhmm_path_logprob, bhmm_decode_logprob): log pi(s_0) + e(s_0, o_0) + sum_t [log A(s_t-1, s_t) + e(s_t, o_t)].
+    With `paths` -- one integer array per trajectory, or one flat uint8 / int32 array concatenated like the
+    observations -- they are scored under each of `models` (one HMM, a list of HMMs of the same output type and
+    number of states, or a SampledHMM) in one pass over paths and observations: an (S, K) array.  With paths=None
+    `models` must be ONE HMM: the observations are decoded with `method` ('viterbi': the result is the Viterbi
+    score; 'posterior') and the decoded path is scored where it lies on the GPU: a (K,) array.  lag > 1 works on
+    the lagged views (lag_observations), one trajectory per view.  Every term is formed in log space; the gaussian
+    outlier rule of the recursions is NOT applied (an outlier gives a very negative finite term).  A zero
+    probability on a path gives -inf for that trajectory -- a posterior-decoded path can take a jump the model
+    forbids --, a NaN observation NaN, an empty trajectory 0.0.  engine_kwargs: device (default 0)."""
+    from .engine import Engine
+    from .estimators.maximum_likelihood import model_tuple
+    if isinstance(models, SampledHMM):
+        models = models.sampled_hmms
+    elif isinstance(models, HMM):
+        models = [models]
+    elif not isinstance(models, (list, tuple)):
+        raise TypeError("models must be an HMM, a list of HMMs or a SampledHMM")
+    models = list(models)
+    if not models:
+        raise ValueError("path_logprob needs at least one model")
+    for m in models:
+        if not isinstance(m, HMM):
+            raise TypeError("models must be HMM objects (or a SampledHMM)")
+    if method not in ('viterbi', 'posterior'):
+        raise ValueError("method must be 'viterbi' or 'posterior', not %r" % (method,))
+    if paths is None and len(models) != 1:
+        raise ValueError("without paths exactly one model decodes (got %d)" % len(models))
+    output = models[0].output_model.model_type
+    nstates = models[0].nstates
+    nsymbols = models[0].output_model.nsymbols if output == 'discrete' else 0
+    for m in models[1:]:
+        if m.output_model.model_type != output:
+            raise ValueError("all models must have the same output type (got %r and %r)"
+                             % (output, m.output_model.model_type))
+        if m.nstates != nstates:
+            raise ValueError("all models must have the same number of states")
+        if output == 'discrete' and m.output_model.nsymbols != nsymbols:
+            raise ValueError("all models must have the same number of symbols")
+    if len(observations) == 0:
+        raise ValueError("no observations")
+    device = engine_kwargs.pop('device', 0)
+    if engine_kwargs:
+        raise TypeError("unexpected keyword arguments: %s" % ", ".join(sorted(engine_kwargs)))
+    if lag > 1:
+        observations = lag_observations(observations, lag)
+    if paths is not None:
+        lengths = [len(o) for o in observations]
+        if isinstance(paths, (list, tuple)):
+            if len(paths) != len(lengths):
+                raise ValueError("expected one path per trajectory (%d), got %d" % (len(lengths), len(paths)))
+            pieces = [np.asarray(p) for p in paths]
+        else:
+            flat = np.asarray(paths)
+            if flat.ndim != 1 or flat.shape[0] != sum(lengths):
+                raise ValueError("a flat path must hold sum(T_k) = %d states" % sum(lengths))
+            pieces = [flat]
+        for k, p in enumerate(pieces):
+            if p.size and not np.issubdtype(p.dtype, np.integer):
+                raise ValueError("paths must hold integers, not %s" % p.dtype.name)
+            if isinstance(paths, (list, tuple)) and (p.ndim != 1 or p.shape[0] != lengths[k]):
+                raise ValueError("path %d must be 1-d with %d steps, not %r" % (k, lengths[k], p.shape))
+        if not isinstance(paths, (list, tuple)):
+            if flat.size and (flat.min() < 0 or flat.max() >= nstates):
+                raise ValueError("paths holds a state outside [0, %d)" % nstates)
+            paths = np.ascontiguousarray(flat, dtype=np.uint8 if flat.dtype == np.uint8 else np.int32)
+    eng = Engine(device)
+    try:
+        if output == 'discrete':
+            obs = [np.asarray(o) for o in observations]
+            eng.set_observations('discrete', obs, nstates, nsymbols=nsymbols)
+        else:
+            eng.set_observations(output, [np.asarray(o, dtype=np.float64) for o in observations], nstates)
+        if paths is None:
+            return eng.decode_logprob(*model_tuple(models[0]), method=method)
+        return eng.path_logprob(paths, [model_tuple(m) for m in models])
+    finally:
+        eng.close()
+
+
 def posterior_marginals(observations, model, lag=1, weights=None, dtype=np.float64, **engine_kwargs):
     """Posterior state probabilities of `observations` under one HMM (bhmm_posterior_marginals): per
     trajectory a (T_k, nstates) array of gamma_t(i) -- what the reference's estimator hands out as

@@ -1707,6 +1707,14 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = (double)c->ds.runs_count;
     else if (n == "runs_ms") // ... device time of its count, scan and scatter passes
         *value = c->last.runs_ms;
+    else if (n == "pathlp_tile") // bhmm_path_logprob / bhmm_decode_logprob: steps of the path per workgroup
+        *value = runs::TILE;
+    else if (n == "pathlp_lane") // ... consecutive steps per lane
+        *value = runs::LANE;
+    else if (n == "pathlp_table") // ... 1: the last call kept the log-transition table in LDS, 0: it read it through L2
+        *value = c->last.pathlp_table;
+    else if (n == "pathlp_ms") // ... device time of the last call's prepare, tile and finish passes
+        *value = c->last.pathlp_ms;
     else
         return invalid_arg("unknown option: " + n);
     return BHMM_OK;

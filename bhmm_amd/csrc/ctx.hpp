@@ -254,6 +254,10 @@ struct bhmm_ctx {
         bool runs_tiles_ready = false;   // ... runs.tile_traj holds the trajectory of every tile's first step for these offsets
         bool runs_valid = false;
         int64_t runs_count = 0;          // ... how many (option runs_count)
+        // bhmm_path_logprob / bhmm_decode_logprob (pathlp_api.hip)
+        bool pathlp_tiles_ready = false; // ... pathlp.tile_traj holds the trajectory of every tile's first step for these offsets
+        int32_t pathlp_traj0 = 0;        // ... its first entry: the trajectory of step 0 (the partial of tile i and trajectory
+                                         // k is slot i + k - pathlp_traj0)
     } ds;
 
     // ---- counters and diagnostics of the last calls (bhmm_ctx_get_option) ----
@@ -307,6 +311,8 @@ struct bhmm_ctx {
         int filter_redone = 0;           // ... filter_path 3: trajectories of the last call done again on k_filter_serial
                                          // because a segment left the range of k_filter_tile (option filter_redone)
         float runs_ms = 0.f;             // bhmm_path_runs / bhmm_decode_runs: device time of count, scan and scatter
+        float pathlp_ms = 0.f;           // bhmm_path_logprob / bhmm_decode_logprob: device time of prepare, tiles and finish
+        int pathlp_table = 0;            // ... 1: the last call kept the log-transition table in LDS, 0: it read it through L2
     } last;
 
     // ---- not reset by bhmm_ctx_set_observations: they outlive the observation set ----
@@ -515,6 +521,28 @@ struct bhmm_ctx {
                     (void)hipEventDestroy(e);
         }
     } runs;
+    // bhmm_path_logprob / bhmm_decode_logprob (pathlp_api.hip): its own buffers -- the path where the call has to hold
+    // it (a host path staged, the Viterbi path of bhmm_decode_logprob), the trajectory of every tile's first step (made
+    // once per observation set, ds.pathlp_tiles_ready), the stacked models as the caller gave them (raw) and their
+    // log tables (tab: per model log A, log pi and log B or mu, 1 / sigma, -log sigma - log(2 pi) / 2), one partial
+    // per (model, tile, trajectory with a step in the tile), the result [nmodels][K], the status word and the events
+    // of pathlp_ms; nothing else reads them
+    struct PathLpBufs {
+        bhmm::DevBuf<char> path;
+        bhmm::DevBuf<int32_t> tile_traj;
+        bhmm::DevBuf<double> raw, tab, part, logp;
+        bhmm::DevBuf<unsigned int> status;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        PathLpBufs() = default;
+        PathLpBufs(const PathLpBufs &) = delete;
+        PathLpBufs &operator=(const PathLpBufs &) = delete;
+        ~PathLpBufs()
+        {
+            for (hipEvent_t e : ev)
+                if (e)
+                    (void)hipEventDestroy(e);
+        }
+    } pathlp;
 
     // ---- pinned host buffers ----
     unsigned int *h_specres = nullptr; // pinned

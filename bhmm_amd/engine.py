@@ -659,6 +659,14 @@ class Engine(object):
         uint8 needs nstates <= 256.  A state outside [0, nstates) raises ValueError.  Returns a PathRuns; with
         `stats` its dwell and jumps tables are filled.  Only the runs cross the link (get_option("runs_count"),
         "runs_ms": device time of the compaction; read-only "runs_tile", "runs_lane")."""
+        ptr, u8, on_dev = self._path_arg(paths)
+        return self._runs_result(
+            lambda off, dwell, jumps: self._L.bhmm_path_runs(self._h, ctypes.c_void_p(int(ptr)), 1 if u8 else 0,
+                                                             on_dev, off, dwell, jumps), stats)
+
+    def _path_arg(self, paths):
+        """(address, one byte per step, on this engine's GPU) of a flat path, validated against the loaded
+        trajectories before any native call (path_runs, path_logprob)."""
         if self.kind is None:
             raise ValueError("no observations loaded")
         total = int(self.offsets[-1])
@@ -687,9 +695,72 @@ class Engine(object):
             raise ValueError("paths must be a numpy array or an object with data_ptr() / is_cuda")
         if u8 and self.nstates > 256:
             raise ValueError("one byte per step holds at most 256 states (pass an int32 path)")
-        return self._runs_result(
-            lambda off, dwell, jumps: self._L.bhmm_path_runs(self._h, ctypes.c_void_p(int(ptr)), 1 if u8 else 0,
-                                                             on_dev, off, dwell, jumps), stats)
+        return ptr, u8, on_dev
+
+    # -- joint log-probability of a path -----------------------------------------------------
+    def path_logprob(self, paths, models):
+        """Joint log-probability log p(s, O | model) of GIVEN hidden paths under each model (bhmm_path_logprob), per
+        trajectory: log pi(s_0) + e(s_0, o_0) + sum_t [log A(s_t-1, s_t) + e(s_t, o_t)] -- the "Viterbi score" when s
+        is the Viterbi path.  `paths` as path_runs takes them -- a C-contiguous numpy uint8 or int32 array of
+        sum(T_k) states concatenated like the observations (staged on the device), or an object with data_ptr() /
+        is_cuda (a torch uint8 / int32 tensor: on this engine's GPU it is read in place and must be aligned to 16
+        bytes) -- or a list / tuple of one integer array per trajectory.  `models` as score takes them: a list of
+        (A, pi, par0, par1) tuples.  Returns an (S, K) float64 array.  Every term is formed in log space: the
+        gaussian density is never exponentiated and the outlier rule of the recursions (an emission row that
+        underflowed to all zeros counts as all ones) is deliberately NOT applied -- an outlier gives a very negative
+        finite term.  A zero probability on the path gives -inf for that trajectory (never NaN, no other trajectory
+        changes), a NaN observation NaN for its own trajectory, an empty trajectory 0.0; a state outside
+        [0, nstates) raises ValueError.  Path and observations are read once for all models; no floating-point
+        atomics, so the result is bitwise the same from call to call, for a host and a device path, for uint8 and
+        int32, and for a model alone and inside a stack (read-only options "pathlp_tile", "pathlp_lane",
+        "pathlp_table": 1 if the log-transition table sat in LDS, "pathlp_ms": device time)."""
+        if self.kind is None:
+            raise ValueError("no observations loaded")
+        if isinstance(paths, (list, tuple)):
+            paths = self._concat_paths(paths)
+        ptr, u8, on_dev = self._path_arg(paths)
+        A, pi, p0, p1 = stack_models(self.kind, self.nstates, self.nsymbols, models)
+        S = A.shape[0]
+        logp = np.empty((S, len(self.lengths)))
+        _lib.check(self._L.bhmm_path_logprob(self._h, ctypes.c_void_p(int(ptr)), 1 if u8 else 0, on_dev, S, _lib.dp(A),
+                                             _lib.dp(pi), _lib.dp(p0), _lib.dp(p1), _lib.dp(logp)))
+        return logp
+
+    def _concat_paths(self, paths):
+        """One flat uint8 (every piece uint8) or int32 array from one integer array per loaded trajectory."""
+        if len(paths) != len(self.lengths):
+            raise ValueError("expected one path per trajectory (%d), got %d" % (len(self.lengths), len(paths)))
+        pieces = [np.asarray(p) for p in paths]
+        for k, p in enumerate(pieces):
+            if p.ndim != 1 or p.shape[0] != int(self.lengths[k]):
+                raise ValueError("path %d must be 1-d with %d steps, not %r" % (k, int(self.lengths[k]), p.shape))
+            if p.size and not np.issubdtype(p.dtype, np.integer):
+                raise ValueError("path %d must hold integers, not %s" % (k, p.dtype.name))
+        dtype = np.uint8 if all(p.dtype == np.uint8 for p in pieces if p.size) else np.int32
+        flat = np.empty(int(self.offsets[-1]), dtype=dtype)
+        for k, p in enumerate(pieces):
+            if p.size and dtype == np.int32 and (p.min() < np.iinfo(np.int32).min or p.max() > np.iinfo(np.int32).max):
+                raise ValueError("path %d holds a state outside int32" % k)
+            flat[self.offsets[k]:self.offsets[k + 1]] = p
+        return flat
+
+    def decode_logprob(self, A, pi, par0=None, par1=None, method='viterbi'):
+        """Decode every loaded trajectory under one model and return the joint log-probability of the decoded path
+        under that model (bhmm_decode_logprob), a (K,) float64 array: method 'viterbi' runs what viterbi_u8 runs
+        into a device buffer (the result is the Viterbi score), 'posterior' what posterior_decode runs up to its
+        copy to the host -- the same kernels, options and side effects on the engine -- and the path is scored on
+        the device: only K numbers cross the link.  A posterior-decoded path can take a jump the model forbids: its
+        trajectory scores -inf.  Terms as for path_logprob (log space, no outlier rule).  Up to 256 states (more:
+        decode with viterbi / posterior_decode and call path_logprob on the int32 path)."""
+        if method not in _METHODS:
+            raise ValueError("method must be 'viterbi' or 'posterior', not %r" % (method,))
+        self._check_model(A, pi, par0, par1)
+        if self.nstates > 256:
+            raise ValueError("decode_logprob handles up to 256 states (decode, then path_logprob on the int32 path)")
+        A, pi, p0, p1 = self._model_ptrs(A, pi, par0, par1)
+        logp = np.empty(len(self.lengths))
+        _lib.check(self._L.bhmm_decode_logprob(self._h, A, pi, p0, p1, _METHODS[method], _lib.dp(logp)))
+        return logp
 
     def decode_runs(self, A, pi, par0=None, par1=None, method='viterbi', stats=False):
         """Decode every loaded trajectory under one model and return the dwell segments of the decoded path

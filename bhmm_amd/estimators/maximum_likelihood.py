@@ -483,6 +483,24 @@ class MaximumLikelihoodEstimator(object):
                 dwell, jumps = res.dwell, res.jumps
         return (segs, dwell, jumps) if stats else segs
 
+    def hidden_state_logprob(self, method='viterbi'):
+        """Joint log-probability log p(s, O | hmm) of the decoded hidden path of every trajectory under the current
+        (fitted) hmm (Engine.decode_logprob): method 'viterbi' -- the Viterbi score -- or 'posterior' (-inf where the
+        posterior-decoded path takes a jump the model forbids); the path is decoded and scored on the GPU and only
+        one number per trajectory crosses the link.  Returns a (number of trajectories,) float64 array in the
+        caller's trajectory order.  With a process_group every rank scores the trajectories it holds and the
+        entries of the others are NaN (local_trajectories lists the ones filled); there is no collective.  Up to
+        256 states."""
+        if method not in ('viterbi', 'posterior'):
+            raise ValueError("method must be 'viterbi' or 'posterior', not %r" % (method,))
+        par0, par1 = self._hmm.output_model.parameters()
+        out = np.full(self._nobs, np.nan)
+        if self._mine:
+            res = self._engine.decode_logprob(self._hmm.transition_matrix, self._hmm.initial_distribution, par0, par1,
+                                              method=method)
+            out[np.asarray(self._mine, dtype=np.int64)] = res
+        return out
+
     def score(self, models=None):
         """Total log-likelihood of the estimator's observations under each model (forward pass
         only, Engine.score): `models` is one HMM, a list of HMMs or (A, pi, par0, par1) tuples, or

@@ -15,7 +15,7 @@ from ..util import config
 
 __all__ = ['set_implementation', 'forward', 'backward', 'state_probabilities', 'state_counts',
            'transition_counts', 'viterbi', 'sample_path', 'posterior_decode', 'posterior_marginals',
-           'posterior_transitions', 'filter_states']
+           'posterior_transitions', 'filter_states', 'path_logprob']
 
 __IMPL_HIP__ = 2
 __impl__ = __IMPL_HIP__
@@ -289,3 +289,32 @@ def filter_states(A, pobs, pi, weights=None, dtype=np.float64, probabilities=Tru
     finally:
         eng.close()
     return (rows[0] if rows is not None else None), (logc[0] if logc is not None else None)
+
+
+def path_logprob(A, pobs, pi, path):
+    """Joint log-probability of one trajectory's hidden path given its pobs rows, in one call (no twin in the
+    reference): log pi[path[0]] + log pobs[0, path[0]] + sum_t (log A[path[t-1], path[t]] + log pobs[t, path[t]]),
+    every term formed in log space, as a float; -inf when the path has probability zero.  `path`: T integers in
+    [0, N) (a state outside raises ValueError).  Explicit pobs gather one double per step in bhmm_path_logprob."""
+    _check_dtype()
+    A_, p_, pi_ = _lib.f64(A), _lib.f64(pobs), _lib.f64(pi)
+    N = A_.shape[0] if A_.ndim == 2 else -1
+    if A_.ndim != 2 or A_.shape != (N, N) or pi_.shape != (N,) or p_.ndim != 2 or p_.shape[1] != N:
+        raise ValueError('A must be (N, N), pi (N,) and pobs (T, N)')
+    if p_.shape[0] < 1:
+        raise ValueError('pobs has no rows')
+    s = np.asarray(path)
+    if s.ndim != 1 or s.shape[0] != p_.shape[0]:
+        raise ValueError('path must hold one state per row of pobs')
+    if not np.issubdtype(s.dtype, np.integer):
+        raise ValueError('path must hold integers, not ' + s.dtype.name)
+    if s.min() < 0 or s.max() >= N:
+        raise ValueError('path holds a state outside [0, N)')
+    s = np.ascontiguousarray(s, dtype=np.uint8 if N <= 256 else np.int32)
+    from ..engine import Engine
+    eng = Engine(0)
+    try:
+        eng.set_observations('explicit', [p_], N)
+        return float(eng.path_logprob(s, [(A_, pi_, None, None)])[0, 0])
+    finally:
+        eng.close()

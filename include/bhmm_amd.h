@@ -429,6 +429,38 @@ int bhmm_decode_runs(bhmm_ctx *ctx, const double *A, const double *pi, const dou
                      int method, int64_t *run_off, int64_t *dwell, int64_t *jumps);
 int bhmm_runs_fetch(bhmm_ctx *ctx, int64_t *start, int64_t *length, int32_t *state);
 
+/* Joint log-probability of GIVEN hidden paths, log p(s, O | model) -- the "Viterbi score" when s is the Viterbi path
+ * (DESIGN.md section 22).  For trajectory k with observations o_0 .. o_{T-1}, path s_0 .. s_{T-1} and model m:
+ *   logp[m * K + k] = log pi(s_0) + e(s_0, o_0) + sum_{t >= 1} [ log A(s_{t-1}, s_t) + e(s_t, o_t) ]
+ * with every term formed in log space: gaussian e(i, o) = -((o - mu_i) / sigma_i)^2 / 2 - log sigma_i - log(2 pi) / 2
+ * (the density is never exponentiated), discrete e(i, o) = log B[i, o], explicit pobs e(i, t) = log pobs[t, i].  The
+ * gaussian outlier rule of the recursions (an emission row that underflowed to all zeros counts as all ones) is
+ * deliberately NOT applied: an outlier gives a very negative finite term here.  A zero probability gives log 0 = -inf
+ * and that trajectory's result is -inf, never NaN, and no other trajectory's changes; a NaN gaussian observation makes
+ * its own trajectory's result NaN; an empty trajectory gives 0.0.
+ * bhmm_path_logprob: paths as for bhmm_path_runs -- flat and trajectory-concatenated, path_u8 != 0 one byte per step
+ * (more than 256 states: BHMM_ERR_INVALID), else int32; paths_on_device == 0: a host buffer, staged in a buffer of
+ * this call's own; != 0: a device buffer on the context's device, aligned to 16 bytes (BHMM_ERR_INVALID otherwise),
+ * read in place.  A state outside [0, N) gives BHMM_ERR_INVALID: it is flagged before anything is indexed by it and
+ * nothing is delivered.  The nmodels models are stacked and validated as for bhmm_score (zeros in A, pi and B are
+ * legal); all three emission kinds, any N up to 4096.  The trajectories are those of the context's offsets (the views
+ * of a lagged set count as trajectories).  The path and the observations are read ONCE for all models.
+ * logp[nmodels * K] (host, row m = model m).
+ * bhmm_decode_logprob decodes exactly as bhmm_decode_runs does (method 0: what bhmm_viterbi_batch_u8 with
+ * paths_on_device != 0 runs, into a buffer of this call's own; method 1: what bhmm_posterior_decode runs up to the
+ * copy to the host -- the same kernels, options, counters and side effects) and scores the decoded path under the
+ * same model where it lies: only K doubles cross the link.  Up to 256 states (BHMM_ERR_INVALID above).  logp[K].
+ * Both calls are synchronous and touch no other call's state (bhmm_decode_logprob: beyond what the decoders touch).
+ * No floating-point atomics: the result is bitwise reproducible from call to call, the same for a host and a device
+ * path, for bytes and int32 at the same states, and for a model alone and anywhere inside a stack.
+ * Read-only options: pathlp_tile (steps per workgroup), pathlp_lane (consecutive steps per lane), pathlp_table (1: the
+ * last call kept the log-transition table in LDS, 0: it read it through L2), pathlp_ms (device time of the last
+ * call's passes). */
+int bhmm_path_logprob(bhmm_ctx *ctx, const void *paths, int path_u8, int paths_on_device, int nmodels,
+                      const double *A, const double *pi, const double *par0, const double *par1, double *logp);
+int bhmm_decode_logprob(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0, const double *par1,
+                        int method, double *logp);
+
 /* Gibbs hidden-path step (bayesian_sampling.py:283-331): forward pass + backward sampling
  * of every trajectory.  Uniforms come either from u (host, concatenated like obs; u[t]
  * used at step t) or, when u == NULL, from a counter-based generator seeded with `seed`.
