@@ -1132,7 +1132,7 @@ static void new_observation_set(bhmm_ctx *c)
     // runs for half a pass (6.7 ms at configs[3]) where margins + mending take 2.6; on white-noise data the round is
     // 0.5 ms cheaper.  Below 33 states a round is short either way: there the rule waits for a call that needed it.
     // (BHMM_AMD_VIT_MARGIN_FORCE: the rule at every state count, for the sweeps)
-    c->ds.vit_margin_want = getenv("BHMM_AMD_VIT_MARGIN_FORCE") != nullptr || (c->n > 32 && c->n <= 64);
+    c->ds.vit.margin_want = getenv("BHMM_AMD_VIT_MARGIN_FORCE") != nullptr || (c->n > 32 && c->n <= 64);
 }
 
 int bhmm_ctx_set_observations(bhmm_ctx *c, int kind, const void *obs, const int64_t *offsets, int K,
@@ -1400,11 +1400,11 @@ int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
     } else if (n == "viterbi_W") { // warm-up of the next segment-parallel Viterbi pass (0: from the E-step's)
         if (value < 0 || value > (1 << 20))
             return BHMM_ERR_INVALID;
-        c->ds.vit_W = (int)value;
+        c->ds.vit.W = (int)value;
     } else if (n == "viterbi_margin") { // 9..128 states: the path-margin acceptance of the segment-parallel first pass
         c->opt.vit_margin = value != 0.0;
         if (value == 2.0) // (up to 64 states: from the next call on, not only after a call with two or more rounds)
-            c->ds.vit_margin_want = true;
+            c->ds.vit.margin_want = true;
     } else if (n == "viterbi_mend") { // 9..64 states: segments further than 1e-12 from their predecessors run again alone
         c->opt.vit_mend = value != 0.0;
     } else if (n == "viterbi_seg_per_simd") { // 9..64 states: segments per SIMD of the Viterbi pass
@@ -1412,7 +1412,7 @@ int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
             return BHMM_ERR_INVALID;
         c->opt.vit_seg_per_simd = (int)value;
         c->ds.pplan[0].nseg = 0;
-        c->ds.vit_seg_given_up = false;
+        c->ds.vit.seg_given_up = false;
     } else if (n == "f32_tol") { // BHMM_FLAG_SINGLE: relative tolerance of the fp32 boundary check
         if (!(value >= 1e-7 && value <= 1e-3))
             return invalid_arg("f32_tol outside [1e-7, 1e-3]");
@@ -1425,7 +1425,7 @@ int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
     } else if (n == "spec_W") {
         c->ds.carry_valid = false;
         c->ds.spec_W = std::max(1, (int)value);
-        c->ds.vit_W = 0;
+        c->ds.vit.W = 0;
         c->opt.spec_W_fixed = c->ds.spec_calibrated = true; // the caller's choice: no probe
     }
     else if (n == "draw_watch") // draws inside the reach of the alpha rows' verified deviation are decided again (draw_verify.hpp)
@@ -1553,7 +1553,7 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
     else if (n == "viterbi_close")
         *value = c->last.viterbi_close;
     else if (n == "viterbi_W") // warm-up the chunk-parallel Viterbi last verified with
-        *value = c->ds.vit_W;
+        *value = c->ds.vit.W;
     else if (n == "viterbi_segments") // 9..64 states: time segments of the last Viterbi pass's plan
         *value = c->ds.pplan[0].nseg;
     else if (n == "sample_segmented") // 9..64 states: the last path sampling ran over time segments

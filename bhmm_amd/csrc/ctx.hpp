@@ -205,13 +205,16 @@ struct bhmm_ctx {
             int64_t maxlen = 0; // longest segment of the plan (boundaries are rounded to multiples of four: up to seglen + 3)
         } pplan[3];
         int smp_W = 0;                   // sampler: warm-up (steps above a segment) of the next call
-        bool vit_margin_want = false;    // 9..64 states: a call on these observations needed two or more fix-up rounds (the
-                                         // margin acceptance costs about one short round: it is tried from then on)
-        bool vit_seg_given_up = false;   // ... boundaries did not coalesce on these observations: serial kernel
-        int vit_rows_fail = 0;           // 129..256 states: first passes in a row that were not accepted (two: given up)
-        int vit_W = 0;                   // warm-up the chunked Viterbi last verified with (0: spec_W)
-        int vit_bad = 0;                 // ... a shorter one that did not verify
-        bool vit_explore = true;         // ... still trying shorter ones (path_api.hip)
+        // Viterbi (path_api.hip, gen_api.hip): what the calls on these observations learnt
+        struct Viterbi {
+            bool margin_want = false;    // 9..64 states: a call on these observations needed two or more fix-up rounds
+                                         // (the margin acceptance costs about one short round: tried from then on)
+            bool seg_given_up = false;   // ... boundaries did not coalesce on these observations: serial kernel
+            int rows_fail = 0;           // 129..256 states: first passes in a row that were not accepted (two: given up)
+            int W = 0;                   // warm-up the chunked Viterbi last verified with (0: spec_W)
+            int bad = 0;                 // ... a shorter one that did not verify
+            bool explore = true;         // ... still trying shorter ones (plan.hpp: vit_chunk_attempts)
+        } vit;
         int wide_replans = 0;            // 9..64 states: segment plans re-made after failed checks
         bool wseg_given_up = false;      // ... and segmentation abandoned for this data set
         bool tile_latched = true;        // opt.tile_enabled latched: plans, buffers and launches of one data set all use THIS

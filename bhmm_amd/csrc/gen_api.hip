@@ -13,6 +13,7 @@
 #include "host_internal.hpp"
 #include "launch.hpp"
 #include "gen_kernels.hpp"
+#include "viterbi_host.hpp"
 
 namespace bhmm {
 
@@ -176,6 +177,153 @@ int gen_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par0
     return BHMM_OK;
 }
 
+namespace {
+
+// ---- Viterbi above 64 states: one function per path (VitCall and the shared hooks: viterbi_host.hpp; v.obs is the
+// emission matrix of gen_pobs; the back-trace walks over the segments of plan 0) ----
+// 65..128 states: over time segments (k_gen_viterbi_seg), accepted by seg_viterbi (path_api.hip).  A fix-up round
+// costs half a first pass here, hence the margin rule from the first call on (round 5: 25.7 -> 11 ms) and the
+// mending of the few far boundaries (round 6); warm-up and segment length: plan::vit_gen_*
+int gen_seg_viterbi(bhmm_ctx *c, const WideModel &m, const VitCall &v, bool *done)
+{
+    const int n = c->n, K = c->K;
+    const int64_t *off = c->d_offsets.p;
+    const double *pobs = static_cast<const double *>(v.obs);
+    const size_t smv = (size_t)(128 * GVS_PITCH + 8 * 128) * sizeof(double);
+    const int W0 = plan::vit_w_estep(c->ds.spec_W), seg_warmups = c->opt.vit_margin ? 1 : c->opt.vit_seg_warmups;
+    const int W_cap = plan::vit_gen_w_cap(W0, plan::vit_gen_fill(c->total, c->num_simd, c->opt.vit_seg_per_simd));
+    int W_try = plan::vit_gen_w_start(c->ds.vit.W, W0, W_cap, c->opt.vit_margin, c->opt.vit_mend), rc;
+    const size_t smm = vit_margin_lds(n);
+    double *vall = vit_vall(c, c->opt.vit_margin);
+    if (vall && !(allow_lds(k_vit_margin<int32_t, 2>, smm) == hipSuccess &&
+                  allow_lds(k_vit_margin<uint8_t, 2>, smm) == hipSuccess)) {
+        (void)hipGetLastError();
+        vall = nullptr;
+    }
+    const int64_t maxT = longest_traj(c);
+    for (int attempt = 0; attempt < 2 && !*done; ++attempt) {
+        if (attempt > 0)
+            W_try *= 2;
+        const int64_t seglen = plan::vit_gen_seglen(c->total, c->num_simd, c->opt.vit_seg_per_simd, seg_warmups, W_try);
+        Segs sg;
+        if ((rc = wide_path_plan(c, 0, seglen, sg)))
+            return rc;
+        if (sg.nseg <= K)
+            break;
+        sg.W = W_try;
+        if ((rc = vit_boundary_bufs(c, sg, 128)))
+            return rc;
+        const dim3 sgrid((sg.nseg + 7) / 8), sblk(512);
+        SegViterbi f;
+        f.pass = [&](bool fix) -> int {
+            BHMM_HIP(launch(fix ? k_gen_viterbi_seg<true> : k_gen_viterbi_seg<false>, sgrid, sblk, smv, c->stream, m,
+                            off, sg, pobs, v.ptr, v.last, c->d_aentry.p, c->d_aexit.p, c->d_vckpt.p, c->d_vflag.p,
+                            fix ? nullptr : vall, 0.0, nullptr));
+            BHMM_HIP(launch(k_wide_vit_check<128>, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
+                            c->d_aentry.p, c->d_aexit.p, c->d_vflag.p, c->d_specres.p, (!fix && vall) ? SEG_VIT_TOL : 0.0));
+            return BHMM_OK;
+        };
+        f.mend = [&]() -> int {
+            BHMM_HIP(launch(k_gen_viterbi_seg<true>, sgrid, sblk, smv, c->stream, m, off, sg, pobs, v.ptr, v.last,
+                            c->d_aentry.p, c->d_aexit.p, c->d_vckpt.p, c->d_vflag.p + sg.nseg, vall, SEG_VIT_TOL,
+                            c->d_specres.p + 1));
+            return BHMM_OK;
+        };
+        f.margins = [&](double margin) { return vit_margins<2>(c, v, sg, m.A, smm, vall, margin); };
+        f.walks = [&]() { return vit_walks<2>(c, v, sg, c->pplan_buf[0].traj0.p); };
+        SegVitResult r;
+        if ((rc = seg_viterbi(c, f, sg, seglen, vall, maxT, 12, false, &r)))
+            return rc;
+        if ((*done = r.accepted))
+            vit_accepted(c, r, vall, W_try, W_cap);
+    }
+    vit_attempts_done(c, *done);
+    return BHMM_OK;
+}
+
+// 129..256 states (round 5): four segments per workgroup share every pass over A (k_gen_viterbi_rows); first pass
+// only -- accepted when every boundary is bit-identical or by the margins of the decisions on its path
+// (k_vit_margin), else the serial kernel decides.  Warm-up: plan::vit_rows_w_start (at 256 states one boundary of
+// 749 was still 1e-12 off after 504 steps, none after 750 -- and a pass that is not accepted is lost time)
+int gen_rows_viterbi(bhmm_ctx *c, const WideModel &m, const VitCall &v, bool *done)
+{
+    const int n = c->n, K = c->K;
+    const int64_t *off = c->d_offsets.p;
+    const double *pobs = static_cast<const double *>(v.obs);
+    static_assert(GVR_ROWS == plan::VIT_ROWS, "the plan's segments per workgroup are the kernel's");
+    const int64_t fill0 = plan::vit_rows_fill(c->total, c->num_simd);
+    const int W_try = plan::vit_rows_w_start(c->ds.vit.W, plan::vit_w_estep(c->ds.spec_W), fill0, c->opt.vit_mend);
+    const int64_t seglen = plan::vit_rows_seglen(fill0, W_try), maxT = longest_traj(c);
+    Segs sg;
+    int rc;
+    if ((rc = wide_path_plan(c, 0, seglen, sg)))
+        return rc;
+    c->last.vit_margin_used = c->last.vit_margin_close = c->last.vit_seg_rounds = 0;
+    // two threads per target state (candidate ranges; measured 15.8 / 13.3 / 14.1 ms at 129 states with 1 / 2 / 4)
+    const size_t smr = (size_t)(2 * GVR_ROWS * n + GVR_ROWS) * sizeof(double) +
+                       (size_t)GVR_ROWS * 256 * (sizeof(double) + sizeof(int));
+    // (no plan to gain from, or a buffer that cannot be had: the serial kernel)
+    if (!(sg.nseg > K && (rc = gen_transposed(c, m)) == BHMM_OK && c->d_gW.ensure((size_t)c->total * n) == BHMM_OK &&
+          c->d_aentry.ensure((size_t)sg.nseg * 256) == BHMM_OK && c->d_aexit.ensure((size_t)sg.nseg * 256) == BHMM_OK &&
+          c->d_vflag.ensure(2 * (size_t)sg.nseg) == BHMM_OK && ensure_specres(c) == BHMM_OK &&
+          c->d_vmaps.ensure((size_t)sg.nseg * 256) == BHMM_OK && c->d_vend.ensure((size_t)sg.nseg) == BHMM_OK)) {
+        (void)hipGetLastError();
+        return BHMM_OK;
+    }
+    sg.W = W_try;
+    double *vall = c->d_gW.p;
+    const dim3 rgrid((sg.nseg + GVR_ROWS - 1) / GVR_ROWS), rblk(512);
+    SegViterbi f;
+    f.pass = [&](bool) -> int { // (first pass only: no fix-up rounds)
+        BHMM_HIP(launch(k_gen_viterbi_rows<GVR_ROWS, 2>, rgrid, rblk, smr, c->stream, m, off, sg, pobs, v.ptr, v.last,
+                        c->d_aentry.p, c->d_aexit.p, vall, nullptr, 0.0, nullptr));
+        BHMM_HIP(launch(k_wide_vit_check<256>, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
+                        c->d_aentry.p, c->d_aexit.p, c->d_vflag.p, c->d_specres.p, SEG_VIT_TOL));
+        return BHMM_OK;
+    };
+    f.mend = [&]() -> int {
+        BHMM_HIP(launch(k_gen_viterbi_rows<GVR_ROWS, 2, true>, rgrid, rblk, smr, c->stream, m, off, sg, pobs, v.ptr,
+                        v.last, c->d_aentry.p, c->d_aexit.p, vall, c->d_vflag.p + sg.nseg, SEG_VIT_TOL,
+                        c->d_specres.p + 1));
+        return BHMM_OK;
+    };
+    f.margins = [&](double margin) { return vit_margins<4, false>(c, v, sg, c->d_gAt.p, 0, vall, margin); };
+    // (the back-trace of the pass is needed either way: enqueued before its verdict is read)
+    f.walks = [&]() { return vit_walks<4>(c, v, sg, c->pplan_buf[0].traj0.p); };
+    SegVitResult r;
+    if ((rc = seg_viterbi(c, f, sg, seglen, vall, maxT, 0, true, &r)))
+        return rc;
+    if ((*done = c->last.viterbi_chunked = r.accepted)) {
+        c->ds.vit.W = W_try;
+        c->ds.vit.rows_fail = 0;
+    } else if (plan::vit_rows_give_up(++c->ds.vit.rows_fail, W_try, maxT)) {
+        // (one pass that was not accepted -- an early EM iterate, say -- only doubles the next call's warm-up)
+        c->ds.vit.seg_given_up = true;
+    } else {
+        c->ds.vit.W = 2 * W_try;
+    }
+    return BHMM_OK;
+}
+
+// one workgroup per trajectory (k_gen_viterbi_fwd, back-pointers of two bytes) and the trace
+int gen_serial_viterbi(bhmm_ctx *c, const WideModel &m, const VitCall &v)
+{
+    const int n = c->n, K = c->K;
+    uint16_t *ptr = reinterpret_cast<uint16_t *>(v.ptr);
+    size_t sm = gen_smem(n, 2, 2);
+    const bool alds = gen_a_in_lds(n, sm);
+    sm += alds ? gen_a_bytes(n) : 0;
+    BHMM_HIP(launch(alds ? k_gen_viterbi_fwd<true> : k_gen_viterbi_fwd<false>, dim3(K), dim3(GEN_TPB), sm, c->stream, m,
+                    c->d_offsets.p, K, static_cast<const double *>(v.obs), ptr, v.last));
+    BHMM_HIP(v.out([&](auto *p) {
+        return launch(k_gen_viterbi_trace<std::remove_pointer_t<decltype(p)>>, dim3((K + 63) / 64), dim3(64), 0, c->stream,
+                      c->d_offsets.p, K, n, ptr, v.last, p);
+    }));
+    return BHMM_OK;
+}
+
+} // namespace
+
 // out_fmt as wide_viterbi_run: 0 int32 host, 1 uint8 host, 2 uint8 device (N <= 256 for the bytes)
 int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
                     const double *par1, void *paths_out, int out_fmt)
@@ -194,200 +342,17 @@ int gen_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double
         (rc = c->d_scratch.ensure((size_t)c->total * n * sizeof(uint16_t))) ||
         (rc = c->d_scratch2.ensure(((size_t)c->total + K) * sizeof(int32_t))))
         return rc;
-    uint16_t *ptr = reinterpret_cast<uint16_t *>(c->d_scratch.p);
-    int32_t *last = reinterpret_cast<int32_t *>(c->d_scratch2.p);
-    int32_t *path = last + K;
-    uint8_t *ptr8 = reinterpret_cast<uint8_t *>(c->d_scratch.p);
-    uint8_t *p8 = out_fmt == 2 ? static_cast<uint8_t *>(paths_out) : reinterpret_cast<uint8_t *>(path);
-    const int64_t *off = c->d_offsets.p;
-    const int64_t maxT = longest_traj(c);
-    const int W0 = std::max(64, c->ds.spec_W > 0 ? (c->ds.spec_W + 7) / 8 * 8 : 128);
-    // back-trace over the segments of plan 0: maps, stitch, apply (NC: column tiles of the back-pointer maps)
-    auto walks_of = [&](const Segs &sg, auto ncc) -> int {
-        constexpr int NC = decltype(ncc)::value;
-        int rcw;
-        if ((rcw = c->d_vmaps.ensure((size_t)sg.nseg * 64 * NC)) || (rcw = c->d_vend.ensure((size_t)sg.nseg)))
-            return rcw;
-        BHMM_HIP(launch(k_wide_vit_walk<false, uint8_t, NC>, dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n, ptr8,
-                        c->d_vmaps.p, nullptr, nullptr));
-        BHMM_HIP(launch(k_wide_vit_stitch, dim3((K + 63) / 64), dim3(64), 0, c->stream, c->pplan_buf[0].traj0.p, K,
-                        c->d_vmaps.p, 64 * NC, last, c->d_vend.p));
-        auto walk = [&](auto *k, auto *out) {
-            return launch(k, dim3(sg.nseg), dim3(64), 0, c->stream, off, sg, n, ptr8, nullptr, c->d_vend.p, out);
-        };
-        BHMM_HIP(out_fmt == 0 ? walk(k_wide_vit_walk<true, int32_t, NC>, path) : walk(k_wide_vit_walk<true, uint8_t, NC>, p8));
-        return BHMM_OK;
-    };
-    // up to 128 states: over time segments (k_gen_viterbi_seg), accepted by seg_viterbi (path_api.hip)
-    if (n <= 128 && c->opt.spec_enabled && !c->ds.vit_seg_given_up) {
-        bool done = false;
-        const size_t smv = (size_t)(128 * GVS_PITCH + 8 * 128) * sizeof(double);
-        // warm-up: the max-product survivors of these larger models meet later than the filter forgets (128
-        // states, 128 x 10 000: 236 of 2048 boundaries further than 1e-12 apart after the E-step's 120 steps, 4
-        // after 240, none after 480), and a fix-up round costs half a first pass here: four times the E-step's
-        // length, and segments as short as one warm-up (round 5; with the path-margin acceptance 25.7 -> 11 ms)
-        // -- but never longer than the segments that fill the chip (a slowly forgetting model keeps the E-step's
-        // length and its segment count; the rounds then do what the margins cannot)
-        const int seg_warmups = c->opt.vit_margin ? 1 : c->opt.vit_seg_warmups;
-        const int64_t fill0 = ((c->total + (int64_t)c->opt.vit_seg_per_simd * c->num_simd - 1) /
-                               ((int64_t)c->opt.vit_seg_per_simd * c->num_simd) + 7) / 8 * 8;
-        // (round 6: with the mending round the E-step's length is where the margin route starts too -- the few
-        // boundaries that need the fourfold length are repaired alone; the length doubles for the next call, up to
-        // that fourfold, when a pass could not be mended or needed three or more rounds)
-        const int W_cap = (int)std::max<int64_t>(W0, std::min<int64_t>(4 * (int64_t)W0, fill0));
-        int W_try = c->ds.vit_W > 0 ? c->ds.vit_W : ((c->opt.vit_margin && !c->opt.vit_mend) ? W_cap : W0);
-        // the path-margin acceptance of the first pass (k_vit_margin, path_kernels.hpp)
-        double *vall = nullptr;
-        const size_t smm = (size_t)n * (n | 1) * sizeof(double); // (odd pitch, k_vit_margin)
-        if (c->opt.vit_margin && c->d_gW.ensure((size_t)c->total * n) == BHMM_OK &&
-            allow_lds(k_vit_margin<int32_t, 2>, smm) == hipSuccess &&
-            allow_lds(k_vit_margin<uint8_t, 2>, smm) == hipSuccess)
-            vall = c->d_gW.p;
-        else
-            (void)hipGetLastError();
-        c->last.vit_margin_used = 0;
-        c->last.vit_margin_close = 0;
-        for (int attempt = 0; attempt < 2 && !done; ++attempt) {
-            if (attempt > 0)
-                W_try *= 2;
-            const int64_t want = (int64_t)c->opt.vit_seg_per_simd * c->num_simd;
-            const int64_t seglen = std::max<int64_t>((c->total + want - 1) / want, seg_warmups * (int64_t)W_try);
-            Segs sg;
-            if ((rc = wide_path_plan(c, 0, seglen, sg)))
-                return rc;
-            if (sg.nseg <= K)
-                break;
-            sg.W = W_try;
-            if ((rc = c->d_aentry.ensure((size_t)sg.nseg * 128)) || (rc = c->d_aexit.ensure((size_t)sg.nseg * 128)) ||
-                (rc = c->d_vckpt.ensure(((size_t)(c->total >> 6) + 1) * 128)) || (rc = c->d_vflag.ensure(2 * (size_t)sg.nseg)))
-                return rc;
-            const dim3 sgrid((sg.nseg + 7) / 8), sblk(512);
-            SegViterbi f;
-            f.pass = [&](bool fix) -> int {
-                BHMM_HIP(launch(fix ? k_gen_viterbi_seg<true> : k_gen_viterbi_seg<false>, sgrid, sblk, smv, c->stream, m,
-                                off, sg, pobs, ptr8, last, c->d_aentry.p, c->d_aexit.p, c->d_vckpt.p, c->d_vflag.p,
-                                fix ? nullptr : vall, 0.0, nullptr));
-                BHMM_HIP(launch(k_wide_vit_check<128>, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
-                                c->d_aentry.p, c->d_aexit.p, c->d_vflag.p, c->d_specres.p, (!fix && vall) ? SEG_VIT_TOL : 0.0));
-                return BHMM_OK;
-            };
-            f.mend = [&]() -> int {
-                BHMM_HIP(launch(k_gen_viterbi_seg<true>, sgrid, sblk, smv, c->stream, m, off, sg, pobs, ptr8, last,
-                                c->d_aentry.p, c->d_aexit.p, c->d_vckpt.p, c->d_vflag.p + sg.nseg, vall, SEG_VIT_TOL,
-                                c->d_specres.p + 1));
-                return BHMM_OK;
-            };
-            f.margins = [&](double margin) -> int {
-                const dim3 mgrid(sg.nseg, (unsigned)((c->ds.pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
-                auto margins = [&](auto *k, auto *p) {
-                    return launch(k, mgrid, dim3(256), smm, c->stream, m.A, n, off, sg, vall, p, margin, c->d_specres.p);
-                };
-                BHMM_HIP(out_fmt == 0 ? margins(k_vit_margin<int32_t, 2>, path) : margins(k_vit_margin<uint8_t, 2>, p8));
-                return BHMM_OK;
-            };
-            f.walks = [&]() { return walks_of(sg, std::integral_constant<int, 2>{}); };
-            SegVitResult r;
-            if ((rc = seg_viterbi(c, f, sg, seglen, vall, maxT, 12, false, &r)))
-                return rc;
-            if (r.accepted) {
-                done = true;
-                // (what converged is where the next call on these observations starts; longer after a pass whose far
-                // boundaries could not be mended or that needed three or more rounds)
-                const bool longer = !r.margin_accepted && ((vall && c->last.vit_far > 0) || r.rounds >= 3);
-                c->ds.vit_W = (longer && W_try < W_cap) ? std::min(2 * W_try, W_cap) : W_try;
-            }
-        }
-        if (!done && c->ds.pplan[0].nseg > K)
-            c->ds.vit_seg_given_up = true; // these observations go to the serial kernel from now on
-        c->last.viterbi_chunked = done;
-        if (done)
-            return deliver_paths(c, paths_out, out_fmt, path);
-    }
-    // 129 .. 256 states (round 5): four segments per workgroup share every pass over A (k_gen_viterbi_rows); first
-    // pass only -- accepted when every boundary is bit-identical or by the margins of the decisions on its path
-    // (k_vit_margin), else the serial kernel below decides
-    if (n > 128 && n <= 256 && c->opt.spec_enabled && c->opt.vit_margin && !c->ds.vit_seg_given_up) {
-        const int64_t want = (int64_t)GVR_ROWS * (c->num_simd / 4); // one workgroup of four segments per compute unit
-        const int64_t fill0 = ((c->total + want - 1) / want + 7) / 8 * 8;
-        // (six E-step forgetting lengths, at most one and a half fill lengths: at 256 states one boundary of 749 was
-        // still 1e-12 off after 504 steps, none after 750 -- and a pass that is not accepted is lost time)
-        // (round 6: with the mending round the E-step's length; a pass that is not accepted doubles it for the next call)
-        const int W_try = c->ds.vit_W > 0 ? c->ds.vit_W
-                          : (c->opt.vit_mend ? W0
-                                         : (int)std::max<int64_t>(W0, std::min<int64_t>(6 * (int64_t)W0, (3 * fill0 / 2 + 7) / 8 * 8)));
-        const int64_t seglen = std::max<int64_t>(fill0, W_try);
-        Segs sg;
-        if ((rc = wide_path_plan(c, 0, seglen, sg)))
-            return rc;
-        c->last.vit_margin_used = 0;
-        c->last.vit_margin_close = 0;
-        c->last.vit_seg_rounds = 0;
-        // two threads per target state (candidate ranges; measured 15.8 / 13.3 / 14.1 ms at 129 states with 1 / 2 / 4)
-        const size_t smr = (size_t)(2 * GVR_ROWS * n + GVR_ROWS) * sizeof(double) +
-                           (size_t)GVR_ROWS * 256 * (sizeof(double) + sizeof(int));
-        if (sg.nseg > K && (rc = gen_transposed(c, m)) == BHMM_OK && c->d_gW.ensure((size_t)c->total * n) == BHMM_OK &&
-            c->d_aentry.ensure((size_t)sg.nseg * 256) == BHMM_OK && c->d_aexit.ensure((size_t)sg.nseg * 256) == BHMM_OK &&
-            c->d_vflag.ensure(2 * (size_t)sg.nseg) == BHMM_OK && ensure_specres(c) == BHMM_OK &&
-            c->d_vmaps.ensure((size_t)sg.nseg * 256) == BHMM_OK && c->d_vend.ensure((size_t)sg.nseg) == BHMM_OK) {
-            sg.W = W_try;
-            double *vall = c->d_gW.p;
-            const dim3 rgrid((sg.nseg + GVR_ROWS - 1) / GVR_ROWS), rblk(512);
-            SegViterbi f;
-            f.pass = [&](bool) -> int { // (first pass only: no fix-up rounds)
-                BHMM_HIP(launch(k_gen_viterbi_rows<GVR_ROWS, 2>, rgrid, rblk, smr, c->stream, m, off, sg, pobs, ptr8, last,
-                                c->d_aentry.p, c->d_aexit.p, vall, nullptr, 0.0, nullptr));
-                BHMM_HIP(launch(k_wide_vit_check<256>, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
-                                c->d_aentry.p, c->d_aexit.p, c->d_vflag.p, c->d_specres.p, SEG_VIT_TOL));
-                return BHMM_OK;
-            };
-            f.mend = [&]() -> int {
-                BHMM_HIP(launch(k_gen_viterbi_rows<GVR_ROWS, 2, true>, rgrid, rblk, smr, c->stream, m, off, sg, pobs, ptr8,
-                                last, c->d_aentry.p, c->d_aexit.p, vall, c->d_vflag.p + sg.nseg, SEG_VIT_TOL,
-                                c->d_specres.p + 1));
-                return BHMM_OK;
-            };
-            f.margins = [&](double margin) -> int {
-                const dim3 mgrid(sg.nseg, (unsigned)((c->ds.pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
-                auto margins = [&](auto *k, auto *p) {
-                    return launch(k, mgrid, dim3(256), 0, c->stream, c->d_gAt.p, n, off, sg, vall, p, margin, c->d_specres.p);
-                };
-                BHMM_HIP(out_fmt == 0 ? margins(k_vit_margin<int32_t, 4, false>, path)
-                                      : margins(k_vit_margin<uint8_t, 4, false>, p8));
-                return BHMM_OK;
-            };
-            // (the back-trace of the pass is needed either way: enqueued before its verdict is read)
-            f.walks = [&]() { return walks_of(sg, std::integral_constant<int, 4>{}); };
-            SegVitResult r;
-            if ((rc = seg_viterbi(c, f, sg, seglen, vall, maxT, 0, true, &r)))
-                return rc;
-            if (r.accepted) {
-                c->last.viterbi_chunked = true;
-                c->ds.vit_W = W_try;
-                c->ds.vit_rows_fail = 0;
-                return deliver_paths(c, paths_out, out_fmt, path);
-            }
-            // One pass that was not accepted (a close decision under THIS model -- an early EM iterate, say) sends
-            // this call to the serial kernel; the next call tries again with twice the warm-up, and only a second
-            // failure in a row (or a warm-up that would exceed half a trajectory) gives the observations up.
-            if (++c->ds.vit_rows_fail >= 2 || 4 * (int64_t)W_try > maxT)
-                c->ds.vit_seg_given_up = true;
-            else
-                c->ds.vit_W = 2 * W_try;
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    size_t sm = gen_smem(n, 2, 2);
-    const bool alds = gen_a_in_lds(n, sm);
-    sm += alds ? gen_a_bytes(n) : 0;
-    auto *kvf = alds ? k_gen_viterbi_fwd<true> : k_gen_viterbi_fwd<false>;
-    BHMM_HIP(launch(kvf, dim3(K), dim3(GEN_TPB), sm, c->stream, m, off, K, pobs, ptr, last));
-    const dim3 tg((K + 63) / 64), tb(64);
-    if (out_fmt == 0)
-        BHMM_HIP(launch(k_gen_viterbi_trace<int32_t>, tg, tb, 0, c->stream, off, K, n, ptr, last, path));
-    else
-        BHMM_HIP(launch(k_gen_viterbi_trace<uint8_t>, tg, tb, 0, c->stream, off, K, n, ptr, last, p8));
-    return deliver_paths(c, paths_out, out_fmt, path);
+    // (one byte per back-pointer in the segment passes, two in the serial kernel)
+    const VitCall v = vit_call(c, paths_out, out_fmt, pobs, EMIT_EXPL);
+    bool done = false;
+    const bool segments = c->opt.spec_enabled && !c->ds.vit.seg_given_up;
+    if (n <= 128 && segments)
+        rc = gen_seg_viterbi(c, m, v, &done);
+    else if (n <= 256 && segments && c->opt.vit_margin)
+        rc = gen_rows_viterbi(c, m, v, &done);
+    if (rc || (!done && (rc = gen_serial_viterbi(c, m, v))))
+        return rc;
+    return deliver_paths(c, paths_out, out_fmt, v.path);
 }
 
 // alpha_dev: rows to sample from (the context's own forward pass when NULL)

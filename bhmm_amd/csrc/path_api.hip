@@ -16,6 +16,7 @@
 #include "plan.hpp"
 #include "path_kernels.hpp"
 #include "draw_verify.hpp"
+#include "viterbi_host.hpp"
 
 namespace bhmm {
 
@@ -577,10 +578,248 @@ int seg_draw(bhmm_ctx *c, const SegDraw &f, const double *A, const double *pi, c
 
 namespace {
 
-// ---- 9..64 states ---------------------------------------------------------------------
-// out_fmt: 0 = int32 paths to a host buffer (the reference's type, hidden.pyx:161-162),
-// 1 = one byte per step to a host buffer, 2 = one byte per step into a device buffer of the
-// context's device (written by the back-trace kernels directly, no copy at all)
+// ---- Viterbi, up to 64 states: one function per path (what they share: VitCall, viterbi_host.hpp) ----
+// Emission probabilities in a separate, fully parallel pass when the (total, n) matrix fits (it is what the
+// reference materialises anyway, maximum_likelihood.py:345-347) -- unless the kernels of the run evaluate them
+template <int KIND>
+hipError_t launch_pobs(bhmm_ctx *c, const WideModel &m, const void *obs)
+{
+    // one thread per element where n is a power of two (coalesced stores), else per step
+    const dim3 pl((unsigned)(((size_t)c->total * c->n + 256 * POBS_LANES_R - 1) / (256 * POBS_LANES_R)));
+    auto lanes = [&](auto nl) {
+        return launch(k_pobs_lanes<KIND, decltype(nl)::value>, pl, dim3(256), 0, c->stream, m, obs, c->total, c->d_alpha_rm.p);
+    };
+    switch (c->n) {
+    case 2: return lanes(std::integral_constant<int, 2>());
+    case 4: return lanes(std::integral_constant<int, 4>());
+    case 8: return lanes(std::integral_constant<int, 8>());
+    case 16: return lanes(std::integral_constant<int, 16>());
+    case 32: return lanes(std::integral_constant<int, 32>());
+    case 64: return lanes(std::integral_constant<int, 64>());
+    }
+    return launch(k_pobs_all<KIND>, dim3((unsigned)((c->total + 255) / 256)), dim3(256), 0, c->stream, m, obs, c->total,
+                  c->d_alpha_rm.p);
+}
+int viterbi_emissions(bhmm_ctx *c, const WideModel &m, VitCall &v)
+{
+    // n <= 8 with a chunk plan: the chunk-parallel kernel evaluates the emission itself (gathers from B / evaluates the
+    // gaussian density): no (total, n) emission matrix is written and re-read
+    const bool disc_direct = !c->wide && c->kind != EMIT_EXPL && c->opt.spec_enabled && c->G > c->K;
+    // 9..64 states over time segments, discrete: the kernel gathers from B itself (no (total, n) matrix).  Measured
+    // for the Gaussian kind too: the division by sigma and the exponential in every step, warm-ups included, cost more
+    // than the matrix pass saves (64 states: 9.0 -> 9.7 ms, 16: 0.67 -> 0.81).  (round 6: the Gaussian density in the
+    // step too, with the reciprocal-based quotient and the one-block exponential of k_pobs_lanes -- at 64 states:
+    // 6.5 GB less written and read again per call)
+    const bool wide_direct = c->wide && (c->kind == EMIT_DISC || c->kind == EMIT_GAUSS) && c->opt.spec_enabled &&
+                             !c->ds.vit.seg_given_up;
+    if (c->kind == EMIT_EXPL || disc_direct || wide_direct)
+        return BHMM_OK;
+    size_t freeb = 0, totb = 0;
+    const size_t need = (size_t)c->total * c->n * sizeof(double);
+    if (hipMemGetInfo(&freeb, &totb) == hipSuccess && need + ((size_t)1 << 30) < freeb + c->d_alpha_rm.n * sizeof(double) &&
+        c->d_alpha_rm.ensure((size_t)c->total * c->n) == BHMM_OK) {
+        BHMM_HIP(c->kind == EMIT_GAUSS ? launch_pobs<EMIT_GAUSS>(c, m, v.obs) : launch_pobs<EMIT_DISC>(c, m, v.obs));
+        v.obs = c->d_alpha_rm.p;
+        v.kind = EMIT_EXPL;
+    } else {
+        (void)hipGetLastError();
+    }
+    return BHMM_OK;
+}
+
+// ---- 8 states and fewer with a chunk plan: the chunk-parallel run (k_viterbi_chunks); its back-pointers are
+// accepted only if every chunk boundary verifies and no decision was close ----
+// Back-trace of such a run (k_vit_walk, maps -> stitch -> paths), parallel over chunks; VNP lanes per chunk (models
+// of up to four states: four lanes, 16 chunks per wavefront)
+template <int VNP>
+hipError_t chunk_walks(bhmm_ctx *c, const VitCall &v)
+{
+    const int K = c->K, n = c->n;
+    const Chunks chs = chunks_of(c);
+    const dim3 wg((c->G + 64 / VNP - 1) / (64 / VNP));
+    uint32_t *vmaps = reinterpret_cast<uint32_t *>(v.path + c->total); // chunk maps,
+    int32_t *vend = reinterpret_cast<int32_t *>(vmaps + c->Gp);        // state at each chunk's end,
+    int32_t *vcoal = vend + c->Gp; // step below which the map pass wrote the path itself (k_vit_walk)
+    return v.out([&](auto *out) {
+        using PT = std::remove_pointer_t<decltype(out)>;
+        hipError_t e = launch(k_vit_walk<VNP, false, PT>, wg, dim3(64), 0, c->stream, chs, c->G, n, v.ptr, nullptr, vmaps, out,
+                              vcoal);
+        if (e == hipSuccess)
+            e = (int64_t)c->G >= (int64_t)32 * K
+                    ? launch(k_smp_stitch, dim3(K), dim3(64), 0, c->stream, c->d_traj_c0.p, K, 1, vmaps, vend, v.last)
+                    : launch(k_smp_stitch_serial, dim3((K + SMP_STITCH_TPB - 1) / SMP_STITCH_TPB), dim3(64), 0, c->stream,
+                             c->d_traj_c0.p, K, 1, vmaps, vend, v.last);
+        if (e == hipSuccess)
+            e = launch(k_vit_walk<VNP, true, PT>, wg, dim3(64), 0, c->stream, chs, c->G, n, v.ptr, vend, nullptr, out, vcoal);
+        return e;
+    });
+}
+// A warm-up too short for some boundary (the survivors of that stretch had not met yet) shows as a boundary out of
+// tolerance: the run is repeated with a longer one (~1 ms a pass) before the serial kernel (tens of ms) has to decide.
+// The warm-up is THIS recursion's (round 4): the max-product chains coalesce faster than the E-step's filter forgets
+// (configs[1]: bit-identical boundaries from W ~ 128 on, the probe says 280); the lengths: plan::vit_chunk_attempts
+template <int VNP>
+int chunk_viterbi(bhmm_ctx *c, const WideModel &m, const VitCall &v, bool *done)
+{
+    const int K = c->K, n = c->n;
+    int maxchunks = 1, rc;
+    for (int k = 0; k < K; ++k)
+        maxchunks = std::max(maxchunks, c->traj_c0[k + 1] - c->traj_c0[k]);
+    const double tol = 1e-11, margin = std::max(1e-7, 16.0 * tol * maxchunks);
+    if ((rc = c->d_aentry.ensure((size_t)c->Gp * 8)) || (rc = c->d_aexit.ensure((size_t)c->Gp * 8)) ||
+        (rc = ensure_specres(c)))
+        return rc;
+    const Chunks chs = chunks_of(c);
+    // discrete: B in LDS when it is small enough to leave four wavefronts per SIMD their room
+    const size_t smB = (v.kind == EMIT_DISC && (size_t)n * c->M * sizeof(double) <= 16 * 1024) ? (size_t)n * c->M * sizeof(double) : 0;
+    const unsigned int *h = c->h_specres;
+    bool walks_in_flight = false;
+    // one attempt at warm-up W: first without the close-decision count (bit-identical boundaries make it
+    // irrelevant), then with it
+    auto attempt = [&](int W, bool first, plan::ChunkVerdict *verdict) -> int {
+        for (int pass = 0; pass < 2; ++pass) {
+            if (int rca = specres_reset(c))
+                return rca;
+            hipError_t e = dispatch_kind(v.kind, [&](auto kc) {
+                constexpr int KIND = decltype(kc)::value;
+                auto *k = pass > 0 ? k_viterbi_chunks<VNP, KIND, true> : k_viterbi_chunks<VNP, KIND, false>;
+                return launch(k, dim3((c->G + 64 / VNP - 1) / (64 / VNP)), dim3(64), smB, c->stream, m, chs, c->G,
+                              c->d_offsets.p, v.obs, W, margin, v.ptr, v.last, c->d_aentry.p, c->d_aexit.p, c->d_specres.p,
+                              smB ? 1 : 0);
+            });
+            if (e == hipSuccess)
+                e = launch(k_viterbi_check<VNP>, dim3((c->G + 255) / 256), dim3(256), 0, c->stream, chs, c->G,
+                           c->d_aentry.p, c->d_aexit.p, tol, c->d_specres.p);
+            BHMM_HIP(e);
+            if (int rca = specres_read(c, 4, false))
+                return rca;
+            // the normal case is "all boundaries bit-identical": the back-trace is enqueued behind the first pass
+            // before its verdict is known (one host round trip less); the walks only read back-pointers, which are
+            // valid state indices whatever the verdict, and are repeated after any further pass
+            const bool speculative = first && pass == 0;
+            if (speculative)
+                BHMM_HIP(chunk_walks<VNP>(c, v));
+            BHMM_HIP(hipStreamSynchronize(c->stream));
+            walks_in_flight = speculative && h[3] == 0;
+            if (h[3] == 0 || h[0] != 0)
+                break; // the serial run outright / out of tolerance: the count cannot help
+        }
+        // all boundaries bit-identical: it is the serial run; else within tolerance and no close decision
+        verdict->accepted = h[3] == 0 || (h[0] == 0 && h[2] == 0);
+        verdict->within = h[0] == 0;
+        return BHMM_OK;
+    };
+    plan::ChunkVerdict verdict;
+    if ((rc = plan::vit_chunk_attempts(c->ds.vit.W, c->ds.vit.bad, c->ds.vit.explore, c->ds.spec_W, c->opt.spec_W_fixed,
+                                       attempt, &verdict)))
+        return rc;
+    *done = c->last.viterbi_chunked = verdict.accepted;
+    memcpy(&c->last.spec_last_dev, &h[1], sizeof(float));
+    c->last.viterbi_close = h[2];
+    if (*done && !walks_in_flight)
+        BHMM_HIP(chunk_walks<VNP>(c, v));
+    return BHMM_OK;
+}
+
+// ---- 9..64 states: one lane group per time segment (k_wide_viterbi_seg), accepted by seg_viterbi ----
+// Warm-up: its own, not the E-step's.  Every length is exact (bitwise check + fix-up rounds), so it only trades
+// warm-up steps against rounds (1.1 ms each at configs[3], whatever the number of flagged segments), and the E-step's
+// length says little about that: its check asks for 1e-11 on every boundary -- 904 steps after a dozen EM iterations
+// on configs[3] --, while the max-product vectors are within rounding noise of their predecessors' after 128 (one
+// round either way: 17.6 ms against 23.6).  The lengths: plan::vit_wide_w_start, vit_next_warmup
+int wide_seg_viterbi(bhmm_ctx *c, const WideModel &m, const VitCall &v, bool *done)
+{
+    const int K = c->K, n = c->n, NP = c->N, GP = 64 / NP;
+    const int W_estep = plan::vit_w_estep(c->ds.spec_W);
+    int W_try = plan::vit_wide_w_start(c->ds.vit.W, W_estep), rc;
+    double *vall = vit_vall(c, c->opt.vit_margin && c->ds.vit.margin_want);
+    const int64_t maxT = longest_traj(c);
+    for (int attempt = 0; attempt < 2 && !*done; ++attempt) {
+        if (attempt > 0)
+            W_try *= 2;
+        const int64_t seglen =
+            plan::vit_wide_seglen(c->total, NP, c->num_simd, c->opt.vit_seg_per_simd, c->opt.vit_seg_warmups, W_try);
+        Segs sg;
+        if ((rc = wide_path_plan(c, 0, seglen, sg)))
+            return rc;
+        if (sg.nseg <= K)
+            break; // nothing to gain: one segment per trajectory is the serial kernel
+        sg.W = W_try;
+        if ((rc = vit_boundary_bufs(c, sg, NP)))
+            return rc;
+        const dim3 sgrid((sg.nseg + GP * WVS_WPB - 1) / (GP * WVS_WPB)), sblk(64 * WVS_WPB);
+        auto seg_kernel = [&](bool fix, uint8_t *flag, double *kept, double tol, unsigned int *notmet) {
+            return dispatch_np<16>(NP, [&](auto npc) {
+                return dispatch_kind(v.kind, [&](auto kc) {
+                    constexpr int V = decltype(npc)::value, KIND = decltype(kc)::value;
+                    return launch(fix ? k_wide_viterbi_seg<V, KIND, true> : k_wide_viterbi_seg<V, KIND, false>, sgrid, sblk, 0,
+                                  c->stream, m, c->d_offsets.p, sg, v.obs, v.ptr, v.last, c->d_aentry.p, c->d_aexit.p, c->d_vckpt.p,
+                                  flag, kept, tol, notmet);
+                });
+            });
+        };
+        SegViterbi f;
+        f.pass = [&](bool fix) -> int {
+            BHMM_HIP(seg_kernel(fix, c->d_vflag.p, fix ? nullptr : vall, 0.0, nullptr));
+            BHMM_HIP(dispatch_np<16>(NP, [&](auto npc) {
+                return launch(k_wide_vit_check<decltype(npc)::value>, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
+                              c->d_aentry.p, c->d_aexit.p, c->d_vflag.p, c->d_specres.p, (!fix && vall) ? SEG_VIT_TOL : 0.0);
+            }));
+            return BHMM_OK;
+        };
+        f.mend = [&]() -> int {
+            BHMM_HIP(seg_kernel(true, c->d_vflag.p + sg.nseg, vall, SEG_VIT_TOL, c->d_specres.p + 1));
+            return BHMM_OK;
+        };
+        f.margins = [&](double margin) { return vit_margins<1>(c, v, sg, m.A, vit_margin_lds(n), vall, margin); };
+        // back-trace on a plan of its own, eight times finer than the pass's: a walk is a chain of dependent
+        // look-ups, its time the length of a segment (configs[3]: 2 x 0.49 ms on the 2048 segments of the pass)
+        f.walks = [&]() -> int {
+            Segs sgw;
+            if (int rcw = wide_path_plan(c, 2, std::max<int64_t>(256, c->ds.pplan[0].seglen / 8), sgw))
+                return rcw;
+            sgw.W = 0;
+            return vit_walks<1>(c, v, sgw, c->pplan_buf[2].traj0.p);
+        };
+        SegVitResult r;
+        if ((rc = seg_viterbi(c, f, sg, seglen, vall, maxT, 12, false, &r)))
+            return rc;
+        // (a round runs as long as its longest flagged segment needs to fall onto a vector of the first pass again:
+        // 1.1 ms at configs[3] on white-noise observations, 6.7 ms -- half a first pass -- on observations drawn from
+        // the model, where 1800 of 2048 boundaries carry rounding noise.  The margins cost about 1.3 ms there: wanted
+        // from the next call on when rounds were many, or the flagged segments more than a quarter)
+        if (r.rounds >= 2 || (r.rounds >= 1 && !r.margin_accepted && (int64_t)c->last.vit_seg_mismatch * 4 > sg.nseg))
+            c->ds.vit.margin_want = true;
+        // (How many boundaries the first pass left to the fix-up does not say whether the warm-up was too short -- most
+        // are rounding noise, a round costs the same for one as for a thousand: doubling on that count was slower.)
+        if ((*done = r.accepted))
+            vit_accepted(c, r, vall, W_try, W_estep);
+    }
+    vit_attempts_done(c, *done);
+    return BHMM_OK;
+}
+
+// ---- one lane group per trajectory (k_wide_viterbi_fwd) and the trace: what no time-parallel run decided ----
+int serial_viterbi(bhmm_ctx *c, const WideModel &m, const VitCall &v)
+{
+    const int K = c->K, NP = c->wide ? c->N : 8, GP = 64 / NP;
+    // U trajectories per lane group.  Measured on configs[1] (256 trajectories): the kernel is bound by the instruction
+    // stream of each wavefront, not by latency, and SIMDs are plentiful (32 of 1024 busy), so U = 1 is fastest (U = 4
+    // was 3.5x slower); the parameter stays for batches with more trajectories than SIMD slots.
+    constexpr int U = 1;
+    BHMM_HIP(dispatch_np(NP, [&](auto npc) {
+        return dispatch_kind(v.kind, [&](auto kc) {
+            return launch(k_wide_viterbi_fwd<decltype(npc)::value, decltype(kc)::value, U>, dim3((K + GP * U - 1) / (GP * U)),
+                          dim3(64), 0, c->stream, m, c->d_offsets.p, K, v.obs, v.ptr, v.last);
+        });
+    }));
+    BHMM_HIP(v.out([&](auto *p) {
+        return launch(k_wide_viterbi_trace<std::remove_pointer_t<decltype(p)>>, dim3(K), dim3(64), 0, c->stream,
+                      c->d_offsets.p, K, c->n, v.ptr, v.last, p);
+    }));
+    return BHMM_OK;
+}
+
 int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const double *par0,
                      const double *par1, void *paths_out, int out_fmt)
 {
@@ -588,346 +827,23 @@ int wide_viterbi_run(bhmm_ctx *c, const double *A, const double *pi, const doubl
     int rc = wide_model(c, c->kind, A, pi, par0, par1, m);
     if (rc)
         return rc;
-    const int K = c->K, n = c->n, NP = c->wide ? c->N : 8, GP = 64 / NP;
     c->last.viterbi_chunked = false;
     c->last.vit_mended = 0;
-    const size_t gpad = c->wide ? 0 : (size_t)c->Gp;
-    if ((rc = c->d_scratch.ensure((size_t)c->total * n)) ||
-        (rc = c->d_scratch2.ensure(((size_t)c->total + K + 3 * gpad) * sizeof(int32_t))))
+    const size_t gpad = c->wide ? 0 : (size_t)c->Gp; // (the chunk maps of chunk_walks behind the paths)
+    if ((rc = c->d_scratch.ensure((size_t)c->total * c->n)) ||
+        (rc = c->d_scratch2.ensure(((size_t)c->total + c->K + 3 * gpad) * sizeof(int32_t))))
         return rc;
-    uint8_t *ptr = reinterpret_cast<uint8_t *>(c->d_scratch.p);
-    int32_t *last = reinterpret_cast<int32_t *>(c->d_scratch2.p);
-    int32_t *path = last + K;
-    uint8_t *path8 = out_fmt == 2 ? static_cast<uint8_t *>(paths_out) : reinterpret_cast<uint8_t *>(path);
-    uint32_t *vmaps = reinterpret_cast<uint32_t *>(path + c->total); // chunked run: chunk maps,
-    int32_t *vend = reinterpret_cast<int32_t *>(vmaps + gpad);       // state at each chunk's end
-    int32_t *vcoal = vend + gpad; // step below which the map pass wrote the path itself (k_vit_walk)
-    // U trajectories per lane group.  Measured on configs[1] (256 trajectories): the kernel is
-    // bound by the instruction stream of each wavefront, not by latency, and SIMDs are plentiful
-    // (32 of 1024 busy), so U = 1 is fastest (U = 4 was 3.5x slower); the parameter stays for
-    // batches with more trajectories than SIMD slots.
-    const int U = 1;
-    const dim3 grid((K + GP * U - 1) / (GP * U)), blk(64);
-    const void *obs = c->d_obs_rm.p;
-    const int64_t *off = c->d_offsets.p;
-    // emission probabilities in a separate, fully parallel pass when the (total, n) matrix
-    // fits (it is what the reference materialises anyway, maximum_likelihood.py:345-347)
-    int vkind = c->kind;
-    // n <= 8 with a chunk plan: the chunk-parallel kernel evaluates the emission itself (gathers
-    // from B / evaluates the gaussian density): no (total, n) emission matrix is written and re-read
-    const bool disc_direct = !c->wide && c->kind != EMIT_EXPL && c->opt.spec_enabled && c->G > K;
-    // 9..64 states over time segments, discrete: the kernel gathers from B itself (no (total, n) matrix).
-    // Measured for the Gaussian kind too: the division by sigma and the exponential in every step,
-    // warm-ups included, cost more than the matrix pass saves (64 states: 9.0 -> 9.7 ms, 16: 0.67 -> 0.81).
-    // (round 6: the Gaussian density in the step too, with the reciprocal-based quotient and the one-block
-    // exponential of k_pobs_lanes -- at 64 states: 6.5 GB less written and read again per call)
-    const bool wide_direct = c->wide && (c->kind == EMIT_DISC || c->kind == EMIT_GAUSS) && c->opt.spec_enabled &&
-                             !c->ds.vit_seg_given_up;
-    if (c->kind != EMIT_EXPL && !disc_direct && !wide_direct) {
-        size_t freeb = 0, totb = 0;
-        const size_t need = (size_t)c->total * n * sizeof(double);
-        if (hipMemGetInfo(&freeb, &totb) == hipSuccess && need + ((size_t)1 << 30) < freeb + c->d_alpha_rm.n * sizeof(double) &&
-            c->d_alpha_rm.ensure((size_t)c->total * n) == BHMM_OK) {
-            const dim3 pg((unsigned)((c->total + 255) / 256)), pb(256);
-            const dim3 pl((unsigned)(((size_t)c->total * n + 256 * POBS_LANES_R - 1) / (256 * POBS_LANES_R)));
-            // one thread per element where n is a power of two (coalesced stores), else per step
-            const bool gauss = c->kind == EMIT_GAUSS;
-            auto *kl = n == 2    ? (gauss ? k_pobs_lanes<EMIT_GAUSS, 2> : k_pobs_lanes<EMIT_DISC, 2>)
-                       : n == 4  ? (gauss ? k_pobs_lanes<EMIT_GAUSS, 4> : k_pobs_lanes<EMIT_DISC, 4>)
-                       : n == 8  ? (gauss ? k_pobs_lanes<EMIT_GAUSS, 8> : k_pobs_lanes<EMIT_DISC, 8>)
-                       : n == 16 ? (gauss ? k_pobs_lanes<EMIT_GAUSS, 16> : k_pobs_lanes<EMIT_DISC, 16>)
-                       : n == 32 ? (gauss ? k_pobs_lanes<EMIT_GAUSS, 32> : k_pobs_lanes<EMIT_DISC, 32>)
-                       : n == 64 ? (gauss ? k_pobs_lanes<EMIT_GAUSS, 64> : k_pobs_lanes<EMIT_DISC, 64>)
-                                 : nullptr;
-            if (kl)
-                BHMM_HIP(launch(kl, pl, pb, 0, c->stream, m, obs, c->total, c->d_alpha_rm.p));
-            else
-                BHMM_HIP(launch(gauss ? k_pobs_all<EMIT_GAUSS> : k_pobs_all<EMIT_DISC>, pg, pb, 0, c->stream, m, obs, c->total,
-                                c->d_alpha_rm.p));
-            obs = c->d_alpha_rm.p;
-            vkind = EMIT_EXPL;
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    // back-trace of an accepted chunk-parallel run (k_vit_walk, maps -> stitch -> paths)
-    // (models of up to four states: four lanes per chunk, 16 chunks per wavefront)
-    const bool vit4 = !c->wide && n <= 4;
-    auto launch_walks_np = [&](auto npc) {
-        constexpr int VNP = decltype(npc)::value;
-        const Chunks chs = chunks_of(c);
-        const dim3 wg((c->G + 64 / VNP - 1) / (64 / VNP));
-        auto walk = [&](auto *kmaps, auto *kpath, auto *out) {
-            hipError_t e = launch(kmaps, wg, dim3(64), 0, c->stream, chs, c->G, n, ptr, nullptr, vmaps, out, vcoal);
-            if (e == hipSuccess)
-                e = (int64_t)c->G >= (int64_t)32 * K
-                        ? launch(k_smp_stitch, dim3(K), dim3(64), 0, c->stream, c->d_traj_c0.p, K, 1, vmaps, vend, last)
-                        : launch(k_smp_stitch_serial, dim3((K + SMP_STITCH_TPB - 1) / SMP_STITCH_TPB), dim3(64), 0,
-                                 c->stream, c->d_traj_c0.p, K, 1, vmaps, vend, last);
-            if (e == hipSuccess)
-                e = launch(kpath, wg, dim3(64), 0, c->stream, chs, c->G, n, ptr, vend, nullptr, out, vcoal);
-            return e;
-        };
-        return out_fmt == 0 ? walk(k_vit_walk<VNP, false, int32_t>, k_vit_walk<VNP, true, int32_t>, path)
-                            : walk(k_vit_walk<VNP, false, uint8_t>, k_vit_walk<VNP, true, uint8_t>, path8);
-    };
-    auto launch_walks = [&]() {
-        return vit4 ? launch_walks_np(std::integral_constant<int, 4>{}) : launch_walks_np(std::integral_constant<int, 8>{});
-    };
-    bool walks_in_flight = false;
-    // n <= 8 with a chunk plan: the chunk-parallel run first; its back-pointers are accepted only
-    // if every chunk boundary verifies and no decision was close (k_viterbi_chunks)
+    VitCall v = vit_call(c, paths_out, out_fmt, c->d_obs_rm.p, c->kind);
+    if ((rc = viterbi_emissions(c, m, v)))
+        return rc;
     bool done = false;
-    if (!c->wide && (vkind == EMIT_EXPL || disc_direct) && c->opt.spec_enabled && c->G > K) {
-        int maxchunks = 1;
-        for (int k = 0; k < K; ++k)
-            maxchunks = std::max(maxchunks, c->traj_c0[k + 1] - c->traj_c0[k]);
-        const double tol = 1e-11, margin = std::max(1e-7, 16.0 * tol * maxchunks);
-        if ((rc = c->d_aentry.ensure((size_t)c->Gp * 8)) || (rc = c->d_aexit.ensure((size_t)c->Gp * 8)) ||
-            (rc = ensure_specres(c)))
-            return rc;
-        const Chunks chs = chunks_of(c);
-        // discrete: B in LDS when it is small enough to leave four wavefronts per SIMD their room
-        const size_t smB = (disc_direct && c->kind == EMIT_DISC &&
-                            (size_t)n * c->M * sizeof(double) <= 16 * 1024)
-                               ? (size_t)n * c->M * sizeof(double) : 0;
-        // A warm-up too short for some boundary (the survivors of that stretch had not met yet) shows
-        // as a boundary out of tolerance: the run is repeated with twice, then four times the warm-up
-        // (one more pass of ~1 ms each) before the serial kernel (tens of ms) has to decide.
-        // The warm-up of THIS recursion (round 4): the max-product chains coalesce faster than the
-        // E-step's filter forgets to 1e-13 (configs[1]: bit-identical boundaries from W ~ 128 on, the
-        // E-step's probe says 280).  The first call on new observations starts from the E-step's
-        // length; every later call that verified tries three quarters of the last good length, until
-        // one does not verify -- that one is repeated with the last good length in the same call, and
-        // the search ends (at most one lost pass per set of observations).
-        int W_try = c->ds.vit_W > 0 ? c->ds.vit_W : c->ds.spec_W;
-        bool exploring = false;
-        if (c->ds.vit_W > 0 && c->ds.vit_explore && !c->opt.spec_W_fixed) {
-            const int Wn = std::max(32, (c->ds.vit_W * 3 / 4 + 7) / 8 * 8);
-            if (Wn < c->ds.vit_W && Wn > c->ds.vit_bad) {
-                W_try = Wn;
-                exploring = true;
-            } else {
-                c->ds.vit_explore = false;
-            }
-        }
-        for (int attempt = 0; attempt < 3; ++attempt) {
-        if (attempt > 0) {
-            if (exploring) { // the shorter warm-up did not verify: back to the one that did
-                c->ds.vit_bad = W_try;
-                c->ds.vit_explore = false;
-                exploring = false;
-                W_try = c->ds.vit_W;
-            } else {
-                W_try *= 2;
-            }
-        }
-        // first without the close-decision count; bit-identical boundaries make it irrelevant
-        for (int pass = 0; pass < 2; ++pass) {
-            if ((rc = specres_reset(c)))
-                return rc;
-            const int vk = disc_direct && c->kind == EMIT_DISC ? EMIT_DISC : disc_direct ? EMIT_GAUSS : EMIT_EXPL;
-            auto vc = [&](auto npc) {
-                constexpr int VNP = decltype(npc)::value;
-                const bool mg = pass > 0; // (the close-decision count)
-                auto *k = vk == EMIT_DISC    ? (mg ? k_viterbi_chunks<VNP, EMIT_DISC, true> : k_viterbi_chunks<VNP, EMIT_DISC, false>)
-                          : vk == EMIT_GAUSS ? (mg ? k_viterbi_chunks<VNP, EMIT_GAUSS, true> : k_viterbi_chunks<VNP, EMIT_GAUSS, false>)
-                                             : (mg ? k_viterbi_chunks<VNP, EMIT_EXPL, true> : k_viterbi_chunks<VNP, EMIT_EXPL, false>);
-                hipError_t e = launch(k, dim3((c->G + 64 / VNP - 1) / (64 / VNP)), dim3(64), smB, c->stream, m, chs, c->G, off,
-                                      obs, W_try, margin, ptr, last, c->d_aentry.p, c->d_aexit.p, c->d_specres.p, smB ? 1 : 0);
-                if (e == hipSuccess)
-                    e = launch(k_viterbi_check<VNP>, dim3((c->G + 255) / 256), dim3(256), 0, c->stream, chs, c->G,
-                               c->d_aentry.p, c->d_aexit.p, tol, c->d_specres.p);
-                return e;
-            };
-            BHMM_HIP(vit4 ? vc(std::integral_constant<int, 4>{}) : vc(std::integral_constant<int, 8>{}));
-            if ((rc = specres_read(c, 4, false)))
-                return rc;
-            // the normal case is "all boundaries bit-identical": the back-trace is enqueued behind
-            // the first pass before its verdict is known (one host round trip less); the walks only
-            // read back-pointers, which are valid state indices whatever the verdict, and are
-            // repeated after any further pass
-            const bool speculative = attempt == 0 && pass == 0;
-            if (speculative)
-                BHMM_HIP(launch_walks());
-            BHMM_HIP(hipStreamSynchronize(c->stream));
-            walks_in_flight = speculative && c->h_specres[3] == 0;
-            if (c->h_specres[3] == 0 || c->h_specres[0] != 0)
-                break; // the serial run outright / out of tolerance: the count cannot help
-        }
-        const bool accepted = c->h_specres[3] == 0 || (c->h_specres[0] == 0 && c->h_specres[2] == 0);
-        if (exploring && !accepted)
-            continue; // (a shorter warm-up must be as good as the longer one was, not merely tolerable)
-        if (c->h_specres[0] == 0) {
-            c->ds.vit_W = W_try; // (what worked is where the next call on these observations starts)
-            break; // every boundary within tolerance: a longer warm-up changes nothing
-        }
-        }
-        // all boundaries bit-identical: it is the serial run; else within tolerance and no
-        // close decision
-        done = c->h_specres[3] == 0 || (c->h_specres[0] == 0 && c->h_specres[2] == 0);
-        c->last.viterbi_chunked = done;
-        float dev;
-        memcpy(&dev, &c->h_specres[1], sizeof(float));
-        c->last.spec_last_dev = dev;
-        c->last.viterbi_close = c->h_specres[2];
-    }
-    // 9..64 states: one lane group per time segment (k_wide_viterbi_seg), accepted by seg_viterbi
-    if (c->wide && c->opt.spec_enabled && !c->ds.vit_seg_given_up) {
-        // warm-up: its own, not the E-step's.  Every length is exact (bitwise check + fix-up rounds), so the length
-        // only trades warm-up steps (W / segment length of the first pass) against rounds (1.1 ms each at configs[3],
-        // whatever the number of flagged segments) -- and the E-step's length says little about that: its boundary
-        // check asks for 1e-11 on every boundary, which after a dozen EM iterations on configs[3] takes 904 steps,
-        // while the max-product vectors are within rounding noise of their predecessors' after 128 (one round
-        // either way: 17.6 ms against 23.6).  Start at 128 steps (less if the filter forgets faster); a call that
-        // needed three or more rounds doubles the length for the next call on these observations, up to the E-step's.
-        const int W_estep = std::max(64, c->ds.spec_W > 0 ? (c->ds.spec_W + 7) / 8 * 8 : 128);
-        int W_try = c->ds.vit_W > 0 ? c->ds.vit_W : std::min(128, W_estep);
-        // the path-margin acceptance (k_vit_margin): every vector of the first pass is kept ([total][n], in the
-        // buffer of the 65..128-state E-step's W rows)
-        double *vall = nullptr;
-        // (up to 64 states one fix-up round is short -- 1.1 ms at configs[3] -- and cheaper than keeping the
-        // vectors and checking the margins: only observations that needed two or more rounds before take this way)
-        if (c->opt.vit_margin && c->ds.vit_margin_want && c->d_gW.ensure((size_t)c->total * n) == BHMM_OK)
-            vall = c->d_gW.p;
-        else
-            (void)hipGetLastError();
-        c->last.vit_margin_used = 0;
-        c->last.vit_margin_close = 0;
-        const int64_t maxT = longest_traj(c);
-        // back-trace over the segments: maps, stitch, apply -- on a plan of its own, eight times finer than the
-        // pass's: a walk is a chain of dependent look-ups, its time the length of a segment (configs[3]: 2 x 0.49 ms
-        // on the 2048 segments of the pass)
-        auto seg_walks = [&]() -> int {
-            Segs sgw;
-            int rcw;
-            if ((rcw = wide_path_plan(c, 2, std::max<int64_t>(256, c->ds.pplan[0].seglen / 8), sgw)))
-                return rcw;
-            sgw.W = 0;
-            if ((rcw = c->d_vmaps.ensure((size_t)sgw.nseg * 64)) || (rcw = c->d_vend.ensure((size_t)sgw.nseg)))
-                return rcw;
-            BHMM_HIP(launch(k_wide_vit_walk<false, uint8_t>, dim3(sgw.nseg), dim3(64), 0, c->stream, off, sgw, n, ptr,
-                            c->d_vmaps.p, nullptr, nullptr));
-            BHMM_HIP(launch(k_wide_vit_stitch, dim3((K + 63) / 64), dim3(64), 0, c->stream, c->pplan_buf[2].traj0.p, K,
-                            c->d_vmaps.p, 64, last, c->d_vend.p));
-            auto walk = [&](auto *k, auto *out) {
-                return launch(k, dim3(sgw.nseg), dim3(64), 0, c->stream, off, sgw, n, ptr, nullptr, c->d_vend.p, out);
-            };
-            BHMM_HIP(out_fmt == 0 ? walk(k_wide_vit_walk<true, int32_t>, path) : walk(k_wide_vit_walk<true, uint8_t>, path8));
-            return BHMM_OK;
-        };
-        for (int attempt = 0; attempt < 2 && !done; ++attempt) {
-            if (attempt > 0)
-                W_try *= 2;
-            // two lane groups' worth of segments per SIMD, none shorter than two warm-ups
-            const int64_t want = (int64_t)c->opt.vit_seg_per_simd * c->num_simd * GP;
-            const int64_t seglen = std::max<int64_t>((c->total + want - 1) / want, c->opt.vit_seg_warmups * (int64_t)W_try);
-            Segs sg;
-            if ((rc = wide_path_plan(c, 0, seglen, sg)))
-                return rc;
-            if (sg.nseg <= K)
-                break; // nothing to gain: one segment per trajectory is the serial kernel
-            sg.W = W_try;
-            if ((rc = c->d_aentry.ensure((size_t)sg.nseg * NP)) || (rc = c->d_aexit.ensure((size_t)sg.nseg * NP)))
-                return rc;
-            const dim3 sgrid((sg.nseg + GP * WVS_WPB - 1) / (GP * WVS_WPB)), sblk(64 * WVS_WPB);
-            if ((rc = c->d_vckpt.ensure(((size_t)(c->total >> 6) + 1) * NP)) ||
-                (rc = c->d_vflag.ensure(2 * (size_t)sg.nseg))) // ([nseg] flagged | [nseg] flagged and further than vm_tol)
-                return rc;
-            auto by_np = [&](auto f) {
-                return NP == 16 ? f(std::integral_constant<int, 16>{})
-                       : NP == 32 ? f(std::integral_constant<int, 32>{})
-                                  : f(std::integral_constant<int, 64>{});
-            };
-            SegViterbi f;
-            f.pass = [&](bool fix) -> int {
-                BHMM_HIP(by_np([&](auto npc) {
-                    constexpr int V = decltype(npc)::value;
-                    auto *k = vkind == EMIT_GAUSS
-                                  ? (fix ? k_wide_viterbi_seg<V, EMIT_GAUSS, true> : k_wide_viterbi_seg<V, EMIT_GAUSS, false>)
-                              : vkind == EMIT_DISC
-                                  ? (fix ? k_wide_viterbi_seg<V, EMIT_DISC, true> : k_wide_viterbi_seg<V, EMIT_DISC, false>)
-                                  : (fix ? k_wide_viterbi_seg<V, EMIT_EXPL, true> : k_wide_viterbi_seg<V, EMIT_EXPL, false>);
-                    hipError_t e = launch(k, sgrid, sblk, 0, c->stream, m, off, sg, obs, ptr, last, c->d_aentry.p,
-                                          c->d_aexit.p, c->d_vckpt.p, c->d_vflag.p, fix ? nullptr : vall, 0.0, nullptr);
-                    if (e == hipSuccess)
-                        e = launch(k_wide_vit_check<V>, dim3((sg.nseg + 255) / 256), dim3(256), 0, c->stream, sg,
-                                   c->d_aentry.p, c->d_aexit.p, c->d_vflag.p, c->d_specres.p,
-                                   (!fix && vall) ? SEG_VIT_TOL : 0.0);
-                    return e;
-                }));
-                return BHMM_OK;
-            };
-            f.mend = [&]() -> int {
-                BHMM_HIP(by_np([&](auto npc) {
-                    constexpr int V = decltype(npc)::value;
-                    auto *k = vkind == EMIT_GAUSS  ? k_wide_viterbi_seg<V, EMIT_GAUSS, true>
-                              : vkind == EMIT_DISC ? k_wide_viterbi_seg<V, EMIT_DISC, true>
-                                                   : k_wide_viterbi_seg<V, EMIT_EXPL, true>;
-                    return launch(k, sgrid, sblk, 0, c->stream, m, off, sg, obs, ptr, last, c->d_aentry.p, c->d_aexit.p,
-                                  c->d_vckpt.p, c->d_vflag.p + sg.nseg, vall, SEG_VIT_TOL, c->d_specres.p + 1);
-                }));
-                return BHMM_OK;
-            };
-            f.margins = [&](double margin) -> int {
-                const size_t smm = (size_t)n * (n | 1) * sizeof(double); // (odd pitch, k_vit_margin)
-                const dim3 mgrid(sg.nseg, (unsigned)((c->ds.pplan[0].maxlen + VM_STEPS - 1) / VM_STEPS)); // (the longest REAL segment)
-                auto margins = [&](auto *k, auto *p) {
-                    return launch(k, mgrid, dim3(256), smm, c->stream, m.A, n, off, sg, vall, p, margin, c->d_specres.p);
-                };
-                BHMM_HIP(out_fmt == 0 ? margins(k_vit_margin<int32_t, 1>, path) : margins(k_vit_margin<uint8_t, 1>, path8));
-                return BHMM_OK;
-            };
-            f.walks = seg_walks;
-            SegVitResult r;
-            if ((rc = seg_viterbi(c, f, sg, seglen, vall, maxT, 12, false, &r)))
-                return rc;
-            // (a round runs as long as its longest flagged segment needs to fall onto a vector of the first pass
-            // again: 1.1 ms at configs[3] on white-noise observations, 6.7 ms -- half a first pass -- on
-            // observations drawn from the model, where 1800 of 2048 boundaries carry rounding noise.  The margins
-            // cost about 1.3 ms there: wanted from the next call on when rounds were many, or the flagged
-            // segments more than a quarter)
-            if (r.rounds >= 2 || (r.rounds >= 1 && !r.margin_accepted && (int64_t)c->last.vit_seg_mismatch * 4 > sg.nseg))
-                c->ds.vit_margin_want = true;
-            // (How many boundaries the first pass left to the fix-up does not say whether the warm-up was
-            // too short -- most of them are rounding noise, and a round costs the same for one segment as
-            // for a thousand: doubling the warm-up on that count was measured slower everywhere.)
-            if (r.accepted) {
-                done = true;
-                // (boundaries further than 1e-12 apart keep the margin rule from being asked: a longer warm-up for
-                // the next call, like after three or more rounds -- never beyond the E-step's)
-                const bool longer = !r.margin_accepted && ((vall && c->last.vit_far > 0) || r.rounds >= 3);
-                c->ds.vit_W = (longer && W_try < W_estep) ? std::min(2 * W_try, W_estep) : W_try;
-            }
-        }
-        if (!done && c->ds.pplan[0].nseg > K)
-            c->ds.vit_seg_given_up = true; // these observations go to the serial kernel from now on
-        c->last.viterbi_chunked = done;
-        walks_in_flight = done; // (seg_viterbi ran the walks of an accepted pass)
-    }
-    if (done) {
-        if (!walks_in_flight)
-            BHMM_HIP(launch_walks());
-    } else {
-        auto *kv = NP == 8    ? (vkind == EMIT_GAUSS  ? k_wide_viterbi_fwd<8, EMIT_GAUSS, 1>
-                                 : vkind == EMIT_DISC ? k_wide_viterbi_fwd<8, EMIT_DISC, 1>
-                                                      : k_wide_viterbi_fwd<8, EMIT_EXPL, 1>)
-                   : NP == 16 ? (vkind == EMIT_GAUSS  ? k_wide_viterbi_fwd<16, EMIT_GAUSS, 1>
-                                 : vkind == EMIT_DISC ? k_wide_viterbi_fwd<16, EMIT_DISC, 1>
-                                                      : k_wide_viterbi_fwd<16, EMIT_EXPL, 1>)
-                   : NP == 32 ? (vkind == EMIT_GAUSS  ? k_wide_viterbi_fwd<32, EMIT_GAUSS, 1>
-                                 : vkind == EMIT_DISC ? k_wide_viterbi_fwd<32, EMIT_DISC, 1>
-                                                      : k_wide_viterbi_fwd<32, EMIT_EXPL, 1>)
-                              : (vkind == EMIT_GAUSS  ? k_wide_viterbi_fwd<64, EMIT_GAUSS, 1>
-                                 : vkind == EMIT_DISC ? k_wide_viterbi_fwd<64, EMIT_DISC, 1>
-                                                      : k_wide_viterbi_fwd<64, EMIT_EXPL, 1>);
-        BHMM_HIP(launch(kv, grid, blk, 0, c->stream, m, off, K, obs, ptr, last));
-        if (out_fmt == 0)
-            BHMM_HIP(launch(k_wide_viterbi_trace<int32_t>, dim3(K), dim3(64), 0, c->stream, off, K, n, ptr, last, path));
-        else
-            BHMM_HIP(launch(k_wide_viterbi_trace<uint8_t>, dim3(K), dim3(64), 0, c->stream, off, K, n, ptr, last, path8));
-    }
-    return deliver_paths(c, paths_out, out_fmt, path);
+    if (!c->wide && c->opt.spec_enabled && c->G > c->K)
+        rc = c->n <= 4 ? chunk_viterbi<4>(c, m, v, &done) : chunk_viterbi<8>(c, m, v, &done);
+    else if (c->wide && c->opt.spec_enabled && !c->ds.vit.seg_given_up)
+        rc = wide_seg_viterbi(c, m, v, &done);
+    if (rc || (!done && (rc = serial_viterbi(c, m, v))))
+        return rc;
+    return deliver_paths(c, paths_out, out_fmt, v.path);
 }
 
 int wide_sample_run(bhmm_ctx *c, const double *A, const double *pi, const double *par0,

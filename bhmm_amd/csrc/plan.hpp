@@ -4,7 +4,7 @@
 // calls (smooth_ranges, smooth_tile_ranges), and the forgetting probe every family
 // warms up by: where it samples (probe_starts) and how its curve is read (curve_last, warmup_of,
 // warmup_wide_of), the acceptance protocol of a verified pass (two_attempts, doubled), and the integer rules of the
-// segment-parallel backward draw (draw_seglen, draw_next_warmup).  Pure C++ (no HIP), so
+// segment-parallel backward draw (draw_seglen, draw_next_warmup) and of the Viterbi passes (vit_*).  Pure C++ (no HIP), so
 // the same code runs under -fsanitize=address,undefined in the CPU sanitizer build
 // (oracle/Makefile `asan`); the .hip files only allocate and upload what these functions return.
 #pragma once
@@ -408,6 +408,103 @@ constexpr int DRAW_W_MAX = 4096;
 constexpr int DRAW_MAX_ROUNDS = 16;
 inline int64_t draw_seglen(int64_t total, int64_t want) { return std::max((total + want - 1) / want, DRAW_SEGLEN_MIN); }
 inline int draw_next_warmup(int W, int64_t mismatch, int64_t nseg) { return mismatch * 10 > nseg && W < DRAW_W_MAX ? 2 * W : W; }
+
+// ---- the integer rules of the Viterbi passes (path_api.hip, gen_api.hip, viterbi_host.hpp) ----
+// Every accepted path is the serial kernel's, so these only trade warm-up steps against fix-up rounds and lost
+// passes.  W0: the E-step's warm-up as the segment passes take it, a multiple of 8 and at least 64 (128 unprobed).
+inline int vit_w_estep(int spec_W) { return std::max(64, spec_W > 0 ? (spec_W + 7) / 8 * 8 : 128); }
+// steps per segment that give `want` (>= 1) segments over `total` steps; ... rounded up to a multiple of 8
+inline int64_t vit_fill(int64_t total, int64_t want) { return (total + want - 1) / want; }
+inline int64_t vit_fill8(int64_t total, int64_t want) { return (vit_fill(total, want) + 7) / 8 * 8; }
+// 9..64 states: per_simd lane groups of np lanes (16, 32, 64) per SIMD, no segment shorter than `warmups` warm-ups
+inline int64_t vit_wide_seglen(int64_t total, int np, int num_simd, int per_simd, int warmups, int W)
+{
+    return std::max<int64_t>(vit_fill(total, (int64_t)per_simd * num_simd * (64 / np)), warmups * (int64_t)W);
+}
+// 65..128 states: per_simd segments per SIMD (with the margin rule on, `warmups` is one: segments as short as a warm-up)
+inline int64_t vit_gen_fill(int64_t total, int num_simd, int per_simd) { return vit_fill8(total, (int64_t)per_simd * num_simd); }
+inline int64_t vit_gen_seglen(int64_t total, int num_simd, int per_simd, int warmups, int W)
+{
+    return std::max<int64_t>(vit_fill(total, (int64_t)per_simd * num_simd), warmups * (int64_t)W);
+}
+// 129..256 states: VIT_ROWS segments per workgroup, one workgroup per compute unit; a multiple of 8
+constexpr int VIT_ROWS = 4;
+inline int64_t vit_rows_fill(int64_t total, int num_simd) { return vit_fill8(total, (int64_t)VIT_ROWS * (num_simd / 4)); }
+inline int64_t vit_rows_seglen(int64_t fill0, int W) { return std::max<int64_t>(fill0, W); }
+// 9..64 states start at 128 steps, less if the filter forgets faster (vit_W: what the last call left, 0: none)
+inline int vit_wide_w_start(int vit_W, int W0) { return vit_W > 0 ? vit_W : std::min(128, W0); }
+// 65..128 states: the survivors of these larger models meet later than the filter forgets -- up to four times the
+// E-step's length, but never longer than the segments that fill the chip (fill0 = vit_gen_fill).  With the mending
+// round the E-step's length is where a new set of observations starts, without it the cap.
+inline int vit_gen_w_cap(int W0, int64_t fill0) { return (int)std::max<int64_t>(W0, std::min<int64_t>(4 * (int64_t)W0, fill0)); }
+inline int vit_gen_w_start(int vit_W, int W0, int W_cap, bool margin, bool mend)
+{
+    return vit_W > 0 ? vit_W : ((margin && !mend) ? W_cap : W0);
+}
+// 129..256 states: with the mending round the E-step's length, else six of them, at most one and a half fill
+// lengths (fill0 = vit_rows_fill)
+inline int vit_rows_w_start(int vit_W, int W0, int64_t fill0, bool mend)
+{
+    if (vit_W > 0)
+        return vit_W;
+    return mend ? W0 : (int)std::max<int64_t>(W0, std::min<int64_t>(6 * (int64_t)W0, (3 * fill0 / 2 + 7) / 8 * 8));
+}
+// ... a pass that was not accepted, the `fails`-th in a row: given up after the second, or when twice the warm-up
+// would exceed half the longest trajectory; else the next call tries 2 W
+inline bool vit_rows_give_up(int fails, int W, int64_t maxT) { return fails >= 2 || 4 * (int64_t)W > maxT; }
+// 9..128 states, the next call's warm-up after an accepted pass (longer: far boundaries kept the margin rule from
+// being asked, or three or more rounds)
+inline int vit_next_warmup(int W, bool longer, int cap) { return (longer && W < cap) ? std::min(2 * W, cap) : W; }
+
+// 8 states and fewer, the warm-up of the chunk-parallel run.  The first call on new observations starts from the
+// E-step's length (spec_W); every later call that verified tries three quarters of the last good length (vit_W),
+// rounded to 8 and at least 32, while that is below vit_W and above a length that failed before (vit_bad) -- until
+// one does not verify: that attempt is repeated with the last good length in the same call and the search ends (at
+// most one lost pass per set of observations).  An attempt out of tolerance otherwise doubles the warm-up; three
+// attempts, then the serial kernel.  `attempt(W, first, &v)` runs the kernels and returns a BHMM code (non-zero:
+// returned at once); *last is the verdict of the last attempt.
+struct ChunkVerdict {
+    bool accepted = false; // every boundary bit-identical, or all within tolerance and no close decision
+    bool within = false;   // every boundary within tolerance
+};
+inline int vit_chunk_w_first(int vit_W, int vit_bad, bool &vit_explore, int spec_W, bool W_fixed, bool *exploring)
+{
+    *exploring = false;
+    if (vit_W > 0 && vit_explore && !W_fixed) {
+        const int Wn = std::max(32, (vit_W * 3 / 4 + 7) / 8 * 8);
+        if (Wn < vit_W && Wn > vit_bad) {
+            *exploring = true;
+            return Wn;
+        }
+        vit_explore = false;
+    }
+    return vit_W > 0 ? vit_W : spec_W;
+}
+template <class Attempt>
+int vit_chunk_attempts(int &vit_W, int &vit_bad, bool &vit_explore, int spec_W, bool W_fixed, Attempt attempt,
+                       ChunkVerdict *last)
+{
+    bool exploring;
+    int W = vit_chunk_w_first(vit_W, vit_bad, vit_explore, spec_W, W_fixed, &exploring);
+    for (int a = 0; a < 3; ++a) {
+        if (a > 0 && exploring) { // the shorter warm-up did not verify: back to the one that did
+            vit_bad = W;
+            vit_explore = exploring = false;
+            W = vit_W;
+        } else if (a > 0) {
+            W *= 2;
+        }
+        if (const int rc = attempt(W, a == 0, last))
+            return rc;
+        if (exploring && !last->accepted)
+            continue; // (a shorter warm-up must be as good as the longer one was, not merely tolerable)
+        if (last->within) {
+            vit_W = W; // (what worked is where the next call on these observations starts)
+            break;     // every boundary within tolerance: a longer warm-up changes nothing
+        }
+    }
+    return 0;
+}
 
 // For every segment of the plan with `seglen`: the start of a segment of the twice-as-fine plan
 // strictly inside it (-1: none).  Cuts the trajectories exactly like plan_segments(.., 1).

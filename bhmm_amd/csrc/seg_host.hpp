@@ -211,5 +211,19 @@ auto dispatch_kind(int kind, F f)
         return f(std::integral_constant<int, EMIT_DISC>());
     return f(std::integral_constant<int, EMIT_EXPL>());
 }
+// f(std::integral_constant<int, NP>()) for the lanes per state vector of the kernels up to 64 states: 8 (LO = 8
+// only), 16, 32 or 64
+template <int LO = 8, class F>
+auto dispatch_np(int np, F f)
+{
+    if constexpr (LO <= 8)
+        if (np == 8)
+            return f(std::integral_constant<int, 8>());
+    if (np == 16)
+        return f(std::integral_constant<int, 16>());
+    if (np == 32)
+        return f(std::integral_constant<int, 32>());
+    return f(std::integral_constant<int, 64>());
+}
 
 } // namespace bhmm

@@ -8,17 +8,17 @@ hands a call to the serial kernel whenever a segmented pass is not accepted, and
 viterbi_seg_per_simd = 1 throughout, so that batches of a few thousand steps are cut into segments at all.
 
 What the dispatch tables say (and the cases follow):
-  * 8 states and fewer (path_api.hip, wide_viterbi_run): k_viterbi_chunks<4 | 8, KIND, MARGIN> on the chunk plan of
+  * 8 states and fewer (path_api.hip, chunk_viterbi): k_viterbi_chunks<4 | 8, KIND, MARGIN> on the chunk plan of
     set_observations(chunk=...); four lanes per chunk up to 4 states, eight above.  MARGIN = true is a second pass that
     runs only when some boundary is within tolerance but not bit-identical.  No fix-up rounds here.
-  * 9 .. 64 states: k_wide_viterbi_seg<16 | 32 | 64, KIND, FIX>.  Gaussian and discrete observations are evaluated in
+  * 9 .. 64 states (wide_seg_viterbi): k_wide_viterbi_seg<16 | 32 | 64, KIND, FIX>.  Gaussian and discrete observations are evaluated in
     the step (KIND as given); FIX = true is a fix-up round or the mending round.
-  * 65 .. 128 states (gen_api.hip, gen_viterbi_run): k_gen_viterbi_seg<FIX> on a materialised emission matrix
+  * 65 .. 128 states (gen_api.hip, gen_seg_viterbi): k_gen_viterbi_seg<FIX> on a materialised emission matrix
     (gen_pobs), so the kind only changes how that matrix is made.
-  * 129 .. 256 states: k_gen_viterbi_rows<4, 2[, MEND]>, first pass only: NO fix-up rounds exist (seg_viterbi is
-    called with max_rounds = 0, gen_api.hip), a pass that is neither bit-identical nor accepted by the margins goes to
+  * 129 .. 256 states (gen_rows_viterbi): k_gen_viterbi_rows<4, 2[, MEND]>, first pass only: NO fix-up rounds exist
+    (seg_viterbi is called with max_rounds = 0), a pass that is neither bit-identical nor accepted by the margins goes to
     the serial kernel.
-  * 257 states and more: k_gen_viterbi_fwd, serial.
+  * 257 states and more (gen_serial_viterbi): k_gen_viterbi_fwd, serial.
 
 The conditions the forced cases rest on ("this warm-up leaves boundaries that differ", "the ties lie on the path",
 "exactly these rows are ones") are established on the same inputs in tests/test_viterbi_matrix_cpu.py.
@@ -37,10 +37,10 @@ Which test executes which instantiation (G, D, E: gaussian, discrete, explicit; 
   ... <16|32|64, G, true> as mending     test_forced_mismatch_with_mending_and_margins_on[15|31|63]
   k_gen_viterbi_seg<false>               test_above_64_states[65|66|127|128-kind]
   k_gen_viterbi_seg<true>                test_forced_mismatch_above_64_states[66-gaussian-32]   (mending and rounds)
-      (no KIND: gen_api.hip, gen_viterbi_run calls gen_pobs first and the kernel reads the matrix)
+      (no KIND: gen_api.hip, gen_viterbi_run calls gen_pobs first and the kernel reads the matrix, VitCall::obs)
   k_gen_viterbi_rows<4, 2>               test_above_64_states[129|130|255|256-kind]
   k_gen_viterbi_rows<4, 2, true>         test_forced_mismatch_above_64_states[130-gaussian-128]   (mended pass accepted)
-      (no fix-up round at 129..256: gen_api.hip passes max_rounds = 0 to seg_viterbi and its f.pass ignores `fix`)
+      (no fix-up round at 129..256: gen_rows_viterbi passes max_rounds = 0 to seg_viterbi and its f.pass ignores `fix`)
   k_gen_viterbi_fwd                      test_257_states_take_the_serial_kernel; k_wide_viterbi_fwd<8|16|32|64, kind>:
                                          the serial halves of test_twin_states_across_the_seams and
                                          test_serial_fallback_8_states_and_fewer
@@ -322,7 +322,7 @@ def test_all_underflow_rows_inside_segments_and_warmups(n):
     into ones -- at step 0, the last step, the first and last step of an interior segment, inside a warm-up and, at 64
     states, on a reload step of the observation register and on the step before one.  The rule lives in the step of
     k_wide_viterbi_seg (a ballot over the lanes of the segment's group, wgroup_mask -- padding lanes are IN that mask
-    and stay out of the way only because their density is an exact zero, cn_j = 0) and nothing in wide_viterbi_run
+    and stay out of the way only because their density is an exact zero, cn_j = 0) and nothing in wide_seg_viterbi
     looks at it: the segmented run stands (a row of ones is a step like any other for the boundary check)."""
     c = vc.s5_case(n)
     eng = _engine(c)

@@ -36,15 +36,17 @@ def np_of(n):
 
 
 def seglen_wide(total, n, W, seg_per_simd=1, warmups=2):
-    """segment length of the 9..64-state pass (path_api.hip, wide_viterbi_run): enough segments for every lane
-    group of the device, none shorter than `warmups` warm-ups"""
+    """segment length of the 9..64-state pass (plan::vit_wide_seglen, called by wide_seg_viterbi in path_api.hip; the
+    two are compared in tests/test_viterbi_plan_cpu.py): enough segments for every lane group of the device, none
+    shorter than `warmups` warm-ups"""
     want = seg_per_simd * NUM_SIMD * (64 // np_of(n))
     return max(-(-total // want), warmups * W)
 
 
 def seglen_gen(total, n, W, seg_per_simd=1):
-    """... of the 65..128-state pass (gen_api.hip; one warm-up per segment with the margin rule on) and of the
-    row-batched pass for 129..256 states (four segments per workgroup, one workgroup per compute unit)"""
+    """... of the 65..128-state pass (plan::vit_gen_seglen, gen_seg_viterbi in gen_api.hip; one warm-up per segment
+    with the margin rule on) and of the row-batched pass for 129..256 states (plan::vit_rows_fill / vit_rows_seglen,
+    gen_rows_viterbi; four segments per workgroup, one workgroup per compute unit)"""
     if n <= 128:
         return max(-(-total // (seg_per_simd * NUM_SIMD)), W)
     fill0 = (-(-total // (4 * (NUM_SIMD // 4))) + 7) // 8 * 8
