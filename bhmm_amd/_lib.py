@@ -36,6 +36,9 @@ PAIR_F32 = 1           # bhmm_posterior_transitions: rows of float
 PAIR_DEVICE = 2        # ... out is a device pointer
 FILT_F32 = 1           # bhmm_filter: both outputs of float
 FILT_DEVICE = 2        # ... both outputs are device pointers
+COV_FULL = 0           # bhmm_mvn_*: covariances (N, D, D)
+COV_DIAG = 1           # ... variances (N, D)
+MVN_MAX_D = 64
 DWELL_COLS = 5         # bhmm_path_runs / bhmm_decode_runs: columns of the dwell table (BHMM_DWELL_COLS)
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
@@ -63,6 +66,8 @@ SIGNATURES = {
     "bhmm_libc_uniforms": (ctypes.c_int, [c_double_p, ctypes.c_int64, ctypes.c_int]),
     "bhmm_pobs_gaussian": (ctypes.c_int, [c_double_p, c_double_p, c_double_p, c_double_p,
                                           ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
+    "bhmm_logpdf_mvn": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_double_p,
+                                       c_double_p, ctypes.c_int]),
     "bhmm_update_pout": (ctypes.c_int, [c_double_p, c_int32_p, c_double_p, ctypes.c_int64,
                                         ctypes.c_int, ctypes.c_int]),
     "bhmm_ctx_create": (ctypes.c_int, [ctypes.POINTER(c_void_p), ctypes.c_int, c_void_p]),
@@ -105,6 +110,12 @@ SIGNATURES = {
                                          c_double_p, c_double_p, c_double_p, c_double_p]),
     "bhmm_decode_logprob": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int,
                                            c_double_p]),
+    "bhmm_ctx_set_observations_mvn": (ctypes.c_int, [c_void_p, c_void_p, c_int64_p, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "bhmm_mvn_emissions": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, ctypes.c_int]),
+    "bhmm_mvn_fetch_scale": (ctypes.c_int, [c_void_p, c_double_p, c_double_p]),
+    "bhmm_mvn_fetch_rows": (ctypes.c_int, [c_void_p, c_double_p]),
+    "bhmm_mvn_moments": (ctypes.c_int, [c_void_p, c_void_p, c_double_p, ctypes.c_int, c_double_p]),
     "bhmm_ctx_path_stats_size": (ctypes.c_int, [c_void_p]),
     "bhmm_ctx_set_stream_offsets": (ctypes.c_int, [c_void_p, c_int64_p]),
     "bhmm_sample_paths_dev": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,
@@ -148,6 +159,10 @@ SIGNATURES = {
                                              ctypes.c_int, ctypes.c_int64, ctypes.c_uint64,
                                              ctypes.c_uint64, c_double_p, c_double_p, c_double_p,
                                              c_double_p, c_int32_p]),
+    "bhmm_host_mvn_prepare": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
+                                             c_double_p, c_double_p]),
+    "bhmm_host_mvn_mstep": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
+                                           ctypes.c_double, c_double_p, c_double_p]),
     "bhmm_host_connected_sets": (ctypes.c_int, [c_int32_p, c_double_p, ctypes.c_int,
                                                 ctypes.c_double, ctypes.c_int]),
     "bhmm_host_stationary_vector": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int]),

@@ -5,7 +5,7 @@ import numpy as np
 from .estimators.bayesian_sampling import BayesianHMMSampler
 from .estimators.maximum_likelihood import MaximumLikelihoodEstimator
 from .hmm import HMM, SampledHMM
-from .output_models import DiscreteOutputModel, GaussianOutputModel
+from .output_models import DiscreteOutputModel, GaussianOutputModel, MultivariateGaussianOutputModel
 
 
 def _guess_output_type(observations):
@@ -15,7 +15,9 @@ def _guess_output_type(observations):
         return 'discrete'
     if np.issubdtype(o1.dtype, np.floating) and o1.ndim == 1:
         return 'gaussian'
-    raise TypeError('Observations is neither sequences of integers nor 1D-sequences of floats.')
+    if np.issubdtype(o1.dtype, np.floating) and o1.ndim == 2:
+        return 'mvgaussian'
+    raise TypeError('Observations is neither sequences of integers nor 1D- or 2D-sequences of floats.')
 
 
 class LaggedObservations(list):
@@ -58,6 +60,24 @@ def discrete_hmm(pi, P, pout):
     return HMM(pi, P, DiscreteOutputModel(pout))
 
 
+def mvgaussian_hmm(pi, P, means, covariances, covariance_type='full'):
+    """An HMM with multivariate gaussian emissions: means (nstates, D), covariances (nstates, D, D), or with
+    covariance_type='diag' the variances (nstates, D)."""
+    nstates = len(means)
+    return HMM(pi, P, MultivariateGaussianOutputModel(nstates, means, covariances, covariance_type=covariance_type))
+
+
+def init_mvgaussian_hmm(observations, nstates, lag=1, reversible=True, covariance_type='full'):
+    """Initial model for (T_k, D) observations, deterministic, numpy only: farthest-point seeding and at most 20
+    Lloyd iterations on at most 1e5 evenly strided points, mean and covariance of every cluster, and a transition
+    matrix from the count matrix of the hard labels at the lag (bhmm_amd/init/mvgaussian.py)."""
+    from .init.mvgaussian import init_model_mvgaussian
+    hmm0 = init_model_mvgaussian(observations, nstates, lag=lag, reversible=reversible,
+                                 covariance_type=covariance_type)
+    hmm0._lag = lag
+    return hmm0
+
+
 def init_gaussian_hmm(observations, nstates, lag=1, reversible=True):
     """bhmm/api.py:202-228."""
     from .init.gaussian import init_model_gaussian1d
@@ -88,6 +108,8 @@ def init_hmm(observations, nstates, lag=1, output=None, reversible=True):
         return init_discrete_hmm(observations, nstates, lag=lag, reversible=reversible)
     if output == 'gaussian':
         return init_gaussian_hmm(observations, nstates, lag=lag, reversible=reversible)
+    if output == 'mvgaussian':
+        return init_mvgaussian_hmm(observations, nstates, lag=lag, reversible=reversible)
     raise NotImplementedError('output model type ' + str(output) + ' not yet implemented.')
 
 
@@ -113,6 +135,8 @@ def bayesian_hmm(observations, estimated_hmm, nsample=100, reversible=True, stat
                  call_back=None, **engine_kwargs):
     """bhmm/api.py:375-470.  Returns a SampledHMM (which also iterates over / indexes the
     sampled models)."""
+    if estimated_hmm.output_model.model_type == 'mvgaussian':
+        raise NotImplementedError('the Bayesian sampler does not handle multivariate gaussian emissions yet')
     sampler = BayesianHMMSampler(observations, estimated_hmm.nstates, initial_model=estimated_hmm,
                                  reversible=reversible, stationary=stationary,
                                  transition_matrix_sampling_steps=1000, p0_prior=p0_prior,
@@ -121,6 +145,12 @@ def bayesian_hmm(observations, estimated_hmm, nsample=100, reversible=True, stat
     sampled = sampler.sample(nsamples=nsample, save_hidden_state_trajectory=store_hidden,
                              call_back=call_back)
     return SampledHMM(estimated_hmm, sampled)
+
+
+def _engine_for(output, device):
+    """The engine of an output type: multivariate gaussian models run on an MvnEngine."""
+    from .engine import Engine, MvnEngine
+    return MvnEngine(device) if output == 'mvgaussian' else Engine(device)
 
 
 def score(observations, models, lag=1, per_trajectory=False, **engine_kwargs):
@@ -132,7 +162,6 @@ def score(observations, models, lag=1, per_trajectory=False, **engine_kwargs):
     under a model scores -inf.  Gaussian and discrete models of up to 128 states run parallel over time
     (verified against the serial recursion, which more states take; Engine.get_option("score_path") is 3 for 65 to
     128 states).  engine_kwargs: device (default 0)."""
-    from .engine import Engine
     from .estimators.maximum_likelihood import model_tuple
     if isinstance(models, SampledHMM):
         models = models.sampled_hmms
@@ -164,7 +193,7 @@ def score(observations, models, lag=1, per_trajectory=False, **engine_kwargs):
         raise TypeError("unexpected keyword arguments: %s" % ", ".join(sorted(engine_kwargs)))
     if lag > 1:
         observations = lag_observations(observations, lag)
-    eng = Engine(device)
+    eng = _engine_for(output, device)
     try:
         if output == 'discrete':
             obs = [np.asarray(o) for o in observations]
@@ -185,7 +214,6 @@ def posterior_decode(observations, model, lag=1, confidence=False, **engine_kwar
     lagged views (lag_observations), one result per view.  Gaussian and discrete models of up to 8 states
     are decoded by one fused kernel that stores no gamma; more states run an E-step that stores gamma.
     engine_kwargs: device (default 0)."""
-    from .engine import Engine
     from .estimators.maximum_likelihood import model_tuple
     if not isinstance(model, HMM):
         raise TypeError("model must be an HMM object")
@@ -199,7 +227,7 @@ def posterior_decode(observations, model, lag=1, confidence=False, **engine_kwar
         raise TypeError("unexpected keyword arguments: %s" % ", ".join(sorted(engine_kwargs)))
     if lag > 1:
         observations = lag_observations(observations, lag)
-    eng = Engine(device)
+    eng = _engine_for(output, device)
     try:
         if output == 'discrete':
             obs = [np.asarray(o) for o in observations]
@@ -220,7 +248,6 @@ def decode_segments(observations, model, lag=1, method='viterbi', stats=False, *
     also dwell ((nstates, 5): runs, steps, longest run, censored runs, censored steps per state) and jumps
     ((nstates, nstates) run pairs i -> j).  lag > 1 decodes the lagged views (lag_observations), one trajectory
     per view.  Up to 256 states.  engine_kwargs: device (default 0)."""
-    from .engine import Engine
     from .estimators.maximum_likelihood import model_tuple
     if not isinstance(model, HMM):
         raise TypeError("model must be an HMM object")
@@ -236,7 +263,7 @@ def decode_segments(observations, model, lag=1, method='viterbi', stats=False, *
         raise TypeError("unexpected keyword arguments: %s" % ", ".join(sorted(engine_kwargs)))
     if lag > 1:
         observations = lag_observations(observations, lag)
-    eng = Engine(device)
+    eng = _engine_for(output, device)
     try:
         if output == 'discrete':
             obs = [np.asarray(o) for o in observations]
@@ -260,7 +287,6 @@ def path_logprob(observations, models, paths=None, method='viterbi', lag=1, **en
     outlier rule of the recursions is NOT applied (an outlier gives a very negative finite term).  A zero
     probability on a path gives -inf for that trajectory -- a posterior-decoded path can take a jump the model
     forbids --, a NaN observation NaN, an empty trajectory 0.0.  engine_kwargs: device (default 0)."""
-    from .engine import Engine
     from .estimators.maximum_likelihood import model_tuple
     if isinstance(models, SampledHMM):
         models = models.sampled_hmms
@@ -316,7 +342,7 @@ def path_logprob(observations, models, paths=None, method='viterbi', lag=1, **en
             if flat.size and (flat.min() < 0 or flat.max() >= nstates):
                 raise ValueError("paths holds a state outside [0, %d)" % nstates)
             paths = np.ascontiguousarray(flat, dtype=np.uint8 if flat.dtype == np.uint8 else np.int32)
-    eng = Engine(device)
+    eng = _engine_for(output, device)
     try:
         if output == 'discrete':
             obs = [np.asarray(o) for o in observations]
@@ -338,7 +364,6 @@ def posterior_marginals(observations, model, lag=1, weights=None, dtype=np.float
     The arrays are views into one array.  lag > 1 works on the lagged views (lag_observations), one result
     per view.  Gaussian and discrete models of up to 8 states run one fused kernel that stores no gamma beyond
     the result; more states run an E-step that stores gamma.  engine_kwargs: device (default 0)."""
-    from .engine import Engine
     from .estimators.maximum_likelihood import model_tuple
     if not isinstance(model, HMM):
         raise TypeError("model must be an HMM object")
@@ -358,7 +383,7 @@ def posterior_marginals(observations, model, lag=1, weights=None, dtype=np.float
         raise TypeError("unexpected keyword arguments: %s" % ", ".join(sorted(engine_kwargs)))
     if lag > 1:
         observations = lag_observations(observations, lag)
-    eng = Engine(device)
+    eng = _engine_for(output, device)
     try:
         if output == 'discrete':
             obs = [np.asarray(o) for o in observations]
@@ -379,7 +404,6 @@ def posterior_transitions(observations, model, lag=1, weights=None, dtype=np.flo
     works on the lagged views (lag_observations), one result per view.  Gaussian and discrete models of up to 8
     states run one fused kernel; more states run filter_states and posterior_marginals on the device, each on the path
     it picks itself, and a kernel over their rows.  engine_kwargs: device (default 0)."""
-    from .engine import Engine
     from .estimators.maximum_likelihood import model_tuple
     if not isinstance(model, HMM):
         raise TypeError("model must be an HMM object")
@@ -401,7 +425,7 @@ def posterior_transitions(observations, model, lag=1, weights=None, dtype=np.flo
         raise TypeError("unexpected keyword arguments: %s" % ", ".join(sorted(engine_kwargs)))
     if lag > 1:
         observations = lag_observations(observations, lag)
-    eng = Engine(device)
+    eng = _engine_for(output, device)
     try:
         if output == 'discrete':
             obs = [np.asarray(o) for o in observations]
@@ -422,7 +446,6 @@ def filter_states(observations, model, lag=1, weights=None, dtype=np.float64, pr
     or float32.  The arrays are views into one array each.  lag > 1 works on the lagged views
     (lag_observations), one result per view.  Gaussian and discrete models of up to 8 states run parallel over
     time; more states run the serial recursion per trajectory.  engine_kwargs: device (default 0)."""
-    from .engine import Engine
     from .estimators.maximum_likelihood import model_tuple
     if not isinstance(model, HMM):
         raise TypeError("model must be an HMM object")
@@ -444,7 +467,7 @@ def filter_states(observations, model, lag=1, weights=None, dtype=np.float64, pr
         raise TypeError("unexpected keyword arguments: %s" % ", ".join(sorted(engine_kwargs)))
     if lag > 1:
         observations = lag_observations(observations, lag)
-    eng = Engine(device)
+    eng = _engine_for(output, device)
     try:
         if output == 'discrete':
             obs = [np.asarray(o) for o in observations]

@@ -1148,6 +1148,12 @@ int bhmm_ctx_set_observations(bhmm_ctx *c, int kind, const void *obs, const int6
         return invalid_arg("nsymbols must be >= 1 for discrete emissions");
     BHMM_HIP(hipSetDevice(c->device));
     BHMM_HIP(hipStreamSynchronize(c->stream));
+    if (!c->mvn.reloading && c->mvn.active) { // observations of another kind: the multivariate set ends (mvn_api.hip)
+        auto &b = c->mvn;                     // and gives its memory back
+        b.active = b.rows_valid = false;
+        b.X.release(), b.rows.release(), b.m.release(), b.shift.release(), b.d_offsets.release();
+        b.tab.release(), b.part.release(), b.out.release();
+    }
     c->d_soff.release(); // random-stream positions belong to the previous trajectories
     c->last_stats = nullptr;
     c->kind = kind;
@@ -1715,6 +1721,12 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->last.pathlp_table;
     else if (n == "pathlp_ms") // ... device time of the last call's prepare, tile and finish passes
         *value = c->last.pathlp_ms;
+    else if (n == "mvn_rows_ms") // multivariate gaussian emissions: device time of the last k_mvn_rows + k_mvn_shift
+        *value = c->mvn.rows_ms;
+    else if (n == "mvn_reload_ms") // ... host time of the explicit re-load that followed them
+        *value = c->mvn.reload_ms;
+    else if (n == "mvn_moments_ms") // ... device time of the last k_mvn_moments + k_mvn_moments_finish
+        *value = c->mvn.moments_ms;
     else
         return invalid_arg("unknown option: " + n);
     return BHMM_OK;

@@ -547,6 +547,35 @@ struct bhmm_ctx {
         }
     } pathlp;
 
+    // multivariate gaussian emissions (mvn_api.hip): the D-dimensional observations X
+    // [total][D], the emission rows made from them [total][n] (handed to bhmm_ctx_set_observations as explicit
+    // observations on the device), m_t [total] and shift_k [K], the tables of the last parameters ([mu | W | c]),
+    // partials and result of the moments.  None of it is touched by bhmm_ctx_set_observations, which the re-load
+    // inside bhmm_mvn_emissions calls (reloading); a call of it from outside ends the set (active)
+    struct MvnBufs {
+        bool active = false;     // bhmm_ctx_set_observations_mvn has loaded X
+        bool reloading = false;  // the bhmm_ctx_set_observations in flight is bhmm_mvn_emissions' own
+        bool rows_valid = false; // rows, m and shift belong to a bhmm_mvn_emissions on these observations
+        int D = 0, n = 0, K = 0, chunk = 0;
+        int64_t total = 0;
+        std::vector<int64_t> offsets; // [K + 1]
+        bhmm::DevBuf<int64_t> d_offsets;
+        bhmm::DevBuf<double> X, rows, m, shift, tab, part, out;
+        // read-only options mvn_rows_ms, mvn_reload_ms, mvn_moments_ms: device time of the rows and shift kernels,
+        // host time of the explicit re-load, device time of the two moment kernels (events ev[0..1], ev[2..3])
+        float rows_ms = 0.f, reload_ms = 0.f, moments_ms = 0.f;
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        MvnBufs() = default;
+        MvnBufs(const MvnBufs &) = delete;
+        MvnBufs &operator=(const MvnBufs &) = delete;
+        ~MvnBufs()
+        {
+            for (hipEvent_t e : ev)
+                if (e)
+                    (void)hipEventDestroy(e);
+        }
+    } mvn;
+
     // ---- pinned host buffers ----
     unsigned int *h_specres = nullptr; // pinned
     double *h_small = nullptr;         // pinned, 64 KB: small results of the path calls (one copy per call)

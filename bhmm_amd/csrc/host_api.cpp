@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <limits>
+#include <string>
 #include <vector>
 
 #include "../../include/bhmm_amd.h"
@@ -99,6 +100,39 @@ extern "C" int bhmm_host_rng_draws(double *out, int64_t count, int what, double 
         out[i] = what == 0 ? rng.u01() : what == 1 ? rng.normal() : what == 2 ? rng.gamma(param)
                                                                                : rng.u01_open();
     return BHMM_OK;
+}
+
+// ---- multivariate gaussian emissions ----------------------------------
+static int mvn_shape_ok(const char *who, int N, int D, int cov_type)
+{
+    if (N < 1 || D < 1 || D > BHMM_MVN_MAX_D)
+        return bhmm::invalid_arg(std::string(who) + ": 1 <= D <= " + std::to_string(BHMM_MVN_MAX_D) +
+                                 " dimensions and at least one state");
+    if (cov_type != BHMM_COV_FULL && cov_type != BHMM_COV_DIAG)
+        return bhmm::invalid_arg(std::string(who) + ": cov_type is BHMM_COV_FULL or BHMM_COV_DIAG");
+    return BHMM_OK;
+}
+
+extern "C" int bhmm_host_mvn_prepare(int N, int D, int cov_type, const double *covs, double *chol, double *winv,
+                                     double *cst)
+{
+    if (int rc = mvn_shape_ok("bhmm_host_mvn_prepare", N, D, cov_type))
+        return rc;
+    if (!covs)
+        return bhmm::invalid_arg("bhmm_host_mvn_prepare: covs == NULL");
+    return mvn_prepare(N, D, cov_type, covs, chol, winv, cst);
+}
+
+extern "C" int bhmm_host_mvn_mstep(int N, int D, int cov_type, const double *moments, const double *means_old,
+                                   double min_covar, double *means_new, double *covs_new)
+{
+    if (int rc = mvn_shape_ok("bhmm_host_mvn_mstep", N, D, cov_type))
+        return rc;
+    if (!moments || !means_old || !means_new || !covs_new)
+        return bhmm::invalid_arg("bhmm_host_mvn_mstep: NULL argument");
+    if (!(min_covar >= 0.0))
+        return bhmm::invalid_arg("bhmm_host_mvn_mstep: min_covar must be >= 0");
+    return mvn_mstep(N, D, cov_type, moments, means_old, min_covar, means_new, covs_new);
 }
 
 // ---- emission M-steps ------------------------------------------------------------------------

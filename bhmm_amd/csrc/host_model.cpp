@@ -14,6 +14,8 @@
 #include <algorithm>
 #include <limits>
 #include <numeric>
+#include <string>
+#include <vector>
 
 #include "../../include/bhmm_amd.h"
 
@@ -682,6 +684,121 @@ void sample_reversible_sweeps_base(const double *C, int n, int64_t nsweeps, uint
 void sample_reversible_sweeps(const double *C, int n, int64_t nsweeps, Rng &rng, double *X)
 {
     sample_reversible_sweeps_base(C, n, nsweeps, rng.bits(), X, 0);
+}
+
+// ---- multivariate gaussian emissions ---------------------------------------------------------
+int mvn_prepare(int n, int D, int cov_type, const double *covs, double *chol, double *winv, double *cst)
+{
+    const size_t fs = mvn_factor_size(D, cov_type);
+    const long double half_log_2pi = 0.5L * logl(2.0L * 3.14159265358979323846264338327950288L);
+    const std::string who = "multivariate gaussian: covariance of state ";
+    if (cov_type) {
+        for (int i = 0; i < n; ++i) {
+            long double lsum = 0.0L;
+            for (int d = 0; d < D; ++d) {
+                const double v = covs[(size_t)i * D + d];
+                if (!std::isfinite(v))
+                    return invalid_arg(who + std::to_string(i) + " has a non-finite entry");
+                if (!(v > 0.0)) {
+                    set_error(who + std::to_string(i) + " is not positive definite");
+                    return BHMM_ERR_SIGMA;
+                }
+                const long double s = sqrtl((long double)v);
+                lsum += logl(s);
+                if (chol)
+                    chol[(size_t)i * D + d] = (double)s;
+                if (winv)
+                    winv[(size_t)i * fs + d] = (double)(1.0L / s);
+            }
+            if (cst)
+                cst[i] = (double)(-lsum - (long double)D * half_log_2pi);
+        }
+        return BHMM_OK;
+    }
+    std::vector<long double> L((size_t)D * D), W((size_t)D * D);
+    for (int i = 0; i < n; ++i) {
+        const double *S = covs + (size_t)i * D * D;
+        for (int a = 0; a < D; ++a)
+            for (int b = 0; b < D; ++b)
+                if (!std::isfinite(S[(size_t)a * D + b]))
+                    return invalid_arg(who + std::to_string(i) + " has a non-finite entry");
+        for (int a = 0; a < D; ++a)
+            for (int b = 0; b < a; ++b) { // symmetric to rounding, on the scale of the two variances
+                const double scale = sqrt(fabs(S[(size_t)a * D + a] * S[(size_t)b * D + b]));
+                if (fabs(S[(size_t)a * D + b] - S[(size_t)b * D + a]) > 1e-10 * scale)
+                    return invalid_arg(who + std::to_string(i) + " is not symmetric");
+            }
+        // Cholesky-Banachiewicz on the lower triangle
+        long double lsum = 0.0L;
+        for (int a = 0; a < D; ++a)
+            for (int b = 0; b <= a; ++b) {
+                long double s = (long double)S[(size_t)a * D + b];
+                for (int k = 0; k < b; ++k)
+                    s -= L[(size_t)a * D + k] * L[(size_t)b * D + k];
+                if (a == b) {
+                    if (!(s > 0.0L) || !std::isfinite((double)s)) {
+                        set_error(who + std::to_string(i) + " is not positive definite");
+                        return BHMM_ERR_SIGMA;
+                    }
+                    L[(size_t)a * D + a] = sqrtl(s);
+                    lsum += logl(L[(size_t)a * D + a]);
+                } else {
+                    L[(size_t)a * D + b] = s / L[(size_t)b * D + b];
+                }
+            }
+        // W = L^-1 by forward substitution, column by column
+        for (int b = 0; b < D; ++b)
+            for (int a = b; a < D; ++a) {
+                long double s = a == b ? 1.0L : 0.0L;
+                for (int k = b; k < a; ++k)
+                    s -= L[(size_t)a * D + k] * W[(size_t)k * D + b];
+                W[(size_t)a * D + b] = s / L[(size_t)a * D + a];
+            }
+        for (int a = 0; a < D; ++a)
+            for (int b = 0; b < D; ++b) {
+                if (chol)
+                    chol[((size_t)i * D + a) * D + b] = b <= a ? (double)L[(size_t)a * D + b] : 0.0;
+                if (winv && b <= a)
+                    winv[(size_t)i * fs + (size_t)a * (a + 1) / 2 + b] = (double)W[(size_t)a * D + b];
+            }
+        if (cst)
+            cst[i] = (double)(-lsum - (long double)D * half_log_2pi);
+    }
+    return BHMM_OK;
+}
+
+int mvn_mstep(int n, int D, int cov_type, const double *moments, const double *means_old, double min_covar,
+              double *means_new, double *covs_new)
+{
+    const size_t ms = mvn_moment_stride(D, cov_type);
+    std::vector<double> delta(D);
+    for (int i = 0; i < n; ++i) {
+        const double *m = moments + (size_t)i * ms;
+        const double w = m[0], *s1 = m + 1, *s2 = m + 1 + D;
+        for (int d = 0; d < D; ++d) {
+            delta[d] = s1[d] / w;
+            means_new[(size_t)i * D + d] = means_old[(size_t)i * D + d] + delta[d];
+        }
+        if (cov_type) {
+            for (int d = 0; d < D; ++d)
+                covs_new[(size_t)i * D + d] = s2[d] / w - delta[d] * delta[d] + min_covar;
+        } else {
+            double *S = covs_new + (size_t)i * D * D;
+            for (int a = 0; a < D; ++a)
+                for (int b = 0; b <= a; ++b) {
+                    const double v = s2[(size_t)a * (a + 1) / 2 + b] / w - delta[a] * delta[b] + (a == b ? min_covar : 0.0);
+                    S[(size_t)a * D + b] = S[(size_t)b * D + a] = v;
+                }
+        }
+    }
+    // (a state without weight gives NaN entries: refused as not positive definite, like a sigma below eps)
+    for (int i = 0; i < n; ++i)
+        for (size_t e = 0; e < (cov_type ? (size_t)D : (size_t)D * D); ++e)
+            if (!std::isfinite(covs_new[(size_t)i * (cov_type ? D : (size_t)D * D) + e])) {
+                set_error("multivariate gaussian M-step: covariance of state " + std::to_string(i) + " is not finite");
+                return BHMM_ERR_SIGMA;
+            }
+    return mvn_prepare(n, D, cov_type, covs_new, nullptr, nullptr, nullptr);
 }
 
 } // namespace host

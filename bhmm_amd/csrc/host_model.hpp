@@ -71,5 +71,22 @@ void sample_reversible_sweeps(const double *C, int n, int64_t nsweeps, Rng &rng,
 void sample_reversible_sweeps_base(const double *C, int n, int64_t nsweeps, uint64_t base, double *X, int lanes);
 int reversible_sampler_lanes();
 
+// ---- multivariate gaussian emissions ----
+// cov_type 0: full, covs[n][D][D] symmetric; 1: diagonal, covs[n][D] variances.  Doubles of one state's factor:
+inline size_t mvn_factor_size(int D, int cov_type) { return cov_type ? (size_t)D : (size_t)D * (D + 1) / 2; }
+// doubles of the packed moments of bhmm_mvn_moments: per state S0 | S1 [D] | S2 (lower triangle, row-major, or diagonal)
+inline size_t mvn_moment_stride(int D, int cov_type) { return 1 + (size_t)D + mvn_factor_size(D, cov_type); }
+// Cholesky factor L_i of every covariance (chol: [n][D][D] lower, zeros above, or [n][D] standard deviations), its
+// inverse W_i packed as the kernels read it (winv: [n][D (D + 1) / 2] lower triangle row-major, or [n][D]) and the
+// constant c_i = -sum_d log L_i[d,d] - D log(2 pi) / 2.  Factor, inverse and constant are formed in long double and
+// rounded once.  Any output may be NULL.  BHMM_ERR_INVALID: a non-finite or asymmetric entry; BHMM_ERR_SIGMA: not
+// positive definite.
+int mvn_prepare(int n, int D, int cov_type, const double *covs, double *chol, double *winv, double *cst);
+// new means and covariances from the packed moments about means_old (gaussian.py:214-272 in D dimensions):
+// mu' = mu + S1 / S0, Sigma' = S2 / S0 - delta delta^T + min_covar I.  BHMM_ERR_SIGMA: a result is not positive
+// definite (or not finite: a state without weight)
+int mvn_mstep(int n, int D, int cov_type, const double *moments, const double *means_old, double min_covar,
+              double *means_new, double *covs_new);
+
 } // namespace host
 } // namespace bhmm

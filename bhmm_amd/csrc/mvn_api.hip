@@ -1,0 +1,284 @@
+// mvn_api.hip -- multivariate gaussian emissions (bhmm_ctx_set_observations_mvn, bhmm_mvn_emissions,
+// bhmm_mvn_fetch_scale, bhmm_mvn_fetch_rows, bhmm_mvn_moments, bhmm_logpdf_mvn): kernels in mvn_kernels.hpp, the
+// factorisation on the host (host::mvn_prepare, host_model.cpp); DESIGN.md section 23.
+//
+// The recursions know nothing of this kind.  bhmm_mvn_emissions turns the observations kept in c->mvn.X into scaled
+// emission rows in c->mvn.rows and hands those to bhmm_ctx_set_observations as BHMM_EMIT_EXPLICIT observations on the
+// device -- the public entry point, nothing of the chunk layouts is touched here -- so every context call then works
+// with par0 = par1 = NULL.  c->mvn.* outlives that re-load (c->mvn.reloading tells bhmm_ctx_set_observations that
+// the call is ours); bhmm_ctx_destroy frees it with the context.
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <string>
+#include <vector>
+
+#include "host_internal.hpp"
+#include "host_model.hpp"
+#include "launch.hpp"
+#include "mvn_kernels.hpp"
+
+namespace bhmm {
+namespace {
+
+using namespace mvn;
+
+int shape_ok(const char *who, int n, int D, int cov_type)
+{
+    if (n < 1 || n > 4096)
+        return invalid_arg(std::string(who) + ": 1..4096 hidden states are supported");
+    if (D < 1 || D > BHMM_MVN_MAX_D)
+        return invalid_arg(std::string(who) + ": 1 <= D <= " + std::to_string(BHMM_MVN_MAX_D) + " dimensions");
+    if (cov_type != BHMM_COV_FULL && cov_type != BHMM_COV_DIAG)
+        return invalid_arg(std::string(who) + ": cov_type is BHMM_COV_FULL or BHMM_COV_DIAG");
+    return BHMM_OK;
+}
+
+// [mu | W | c] of the parameters, validated; BHMM_ERR_INVALID / BHMM_ERR_SIGMA
+int make_table(const char *who, int n, int D, int cov_type, const double *means, const double *covs,
+               std::vector<double> &tab)
+{
+    for (size_t e = 0; e < (size_t)n * D; ++e)
+        if (!std::isfinite(means[e]))
+            return invalid_arg(std::string(who) + ": a mean is not finite");
+    const size_t fs = factor_size(D, cov_type == BHMM_COV_DIAG);
+    tab.resize((size_t)n * D + (size_t)n * fs + n);
+    memcpy(tab.data(), means, (size_t)n * D * sizeof(double));
+    return host::mvn_prepare(n, D, cov_type, covs, nullptr, tab.data() + (size_t)n * D,
+                             tab.data() + (size_t)n * D + (size_t)n * fs);
+}
+
+template <bool DIAG>
+hipError_t launch_rows(hipStream_t stream, const double *X, int64_t total, int D, int n, const double *tab,
+                       double *rows, double *m, double *logp)
+{
+    const dim3 grid((unsigned)((total + ROWS_THREADS - 1) / ROWS_THREADS)), block(ROWS_THREADS);
+#define BHMM_MVN_ROWS(DMAX) launch(k_mvn_rows<DMAX, DIAG>, grid, block, 0, stream, X, total, D, n, tab, rows, m, logp)
+    if (D <= 2)
+        return BHMM_MVN_ROWS(2);
+    if (D <= 4)
+        return BHMM_MVN_ROWS(4);
+    if (D <= 8)
+        return BHMM_MVN_ROWS(8);
+    if (D <= 16)
+        return BHMM_MVN_ROWS(16);
+    if (D <= 32)
+        return BHMM_MVN_ROWS(32);
+    return BHMM_MVN_ROWS(64);
+#undef BHMM_MVN_ROWS
+}
+
+int run_rows(hipStream_t stream, const double *X, int64_t total, int D, int n, int cov_type, const double *tab,
+             double *rows, double *m, double *logp)
+{
+    if ((total + ROWS_THREADS - 1) / ROWS_THREADS > 0x7fffffff)
+        return invalid_arg("multivariate gaussian emissions: more steps than a grid has workgroups");
+    BHMM_HIP(cov_type == BHMM_COV_DIAG ? launch_rows<true>(stream, X, total, D, n, tab, rows, m, logp)
+                                       : launch_rows<false>(stream, X, total, D, n, tab, rows, m, logp));
+    return BHMM_OK;
+}
+
+struct Tmp { // device allocations of one level-1 call
+    std::vector<void *> ptrs;
+    ~Tmp()
+    {
+        for (void *p : ptrs)
+            (void)hipFree(p);
+    }
+    int alloc(double **out, size_t count)
+    {
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, count * sizeof(double));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("hipMalloc of " + std::to_string(count * sizeof(double)) + " bytes failed");
+            return BHMM_ERR_NO_MEM;
+        }
+        ptrs.push_back(p);
+        *out = static_cast<double *>(p);
+        return BHMM_OK;
+    }
+};
+
+} // namespace
+} // namespace bhmm
+
+using namespace bhmm;
+
+extern "C" {
+
+int bhmm_ctx_set_observations_mvn(bhmm_ctx *c, const double *X, const int64_t *offsets, int K, int D, int nstates,
+                                  int chunk, int obs_on_device)
+{
+    if (!c || !X || !offsets || K < 1)
+        return invalid_arg("bhmm_ctx_set_observations_mvn: bad context / X / offsets / K");
+    if (int rc = shape_ok("bhmm_ctx_set_observations_mvn", nstates, D, BHMM_COV_FULL))
+        return rc;
+    for (int k = 0; k < K; ++k)
+        if (offsets[k + 1] < offsets[k])
+            return invalid_arg("bhmm_ctx_set_observations_mvn: offsets must be non-decreasing");
+    const int64_t total = offsets[K] - offsets[0];
+    if (total <= 0)
+        return invalid_arg("bhmm_ctx_set_observations_mvn: no observations");
+    BHMM_HIP(hipSetDevice(c->device));
+    BHMM_HIP(hipStreamSynchronize(c->stream));
+    auto &b = c->mvn;
+    b.active = b.rows_valid = false;
+    c->kind = -1; // (whatever was loaded before is not what the caller means any more: no model call until the
+                  // first bhmm_mvn_emissions)
+    int rc;
+    if ((rc = b.X.ensure((size_t)total * D)) || (rc = b.rows.ensure((size_t)total * nstates)) ||
+        (rc = b.m.ensure((size_t)total)) || (rc = b.shift.ensure((size_t)K)) || (rc = b.d_offsets.ensure((size_t)K + 1)))
+        return rc;
+    b.offsets.resize((size_t)K + 1);
+    for (int k = 0; k <= K; ++k) // positions relative to the first step handed over
+        b.offsets[k] = offsets[k] - offsets[0];
+    BHMM_HIP(hipMemcpyAsync(b.X.p, X + (size_t)offsets[0] * D, (size_t)total * D * sizeof(double),
+                            obs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(b.d_offsets.p, b.offsets.data(), ((size_t)K + 1) * sizeof(int64_t), hipMemcpyHostToDevice,
+                            c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream));
+    b.D = D;
+    b.n = nstates;
+    b.K = K;
+    b.chunk = chunk;
+    b.total = total;
+    b.active = true;
+    return BHMM_OK;
+}
+
+int bhmm_mvn_emissions(bhmm_ctx *c, const double *means, const double *covs, int cov_type)
+{
+    if (!c || !c->mvn.active)
+        return invalid_arg("bhmm_mvn_emissions: no multivariate observations loaded");
+    if (!means || !covs)
+        return invalid_arg("bhmm_mvn_emissions: means / covs == NULL");
+    auto &b = c->mvn;
+    int rc;
+    if ((rc = shape_ok("bhmm_mvn_emissions", b.n, b.D, cov_type)))
+        return rc;
+    std::vector<double> tab;
+    if ((rc = make_table("bhmm_mvn_emissions", b.n, b.D, cov_type, means, covs, tab)))
+        return rc;
+    BHMM_HIP(hipSetDevice(c->device));
+    b.rows_valid = false;
+    if ((rc = b.tab.ensure(tab.size())))
+        return rc;
+    BHMM_HIP(hipMemcpyAsync(b.tab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    for (hipEvent_t &e : b.ev)
+        if (!e)
+            BHMM_HIP(hipEventCreate(&e));
+    BHMM_HIP(hipEventRecord(b.ev[0], c->stream));
+    if ((rc = run_rows(c->stream, b.X.p, b.total, b.D, b.n, cov_type, b.tab.p, b.rows.p, b.m.p, nullptr)))
+        return rc;
+    BHMM_HIP(launch(k_mvn_shift, dim3((unsigned)std::min(b.K, 65535)), dim3(SHIFT_THREADS), 0, c->stream, b.m.p,
+                    b.d_offsets.p, b.K, b.shift.p));
+    BHMM_HIP(hipEventRecord(b.ev[1], c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream)); // (tab is a temporary; the re-load below waits for the stream anyway)
+    (void)hipEventElapsedTime(&b.rows_ms, b.ev[0], b.ev[1]);
+    const auto t0 = std::chrono::steady_clock::now();
+    b.reloading = true;
+    rc = bhmm_ctx_set_observations(c, BHMM_EMIT_EXPLICIT, b.rows.p, b.offsets.data(), b.K, b.n, 0, b.chunk, 1);
+    b.reloading = false;
+    b.reload_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc)
+        return rc;
+    b.rows_valid = true;
+    return BHMM_OK;
+}
+
+int bhmm_mvn_fetch_scale(bhmm_ctx *c, double *shift_k, double *m_t)
+{
+    if (!c || !c->mvn.active || !c->mvn.rows_valid)
+        return invalid_arg("bhmm_mvn_fetch_scale: no bhmm_mvn_emissions has run on these observations");
+    auto &b = c->mvn;
+    BHMM_HIP(hipSetDevice(c->device));
+    if (shift_k)
+        BHMM_HIP(hipMemcpyAsync(shift_k, b.shift.p, (size_t)b.K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (m_t)
+        BHMM_HIP(hipMemcpyAsync(m_t, b.m.p, (size_t)b.total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream));
+    return BHMM_OK;
+}
+
+int bhmm_mvn_fetch_rows(bhmm_ctx *c, double *rows)
+{
+    if (!c || !c->mvn.active || !c->mvn.rows_valid)
+        return invalid_arg("bhmm_mvn_fetch_rows: no bhmm_mvn_emissions has run on these observations");
+    if (!rows)
+        return invalid_arg("bhmm_mvn_fetch_rows: rows == NULL");
+    auto &b = c->mvn;
+    BHMM_HIP(hipSetDevice(c->device));
+    BHMM_HIP(hipMemcpyAsync(rows, b.rows.p, (size_t)b.total * b.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream));
+    return BHMM_OK;
+}
+
+int bhmm_mvn_moments(bhmm_ctx *c, const double *gamma_dev, const double *means, int cov_type, double *out)
+{
+    if (!c || !c->mvn.active)
+        return invalid_arg("bhmm_mvn_moments: no multivariate observations loaded");
+    if (!gamma_dev || !means || !out)
+        return invalid_arg("bhmm_mvn_moments: gamma_dev / means / out == NULL");
+    auto &b = c->mvn;
+    int rc;
+    if ((rc = shape_ok("bhmm_mvn_moments", b.n, b.D, cov_type)))
+        return rc;
+    const bool diag = cov_type == BHMM_COV_DIAG;
+    const int D = b.D, n = b.n;
+    const int64_t ms = (int64_t)moment_stride(D, diag), E = (int64_t)n * ms;
+    const int epb = (int)std::min<int64_t>(E, MOM_THREADS);
+    const int64_t gy = (E + epb - 1) / epb;
+    const int nsi_max = (int)std::min<int64_t>(n, (epb - 1) / ms + 2);
+    const int64_t tiles = (b.total + MOM_TILE - 1) / MOM_TILE;
+    const int G = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, MOM_MAX_GROUPS / gy));
+    const int64_t span = (b.total + G - 1) / G;
+    const size_t lds = ((size_t)MOM_TILE * (D + nsi_max) + MOM_THREADS) * sizeof(double);
+    BHMM_HIP(hipSetDevice(c->device));
+    if ((rc = b.part.ensure((size_t)G * E)) || (rc = b.out.ensure((size_t)E)) || (rc = b.tab.ensure((size_t)n * D)))
+        return rc;
+    // (the table of the last bhmm_mvn_emissions is not needed any more: the rows are made)
+    BHMM_HIP(hipMemcpyAsync(b.tab.p, means, (size_t)n * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const dim3 grid((unsigned)G, (unsigned)gy), block(MOM_THREADS);
+    for (hipEvent_t &e : b.ev)
+        if (!e)
+            BHMM_HIP(hipEventCreate(&e));
+    BHMM_HIP(hipEventRecord(b.ev[2], c->stream));
+    BHMM_HIP(diag ? launch(k_mvn_moments<true>, grid, block, lds, c->stream, b.X.p, gamma_dev, b.total, D, n, b.tab.p,
+                           span, epb, nsi_max, b.part.p)
+                  : launch(k_mvn_moments<false>, grid, block, lds, c->stream, b.X.p, gamma_dev, b.total, D, n, b.tab.p,
+                           span, epb, nsi_max, b.part.p));
+    BHMM_HIP(launch(k_mvn_moments_finish, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, c->stream, b.part.p, G, E,
+                    b.out.p));
+    BHMM_HIP(hipEventRecord(b.ev[3], c->stream));
+    BHMM_HIP(hipMemcpyAsync(out, b.out.p, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream));
+    (void)hipEventElapsedTime(&b.moments_ms, b.ev[2], b.ev[3]);
+    return BHMM_OK;
+}
+
+int bhmm_logpdf_mvn(double *logp, const double *X, int64_t T, int D, int N, const double *means, const double *covs,
+                    int cov_type)
+{
+    if (!logp || !X || !means || !covs || T < 1)
+        return invalid_arg("bhmm_logpdf_mvn: NULL argument or empty problem");
+    int rc;
+    if ((rc = shape_ok("bhmm_logpdf_mvn", N, D, cov_type)))
+        return rc;
+    std::vector<double> tab;
+    if ((rc = make_table("bhmm_logpdf_mvn", N, D, cov_type, means, covs, tab)))
+        return rc;
+    Tmp tmp;
+    double *dX, *dtab, *dl;
+    if ((rc = tmp.alloc(&dX, (size_t)T * D)) || (rc = tmp.alloc(&dtab, tab.size())) || (rc = tmp.alloc(&dl, (size_t)T * N)))
+        return rc;
+    BHMM_HIP(hipMemcpy(dX, X, (size_t)T * D * sizeof(double), hipMemcpyHostToDevice));
+    BHMM_HIP(hipMemcpy(dtab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = run_rows(nullptr, dX, T, D, N, cov_type, dtab, nullptr, nullptr, dl))) // (l alone: no rows, no m_t)
+        return rc;
+    BHMM_HIP(hipMemcpy(logp, dl, (size_t)T * N * sizeof(double), hipMemcpyDeviceToHost));
+    return BHMM_OK;
+}
+
+} // extern "C"

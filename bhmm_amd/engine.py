@@ -16,7 +16,7 @@ class EStepResult(object):
     """Reduced sufficient statistics of one E-step (what maximum_likelihood.py:271-282 and the
     emission `estimate` methods consume)."""
 
-    def __init__(self, kind, n, M, packed, logL_k):
+    def __init__(self, kind, n, M, packed, logL_k, dimension=0, covariance_type=None):
         self.kind = kind
         self.packed = packed
         self.logL_k = logL_k
@@ -31,6 +31,14 @@ class EStepResult(object):
             self.sum_gdd = packed[o:o + n].copy(); o += n
         elif kind == 'discrete':
             self.symbol_counts = packed[o:o + n * M].reshape(n, M).copy(); o += n * M
+        # multivariate gaussian: the moments about the means of the E-step's model (bhmm_mvn_moments) -- S0 (n,),
+        # S1 (n, D), S2 (n, D, D) symmetric or (n, D) -- and the packed block they came in
+        self.moments = self.S0 = self.S1 = self.S2 = None
+        if kind == 'mvgaussian':
+            from .output_models.mvgaussian import moment_stride, unpack_moments
+            size = n * moment_stride(dimension, covariance_type)
+            self.moments = packed[o:o + size].copy(); o += size
+            self.S0, self.S1, self.S2 = unpack_moments(self.moments, n, dimension, covariance_type)
 
 
 class PathRuns(object):
@@ -181,7 +189,17 @@ class Engine(object):
         self._fetch = None
 
     @property
+    def _ctx_kind(self):
+        """The kind of what the CONTEXT holds, which is what this class's methods go by: the kind the caller loaded,
+        unless a subclass loads the context with something else (MvnEngine: explicit rows)."""
+        return self.kind
+
+    @property
     def stats_size(self):
+        return self._ctx_stats_size()
+
+    def _ctx_stats_size(self):
+        """doubles of the context's own packed statistics vector"""
         return self._L.bhmm_ctx_stats_size(self._h)
 
     @property
@@ -268,17 +286,17 @@ class Engine(object):
                                       flags))
 
     def estep_fetch(self):
-        S = self.stats_size
+        S = self._ctx_stats_size()
         packed = np.empty(S)
         logL_k = np.empty(len(self.lengths))
         _lib.check(self._L.bhmm_estep_fetch(self._h, _lib.dp(packed), _lib.dp(logL_k)))
-        return EStepResult(self.kind, self.nstates, self.nsymbols, packed, logL_k)
+        return EStepResult(self._ctx_kind, self.nstates, self.nsymbols, packed, logL_k)
 
     def estep_fetch_packed(self, out=None):
         """Wait for the last E-step and return only its packed statistics vector (layout:
         include/bhmm_amd.h, bhmm_ctx_stats_size) -- no per-field copies, no logL_k."""
         if out is None:
-            out = np.empty(self.stats_size)
+            out = np.empty(self._ctx_stats_size())
         f = self._fetch
         if f is None or f[0] is not out:            # the pointer of a re-used `out` is made once
             f = self._fetch = (out, _lib.dp(out))
@@ -297,7 +315,7 @@ class Engine(object):
         return self.estep_fetch()
 
     def unpack(self, packed, logL_k=None):
-        return EStepResult(self.kind, self.nstates, self.nsymbols, np.asarray(packed), logL_k)
+        return EStepResult(self._ctx_kind, self.nstates, self.nsymbols, np.asarray(packed), logL_k)
 
     def gamma(self, k):
         T = int(self.lengths[k])
@@ -315,9 +333,9 @@ class Engine(object):
         score_seglen; get_option("score_path") is 2 there, "score_segments" the plan's size), 65 to 128 states
         the same on the matrix cores (score_path 3) -- up to 128 states run parallel over time; more than 128
         states and explicit pobs take the exact serial recursion (score_path 0)."""
-        if self.kind is None:
+        if self._ctx_kind is None:
             raise ValueError("no observations loaded")
-        A, pi, p0, p1 = stack_models(self.kind, self.nstates, self.nsymbols, models)
+        A, pi, p0, p1 = stack_models(self._ctx_kind, self.nstates, self.nsymbols, models)
         logL = np.empty((len(models), len(self.lengths)))
         _lib.check(self._L.bhmm_score(self._h, len(models), _lib.dp(A), _lib.dp(pi), _lib.dp(p0), _lib.dp(p1),
                                       _lib.dp(logL)))
@@ -325,17 +343,17 @@ class Engine(object):
 
     def _check_model(self, A, pi, par0, par1):
         """Shapes of one model against the loaded observations, before any native call."""
-        if self.kind is None:
+        if self._ctx_kind is None:
             raise ValueError("no observations loaded")
         n, M = self.nstates, self.nsymbols
         if np.shape(A) != (n, n) or np.shape(pi) != (n,):
             raise ValueError("A must be (%d, %d) and pi (%d,)" % (n, n, n))
-        if self.kind == 'gaussian':
+        if self._ctx_kind == 'gaussian':
             if par0 is None or par1 is None:
                 raise ValueError("gaussian emissions need means and sigmas")
             if np.shape(par0) != (n,) or np.shape(par1) != (n,):
                 raise ValueError("means and sigmas must be (%d,)" % n)
-        elif self.kind == 'discrete':
+        elif self._ctx_kind == 'discrete':
             if par0 is None:
                 raise ValueError("discrete emissions need B")
             if np.shape(par0) != (n, M):
@@ -363,7 +381,7 @@ class Engine(object):
         observation) sends the whole call to the E-step route; the same options, read-only
         smooth_tile_min_total.  Everything else (9 states and more otherwise, explicit pobs) runs an
         E-step that stores gamma and counts as one (post_path 0)."""
-        if self.kind is None:
+        if self._ctx_kind is None:
             raise ValueError("no observations loaded")
         n = self.nstates
         self._check_model(A, pi, par0, par1)
@@ -667,7 +685,7 @@ class Engine(object):
     def _path_arg(self, paths):
         """(address, one byte per step, on this engine's GPU) of a flat path, validated against the loaded
         trajectories before any native call (path_runs, path_logprob)."""
-        if self.kind is None:
+        if self._ctx_kind is None:
             raise ValueError("no observations loaded")
         total = int(self.offsets[-1])
         on_dev = 0
@@ -714,12 +732,12 @@ class Engine(object):
         atomics, so the result is bitwise the same from call to call, for a host and a device path, for uint8 and
         int32, and for a model alone and inside a stack (read-only options "pathlp_tile", "pathlp_lane",
         "pathlp_table": 1 if the log-transition table sat in LDS, "pathlp_ms": device time)."""
-        if self.kind is None:
+        if self._ctx_kind is None:
             raise ValueError("no observations loaded")
         if isinstance(paths, (list, tuple)):
             paths = self._concat_paths(paths)
         ptr, u8, on_dev = self._path_arg(paths)
-        A, pi, p0, p1 = stack_models(self.kind, self.nstates, self.nsymbols, models)
+        A, pi, p0, p1 = stack_models(self._ctx_kind, self.nstates, self.nsymbols, models)
         S = A.shape[0]
         logp = np.empty((S, len(self.lengths)))
         _lib.check(self._L.bhmm_path_logprob(self._h, ctypes.c_void_p(int(ptr)), 1 if u8 else 0, on_dev, S, _lib.dp(A),
@@ -824,9 +842,9 @@ class Engine(object):
         C = np.rint(packed[:n * n]).astype(np.int64).reshape(n, n)
         n0 = np.rint(packed[n * n:n * n + n]).astype(np.int64)
         rest = packed[n * n + n:]
-        if self.kind == 'gaussian':
+        if self._ctx_kind == 'gaussian':
             emis = rest[:3 * n].reshape(3, n).copy()
-        elif self.kind == 'discrete':
+        elif self._ctx_kind == 'discrete':
             emis = rest[:n * M].reshape(n, M).copy()
         else:
             emis = None
@@ -840,9 +858,9 @@ class Engine(object):
         paths = np.empty(total, dtype=np.int32) if want_paths else None
         C = np.zeros((n, n), dtype=np.int64)
         n0 = np.zeros(n, dtype=np.int64)
-        if self.kind == 'gaussian':
+        if self._ctx_kind == 'gaussian':
             emis = np.zeros((3, n))
-        elif self.kind == 'discrete':
+        elif self._ctx_kind == 'discrete':
             emis = np.zeros((n, self.nsymbols))
         else:
             emis = None
@@ -854,6 +872,288 @@ class Engine(object):
         if want_paths:
             plist = [paths[self.offsets[k]:self.offsets[k + 1]] for k in range(len(self.lengths))]
         return plist, C, n0, emis
+
+
+class MvnEngine(Engine):
+    """Engine for multivariate gaussian emissions (kind 'mvgaussian'): the observations are
+    (T_k, D) arrays, a model is (A, pi, means (n, D), covariances (n, D, D) or (n, D) variances).  The recursions run
+    on explicit emission rows: a model-taking method first makes the rows exp(l_ti - m_t) on the device from the
+    observations kept there (bhmm_mvn_emissions; not again while the parameters are the ones the loaded rows were
+    made from), calls the base method without emission parameters and adds what the scaling took out -- shift_k =
+    sum_t m_t to every per-trajectory log-likelihood and path log-probability, m_t to the filter increments.  An
+    E-step also returns the moments of the M-step (bhmm_mvn_moments) from the posterior rows left on the device."""
+
+    def __init__(self, device=0, stream=None):
+        Engine.__init__(self, device, stream)
+        self.dimension = 0
+        self._loaded = None        # (means, covariances) the rows on the device were made from
+        self._shift = self._m_t = None
+        self._gamma_dev = None
+        self._moments = None
+        self._cov_last = None
+
+    @property
+    def _ctx_kind(self):
+        """explicit rows once emissions have been made, nothing a model call can use before"""
+        return 'explicit' if self._shift is not None else None
+
+    # -- data ---------------------------------------------------------------------------
+    def _set(self, ptr, off, nstates, D, chunk, on_device):
+        if not 1 <= int(D) <= _lib.MVN_MAX_D:
+            raise ValueError("1 <= D <= %d dimensions are supported, not %d" % (_lib.MVN_MAX_D, D))
+        self.dimension = 0
+        _lib.check(self._L.bhmm_ctx_set_observations_mvn(self._h, ctypes.c_void_p(int(ptr)), _lib.lp(off), len(off) - 1,
+                                                         int(D), int(nstates), int(chunk), on_device))
+        self._adopt('mvgaussian', nstates, 0, np.diff(off))
+        self.dimension = int(D)
+        self._loaded = self._shift = self._m_t = self._moments = self._cov_last = None
+
+    def set_observations(self, kind, observations, nstates, nsymbols=0, chunk=0):
+        """observations: list of (T_k, D) float arrays, 1 <= D <= 64."""
+        if kind != 'mvgaussian':
+            raise ValueError("an MvnEngine holds observations of kind 'mvgaussian', not %r" % (kind,))
+        from .output_models.mvgaussian import check_observation
+        obs = [check_observation(o) for o in observations]
+        if not obs:
+            raise ValueError("no observations")
+        D = obs[0].shape[1]
+        if any(o.shape[1] != D for o in obs):
+            raise ValueError("every trajectory must have the same number of columns")
+        off = np.zeros(len(obs) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([o.shape[0] for o in obs])
+        flat = np.ascontiguousarray(np.concatenate(obs, axis=0))
+        self._set(flat.ctypes.data, off, nstates, D, chunk, 0)
+
+    def set_observations_device(self, kind, dev_ptr, offsets, nstates, nsymbols=0, chunk=0, dimension=None):
+        """The same for a (sum T_k, D) row-major float64 buffer already on this GPU (integer device address)."""
+        if kind != 'mvgaussian' or dimension is None:
+            raise ValueError("an MvnEngine takes kind 'mvgaussian' and the dimension of the observations")
+        self._set(dev_ptr, np.ascontiguousarray(offsets, dtype=np.int64), nstates, dimension, chunk, 1)
+
+    def set_observations_lagged(self, *args, **kwargs):
+        raise NotImplementedError("lagged views are cut on the host for multivariate observations")
+
+    @property
+    def stats_size(self):
+        """The explicit kind's vector followed by the moment block of the last covariance type (full before any)."""
+        from .output_models.mvgaussian import moment_stride
+        return self._ctx_stats_size() + self.nstates * moment_stride(self.dimension, self._cov_last or 'full')
+
+    # -- emissions ------------------------------------------------------------------------
+    def _params(self, par0, par1):
+        """(means (n, D), covariances, covariance type) of one model, shapes checked."""
+        if self.dimension == 0:
+            raise ValueError("no observations loaded")
+        if par0 is None or par1 is None:
+            raise ValueError("multivariate gaussian emissions need means and covariances")
+        n, D = self.nstates, self.dimension
+        mu, cov = _lib.f64(par0), _lib.f64(par1)
+        if mu.shape != (n, D):
+            raise ValueError("means must be (%d, %d), not %r" % (n, D, mu.shape))
+        if cov.shape == (n, D, D):
+            return mu, cov, 'full'
+        if cov.shape == (n, D):
+            return mu, cov, 'diag'
+        raise ValueError("covariances must be (%d, %d, %d) or (%d, %d), not %r" % (n, D, D, n, D, cov.shape))
+
+    def emissions(self, par0, par1, force=False):
+        """Make the emission rows of (means, covariances) the context's observations, unless the loaded ones were
+        made from the same parameters (force: make them anyway).  Returns the covariance type."""
+        mu, cov, ctype = self._params(par0, par1)
+        ld = self._loaded
+        if not force and ld is not None and ld[0].shape == mu.shape and ld[1].shape == cov.shape \
+                and np.array_equal(ld[0], mu) and np.array_equal(ld[1], cov):
+            return ctype
+        self._loaded = self._shift = self._m_t = self._moments = None   # (the re-load ends the last E-step too)
+        _lib.check(self._L.bhmm_mvn_emissions(self._h, _lib.dp(mu), _lib.dp(cov),
+                                              _lib.COV_FULL if ctype == 'full' else _lib.COV_DIAG))
+        self._stage = None
+        self._fetch = None
+        shift = np.empty(len(self.lengths))
+        _lib.check(self._L.bhmm_mvn_fetch_scale(self._h, _lib.dp(shift), None))
+        self._shift = shift
+        self._loaded = (mu.copy(), cov.copy())
+        return ctype
+
+    @property
+    def shifts(self):
+        """shift_k = sum_t m_t of the loaded emission rows, per trajectory."""
+        if self._shift is None:
+            raise ValueError("no emissions made yet")
+        return self._shift
+
+    def step_scales(self):
+        """m_t = max_i l_ti of the loaded emission rows, concatenated over the trajectories."""
+        if self._shift is None:
+            raise ValueError("no emissions made yet")
+        if self._m_t is None:
+            m = np.empty(int(self.offsets[-1]))
+            _lib.check(self._L.bhmm_mvn_fetch_scale(self._h, None, _lib.dp(m)))
+            self._m_t = m
+        return self._m_t
+
+    def emission_rows(self):
+        """The loaded emission rows exp(l_ti - m_t), (sum T_k, nstates), copied to the host (tests, diagnostics)."""
+        if self._shift is None:
+            raise ValueError("no emissions made yet")
+        rows = np.empty((int(self.offsets[-1]), self.nstates))
+        _lib.check(self._L.bhmm_mvn_fetch_rows(self._h, _lib.dp(rows)))
+        return rows
+
+    def moments(self, gamma_dev, means, covariance_type='full'):
+        """Packed moments of the M-step (bhmm_mvn_moments) from posterior rows on this GPU: gamma_dev is the
+        integer device address of (sum T_k, nstates) float64 rows, or an object with data_ptr()."""
+        from .output_models.mvgaussian import moment_stride
+        mu = _lib.f64(means)
+        if mu.shape != (self.nstates, self.dimension):
+            raise ValueError("means must be (%d, %d)" % (self.nstates, self.dimension))
+        ptr = gamma_dev.data_ptr() if hasattr(gamma_dev, 'data_ptr') else int(gamma_dev)
+        out = np.empty(self.nstates * moment_stride(self.dimension, covariance_type))
+        _lib.check(self._L.bhmm_mvn_moments(self._h, ctypes.c_void_p(ptr), _lib.dp(mu),
+                                            _lib.COV_FULL if covariance_type == 'full' else _lib.COV_DIAG,
+                                            _lib.dp(out)))
+        return out
+
+    # -- E-step --------------------------------------------------------------------------
+    def estep_launch(self, A, pi, par0=None, par1=None, stats_dev=None, store_gamma=False, single=False):
+        """One E-step: emission rows, then ONE pass of the recursions that leaves the posterior rows on the device
+        (posterior_marginals, which on explicit rows is an E-step that stores gamma: its packed statistics stay in
+        the context for estep_fetch), then the moments from those rows.  Synchronous."""
+        if stats_dev is not None:
+            raise NotImplementedError("multivariate gaussian E-steps keep their statistics in the context")
+        if single:
+            raise NotImplementedError("multivariate gaussian E-steps run in float64")
+        ctype = self.emissions(par0, par1)
+        import torch
+        total = int(self.offsets[-1])
+        g = self._gamma_dev
+        if g is None or g.numel() != total * self.nstates or g.device.index != self.device:
+            g = self._gamma_dev = torch.empty(total * self.nstates, dtype=torch.float64,
+                                              device='cuda:%d' % self.device)
+        Engine.posterior_marginals(self, A, pi, out=g.data_ptr())
+        self._moments = self.moments(g.data_ptr(), self._loaded[0], ctype)
+        self._cov_last = ctype
+
+    def _shifted(self, packed):
+        packed[0] += self._shift.sum()
+        return np.concatenate([packed, self._moments])
+
+    def estep_fetch(self):
+        if self._moments is None:
+            raise ValueError("no E-step has run on these observations")
+        res = Engine.estep_fetch(self)
+        return EStepResult('mvgaussian', self.nstates, 0, self._shifted(res.packed), res.logL_k + self._shift,
+                           self.dimension, self._cov_last)
+
+    def estep_fetch_packed(self, out=None):
+        """The explicit kind's packed vector, its log-likelihood with the shifts added, followed by the packed
+        moments of bhmm_mvn_moments."""
+        if self._moments is None:
+            raise ValueError("no E-step has run on these observations")
+        packed = Engine.estep_fetch_packed(self)
+        packed = self._shifted(packed)
+        if out is None:
+            return packed
+        out[:] = packed
+        return out
+
+    def estep_fetch_logL(self):
+        return Engine.estep_fetch_logL(self) + self._shift
+
+    def estep(self, A, pi, par0=None, par1=None, store_gamma=False, single=False):
+        self.estep_launch(A, pi, par0, par1, store_gamma=store_gamma, single=single)
+        return self.estep_fetch()
+
+    def unpack(self, packed, logL_k=None):
+        return EStepResult('mvgaussian', self.nstates, 0, np.asarray(packed), logL_k, self.dimension,
+                           self._cov_last or 'full')
+
+    # -- everything else: emissions, the base call on explicit rows, the shifts --------------
+    def score(self, models):
+        """(S, K) log-likelihoods; one emission pass per model."""
+        models = list(models)
+        if not models:
+            raise ValueError("score needs at least one model")
+        out = np.empty((len(models), len(self.lengths)))
+        for s, m in enumerate(models):
+            if len(m) != 4:
+                raise ValueError("model %d: expected an (A, pi, means, covariances) tuple" % s)
+            self.emissions(m[2], m[3])
+            out[s] = Engine.score(self, [(m[0], m[1], None, None)])[0] + self._shift
+        return out
+
+    def posterior_decode(self, A, pi, par0=None, par1=None, confidence=False, out=None):
+        self.emissions(par0, par1)
+        return Engine.posterior_decode(self, A, pi, confidence=confidence, out=out)
+
+    def posterior_marginals(self, A, pi, par0=None, par1=None, weights=None, dtype=np.float64, out=None):
+        self.emissions(par0, par1)
+        return Engine.posterior_marginals(self, A, pi, weights=weights, dtype=dtype, out=out)
+
+    def posterior_transitions(self, A, pi, par0=None, par1=None, weights=None, dtype=np.float64, out=None):
+        self.emissions(par0, par1)
+        return Engine.posterior_transitions(self, A, pi, weights=weights, dtype=dtype, out=out)
+
+    def filter_states(self, A, pi, par0=None, par1=None, weights=None, dtype=np.float64, probabilities=True,
+                      increments=True, out=None, out_increments=None):
+        """As Engine.filter_states; m_t is added to the increments, so they are those of the true densities and sum
+        to the log-likelihood.  Increments left at a raw device address are not supported (pass a tensor)."""
+        if increments and out_increments is not None and not isinstance(out_increments, np.ndarray) \
+                and not hasattr(out_increments, 'data_ptr'):
+            raise NotImplementedError("increments at a raw device address: pass a numpy array or a tensor")
+        self.emissions(par0, par1)
+        rows, logc = Engine.filter_states(self, A, pi, weights=weights, dtype=dtype, probabilities=probabilities,
+                                          increments=increments, out=out, out_increments=out_increments)
+        if logc is not None:
+            m = self.step_scales()
+            on_tensor = out_increments is not None and hasattr(out_increments, 'data_ptr')
+            if on_tensor:
+                import torch
+                self.sync()
+            for k, l in enumerate(logc):
+                mk = m[self.offsets[k]:self.offsets[k + 1]]
+                if on_tensor:
+                    l += torch.from_numpy(mk).to(device=l.device, dtype=l.dtype)
+                else:
+                    l += mk.astype(l.dtype)
+        return rows, logc
+
+    def viterbi(self, A, pi, par0=None, par1=None):
+        self.emissions(par0, par1)
+        return Engine.viterbi(self, A, pi)
+
+    def viterbi_u8(self, A, pi, par0=None, par1=None, out=None):
+        self.emissions(par0, par1)
+        return Engine.viterbi_u8(self, A, pi, out=out)
+
+    def path_logprob(self, paths, models):
+        """(S, K) joint log-probabilities of given paths; one emission pass per model."""
+        models = list(models)
+        if not models:
+            raise ValueError("path_logprob needs at least one model")
+        out = np.empty((len(models), len(self.lengths)))
+        for s, m in enumerate(models):
+            if len(m) != 4:
+                raise ValueError("model %d: expected an (A, pi, means, covariances) tuple" % s)
+            self.emissions(m[2], m[3])
+            out[s] = Engine.path_logprob(self, paths, [(m[0], m[1], None, None)])[0] + self._shift
+        return out
+
+    def decode_logprob(self, A, pi, par0=None, par1=None, method='viterbi'):
+        self.emissions(par0, par1)
+        return Engine.decode_logprob(self, A, pi, method=method) + self._shift
+
+    def decode_runs(self, A, pi, par0=None, par1=None, method='viterbi', stats=False):
+        self.emissions(par0, par1)
+        return Engine.decode_runs(self, A, pi, method=method, stats=stats)
+
+    def sample_paths_dev(self, A, pi, par0, par1, stats_dev, u=None, seed=0, want_paths=False):
+        self.emissions(par0, par1)
+        return Engine.sample_paths_dev(self, A, pi, None, None, stats_dev, u=u, seed=seed, want_paths=want_paths)
+
+    def sample_paths(self, A, pi, par0=None, par1=None, u=None, seed=0, want_paths=True):
+        self.emissions(par0, par1)
+        return Engine.sample_paths(self, A, pi, u=u, seed=seed, want_paths=want_paths)
 
 
 def stack_models(kind, nstates, nsymbols, models):

@@ -25,6 +25,11 @@ def _default_engine_factory(device):
     return Engine(device)
 
 
+def _mvn_engine_factory(device):
+    from ..engine import MvnEngine
+    return MvnEngine(device)
+
+
 def default_device(comm):
     """One process per GPU: rank r drives GPU r (modulo the GPUs visible to this process).
     Counting devices does not initialise the GPU."""
@@ -61,7 +66,7 @@ def _load_observations(engine, kind, given, copied, mine, comm, nstates, nsymbol
     the views are cut on the GPU (bhmm_ctx_set_observations_lagged) -- single process only, a
     sharded run uploads each rank's own pieces."""
     views = getattr(given, 'views', None)
-    if (views is not None and not comm.active and hasattr(engine, 'set_observations_lagged')
+    if (views is not None and not comm.active and kind != 'mvgaussian' and hasattr(engine, 'set_observations_lagged')
             and len(views) == len(copied) and _views_intact(given)):
         engine.set_observations_lagged(kind, given.base, given.lag, views, nstates,
                                        nsymbols=nsymbols)
@@ -152,7 +157,15 @@ class MaximumLikelihoodEstimator(object):
             device = default_device(self._comm)
         self._device = device
         self._comm.bind_device(device)       # collectives run on the engine's GPU, not on "current"
-        factory = engine_factory or _default_engine_factory
+        if self._output == 'mvgaussian':
+            # multivariate gaussian emissions: single process, fp64 E-steps
+            if process_group is not None:
+                raise NotImplementedError('multivariate gaussian emissions do not run over a process_group yet')
+            if estep_precision != 'float64':
+                raise NotImplementedError("multivariate gaussian E-steps run in float64 (estep_precision=%r)"
+                                          % (estep_precision,))
+        factory = engine_factory or (_mvn_engine_factory if self._output == 'mvgaussian'
+                                     else _default_engine_factory)
         self._engine = factory(device)
         M = self._hmm.output_model.nsymbols if self._output == 'discrete' else 0
         self._nsymbols = M
@@ -311,7 +324,10 @@ class MaximumLikelihoodEstimator(object):
         # kept for hidden_state_probabilities: gamma is that of the model BEFORE the following M-step
         self._estep_model = tuple(None if x is None else np.array(x, dtype=np.float64) for x in (A, pi, par0, par1))
         kw = {'single': True} if single else {}
-        if not comm.active and hasattr(eng, 'estep_fetch_packed'):
+        if self._output == 'mvgaussian':
+            # emission rows, ONE pass of the recursions that leaves gamma on the device, the moments from it
+            res = eng.estep(A, pi, par0, par1)
+        elif not comm.active and hasattr(eng, 'estep_fetch_packed'):
             # (the per-trajectory log-likelihoods stay on the device: the EM loop needs their sum,
             # which is packed[0]; with 1e6 short trajectories they would be 8 MB per iteration)
             eng.estep_launch(A, pi, par0, par1, store_gamma=self._store_gamma, **kw)
@@ -375,15 +391,22 @@ class MaximumLikelihoodEstimator(object):
         transition matrix, like the reference's `self._hmm.is_reversible`."""
         om = self._hmm.output_model
         par0, par1 = om.parameters()
+        mvn = self._output == 'mvgaussian'
         if self._mstep is None:
             from ._native import MStep
-            self._mstep = MStep(self._output, self._nstates, self._nsymbols)
+            # (multivariate gaussian: transition matrix and pi from the explicit kind's statistics, which lead the
+            # packed vector; the emission update is the output model's, from the moment block)
+            self._mstep = MStep('explicit' if mvn else self._output, self._nstates, self._nsymbols)
         fixed = (self._fixed_stationary_distribution if self._stationary
                  else self._fixed_initial_distribution)
-        T, pi, new0, new1 = self._mstep(res.packed, self._hmm.transition_matrix, par0, par1, None,
+        T, pi, new0, new1 = self._mstep(res.packed, self._hmm.transition_matrix, None if mvn else par0,
+                                        None if mvn else par1, None,
                                         self._stationary, fixed, maxiter, 1e-12, 1e-16)
         self._hmm.update(pi, T)
-        om.set_parameters(new0, new1)
+        if mvn:
+            om.estimate_from_packed(res.moments)
+        else:
+            om.set_parameters(new0, new1)
 
     def _update_model_numpy(self, res, maxiter=10000000):
         """The same M-step in numpy (_tmatrix.py): the restatement bhmm_mstep is tested against."""
@@ -405,6 +428,8 @@ class MaximumLikelihoodEstimator(object):
         om = self._hmm.output_model
         if self._output == 'gaussian':
             om.estimate_from_statistics(res.state_counts, res.sum_gd, res.sum_gdd)
+        elif self._output == 'mvgaussian':
+            om.estimate_from_statistics(res.S0, res.S1, res.S2)
         else:
             om.estimate_from_statistics(res.symbol_counts)
 

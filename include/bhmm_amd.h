@@ -94,6 +94,15 @@ int bhmm_pobs_gaussian(double *pobs, const double *obs, const double *mu, const 
 int bhmm_update_pout(double *pout, const int32_t *obs, const double *weights, int64_t T, int N,
                      int M);
 
+/* Multivariate gaussian log-densities, beside bhmm_pobs_gaussian: logp[t*N + i] =
+ * log N(x_t; mu_i, Sigma_i) for X[T*D] row-major, means[N*D] and covs as below, formed by the kernel of
+ * bhmm_mvn_emissions (centred, whitened with the inverse Cholesky factor, fp64).  Host pointers, synchronous. */
+#define BHMM_COV_FULL 0  /* covs[N*D*D]: symmetric positive definite matrices, row-major */
+#define BHMM_COV_DIAG 1  /* covs[N*D]: variances                                          */
+#define BHMM_MVN_MAX_D 64
+int bhmm_logpdf_mvn(double *logp, const double *X, int64_t T, int D, int N, const double *means,
+                    const double *covs, int cov_type);
+
 /* ------------------------------------------------------------------------------------
  * (2) batched device-resident context
  * ---------------------------------------------------------------------------------- */
@@ -461,6 +470,40 @@ int bhmm_path_logprob(bhmm_ctx *ctx, const void *paths, int path_u8, int paths_o
 int bhmm_decode_logprob(bhmm_ctx *ctx, const double *A, const double *pi, const double *par0, const double *par1,
                         int method, double *logp);
 
+/* Multivariate gaussian emissions: D-dimensional observations, 1 <= D <= BHMM_MVN_MAX_D, one
+ * mean vector and one covariance (full or diagonal) per state.  The recursions run on explicit emission rows; these
+ * calls are the two passes over the data around them.
+ *   bhmm_ctx_set_observations_mvn keeps X[total*D] (row-major, trajectory-concatenated; offsets, K, nstates, chunk and
+ *     obs_on_device as for bhmm_ctx_set_observations) on the device in the context, in buffers of its own that the
+ *     re-loads below do not touch and bhmm_ctx_destroy frees.  No model call works before the first
+ *     bhmm_mvn_emissions.  A later bhmm_ctx_set_observations[_lagged] by the caller ends the multivariate set.
+ *   bhmm_mvn_emissions validates means[N*D] and covs (BHMM_COV_FULL: [N*D*D], BHMM_COV_DIAG: [N*D]; non-finite or
+ *     asymmetric: BHMM_ERR_INVALID, not positive definite: BHMM_ERR_SIGMA), forms for every step t and state i
+ *       l_ti = -|L_i^-1 (x_t - mu_i)|^2 / 2 - sum_d log L_i[d,d] - D log(2 pi) / 2     (L_i L_i^T = Sigma_i)
+ *     in fp64 -- the mean is subtracted first, then the difference is whitened -- and m_t = max_i l_ti, writes the
+ *     rows exp(l_ti - m_t) (every finite row has maximum exactly 1.0), sums shift_k = sum_t m_t per trajectory in a
+ *     fixed order, and loads the rows as the context's BHMM_EMIT_EXPLICIT observations through
+ *     bhmm_ctx_set_observations with obs_on_device = 1.  After it every context call works unchanged with
+ *     par0 = par1 = NULL; the true log-likelihood of trajectory k is the context's on the scaled rows plus shift_k,
+ *     and the filter's increment of step t the context's plus m_t.  A NaN in x_t makes its row, m_t and shift_k NaN.
+ *   bhmm_mvn_fetch_scale copies shift_k[K] and, unless NULL, m_t[total] of the last bhmm_mvn_emissions to the host.
+ *   bhmm_mvn_moments: gamma_dev is a DEVICE buffer of total*N doubles, trajectory-major -- what
+ *     bhmm_posterior_marginals leaves with BHMM_MARG_DEVICE -- means[N*D] the means the moments are taken about.
+ *     out (host), per state i: S0 = sum_t g_ti | S1[D] = sum_t g_ti (x_t - mu_i) | S2 = sum_t g_ti (x_t - mu_i)
+ *     (x_t - mu_i)^T, its lower triangle row-major (D (D + 1) / 2, BHMM_COV_FULL) or its diagonal (D,
+ *     BHMM_COV_DIAG): N * (1 + D + D (D + 1) / 2) or N * (1 + 2 D) doubles.  One partial per workgroup in a fixed
+ *     tree order, a second launch adds the partials in ascending order; no floating-point atomics: bitwise the same
+ *     from call to call.  Synchronous.
+ * Read-only options: mvn_rows_ms (device time of the last rows and shift kernels), mvn_reload_ms (host time of the
+ * explicit re-load that followed), mvn_moments_ms (device time of the last two moment kernels). */
+int bhmm_ctx_set_observations_mvn(bhmm_ctx *ctx, const double *X, const int64_t *offsets, int K, int D,
+                                  int nstates, int chunk, int obs_on_device);
+int bhmm_mvn_emissions(bhmm_ctx *ctx, const double *means, const double *covs, int cov_type);
+int bhmm_mvn_fetch_scale(bhmm_ctx *ctx, double *shift_k, double *m_t);
+/* the scaled rows of the last bhmm_mvn_emissions, rows[total*N] (host; tests and diagnostics) */
+int bhmm_mvn_fetch_rows(bhmm_ctx *ctx, double *rows);
+int bhmm_mvn_moments(bhmm_ctx *ctx, const double *gamma_dev, const double *means, int cov_type, double *out);
+
 /* Gibbs hidden-path step (bayesian_sampling.py:283-331): forward pass + backward sampling
  * of every trajectory.  Uniforms come either from u (host, concatenated like obs; u[t]
  * used at step t) or, when u == NULL, from a counter-based generator seeded with `seed`.
@@ -660,6 +703,18 @@ int bhmm_gibbs_parameters(int kind, int n, int M, const double *path_stats, cons
                           const double *prior_n0, const double *prior_B, int reversible,
                           int stationary, int64_t nsteps, uint64_t seed, uint64_t sweep, double *T,
                           double *p0, double *par0, double *par1, int32_t *info);
+
+/* Multivariate gaussian emissions, host side.  bhmm_host_mvn_prepare: what
+ * bhmm_mvn_emissions hands its kernel -- chol: the Cholesky factors L_i ([N*D*D] lower triangular, zeros above, or
+ * [N*D] standard deviations), winv: their inverses as packed for the kernel ([N*D(D+1)/2] lower triangle row-major,
+ * or [N*D]), cst[N]: -sum_d log L_i[d,d] - D log(2 pi) / 2; formed in long double, rounded once; any output may be
+ * NULL.  BHMM_ERR_INVALID for a non-finite or asymmetric covariance, BHMM_ERR_SIGMA for one that is not positive
+ * definite.  bhmm_host_mvn_mstep: from the moments of bhmm_mvn_moments about means_old, mu' = mu + S1 / S0 and
+ * Sigma' = S2 / S0 - delta delta^T + min_covar I (covs_new in the layout of cov_type); BHMM_ERR_SIGMA if a result is
+ * not positive definite. */
+int bhmm_host_mvn_prepare(int N, int D, int cov_type, const double *covs, double *chol, double *winv, double *cst);
+int bhmm_host_mvn_mstep(int N, int D, int cov_type, const double *moments, const double *means_old,
+                        double min_covar, double *means_new, double *covs_new);
 
 /* building blocks of the two calls above, exported for the parity / property tests:
  * component label per state (sets numbered by decreasing size, _tmatrix_disconnected.py:28-43) */
