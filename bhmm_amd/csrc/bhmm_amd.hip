@@ -101,7 +101,12 @@ static int lds_symbols(const bhmm_ctx *c) { return c->bt_global ? 0 : c->M; }
 static int64_t ci_records(const bhmm_ctx *c) { return (int64_t)(c->Gp / 64) * c->Lmax; }
 // the unconditional refills of the sweeps (estep_sweep.hpp) stay inside the guards of the buffers they read
 static_assert(SWEEP_REACH_BACK <= (int)bhmm_ctx::SWEEP_GUARD_BACK && SWEEP_REACH_FRONT <= (int)bhmm_ctx::SWEEP_GUARD_FRONT,
-              "a deeper prefetch needs wider guards around d_obs_ci, d_ws and d_ea (ctx.hpp)");
+              "a deeper prefetch needs wider guards around d_obs_ci, d_obs16, d_ws and d_ea (ctx.hpp)");
+// ... and the loops on the 16-bit copy move in whole blocks of OBS16_BLK steps: two blocks behind a chunk's last
+// record (forward), two before its first (backward quads)
+static_assert(SWEEP_REACH_BACK % OBS16_BLK == 0 && SWEEP_REACH_FRONT % OBS16_BLK == 0 && SWEEP_REACH_BACK >= 2 * OBS16_BLK &&
+                  SWEEP_REACH_FRONT >= 2 * OBS16_BLK,
+              "the guards of d_obs16 are whole blocks and cover two of them on either side");
 
 int replan_coarse(bhmm_ctx *c, bool half = false, int chunk = 0); // (defined with bhmm_ctx_set_observations)
 int replan_for_warmup(bhmm_ctx *c);
@@ -162,9 +167,11 @@ struct Runner {
                                     (size_t)DISC_GLOBAL_TABLES * c->M * N * sizeof(double), c->stream));
         if constexpr (MODE == MODE_ESTEP) {
             // (every E-step kernel takes the same arguments)
+            const void *o16 = nullptr; // (set for the split launches below when they read the 16-bit observations)
+            c->last.obs16_used = false;
             auto estep = [&](auto kern, int grid, const Model<N> &mm, size_t smem, double *gam, const Carry &cy) {
                 return launch(kern, dim3(grid), dim3(32 * N), smem, c->stream, mm, ch, c->d_obs_ci.p, c->d_obs_rm.p,
-                              c->d_offsets.p, c->d_Bt.p, c->d_aentry.p, c->d_bexit.p, c->d_aexit.p, c->d_bentry.p,
+                              o16, c->d_offsets.p, c->d_Bt.p, c->d_aentry.p, c->d_bexit.p, c->d_aexit.p, c->d_bentry.p,
                               c->ds.spec_W, c->d_ws.p, gam, c->d_logLc.p, c->d_gamma0.p, c->d_partials.p,
                               c->d_dpartials.p, flag_words, c->d_ea.p, cy);
             };
@@ -189,6 +196,10 @@ struct Runner {
                     const size_t sm1 = KIND == EMIT_DISC ? smem_fwdbwd<N, KIND>(lds_symbols(c), 0) : sm;
                     // boundary vectors carried between E-steps (decided by estep_kind): P1 starts its
                     // warm-ups from them, P2 captures beta for the next E-step
+                    if (KIND == EMIT_DISC && c->obs16 && c->opt.obs16_enabled && !c->bt_global) {
+                        o16 = c->d_obs16.p;
+                        c->last.obs16_used = true;
+                    }
                     Carry c1, c2;
                     if (c->ds.carry_use > 0) {
                         c1.a_in = c->d_carry_a.p;
@@ -664,7 +675,7 @@ struct Runner {
         if (rc)
             return rc;
         BHMM_HIP(launch(k_estep_light<N, KIND, true, false, CAREFUL, PH_FWDROWS>, dim3(c->Gp / 64), dim3(32 * N), sm,
-                        c->stream, m, ch, c->d_obs_ci.p, c->d_obs_rm.p, c->d_offsets.p, c->d_Bt.p, c->d_aentry.p,
+                        c->stream, m, ch, c->d_obs_ci.p, c->d_obs_rm.p, nullptr, c->d_offsets.p, c->d_Bt.p, c->d_aentry.p,
                         c->d_bexit.p, c->d_aexit.p, c->d_bentry.p, c->ds.spec_W, c->d_ws.p,
                         reinterpret_cast<double *>(c->d_ws32.p), c->d_logLc.p, c->d_gamma0.p, c->d_partials.p,
                         c->d_dpartials.p, c->d_specres.p, c->d_ea.p, Carry()));
@@ -1053,9 +1064,10 @@ static int pack_observations(bhmm_ctx *c, const char *src_dev)
     const size_t ci_elems = (size_t)ci_records(c) * 64;
     const Chunks ch = chunks_of(c);
     const int nblk = c->Gp / BLOCK;
-    if ((rc = c->d_obsnan.ensure(1)))
+    if ((rc = c->d_obsnan.ensure(2))) // [1]: a discrete symbol outside [0, M) (k_pack_obs16)
         return rc;
-    BHMM_HIP(hipMemsetAsync(c->d_obsnan.p, 0, sizeof(int32_t), c->stream));
+    BHMM_HIP(hipMemsetAsync(c->d_obsnan.p, 0, 2 * sizeof(int32_t), c->stream));
+    c->obs16 = false;
     if (kind == BHMM_EMIT_GAUSSIAN) {
         if ((rc = c->d_obs_ci.ensure(ci_elems * sizeof(double))))
             return rc;
@@ -1068,6 +1080,15 @@ static int pack_observations(bhmm_ctx *c, const char *src_dev)
         BHMM_HIP(launch(k_pack_scalar<int32_t>, dim3(nblk), dim3(BLOCK), 0, c->stream, ch,
                         reinterpret_cast<const int32_t *>(src_dev), reinterpret_cast<int32_t *>(c->d_obs_ci.p),
                         c->d_obsnan.p));
+        // the second, 16-bit copy (2 bytes per step more) for the main loops of the split E-step: B^T in LDS and
+        // every row offset within 16 bits; the int32 copy above stays for everything else
+        if (c->opt.obs16_enabled && !c->bt_global && obs16_fits(c->N, c->M)) {
+            if ((rc = c->d_obs16.ensure((size_t)(c->Gp / 64) * obs16_blocks(c->Lmax) * 64 * OBS16_BLK)))
+                return rc;
+            BHMM_HIP(launch(k_pack_obs16, dim3(nblk), dim3(BLOCK), 0, c->stream, ch,
+                            reinterpret_cast<const int32_t *>(src_dev), c->d_obs16.p, c->N, c->M, c->d_obsnan.p + 1));
+            c->obs16 = true; // (until pack_settle has looked at the symbols)
+        }
     } else {
         if ((rc = c->d_obs_ci.ensure(ci_elems * sizeof(double) * c->N)))
             return rc;
@@ -1075,6 +1096,20 @@ static int pack_observations(bhmm_ctx *c, const char *src_dev)
         if (rc)
             return rc;
     }
+    return BHMM_OK;
+}
+
+// after pack_observations, once the stream has been waited for: a symbol outside [0, M) keeps the context off the
+// 16-bit copy (it holds such a symbol modulo 2^16, the int32 copy as it is)
+static int pack_settle(bhmm_ctx *c, int32_t *has_nan)
+{
+    int32_t words[2] = {0, 0};
+    BHMM_HIP(hipMemcpyAsync(words, c->d_obsnan.p, sizeof(words), hipMemcpyDeviceToHost, c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream));
+    if (words[1])
+        c->obs16 = false;
+    if (has_nan)
+        *has_nan = words[0];
     return BHMM_OK;
 }
 
@@ -1102,9 +1137,8 @@ int bhmm::replan_coarse(bhmm_ctx *c, bool half, int chunk)
     BHMM_HIP(hipStreamSynchronize(c->stream));
     if ((rc = plan_chunks(c, chunk, false, half)) || (rc = alloc_work(c)))
         return rc;
-    if ((rc = pack_observations(c, c->d_obs_rm.p)))
+    if ((rc = pack_observations(c, c->d_obs_rm.p)) || (rc = pack_settle(c, nullptr)))
         return rc;
-    BHMM_HIP(hipStreamSynchronize(c->stream));
     // rows stored under the old plan are gone; an E-step in flight that stores gamma (this runs
     // inside its first call) gets rows of the new plan's size -- bhmm_estep sets gamma_valid
     // when that E-step has been enqueued
@@ -1177,6 +1211,7 @@ int bhmm_ctx_set_observations(bhmm_ctx *c, int kind, const void *obs, const int6
     new_observation_set(c);
     // discrete alphabets whose emission / count tables do not fit the LDS of the sweep kernels
     // (M above ~1200 at 8 states) keep them in global memory instead (estep_sweep.hpp, BtSrc)
+    c->obs16 = false;
     c->bt_global = kind == BHMM_EMIT_DISCRETE && !c->wide && !c->gen &&
                    smem_fwdbwd<8, EMIT_DISC>(c->M) > (size_t)150 * 1024;
     int rc;
@@ -1234,9 +1269,8 @@ int bhmm_ctx_set_observations(bhmm_ctx *c, int kind, const void *obs, const int6
         BHMM_HIP(hipMemcpyAsync(c->d_obs_rm.p, src_dev, bytes, hipMemcpyDeviceToDevice, c->stream));
     }
     int32_t has_nan = 0;
-    BHMM_HIP(hipMemcpyAsync(&has_nan, c->d_obsnan.p, sizeof(int32_t), hipMemcpyDeviceToHost,
-                            c->stream));
-    BHMM_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = pack_settle(c, &has_nan)))
+        return rc;
     if (kind == BHMM_EMIT_GAUSSIAN && has_nan)
         c->ds.careful = true; // gauss_pdf(): the branch-free kernels take NaN for a perfect hit
     return BHMM_OK;
@@ -1382,6 +1416,11 @@ int bhmm_ctx_set_option(bhmm_ctx *c, const char *name, double value)
     } else if (n == "carry") { // warm-ups from the previous E-step's boundary vectors (EM sequences)
         c->opt.carry_enabled = value != 0.0;
         c->ds.carry_valid = false;
+    } else if (n == "obs16") {
+        // discrete kind, up to 8 states: 0 keeps the split E-step on the int32 observations (same statistics, bit
+        // for bit; tests).  Takes effect at the next E-step; switching it back on needs new observations if they
+        // were loaded while it was off (the 16-bit copy is made with them).
+        c->opt.obs16_enabled = value != 0.0;
     } else if (n == "carry_kappa") { // (tests: the sensitivity bound that sizes the carried warm-ups)
         c->ds.carry_kappa = value;
     } else if (n == "spec_tol") {
@@ -1600,6 +1639,10 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->last.draw_alpha_dev;
     else if (n == "carry")
         *value = c->opt.carry_enabled ? 1.0 : 0.0;
+    else if (n == "obs16")
+        *value = c->opt.obs16_enabled ? 1.0 : 0.0;
+    else if (n == "obs16_used") // the sweeps of the last E-step read the 16-bit copy of the observations
+        *value = c->last.obs16_used ? 1.0 : 0.0;
     else if (n == "carry_W") // warm-up steps of the last E-step's carried starts (0: full warm-ups)
         *value = c->last.carry_last_W;
     else if (n == "carry_cap") // where the last E-step's backward sweep was split for the capture (0: not split)
@@ -1894,6 +1937,7 @@ int bhmm_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par
     // BHMM_FLAG_SINGLE: the fp32 kernels where they apply and verify (estep_f32.hip), else this fp64 path
     bool single_done = false;
     c->last.f32_used = false;
+    c->last.obs16_used = false; // (set by the split launches of the discrete kind, Runner::fwdbwd)
     if ((flags & BHMM_FLAG_SINGLE) && (rc = estep_f32(c, A, pi, par0, par1, sd, flags, &single_done)))
         return rc;
     if (flags & BHMM_FLAG_SINGLE) {

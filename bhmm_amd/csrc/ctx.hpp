@@ -111,6 +111,7 @@ struct bhmm_ctx {
         bool spec_W_fixed = false;       // warm-up given by the caller (option / BHMM_AMD_SPEC_W): never probed
         double spec_tol = 1e-11;         // N <= 8: tolerance of the boundary check (option spec_tol)
         bool carry_enabled = true;       // option "carry" / BHMM_AMD_CARRY=0
+        bool obs16_enabled = true;       // option "obs16": 0 keeps the split E-step of the discrete kind on the int32 observations
         bool draw_watch = true;          // option "draw_watch": record and verify draws near the alpha rows' deviation
         double draw_watch_tol = 0.0;     // option "draw_watch_tol" (tests): watch tolerance instead of 64 x deviation
         bool draw_test_redo = false;     // option "draw_test_redo" (tests): treat every event as a decision that did not stand
@@ -163,6 +164,7 @@ struct bhmm_ctx {
     int N = 0;    // padded (2, 4, 8)
     int M = 0;    // symbols
     bool bt_global = false; // discrete alphabet too large for the LDS tables (global / L2 instead)
+    bool obs16 = false;     // discrete, N <= 8: d_obs16 holds the 16-bit copy of these observations under the current plan
     int K = 0;    // trajectories
     int64_t total = 0;
     int L = 0, Lmax = 0, G = 0, Gp = 0;
@@ -268,6 +270,7 @@ struct bhmm_ctx {
         int spec_fail = 0, spec_ok = 0;
         float spec_last_dev = 0.f;
         int carry_ok = 0, carry_fail = 0, carry_last_W = 0;
+        bool obs16_used = false;         // the sweeps of the last E-step read the 16-bit observations (option obs16_used)
         bool draw_fwd_segmented = false; // the last sampler's alpha rows came from the time-segmented forward pass
         bool smp_segmented = false;      // the last sample_paths call ran over time segments
         int smp_seg_mismatch = 0, smp_seg_rounds = 0;
@@ -361,6 +364,9 @@ struct bhmm_ctx {
     static constexpr size_t SWEEP_GUARD_FRONT = 8, SWEEP_GUARD_BACK = 8, SWEEP_REC_DOUBLES = 8 * 64;
     bhmm::DevBuf<char> d_obs_ci{SWEEP_GUARD_FRONT * SWEEP_REC_DOUBLES * sizeof(double),
                                 SWEEP_GUARD_BACK * SWEEP_REC_DOUBLES * sizeof(double)}; // CI observations (double / int32 / N doubles)
+    // the discrete kind's 16-bit copy for the main loops of the split E-step (k_pack_obs16): 64 elements per step
+    // of a record group, guards in elements of this type
+    bhmm::DevBuf<uint16_t> d_obs16{SWEEP_GUARD_FRONT * 64, SWEEP_GUARD_BACK * 64};
     bhmm::DevBuf<char> d_obs_rm;     // trajectory-major observations (Viterbi / sampling)
     bhmm::DevBuf<double> d_Bt;       // [M][N] transposed emission matrix
     bhmm::DevBuf<double> d_M;        // chunk transfer matrices

@@ -1452,6 +1452,39 @@ __global__ void k_pack_scalar(const Chunks ch, const T *src, T *dst_ci, int32_t 
         *has_nan = 1;
 }
 
+// Second copy of discrete observations for the main loops of the split E-step (estep_sweep.hpp, Obs16Cursor): two
+// bytes per step, and the value is not the symbol but what the sweeps make of it, the byte offset sym * N * 8 of
+// its row in B^T and in the count tables (it must fit 16 bits: obs16_fits).  A chunk's steps 4b .. 4b+3 form one
+// 8-byte block per lane, blocks are laid out like CI records: [record group][block][lane][4], OBS16_BLK steps per
+// block and obs16_blocks(Lmax) blocks per record group, so that one dwordx2 load brings four steps of a lane and
+// the 64 lanes of a wavefront read 512 consecutive bytes.  Words of a chunk's last block behind its last step are
+// zero.  `bad` is set if a symbol lies outside [0, M): the int32 copy hands such a symbol to the kernels as it is,
+// which 16 bits cannot, so the context then stays on the int32 copy alone.
+constexpr int OBS16_BLK = 4;
+__host__ __device__ constexpr int64_t obs16_blocks(int Lmax) { return ((int64_t)Lmax + OBS16_BLK - 1) / OBS16_BLK; }
+__host__ __device__ constexpr bool obs16_fits(int N, int M) { return (int64_t)M * N * 8 <= 65536; }
+[[maybe_unused]] static __global__ void k_pack_obs16(const Chunks ch, const int32_t *src, uint16_t *dst16, int N, int M, int32_t *bad)
+{
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int len = ch.len[g];
+    const int64_t off = ch.goff[g];
+    uint2 *dst = reinterpret_cast<uint2 *>(dst16) + (g >> 6) * obs16_blocks(ch.Lmax) * 64 + lane;
+    bool out = false;
+    for (int s0 = 0; s0 < len; s0 += OBS16_BLK) {
+        uint32_t w[OBS16_BLK];
+#pragma unroll
+        for (int j = 0; j < OBS16_BLK; ++j) {
+            const int32_t v = s0 + j < len ? src[off + s0 + j] : 0;
+            out |= v < 0 || v >= M;
+            w[j] = ((uint32_t)v * (uint32_t)(N * 8)) & 0xffffu;
+        }
+        dst[(int64_t)(s0 / OBS16_BLK) * 64] = make_uint2(w[0] | (w[1] << 16), w[2] | (w[3] << 16));
+    }
+    if (out)
+        *bad = 1;
+}
+
 // rows of nreal doubles (row-major) -> CI records of N doubles (zero padded)
 template <int N>
 __global__ void k_pack_rows(const Chunks ch, const double *src, int nreal, double *dst_ci)

@@ -197,6 +197,32 @@ struct ObsCursor {
     __device__ __forceinline__ void move(int drec) { p += drec * STRIDE; }
 };
 
+// A discrete observation as the 16-bit copy holds it (k_pack_obs16, estep_kernels.hpp): the byte offset sym * N * 8
+// of the symbol's row in B^T and in the count tables.
+struct ObsOff {
+    uint32_t off;
+};
+// Per-lane cursor into that copy, in blocks of OBS16_BLK = 4 steps (one dwordx2 load each; block b of a chunk holds
+// its steps 4b .. 4b+3).  word<J> takes step 4b+J out of a loaded block as `w & 0xffff` or `w >> 16`: added to a
+// table's base it is one v_add_u32_sdwa with a WORD_0 / WORD_1 operand, where the int32 copy takes one
+// v_lshl_add_u32.
+struct Obs16Cursor {
+    const uint2 *p;
+    __device__ __forceinline__ Obs16Cursor(const void *obs16, int64_t g, int Lmax, int blk, int cl)
+    {
+        p = static_cast<const uint2 *>(obs16) + ((g >> 6) * obs16_blocks(Lmax) + blk) * 64 + cl;
+    }
+    __device__ __forceinline__ uint2 blk(int dblk) const { return p[dblk * 64]; }
+    __device__ __forceinline__ void move(int dblk) { p += dblk * 64; }
+    template <int J>
+    __device__ __forceinline__ static ObsOff word(const uint2 &b)
+    {
+        static_assert(J >= 0 && J < OBS16_BLK, "four steps per block");
+        const uint32_t w = J < 2 ? b.x : b.y;
+        return ObsOff{(J & 1) ? w >> 16 : w & 0xffffu};
+    }
+};
+
 // emission probabilities of my two states WITHOUT the outlier rule; d = o - mu (gaussian)
 // where the transposed emission matrix B^T [M][N] of the discrete model lives: staged in LDS, or
 // -- alphabets too large for that -- in global memory (two pointers, so that the LDS accesses
@@ -214,12 +240,21 @@ struct BtSrc {
 // returned times 2^900; the return value is that exponent (else 0).  gamma and xi do not see the
 // factor, the forward sweep takes it off its exponent count.  An all-zero row is left to the
 // outlier rule.
-template <int N, int KIND, bool NANSAFE>
+template <int N, int KIND, bool NANSAFE, class IN>
 __device__ __forceinline__ int emit_raw(const Model<N> &m, unsigned long long gmask, int nreal,
-                                        const ObsIn &in, const BtSrc &Bt, int q,
+                                        const IN &in, const BtSrc &Bt, int q,
                                         const EmisPair &em, double (&p)[2], double (&d)[2])
 {
-    if constexpr (KIND == EMIT_GAUSS) {
+    if constexpr (std::is_same<IN, ObsOff>::value) {
+        // (the branch-free discrete main loops on the 16-bit copy: B^T in LDS, row at the stored byte offset)
+        static_assert(KIND == EMIT_DISC && !NANSAFE, "byte offsets: discrete kind, branch-free sweeps");
+        const double2 x =
+            *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(Bt.lds + 2 * q) + in.off);
+        p[0] = x.x;
+        p[1] = x.y;
+        d[0] = d[1] = 0.0;
+        return 0;
+    } else if constexpr (KIND == EMIT_GAUSS) {
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
             d[b] = in.o - em.mu[b];
@@ -313,8 +348,8 @@ __device__ __forceinline__ bool small_hi(int hm) { return hm < ((1023 - 400) << 
 //   depend on the schedule) and records the smallest maximum seen at those points (hmin); the
 //   kernel reports chunks where that fell below 2^-400 and the host repeats the E-step with the
 //   CAREFUL instantiation.
-template <int N, int KIND, bool CAREFUL, bool SCALE>
-__device__ __forceinline__ int scaled_emit(const ObsIn &in, int q, int nreal,
+template <int N, int KIND, bool CAREFUL, bool SCALE, class IN>
+__device__ __forceinline__ int scaled_emit(const IN &in, int q, int nreal,
                                            unsigned long long gmask, const double (&s)[2],
                                            double (&p)[2], double (&a)[2], int &hmin)
 {
@@ -604,9 +639,10 @@ struct Carry {
 };
 
 template <int N, int KIND, bool SPEC, bool GAMMA, bool CAREFUL, int PHASE, bool BIGM = false,
-          bool TABSG = false>
+          bool TABSG = false, bool OBS16 = false>
 __device__ __forceinline__ void estep_body(
     const Model<N> &m, const Chunks &ch, const void *obs_ci, const void *obs_rm,
+    const void *obs16,     // OBS16: the 16-bit copy of discrete observations (k_pack_obs16), read by the main loops
     const int64_t *toff,   // [K+1] trajectory offsets (time steps)
     const double *Bt_g, double *alpha_entry, double *beta_exit,
     double *a_exit,        // SPEC: [G][N] alpha at each chunk's last step (any scale)
@@ -633,6 +669,10 @@ __device__ __forceinline__ void estep_body(
     // the same gamma), taken once in the epilogue instead of two additions per step and lane
     static_assert(!TABSG || (KIND == EMIT_DISC && PHASE == PH_P2 && !CAREFUL && !BIGM),
                   "only the branch-free backward launch of the discrete kind with LDS tables");
+    // OBS16: the main loops of the split launches read pre-scaled 16-bit observations (Obs16Cursor); the single
+    // steps, warm-ups and step 0 stay on the int32 copies
+    static_assert(!OBS16 || (KIND == EMIT_DISC && (PHASE == PH_P1 || PHASE == PH_P2) && !CAREFUL && !BIGM),
+                  "only the branch-free split launches of the discrete kind with LDS tables");
     // PH_P1: workgroup b and b + gridDim/2 share record group b (forward / backward warm-up)
     const int bidx = PHASE == PH_P1 ? (int)(blockIdx.x % (gridDim.x / 2)) : (int)blockIdx.x;
     const bool role_f = PHASE != PH_P1 || blockIdx.x < gridDim.x / 2;
@@ -829,7 +869,7 @@ __device__ __forceinline__ void estep_body(
             // even steps are, plus the last rows of the chunk that the single steps of the
             // backward sweep read; the backward sweep rebuilds alpha_{s-1} from alpha_{s-2} and
             // the emission of step s-1, which it needs anyway.
-            auto fstep = [&](const ObsIn &in, double2 &out, auto sc) {
+            auto fstep = [&](const auto &in, double2 &out, auto sc) { // (in: ObsIn, or ObsOff in the OBS16 groups)
                 double p[2], d[2], sv[2], af[N];
                 gather(a, af);
                 sched_fence();
@@ -896,27 +936,48 @@ __device__ __forceinline__ void estep_body(
             const int tail = (len - s) % (2 * PF);
             int rem = len - s - tail;
             if (rem > 0) {
-                ObsIn x[PF], y[PF];
+                // a register set: the PF observations of one half group -- OBS16: one block of the 16-bit copy
+                // (the group base s is a multiple of ALIGN = 4 here, so a half group is exactly one block; po stays
+                // behind and is moved past the groups after the loop, for the single steps of the tail)
+                static_assert(!OBS16 || (PF == OBS16_BLK && ALIGN % OBS16_BLK == 0), "a half group is one block");
+                struct SetI { ObsIn v[PF]; };
+                using Set = typename std::conditional<OBS16, uint2, SetI>::type;
+                [[maybe_unused]] Obs16Cursor po16(OBS16 ? obs16 : nullptr, g, ch.Lmax, s / OBS16_BLK, cl);
+                [[maybe_unused]] const int nmain = rem;
+                // set <- the observations of the steps first .. first + PF - 1 after the group base
+                auto fill = [&](Set &set, int first, auto fenced) __attribute__((always_inline)) {
+                    if constexpr (OBS16) {
+                        set = po16.blk(first / PF);
+                        if constexpr (decltype(fenced)::value)
+                            sched_fence();
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < PF; ++j) {
+                            set.v[j] = po.at(first + j);
+                            if constexpr (decltype(fenced)::value)
+                                sched_fence();
+                        }
+                    }
+                };
+                auto obs_of = [&](const Set &set, auto j) __attribute__((always_inline)) {
+                    if constexpr (OBS16)
+                        return Obs16Cursor::word<decltype(j)::value>(set);
+                    else
+                        return set.v[decltype(j)::value];
+                };
+                Set x, y;
                 double2 ox[PF], oy[PF];
                 // (in the order of their use, each behind a fence: the wait counts of the loop hold on
                 // the way in as well, and the compiler, left alone, issues these loads last one first)
-#pragma unroll
-                for (int j = 0; j < PF; ++j) {
-                    x[j] = po.at(j);
-                    sched_fence();
-                }
-#pragma unroll
-                for (int j = 0; j < PF; ++j) {
-                    y[j] = po.at(PF + j);
-                    sched_fence();
-                }
+                fill(x, 0, std::true_type());
+                fill(y, PF, std::true_type());
                 // one group of 2 PF steps.  It stands twice: once in front of the loop and once as the
                 // loop body, so that the loop is entered with the same operations in flight as it is
                 // repeated with -- the wait counts of the loop body are then not bounded by a path into
                 // it on which no stores follow the loads of the x set
                 auto group = [&]() __attribute__((always_inline)) {
                     unrolled<PF>([&](auto j) {
-                        fstep(x[j], ox[j], sc_at<j>());
+                        fstep(obs_of(x, j), ox[j], sc_at<j>());
                         if constexpr (FWDONLY) {
                             pw32[j * RS32] = make_float2((float)ox[j].x, (float)ox[j].y);
                             if (j == 0 && (s % CKS) == 0)
@@ -927,11 +988,9 @@ __device__ __forceinline__ void estep_body(
                                 pe[j * 64] = eP;
                         }
                     });
-#pragma unroll
-                    for (int j = 0; j < PF; ++j)
-                        x[j] = po.at(2 * PF + j);
+                    fill(x, 2 * PF, std::false_type());
                     unrolled<PF>([&](auto j) {
-                        fstep(y[j], oy[j], sc_at<PF + j>());
+                        fstep(obs_of(y, j), oy[j], sc_at<PF + j>());
                         if constexpr (FWDONLY) {
                             pw32[(PF + j) * RS32] = make_float2((float)oy[j].x, (float)oy[j].y);
                         } else if constexpr ((PF + j) % CKS == 0) {
@@ -940,9 +999,7 @@ __device__ __forceinline__ void estep_body(
                                 pe[(PF + j) * 64] = eP;
                         }
                     });
-#pragma unroll
-                    for (int j = 0; j < PF; ++j)
-                        y[j] = po.at(3 * PF + j);
+                    fill(y, 3 * PF, std::false_type());
                     if constexpr (CKPT) {
                         // the backward sweep reads the last (len-1) % (2 CKS) + 1 rows directly: if
                         // the single steps below do not cover them, all rows of the last group are kept
@@ -956,7 +1013,10 @@ __device__ __forceinline__ void estep_body(
                             }
                         }
                     }
-                    po.move(2 * PF);
+                    if constexpr (OBS16)
+                        po16.move(2);
+                    else
+                        po.move(2 * PF);
                     pw += 2 * PF * RS;
                     pe += 2 * PF * 64;
                     if constexpr (FWDONLY) {
@@ -967,6 +1027,8 @@ __device__ __forceinline__ void estep_body(
                 group();
                 for (rem -= 2 * PF; rem > 0; rem -= 2 * PF)
                     group();
+                if constexpr (OBS16)
+                    po.move(nmain);
             }
             for (int i = tail; i > 0; --i) // step len - i
                 single(po, pw, ((len - i) % CKS) == 0);
@@ -1095,7 +1157,8 @@ __device__ __forceinline__ void estep_body(
         }
         // consume gamma_s: state counts, emission statistics, optional gamma row
         constexpr int RS = (N / 2) * 64; // double2 elements per CI record of N doubles
-        auto consume = [&](const ObsIn &in, const double (&d)[2], double2 *gdst) {
+        auto consume = [&](const auto &in, const double (&d)[2], double2 *gdst) { // (in: ObsIn, or ObsOff in the OBS16 quads)
+            using IN = typename std::decay<decltype(in)>::type;
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
                 if constexpr (!TABSG)
@@ -1105,7 +1168,9 @@ __device__ __forceinline__ void estep_body(
                     sd[b] += gd;
                     sdd[b] = fma(gd, d[b], sdd[b]);
                 }
-                if constexpr (KIND == EMIT_DISC) { // _discrete.c:22-30
+                if constexpr (std::is_same<IN, ObsOff>::value) { // (the same row of my table, by its byte offset)
+                    atomicAdd(reinterpret_cast<double *>(reinterpret_cast<char *>(dstat + 2 * q + b) + in.off), gam[b]);
+                } else if constexpr (KIND == EMIT_DISC) { // _discrete.c:22-30
                     if (big)
                         atomicAdd(&dstat_g[(int64_t)in.sym * N + 2 * q + b], gam[b]);
                     else
@@ -1271,8 +1336,8 @@ __device__ __forceinline__ void estep_body(
         // Four steps s .. s-3 from the stored row alpha_{s-4} (ESTEP_CK_OF == 4): the three rows in
         // between are rebuilt first, forwards (each needs the emission row of its own step, which
         // the backward steps below use again), then the four backward steps run as in bpair.
-        [[maybe_unused]] auto bquad = [&](const ObsIn &x3, const ObsIn &x2, const ObsIn &x1,
-                                          const ObsIn &x0, const double2 &alo, int ea, double2 *gdst,
+        [[maybe_unused]] auto bquad = [&](const auto &x3, const auto &x2, const auto &x1,
+                                          const auto &x0, const double2 &alo, int ea, double2 *gdst,
                                           auto sc3, auto sc2, auto sc1, auto sc0) {
             double p3[2], d3[2], p2[2], d2[2], p1[2], d1[2], p0[2], d0[2], sv[2];
             double a1[2], a2[2], a3[2], af[N], bf[N];
@@ -1330,7 +1395,7 @@ __device__ __forceinline__ void estep_body(
                 wcheck(a2);
                 wcheck(a3);
             }
-            auto back = [&](const ObsIn &in, const double (&p)[2], const double (&d)[2],
+            auto back = [&](const auto &in, const double (&p)[2], const double (&d)[2],
                             const double2 &apv, double2 *gd, auto sc) {
                 consume(in, d, gd);
                 const double bb[2] = {p[0] * b2[0], p[1] * b2[1]};
@@ -1365,6 +1430,29 @@ __device__ __forceinline__ void estep_body(
                 if (rem > 0) {
                     const int32_t *pea = ea_rows + (rec0 + rem) * 64 + cl;
                     ObsIn x[4], y[4];
+                    // OBS16: a quad s .. s-3 (s a multiple of 4) is word 0 of block s/4 and words 3, 2, 1 of the block
+                    // before it, whose word 0 is the top step of the NEXT quad: the sets are one block each (xb, yb),
+                    // and the top step of a quad is taken out of the other set's block (xt, yt) before that set is
+                    // refilled -- no block is loaded twice.  It is taken out as a value of its own (top16: one v_and_b32
+                    // where the steps read straight from a block take none): left to the compiler, the block's low
+                    // dword was carried instead, as a copy of the REFILLED register made at the loop's ends, and the
+                    // wait in front of that copy took in the loads just issued (vmcnt(0) at the top of the loop).
+                    // po16 points at block rem / 4.
+                    [[maybe_unused]] Obs16Cursor po16(OBS16 ? obs16 : nullptr, g, ch.Lmax, rem / OBS16_BLK, cl);
+                    [[maybe_unused]] uint2 xb = make_uint2(0, 0), yb = make_uint2(0, 0);
+                    [[maybe_unused]] ObsOff xt = {0}, yt = {0};
+                    [[maybe_unused]] auto top16 = [](const uint2 &blk) __attribute__((always_inline)) {
+                        uint32_t t = blk.x & 0xffffu;
+                        asm volatile("" : "+v"(t)); // (a register of its own, here)
+                        return ObsOff{t};
+                    };
+                    [[maybe_unused]] auto quad16 = [&](const ObsOff &top, const uint2 &blk, const double2 &alo, int ea,
+                                                       double2 *gdst) __attribute__((always_inline)) {
+                        if constexpr (OBS16)
+                            bquad(top, Obs16Cursor::word<3>(blk), Obs16Cursor::word<2>(blk),
+                                  Obs16Cursor::word<1>(blk), alo, ea, gdst, sc_at<0>(), sc_at<1>(), sc_at<2>(),
+                                  sc_at<3>());
+                    };
                     double2 xa, ya;
                     int xe = 0, ye = 0;
                     // both sets before the loop, in the order of their use and each load behind a
@@ -1376,10 +1464,17 @@ __device__ __forceinline__ void estep_body(
                     }
                     xa = pa[-4 * RS];
                     sched_fence();
-#pragma unroll
-                    for (int j = 3; j >= 0; --j) {
-                        x[j] = po.at(-j);
+                    if constexpr (OBS16) {
+                        xb = po16.blk(-1);
                         sched_fence();
+                        xt = Obs16Cursor::word<0>(po16.blk(0));
+                        sched_fence();
+                    } else {
+#pragma unroll
+                        for (int j = 3; j >= 0; --j) {
+                            x[j] = po.at(-j);
+                            sched_fence();
+                        }
                     }
                     if constexpr (EXPO) {
                         ye = pea[-8 * 64];
@@ -1387,10 +1482,15 @@ __device__ __forceinline__ void estep_body(
                     }
                     ya = pa[-8 * RS];
                     sched_fence();
-#pragma unroll
-                    for (int j = 3; j >= 0; --j) {
-                        y[j] = po.at(-4 - j);
+                    if constexpr (OBS16) {
+                        yb = po16.blk(-2);
                         sched_fence();
+                    } else {
+#pragma unroll
+                        for (int j = 3; j >= 0; --j) {
+                            y[j] = po.at(-4 - j);
+                            sched_fence();
+                        }
                     }
                     // (PH_P2 with a capture request: the same loop runs in two stretches, down to
                     // `cap` remaining steps and then to the end; in between b2 -- beta at my local
@@ -1402,8 +1502,11 @@ __device__ __forceinline__ void estep_body(
 #pragma clang loop unroll(disable)
                     for (int stretch = 0; stretch < 2; ++stretch) {
                     for (; rem > stop; rem -= 8) {
-                        bquad(x[0], x[1], x[2], x[3], xa, xe, pg, sc_at<0>(), sc_at<1>(), sc_at<2>(),
-                              sc_at<3>());
+                        if constexpr (OBS16)
+                            quad16(xt, xb, xa, xe, pg);
+                        else
+                            bquad(x[0], x[1], x[2], x[3], xa, xe, pg, sc_at<0>(), sc_at<1>(), sc_at<2>(),
+                                  sc_at<3>());
                         // Each set is refilled right after its last use, unconditionally.  A wavefront's
                         // vector-memory operations retire in issue order and a wait names how many may
                         // stay outstanding: with the refill of x inside `if (rem > 8)` the wait in front
@@ -1412,21 +1515,36 @@ __device__ __forceinline__ void estep_body(
                         // (profiles/prefetch_waits/isa_waits.md).  The last iteration reads up to eight
                         // records before the chunk's first one, which nothing consumes: the previous
                         // record group's, or the guards in front of the buffers (DevBuf::front).
+                        if constexpr (OBS16) {
+                            yt = top16(xb); // (step rem - 4)
+                            xb = po16.blk(-3);
+                        } else {
 #pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            x[j] = po.at(-8 - j);
+                            for (int j = 0; j < 4; ++j)
+                                x[j] = po.at(-8 - j);
+                        }
                         xa = pa[-12 * RS];
                         if constexpr (EXPO)
                             xe = pea[-12 * 64];
-                        bquad(y[0], y[1], y[2], y[3], ya, ye, pg - 4 * RS, sc_at<0>(), sc_at<1>(),
-                              sc_at<2>(), sc_at<3>());
+                        if constexpr (OBS16)
+                            quad16(yt, yb, ya, ye, pg - 4 * RS);
+                        else
+                            bquad(y[0], y[1], y[2], y[3], ya, ye, pg - 4 * RS, sc_at<0>(), sc_at<1>(),
+                                  sc_at<2>(), sc_at<3>());
+                        if constexpr (OBS16) {
+                            xt = top16(yb); // (step rem - 8)
+                            yb = po16.blk(-4);
+                            po16.move(-2);
+                        } else {
 #pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            y[j] = po.at(-12 - j);
+                            for (int j = 0; j < 4; ++j)
+                                y[j] = po.at(-12 - j);
+                        }
                         ya = pa[-16 * RS];
                         if constexpr (EXPO)
                             ye = pea[-16 * 64];
-                        po.move(-8);
+                        if constexpr (!OBS16)
+                            po.move(-8);
                         pa -= 8 * RS;
                         pg -= 8 * RS;
                         pea -= 8 * 64;
@@ -1662,13 +1780,13 @@ __device__ __forceinline__ void estep_body(
 }
 
 #define ESTEP_ARGS                                                                               \
-    const Model<N> m, const Chunks ch, const void *obs_ci, const void *obs_rm, const int64_t *toff, \
-        const double *Bt_g, double *alpha_entry, double *beta_exit, double *a_exit,              \
+    const Model<N> m, const Chunks ch, const void *obs_ci, const void *obs_rm, const void *obs16, \
+        const int64_t *toff, const double *Bt_g, double *alpha_entry, double *beta_exit, double *a_exit, \
         double *b_entry, int W, double *ws, double *gamma_ci, double *logL_chunk, double *gamma0, \
         double *partials, double *disc_partials, unsigned int *flags, int32_t *ea_ci,          \
         const Carry carry
 #define ESTEP_PASS                                                                               \
-    m, ch, obs_ci, obs_rm, toff, Bt_g, alpha_entry, beta_exit, a_exit, b_entry, W, ws, gamma_ci,   \
+    m, ch, obs_ci, obs_rm, obs16, toff, Bt_g, alpha_entry, beta_exit, a_exit, b_entry, W, ws, gamma_ci, \
         logL_chunk, gamma0, partials, disc_partials, flags, ea_ci, carry
 
 // the sweeps that carry the xi accumulators: two wavefronts per SIMD, up to 256 VGPRs
@@ -1684,8 +1802,16 @@ __global__ __launch_bounds__(32 * N)
         }
         // one count table per wavefront (bit-reproducible sums): the state counts come from the tables
         if constexpr (PHASE == PH_P2 && !CAREFUL) {
+            // (obs16: the host packed the 16-bit copy of the observations and this launch reads it; uniform)
             if (m.dcopies == (32 * N + 63) / 64) {
-                estep_body<N, KIND, SPEC, GAMMA, CAREFUL, PHASE, false, true>(ESTEP_PASS);
+                if (obs16)
+                    estep_body<N, KIND, SPEC, GAMMA, CAREFUL, PHASE, false, true, true>(ESTEP_PASS);
+                else
+                    estep_body<N, KIND, SPEC, GAMMA, CAREFUL, PHASE, false, true>(ESTEP_PASS);
+                return;
+            }
+            if (obs16) {
+                estep_body<N, KIND, SPEC, GAMMA, CAREFUL, PHASE, false, false, true>(ESTEP_PASS);
                 return;
             }
         }
@@ -1703,6 +1829,12 @@ __global__ __launch_bounds__(32 * N) __attribute__((amdgpu_waves_per_eu(4))) voi
         if (m.bt_global) {
             estep_body<N, KIND, SPEC, GAMMA, CAREFUL, PHASE, true>(ESTEP_PASS);
             return;
+        }
+        if constexpr (PHASE == PH_P1 && !CAREFUL) {
+            if (obs16) { // (see k_estep)
+                estep_body<N, KIND, SPEC, GAMMA, CAREFUL, PHASE, false, false, true>(ESTEP_PASS);
+                return;
+            }
         }
     }
     estep_body<N, KIND, SPEC, GAMMA, CAREFUL, PHASE>(ESTEP_PASS);

@@ -555,6 +555,12 @@ int bhmm_sample_paths_dev(bhmm_ctx *ctx, const double *A, const double *pi, cons
  *                        had to be repeated
  *   "carry_cap"          (read-only) local step at which the last E-step's backward sweep was split
  *                        to capture beta for the next one (0: one stretch, nothing captured)
+ *   "obs16"         1/0  (N <= 8, discrete, tables in LDS, nsymbols * N * 8 <= 65536 with N the padded state
+ *                        count) the main loops of the two-launch E-step read a second copy of the observations,
+ *                        2 bytes per step, packed by bhmm_ctx_set_observations (default 1).  0 keeps them on the
+ *                        int32 copy -- same statistics, bit for bit -- from the next E-step on; setting it back
+ *                        to 1 takes effect for observations loaded afterwards
+ *   "obs16_used"         (read-only) 1 if the sweeps of the last E-step read that copy
  *   "spec_ok", "spec_fail"  (read-only) E-steps whose boundaries verified / fell back
  *   "spec_last_dev" (read-only) largest relative boundary deviation of the last check
  *   "f32_used"      (read-only) 1 if the last E-step ran in fp32 end to end (BHMM_FLAG_SINGLE)
