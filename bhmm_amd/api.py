@@ -136,7 +136,8 @@ def bayesian_hmm(observations, estimated_hmm, nsample=100, reversible=True, stat
     """bhmm/api.py:375-470.  Returns a SampledHMM (which also iterates over / indexes the
     sampled models)."""
     if estimated_hmm.output_model.model_type == 'mvgaussian':
-        raise NotImplementedError('the Bayesian sampler does not handle multivariate gaussian emissions yet')
+        raise NotImplementedError('multivariate gaussian emissions are sampled by bayesian_mvgaussian_hmm, '
+                                  'not by bayesian_hmm yet')
     sampler = BayesianHMMSampler(observations, estimated_hmm.nstates, initial_model=estimated_hmm,
                                  reversible=reversible, stationary=stationary,
                                  transition_matrix_sampling_steps=1000, p0_prior=p0_prior,
@@ -144,6 +145,31 @@ def bayesian_hmm(observations, estimated_hmm, nsample=100, reversible=True, stat
                                  output=estimated_hmm.output_model.model_type, **engine_kwargs)
     sampled = sampler.sample(nsamples=nsample, save_hidden_state_trajectory=store_hidden,
                              call_back=call_back)
+    return SampledHMM(estimated_hmm, sampled)
+
+
+def bayesian_mvgaussian_hmm(observations, estimated_hmm, nsample=100, reversible=True, stationary=False,
+                            p0_prior='mixed', transition_matrix_prior='mixed', store_hidden=False,
+                            call_back=None, **engine_kwargs):
+    """bayesian_hmm for multivariate gaussian emissions: observations are (T_k, D) arrays,
+    estimated_hmm a model of output type 'mvgaussian' (estimate_hmm, mvgaussian_hmm).  Every sweep draws the hidden
+    paths and takes their moments on the device (MvnEngine.sample_paths_moments), then draws per state a mean vector
+    and -- inverse Wishart (full) or one inverse chi-square per dimension (diag) -- a covariance, the transition
+    matrix and the initial distribution (bhmm_gibbs_parameters_mvn).  Returns a SampledHMM: means_mean,
+    covariances_std, covariances_conf ... summarise the sampled emission parameters.  Sampled models are not
+    relabelled (label switching is the user's to watch, as in the reference).  engine_kwargs: device, seed (of the
+    chain; one from numpy's global generator if not given), native_parameters."""
+    if estimated_hmm.output_model.model_type != 'mvgaussian':
+        raise ValueError("bayesian_mvgaussian_hmm takes a model with multivariate gaussian emissions, not %r"
+                         % (estimated_hmm.output_model.model_type,))
+    seed = engine_kwargs.pop('seed', None)
+    sampler = BayesianHMMSampler(observations, estimated_hmm.nstates, initial_model=estimated_hmm,
+                                 reversible=reversible, stationary=stationary,
+                                 transition_matrix_sampling_steps=1000, p0_prior=p0_prior,
+                                 transition_matrix_prior=transition_matrix_prior, output='mvgaussian',
+                                 **engine_kwargs)
+    sampled = sampler.sample(nsamples=nsample, save_hidden_state_trajectory=store_hidden,
+                             call_back=call_back, seed=seed)
     return SampledHMM(estimated_hmm, sampled)
 
 

@@ -1770,6 +1770,8 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->mvn.reload_ms;
     else if (n == "mvn_moments_ms") // ... device time of the last k_mvn_moments + k_mvn_moments_finish
         *value = c->mvn.moments_ms;
+    else if (n == "mvn_path_moments_ms") // ... device time of the last k_mvn_path_moments + k_mvn_moments_finish
+        *value = c->mvn.path_moments_ms;
     else
         return invalid_arg("unknown option: " + n);
     return BHMM_OK;

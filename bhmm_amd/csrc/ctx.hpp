@@ -337,6 +337,9 @@ struct bhmm_ctx {
     // ---- the call in flight / the previous call ----
     bool fwd_defer = false;          // forward-only pass: enqueue the boundary check, do not wait for it
     bool fwd_pending = false;        // ... its verdict is still to be read (forward_ci_verdict)
+    bool keep_path = false;          // bhmm_sample_paths from bhmm_mvn_sample_paths: sample_run<N> leaves the int32 path at
+                                     // the front of d_scratch2 although no host pointer is given (the wide and generic
+                                     // families always do)
     int carry_Wout = 0;              // this launch: capture alpha this many steps before the chunks
     bool carry_store = false;        // this launch: store the captures (else the sweep is only split there)
     std::vector<double> last_pi;     // initial distribution and flags of the last E-step (nonfinite_retry repeats that call)
@@ -567,10 +570,14 @@ struct bhmm_ctx {
         std::vector<int64_t> offsets; // [K + 1]
         bhmm::DevBuf<int64_t> d_offsets;
         bhmm::DevBuf<double> X, rows, m, shift, tab, part, out;
-        // read-only options mvn_rows_ms, mvn_reload_ms, mvn_moments_ms: device time of the rows and shift kernels,
-        // host time of the explicit re-load, device time of the two moment kernels (events ev[0..1], ev[2..3])
-        float rows_ms = 0.f, reload_ms = 0.f, moments_ms = 0.f;
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        // bhmm_mvn_path_moments: a host path staged on the device, the bad-state word
+        bhmm::DevBuf<char> path;
+        bhmm::DevBuf<unsigned int> path_status;
+        // read-only options mvn_rows_ms, mvn_reload_ms, mvn_moments_ms, mvn_path_moments_ms: device time of the rows
+        // and shift kernels, host time of the explicit re-load, device time of the two moment kernels, of the path
+        // moments and their finish (events ev[0..1], ev[2..3], ev[4..5])
+        float rows_ms = 0.f, reload_ms = 0.f, moments_ms = 0.f, path_moments_ms = 0.f;
+        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         MvnBufs() = default;
         MvnBufs(const MvnBufs &) = delete;
         MvnBufs &operator=(const MvnBufs &) = delete;

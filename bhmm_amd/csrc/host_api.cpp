@@ -1,6 +1,6 @@
 // host_api.cpp -- C-ABI entry points of the host-side model updates (include/bhmm_amd.h, last
 // section): ONE call per EM iteration (bhmm_mstep) and ONE call per Gibbs sweep
-// (bhmm_gibbs_parameters) for everything the reference does in Python / numpy / msmtools between
+// (bhmm_gibbs_parameters, bhmm_gibbs_parameters_mvn) for everything the reference does in Python / numpy / msmtools between
 // two passes over the trajectories.  No device code.
 #include <math.h>
 #include <string.h>
@@ -212,48 +212,12 @@ extern "C" int bhmm_mstep(int kind, int n, int M, const double *stats, const dou
 }
 
 // ---- Gibbs parameter step --------------------------------------------------------------------
-extern "C" int bhmm_gibbs_parameters(int kind, int n, int M, const double *path_stats,
-                                     const double *prior_C, const double *prior_n0,
-                                     const double *prior_B, int reversible, int stationary,
-                                     int64_t nsteps, uint64_t seed, uint64_t sweep, double *T,
-                                     double *p0, double *par0, double *par1, int32_t *info)
+// transition matrix (bayesian_sampling.py:341-360) and initial distribution (:362-370) from the counts of the drawn
+// paths: the part of the sweep that does not depend on the emission kind
+static int draw_transitions(int n, const double *Cint, const double *n0, const double *prior_C, const double *prior_n0,
+                            int reversible, int stationary, int64_t nsteps, Rng &rng, double *T, double *p0)
 {
-    if (!path_stats || !T || !p0 || n < 1)
-        return bhmm::invalid_arg("bhmm_gibbs_parameters: NULL argument or no states");
     const size_t nn = (size_t)n * n;
-    const double *Cint = path_stats, *n0 = path_stats + nn, *emis = path_stats + nn + n;
-    Rng rng(seed, sweep);
-    // (1) emission parameters, bayesian_sampling.py:333-339
-    if (kind == BHMM_EMIT_GAUSSIAN) {
-        if (!par0 || !par1)
-            return bhmm::invalid_arg("bhmm_gibbs_parameters: gaussian emissions need means and sigmas");
-        // gaussian.py:303-318: mu ~ N(mean of the state's observations, sigma^2 / n), then
-        // sigma from the Jeffreys-prior posterior given the NEW mean (chi-square with n - 1)
-        const double *cnt = emis, *sd = emis + n, *sdd = emis + 2 * n;
-        for (int i = 0; i < n; ++i) {
-            const double ni = nearbyint(cnt[i]);
-            if (ni > 0.0) {
-                const double mu_old = par0[i];
-                const double mean_obs = mu_old + sd[i] / ni;
-                par0[i] = rng.normal() * par1[i] / sqrt(ni) + mean_obs;
-                if (ni > 1.0) {
-                    const double chi2 = rng.chisquare(ni - 1.0);
-                    const double shift = par0[i] - mu_old;
-                    const double s2 = (sdd[i] - 2.0 * shift * sd[i]) / ni + shift * shift;
-                    par1[i] = sqrt(std::max(s2, 0.0)) / sqrt(chi2 / ni);
-                }
-            }
-        }
-    } else if (kind == BHMM_EMIT_DISCRETE) {
-        if (!par0 || M < 1)
-            return bhmm::invalid_arg("bhmm_gibbs_parameters: discrete emissions need B");
-        std::vector<double> cnt(M);
-        for (int i = 0; i < n; ++i) { // discrete.py:243-251: Dirichlet over the positive counts
-            for (int k = 0; k < M; ++k)
-                cnt[k] = emis[(size_t)i * M + k] + (prior_B ? prior_B[(size_t)i * M + k] : 0.0);
-            rng.dirichlet(cnt.data(), M, par0 + (size_t)i * M);
-        }
-    }
     // (2) transition matrix, bayesian_sampling.py:341-360
     std::vector<double> C(nn);
     for (size_t e = 0; e < nn; ++e)
@@ -312,7 +276,87 @@ extern "C" int bhmm_gibbs_parameters(int kind, int n, int M, const double *path_
         }
         rng.dirichlet(w.data(), n, p0);
     }
+    return BHMM_OK;
+}
+
+extern "C" int bhmm_gibbs_parameters(int kind, int n, int M, const double *path_stats,
+                                     const double *prior_C, const double *prior_n0,
+                                     const double *prior_B, int reversible, int stationary,
+                                     int64_t nsteps, uint64_t seed, uint64_t sweep, double *T,
+                                     double *p0, double *par0, double *par1, int32_t *info)
+{
+    if (!path_stats || !T || !p0 || n < 1)
+        return bhmm::invalid_arg("bhmm_gibbs_parameters: NULL argument or no states");
+    const size_t nn = (size_t)n * n;
+    const double *Cint = path_stats, *n0 = path_stats + nn, *emis = path_stats + nn + n;
+    Rng rng(seed, sweep);
+    // (1) emission parameters, bayesian_sampling.py:333-339
+    if (kind == BHMM_EMIT_GAUSSIAN) {
+        if (!par0 || !par1)
+            return bhmm::invalid_arg("bhmm_gibbs_parameters: gaussian emissions need means and sigmas");
+        // gaussian.py:303-318: mu ~ N(mean of the state's observations, sigma^2 / n), then
+        // sigma from the Jeffreys-prior posterior given the NEW mean (chi-square with n - 1)
+        const double *cnt = emis, *sd = emis + n, *sdd = emis + 2 * n;
+        for (int i = 0; i < n; ++i) {
+            const double ni = nearbyint(cnt[i]);
+            if (ni > 0.0) {
+                const double mu_old = par0[i];
+                const double mean_obs = mu_old + sd[i] / ni;
+                par0[i] = rng.normal() * par1[i] / sqrt(ni) + mean_obs;
+                if (ni > 1.0) {
+                    const double chi2 = rng.chisquare(ni - 1.0);
+                    const double shift = par0[i] - mu_old;
+                    const double s2 = (sdd[i] - 2.0 * shift * sd[i]) / ni + shift * shift;
+                    par1[i] = sqrt(std::max(s2, 0.0)) / sqrt(chi2 / ni);
+                }
+            }
+        }
+    } else if (kind == BHMM_EMIT_DISCRETE) {
+        if (!par0 || M < 1)
+            return bhmm::invalid_arg("bhmm_gibbs_parameters: discrete emissions need B");
+        std::vector<double> cnt(M);
+        for (int i = 0; i < n; ++i) { // discrete.py:243-251: Dirichlet over the positive counts
+            for (int k = 0; k < M; ++k)
+                cnt[k] = emis[(size_t)i * M + k] + (prior_B ? prior_B[(size_t)i * M + k] : 0.0);
+            rng.dirichlet(cnt.data(), M, par0 + (size_t)i * M);
+        }
+    }
+    // (2) transition matrix, (3) initial distribution
+    if (int rc = draw_transitions(n, Cint, n0, prior_C, prior_n0, reversible, stationary, nsteps, rng, T, p0))
+        return rc;
     if (info)
         info[0] = (int32_t)std::min<uint64_t>(rng.ctr, 2147483647u);
+    return BHMM_OK;
+}
+
+// the same sweep for multivariate gaussian emissions: the emission draws of
+// mvn_gibbs_emissions (host_model.cpp), then the transition matrix and p0 as above, on one generator
+extern "C" int bhmm_gibbs_parameters_mvn(int n, int D, int cov_type, const double *path_stats, const double *prior_C,
+                                         const double *prior_n0, int reversible, int stationary, int64_t nsteps,
+                                         uint64_t seed, uint64_t sweep, double *T, double *p0, double *means,
+                                         double *covs, int32_t *info)
+{
+    if (!path_stats || !T || !p0 || !means || !covs)
+        return bhmm::invalid_arg("bhmm_gibbs_parameters_mvn: NULL argument");
+    if (n < 1 || n > 4096 || D < 1 || D > BHMM_MVN_MAX_D)
+        return bhmm::invalid_arg("bhmm_gibbs_parameters_mvn: 1..4096 states and 1.." + std::to_string(BHMM_MVN_MAX_D) +
+                                 " dimensions are supported");
+    if (cov_type != BHMM_COV_FULL && cov_type != BHMM_COV_DIAG)
+        return bhmm::invalid_arg("bhmm_gibbs_parameters_mvn: cov_type is BHMM_COV_FULL or BHMM_COV_DIAG");
+    const size_t nn = (size_t)n * n;
+    const double *Cint = path_stats, *n0 = path_stats + nn, *moments = path_stats + nn + n;
+    for (size_t e = 0; e < (size_t)n * D; ++e)
+        if (!std::isfinite(means[e]))
+            return bhmm::invalid_arg("bhmm_gibbs_parameters_mvn: a mean is not finite");
+    Rng rng(seed, sweep);
+    int32_t kept = 0;
+    if (int rc = mvn_gibbs_emissions(n, D, cov_type, moments, rng, means, covs, &kept))
+        return rc;
+    if (int rc = draw_transitions(n, Cint, n0, prior_C, prior_n0, reversible, stationary, nsteps, rng, T, p0))
+        return rc;
+    if (info) {
+        info[0] = (int32_t)std::min<uint64_t>(rng.ctr, 2147483647u);
+        info[1] = kept;
+    }
     return BHMM_OK;
 }

@@ -801,5 +801,109 @@ int mvn_mstep(int n, int D, int cov_type, const double *moments, const double *m
     return mvn_prepare(n, D, cov_type, covs_new, nullptr, nullptr, nullptr);
 }
 
+// Cholesky-Banachiewicz of the symmetric S (lower triangle read) into L (lower, zeros above).  false: not positive
+// definite -- a pivot that is not finite or not above 1e-12 of its diagonal entry counts as zero (the scatter of
+// points in a subspace leaves rounding residue of either sign there)
+static bool scatter_factor(const double *S, int D, double *L)
+{
+    for (int a = 0; a < D; ++a)
+        for (int b = 0; b < D; ++b)
+            L[(size_t)a * D + b] = 0.0;
+    for (int a = 0; a < D; ++a)
+        for (int b = 0; b <= a; ++b) {
+            double s = S[(size_t)a * D + b];
+            for (int k = 0; k < b; ++k)
+                s -= L[(size_t)a * D + k] * L[(size_t)b * D + k];
+            if (a == b) {
+                if (!std::isfinite(s) || !(s > 1e-12 * S[(size_t)a * D + a]))
+                    return false;
+                L[(size_t)a * D + a] = sqrt(s);
+            } else {
+                L[(size_t)a * D + b] = s / L[(size_t)b * D + b];
+            }
+        }
+    return true;
+}
+
+int mvn_gibbs_emissions(int n, int D, int cov_type, const double *moments, Rng &rng, double *means, double *covs,
+                        int32_t *kept)
+{
+    const size_t ms = mvn_moment_stride(D, cov_type), cs = cov_type ? (size_t)D : (size_t)D * D;
+    std::vector<double> chol((size_t)n * cs);
+    if (int rc = mvn_prepare(n, D, cov_type, covs, chol.data(), nullptr, nullptr))
+        return rc;
+    std::vector<double> z(D), delta(D), S((size_t)D * D), LS((size_t)D * D), B((size_t)D * D), M((size_t)D * D);
+    *kept = 0;
+    for (int i = 0; i < n; ++i) {
+        const double *m = moments + (size_t)i * ms, *s1 = m + 1, *s2 = m + 1 + D;
+        const double ni = nearbyint(m[0]);
+        if (!(ni > 0.0))
+            continue;
+        double *mu = means + (size_t)i * D, *cov = covs + (size_t)i * cs;
+        const double *L = chol.data() + (size_t)i * cs;
+        const double rn = sqrt(ni);
+        // the mean: N(mean of the state's observations, Sigma_old / n_i)
+        for (int d = 0; d < D; ++d)
+            z[d] = rng.normal();
+        for (int d = 0; d < D; ++d) {
+            double lz;
+            if (cov_type) {
+                lz = z[d] * L[d];
+            } else {
+                lz = 0.0;
+                for (int k = 0; k <= d; ++k)
+                    lz += L[(size_t)d * D + k] * z[k];
+            }
+            const double mu_new = lz / rn + (mu[d] + s1[d] / ni);
+            delta[d] = mu_new - mu[d];
+            mu[d] = mu_new;
+        }
+        // the covariance given the NEW mean, from the scatter about it
+        if (cov_type) {
+            if (ni > 1.0)
+                for (int d = 0; d < D; ++d) {
+                    const double chi2 = rng.chisquare(ni - 1.0);
+                    const double sdd = s2[d] - 2.0 * delta[d] * s1[d] + ni * delta[d] * delta[d];
+                    if (sdd > 0.0)
+                        cov[d] = sdd / chi2;
+                    else
+                        ++*kept; // (every observation of the state on the new mean: the variance stays)
+                }
+            continue;
+        }
+        for (int a = 0; a < D; ++a)
+            for (int b = 0; b <= a; ++b)
+                S[(size_t)a * D + b] = S[(size_t)b * D + a] =
+                    s2[(size_t)a * (a + 1) / 2 + b] - delta[a] * s1[b] - s1[a] * delta[b] + ni * delta[a] * delta[b];
+        if (!(ni - 1.0 >= (double)D) || !scatter_factor(S.data(), D, LS.data())) {
+            ++*kept;
+            continue;
+        }
+        // Bartlett factor of a Wishart(I, n_i - 1) draw: diagonal first, then below it row by row
+        std::fill(B.begin(), B.end(), 0.0);
+        for (int d = 0; d < D; ++d)
+            B[(size_t)d * D + d] = sqrt(rng.chisquare(ni - 1.0 - d));
+        for (int a = 1; a < D; ++a)
+            for (int b = 0; b < a; ++b)
+                B[(size_t)a * D + b] = rng.normal();
+        // M = L_S B^-T: row r of M solves B m = (row r of L_S)^T by forward substitution
+        for (int r = 0; r < D; ++r)
+            for (int a = 0; a < D; ++a) {
+                double s = LS[(size_t)r * D + a];
+                for (int k = 0; k < a; ++k)
+                    s -= B[(size_t)a * D + k] * M[(size_t)r * D + k];
+                M[(size_t)r * D + a] = s / B[(size_t)a * D + a];
+            }
+        for (int a = 0; a < D; ++a)
+            for (int b = 0; b <= a; ++b) {
+                double s = 0.0;
+                for (int k = 0; k < D; ++k)
+                    s += M[(size_t)a * D + k] * M[(size_t)b * D + k];
+                cov[(size_t)a * D + b] = cov[(size_t)b * D + a] = s;
+            }
+    }
+    return BHMM_OK;
+}
+
 } // namespace host
 } // namespace bhmm

@@ -87,6 +87,12 @@ int mvn_prepare(int n, int D, int cov_type, const double *covs, double *chol, do
 // definite (or not finite: a state without weight)
 int mvn_mstep(int n, int D, int cov_type, const double *moments, const double *means_old, double min_covar,
               double *means_new, double *covs_new);
+// the emission draws of a Gibbs sweep from the packed moments of a hidden path about `means` (DESIGN.md section 24,
+// the rule in include/bhmm_amd.h at bhmm_gibbs_parameters_mvn): means and covs in (current) and out (new), per state in
+// ascending order; kept: states whose covariance could not be drawn and stays.  BHMM_ERR_INVALID / BHMM_ERR_SIGMA
+// from mvn_prepare on the current covariances
+int mvn_gibbs_emissions(int n, int D, int cov_type, const double *moments, Rng &rng, double *means, double *covs,
+                        int32_t *kept);
 
 } // namespace host
 } // namespace bhmm

@@ -1,6 +1,7 @@
 // mvn_api.hip -- multivariate gaussian emissions (bhmm_ctx_set_observations_mvn, bhmm_mvn_emissions,
-// bhmm_mvn_fetch_scale, bhmm_mvn_fetch_rows, bhmm_mvn_moments, bhmm_logpdf_mvn): kernels in mvn_kernels.hpp, the
-// factorisation on the host (host::mvn_prepare, host_model.cpp); DESIGN.md section 23.
+// bhmm_mvn_fetch_scale, bhmm_mvn_fetch_rows, bhmm_mvn_moments, bhmm_mvn_path_moments, bhmm_mvn_sample_paths,
+// bhmm_logpdf_mvn): kernels in mvn_kernels.hpp, the factorisation on the host (host::mvn_prepare, host_model.cpp);
+// DESIGN.md sections 23 and 24.
 //
 // The recursions know nothing of this kind.  bhmm_mvn_emissions turns the observations kept in c->mvn.X into scaled
 // emission rows in c->mvn.rows and hands those to bhmm_ctx_set_observations as BHMM_EMIT_EXPLICIT observations on the
@@ -100,6 +101,56 @@ struct Tmp { // device allocations of one level-1 call
         return BHMM_OK;
     }
 };
+
+// Packed moments of the hidden path at path_dev (device; int32 or one byte per step) about means (host) into out
+// (host): k_mvn_path_moments, one slab per workgroup, then k_mvn_moments_finish over the slabs.  A state outside
+// [0, n) is found by the kernel before it indexes anything with it: BHMM_ERR_INVALID, nothing is delivered.
+int run_path_moments(bhmm_ctx *c, const char *who, const void *path_dev, int path_u8, const double *means, int cov_type,
+                     double *out)
+{
+    auto &b = c->mvn;
+    const bool diag = cov_type == BHMM_COV_DIAG;
+    const int D = b.D, n = b.n;
+    const int mode = diag ? PM_ELEM_DIAG : (D >= PM_BLOCK_MIN_D ? PM_BLOCK : PM_ELEM_FULL);
+    const size_t E = (size_t)n * moment_stride(D, diag);
+    const PmPlan pl = pm_plan(b.total, D, n, mode);
+    int rc;
+    if ((rc = b.part.ensure((size_t)pl.groups * E)) || (rc = b.out.ensure(E)) || (rc = b.tab.ensure((size_t)n * D)) ||
+        (rc = b.path_status.ensure(1)))
+        return rc;
+    // (the table of the last bhmm_mvn_emissions is not needed any more: the rows are made)
+    BHMM_HIP(hipMemcpyAsync(b.tab.p, means, (size_t)n * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemsetAsync(b.path_status.p, 0, sizeof(unsigned int), c->stream));
+    for (hipEvent_t &e : b.ev)
+        if (!e)
+            BHMM_HIP(hipEventCreate(&e));
+    BHMM_HIP(hipEventRecord(b.ev[4], c->stream));
+    if (!pl.slab_lds) // the slabs are accumulated where they lie
+        BHMM_HIP(hipMemsetAsync(b.part.p, 0, (size_t)pl.groups * E * sizeof(double), c->stream));
+    const dim3 grid((unsigned)pl.groups), block(PM_THREADS);
+#define BHMM_MVN_PM(PT, MODE)                                                                                          \
+    launch(k_mvn_path_moments<PT, MODE>, grid, block, pl.lds, c->stream, b.X.p, static_cast<const PT *>(path_dev),      \
+           b.total, D, n, b.tab.p, pl, b.part.p, b.path_status.p)
+#define BHMM_MVN_PM_MODE(PT)                                                                                           \
+    (mode == PM_BLOCK ? BHMM_MVN_PM(PT, PM_BLOCK) : mode == PM_ELEM_DIAG ? BHMM_MVN_PM(PT, PM_ELEM_DIAG)               \
+                                                                         : BHMM_MVN_PM(PT, PM_ELEM_FULL))
+    BHMM_HIP(path_u8 ? BHMM_MVN_PM_MODE(uint8_t) : BHMM_MVN_PM_MODE(int32_t));
+#undef BHMM_MVN_PM_MODE
+#undef BHMM_MVN_PM
+    BHMM_HIP(launch(k_mvn_moments_finish, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, c->stream, b.part.p, pl.groups,
+                    (int64_t)E, b.out.p));
+    BHMM_HIP(hipEventRecord(b.ev[5], c->stream));
+    std::vector<double> res(E);
+    unsigned int status = 0;
+    BHMM_HIP(hipMemcpyAsync(res.data(), b.out.p, E * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    BHMM_HIP(hipMemcpyAsync(&status, b.path_status.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream));
+    (void)hipEventElapsedTime(&b.path_moments_ms, b.ev[4], b.ev[5]);
+    if (status & PM_BAD_STATE)
+        return invalid_arg(std::string(who) + ": the path holds a state outside [0, " + std::to_string(n) + ")");
+    memcpy(out, res.data(), E * sizeof(double));
+    return BHMM_OK;
+}
 
 } // namespace
 } // namespace bhmm
@@ -256,6 +307,55 @@ int bhmm_mvn_moments(bhmm_ctx *c, const double *gamma_dev, const double *means, 
     BHMM_HIP(hipStreamSynchronize(c->stream));
     (void)hipEventElapsedTime(&b.moments_ms, b.ev[2], b.ev[3]);
     return BHMM_OK;
+}
+
+int bhmm_mvn_path_moments(bhmm_ctx *c, const void *paths, int path_u8, int paths_on_device, const double *means,
+                          int cov_type, double *out)
+{
+    if (!c || !c->mvn.active)
+        return invalid_arg("bhmm_mvn_path_moments: no multivariate observations loaded");
+    if (!paths || !means || !out)
+        return invalid_arg("bhmm_mvn_path_moments: paths / means / out == NULL");
+    auto &b = c->mvn;
+    if (int rc = shape_ok("bhmm_mvn_path_moments", b.n, b.D, cov_type))
+        return rc;
+    if (path_u8 && b.n > 256) // (every byte is a state then; the int32 form holds the others)
+        return invalid_arg("bhmm_mvn_path_moments: one byte per step holds at most 256 states (use the int32 form)");
+    BHMM_HIP(hipSetDevice(c->device));
+    if (paths_on_device) {
+        if (reinterpret_cast<uintptr_t>(paths) % 16)
+            return invalid_arg("bhmm_mvn_path_moments: a device path must be aligned to 16 bytes");
+        return run_path_moments(c, "bhmm_mvn_path_moments", paths, path_u8, means, cov_type, out);
+    }
+    const size_t bytes = (size_t)b.total * (path_u8 ? sizeof(uint8_t) : sizeof(int32_t));
+    if (int rc = b.path.ensure(bytes))
+        return rc;
+    BHMM_HIP(hipMemcpyAsync(b.path.p, paths, bytes, hipMemcpyHostToDevice, c->stream));
+    return run_path_moments(c, "bhmm_mvn_path_moments", b.path.p, path_u8, means, cov_type, out);
+}
+
+int bhmm_mvn_sample_paths(bhmm_ctx *c, const double *A, const double *pi, const double *u, uint64_t seed,
+                          int32_t *paths, int64_t *counts, int64_t *n0, const double *means, int cov_type,
+                          double *moments)
+{
+    if (!c || !c->mvn.active || !c->mvn.rows_valid)
+        return invalid_arg("bhmm_mvn_sample_paths: no bhmm_mvn_emissions has run on these observations");
+    if (!A || !pi || !means || !moments)
+        return invalid_arg("bhmm_mvn_sample_paths: A / pi / means / moments == NULL");
+    auto &b = c->mvn;
+    if (int rc = shape_ok("bhmm_mvn_sample_paths", b.n, b.D, cov_type))
+        return rc;
+    if (c->n != b.n || c->total != b.total)
+        return invalid_arg("bhmm_mvn_sample_paths: the loaded emission rows are not those of the multivariate set");
+    // the draw leaves its int32 path at the front of c->d_scratch2 (sample_run<N>: because keep_path says so); it
+    // crosses the link only when the caller wants it
+    c->keep_path = true;
+    const int rc = bhmm_sample_paths(c, A, pi, nullptr, nullptr, u, seed, paths, counts, n0, nullptr);
+    c->keep_path = false;
+    if (rc)
+        return rc;
+    // ... and is read here, before anything else uses that buffer
+    return run_path_moments(c, "bhmm_mvn_sample_paths", c->d_scratch2.p, 0, means, cov_type, moments);
 }
 
 int bhmm_logpdf_mvn(double *logp, const double *X, int64_t T, int D, int N, const double *means, const double *covs,

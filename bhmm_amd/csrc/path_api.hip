@@ -176,14 +176,16 @@ int sample_run(bhmm_ctx *c, const double *A, const double *pi, const double *par
     const size_t esz = c->kind == EMIT_GAUSS ? 3 * (size_t)N : (c->kind == EMIT_DISC ? (size_t)c->M * N : 0);
     // scratch2: [path] | status | part maps | next-part states | lowest non-final step per part |
     // nibbles of the final steps (8 per word)
-    const size_t npath = paths ? (size_t)c->total : 0;
+    // (c->keep_path: the caller reads the path on the device afterwards -- bhmm_mvn_sample_paths -- no copy for it)
+    const bool want_path = paths || c->keep_path;
+    const size_t npath = want_path ? (size_t)c->total : 0;
     const int Lp = c->Lmax / P + 2;          // steps per part (upper bound)
     const int W8 = (Lp + 7) / 8 + 1;
     // ... | full step maps above the coalescence point (one word per step)
     if ((rc = c->d_scratch2.ensure((npath + 4 + (3 + (size_t)W8 + (size_t)Lp) * (size_t)c->Gp * P) *
                                    sizeof(int32_t))))
         return rc;
-    int32_t *path = paths ? reinterpret_cast<int32_t *>(c->d_scratch2.p) : nullptr;
+    int32_t *path = want_path ? reinterpret_cast<int32_t *>(c->d_scratch2.p) : nullptr;
     int *status = nullptr; // (lives behind the counts, see below)
     uint32_t *fmap = reinterpret_cast<uint32_t *>(reinterpret_cast<int32_t *>(c->d_scratch2.p) + npath + 4);
     int32_t *nstate = reinterpret_cast<int32_t *>(fmap + (size_t)c->Gp * P);

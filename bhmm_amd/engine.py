@@ -682,10 +682,11 @@ class Engine(object):
             lambda off, dwell, jumps: self._L.bhmm_path_runs(self._h, ctypes.c_void_p(int(ptr)), 1 if u8 else 0,
                                                              on_dev, off, dwell, jumps), stats)
 
-    def _path_arg(self, paths):
+    def _path_arg(self, paths, loaded=None):
         """(address, one byte per step, on this engine's GPU) of a flat path, validated against the loaded
-        trajectories before any native call (path_runs, path_logprob)."""
-        if self._ctx_kind is None:
+        trajectories before any native call (path_runs, path_logprob; loaded: the caller's own answer to "are there
+        observations", where that is not the context's kind)."""
+        if not (self._ctx_kind is not None if loaded is None else loaded):
             raise ValueError("no observations loaded")
         total = int(self.offsets[-1])
         on_dev = 0
@@ -1013,6 +1014,54 @@ class MvnEngine(Engine):
                                             _lib.COV_FULL if covariance_type == 'full' else _lib.COV_DIAG,
                                             _lib.dp(out)))
         return out
+
+    def _moments_args(self, means, covariance_type):
+        from .output_models.mvgaussian import moment_stride
+        if self.dimension == 0:
+            raise ValueError("no observations loaded")
+        mu = _lib.f64(means)
+        if mu.shape != (self.nstates, self.dimension):
+            raise ValueError("means must be (%d, %d)" % (self.nstates, self.dimension))
+        out = np.empty(self.nstates * moment_stride(self.dimension, covariance_type))
+        return mu, _lib.COV_FULL if covariance_type == 'full' else _lib.COV_DIAG, out
+
+    def path_moments(self, paths, means, covariance_type='full'):
+        """Packed moments of a hidden path about `means` (bhmm_mvn_path_moments), in the layout of `moments`: per
+        state the count S0, S1 = sum (x_t - mu_i) and S2 = sum (x_t - mu_i)(x_t - mu_i)^T (lower triangle or
+        diagonal) over the steps with s_t = i.  `paths` as path_logprob takes them: a flat uint8 / int32 numpy array,
+        a list of one integer array per trajectory, or a uint8 / int32 tensor (read in place on this engine's GPU).
+        Needs no emissions.  The arithmetic per step does not grow with the number of states; a state that never
+        occurs gives exact zeros, a state outside [0, nstates) raises ValueError; bitwise the same from call to
+        call and for every form of the same path (read-only option "mvn_path_moments_ms": device time)."""
+        mu, ctype, out = self._moments_args(means, covariance_type)
+        if isinstance(paths, (list, tuple)):
+            paths = self._concat_paths(paths)
+        ptr, u8, on_dev = self._path_arg(paths, loaded=True)
+        _lib.check(self._L.bhmm_mvn_path_moments(self._h, ctypes.c_void_p(int(ptr)), 1 if u8 else 0, on_dev,
+                                                 _lib.dp(mu), ctype, _lib.dp(out)))
+        return out
+
+    def sample_paths_moments(self, A, pi, means, covariances, u=None, seed=0, want_paths=False):
+        """Gibbs hidden-path step under (A, pi, means, covariances) followed by the packed moments of the drawn path
+        about `means` (bhmm_mvn_sample_paths).  Returns (paths or None, C int64 (n, n), n0 int64 (n,), moments);
+        paths, C and n0 are those of sample_paths for the same arguments.  The path stays on the device unless
+        want_paths."""
+        ctype = self.emissions(means, covariances)
+        mu, code, out = self._moments_args(means, ctype)
+        A, pi, _, _ = self._model_ptrs(A, pi, None, None)
+        n = self.nstates
+        total = int(self.offsets[-1])
+        paths = np.empty(total, dtype=np.int32) if want_paths else None
+        C = np.zeros((n, n), dtype=np.int64)
+        n0 = np.zeros(n, dtype=np.int64)
+        uu = _lib.f64(np.concatenate(u)) if u is not None else None
+        _lib.check(self._L.bhmm_mvn_sample_paths(self._h, A, pi, _lib.dp(uu), ctypes.c_uint64(int(seed)),
+                                                 _lib.ip(paths), _lib.lp(C), _lib.lp(n0), _lib.dp(mu), code,
+                                                 _lib.dp(out)))
+        plist = None
+        if want_paths:
+            plist = [paths[self.offsets[k]:self.offsets[k + 1]] for k in range(len(self.lengths))]
+        return plist, C, n0, out
 
     # -- E-step --------------------------------------------------------------------------
     def estep_launch(self, A, pi, par0=None, par1=None, stats_dev=None, store_gamma=False, single=False):

@@ -97,3 +97,43 @@ class GibbsParameters(object):
                             int(seed) & 0xFFFFFFFFFFFFFFFF, int(sweep), *self._out, _addr(p0n),
                             _addr(p1n), self._info))
         return self.T.copy(), self.p0.copy(), p0n, p1n
+
+
+class GibbsParametersMvn(object):
+    """Persistent argument block of bhmm_gibbs_parameters_mvn for one sampler (multivariate gaussian emissions)."""
+
+    def __init__(self, n, D, covariance_type='full', prior_C=None, prior_n0=None, reversible=True,
+                 stationary=False, nsteps=1000):
+        if covariance_type not in ('full', 'diag'):
+            raise ValueError("covariance_type must be 'full' or 'diag', not %r" % (covariance_type,))
+        self._L = _lib.load()
+        self._fn = self._L.bhmm_gibbs_parameters_mvn
+        self.n, self.D, self.covariance_type = int(n), int(D), covariance_type
+        self._code = _lib.COV_FULL if covariance_type == 'full' else _lib.COV_DIAG
+        self.prior_C = _lib.f64(prior_C) if prior_C is not None else None
+        self.prior_n0 = _lib.f64(prior_n0) if prior_n0 is not None else None
+        self.reversible, self.stationary, self.nsteps = bool(reversible), bool(stationary), int(nsteps)
+        self.T = np.empty((n, n))
+        self.p0 = np.empty(n)
+        self.info = np.zeros(2, dtype=np.int32)   # draws consumed, states whose covariance was kept
+        self._priors = (_addr(self.prior_C), _addr(self.prior_n0))
+        self._out = (_addr(self.T), _addr(self.p0))
+        self._info = _lib.ip(self.info)
+
+    def __call__(self, packed_path_stats, means, covariances, seed, sweep):
+        """packed_path_stats: [C n*n | n0 n | packed moments about `means`]; means / covariances: the current
+        parameters (copied, then updated in the copies).  Returns (T, p0, means_new, covariances_new)."""
+        n, D = self.n, self.D
+        packed = _c64(packed_path_stats)
+        stride = 1 + D + (D * (D + 1) // 2 if self.covariance_type == 'full' else D)
+        if packed.shape != (n * n + n + n * stride,):
+            raise ValueError("packed path statistics must hold %d doubles" % (n * n + n + n * stride))
+        mu = np.array(means, dtype=np.float64)
+        cov = np.array(covariances, dtype=np.float64)
+        if mu.shape != (n, D) or cov.shape != ((n, D, D) if self.covariance_type == 'full' else (n, D)):
+            raise ValueError("means / covariances do not have the shapes of %d states, %d dimensions, %r"
+                             % (n, D, self.covariance_type))
+        _lib.check(self._fn(n, D, self._code, _addr(packed), *self._priors, int(self.reversible),
+                            int(self.stationary), self.nsteps, int(seed) & 0xFFFFFFFFFFFFFFFF, int(sweep),
+                            *self._out, _addr(mu), _addr(cov), self._info))
+        return self.T.copy(), self.p0.copy(), mu, cov

@@ -36,6 +36,8 @@ def _unpack_path_stats(packed, kind, n, M):
         return C, n0, rest[:3 * n].reshape(3, n).copy()
     if kind == 'discrete':
         return C, n0, rest[:n * M].reshape(n, M).copy()
+    if kind == 'mvgaussian':
+        return C, n0, rest.copy()       # the packed moments of bhmm_mvn_path_moments
     return C, n0, None
 
 
@@ -46,6 +48,10 @@ class BayesianHMMSampler(object):
                  process_group=None, engine_factory=None, native_parameters=True):
         if len(observations) == 0:
             raise Exception("No observations were provided.")
+        kind = initial_model.output_model.model_type if initial_model else output
+        if kind == 'mvgaussian' and process_group is not None:
+            # multivariate gaussian emissions: single process, as for the estimator
+            raise NotImplementedError('multivariate gaussian emissions do not run over a process_group yet')
         self.reversible = reversible
         self.stationary = stationary
         self.nstates = nstates
@@ -104,6 +110,9 @@ class BayesianHMMSampler(object):
             device = default_device(self._comm)
         self._comm.bind_device(device)       # collectives run on the engine's GPU
         factory = engine_factory or _default_engine_factory
+        if self._output == 'mvgaussian' and engine_factory is None:
+            from .maximum_likelihood import _mvn_engine_factory
+            factory = _mvn_engine_factory
         self._engine = factory(device)
         M = self.model.output_model.nsymbols if self._output == 'discrete' else 0
         self._nsymbols = M
@@ -189,6 +198,13 @@ class BayesianHMMSampler(object):
                 base = int(self._rng.randint(0, 2 ** 31 - 1)) * 2 ** 31 + int(self._rng.randint(0, 2 ** 31 - 1))
                 base = int(self._comm.broadcast_numpy(np.array([base], dtype=np.int64), src=0)[0])
             self._param_seed = (base * 0x9E3779B1 + 0x7F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        if self._draw is None and self._output == 'mvgaussian':
+            from ._native import GibbsParametersMvn
+            om = self.model.output_model
+            self._draw = GibbsParametersMvn(
+                self.nstates, om.dimension, om.covariance_type, prior_C=self.prior_C, prior_n0=self.prior_n0,
+                reversible=self.reversible, stationary=self.stationary,
+                nsteps=self.transition_matrix_sampling_steps)
         if self._draw is None:
             from ._native import GibbsParameters
             om = self.model.output_model
@@ -248,7 +264,13 @@ class BayesianHMMSampler(object):
             return np.concatenate([np.ravel(C).astype(np.float64), np.ravel(n0).astype(np.float64)]
                                   + ([np.ravel(emis)] if esz else []))
 
-        if not comm.active:
+        if self._output == 'mvgaussian':
+            # (single process.)  The drawn path stays on the device, where its moments about the current means are
+            # taken (bhmm_mvn_sample_paths): [C | n0 | packed moments]
+            paths, C, n0, mom = eng.sample_paths_moments(A, pi, par0, par1, seed=sweep_seed,
+                                                         want_paths=keep_paths)
+            packed = np.concatenate([np.ravel(C).astype(np.float64), np.ravel(n0).astype(np.float64), mom])
+        elif not comm.active:
             paths, C, n0, emis = eng.sample_paths(A, pi, par0, par1, seed=sweep_seed,
                                                   want_paths=keep_paths)
             packed = pack(C, n0, emis)
@@ -289,6 +311,10 @@ class BayesianHMMSampler(object):
         om = self.model.output_model
         if self._output == 'gaussian':
             om.sample_from_statistics(emis[0], emis[1], emis[2], rng=self._rng)
+        elif self._output == 'mvgaussian':
+            from ..output_models.mvgaussian import unpack_moments
+            om.sample_from_statistics(*unpack_moments(emis, self.nstates, om.dimension, om.covariance_type),
+                                      rng=self._rng)
         else:
             om.sample_from_statistics(emis, rng=self._rng)
 

@@ -50,6 +50,23 @@ def unpack_moments(packed, N, D, covariance_type):
     return S0, S1, S2
 
 
+def _scatter_factor(S):
+    """Cholesky factor of a scatter matrix, or None where it has none: a pivot that is not above 1e-12 of its
+    diagonal entry counts as zero (the rule of the native draw, host_model.cpp)."""
+    D = S.shape[0]
+    L = np.zeros((D, D))
+    for a in range(D):
+        for b in range(a + 1):
+            s = S[a, b] - np.dot(L[a, :b], L[b, :b])
+            if a == b:
+                if not np.isfinite(s) or not s > 1e-12 * S[a, a]:
+                    return None
+                L[a, a] = np.sqrt(s)
+            else:
+                L[a, b] = s / L[b, b]
+    return L
+
+
 def check_observation(o, D=None):
     """One trajectory as a C-contiguous float64 (T, D) array."""
     o = np.asarray(o, dtype=np.float64)
@@ -164,6 +181,69 @@ class MultivariateGaussianOutputModel(OutputModel):
                                                    _lib.dp(_lib.f64(self._means)), self.min_covar, _lib.dp(means),
                                                    _lib.dp(covs)))
         self._means, self._covs = means, covs
+
+    def sample_from_statistics(self, S0, S1, S2, rng=np.random):
+        """Gibbs update from the moments of a hidden path about the current means (the rule
+        of bhmm_gibbs_parameters_mvn in numpy, on rng's stream): S0 (N,) counts, S1 (N, D) = sum (x - mu_old),
+        S2 (N, D, D) or (N, D) = sum (x - mu_old)(x - mu_old)^T (its diagonal).  Per state with n = S0 > 0:
+        mu' = mu + S1 / n + L z / sqrt(n) (z: D standard normals, L the Cholesky factor of the current covariance);
+        S = the scatter about mu'; full with n - 1 >= D and S positive definite: Sigma' = (L_S B^-T)(L_S B^-T)^T, B a
+        Bartlett factor (sqrt of chi-squares with n - 1 - d degrees of freedom on the diagonal, then the standard
+        normals below it, row-major) -- an inverse-Wishart draw; diag with n > 1: S_dd / chi2(n - 1) per dimension.
+        At D = 1 this consumes the variates of GaussianOutputModel.sample_from_statistics in its order.  Returns the
+        number of states whose covariance was kept because it could not be drawn."""
+        N, D = self.nstates, self._D
+        S0, S1, S2 = (np.asarray(a, dtype=np.float64) for a in (S0, S1, S2))
+        if S0.shape != (N,) or S1.shape != (N, D) or S2.shape != self._cov_shape():
+            raise ValueError('moments must have shapes (%d,), (%d, %d) and %r' % (N, N, D, self._cov_shape()))
+        full = self._covariance_type == 'full'
+        kept = 0
+        for i in range(N):
+            n = int(round(S0[i]))
+            if n <= 0:
+                continue
+            old_mu = self._means[i].copy()
+            L = self._factor(i)
+            z = np.array([rng.randn()]) if D == 1 else rng.standard_normal(D)
+            self._means[i] = L.dot(z) / np.sqrt(n) + (old_mu + S1[i] / n)
+            delta = self._means[i] - old_mu
+            if not full:
+                if n > 1:
+                    for d in range(D):
+                        chi2 = rng.chisquare(n - 1)
+                        sdd = S2[i, d] - 2.0 * delta[d] * S1[i, d] + n * delta[d] * delta[d]
+                        if sdd > 0.0:
+                            self._covs[i, d] = sdd / chi2
+                        else:
+                            kept += 1
+                continue
+            S = S2[i] - np.outer(delta, S1[i]) - np.outer(S1[i], delta) + n * np.outer(delta, delta)
+            LS = _scatter_factor(S) if n - 1 >= D else None
+            if LS is None:
+                kept += 1
+                continue
+            B = np.zeros((D, D))
+            for d in range(D):
+                B[d, d] = np.sqrt(rng.chisquare(n - 1 - d))
+            if D > 1:
+                B[np.tril_indices(D, -1)] = rng.standard_normal(D * (D - 1) // 2)
+            M = np.linalg.solve(B, LS.T).T          # L_S B^-T
+            cov = M.dot(M.T)
+            self._covs[i] = 0.5 * (cov + cov.T)
+        return kept
+
+    def sample(self, observations, prior=None, rng=np.random):
+        """The reference's signature (gaussian.py:274-320) on top of sample_from_statistics: observations[k] are the
+        (n_k, D) observations assigned to state k."""
+        N, D = self.nstates, self._D
+        S0, S1 = np.zeros(N), np.zeros((N, D))
+        S2 = np.zeros(self._cov_shape())
+        for i in range(N):
+            o = np.asarray(observations[i], dtype=np.float64).reshape(-1, D)
+            d = o - self._means[i]
+            S0[i], S1[i] = o.shape[0], d.sum(axis=0)
+            S2[i] = d.T.dot(d) if self._covariance_type == 'full' else (d * d).sum(axis=0)
+        return self.sample_from_statistics(S0, S1, S2, rng=rng)
 
     def _factor(self, state_index):
         c = self._covs[state_index]

@@ -494,8 +494,23 @@ int bhmm_decode_logprob(bhmm_ctx *ctx, const double *A, const double *pi, const 
  *     BHMM_COV_DIAG): N * (1 + D + D (D + 1) / 2) or N * (1 + 2 D) doubles.  One partial per workgroup in a fixed
  *     tree order, a second launch adds the partials in ascending order; no floating-point atomics: bitwise the same
  *     from call to call.  Synchronous.
+ *   bhmm_mvn_path_moments: the same packed moments for a hidden path: S0_i = #{t : s_t = i},
+ *     S1_i and S2_i the sums of (x_t - mu_i) and (x_t - mu_i)(x_t - mu_i)^T over the steps with s_t = i, in exactly the
+ *     layout above.  paths / path_u8 / paths_on_device as for bhmm_path_logprob: int32 or one byte per step,
+ *     concatenated like the observations, on the host or (aligned to 16 bytes) on the context's device.  The
+ *     arithmetic per step is that of ONE state whatever N is; a state that never occurs gives exact zeros; a state
+ *     outside [0, N) gives BHMM_ERR_INVALID (found before anything is indexed by it; nothing is delivered).  The order
+ *     of every sum is a function of the path's values alone (a stable sort of each tile's steps by state, one slab per
+ *     workgroup, the slabs added in ascending order; no floating-point atomics): bitwise the same from call to call
+ *     and for the same path as int32 or bytes, on the host or the device.  Useful on its own: moments of a Viterbi
+ *     path are hard-assignment training.  Needs no bhmm_mvn_emissions.  Synchronous.
+ *   bhmm_mvn_sample_paths: the Gibbs hidden-path step (bhmm_sample_paths with par0 = par1 = emis = NULL) on the
+ *     loaded emission rows, followed by bhmm_mvn_path_moments of the drawn path about means[N*D] into moments (host).
+ *     The path is read where the draw left it on the device; it is copied to the host only when paths != NULL.
+ *     paths, counts and n0 are bitwise those of bhmm_sample_paths for the same arguments.
  * Read-only options: mvn_rows_ms (device time of the last rows and shift kernels), mvn_reload_ms (host time of the
- * explicit re-load that followed), mvn_moments_ms (device time of the last two moment kernels). */
+ * explicit re-load that followed), mvn_moments_ms (device time of the last two moment kernels), mvn_path_moments_ms
+ * (device time of the last path moments and their finish). */
 int bhmm_ctx_set_observations_mvn(bhmm_ctx *ctx, const double *X, const int64_t *offsets, int K, int D,
                                   int nstates, int chunk, int obs_on_device);
 int bhmm_mvn_emissions(bhmm_ctx *ctx, const double *means, const double *covs, int cov_type);
@@ -503,6 +518,11 @@ int bhmm_mvn_fetch_scale(bhmm_ctx *ctx, double *shift_k, double *m_t);
 /* the scaled rows of the last bhmm_mvn_emissions, rows[total*N] (host; tests and diagnostics) */
 int bhmm_mvn_fetch_rows(bhmm_ctx *ctx, double *rows);
 int bhmm_mvn_moments(bhmm_ctx *ctx, const double *gamma_dev, const double *means, int cov_type, double *out);
+int bhmm_mvn_path_moments(bhmm_ctx *ctx, const void *paths, int path_u8, int paths_on_device, const double *means,
+                          int cov_type, double *out);
+int bhmm_mvn_sample_paths(bhmm_ctx *ctx, const double *A, const double *pi, const double *u, uint64_t seed,
+                          int32_t *paths, int64_t *counts, int64_t *n0, const double *means, int cov_type,
+                          double *moments);
 
 /* Gibbs hidden-path step (bayesian_sampling.py:283-331): forward pass + backward sampling
  * of every trajectory.  Uniforms come either from u (host, concatenated like obs; u[t]
@@ -721,6 +741,26 @@ int bhmm_gibbs_parameters(int kind, int n, int M, const double *path_stats, cons
 int bhmm_host_mvn_prepare(int N, int D, int cov_type, const double *covs, double *chol, double *winv, double *cst);
 int bhmm_host_mvn_mstep(int N, int D, int cov_type, const double *moments, const double *means_old,
                         double min_covar, double *means_new, double *covs_new);
+
+/* The parameter draws of one Gibbs sweep for multivariate gaussian emissions: as
+ * bhmm_gibbs_parameters, with path_stats = [C n*n | n0 n | packed moments of bhmm_mvn_path_moments about `means`],
+ * means[n*D] and covs ([n*D*D] or [n*D]) in (current) and out (new).  Per state i in ascending order, before the
+ * transition matrix, with n_i = S0_i:
+ *   n_i = 0: nothing is drawn, nothing changes;
+ *   mean: xbar = mu + S1 / n_i, mu' = xbar + L z / sqrt(n_i), z: D standard normals in order, L the Cholesky factor of
+ *     the current covariance (diag: the square roots of the variances);
+ *   scatter about the new mean: S = S2 - delta S1^T - S1 delta^T + n_i delta delta^T, delta = mu' - mu;
+ *   full, when n_i - 1 >= D and S has a Cholesky factor L_S: a Bartlett factor B (lower triangular; first
+ *     B_dd = sqrt(chi2(n_i - 1 - d)) for d = 0 .. D-1, then the entries below the diagonal as standard normals,
+ *     row-major), Sigma' = (L_S B^-T)(L_S B^-T)^T: inverse Wishart with n_i - 1 degrees of freedom and scale S, always
+ *     symmetric positive definite.  Otherwise the covariance stays and info[1] counts the state;
+ *   diag, when n_i > 1: sigma2_d = S_dd / chi2(n_i - 1), one chi-square per dimension in order.
+ * At D = 1 both types consume the variates of the gaussian kind (gaussian.py:303-318) in its order.  info: optional
+ * int32[2]: 64-bit draws consumed, states whose full covariance was kept.  BHMM_ERR_INVALID: bad shapes, cov_type or
+ * NULL; BHMM_ERR_SIGMA: a current covariance is not positive definite. */
+int bhmm_gibbs_parameters_mvn(int n, int D, int cov_type, const double *path_stats, const double *prior_C,
+                              const double *prior_n0, int reversible, int stationary, int64_t nsteps, uint64_t seed,
+                              uint64_t sweep, double *T, double *p0, double *means, double *covs, int32_t *info);
 
 /* building blocks of the two calls above, exported for the parity / property tests:
  * component label per state (sets numbered by decreasing size, _tmatrix_disconnected.py:28-43) */
