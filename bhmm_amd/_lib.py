@@ -68,6 +68,8 @@ SIGNATURES = {
                                           ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
     "bhmm_logpdf_mvn": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_double_p,
                                        c_double_p, ctypes.c_int]),
+    "bhmm_logpdf_gmm": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       c_double_p, c_double_p, c_double_p, ctypes.c_int]),
     "bhmm_update_pout": (ctypes.c_int, [c_double_p, c_int32_p, c_double_p, ctypes.c_int64,
                                         ctypes.c_int, ctypes.c_int]),
     "bhmm_ctx_create": (ctypes.c_int, [ctypes.POINTER(c_void_p), ctypes.c_int, c_void_p]),
@@ -120,6 +122,10 @@ SIGNATURES = {
                                              c_double_p]),
     "bhmm_mvn_sample_paths": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, ctypes.c_uint64, c_int32_p,
                                              c_int64_p, c_int64_p, c_double_p, ctypes.c_int, c_double_p]),
+    "bhmm_gmm_emissions": (ctypes.c_int, [c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int,
+                                          ctypes.c_int]),
+    "bhmm_gmm_fetch_resp": (ctypes.c_int, [c_void_p, c_double_p]),
+    "bhmm_gmm_moments": (ctypes.c_int, [c_void_p, c_void_p, c_double_p, ctypes.c_int, c_double_p]),
     "bhmm_ctx_path_stats_size": (ctypes.c_int, [c_void_p]),
     "bhmm_ctx_set_stream_offsets": (ctypes.c_int, [c_void_p, c_int64_p]),
     "bhmm_sample_paths_dev": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,

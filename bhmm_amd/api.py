@@ -5,7 +5,8 @@ import numpy as np
 from .estimators.bayesian_sampling import BayesianHMMSampler
 from .estimators.maximum_likelihood import MaximumLikelihoodEstimator
 from .hmm import HMM, SampledHMM
-from .output_models import DiscreteOutputModel, GaussianOutputModel, MultivariateGaussianOutputModel
+from .output_models import (DiscreteOutputModel, GaussianMixtureOutputModel, GaussianOutputModel,
+                            MultivariateGaussianOutputModel)
 
 
 def _guess_output_type(observations):
@@ -67,6 +68,27 @@ def mvgaussian_hmm(pi, P, means, covariances, covariance_type='full'):
     return HMM(pi, P, MultivariateGaussianOutputModel(nstates, means, covariances, covariance_type=covariance_type))
 
 
+def gaussian_mixture_hmm(pi, P, weights, means, covariances, covariance_type='full'):
+    """An HMM with a mixture of M gaussians per state: weights (nstates, M), means
+    (nstates, M, D), covariances (nstates, M, D, D), or with covariance_type='diag' the variances (nstates, M, D)."""
+    nstates = len(means)
+    return HMM(pi, P, GaussianMixtureOutputModel(nstates, weights, means, covariances,
+                                                 covariance_type=covariance_type))
+
+
+def init_gaussian_mixture_hmm(observations, nstates, ncomponents, lag=1, reversible=True, covariance_type='full'):
+    """Initial model with `ncomponents` gaussian components per state for (T_k, D) observations, deterministic, numpy
+    only: the model of init_mvgaussian_hmm and its hard labels, then inside every state the same farthest-point
+    seeding and at most 20 Lloyd iterations on that state's points; a component of fewer than D + 1 points takes the
+    state's covariance; weights are the cluster shares, floored at 1e-3 and renormalised
+    (bhmm_amd/init/mvgaussian.py)."""
+    from .init.mvgaussian import init_model_gaussian_mixture
+    hmm0 = init_model_gaussian_mixture(observations, nstates, ncomponents, lag=lag, reversible=reversible,
+                                       covariance_type=covariance_type)
+    hmm0._lag = lag
+    return hmm0
+
+
 def init_mvgaussian_hmm(observations, nstates, lag=1, reversible=True, covariance_type='full'):
     """Initial model for (T_k, D) observations, deterministic, numpy only: farthest-point seeding and at most 20
     Lloyd iterations on at most 1e5 evenly strided points, mean and covariance of every cluster, and a transition
@@ -100,8 +122,8 @@ def init_discrete_hmm(observations, nstates, lag=1, reversible=True, stationary=
     return hmm0
 
 
-def init_hmm(observations, nstates, lag=1, output=None, reversible=True):
-    """bhmm/api.py:161-199."""
+def init_hmm(observations, nstates, lag=1, output=None, reversible=True, ncomponents=None):
+    """bhmm/api.py:161-199.  output='gaussian_mixture' (never guessed) needs ncomponents."""
     if output is None:
         output = _guess_output_type(observations)
     if output == 'discrete':
@@ -110,6 +132,10 @@ def init_hmm(observations, nstates, lag=1, output=None, reversible=True):
         return init_gaussian_hmm(observations, nstates, lag=lag, reversible=reversible)
     if output == 'mvgaussian':
         return init_mvgaussian_hmm(observations, nstates, lag=lag, reversible=reversible)
+    if output == 'gaussian_mixture':
+        if ncomponents is None:
+            raise ValueError("output='gaussian_mixture' needs ncomponents")
+        return init_gaussian_mixture_hmm(observations, nstates, ncomponents, lag=lag, reversible=reversible)
     raise NotImplementedError('output model type ' + str(output) + ' not yet implemented.')
 
 
@@ -138,6 +164,8 @@ def bayesian_hmm(observations, estimated_hmm, nsample=100, reversible=True, stat
     if estimated_hmm.output_model.model_type == 'mvgaussian':
         raise NotImplementedError('multivariate gaussian emissions are sampled by bayesian_mvgaussian_hmm, '
                                   'not by bayesian_hmm yet')
+    if estimated_hmm.output_model.model_type == 'gaussian_mixture':
+        raise NotImplementedError('there is no Gibbs sampler for gaussian-mixture emissions yet')
     sampler = BayesianHMMSampler(observations, estimated_hmm.nstates, initial_model=estimated_hmm,
                                  reversible=reversible, stationary=stationary,
                                  transition_matrix_sampling_steps=1000, p0_prior=p0_prior,
@@ -159,6 +187,8 @@ def bayesian_mvgaussian_hmm(observations, estimated_hmm, nsample=100, reversible
     covariances_std, covariances_conf ... summarise the sampled emission parameters.  Sampled models are not
     relabelled (label switching is the user's to watch, as in the reference).  engine_kwargs: device, seed (of the
     chain; one from numpy's global generator if not given), native_parameters."""
+    if estimated_hmm.output_model.model_type == 'gaussian_mixture':
+        raise NotImplementedError('there is no Gibbs sampler for gaussian-mixture emissions yet')
     if estimated_hmm.output_model.model_type != 'mvgaussian':
         raise ValueError("bayesian_mvgaussian_hmm takes a model with multivariate gaussian emissions, not %r"
                          % (estimated_hmm.output_model.model_type,))
@@ -174,8 +204,11 @@ def bayesian_mvgaussian_hmm(observations, estimated_hmm, nsample=100, reversible
 
 
 def _engine_for(output, device):
-    """The engine of an output type: multivariate gaussian models run on an MvnEngine."""
-    from .engine import Engine, MvnEngine
+    """The engine of an output type: multivariate gaussian models run on an MvnEngine, gaussian mixtures on a
+    GmmEngine."""
+    from .engine import Engine, GmmEngine, MvnEngine
+    if output == 'gaussian_mixture':
+        return GmmEngine(device)
     return MvnEngine(device) if output == 'mvgaussian' else Engine(device)
 
 

@@ -589,6 +589,28 @@ struct bhmm_ctx {
         }
     } mvn;
 
+    // gaussian-mixture emissions (gmm_api.hip), on the observations of the mvn block: rows, m,
+    // shift and the table are that block's; here the (total, n M) buffer that holds the log responsibilities of the
+    // last bhmm_gmm_emissions with want_resp and, after bhmm_gmm_moments, the weights the moments were taken with
+    struct GmmBufs {
+        int M = 0;             // components per state of the last bhmm_gmm_emissions (0: the rows are not a mixture's)
+        bool resp_log = false; // resp holds log responsibilities of the loaded rows
+        bool resp_any = false; // ... or the weights made from them (bhmm_gmm_fetch_resp)
+        bhmm::DevBuf<double> resp;
+        float weights_ms = 0.f; // read-only option gmm_weights_ms: device time of the last k_gmm_weights
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        GmmBufs() = default;
+        GmmBufs(const GmmBufs &) = delete;
+        GmmBufs &operator=(const GmmBufs &) = delete;
+        ~GmmBufs()
+        {
+            for (hipEvent_t e : ev)
+                if (e)
+                    (void)hipEventDestroy(e);
+        }
+        void forget() { M = 0, resp_log = resp_any = false; }
+    } gmm;
+
     // ---- pinned host buffers ----
     unsigned int *h_specres = nullptr; // pinned
     double *h_small = nullptr;         // pinned, 64 KB: small results of the path calls (one copy per call)

@@ -2,6 +2,8 @@
 // bhmm_mvn_fetch_scale, bhmm_mvn_fetch_rows, bhmm_mvn_moments, bhmm_mvn_path_moments, bhmm_mvn_sample_paths,
 // bhmm_logpdf_mvn): kernels in mvn_kernels.hpp, the factorisation on the host (host::mvn_prepare, host_model.cpp);
 // DESIGN.md sections 23 and 24.
+// The checks of shapes and parameters, the launcher of the moment kernels for any column count and the shift launch
+// are declared in mvn_host.hpp: gmm_api.hip (mixtures per state) calls them too.
 //
 // The recursions know nothing of this kind.  bhmm_mvn_emissions turns the observations kept in c->mvn.X into scaled
 // emission rows in c->mvn.rows and hands those to bhmm_ctx_set_observations as BHMM_EMIT_EXPLICIT observations on the
@@ -18,14 +20,14 @@
 #include "host_internal.hpp"
 #include "host_model.hpp"
 #include "launch.hpp"
+#include "mvn_host.hpp"
 #include "mvn_kernels.hpp"
 
 namespace bhmm {
-namespace {
 
 using namespace mvn;
 
-int shape_ok(const char *who, int n, int D, int cov_type)
+int mvn_shape_ok(const char *who, int n, int D, int cov_type)
 {
     if (n < 1 || n > 4096)
         return invalid_arg(std::string(who) + ": 1..4096 hidden states are supported");
@@ -36,9 +38,8 @@ int shape_ok(const char *who, int n, int D, int cov_type)
     return BHMM_OK;
 }
 
-// [mu | W | c] of the parameters, validated; BHMM_ERR_INVALID / BHMM_ERR_SIGMA
-int make_table(const char *who, int n, int D, int cov_type, const double *means, const double *covs,
-               std::vector<double> &tab)
+int mvn_make_table(const char *who, int n, int D, int cov_type, const double *means, const double *covs,
+                   std::vector<double> &tab)
 {
     for (size_t e = 0; e < (size_t)n * D; ++e)
         if (!std::isfinite(means[e]))
@@ -49,6 +50,52 @@ int make_table(const char *who, int n, int D, int cov_type, const double *means,
     return host::mvn_prepare(n, D, cov_type, covs, nullptr, tab.data() + (size_t)n * D,
                              tab.data() + (size_t)n * D + (size_t)n * fs);
 }
+
+hipError_t mvn_launch_shift(bhmm_ctx *c)
+{
+    auto &b = c->mvn;
+    return launch(k_mvn_shift, dim3((unsigned)std::min(b.K, 65535)), dim3(SHIFT_THREADS), 0, c->stream, b.m.p,
+                  b.d_offsets.p, b.K, b.shift.p);
+}
+
+// (c->mvn.tab: the table of the last emissions is not needed any more once the rows are made)
+int mvn_run_moments(bhmm_ctx *c, const double *gamma_dev, int ncols, const double *means, int cov_type, double *out)
+{
+    auto &b = c->mvn;
+    int rc;
+    const bool diag = cov_type == BHMM_COV_DIAG;
+    const int D = b.D, n = ncols;
+    const int64_t ms = (int64_t)moment_stride(D, diag), E = (int64_t)n * ms;
+    const int epb = (int)std::min<int64_t>(E, MOM_THREADS);
+    const int64_t gy = (E + epb - 1) / epb;
+    const int nsi_max = (int)std::min<int64_t>(n, (epb - 1) / ms + 2);
+    const int64_t tiles = (b.total + MOM_TILE - 1) / MOM_TILE;
+    const int G = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, MOM_MAX_GROUPS / gy));
+    const int64_t span = (b.total + G - 1) / G;
+    const size_t lds = ((size_t)MOM_TILE * (D + nsi_max) + MOM_THREADS) * sizeof(double);
+    BHMM_HIP(hipSetDevice(c->device));
+    if ((rc = b.part.ensure((size_t)G * E)) || (rc = b.out.ensure((size_t)E)) || (rc = b.tab.ensure((size_t)n * D)))
+        return rc;
+    BHMM_HIP(hipMemcpyAsync(b.tab.p, means, (size_t)n * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const dim3 grid((unsigned)G, (unsigned)gy), block(MOM_THREADS);
+    for (hipEvent_t &e : b.ev)
+        if (!e)
+            BHMM_HIP(hipEventCreate(&e));
+    BHMM_HIP(hipEventRecord(b.ev[2], c->stream));
+    BHMM_HIP(diag ? launch(k_mvn_moments<true>, grid, block, lds, c->stream, b.X.p, gamma_dev, b.total, D, n, b.tab.p,
+                           span, epb, nsi_max, b.part.p)
+                  : launch(k_mvn_moments<false>, grid, block, lds, c->stream, b.X.p, gamma_dev, b.total, D, n, b.tab.p,
+                           span, epb, nsi_max, b.part.p));
+    BHMM_HIP(launch(k_mvn_moments_finish, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, c->stream, b.part.p, G, E,
+                    b.out.p));
+    BHMM_HIP(hipEventRecord(b.ev[3], c->stream));
+    BHMM_HIP(hipMemcpyAsync(out, b.out.p, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream));
+    (void)hipEventElapsedTime(&b.moments_ms, b.ev[2], b.ev[3]);
+    return BHMM_OK;
+}
+
+namespace {
 
 template <bool DIAG>
 hipError_t launch_rows(hipStream_t stream, const double *X, int64_t total, int D, int n, const double *tab,
@@ -79,28 +126,6 @@ int run_rows(hipStream_t stream, const double *X, int64_t total, int D, int n, i
                                        : launch_rows<false>(stream, X, total, D, n, tab, rows, m, logp));
     return BHMM_OK;
 }
-
-struct Tmp { // device allocations of one level-1 call
-    std::vector<void *> ptrs;
-    ~Tmp()
-    {
-        for (void *p : ptrs)
-            (void)hipFree(p);
-    }
-    int alloc(double **out, size_t count)
-    {
-        void *p = nullptr;
-        const hipError_t e = hipMalloc(&p, count * sizeof(double));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("hipMalloc of " + std::to_string(count * sizeof(double)) + " bytes failed");
-            return BHMM_ERR_NO_MEM;
-        }
-        ptrs.push_back(p);
-        *out = static_cast<double *>(p);
-        return BHMM_OK;
-    }
-};
 
 // Packed moments of the hidden path at path_dev (device; int32 or one byte per step) about means (host) into out
 // (host): k_mvn_path_moments, one slab per workgroup, then k_mvn_moments_finish over the slabs.  A state outside
@@ -164,7 +189,7 @@ int bhmm_ctx_set_observations_mvn(bhmm_ctx *c, const double *X, const int64_t *o
 {
     if (!c || !X || !offsets || K < 1)
         return invalid_arg("bhmm_ctx_set_observations_mvn: bad context / X / offsets / K");
-    if (int rc = shape_ok("bhmm_ctx_set_observations_mvn", nstates, D, BHMM_COV_FULL))
+    if (int rc = mvn_shape_ok("bhmm_ctx_set_observations_mvn", nstates, D, BHMM_COV_FULL))
         return rc;
     for (int k = 0; k < K; ++k)
         if (offsets[k + 1] < offsets[k])
@@ -176,6 +201,7 @@ int bhmm_ctx_set_observations_mvn(bhmm_ctx *c, const double *X, const int64_t *o
     BHMM_HIP(hipStreamSynchronize(c->stream));
     auto &b = c->mvn;
     b.active = b.rows_valid = false;
+    c->gmm.forget();
     c->kind = -1; // (whatever was loaded before is not what the caller means any more: no model call until the
                   // first bhmm_mvn_emissions)
     int rc;
@@ -207,13 +233,14 @@ int bhmm_mvn_emissions(bhmm_ctx *c, const double *means, const double *covs, int
         return invalid_arg("bhmm_mvn_emissions: means / covs == NULL");
     auto &b = c->mvn;
     int rc;
-    if ((rc = shape_ok("bhmm_mvn_emissions", b.n, b.D, cov_type)))
+    if ((rc = mvn_shape_ok("bhmm_mvn_emissions", b.n, b.D, cov_type)))
         return rc;
     std::vector<double> tab;
-    if ((rc = make_table("bhmm_mvn_emissions", b.n, b.D, cov_type, means, covs, tab)))
+    if ((rc = mvn_make_table("bhmm_mvn_emissions", b.n, b.D, cov_type, means, covs, tab)))
         return rc;
     BHMM_HIP(hipSetDevice(c->device));
     b.rows_valid = false;
+    c->gmm.forget(); // (the rows are not a mixture's any more)
     if ((rc = b.tab.ensure(tab.size())))
         return rc;
     BHMM_HIP(hipMemcpyAsync(b.tab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -223,8 +250,7 @@ int bhmm_mvn_emissions(bhmm_ctx *c, const double *means, const double *covs, int
     BHMM_HIP(hipEventRecord(b.ev[0], c->stream));
     if ((rc = run_rows(c->stream, b.X.p, b.total, b.D, b.n, cov_type, b.tab.p, b.rows.p, b.m.p, nullptr)))
         return rc;
-    BHMM_HIP(launch(k_mvn_shift, dim3((unsigned)std::min(b.K, 65535)), dim3(SHIFT_THREADS), 0, c->stream, b.m.p,
-                    b.d_offsets.p, b.K, b.shift.p));
+    BHMM_HIP(mvn_launch_shift(c));
     BHMM_HIP(hipEventRecord(b.ev[1], c->stream));
     BHMM_HIP(hipStreamSynchronize(c->stream)); // (tab is a temporary; the re-load below waits for the stream anyway)
     (void)hipEventElapsedTime(&b.rows_ms, b.ev[0], b.ev[1]);
@@ -274,39 +300,9 @@ int bhmm_mvn_moments(bhmm_ctx *c, const double *gamma_dev, const double *means, 
         return invalid_arg("bhmm_mvn_moments: gamma_dev / means / out == NULL");
     auto &b = c->mvn;
     int rc;
-    if ((rc = shape_ok("bhmm_mvn_moments", b.n, b.D, cov_type)))
+    if ((rc = mvn_shape_ok("bhmm_mvn_moments", b.n, b.D, cov_type)))
         return rc;
-    const bool diag = cov_type == BHMM_COV_DIAG;
-    const int D = b.D, n = b.n;
-    const int64_t ms = (int64_t)moment_stride(D, diag), E = (int64_t)n * ms;
-    const int epb = (int)std::min<int64_t>(E, MOM_THREADS);
-    const int64_t gy = (E + epb - 1) / epb;
-    const int nsi_max = (int)std::min<int64_t>(n, (epb - 1) / ms + 2);
-    const int64_t tiles = (b.total + MOM_TILE - 1) / MOM_TILE;
-    const int G = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, MOM_MAX_GROUPS / gy));
-    const int64_t span = (b.total + G - 1) / G;
-    const size_t lds = ((size_t)MOM_TILE * (D + nsi_max) + MOM_THREADS) * sizeof(double);
-    BHMM_HIP(hipSetDevice(c->device));
-    if ((rc = b.part.ensure((size_t)G * E)) || (rc = b.out.ensure((size_t)E)) || (rc = b.tab.ensure((size_t)n * D)))
-        return rc;
-    // (the table of the last bhmm_mvn_emissions is not needed any more: the rows are made)
-    BHMM_HIP(hipMemcpyAsync(b.tab.p, means, (size_t)n * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const dim3 grid((unsigned)G, (unsigned)gy), block(MOM_THREADS);
-    for (hipEvent_t &e : b.ev)
-        if (!e)
-            BHMM_HIP(hipEventCreate(&e));
-    BHMM_HIP(hipEventRecord(b.ev[2], c->stream));
-    BHMM_HIP(diag ? launch(k_mvn_moments<true>, grid, block, lds, c->stream, b.X.p, gamma_dev, b.total, D, n, b.tab.p,
-                           span, epb, nsi_max, b.part.p)
-                  : launch(k_mvn_moments<false>, grid, block, lds, c->stream, b.X.p, gamma_dev, b.total, D, n, b.tab.p,
-                           span, epb, nsi_max, b.part.p));
-    BHMM_HIP(launch(k_mvn_moments_finish, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, c->stream, b.part.p, G, E,
-                    b.out.p));
-    BHMM_HIP(hipEventRecord(b.ev[3], c->stream));
-    BHMM_HIP(hipMemcpyAsync(out, b.out.p, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    BHMM_HIP(hipStreamSynchronize(c->stream));
-    (void)hipEventElapsedTime(&b.moments_ms, b.ev[2], b.ev[3]);
-    return BHMM_OK;
+    return mvn_run_moments(c, gamma_dev, b.n, means, cov_type, out);
 }
 
 int bhmm_mvn_path_moments(bhmm_ctx *c, const void *paths, int path_u8, int paths_on_device, const double *means,
@@ -317,7 +313,7 @@ int bhmm_mvn_path_moments(bhmm_ctx *c, const void *paths, int path_u8, int paths
     if (!paths || !means || !out)
         return invalid_arg("bhmm_mvn_path_moments: paths / means / out == NULL");
     auto &b = c->mvn;
-    if (int rc = shape_ok("bhmm_mvn_path_moments", b.n, b.D, cov_type))
+    if (int rc = mvn_shape_ok("bhmm_mvn_path_moments", b.n, b.D, cov_type))
         return rc;
     if (path_u8 && b.n > 256) // (every byte is a state then; the int32 form holds the others)
         return invalid_arg("bhmm_mvn_path_moments: one byte per step holds at most 256 states (use the int32 form)");
@@ -343,7 +339,7 @@ int bhmm_mvn_sample_paths(bhmm_ctx *c, const double *A, const double *pi, const 
     if (!A || !pi || !means || !moments)
         return invalid_arg("bhmm_mvn_sample_paths: A / pi / means / moments == NULL");
     auto &b = c->mvn;
-    if (int rc = shape_ok("bhmm_mvn_sample_paths", b.n, b.D, cov_type))
+    if (int rc = mvn_shape_ok("bhmm_mvn_sample_paths", b.n, b.D, cov_type))
         return rc;
     if (c->n != b.n || c->total != b.total)
         return invalid_arg("bhmm_mvn_sample_paths: the loaded emission rows are not those of the multivariate set");
@@ -364,12 +360,12 @@ int bhmm_logpdf_mvn(double *logp, const double *X, int64_t T, int D, int N, cons
     if (!logp || !X || !means || !covs || T < 1)
         return invalid_arg("bhmm_logpdf_mvn: NULL argument or empty problem");
     int rc;
-    if ((rc = shape_ok("bhmm_logpdf_mvn", N, D, cov_type)))
+    if ((rc = mvn_shape_ok("bhmm_logpdf_mvn", N, D, cov_type)))
         return rc;
     std::vector<double> tab;
-    if ((rc = make_table("bhmm_logpdf_mvn", N, D, cov_type, means, covs, tab)))
+    if ((rc = mvn_make_table("bhmm_logpdf_mvn", N, D, cov_type, means, covs, tab)))
         return rc;
-    Tmp tmp;
+    MvnTmp tmp;
     double *dX, *dtab, *dl;
     if ((rc = tmp.alloc(&dX, (size_t)T * D)) || (rc = tmp.alloc(&dtab, tab.size())) || (rc = tmp.alloc(&dl, (size_t)T * N)))
         return rc;

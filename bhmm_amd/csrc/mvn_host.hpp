@@ -1,0 +1,48 @@
+// mvn_host.hpp -- what mvn_api.hip defines and gmm_api.hip also calls: the checks of shapes and parameters, the
+// launcher of the moment kernels for any column count, the device temporaries of a level-1 call.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "host_internal.hpp"
+
+namespace bhmm {
+
+// n table entries (states, or components of all states), D dimensions, the covariance type; BHMM_ERR_INVALID
+int mvn_shape_ok(const char *who, int n, int D, int cov_type);
+// [mu | W | c] of n entries, validated, in tab[0 .. n * (D + factor size + 1)); BHMM_ERR_INVALID / BHMM_ERR_SIGMA
+int mvn_make_table(const char *who, int n, int D, int cov_type, const double *means, const double *covs,
+                   std::vector<double> &tab);
+// k_mvn_moments + k_mvn_moments_finish over the observations of c->mvn with weights gamma_dev [total][ncols] (device)
+// about means [ncols * D] (host) into out [ncols * moment stride] (host); device time in c->mvn.moments_ms.
+// Synchronous.
+int mvn_run_moments(bhmm_ctx *c, const double *gamma_dev, int ncols, const double *means, int cov_type, double *out);
+
+// k_mvn_shift on the stream: c->mvn.shift[k] = sum of c->mvn.m over trajectory k
+hipError_t mvn_launch_shift(bhmm_ctx *c);
+
+struct MvnTmp { // device allocations of one level-1 call
+    std::vector<void *> ptrs;
+    ~MvnTmp()
+    {
+        for (void *p : ptrs)
+            (void)hipFree(p);
+    }
+    int alloc(double **out, size_t count)
+    {
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, count * sizeof(double));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("hipMalloc of " + std::to_string(count * sizeof(double)) + " bytes failed");
+            return BHMM_ERR_NO_MEM;
+        }
+        ptrs.push_back(p);
+        *out = static_cast<double *>(p);
+        return BHMM_OK;
+    }
+};
+
+} // namespace bhmm

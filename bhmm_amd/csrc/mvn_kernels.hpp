@@ -24,6 +24,8 @@
 // time go through LDS so that rows (and l) are written in whole cache lines by the workgroup, not one state per lane
 // and instruction.  With more than ROWS_NB states the raw l of a block of states is parked in the row itself and the
 // workgroup rescales its own rows once every block is done and m_t is known.
+// The shape constants of the rows kernel and the arithmetic of one log-density (mvn::log_density) are in
+// mvn_density.hpp, which k_gmm_rows (gmm_kernels.hpp) shares.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -32,25 +34,18 @@
 
 #include <algorithm>
 
+#include "mvn_density.hpp"
+
 namespace bhmm {
 namespace mvn {
 
-constexpr int ROWS_THREADS = 256; // steps per workgroup of k_mvn_rows
-constexpr int ROWS_NB = 16;       // states whose l pass through LDS at a time (ROWS_NB * ROWS_THREADS doubles)
-constexpr int X_PIECE = 3968;     // doubles of a tile's observations staged at a time: X_PIECE * 33 / 32 <= ROWS_NB * ROWS_THREADS
-static_assert(X_PIECE + X_PIECE / 32 <= ROWS_NB * ROWS_THREADS, "the skewed piece must fit s_l");
 constexpr int SHIFT_THREADS = 256;
 constexpr int MOM_THREADS = 256;  // outputs per workgroup of k_mvn_moments
 constexpr int MOM_TILE = 128;     // steps it stages in LDS at a time
 constexpr int MOM_MAX_GROUPS = 2048; // partials per output at most
 
-// doubles of one state's whitening table
-__host__ __device__ inline size_t factor_size(int D, bool diag) { return diag ? (size_t)D : (size_t)D * (D + 1) / 2; }
 // doubles of one state's packed moments: S0 | S1 [D] | S2
 __host__ __device__ inline size_t moment_stride(int D, bool diag) { return 1 + (size_t)D + factor_size(D, diag); }
-
-// NaN stays; a NaN l makes m NaN
-__device__ inline double nan_max(double m, double l) { return m != m ? m : ((l > m || l != l) ? l : m); }
 
 // tab: [mu n*D | W n*factor_size | c n].  rows [total][n] and m [total], or both nullptr (only l is wanted); logp
 // [total][n] or nullptr.
@@ -99,30 +94,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void k_mvn_rows(const double *__restr
         const int nb = n - i0 < ROWS_NB ? n - i0 : ROWS_NB;
         for (int j = 0; j < nb; ++j) {
             const int i = i0 + j;
-            const double *mui = mu + (size_t)i * D;
-            const double *Wi = W + (size_t)i * fs;
-            double d[DMAX];
-#pragma unroll
-            for (int a = 0; a < DMAX; ++a)
-                d[a] = a < D ? x[a] - mui[a] : 0.0;
-            double q = 0.0;
-#pragma unroll
-            for (int a = 0; a < DMAX; ++a) {
-                if (a < D) { // (uniform)
-                    double z;
-                    if constexpr (DIAG) {
-                        z = Wi[a] * d[a];
-                    } else {
-                        const double *Wa = Wi + a * (a + 1) / 2;
-                        z = 0.0;
-#pragma unroll
-                        for (int b = 0; b <= a; ++b)
-                            z = fma(Wa[b], d[b], z);
-                    }
-                    q = fma(z, z, q);
-                }
-            }
-            const double l = fma(-0.5, q, cst[i]);
+            const double l = log_density<DMAX, DIAG>(x, D, mu + (size_t)i * D, W + (size_t)i * fs, cst[i]);
             s_l[j * ROWS_THREADS + threadIdx.x] = l;
             m = nan_max(m, l);
         }

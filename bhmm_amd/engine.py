@@ -39,6 +39,14 @@ class EStepResult(object):
             size = n * moment_stride(dimension, covariance_type)
             self.moments = packed[o:o + size].copy(); o += size
             self.S0, self.S1, self.S2 = unpack_moments(self.moments, n, dimension, covariance_type)
+        # gaussian mixture (M components per state): the per-component moments of bhmm_gmm_moments -- S0 (n, M), S1
+        # (n, M, D), S2 (n, M, D, D) symmetric or (n, M, D)
+        if kind == 'gaussian_mixture':
+            from .output_models.gaussian_mixture import unpack_component_moments
+            from .output_models.mvgaussian import moment_stride
+            size = n * M * moment_stride(dimension, covariance_type)
+            self.moments = packed[o:o + size].copy(); o += size
+            self.S0, self.S1, self.S2 = unpack_component_moments(self.moments, n, M, dimension, covariance_type)
 
 
 class PathRuns(object):
@@ -1203,6 +1211,160 @@ class MvnEngine(Engine):
     def sample_paths(self, A, pi, par0=None, par1=None, u=None, seed=0, want_paths=True):
         self.emissions(par0, par1)
         return Engine.sample_paths(self, A, pi, u=u, seed=seed, want_paths=want_paths)
+
+
+class GmmEngine(MvnEngine):
+    """Engine for gaussian-mixture emissions per state (kind 'gaussian_mixture'): observations
+    as for MvnEngine, a model is (A, pi, par0, par1) with par0 (n, M, 1 + D) -- column 0 the mixture weight, the rest
+    the mean of component (i, c) -- and par1 (n, M, D, D) covariances or (n, M, D) variances.  Everything runs as in
+    MvnEngine on the explicit rows of the mixture densities (bhmm_gmm_emissions); an E-step makes those rows with the
+    log responsibilities of the components, runs ONE pass of the recursions that leaves gamma on the device, and
+    takes the per-component moments from gamma and the responsibilities (bhmm_gmm_moments)."""
+
+    def __init__(self, device=0, stream=None):
+        MvnEngine.__init__(self, device, stream)
+        self.ncomponents = 0       # of the last emissions
+        self._resp = False         # the context holds log responsibilities of the loaded rows
+
+    def _set(self, ptr, off, nstates, D, chunk, on_device):
+        MvnEngine._set(self, ptr, off, nstates, D, chunk, on_device)
+        self.kind = 'gaussian_mixture'
+        self._resp = False
+
+    def set_observations(self, kind, observations, nstates, nsymbols=0, chunk=0):
+        """observations: list of (T_k, D) float arrays, 1 <= D <= 64."""
+        if kind != 'gaussian_mixture':
+            raise ValueError("a GmmEngine holds observations of kind 'gaussian_mixture', not %r" % (kind,))
+        MvnEngine.set_observations(self, 'mvgaussian', observations, nstates, chunk=chunk)
+
+    def set_observations_device(self, kind, dev_ptr, offsets, nstates, nsymbols=0, chunk=0, dimension=None):
+        if kind != 'gaussian_mixture':
+            raise ValueError("a GmmEngine holds observations of kind 'gaussian_mixture', not %r" % (kind,))
+        MvnEngine.set_observations_device(self, 'mvgaussian', dev_ptr, offsets, nstates, chunk=chunk,
+                                          dimension=dimension)
+
+    def set_observations_lagged(self, *args, **kwargs):
+        raise NotImplementedError("lagged views are cut on the host for multivariate observations")
+
+    @property
+    def stats_size(self):
+        """The explicit kind's vector followed by the n M moment blocks of the last covariance type (full before
+        any)."""
+        from .output_models.mvgaussian import moment_stride
+        return self._ctx_stats_size() + self.nstates * max(self.ncomponents, 1) * \
+            moment_stride(self.dimension, self._cov_last or 'full')
+
+    def _params(self, par0, par1):
+        """(par0 (n, M, 1 + D), covariances, covariance type) of one model, shapes checked."""
+        if self.dimension == 0:
+            raise ValueError("no observations loaded")
+        if par0 is None or par1 is None:
+            raise ValueError("gaussian-mixture emissions need par0 = [weights | means] and covariances")
+        n, D = self.nstates, self.dimension
+        p0, cov = _lib.f64(par0), _lib.f64(par1)
+        if p0.ndim != 3 or p0.shape[0] != n or p0.shape[1] < 1 or p0.shape[2] != 1 + D:
+            raise ValueError("par0 must be (%d, M, %d): the weight and the mean of every component, not %r"
+                             % (n, 1 + D, p0.shape))
+        M = p0.shape[1]
+        if n * M > 4096:
+            raise ValueError("at most 4096 components in all are supported, not %d x %d" % (n, M))
+        if cov.shape == (n, M, D, D):
+            return p0, cov, 'full'
+        if cov.shape == (n, M, D):
+            return p0, cov, 'diag'
+        raise ValueError("covariances must be (%d, %d, %d, %d) or (%d, %d, %d), not %r"
+                         % (n, M, D, D, n, M, D, cov.shape))
+
+    def emissions(self, par0, par1, force=False, want_resp=False):
+        """Make the mixture rows of (par0, par1) the context's observations, unless the loaded ones were made from
+        the same parameters (force: make them anyway; want_resp: with the log responsibilities of the components,
+        which are made again when the loaded rows came without them or a moments call has used them up).  Returns
+        the covariance type."""
+        p0, cov, ctype = self._params(par0, par1)
+        ld = self._loaded
+        if not force and ld is not None and ld[0].shape == p0.shape and ld[1].shape == cov.shape \
+                and np.array_equal(ld[0], p0) and np.array_equal(ld[1], cov) and (self._resp or not want_resp):
+            return ctype
+        self._loaded = self._shift = self._m_t = self._moments = None   # (the re-load ends the last E-step too)
+        self._resp = False
+        M = p0.shape[1]
+        w = np.ascontiguousarray(p0[:, :, 0])
+        mu = np.ascontiguousarray(p0[:, :, 1:])
+        _lib.check(self._L.bhmm_gmm_emissions(self._h, int(M), _lib.dp(w), _lib.dp(mu), _lib.dp(cov),
+                                              _lib.COV_FULL if ctype == 'full' else _lib.COV_DIAG,
+                                              1 if want_resp else 0))
+        self._stage = None
+        self._fetch = None
+        shift = np.empty(len(self.lengths))
+        _lib.check(self._L.bhmm_mvn_fetch_scale(self._h, _lib.dp(shift), None))
+        self._shift = shift
+        self._loaded = (p0.copy(), cov.copy())
+        self.ncomponents = int(M)
+        self._resp = bool(want_resp)
+        return ctype
+
+    def responsibilities(self):
+        """The (sum T_k, n, M) buffer of the context, copied to the host (bhmm_gmm_fetch_resp; tests, diagnostics):
+        log r_t(i,c) after emissions with want_resp, the weights gamma_t(i) r_t(i,c) after `moments`."""
+        out = np.empty((int(self.offsets[-1]), self.nstates, self.ncomponents))
+        _lib.check(self._L.bhmm_gmm_fetch_resp(self._h, _lib.dp(out)))
+        return out
+
+    def moments(self, gamma_dev, means=None, covariance_type='full'):
+        """Packed per-component moments of the M-step (bhmm_gmm_moments) from posterior rows on this GPU: gamma_dev
+        is the integer device address of (sum T_k, nstates) float64 rows, or an object with data_ptr(); means
+        (n, M, D) to take them about (default: those of the loaded emissions).  Uses up the log responsibilities."""
+        from .output_models.mvgaussian import moment_stride
+        if self._loaded is None:
+            raise ValueError("no emissions made yet")
+        n, M, D = self.nstates, self.ncomponents, self.dimension
+        mu = _lib.f64(self._loaded[0][:, :, 1:] if means is None else means)
+        if mu.shape != (n, M, D):
+            raise ValueError("means must be (%d, %d, %d)" % (n, M, D))
+        mu = np.ascontiguousarray(mu)
+        ptr = gamma_dev.data_ptr() if hasattr(gamma_dev, 'data_ptr') else int(gamma_dev)
+        out = np.empty(n * M * moment_stride(D, covariance_type))
+        self._resp = False
+        _lib.check(self._L.bhmm_gmm_moments(self._h, ctypes.c_void_p(ptr), _lib.dp(mu),
+                                            _lib.COV_FULL if covariance_type == 'full' else _lib.COV_DIAG,
+                                            _lib.dp(out)))
+        return out
+
+    def path_moments(self, *args, **kwargs):
+        raise NotImplementedError("moments of a hidden path are not made for gaussian-mixture emissions")
+
+    def sample_paths_moments(self, *args, **kwargs):
+        raise NotImplementedError("the Gibbs sampler does not run on gaussian-mixture emissions")
+
+    # -- E-step --------------------------------------------------------------------------
+    def estep_launch(self, A, pi, par0=None, par1=None, stats_dev=None, store_gamma=False, single=False):
+        """One E-step: mixture rows with log responsibilities, ONE pass of the recursions that leaves the posterior
+        rows on the device (Engine.posterior_marginals), the per-component moments from both.  Synchronous."""
+        if stats_dev is not None:
+            raise NotImplementedError("gaussian-mixture E-steps keep their statistics in the context")
+        if single:
+            raise NotImplementedError("gaussian-mixture E-steps run in float64")
+        ctype = self.emissions(par0, par1, want_resp=True)
+        import torch
+        total = int(self.offsets[-1])
+        g = self._gamma_dev
+        if g is None or g.numel() != total * self.nstates or g.device.index != self.device:
+            g = self._gamma_dev = torch.empty(total * self.nstates, dtype=torch.float64,
+                                              device='cuda:%d' % self.device)
+        Engine.posterior_marginals(self, A, pi, out=g.data_ptr())
+        self._moments = self.moments(g.data_ptr(), None, ctype)
+        self._cov_last = ctype
+
+    def estep_fetch(self):
+        if self._moments is None:
+            raise ValueError("no E-step has run on these observations")
+        res = Engine.estep_fetch(self)
+        return EStepResult('gaussian_mixture', self.nstates, self.ncomponents, self._shifted(res.packed),
+                           res.logL_k + self._shift, self.dimension, self._cov_last)
+
+    def unpack(self, packed, logL_k=None):
+        return EStepResult('gaussian_mixture', self.nstates, self.ncomponents, np.asarray(packed), logL_k,
+                           self.dimension, self._cov_last or 'full')
 
 
 def stack_models(kind, nstates, nsymbols, models):

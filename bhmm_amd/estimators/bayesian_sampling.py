@@ -49,6 +49,9 @@ class BayesianHMMSampler(object):
         if len(observations) == 0:
             raise Exception("No observations were provided.")
         kind = initial_model.output_model.model_type if initial_model else output
+        if kind == 'gaussian_mixture':
+            # (the Gibbs sampler for mixtures per state is not built)
+            raise NotImplementedError('there is no Gibbs sampler for gaussian-mixture emissions yet')
         if kind == 'mvgaussian' and process_group is not None:
             # multivariate gaussian emissions: single process, as for the estimator
             raise NotImplementedError('multivariate gaussian emissions do not run over a process_group yet')

@@ -30,6 +30,14 @@ def _mvn_engine_factory(device):
     return MvnEngine(device)
 
 
+def _gmm_engine_factory(device):
+    from ..engine import GmmEngine
+    return GmmEngine(device)
+
+
+_MULTIVARIATE = ('mvgaussian', 'gaussian_mixture')   # kinds on (T, D) observations: the same branches throughout
+
+
 def default_device(comm):
     """One process per GPU: rank r drives GPU r (modulo the GPUs visible to this process).
     Counting devices does not initialise the GPU."""
@@ -66,7 +74,7 @@ def _load_observations(engine, kind, given, copied, mine, comm, nstates, nsymbol
     the views are cut on the GPU (bhmm_ctx_set_observations_lagged) -- single process only, a
     sharded run uploads each rank's own pieces."""
     views = getattr(given, 'views', None)
-    if (views is not None and not comm.active and kind != 'mvgaussian' and hasattr(engine, 'set_observations_lagged')
+    if (views is not None and not comm.active and kind not in _MULTIVARIATE and hasattr(engine, 'set_observations_lagged')
             and len(views) == len(copied) and _views_intact(given)):
         engine.set_observations_lagged(kind, given.base, given.lag, views, nstates,
                                        nsymbols=nsymbols)
@@ -91,7 +99,7 @@ class MaximumLikelihoodEstimator(object):
     def __init__(self, observations, nstates, initial_model=None, output='gaussian',
                  reversible=True, stationary=False, p=None, accuracy=1e-3, maxit=1000,
                  maxit_P=100000, device=None, process_group=None, store_gamma=False,
-                 engine_factory=None, multi_start=False, estep_precision='float64'):
+                 engine_factory=None, multi_start=False, estep_precision='float64', ncomponents=None):
         # opt-in precision of the E-steps (the reference is fp64 throughout): 'float64' (default),
         # 'float32' (every E-step may run the single-precision kernels) or 'mixed' (fp32 while the
         # likelihood still climbs clearly, then fp64 to convergence; see fit()).  Not a speed option yet:
@@ -116,7 +124,7 @@ class MaximumLikelihoodEstimator(object):
             # (bhmm_amd/init/discrete.py).
             from .. import api as _api
             initial_model = _api.init_hmm(observations, nstates, output=output,
-                                          reversible=reversible)
+                                          reversible=reversible, ncomponents=ncomponents)
             if multi_start and output == 'gaussian' and nstates > 1:
                 # opt-in extension (the reference starts from init_hmm alone, :111-116): EM only
                 # finds the optimum next to its start and an E-step costs milliseconds here, so a
@@ -130,6 +138,9 @@ class MaximumLikelihoodEstimator(object):
         if self._hmm.nstates != nstates:
             raise ValueError('initial_model has %d states, nstates=%d' % (self._hmm.nstates, nstates))
         self._output = self._hmm.output_model.model_type
+        if ncomponents is not None and (self._output != 'gaussian_mixture'
+                                        or self._hmm.output_model.ncomponents != int(ncomponents)):
+            raise ValueError('ncomponents=%r does not fit the model (output type %r)' % (ncomponents, self._output))
         self._fixed_stationary_distribution = None
         self._fixed_initial_distribution = None
         if p is not None:
@@ -157,15 +168,16 @@ class MaximumLikelihoodEstimator(object):
             device = default_device(self._comm)
         self._device = device
         self._comm.bind_device(device)       # collectives run on the engine's GPU, not on "current"
-        if self._output == 'mvgaussian':
-            # multivariate gaussian emissions: single process, fp64 E-steps
+        if self._output in _MULTIVARIATE:
+            # multivariate gaussian and gaussian-mixture emissions (DESIGN.md sections 23, 25): single process, fp64
+            # E-steps
+            name = 'multivariate gaussian' if self._output == 'mvgaussian' else 'gaussian-mixture'
             if process_group is not None:
-                raise NotImplementedError('multivariate gaussian emissions do not run over a process_group yet')
+                raise NotImplementedError('%s emissions do not run over a process_group yet' % name)
             if estep_precision != 'float64':
-                raise NotImplementedError("multivariate gaussian E-steps run in float64 (estep_precision=%r)"
-                                          % (estep_precision,))
-        factory = engine_factory or (_mvn_engine_factory if self._output == 'mvgaussian'
-                                     else _default_engine_factory)
+                raise NotImplementedError("%s E-steps run in float64 (estep_precision=%r)" % (name, estep_precision))
+        factory = engine_factory or {'mvgaussian': _mvn_engine_factory, 'gaussian_mixture': _gmm_engine_factory
+                                     }.get(self._output, _default_engine_factory)
         self._engine = factory(device)
         M = self._hmm.output_model.nsymbols if self._output == 'discrete' else 0
         self._nsymbols = M
@@ -324,7 +336,7 @@ class MaximumLikelihoodEstimator(object):
         # kept for hidden_state_probabilities: gamma is that of the model BEFORE the following M-step
         self._estep_model = tuple(None if x is None else np.array(x, dtype=np.float64) for x in (A, pi, par0, par1))
         kw = {'single': True} if single else {}
-        if self._output == 'mvgaussian':
+        if self._output in _MULTIVARIATE:
             # emission rows, ONE pass of the recursions that leaves gamma on the device, the moments from it
             res = eng.estep(A, pi, par0, par1)
         elif not comm.active and hasattr(eng, 'estep_fetch_packed'):
@@ -391,7 +403,7 @@ class MaximumLikelihoodEstimator(object):
         transition matrix, like the reference's `self._hmm.is_reversible`."""
         om = self._hmm.output_model
         par0, par1 = om.parameters()
-        mvn = self._output == 'mvgaussian'
+        mvn = self._output in _MULTIVARIATE
         if self._mstep is None:
             from ._native import MStep
             # (multivariate gaussian: transition matrix and pi from the explicit kind's statistics, which lead the
@@ -428,7 +440,7 @@ class MaximumLikelihoodEstimator(object):
         om = self._hmm.output_model
         if self._output == 'gaussian':
             om.estimate_from_statistics(res.state_counts, res.sum_gd, res.sum_gdd)
-        elif self._output == 'mvgaussian':
+        elif self._output in _MULTIVARIATE:
             om.estimate_from_statistics(res.S0, res.S1, res.S2)
         else:
             om.estimate_from_statistics(res.symbol_counts)

@@ -86,3 +86,64 @@ def init_model_mvgaussian(observations, nstates, lag=1, reversible=True, covaria
     pi = _tmatrix.stationary_distribution(P, C=C, mincount_connectivity=1e-16)
     om = MultivariateGaussianOutputModel(nstates, means, covs, covariance_type=covariance_type)
     return HMM(pi, P, om)
+
+
+def _state_components(pts, M, state_mean, state_cov):
+    """Weights (M,), means (M, D) and covariances (M, D, D) of M components of one state's points: the farthest-point
+    seeding and Lloyd iterations of `kmeans` on them; a component of fewer than D + 1 points takes the state's
+    covariance (one without points also the state's mean); weights are the cluster shares, floored at 1e-3 and
+    renormalised."""
+    D = state_mean.shape[0]
+    means = np.tile(state_mean, (M, 1))
+    covs = np.tile(state_cov, (M, 1, 1))
+    counts = np.zeros(M)
+    if pts.shape[0] >= M:
+        centres = kmeans(pts, M)
+        centres = centres[np.argsort(centres[:, 0], kind='stable')]
+        lab = _labels(pts, centres)
+        for c in range(M):
+            sel = pts[lab == c]
+            counts[c] = sel.shape[0]
+            if sel.shape[0] == 0:
+                means[c] = centres[c]
+                continue
+            means[c] = sel.mean(axis=0)
+            if sel.shape[0] >= D + 1:
+                d = sel - means[c]
+                # (the floor of the state's covariance is in state_cov; a cluster on a line still needs one)
+                covs[c] = d.T.dot(d) / sel.shape[0] + 1e-6 * np.eye(D) * max(np.trace(state_cov) / D,
+                                                                             np.finfo(np.float64).tiny)
+    elif pts.shape[0]:
+        means[:pts.shape[0]] = pts
+        counts[:pts.shape[0]] = 1.0
+    w = counts / counts.sum() if counts.sum() > 0 else np.full(M, 1.0 / M)
+    w = np.maximum(w, 1e-3)
+    return w / w.sum(), means, covs
+
+
+def init_model_gaussian_mixture(observations, nstates, ncomponents, lag=1, reversible=True, covariance_type='full'):
+    """Initial HMM with `ncomponents` gaussian components per state, deterministic and numpy
+    only: the model of init_model_mvgaussian and its hard labels first, then inside every state the same seeding and
+    Lloyd iterations on that state's points."""
+    from ..output_models import GaussianMixtureOutputModel
+    M = int(ncomponents)
+    if M < 1 or nstates * M > 4096:
+        raise ValueError('ncomponents must be >= 1 and nstates * ncomponents <= 4096')
+    base = init_model_mvgaussian(observations, nstates, lag=lag, reversible=reversible, covariance_type='full')
+    om = base.output_model
+    x = np.concatenate([np.asarray(o, dtype=np.float64) for o in observations], axis=0)
+    D = x.shape[1]
+    # the hard labels of init_model_mvgaussian: nearest cluster centre; the cluster means are its centres' successors
+    # by one averaging, so the nearest mean is taken
+    lab = _labels(x, om.means)
+    w = np.empty((nstates, M))
+    mu = np.empty((nstates, M, D))
+    cov = np.empty((nstates, M, D, D))
+    for i in range(nstates):
+        w[i], mu[i], cov[i] = _state_components(x[lab == i], M, om.means[i], om.covariances[i])
+    if covariance_type == 'diag':
+        cov = np.einsum('icaa->ica', cov).copy()
+    elif covariance_type != 'full':
+        raise ValueError("covariance_type must be 'full' or 'diag', not %r" % (covariance_type,))
+    return HMM(base.initial_distribution, base.transition_matrix,
+               GaussianMixtureOutputModel(nstates, w, mu, cov, covariance_type=covariance_type))

@@ -103,6 +103,13 @@ int bhmm_update_pout(double *pout, const int32_t *obs, const double *weights, in
 int bhmm_logpdf_mvn(double *logp, const double *X, int64_t T, int D, int N, const double *means,
                     const double *covs, int cov_type);
 
+/* Gaussian-mixture log-densities, beside bhmm_logpdf_mvn: logp[t*N + i] =
+ * log sum_c w_ic N(x_t; mu_ic, Sigma_ic) for M components per state, weights[N*M], means[N*M*D] and covs
+ * ([N*M*D*D] or [N*M*D]) component (i, c) at i * M + c, formed by the kernel of bhmm_gmm_emissions (below, where
+ * the arguments are described).  Host pointers, synchronous. */
+int bhmm_logpdf_gmm(double *logp, const double *X, int64_t T, int D, int N, int M, const double *weights,
+                    const double *means, const double *covs, int cov_type);
+
 /* ------------------------------------------------------------------------------------
  * (2) batched device-resident context
  * ---------------------------------------------------------------------------------- */
@@ -523,6 +530,39 @@ int bhmm_mvn_path_moments(bhmm_ctx *ctx, const void *paths, int path_u8, int pat
 int bhmm_mvn_sample_paths(bhmm_ctx *ctx, const double *A, const double *pi, const double *u, uint64_t seed,
                           int32_t *paths, int64_t *counts, int64_t *n0, const double *means, int cov_type,
                           double *moments);
+
+/* Gaussian-mixture emissions per state, on the observations of
+ * bhmm_ctx_set_observations_mvn: every state i has M components (the same M for all), b_i(x) = sum_c w_ic
+ * N(x; mu_ic, Sigma_ic), N * M <= 4096; component (i, c) is entry i * M + c of weights[N*M], means[N*M*D] and covs
+ * (BHMM_COV_FULL: [N*M*D*D], BHMM_COV_DIAG: [N*M*D]).  The recursions need nothing new: they run on the explicit
+ * rows of the mixture densities.
+ *   bhmm_gmm_emissions validates its arguments (M < 1, N * M > 4096, a weight that is not finite or negative, a row
+ *     of weights that does not sum to 1 within 1e-8: BHMM_ERR_INVALID; means and covs as bhmm_mvn_emissions), forms
+ *       a_tic = log w_ic + l_tic      (l_tic: the arithmetic of bhmm_mvn_emissions on component (i, c); log w_ic formed
+ *                                      in long double and rounded once; a component of weight zero is skipped)
+ *       L_ti  = log sum_c exp(a_tic)  (online: a running maximum and a rescaled sum per state)
+ *     and m_t = max_i L_ti, writes the rows exp(L_ti - m_t) (every finite row has maximum exactly 1.0), shift_k, and
+ *     loads the rows as the context's BHMM_EMIT_EXPLICIT observations -- all as bhmm_mvn_emissions does, into the same
+ *     buffers: bhmm_mvn_fetch_scale and bhmm_mvn_fetch_rows then deliver the mixture's, the read-only option
+ *     mvn_rows_ms its device time.  With M = 1 and weight 1 rows, m_t and shift_k are bitwise those of
+ *     bhmm_mvn_emissions.  With want_resp it also keeps log r_t(i,c) = a_tic - L_ti for every component in a buffer
+ *     of total * N * M doubles in the context (<= 0; -inf for a weight of zero; the normaliser is formed from the
+ *     a_tic of the state themselves, so sum_c exp(log r_t(i,c)) = 1 to a few ulp).  A NaN in x_t makes its row, m_t,
+ *     shift_k and its log responsibilities NaN.
+ *   bhmm_gmm_fetch_resp copies that buffer, out[total*N*M], to the host: log responsibilities before
+ *     bhmm_gmm_moments, the weights u_t(i,c) = gamma_t(i) r_t(i,c) after it (tests and diagnostics).
+ *   bhmm_gmm_moments: gamma_dev as for bhmm_mvn_moments (DEVICE, total * N doubles).  Turns the log responsibilities
+ *     into the weights u in place (k_gmm_weights) and runs the moment kernels of bhmm_mvn_moments over their N * M
+ *     columns about means[N*M*D]: out (host) holds N * M blocks S0_ic | S1_ic | S2_ic in the packed layout of
+ *     bhmm_mvn_moments; no floating-point atomics, bitwise the same from call to call.  BHMM_ERR_INVALID when the
+ *     last emissions were not bhmm_gmm_emissions with want_resp, or when their responsibilities have been used up
+ *     by an earlier bhmm_gmm_moments (make the emissions again).  Synchronous.
+ * Read-only option: gmm_weights_ms (device time of the last k_gmm_weights; mvn_moments_ms is that of the moment
+ * kernels that followed). */
+int bhmm_gmm_emissions(bhmm_ctx *ctx, int M, const double *weights, const double *means, const double *covs,
+                       int cov_type, int want_resp);
+int bhmm_gmm_fetch_resp(bhmm_ctx *ctx, double *out);
+int bhmm_gmm_moments(bhmm_ctx *ctx, const double *gamma_dev, const double *means, int cov_type, double *out);
 
 /* Gibbs hidden-path step (bayesian_sampling.py:283-331): forward pass + backward sampling
  * of every trajectory.  Uniforms come either from u (host, concatenated like obs; u[t]
