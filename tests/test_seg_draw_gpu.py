@@ -113,8 +113,8 @@ def test_rounds_and_the_forced_repeat_leave_the_first_trip_s_counters(n, kind):
     with a wide watch): the oracle's paths and counts both times; after a repeat the rows are the serial
     recursion's, draw_redone is set and draw_events / draw_checked are those of the first trip (the repeat has no
     watch: its own would be 0).  (On this model the first round leaves no segment to the fix-up -- sample_mismatch
-    and sample_rounds, printed below, are 0 at all three cases -- so a fix-up round is not asserted here; the 64-state
-    shape of tools/wide_sample.py takes one.)"""
+    and sample_rounds, printed below, are 0 at all three cases -- so a fix-up round is not asserted here;
+    tests/test_seg_draw_rounds_gpu.py asserts them, on slowly mixing models.)"""
     model, obs, u, ref, counts = _case(n, kind)
     eng = _engine(n, kind, obs)
     assert _is_ref(eng.sample_paths(*model, u=u), ref, counts)
