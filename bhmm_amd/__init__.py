@@ -15,9 +15,9 @@ from .hmm import (HMM, SampledHMM, GaussianHMM, DiscreteHMM, SampledGaussianHMM,
 from .output_models import (OutputModel, GaussianOutputModel, DiscreteOutputModel,  # noqa: F401
                             MultivariateGaussianOutputModel, GaussianMixtureOutputModel)
 from .estimators.maximum_likelihood import MaximumLikelihoodEstimator  # noqa: F401
-from .estimators.bayesian_sampling import BayesianHMMSampler  # noqa: F401
+from .estimators.bayesian_sampling import BayesianHMMSampler, BayesianGaussianMixtureHMMSampler  # noqa: F401
 from .api import (estimate_hmm, bayesian_hmm, bayesian_mvgaussian_hmm, lag_observations, gaussian_hmm,  # noqa: F401
-                  discrete_hmm, mvgaussian_hmm, gaussian_mixture_hmm, init_hmm, init_gaussian_hmm, init_discrete_hmm,
+                  bayesian_gaussian_mixture_hmm, discrete_hmm, mvgaussian_hmm, gaussian_mixture_hmm, init_hmm, init_gaussian_hmm, init_discrete_hmm,
                   init_mvgaussian_hmm, init_gaussian_mixture_hmm, score, posterior_decode,
                   posterior_marginals, posterior_transitions, filter_states, decode_segments, path_logprob)
 from .engine import PathRuns, MvnEngine, GmmEngine  # noqa: F401

@@ -126,6 +126,10 @@ SIGNATURES = {
                                           ctypes.c_int]),
     "bhmm_gmm_fetch_resp": (ctypes.c_int, [c_void_p, c_double_p]),
     "bhmm_gmm_moments": (ctypes.c_int, [c_void_p, c_void_p, c_double_p, ctypes.c_int, c_double_p]),
+    "bhmm_gmm_path_components": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                                c_int32_p, c_double_p]),
+    "bhmm_gmm_sample_paths": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, ctypes.c_uint64, c_int32_p,
+                                             c_int32_p, c_int64_p, c_int64_p, c_double_p]),
     "bhmm_ctx_path_stats_size": (ctypes.c_int, [c_void_p]),
     "bhmm_ctx_set_stream_offsets": (ctypes.c_int, [c_void_p, c_int64_p]),
     "bhmm_sample_paths_dev": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,
@@ -173,6 +177,10 @@ SIGNATURES = {
                                                  c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                                  ctypes.c_uint64, ctypes.c_uint64, c_double_p, c_double_p,
                                                  c_double_p, c_double_p, c_int32_p]),
+    "bhmm_gibbs_parameters_gmm": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p,
+                                                 c_double_p, c_double_p, c_double_p, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, c_double_p,
+                                                 c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p]),
     "bhmm_host_mvn_prepare": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
                                              c_double_p, c_double_p]),
     "bhmm_host_mvn_mstep": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,

@@ -165,7 +165,8 @@ def bayesian_hmm(observations, estimated_hmm, nsample=100, reversible=True, stat
         raise NotImplementedError('multivariate gaussian emissions are sampled by bayesian_mvgaussian_hmm, '
                                   'not by bayesian_hmm yet')
     if estimated_hmm.output_model.model_type == 'gaussian_mixture':
-        raise NotImplementedError('there is no Gibbs sampler for gaussian-mixture emissions yet')
+        raise NotImplementedError('the Gibbs sampler for gaussian-mixture emissions is '
+                                  'bayesian_gaussian_mixture_hmm')
     sampler = BayesianHMMSampler(observations, estimated_hmm.nstates, initial_model=estimated_hmm,
                                  reversible=reversible, stationary=stationary,
                                  transition_matrix_sampling_steps=1000, p0_prior=p0_prior,
@@ -188,7 +189,8 @@ def bayesian_mvgaussian_hmm(observations, estimated_hmm, nsample=100, reversible
     relabelled (label switching is the user's to watch, as in the reference).  engine_kwargs: device, seed (of the
     chain; one from numpy's global generator if not given), native_parameters."""
     if estimated_hmm.output_model.model_type == 'gaussian_mixture':
-        raise NotImplementedError('there is no Gibbs sampler for gaussian-mixture emissions yet')
+        raise NotImplementedError('the Gibbs sampler for gaussian-mixture emissions is '
+                                  'bayesian_gaussian_mixture_hmm')
     if estimated_hmm.output_model.model_type != 'mvgaussian':
         raise ValueError("bayesian_mvgaussian_hmm takes a model with multivariate gaussian emissions, not %r"
                          % (estimated_hmm.output_model.model_type,))
@@ -198,6 +200,34 @@ def bayesian_mvgaussian_hmm(observations, estimated_hmm, nsample=100, reversible
                                  transition_matrix_sampling_steps=1000, p0_prior=p0_prior,
                                  transition_matrix_prior=transition_matrix_prior, output='mvgaussian',
                                  **engine_kwargs)
+    sampled = sampler.sample(nsamples=nsample, save_hidden_state_trajectory=store_hidden,
+                             call_back=call_back, seed=seed)
+    return SampledHMM(estimated_hmm, sampled)
+
+
+def bayesian_gaussian_mixture_hmm(observations, estimated_hmm, nsample=100, reversible=True, stationary=False,
+                                  p0_prior='mixed', transition_matrix_prior='mixed', store_hidden=False,
+                                  call_back=None, weights_prior=1.0, seed=None, **engine_kwargs):
+    """bayesian_hmm for gaussian-mixture emissions per state: observations are (T_k, D) arrays,
+    estimated_hmm a model of output type 'gaussian_mixture' (estimate_hmm, gaussian_mixture_hmm).  Every sweep draws
+    the hidden paths, a component for every step and the moments of the component labels on the device
+    (GmmEngine.sample_paths_components), then mean and covariance of every component as bayesian_mvgaussian_hmm
+    draws them per state, the mixture weights of every state from Dirichlet(weights_prior + counts), the transition
+    matrix and the initial distribution (bhmm_gibbs_parameters_gmm).  weights_prior: a scalar or an (N, M) array;
+    1.0 is the flat Dirichlet, 0 lets a component that was emptied once stay empty for good.  seed: of the chain
+    (one from numpy's global generator if not given).  Returns a SampledHMM: weights_mean / _std / _conf (N, M),
+    means_* and covariances_* as for the multivariate gaussian kind with the component axis after the state's;
+    bhmm_amd.score takes it.  Sampled models are not relabelled: label switching, between states and between the
+    components of a state, is the user's to watch.  engine_kwargs: device, native_parameters."""
+    if estimated_hmm.output_model.model_type != 'gaussian_mixture':
+        raise ValueError("bayesian_gaussian_mixture_hmm takes a model with gaussian-mixture emissions, not %r"
+                         % (estimated_hmm.output_model.model_type,))
+    from .estimators.bayesian_sampling import BayesianGaussianMixtureHMMSampler
+    sampler = BayesianGaussianMixtureHMMSampler(observations, estimated_hmm.nstates, initial_model=estimated_hmm,
+                                                reversible=reversible, stationary=stationary,
+                                                transition_matrix_sampling_steps=1000, p0_prior=p0_prior,
+                                                transition_matrix_prior=transition_matrix_prior,
+                                                weights_prior=weights_prior, **engine_kwargs)
     sampled = sampler.sample(nsamples=nsample, save_hidden_state_trajectory=store_hidden,
                              call_back=call_back, seed=seed)
     return SampledHMM(estimated_hmm, sampled)

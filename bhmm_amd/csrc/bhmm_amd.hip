@@ -1187,7 +1187,7 @@ int bhmm_ctx_set_observations(bhmm_ctx *c, int kind, const void *obs, const int6
         b.active = b.rows_valid = false;
         b.X.release(), b.rows.release(), b.m.release(), b.shift.release(), b.d_offsets.release();
         b.tab.release(), b.part.release(), b.out.release();
-        c->gmm.forget(), c->gmm.resp.release();
+        c->gmm.forget(), c->gmm.resp.release(), c->gmm.tab.release(), c->gmm.labels.release();
     }
     c->d_soff.release(); // random-stream positions belong to the previous trajectories
     c->last_stats = nullptr;
@@ -1773,6 +1773,8 @@ int bhmm_ctx_get_option(bhmm_ctx *c, const char *name, double *value)
         *value = c->mvn.moments_ms;
     else if (n == "gmm_weights_ms") // gaussian-mixture emissions: device time of the last k_gmm_weights
         *value = c->gmm.weights_ms;
+    else if (n == "gmm_draw_ms") // ... device time of the last k_gmm_draw_components
+        *value = c->gmm.draw_ms;
     else if (n == "mvn_path_moments_ms") // ... device time of the last k_mvn_path_moments + k_mvn_moments_finish
         *value = c->mvn.path_moments_ms;
     else

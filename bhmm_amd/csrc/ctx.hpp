@@ -590,15 +590,23 @@ struct bhmm_ctx {
     } mvn;
 
     // gaussian-mixture emissions (gmm_api.hip), on the observations of the mvn block: rows, m,
-    // shift and the table are that block's; here the (total, n M) buffer that holds the log responsibilities of the
+    // and shift are that block's; here the table of the components and the (total, n M) buffer that holds the log responsibilities of the
     // last bhmm_gmm_emissions with want_resp and, after bhmm_gmm_moments, the weights the moments were taken with
     struct GmmBufs {
         int M = 0;             // components per state of the last bhmm_gmm_emissions (0: the rows are not a mixture's)
         bool resp_log = false; // resp holds log responsibilities of the loaded rows
         bool resp_any = false; // ... or the weights made from them (bhmm_gmm_fetch_resp)
         bhmm::DevBuf<double> resp;
+        // the component draws of a Gibbs sweep: the table [mu | W | c | log w] of the last
+        // bhmm_gmm_emissions, kept (the mvn block's table is overwritten by the means of every moments call), its
+        // covariance type, and the labels s_t M + c_t of the last draw
+        int cov_type = 0;
+        bhmm::DevBuf<double> tab;
+        bhmm::DevBuf<int32_t> labels;
+        bhmm::DevBuf<unsigned int> draw_status;
         float weights_ms = 0.f; // read-only option gmm_weights_ms: device time of the last k_gmm_weights
-        hipEvent_t ev[2] = {nullptr, nullptr};
+        float draw_ms = 0.f;    // read-only option gmm_draw_ms: device time of the last k_gmm_draw_components
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
         GmmBufs() = default;
         GmmBufs(const GmmBufs &) = delete;
         GmmBufs &operator=(const GmmBufs &) = delete;

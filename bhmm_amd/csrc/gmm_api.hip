@@ -1,6 +1,7 @@
 // gmm_api.hip -- gaussian-mixture emissions per state (bhmm_gmm_emissions, bhmm_gmm_fetch_resp, bhmm_gmm_moments,
-// bhmm_logpdf_gmm): kernels in gmm_kernels.hpp, the factorisation of the N M components on the host
-// (host::mvn_prepare through mvn_make_table); DESIGN.md section 25.
+// bhmm_logpdf_gmm) and the component draws of their Gibbs sweep (bhmm_gmm_path_components, bhmm_gmm_sample_paths):
+// kernels in gmm_kernels.hpp, the factorisation of the N M components on the host (host::mvn_prepare through
+// mvn_make_table); DESIGN.md sections 25 and 26.
 //
 // The mixture runs on the observations bhmm_ctx_set_observations_mvn keeps in c->mvn.X.  bhmm_gmm_emissions makes the
 // rows, m_t and shifts of the mixture densities where bhmm_mvn_emissions makes those of single gaussians -- the same
@@ -85,6 +86,77 @@ int run_rows(hipStream_t stream, const double *X, int64_t total, int D, int n, i
     return BHMM_OK;
 }
 
+template <typename PT, bool DIAG>
+hipError_t launch_draw(hipStream_t stream, const double *X, const PT *path, int64_t total, int D, int n, int M,
+                       const double *tab, const int64_t *off, const int64_t *soff, int K, uint64_t key, int32_t *labels,
+                       unsigned int *status)
+{
+    const dim3 grid((unsigned)((total + ROWS_THREADS - 1) / ROWS_THREADS)), block(ROWS_THREADS);
+#define BHMM_GMM_DRAW(DMAX)                                                                                            \
+    launch(k_gmm_draw_components<PT, DMAX, DIAG>, grid, block, 0, stream, X, path, total, D, n, M, tab, off, soff, K,  \
+           key, labels, status)
+    if (D <= 2)
+        return BHMM_GMM_DRAW(2);
+    if (D <= 4)
+        return BHMM_GMM_DRAW(4);
+    if (D <= 8)
+        return BHMM_GMM_DRAW(8);
+    if (D <= 16)
+        return BHMM_GMM_DRAW(16);
+    if (D <= 32)
+        return BHMM_GMM_DRAW(32);
+    return BHMM_GMM_DRAW(64);
+#undef BHMM_GMM_DRAW
+}
+
+bool mixture_loaded(const bhmm_ctx *c) { return c && c->mvn.active && c->mvn.rows_valid && c->gmm.M > 0; }
+
+// The components of the path at path_dev (device; int32 or one byte per step) under the table of the last
+// bhmm_gmm_emissions, as labels s_t M + c_t in c->gmm.labels, then the packed moments of those labels about the
+// table's own means into moments (host); the labels go to the host only when asked for.  A state outside [0, n):
+// BHMM_ERR_INVALID, nothing is delivered.
+int run_components(bhmm_ctx *c, const char *who, const void *path_dev, int path_u8, uint64_t seed, int32_t *labels,
+                   double *moments)
+{
+    auto &b = c->mvn;
+    auto &g = c->gmm;
+    int rc;
+    if ((b.total + ROWS_THREADS - 1) / ROWS_THREADS > 0x7fffffff)
+        return invalid_arg(std::string(who) + ": more steps than a grid has workgroups");
+    if ((rc = g.labels.ensure((size_t)b.total)) || (rc = g.draw_status.ensure(1)))
+        return rc;
+    for (hipEvent_t &e : g.ev)
+        if (!e)
+            BHMM_HIP(hipEventCreate(&e));
+    const bool diag = g.cov_type == BHMM_COV_DIAG;
+    const int64_t *soff = c->d_soff.p; // (nullptr: a step's position in the random stream is its index)
+    const uint64_t key = draw_key(seed);
+    BHMM_HIP(hipMemsetAsync(g.draw_status.p, 0, sizeof(unsigned int), c->stream));
+    BHMM_HIP(hipEventRecord(g.ev[2], c->stream));
+#define BHMM_GMM_DRAW_PT(PT)                                                                                           \
+    (diag ? launch_draw<PT, true>(c->stream, b.X.p, static_cast<const PT *>(path_dev), b.total, b.D, b.n, g.M, g.tab.p, \
+                                  b.d_offsets.p, soff, b.K, key, g.labels.p, g.draw_status.p)                          \
+          : launch_draw<PT, false>(c->stream, b.X.p, static_cast<const PT *>(path_dev), b.total, b.D, b.n, g.M,        \
+                                   g.tab.p, b.d_offsets.p, soff, b.K, key, g.labels.p, g.draw_status.p))
+    BHMM_HIP(path_u8 ? BHMM_GMM_DRAW_PT(uint8_t) : BHMM_GMM_DRAW_PT(int32_t));
+#undef BHMM_GMM_DRAW_PT
+    BHMM_HIP(hipEventRecord(g.ev[3], c->stream));
+    unsigned int status = 0;
+    BHMM_HIP(hipMemcpyAsync(&status, g.draw_status.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream));
+    (void)hipEventElapsedTime(&g.draw_ms, g.ev[2], g.ev[3]);
+    if (status & DRAW_BAD_STATE)
+        return invalid_arg(std::string(who) + ": the path holds a state outside [0, " + std::to_string(b.n) + ")");
+    // the means of the table's front are the means the moments are taken about: nothing is uploaded
+    if ((rc = mvn_run_path_moments(c, who, g.labels.p, 0, b.n * g.M, nullptr, g.tab.p, g.cov_type, moments)))
+        return rc;
+    if (labels) {
+        BHMM_HIP(hipMemcpyAsync(labels, g.labels.p, (size_t)b.total * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        BHMM_HIP(hipStreamSynchronize(c->stream));
+    }
+    return BHMM_OK;
+}
+
 } // namespace
 } // namespace bhmm
 
@@ -110,16 +182,18 @@ int bhmm_gmm_emissions(bhmm_ctx *c, int M, const double *weights, const double *
     BHMM_HIP(hipSetDevice(c->device));
     b.rows_valid = false;
     g.forget();
-    if ((rc = b.tab.ensure(tab.size())))
+    // (the table stays in g.tab for the component draws of bhmm_gmm_path_components: b.tab takes the means of every
+    // moments call)
+    if ((rc = g.tab.ensure(tab.size())))
         return rc;
     if (want_resp && (rc = g.resp.ensure((size_t)b.total * b.n * M)))
         return rc;
-    BHMM_HIP(hipMemcpyAsync(b.tab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BHMM_HIP(hipMemcpyAsync(g.tab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     for (hipEvent_t &e : b.ev)
         if (!e)
             BHMM_HIP(hipEventCreate(&e));
     BHMM_HIP(hipEventRecord(b.ev[0], c->stream));
-    if ((rc = run_rows(c->stream, b.X.p, b.total, b.D, b.n, M, cov_type, b.tab.p, b.rows.p, b.m.p, nullptr,
+    if ((rc = run_rows(c->stream, b.X.p, b.total, b.D, b.n, M, cov_type, g.tab.p, b.rows.p, b.m.p, nullptr,
                        want_resp ? g.resp.p : nullptr)))
         return rc;
     BHMM_HIP(mvn_launch_shift(c));
@@ -135,6 +209,7 @@ int bhmm_gmm_emissions(bhmm_ctx *c, int M, const double *weights, const double *
         return rc;
     b.rows_valid = true;
     g.M = M;
+    g.cov_type = cov_type;
     g.resp_log = g.resp_any = want_resp != 0;
     return BHMM_OK;
 }
@@ -181,6 +256,51 @@ int bhmm_gmm_moments(bhmm_ctx *c, const double *gamma_dev, const double *means, 
     if (!rc)
         (void)hipEventElapsedTime(&g.weights_ms, g.ev[0], g.ev[1]);
     return rc;
+}
+
+int bhmm_gmm_path_components(bhmm_ctx *c, const void *paths, int path_u8, int paths_on_device, uint64_t seed,
+                             int32_t *labels, double *moments)
+{
+    if (!mixture_loaded(c))
+        return invalid_arg("bhmm_gmm_path_components: the last emissions on these observations were not "
+                           "bhmm_gmm_emissions");
+    if (!paths || !moments)
+        return invalid_arg("bhmm_gmm_path_components: paths / moments == NULL");
+    auto &b = c->mvn;
+    if (path_u8 && b.n > 256) // (every byte is a state then; the int32 form holds the others)
+        return invalid_arg("bhmm_gmm_path_components: one byte per step holds at most 256 states (use the int32 form)");
+    BHMM_HIP(hipSetDevice(c->device));
+    if (paths_on_device) {
+        if (reinterpret_cast<uintptr_t>(paths) % 16)
+            return invalid_arg("bhmm_gmm_path_components: a device path must be aligned to 16 bytes");
+        return run_components(c, "bhmm_gmm_path_components", paths, path_u8, seed, labels, moments);
+    }
+    const size_t bytes = (size_t)b.total * (path_u8 ? sizeof(uint8_t) : sizeof(int32_t));
+    if (int rc = b.path.ensure(bytes))
+        return rc;
+    BHMM_HIP(hipMemcpyAsync(b.path.p, paths, bytes, hipMemcpyHostToDevice, c->stream));
+    return run_components(c, "bhmm_gmm_path_components", b.path.p, path_u8, seed, labels, moments);
+}
+
+int bhmm_gmm_sample_paths(bhmm_ctx *c, const double *A, const double *pi, const double *u, uint64_t seed,
+                          int32_t *paths, int32_t *labels, int64_t *counts, int64_t *n0, double *moments)
+{
+    if (!mixture_loaded(c))
+        return invalid_arg("bhmm_gmm_sample_paths: the last emissions on these observations were not "
+                           "bhmm_gmm_emissions");
+    if (!A || !pi || !moments)
+        return invalid_arg("bhmm_gmm_sample_paths: A / pi / moments == NULL");
+    auto &b = c->mvn;
+    if (c->n != b.n || c->total != b.total)
+        return invalid_arg("bhmm_gmm_sample_paths: the loaded emission rows are not those of the multivariate set");
+    // the draw leaves its int32 path at the front of c->d_scratch2 (keep_path, as for bhmm_mvn_sample_paths) ...
+    c->keep_path = true;
+    const int rc = bhmm_sample_paths(c, A, pi, nullptr, nullptr, u, seed, paths, counts, n0, nullptr);
+    c->keep_path = false;
+    if (rc)
+        return rc;
+    // ... where the components are drawn and their moments taken, before anything else uses that buffer
+    return run_components(c, "bhmm_gmm_sample_paths", c->d_scratch2.p, 0, seed, labels, moments);
 }
 
 int bhmm_logpdf_gmm(double *logp, const double *X, int64_t T, int D, int N, int M, const double *weights,

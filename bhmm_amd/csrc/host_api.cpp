@@ -360,3 +360,61 @@ extern "C" int bhmm_gibbs_parameters_mvn(int n, int D, int cov_type, const doubl
     }
     return BHMM_OK;
 }
+
+// the same sweep for gaussian-mixture emissions per state: the emission draws of
+// mvn_gibbs_emissions over the n M components, then the transition matrix and p0 over the n states, on one generator
+// -- at M = 1 the call above, draw for draw; the mixture weights on a generator of their own
+extern "C" int bhmm_gibbs_parameters_gmm(int n, int M, int D, int cov_type, const double *path_stats,
+                                         const double *prior_C, const double *prior_n0, const double *prior_w,
+                                         int reversible, int stationary, int64_t nsteps, uint64_t seed, uint64_t sweep,
+                                         double *T, double *p0, double *weights, double *means, double *covs,
+                                         int32_t *info)
+{
+    if (!path_stats || !T || !p0 || !weights || !means || !covs)
+        return bhmm::invalid_arg("bhmm_gibbs_parameters_gmm: NULL argument");
+    if (n < 1 || M < 1 || (int64_t)n * M > 4096 || D < 1 || D > BHMM_MVN_MAX_D)
+        return bhmm::invalid_arg("bhmm_gibbs_parameters_gmm: n >= 1 states, M >= 1 components each, n * M <= 4096 and 1.." +
+                                 std::to_string(BHMM_MVN_MAX_D) + " dimensions are supported");
+    if (cov_type != BHMM_COV_FULL && cov_type != BHMM_COV_DIAG)
+        return bhmm::invalid_arg("bhmm_gibbs_parameters_gmm: cov_type is BHMM_COV_FULL or BHMM_COV_DIAG");
+    const int nm = n * M;
+    const size_t nn = (size_t)n * n, ms = mvn_moment_stride(D, cov_type);
+    const double *Cint = path_stats, *n0 = path_stats + nn, *moments = path_stats + nn + n;
+    for (size_t e = 0; e < (size_t)nm * D; ++e)
+        if (!std::isfinite(means[e]))
+            return bhmm::invalid_arg("bhmm_gibbs_parameters_gmm: a mean is not finite");
+    for (int q = 0; q < nm; ++q)
+        if (prior_w && !(prior_w[q] >= 0.0 && std::isfinite(prior_w[q])))
+            return bhmm::invalid_arg("bhmm_gibbs_parameters_gmm: a weight prior is negative or not finite");
+    Rng rng(seed, sweep);
+    int32_t kept = 0;
+    if (int rc = mvn_gibbs_emissions(nm, D, cov_type, moments, rng, means, covs, &kept))
+        return rc;
+    if (int rc = draw_transitions(n, Cint, n0, prior_C, prior_n0, reversible, stationary, nsteps, rng, T, p0))
+        return rc;
+    // the weights: per state a Dirichlet on prior + counts, on a stream of their own (M = 1 consumes nothing)
+    Rng wrng(rng_mix64(seed ^ 0xA0761D6478BD642Full), sweep);
+    std::vector<double> alpha(M);
+    for (int i = 0; i < n && M > 1; ++i) {
+        bool any = false;
+        for (int c = 0; c < M; ++c) {
+            alpha[c] = (prior_w ? prior_w[(size_t)i * M + c] : 0.0) + nearbyint(moments[((size_t)i * M + c) * ms]);
+            any = any || alpha[c] > 0.0;
+        }
+        if (!any) // (a state the path never visited, without a prior: its weights stay)
+            continue;
+        double *w = weights + (size_t)i * M;
+        for (int c = 0; c < M; ++c)
+            w[c] = 0.0; // (dirichlet leaves the entries with alpha <= 0 as they are: exactly 0)
+        wrng.dirichlet(alpha.data(), M, w);
+    }
+    if (info) {
+        int32_t zero = 0;
+        for (int q = 0; q < nm; ++q)
+            zero += weights[q] == 0.0;
+        info[0] = (int32_t)std::min<uint64_t>(rng.ctr, 2147483647u);
+        info[1] = kept;
+        info[2] = zero;
+    }
+    return BHMM_OK;
+}

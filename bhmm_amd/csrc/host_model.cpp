@@ -525,6 +525,7 @@ static inline uint64_t mix64(uint64_t z)
     return z ^ (z >> 31);
 }
 static const uint64_t GOLDEN = 0x9E3779B97F4A7C15ull;
+uint64_t rng_mix64(uint64_t z) { return mix64(z); }
 
 Rng::Rng(uint64_t seed, uint64_t stream) : key(mix64(mix64(seed) + GOLDEN * (stream + 1))) {}
 

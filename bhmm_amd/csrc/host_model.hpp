@@ -48,6 +48,7 @@ bool is_reversible(const double *P, int n);
 // Counter-based generator: draw i of stream `key` is the SplitMix64 finaliser of
 // key + golden * (i + 1) -- the device's uniform01 (path_kernels.hpp) -- so a chain is a function of
 // (seed, sweep) alone and a host restatement reproduces it.
+uint64_t rng_mix64(uint64_t z); // the SplitMix64 finaliser itself: a second seed from a first (seed' = mix64(seed ^ constant))
 struct Rng {
     uint64_t key;
     uint64_t ctr = 0;

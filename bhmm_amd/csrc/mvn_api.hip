@@ -95,6 +95,61 @@ int mvn_run_moments(bhmm_ctx *c, const double *gamma_dev, int ncols, const doubl
     return BHMM_OK;
 }
 
+// Packed moments of the hard labels at path_dev (device; int32 or one byte per step) about the nlabels means into out
+// (host): k_mvn_path_moments, one slab per workgroup, then k_mvn_moments_finish over the slabs.  The labels are the
+// states of a hidden path (nlabels = n) or its components s_t M + c_t (nlabels = n M, gmm_api.hip); the means come
+// from the host (means) or, means == NULL, lie on the device already (means_dev).  A label outside [0, nlabels) is
+// found by the kernel before it indexes anything with it: BHMM_ERR_INVALID, nothing is delivered.
+int mvn_run_path_moments(bhmm_ctx *c, const char *who, const void *path_dev, int path_u8, int nlabels,
+                         const double *means, const double *means_dev, int cov_type, double *out)
+{
+    auto &b = c->mvn;
+    const bool diag = cov_type == BHMM_COV_DIAG;
+    const int D = b.D, n = nlabels;
+    const int mode = diag ? PM_ELEM_DIAG : (D >= PM_BLOCK_MIN_D ? PM_BLOCK : PM_ELEM_FULL);
+    const size_t E = (size_t)n * moment_stride(D, diag);
+    const PmPlan pl = pm_plan(b.total, D, n, mode);
+    int rc;
+    if ((rc = b.part.ensure((size_t)pl.groups * E)) || (rc = b.out.ensure(E)) ||
+        (means && (rc = b.tab.ensure((size_t)n * D))) || (rc = b.path_status.ensure(1)))
+        return rc;
+    // (the table of the last bhmm_mvn_emissions is not needed any more: the rows are made)
+    if (means)
+        BHMM_HIP(hipMemcpyAsync(b.tab.p, means, (size_t)n * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const double *mu_dev = means ? b.tab.p : means_dev;
+    BHMM_HIP(hipMemsetAsync(b.path_status.p, 0, sizeof(unsigned int), c->stream));
+    for (hipEvent_t &e : b.ev)
+        if (!e)
+            BHMM_HIP(hipEventCreate(&e));
+    BHMM_HIP(hipEventRecord(b.ev[4], c->stream));
+    if (!pl.slab_lds) // the slabs are accumulated where they lie
+        BHMM_HIP(hipMemsetAsync(b.part.p, 0, (size_t)pl.groups * E * sizeof(double), c->stream));
+    const dim3 grid((unsigned)pl.groups), block(PM_THREADS);
+#define BHMM_MVN_PM(PT, MODE)                                                                                          \
+    launch(k_mvn_path_moments<PT, MODE>, grid, block, pl.lds, c->stream, b.X.p, static_cast<const PT *>(path_dev),      \
+           b.total, D, n, mu_dev, pl, b.part.p, b.path_status.p)
+#define BHMM_MVN_PM_MODE(PT)                                                                                           \
+    (mode == PM_BLOCK ? BHMM_MVN_PM(PT, PM_BLOCK) : mode == PM_ELEM_DIAG ? BHMM_MVN_PM(PT, PM_ELEM_DIAG)               \
+                                                                         : BHMM_MVN_PM(PT, PM_ELEM_FULL))
+    BHMM_HIP(path_u8 ? BHMM_MVN_PM_MODE(uint8_t) : BHMM_MVN_PM_MODE(int32_t));
+#undef BHMM_MVN_PM_MODE
+#undef BHMM_MVN_PM
+    BHMM_HIP(launch(k_mvn_moments_finish, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, c->stream, b.part.p, pl.groups,
+                    (int64_t)E, b.out.p));
+    BHMM_HIP(hipEventRecord(b.ev[5], c->stream));
+    std::vector<double> res(E);
+    unsigned int status = 0;
+    BHMM_HIP(hipMemcpyAsync(res.data(), b.out.p, E * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    BHMM_HIP(hipMemcpyAsync(&status, b.path_status.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    BHMM_HIP(hipStreamSynchronize(c->stream));
+    (void)hipEventElapsedTime(&b.path_moments_ms, b.ev[4], b.ev[5]);
+    if (status & PM_BAD_STATE)
+        return invalid_arg(std::string(who) + ": the path holds a " + (n == b.n ? "state" : "label") + " outside [0, " +
+                           std::to_string(n) + ")");
+    memcpy(out, res.data(), E * sizeof(double));
+    return BHMM_OK;
+}
+
 namespace {
 
 template <bool DIAG>
@@ -124,56 +179,6 @@ int run_rows(hipStream_t stream, const double *X, int64_t total, int D, int n, i
         return invalid_arg("multivariate gaussian emissions: more steps than a grid has workgroups");
     BHMM_HIP(cov_type == BHMM_COV_DIAG ? launch_rows<true>(stream, X, total, D, n, tab, rows, m, logp)
                                        : launch_rows<false>(stream, X, total, D, n, tab, rows, m, logp));
-    return BHMM_OK;
-}
-
-// Packed moments of the hidden path at path_dev (device; int32 or one byte per step) about means (host) into out
-// (host): k_mvn_path_moments, one slab per workgroup, then k_mvn_moments_finish over the slabs.  A state outside
-// [0, n) is found by the kernel before it indexes anything with it: BHMM_ERR_INVALID, nothing is delivered.
-int run_path_moments(bhmm_ctx *c, const char *who, const void *path_dev, int path_u8, const double *means, int cov_type,
-                     double *out)
-{
-    auto &b = c->mvn;
-    const bool diag = cov_type == BHMM_COV_DIAG;
-    const int D = b.D, n = b.n;
-    const int mode = diag ? PM_ELEM_DIAG : (D >= PM_BLOCK_MIN_D ? PM_BLOCK : PM_ELEM_FULL);
-    const size_t E = (size_t)n * moment_stride(D, diag);
-    const PmPlan pl = pm_plan(b.total, D, n, mode);
-    int rc;
-    if ((rc = b.part.ensure((size_t)pl.groups * E)) || (rc = b.out.ensure(E)) || (rc = b.tab.ensure((size_t)n * D)) ||
-        (rc = b.path_status.ensure(1)))
-        return rc;
-    // (the table of the last bhmm_mvn_emissions is not needed any more: the rows are made)
-    BHMM_HIP(hipMemcpyAsync(b.tab.p, means, (size_t)n * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    BHMM_HIP(hipMemsetAsync(b.path_status.p, 0, sizeof(unsigned int), c->stream));
-    for (hipEvent_t &e : b.ev)
-        if (!e)
-            BHMM_HIP(hipEventCreate(&e));
-    BHMM_HIP(hipEventRecord(b.ev[4], c->stream));
-    if (!pl.slab_lds) // the slabs are accumulated where they lie
-        BHMM_HIP(hipMemsetAsync(b.part.p, 0, (size_t)pl.groups * E * sizeof(double), c->stream));
-    const dim3 grid((unsigned)pl.groups), block(PM_THREADS);
-#define BHMM_MVN_PM(PT, MODE)                                                                                          \
-    launch(k_mvn_path_moments<PT, MODE>, grid, block, pl.lds, c->stream, b.X.p, static_cast<const PT *>(path_dev),      \
-           b.total, D, n, b.tab.p, pl, b.part.p, b.path_status.p)
-#define BHMM_MVN_PM_MODE(PT)                                                                                           \
-    (mode == PM_BLOCK ? BHMM_MVN_PM(PT, PM_BLOCK) : mode == PM_ELEM_DIAG ? BHMM_MVN_PM(PT, PM_ELEM_DIAG)               \
-                                                                         : BHMM_MVN_PM(PT, PM_ELEM_FULL))
-    BHMM_HIP(path_u8 ? BHMM_MVN_PM_MODE(uint8_t) : BHMM_MVN_PM_MODE(int32_t));
-#undef BHMM_MVN_PM_MODE
-#undef BHMM_MVN_PM
-    BHMM_HIP(launch(k_mvn_moments_finish, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, c->stream, b.part.p, pl.groups,
-                    (int64_t)E, b.out.p));
-    BHMM_HIP(hipEventRecord(b.ev[5], c->stream));
-    std::vector<double> res(E);
-    unsigned int status = 0;
-    BHMM_HIP(hipMemcpyAsync(res.data(), b.out.p, E * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    BHMM_HIP(hipMemcpyAsync(&status, b.path_status.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-    BHMM_HIP(hipStreamSynchronize(c->stream));
-    (void)hipEventElapsedTime(&b.path_moments_ms, b.ev[4], b.ev[5]);
-    if (status & PM_BAD_STATE)
-        return invalid_arg(std::string(who) + ": the path holds a state outside [0, " + std::to_string(n) + ")");
-    memcpy(out, res.data(), E * sizeof(double));
     return BHMM_OK;
 }
 
@@ -321,13 +326,13 @@ int bhmm_mvn_path_moments(bhmm_ctx *c, const void *paths, int path_u8, int paths
     if (paths_on_device) {
         if (reinterpret_cast<uintptr_t>(paths) % 16)
             return invalid_arg("bhmm_mvn_path_moments: a device path must be aligned to 16 bytes");
-        return run_path_moments(c, "bhmm_mvn_path_moments", paths, path_u8, means, cov_type, out);
+        return mvn_run_path_moments(c, "bhmm_mvn_path_moments", paths, path_u8, b.n, means, nullptr, cov_type, out);
     }
     const size_t bytes = (size_t)b.total * (path_u8 ? sizeof(uint8_t) : sizeof(int32_t));
     if (int rc = b.path.ensure(bytes))
         return rc;
     BHMM_HIP(hipMemcpyAsync(b.path.p, paths, bytes, hipMemcpyHostToDevice, c->stream));
-    return run_path_moments(c, "bhmm_mvn_path_moments", b.path.p, path_u8, means, cov_type, out);
+    return mvn_run_path_moments(c, "bhmm_mvn_path_moments", b.path.p, path_u8, b.n, means, nullptr, cov_type, out);
 }
 
 int bhmm_mvn_sample_paths(bhmm_ctx *c, const double *A, const double *pi, const double *u, uint64_t seed,
@@ -351,7 +356,7 @@ int bhmm_mvn_sample_paths(bhmm_ctx *c, const double *A, const double *pi, const 
     if (rc)
         return rc;
     // ... and is read here, before anything else uses that buffer
-    return run_path_moments(c, "bhmm_mvn_sample_paths", c->d_scratch2.p, 0, means, cov_type, moments);
+    return mvn_run_path_moments(c, "bhmm_mvn_sample_paths", c->d_scratch2.p, 0, b.n, means, nullptr, cov_type, moments);
 }
 
 int bhmm_logpdf_mvn(double *logp, const double *X, int64_t T, int D, int N, const double *means, const double *covs,

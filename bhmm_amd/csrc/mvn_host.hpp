@@ -19,6 +19,13 @@ int mvn_make_table(const char *who, int n, int D, int cov_type, const double *me
 // about means [ncols * D] (host) into out [ncols * moment stride] (host); device time in c->mvn.moments_ms.
 // Synchronous.
 int mvn_run_moments(bhmm_ctx *c, const double *gamma_dev, int ncols, const double *means, int cov_type, double *out);
+// k_mvn_path_moments + k_mvn_moments_finish over the observations of c->mvn with the hard labels at path_dev (device;
+// int32, or path_u8: one byte per step) in [0, nlabels): the states of a hidden path, or its components s_t M + c_t.
+// About means [nlabels * D] (host) or, means == NULL, means_dev (device) into out [nlabels * moment stride] (host);
+// device time in c->mvn.path_moments_ms.  BHMM_ERR_INVALID (who: the caller's name) for a label out of range, nothing
+// is delivered then.  Synchronous.
+int mvn_run_path_moments(bhmm_ctx *c, const char *who, const void *path_dev, int path_u8, int nlabels,
+                         const double *means, const double *means_dev, int cov_type, double *out);
 
 // k_mvn_shift on the stream: c->mvn.shift[k] = sum of c->mvn.m over trajectory k
 hipError_t mvn_launch_shift(bhmm_ctx *c);

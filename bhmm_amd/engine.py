@@ -1331,10 +1331,65 @@ class GmmEngine(MvnEngine):
         return out
 
     def path_moments(self, *args, **kwargs):
-        raise NotImplementedError("moments of a hidden path are not made for gaussian-mixture emissions")
+        raise NotImplementedError("a hidden path has no moments per state under gaussian-mixture emissions: "
+                                  "draw_components gives those of its components")
 
     def sample_paths_moments(self, *args, **kwargs):
-        raise NotImplementedError("the Gibbs sampler does not run on gaussian-mixture emissions")
+        raise NotImplementedError("the Gibbs sweep of gaussian-mixture emissions is sample_paths_components")
+
+    # -- the components of a hidden path ------------------------------
+    def _component_moments(self):
+        from .output_models.mvgaussian import moment_stride
+        if self._loaded is None:
+            raise ValueError("no emissions made yet")
+        ctype = 'full' if self._loaded[1].ndim == 4 else 'diag'
+        return np.empty(self.nstates * self.ncomponents * moment_stride(self.dimension, ctype))
+
+    def draw_components(self, paths, seed=0, want_labels=True):
+        """For every step of a given hidden path a component c_t ~ r_t(s_t, .) under the loaded emissions
+        (bhmm_gmm_path_components), and the packed moments of the labels s_t M + c_t about the component means of
+        those emissions, in the layout of `moments`.  `paths` as path_logprob takes them.  Returns (labels or None,
+        moments): labels a flat int32 array.  Only the M densities of the state a step is in are formed, and no
+        responsibilities are kept or needed.  A state outside [0, nstates) raises ValueError.  Labels and moments
+        are a function of (observations, path, parameters, seed, stream offsets) alone: bitwise the same from call
+        to call and for every form of the same path.  Stream offsets (set_stream_offsets, after the emissions: a
+        re-load forgets them) place the trajectories in the random stream as they do for the path draw (read-only
+        option "gmm_draw_ms": device time of the draw)."""
+        out = self._component_moments()
+        if isinstance(paths, (list, tuple)):
+            paths = self._concat_paths(paths)
+        ptr, u8, on_dev = self._path_arg(paths, loaded=True)
+        labels = np.empty(int(self.offsets[-1]), dtype=np.int32) if want_labels else None
+        _lib.check(self._L.bhmm_gmm_path_components(self._h, ctypes.c_void_p(int(ptr)), 1 if u8 else 0, on_dev,
+                                                    ctypes.c_uint64(int(seed)), _lib.ip(labels), _lib.dp(out)))
+        return labels, out
+
+    def sample_paths_components(self, A, pi, par0, par1, u=None, seed=0, want_paths=False, want_labels=False):
+        """Gibbs hidden-path step under (A, pi, par0, par1) followed by the component draw of draw_components on
+        the drawn path, where it lies on the device, and the moments of the labels (bhmm_gmm_sample_paths).  Makes
+        the emissions first when the loaded ones are not those of (par0, par1).  Returns (paths or None, labels or
+        None, C int64 (n, n), n0 int64 (n,), moments); paths, C and n0 are those of sample_paths for the same
+        arguments; paths and labels are lists of one int32 array per trajectory and cross the link only when
+        asked for."""
+        self.emissions(par0, par1)
+        out = self._component_moments()
+        A, pi, _, _ = self._model_ptrs(A, pi, None, None)
+        n = self.nstates
+        total = int(self.offsets[-1])
+        paths = np.empty(total, dtype=np.int32) if want_paths else None
+        labels = np.empty(total, dtype=np.int32) if want_labels else None
+        C = np.zeros((n, n), dtype=np.int64)
+        n0 = np.zeros(n, dtype=np.int64)
+        uu = _lib.f64(np.concatenate(u)) if u is not None else None
+        _lib.check(self._L.bhmm_gmm_sample_paths(self._h, A, pi, _lib.dp(uu), ctypes.c_uint64(int(seed)),
+                                                 _lib.ip(paths), _lib.ip(labels), _lib.lp(C), _lib.lp(n0),
+                                                 _lib.dp(out)))
+
+        def split(flat):
+            if flat is None:
+                return None
+            return [flat[self.offsets[k]:self.offsets[k + 1]] for k in range(len(self.lengths))]
+        return split(paths), split(labels), C, n0, out
 
     # -- E-step --------------------------------------------------------------------------
     def estep_launch(self, A, pi, par0=None, par1=None, stats_dev=None, store_gamma=False, single=False):

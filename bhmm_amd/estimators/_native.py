@@ -137,3 +137,51 @@ class GibbsParametersMvn(object):
                             int(self.stationary), self.nsteps, int(seed) & 0xFFFFFFFFFFFFFFFF, int(sweep),
                             *self._out, _addr(mu), _addr(cov), self._info))
         return self.T.copy(), self.p0.copy(), mu, cov
+
+
+class GibbsParametersGmm(object):
+    """Persistent argument block of bhmm_gibbs_parameters_gmm for one sampler (gaussian-mixture emissions per state):
+    prior_w (n, M) >= 0 is the Dirichlet prior of the mixture weights (None: zeros)."""
+
+    def __init__(self, n, M, D, covariance_type='full', prior_C=None, prior_n0=None, prior_w=None, reversible=True,
+                 stationary=False, nsteps=1000):
+        if covariance_type not in ('full', 'diag'):
+            raise ValueError("covariance_type must be 'full' or 'diag', not %r" % (covariance_type,))
+        self._L = _lib.load()
+        self._fn = self._L.bhmm_gibbs_parameters_gmm
+        self.n, self.M, self.D, self.covariance_type = int(n), int(M), int(D), covariance_type
+        self._code = _lib.COV_FULL if covariance_type == 'full' else _lib.COV_DIAG
+        self.prior_C = _lib.f64(prior_C) if prior_C is not None else None
+        self.prior_n0 = _lib.f64(prior_n0) if prior_n0 is not None else None
+        self.prior_w = _lib.f64(prior_w) if prior_w is not None else None
+        if self.prior_w is not None and self.prior_w.shape != (self.n, self.M):
+            raise ValueError("prior_w must be (%d, %d), not %r" % (self.n, self.M, self.prior_w.shape))
+        self.reversible, self.stationary, self.nsteps = bool(reversible), bool(stationary), int(nsteps)
+        self.T = np.empty((n, n))
+        self.p0 = np.empty(n)
+        # draws consumed, components whose covariance was kept, components of weight 0
+        self.info = np.zeros(3, dtype=np.int32)
+        self._priors = (_addr(self.prior_C), _addr(self.prior_n0), _addr(self.prior_w))
+        self._out = (_addr(self.T), _addr(self.p0))
+        self._info = _lib.ip(self.info)
+
+    def __call__(self, packed_path_stats, weights, means, covariances, seed, sweep):
+        """packed_path_stats: [C n*n | n0 n | the n M packed moment blocks of the labels about `means`]; weights (n, M),
+        means (n, M, D), covariances (n, M, D, D) or (n, M, D): the current parameters (copied, then updated in the
+        copies).  Returns (T, p0, weights_new, means_new, covariances_new)."""
+        n, M, D = self.n, self.M, self.D
+        packed = _c64(packed_path_stats)
+        stride = 1 + D + (D * (D + 1) // 2 if self.covariance_type == 'full' else D)
+        if packed.shape != (n * n + n + n * M * stride,):
+            raise ValueError("packed path statistics must hold %d doubles" % (n * n + n + n * M * stride))
+        w = np.array(weights, dtype=np.float64)
+        mu = np.array(means, dtype=np.float64)
+        cov = np.array(covariances, dtype=np.float64)
+        if w.shape != (n, M) or mu.shape != (n, M, D) or \
+                cov.shape != ((n, M, D, D) if self.covariance_type == 'full' else (n, M, D)):
+            raise ValueError("weights / means / covariances do not have the shapes of %d states, %d components, "
+                             "%d dimensions, %r" % (n, M, D, self.covariance_type))
+        _lib.check(self._fn(n, M, D, self._code, _addr(packed), *self._priors, int(self.reversible),
+                            int(self.stationary), self.nsteps, int(seed) & 0xFFFFFFFFFFFFFFFF, int(sweep),
+                            *self._out, _addr(w), _addr(mu), _addr(cov), self._info))
+        return self.T.copy(), self.p0.copy(), w, mu, cov

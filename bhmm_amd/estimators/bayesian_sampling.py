@@ -36,12 +36,14 @@ def _unpack_path_stats(packed, kind, n, M):
         return C, n0, rest[:3 * n].reshape(3, n).copy()
     if kind == 'discrete':
         return C, n0, rest[:n * M].reshape(n, M).copy()
-    if kind == 'mvgaussian':
-        return C, n0, rest.copy()       # the packed moments of bhmm_mvn_path_moments
+    if kind in ('mvgaussian', 'gaussian_mixture'):
+        return C, n0, rest.copy()       # the packed moments of bhmm_mvn_path_moments / bhmm_gmm_path_components
     return C, n0, None
 
 
 class BayesianHMMSampler(object):
+    _mixture = False    # BayesianGaussianMixtureHMMSampler: the one sampler that takes gaussian-mixture emissions
+
     def __init__(self, observations, nstates, initial_model=None, reversible=True,
                  stationary=False, transition_matrix_sampling_steps=1000, p0_prior='mixed',
                  transition_matrix_prior='mixed', output='gaussian', device=None,
@@ -49,9 +51,15 @@ class BayesianHMMSampler(object):
         if len(observations) == 0:
             raise Exception("No observations were provided.")
         kind = initial_model.output_model.model_type if initial_model else output
-        if kind == 'gaussian_mixture':
-            # (the Gibbs sampler for mixtures per state is not built)
-            raise NotImplementedError('there is no Gibbs sampler for gaussian-mixture emissions yet')
+        if kind == 'gaussian_mixture' and not self._mixture:
+            # (mixtures per state have a sampler class of their own)
+            raise NotImplementedError('the Gibbs sampler for gaussian-mixture emissions is '
+                                      'BayesianGaussianMixtureHMMSampler (bayesian_gaussian_mixture_hmm)')
+        if self._mixture and kind != 'gaussian_mixture':
+            raise ValueError("BayesianGaussianMixtureHMMSampler takes a model with gaussian-mixture emissions, not %r"
+                             % (kind,))
+        if self._mixture and process_group is not None:
+            raise NotImplementedError('gaussian-mixture emissions do not run over a process_group yet')
         if kind == 'mvgaussian' and process_group is not None:
             # multivariate gaussian emissions: single process, as for the estimator
             raise NotImplementedError('multivariate gaussian emissions do not run over a process_group yet')
@@ -116,6 +124,9 @@ class BayesianHMMSampler(object):
         if self._output == 'mvgaussian' and engine_factory is None:
             from .maximum_likelihood import _mvn_engine_factory
             factory = _mvn_engine_factory
+        if self._output == 'gaussian_mixture' and engine_factory is None:
+            from .maximum_likelihood import _gmm_engine_factory
+            factory = _gmm_engine_factory
         self._engine = factory(device)
         M = self.model.output_model.nsymbols if self._output == 'discrete' else 0
         self._nsymbols = M
@@ -201,6 +212,8 @@ class BayesianHMMSampler(object):
                 base = int(self._rng.randint(0, 2 ** 31 - 1)) * 2 ** 31 + int(self._rng.randint(0, 2 ** 31 - 1))
                 base = int(self._comm.broadcast_numpy(np.array([base], dtype=np.int64), src=0)[0])
             self._param_seed = (base * 0x9E3779B1 + 0x7F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        if self._output == 'gaussian_mixture':
+            return self._update_mixture_native(packed)
         if self._draw is None and self._output == 'mvgaussian':
             from ._native import GibbsParametersMvn
             om = self.model.output_model
@@ -273,6 +286,12 @@ class BayesianHMMSampler(object):
             paths, C, n0, mom = eng.sample_paths_moments(A, pi, par0, par1, seed=sweep_seed,
                                                          want_paths=keep_paths)
             packed = np.concatenate([np.ravel(C).astype(np.float64), np.ravel(n0).astype(np.float64), mom])
+        elif self._output == 'gaussian_mixture':
+            # (single process.)  Path, component of every step and the moments of the n M labels in one call, all on
+            # the device (bhmm_gmm_sample_paths): [C | n0 | packed component moments]
+            paths, self.component_labels, C, n0, mom = eng.sample_paths_components(
+                A, pi, par0, par1, seed=sweep_seed, want_paths=keep_paths, want_labels=keep_paths)
+            packed = np.concatenate([np.ravel(C).astype(np.float64), np.ravel(n0).astype(np.float64), mom])
         elif not comm.active:
             paths, C, n0, emis = eng.sample_paths(A, pi, par0, par1, seed=sweep_seed,
                                                   want_paths=keep_paths)
@@ -318,6 +337,11 @@ class BayesianHMMSampler(object):
             from ..output_models.mvgaussian import unpack_moments
             om.sample_from_statistics(*unpack_moments(emis, self.nstates, om.dimension, om.covariance_type),
                                       rng=self._rng)
+        elif self._output == 'gaussian_mixture':
+            from ..output_models.gaussian_mixture import unpack_component_moments
+            om.sample_from_statistics(*unpack_component_moments(emis, self.nstates, om.ncomponents, om.dimension,
+                                                                om.covariance_type),
+                                      rng=self._rng, weights_prior=self.prior_w)
         else:
             om.sample_from_statistics(emis, rng=self._rng)
 
@@ -344,4 +368,57 @@ class BayesianHMMSampler(object):
             positive = w > 0
             p0 = np.zeros_like(n0)
             p0[positive] = self._rng.dirichlet(w[positive])
+        self.model.update(p0, Tij)
+
+
+class BayesianGaussianMixtureHMMSampler(BayesianHMMSampler):
+    """Gibbs sampler for HMMs with gaussian-mixture emissions per state, with the interface of
+    BayesianHMMSampler.  A sweep draws the hidden paths, then for every step a component of the state it is in and
+    the moments of the n M labels -- all on the device, no responsibilities kept (GmmEngine.sample_paths_components)
+    -- then the parameters: mean and covariance of every component by the rule of the multivariate gaussian kind,
+    per state w_i ~ Dirichlet(weights_prior + counts), the transition matrix and the initial distribution
+    (bhmm_gibbs_parameters_gmm; native_parameters=False: the same rule in numpy on np.random's stream).
+
+    weights_prior: the Dirichlet prior of the mixture weights, a scalar or an (N, M) array, >= 0.  The default 1.0
+    is the flat Dirichlet.  A sparse prior of 0 makes an emptied component absorbing: a component that no step is
+    assigned to in one sweep takes weight exactly 0, is never drawn again and keeps its mean and covariance for the
+    rest of the chain.  initial_model is required (a fitted or hand-made mixture model).  Runs in a single process:
+    process_group raises NotImplementedError.  Label switching between the components of a state is not handled,
+    no more than between states: summaries over the samples mean what they say only while the components keep
+    their identity.  After a sweep with keep_paths, component_labels holds the labels s_t M + c_t per trajectory."""
+    _mixture = True
+
+    def __init__(self, observations, nstates, initial_model=None, reversible=True, stationary=False,
+                 transition_matrix_sampling_steps=1000, p0_prior='mixed', transition_matrix_prior='mixed',
+                 weights_prior=1.0, device=None, process_group=None, engine_factory=None, native_parameters=True):
+        if initial_model is None:
+            raise ValueError('BayesianGaussianMixtureHMMSampler needs an initial_model with gaussian-mixture emissions')
+        BayesianHMMSampler.__init__(self, observations, nstates, initial_model=initial_model, reversible=reversible,
+                                    stationary=stationary,
+                                    transition_matrix_sampling_steps=transition_matrix_sampling_steps,
+                                    p0_prior=p0_prior, transition_matrix_prior=transition_matrix_prior,
+                                    output='gaussian_mixture', device=device, process_group=process_group,
+                                    engine_factory=engine_factory, native_parameters=native_parameters)
+        om = self.model.output_model
+        prior = np.asarray(weights_prior, dtype=np.float64)
+        if prior.ndim not in (0, 2) or (prior.ndim == 2 and prior.shape != (nstates, om.ncomponents)):
+            raise ValueError('weights_prior must be a scalar or have shape (%d, %d)' % (nstates, om.ncomponents))
+        if not np.all(np.isfinite(prior)) or np.any(prior < 0.0):
+            raise ValueError('weights_prior must be >= 0 and finite')
+        self.prior_w = np.ascontiguousarray(np.broadcast_to(prior, (nstates, om.ncomponents)), dtype=np.float64)
+        self.component_labels = None
+
+    def _update_mixture_native(self, packed):
+        if self._draw is None:
+            from ._native import GibbsParametersGmm
+            om = self.model.output_model
+            self._draw = GibbsParametersGmm(
+                self.nstates, om.ncomponents, om.dimension, om.covariance_type, prior_C=self.prior_C,
+                prior_n0=self.prior_n0, prior_w=self.prior_w, reversible=self.reversible,
+                stationary=self.stationary, nsteps=self.transition_matrix_sampling_steps)
+        om = self.model.output_model
+        Tij, p0, w, mu, cov = self._draw(packed, om.weights, om.means, om.covariances, self._param_seed,
+                                         self._sweep)
+        from ..output_models.gaussian_mixture import pack_parameters
+        om.set_parameters(*pack_parameters(w, mu, cov))
         self.model.update(p0, Tij)

@@ -308,10 +308,11 @@ class SampledHMM(HMM):
         return np.array([np.asarray(getattr(h.output_model, name)) for h in self._sampled_hmms])
 
     def __getattr__(self, attr):
-        # means_* / sigmas_* (Gaussian), means_* / covariances_* (multivariate) and output_probabilities_* (discrete)
+        # means_* / sigmas_* (Gaussian), means_* / covariances_* (multivariate), weights_* (mixtures) and
+        # output_probabilities_* (discrete)
         if attr.startswith('_') or attr == 'output_model':
             raise AttributeError(attr)
-        for base in ('means', 'sigmas', 'covariances', 'output_probabilities'):
+        for base in ('means', 'sigmas', 'covariances', 'weights', 'output_probabilities'):
             if attr.startswith(base + '_') and hasattr(self.output_model, base):
                 x = self._output_samples(base)
                 kind = attr[len(base) + 1:]

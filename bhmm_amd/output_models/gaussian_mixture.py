@@ -193,6 +193,41 @@ class GaussianMixtureOutputModel(OutputModel):
         self._weights = S0 / tot[:, None]
         self._means, self._covs = means, covs
 
+    def sample_from_statistics(self, S0, S1, S2, rng=np.random, weights_prior=1.0):
+        """Gibbs update from the moments of the component labels of a hidden path about the current means (DESIGN.md
+        section 26; the rule of bhmm_gibbs_parameters_gmm in numpy, on rng's stream): S0 (N, M) counts, S1 (N, M, D),
+        S2 (N, M, D, D) or (N, M, D).  Means and covariances component by component as
+        MultivariateGaussianOutputModel.sample_from_statistics draws them per state (an empty component keeps both);
+        then per state w_i ~ Dirichlet(weights_prior + S0_i): a component with alpha = 0 takes weight exactly 0, a
+        state whose alpha are all 0 keeps its weights, M = 1 draws nothing.  weights_prior: a scalar or (N, M).
+        Returns the number of components whose covariance was kept because it could not be drawn."""
+        from .mvgaussian import MultivariateGaussianOutputModel
+        N, M, D = self.nstates, self._M, self._D
+        S0, S1, S2 = (np.asarray(a, dtype=np.float64) for a in (S0, S1, S2))
+        if S0.shape != (N, M) or S1.shape != (N, M, D) or S2.shape != self._cov_shape():
+            raise ValueError('moments must have shapes %r, %r and %r' % ((N, M), (N, M, D), self._cov_shape()))
+        prior = np.broadcast_to(np.asarray(weights_prior, dtype=np.float64), (N, M))
+        if not np.all(np.isfinite(prior)) or np.any(prior < 0.0):
+            raise ValueError('weights_prior must be >= 0 and finite')
+        flat = MultivariateGaussianOutputModel(N * M, self._means.reshape(N * M, D),
+                                               self._covs.reshape((N * M,) + self._cov_shape()[2:]),
+                                               covariance_type=self._covariance_type)
+        kept = flat.sample_from_statistics(S0.reshape(N * M), S1.reshape(N * M, D),
+                                           S2.reshape((N * M,) + S2.shape[2:]), rng=rng)
+        self._means = flat.means.reshape(N, M, D).copy()
+        self._covs = flat.covariances.reshape(self._cov_shape()).copy()
+        if M > 1:
+            alpha = prior + np.rint(S0)
+            w = self._weights.copy()
+            for i in range(N):
+                pos = alpha[i] > 0.0
+                if not pos.any():
+                    continue
+                w[i] = 0.0
+                w[i, pos] = rng.dirichlet(alpha[i, pos])
+            self._weights = w
+        return kept
+
     def _factor(self, i, c):
         cv = self._covs[i, c]
         return np.linalg.cholesky(cv) if self._covariance_type == 'full' else np.diag(np.sqrt(cv))

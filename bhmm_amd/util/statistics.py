@@ -29,12 +29,13 @@ def confidence_interval(data, alpha):
 
 def confidence_interval_arr(data, conf=0.95):
     """Element-wise (lower, upper) over the leading sample axis (statistics.py:103-151; the reference stops at
-    samples of matrices, the sampled covariances (N, D, D) of a multivariate model add one axis)."""
+    samples of matrices, the sampled covariances (N, D, D) of a multivariate model add one axis, the (N, M, D, D) of
+    a mixture model two)."""
     if conf < 0 or conf > 1:
         raise ValueError('Not a meaningful confidence level: ' + str(conf))
     data = np.array([np.asarray(d, dtype=np.float64) for d in data])
-    if data.ndim < 2 or data.ndim > 4:
-        raise NotImplementedError('Only supporting arrays of dimension 1 to 3 as yet.')
+    if data.ndim < 2 or data.ndim > 5:
+        raise NotImplementedError('Only supporting arrays of dimension 1 to 4 as yet.')
     lower = np.zeros(data.shape[1:])
     upper = np.zeros(data.shape[1:])
     for idx in np.ndindex(*data.shape[1:]):

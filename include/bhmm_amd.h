@@ -564,6 +564,37 @@ int bhmm_gmm_emissions(bhmm_ctx *ctx, int M, const double *weights, const double
 int bhmm_gmm_fetch_resp(bhmm_ctx *ctx, double *out);
 int bhmm_gmm_moments(bhmm_ctx *ctx, const double *gamma_dev, const double *means, int cov_type, double *out);
 
+/* The component of every step of a hidden path: what a Gibbs sweep of a mixture model needs
+ * between the path and the parameter draws.  Both calls use the table, M, covariance type and means of the last
+ * bhmm_gmm_emissions, which the context keeps (with or without want_resp: the responsibilities are neither read nor
+ * needed), and return BHMM_ERR_INVALID when the last emissions on these observations were not a mixture's.
+ *   bhmm_gmm_path_components: paths / path_u8 / paths_on_device as for bhmm_mvn_path_moments.  For every step, with
+ *     i = s_t, the components c of state i in ascending order, those of weight zero skipped:
+ *       a_c = log w_ic + l_tic, the running maximum a* and the rescaled sum s of bhmm_gmm_emissions' log-sum-exp
+ *       (a new maximum: s = s exp(a* - a_c) + 1, e = 1; else e = exp(a_c - a*), s += e);
+ *       the first component visited is the pick; a later one becomes the pick when u s < e,
+ *       u = uniform(key, g M + c) in [0, 1) -- the counter-based generator of bhmm_sample_paths, key one mix of seed
+ *       with a constant, g the position of the step in the random stream (its index, or with
+ *       bhmm_ctx_set_stream_offsets the trajectory's offset plus the step).
+ *     The pick is c with probability e_c / sum e = r_t(i, c) exactly: one pass, nothing stored per component.  A NaN
+ *     observation keeps the first component.  labels (host, int32[total], may be NULL): s_t M + c_t.  moments (host):
+ *     N * M blocks S0 | S1 | S2 of the labels about the means of those emissions, in the packed layout of
+ *     bhmm_gmm_moments, by the kernels of bhmm_mvn_path_moments (the same guarantees: no floating-point atomics,
+ *     the order of every sum a function of the labels alone).  A state outside [0, N) gives BHMM_ERR_INVALID (found
+ *     before anything is indexed by it; nothing is delivered).  Labels and moments are a function of the
+ *     observations, the path, the parameters, the seed and the stream offsets alone: bitwise the same from call to
+ *     call, for a host and a device path, for bytes and int32.  Synchronous.
+ *   bhmm_gmm_sample_paths: bhmm_sample_paths (par0 = par1 = emis = NULL) on the loaded mixture rows, then the draw
+ *     and the moments above on the path where the draw left it on the device, with the same seed (the two streams
+ *     are disjoint).  paths, counts and n0 are bitwise those of bhmm_sample_paths for the same arguments; paths and
+ *     labels (both may be NULL) cross the link only when given.
+ * Memory: 4 bytes per step for the labels; no buffer of total * N * M.  Read-only option: gmm_draw_ms (device time of
+ * the last component draw; mvn_path_moments_ms is that of the moment kernels that followed). */
+int bhmm_gmm_path_components(bhmm_ctx *ctx, const void *paths, int path_u8, int paths_on_device, uint64_t seed,
+                             int32_t *labels, double *moments);
+int bhmm_gmm_sample_paths(bhmm_ctx *ctx, const double *A, const double *pi, const double *u, uint64_t seed,
+                          int32_t *paths, int32_t *labels, int64_t *counts, int64_t *n0, double *moments);
+
 /* Gibbs hidden-path step (bayesian_sampling.py:283-331): forward pass + backward sampling
  * of every trajectory.  Uniforms come either from u (host, concatenated like obs; u[t]
  * used at step t) or, when u == NULL, from a counter-based generator seeded with `seed`.
@@ -801,6 +832,23 @@ int bhmm_host_mvn_mstep(int N, int D, int cov_type, const double *moments, const
 int bhmm_gibbs_parameters_mvn(int n, int D, int cov_type, const double *path_stats, const double *prior_C,
                               const double *prior_n0, int reversible, int stationary, int64_t nsteps, uint64_t seed,
                               uint64_t sweep, double *T, double *p0, double *means, double *covs, int32_t *info);
+
+/* The parameter draws of one Gibbs sweep for gaussian-mixture emissions per state, host only:
+ * path_stats = [C n*n | n0 n | the n * M packed blocks of bhmm_gmm_path_components], weights[n*M], means[n*M*D] and covs
+ * ([n*M*D*D] or [n*M*D]) in (current) and out (new); prior_w[n*M] >= 0 (NULL: zeros) the Dirichlet prior of the weights.
+ *   On the generator of (seed, sweep): the rule of bhmm_gibbs_parameters_mvn, unchanged, over the n * M components in
+ *   ascending order (an empty component keeps its mean and covariance), then the transition matrix and p0 over the n
+ *   states as in bhmm_gibbs_parameters.  At M = 1 T, p0, means and covs are bitwise those of
+ *   bhmm_gibbs_parameters_mvn on the same statistics.
+ *   On a generator of their own, (seed', sweep) with seed' one mix of seed with a constant: per state i in ascending
+ *   order w_i ~ Dirichlet(alpha_i), alpha_ic = prior_w[i,c] + S0_ic.  A component with alpha_ic = 0 takes weight exactly
+ *   0; a state whose alpha are all 0 keeps its weights; M = 1 consumes nothing.
+ * info: optional int32[3]: 64-bit draws consumed by the first generator, components whose covariance was kept (as
+ * info[1] of bhmm_gibbs_parameters_mvn), components of weight 0 after the call. */
+int bhmm_gibbs_parameters_gmm(int n, int M, int D, int cov_type, const double *path_stats, const double *prior_C,
+                              const double *prior_n0, const double *prior_w, int reversible, int stationary,
+                              int64_t nsteps, uint64_t seed, uint64_t sweep, double *T, double *p0, double *weights,
+                              double *means, double *covs, int32_t *info);
 
 /* building blocks of the two calls above, exported for the parity / property tests:
  * component label per state (sets numbered by decreasing size, _tmatrix_disconnected.py:28-43) */
