@@ -70,6 +70,8 @@ SIGNATURES = {
                                        c_double_p, ctypes.c_int]),
     "bhmm_logpdf_gmm": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                        c_double_p, c_double_p, c_double_p, ctypes.c_int]),
+    "bhmm_logpdf_poisson": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                           c_double_p]),
     "bhmm_update_pout": (ctypes.c_int, [c_double_p, c_int32_p, c_double_p, ctypes.c_int64,
                                         ctypes.c_int, ctypes.c_int]),
     "bhmm_ctx_create": (ctypes.c_int, [ctypes.POINTER(c_void_p), ctypes.c_int, c_void_p]),
@@ -130,6 +132,7 @@ SIGNATURES = {
                                                 c_int32_p, c_double_p]),
     "bhmm_gmm_sample_paths": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p, ctypes.c_uint64, c_int32_p,
                                              c_int32_p, c_int64_p, c_int64_p, c_double_p]),
+    "bhmm_pois_emissions": (ctypes.c_int, [c_void_p, c_double_p]),
     "bhmm_ctx_path_stats_size": (ctypes.c_int, [c_void_p]),
     "bhmm_ctx_set_stream_offsets": (ctypes.c_int, [c_void_p, c_int64_p]),
     "bhmm_sample_paths_dev": (ctypes.c_int, [c_void_p, c_double_p, c_double_p, c_double_p,
@@ -185,6 +188,7 @@ SIGNATURES = {
                                              c_double_p, c_double_p]),
     "bhmm_host_mvn_mstep": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
                                            ctypes.c_double, c_double_p, c_double_p]),
+    "bhmm_host_pois_mstep": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
     "bhmm_host_connected_sets": (ctypes.c_int, [c_int32_p, c_double_p, ctypes.c_int,
                                                 ctypes.c_double, ctypes.c_int]),
     "bhmm_host_stationary_vector": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int]),

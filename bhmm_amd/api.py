@@ -6,7 +6,7 @@ from .estimators.bayesian_sampling import BayesianHMMSampler
 from .estimators.maximum_likelihood import MaximumLikelihoodEstimator
 from .hmm import HMM, SampledHMM
 from .output_models import (DiscreteOutputModel, GaussianMixtureOutputModel, GaussianOutputModel,
-                            MultivariateGaussianOutputModel)
+                            MultivariateGaussianOutputModel, PoissonOutputModel)
 
 
 def _guess_output_type(observations):
@@ -18,7 +18,9 @@ def _guess_output_type(observations):
         return 'gaussian'
     if np.issubdtype(o1.dtype, np.floating) and o1.ndim == 2:
         return 'mvgaussian'
-    raise TypeError('Observations is neither sequences of integers nor 1D- or 2D-sequences of floats.')
+    if np.issubdtype(o1.dtype, np.integer) and o1.ndim == 2:
+        return 'poisson'        # (T, D) counts: binned multi-channel photon data
+    raise TypeError('Observations is neither 1D- or 2D-sequences of integers nor 1D- or 2D-sequences of floats.')
 
 
 class LaggedObservations(list):
@@ -74,6 +76,25 @@ def gaussian_mixture_hmm(pi, P, weights, means, covariances, covariance_type='fu
     nstates = len(means)
     return HMM(pi, P, GaussianMixtureOutputModel(nstates, weights, means, covariances,
                                                  covariance_type=covariance_type))
+
+
+def poisson_hmm(pi, P, rates):
+    """An HMM with Poisson count emissions: rates (nstates, D), one rate >= 0 per state and
+    channel; the observations are (T_k, D) arrays of counts."""
+    nstates = len(rates)
+    return HMM(pi, P, PoissonOutputModel(nstates, rates))
+
+
+def init_poisson_hmm(observations, nstates, lag=1, reversible=True):
+    """Initial model for (T_k, D) count observations, deterministic, numpy only: the seeding and Lloyd iterations of
+    init_mvgaussian_hmm on the variance-stabilised counts sqrt(x + 3/8), rates from the cluster means of the raw
+    counts (a channel that is all zero in a cluster gets 0.5 / its points), refined by a few EM iterations of the
+    Poisson mixture, and a transition matrix from the count matrix of the labels at the lag
+    (bhmm_amd/init/poisson.py)."""
+    from .init.poisson import init_model_poisson
+    hmm0 = init_model_poisson(observations, nstates, lag=lag, reversible=reversible)
+    hmm0._lag = lag
+    return hmm0
 
 
 def init_gaussian_mixture_hmm(observations, nstates, ncomponents, lag=1, reversible=True, covariance_type='full'):
@@ -132,6 +153,8 @@ def init_hmm(observations, nstates, lag=1, output=None, reversible=True, ncompon
         return init_gaussian_hmm(observations, nstates, lag=lag, reversible=reversible)
     if output == 'mvgaussian':
         return init_mvgaussian_hmm(observations, nstates, lag=lag, reversible=reversible)
+    if output == 'poisson':
+        return init_poisson_hmm(observations, nstates, lag=lag, reversible=reversible)
     if output == 'gaussian_mixture':
         if ncomponents is None:
             raise ValueError("output='gaussian_mixture' needs ncomponents")
@@ -156,11 +179,17 @@ def estimate_hmm(observations, nstates, lag=1, initial_model=None, output=None, 
     return est.hmm
 
 
+def _refuse_poisson(estimated_hmm):
+    if estimated_hmm.output_model.model_type == 'poisson':
+        raise NotImplementedError('Poisson count emissions have no Gibbs sampler yet (DESIGN.md section 27)')
+
+
 def bayesian_hmm(observations, estimated_hmm, nsample=100, reversible=True, stationary=False,
                  p0_prior='mixed', transition_matrix_prior='mixed', store_hidden=False,
                  call_back=None, **engine_kwargs):
     """bhmm/api.py:375-470.  Returns a SampledHMM (which also iterates over / indexes the
     sampled models)."""
+    _refuse_poisson(estimated_hmm)
     if estimated_hmm.output_model.model_type == 'mvgaussian':
         raise NotImplementedError('multivariate gaussian emissions are sampled by bayesian_mvgaussian_hmm, '
                                   'not by bayesian_hmm yet')
@@ -188,6 +217,7 @@ def bayesian_mvgaussian_hmm(observations, estimated_hmm, nsample=100, reversible
     covariances_std, covariances_conf ... summarise the sampled emission parameters.  Sampled models are not
     relabelled (label switching is the user's to watch, as in the reference).  engine_kwargs: device, seed (of the
     chain; one from numpy's global generator if not given), native_parameters."""
+    _refuse_poisson(estimated_hmm)
     if estimated_hmm.output_model.model_type == 'gaussian_mixture':
         raise NotImplementedError('the Gibbs sampler for gaussian-mixture emissions is '
                                   'bayesian_gaussian_mixture_hmm')
@@ -219,6 +249,7 @@ def bayesian_gaussian_mixture_hmm(observations, estimated_hmm, nsample=100, reve
     means_* and covariances_* as for the multivariate gaussian kind with the component axis after the state's;
     bhmm_amd.score takes it.  Sampled models are not relabelled: label switching, between states and between the
     components of a state, is the user's to watch.  engine_kwargs: device, native_parameters."""
+    _refuse_poisson(estimated_hmm)
     if estimated_hmm.output_model.model_type != 'gaussian_mixture':
         raise ValueError("bayesian_gaussian_mixture_hmm takes a model with gaussian-mixture emissions, not %r"
                          % (estimated_hmm.output_model.model_type,))
@@ -235,10 +266,12 @@ def bayesian_gaussian_mixture_hmm(observations, estimated_hmm, nsample=100, reve
 
 def _engine_for(output, device):
     """The engine of an output type: multivariate gaussian models run on an MvnEngine, gaussian mixtures on a
-    GmmEngine."""
-    from .engine import Engine, GmmEngine, MvnEngine
+    GmmEngine, Poisson count models on a PoissonEngine."""
+    from .engine import Engine, GmmEngine, MvnEngine, PoissonEngine
     if output == 'gaussian_mixture':
         return GmmEngine(device)
+    if output == 'poisson':
+        return PoissonEngine(device)
     return MvnEngine(device) if output == 'mvgaussian' else Engine(device)
 
 

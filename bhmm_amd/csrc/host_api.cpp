@@ -135,6 +135,17 @@ extern "C" int bhmm_host_mvn_mstep(int N, int D, int cov_type, const double *mom
     return mvn_mstep(N, D, cov_type, moments, means_old, min_covar, means_new, covs_new);
 }
 
+// ---- Poisson count emissions ------------------------------------------
+extern "C" int bhmm_host_pois_mstep(int N, int D, const double *moments, const double *rates_old, double *rates_new)
+{
+    if (int rc = mvn_shape_ok("bhmm_host_pois_mstep", N, D, BHMM_COV_DIAG))
+        return rc;
+    if (!moments || !rates_old || !rates_new)
+        return bhmm::invalid_arg("bhmm_host_pois_mstep: NULL argument");
+    pois_mstep(N, D, moments, rates_old, rates_new);
+    return BHMM_OK;
+}
+
 // ---- emission M-steps ------------------------------------------------------------------------
 // gaussian.py:214-272 from  sum gamma, sum gamma (o - mu_old), sum gamma (o - mu_old)^2: the new mean
 // is mu_old + <d>, the variance around the NEW mean <d^2> - <d>^2.

@@ -802,6 +802,20 @@ int mvn_mstep(int n, int D, int cov_type, const double *moments, const double *m
     return mvn_prepare(n, D, cov_type, covs_new, nullptr, nullptr, nullptr);
 }
 
+void pois_mstep(int n, int D, const double *moments, const double *rates_old, double *rates_new)
+{
+    const size_t ms = mvn_moment_stride(D, 1);
+    for (int i = 0; i < n; ++i) {
+        const double *m = moments + (size_t)i * ms;
+        const double w = m[0], *s1 = m + 1;
+        for (int d = 0; d < D; ++d) {
+            const double old = rates_old[(size_t)i * D + d];
+            // (the mean of the counts about the old rate; rounding may leave it a hair below zero)
+            rates_new[(size_t)i * D + d] = w > 0.0 ? std::max(0.0, old + s1[d] / w) : old;
+        }
+    }
+}
+
 // Cholesky-Banachiewicz of the symmetric S (lower triangle read) into L (lower, zeros above).  false: not positive
 // definite -- a pivot that is not finite or not above 1e-12 of its diagonal entry counts as zero (the scatter of
 // points in a subspace leaves rounding residue of either sign there)

@@ -95,5 +95,11 @@ int mvn_mstep(int n, int D, int cov_type, const double *moments, const double *m
 int mvn_gibbs_emissions(int n, int D, int cov_type, const double *moments, Rng &rng, double *means, double *covs,
                         int32_t *kept);
 
+
+// ---- Poisson count emissions ----
+// new rates from the packed moments of bhmm_mvn_moments with BHMM_COV_DIAG about rates_old (the second-moment block is
+// not read): lambda' = max(0, lambda + S1 / S0); a state with S0 = 0 keeps its rates
+void pois_mstep(int n, int D, const double *moments, const double *rates_old, double *rates_new);
+
 } // namespace host
 } // namespace bhmm

@@ -47,6 +47,13 @@ class EStepResult(object):
             size = n * M * moment_stride(dimension, covariance_type)
             self.moments = packed[o:o + size].copy(); o += size
             self.S0, self.S1, self.S2 = unpack_component_moments(self.moments, n, M, dimension, covariance_type)
+        # poisson counts: the moments of bhmm_mvn_moments with diagonal second moments about the rates of the
+        # E-step's model -- S0 (n,), S1 (n, D); S2 (n, D) comes along and is not used by the M-step
+        if kind == 'poisson':
+            from .output_models.mvgaussian import moment_stride, unpack_moments
+            size = n * moment_stride(dimension, 'diag')
+            self.moments = packed[o:o + size].copy(); o += size
+            self.S0, self.S1, self.S2 = unpack_moments(self.moments, n, dimension, 'diag')
 
 
 class PathRuns(object):
@@ -1420,6 +1427,109 @@ class GmmEngine(MvnEngine):
     def unpack(self, packed, logL_k=None):
         return EStepResult('gaussian_mixture', self.nstates, self.ncomponents, np.asarray(packed), logL_k,
                            self.dimension, self._cov_last or 'full')
+
+
+class PoissonEngine(MvnEngine):
+    """Engine for Poisson count emissions (kind 'poisson'): the observations are (T_k, D) arrays
+    of counts (integer or float dtype; held as float64 on the device), a model is (A, pi, rates (n, D), None).
+    Everything runs as in MvnEngine on the explicit rows bhmm_pois_emissions makes; the step scales are m_t + c_t with
+    c_t = -sum_d log(x_td !), so every log-likelihood, path log-probability and filter increment is that of the
+    complete density.  An E-step makes the rows, runs ONE pass of the recursions that leaves gamma on the device and
+    takes the moments about the loaded rates (bhmm_mvn_moments with diagonal second moments, which go unused)."""
+
+    def _set(self, ptr, off, nstates, D, chunk, on_device):
+        MvnEngine._set(self, ptr, off, nstates, D, chunk, on_device)
+        self.kind = 'poisson'
+
+    def set_observations(self, kind, observations, nstates, nsymbols=0, chunk=0):
+        """observations: list of (T_k, D) arrays of counts, 1 <= D <= 64; a negative or fractional value is refused."""
+        if kind != 'poisson':
+            raise ValueError("a PoissonEngine holds observations of kind 'poisson', not %r" % (kind,))
+        from .output_models.poisson import check_observation
+        MvnEngine.set_observations(self, 'mvgaussian', [check_observation(o) for o in observations], nstates,
+                                   chunk=chunk)
+
+    def set_observations_device(self, kind, dev_ptr, offsets, nstates, nsymbols=0, chunk=0, dimension=None):
+        """The same for a (sum T_k, D) row-major float64 buffer of counts already on this GPU; its values are checked
+        by the kernel that makes the rows (ValueError from the first model call)."""
+        if kind != 'poisson':
+            raise ValueError("a PoissonEngine holds observations of kind 'poisson', not %r" % (kind,))
+        MvnEngine.set_observations_device(self, 'mvgaussian', dev_ptr, offsets, nstates, chunk=chunk,
+                                          dimension=dimension)
+
+    def set_observations_lagged(self, *args, **kwargs):
+        raise NotImplementedError("lagged views are cut on the host for multivariate observations")
+
+    @property
+    def stats_size(self):
+        """The explicit kind's vector followed by the moment block (diagonal second moments)."""
+        from .output_models.mvgaussian import moment_stride
+        return self._ctx_stats_size() + self.nstates * moment_stride(self.dimension, 'diag')
+
+    def _params(self, par0, par1):
+        """rates (n, D) of one model, checked (before anything loaded is given up)."""
+        if self.dimension == 0:
+            raise ValueError("no observations loaded")
+        if par0 is None:
+            raise ValueError("poisson emissions need rates")
+        if par1 is not None:
+            raise ValueError("poisson emissions take par0 = rates and par1 = None")
+        n, D = self.nstates, self.dimension
+        rates = _lib.f64(par0)
+        if rates.shape != (n, D):
+            raise ValueError("rates must be (%d, %d), not %r" % (n, D, rates.shape))
+        if not np.all(np.isfinite(rates)) or np.any(rates < 0.0):
+            raise ValueError("rates must be finite and not negative")
+        return rates
+
+    def emissions(self, par0, par1=None, force=False):
+        """Make the emission rows of `rates` the context's observations, unless the loaded ones were made from the
+        same rates (force: make them anyway).  Returns 'diag', the layout of the moments."""
+        rates = self._params(par0, par1)
+        ld = self._loaded
+        if not force and ld is not None and np.array_equal(ld[0], rates):
+            return 'diag'
+        self._loaded = self._shift = self._m_t = self._moments = None   # (the re-load ends the last E-step too)
+        _lib.check(self._L.bhmm_pois_emissions(self._h, _lib.dp(rates)))
+        self._stage = None
+        self._fetch = None
+        shift = np.empty(len(self.lengths))
+        _lib.check(self._L.bhmm_mvn_fetch_scale(self._h, _lib.dp(shift), None))
+        self._shift = shift
+        self._loaded = (rates.copy(), None)
+        return 'diag'
+
+    def sample_paths_moments(self, *args, **kwargs):
+        raise NotImplementedError("Poisson count emissions have no Gibbs sweep yet")
+
+    # -- E-step --------------------------------------------------------------------------
+    def estep_launch(self, A, pi, par0=None, par1=None, stats_dev=None, store_gamma=False, single=False):
+        """One E-step: rows, ONE pass of the recursions that leaves the posterior rows on the device
+        (Engine.posterior_marginals), the moments from them about the loaded rates.  Synchronous."""
+        if stats_dev is not None:
+            raise NotImplementedError("poisson E-steps keep their statistics in the context")
+        if single:
+            raise NotImplementedError("poisson E-steps run in float64")
+        self.emissions(par0, par1)
+        import torch
+        total = int(self.offsets[-1])
+        g = self._gamma_dev
+        if g is None or g.numel() != total * self.nstates or g.device.index != self.device:
+            g = self._gamma_dev = torch.empty(total * self.nstates, dtype=torch.float64,
+                                              device='cuda:%d' % self.device)
+        Engine.posterior_marginals(self, A, pi, out=g.data_ptr())
+        self._moments = self.moments(g.data_ptr(), self._loaded[0], 'diag')
+        self._cov_last = 'diag'
+
+    def estep_fetch(self):
+        if self._moments is None:
+            raise ValueError("no E-step has run on these observations")
+        res = Engine.estep_fetch(self)
+        return EStepResult('poisson', self.nstates, 0, self._shifted(res.packed), res.logL_k + self._shift,
+                           self.dimension)
+
+    def unpack(self, packed, logL_k=None):
+        return EStepResult('poisson', self.nstates, 0, np.asarray(packed), logL_k, self.dimension)
 
 
 def stack_models(kind, nstates, nsymbols, models):

@@ -51,6 +51,9 @@ class BayesianHMMSampler(object):
         if len(observations) == 0:
             raise Exception("No observations were provided.")
         kind = initial_model.output_model.model_type if initial_model else output
+        if kind == 'poisson':
+            # (the kind has EM only so far)
+            raise NotImplementedError('Poisson count emissions have no Gibbs sampler yet')
         if kind == 'gaussian_mixture' and not self._mixture:
             # (mixtures per state have a sampler class of their own)
             raise NotImplementedError('the Gibbs sampler for gaussian-mixture emissions is '

@@ -35,7 +35,15 @@ def _gmm_engine_factory(device):
     return GmmEngine(device)
 
 
-_MULTIVARIATE = ('mvgaussian', 'gaussian_mixture')   # kinds on (T, D) observations: the same branches throughout
+def _poisson_engine_factory(device):
+    from ..engine import PoissonEngine
+    return PoissonEngine(device)
+
+
+# kinds on (T, D) observations: the same branches throughout
+_MULTIVARIATE = ('mvgaussian', 'gaussian_mixture', 'poisson')
+_MULTIVARIATE_NAMES = {'mvgaussian': 'multivariate gaussian', 'gaussian_mixture': 'gaussian-mixture',
+                       'poisson': 'poisson'}
 
 
 def default_device(comm):
@@ -169,15 +177,15 @@ class MaximumLikelihoodEstimator(object):
         self._device = device
         self._comm.bind_device(device)       # collectives run on the engine's GPU, not on "current"
         if self._output in _MULTIVARIATE:
-            # multivariate gaussian and gaussian-mixture emissions (DESIGN.md sections 23, 25): single process, fp64
-            # E-steps
-            name = 'multivariate gaussian' if self._output == 'mvgaussian' else 'gaussian-mixture'
+            # multivariate gaussian, gaussian-mixture and poisson emissions (DESIGN.md sections 23, 25, 27): single
+            # process, fp64 E-steps
+            name = _MULTIVARIATE_NAMES[self._output]
             if process_group is not None:
                 raise NotImplementedError('%s emissions do not run over a process_group yet' % name)
             if estep_precision != 'float64':
                 raise NotImplementedError("%s E-steps run in float64 (estep_precision=%r)" % (name, estep_precision))
-        factory = engine_factory or {'mvgaussian': _mvn_engine_factory, 'gaussian_mixture': _gmm_engine_factory
-                                     }.get(self._output, _default_engine_factory)
+        factory = engine_factory or {'mvgaussian': _mvn_engine_factory, 'gaussian_mixture': _gmm_engine_factory,
+                                     'poisson': _poisson_engine_factory}.get(self._output, _default_engine_factory)
         self._engine = factory(device)
         M = self._hmm.output_model.nsymbols if self._output == 'discrete' else 0
         self._nsymbols = M

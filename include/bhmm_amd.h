@@ -110,6 +110,13 @@ int bhmm_logpdf_mvn(double *logp, const double *X, int64_t T, int D, int N, cons
 int bhmm_logpdf_gmm(double *logp, const double *X, int64_t T, int D, int N, int M, const double *weights,
                     const double *means, const double *covs, int cov_type);
 
+/* Poisson log-densities of counts, beside bhmm_logpdf_mvn: logp[t*N + i] =
+ * sum_d [x_td log lambda_id - lambda_id - log(x_td !)] for X[T*D] row-major (counts held as doubles) and
+ * rates[N*D], formed by the kernel of bhmm_pois_emissions (below, where the rules are described).  A rate that is
+ * negative or not finite, a count that is negative or not an integer, D outside 1..BHMM_MVN_MAX_D: BHMM_ERR_INVALID.
+ * Host pointers, synchronous. */
+int bhmm_logpdf_poisson(double *logp, const double *X, int64_t T, int D, int N, const double *rates);
+
 /* ------------------------------------------------------------------------------------
  * (2) batched device-resident context
  * ---------------------------------------------------------------------------------- */
@@ -595,6 +602,26 @@ int bhmm_gmm_path_components(bhmm_ctx *ctx, const void *paths, int path_u8, int 
 int bhmm_gmm_sample_paths(bhmm_ctx *ctx, const double *A, const double *pi, const double *u, uint64_t seed,
                           int32_t *paths, int32_t *labels, int64_t *counts, int64_t *n0, double *moments);
 
+/* Poisson count emissions, on the observations of bhmm_ctx_set_observations_mvn (counts held
+ * as doubles, D channels): state i has a rate lambda_id >= 0 per channel, log b_i(x_t) = sum_d [x_td log lambda_id -
+ * lambda_id - log(x_td !)].  The recursions need nothing new: they run on explicit rows.
+ *   bhmm_pois_emissions validates rates[N*D] (negative or not finite: BHMM_ERR_INVALID, nothing changes), forms
+ *       l_ti = sum_d x_td log lambda_id - Lambda_i      (log lambda in long double, rounded once, log 0 = -inf;
+ *                                                        Lambda_i = sum_d lambda_id in ascending d; one fma per
+ *                                                        channel in ascending d)
+ *     where a channel with x_td = 0 is skipped -- it contributes exactly 0 whatever the rate -- and a positive count
+ *     under rate 0 gives -inf; m_t = max_i l_ti and the rows exp(l_ti - m_t) (every finite row has maximum exactly
+ *     1.0); a step that every state gives probability zero: a row of zeros and m_t = 0, so that the recursions give
+ *     -inf for that trajectory only.  c_t = -sum_d log(x_td !) does not depend on the state: the step scale kept is
+ *     m_t + c_t, shift_k their sum per trajectory, so that bhmm_mvn_fetch_scale, the filter increments and every
+ *     log-likelihood carry the complete density.  Rows, scales and shifts go into the buffers of bhmm_mvn_emissions
+ *     and are loaded the same way; bhmm_mvn_fetch_scale and bhmm_mvn_fetch_rows deliver them, the read-only option
+ *     mvn_rows_ms the device time.  A NaN count makes its row, scale and shift_k NaN.  A count that is negative or not
+ *     an integer: BHMM_ERR_INVALID, no rows are loaded.
+ * The moments of the M-step and of a hidden path are bhmm_mvn_moments / bhmm_mvn_path_moments with BHMM_COV_DIAG about
+ * the rates (their second-moment block is not used). */
+int bhmm_pois_emissions(bhmm_ctx *ctx, const double *rates);
+
 /* Gibbs hidden-path step (bayesian_sampling.py:283-331): forward pass + backward sampling
  * of every trajectory.  Uniforms come either from u (host, concatenated like obs; u[t]
  * used at step t) or, when u == NULL, from a counter-based generator seeded with `seed`.
@@ -812,6 +839,11 @@ int bhmm_gibbs_parameters(int kind, int n, int M, const double *path_stats, cons
 int bhmm_host_mvn_prepare(int N, int D, int cov_type, const double *covs, double *chol, double *winv, double *cst);
 int bhmm_host_mvn_mstep(int N, int D, int cov_type, const double *moments, const double *means_old,
                         double min_covar, double *means_new, double *covs_new);
+
+/* Poisson count emissions, host side: from the moments of bhmm_mvn_moments with BHMM_COV_DIAG
+ * about rates_old[N*D] (N * (1 + 2 D) doubles, the second-moment block is not read), lambda' = max(0, lambda +
+ * S1 / S0) into rates_new[N*D]; a state with S0 = 0 keeps its rates. */
+int bhmm_host_pois_mstep(int N, int D, const double *moments, const double *rates_old, double *rates_new);
 
 /* The parameter draws of one Gibbs sweep for multivariate gaussian emissions: as
  * bhmm_gibbs_parameters, with path_stats = [C n*n | n0 n | packed moments of bhmm_mvn_path_moments about `means`],
