@@ -52,12 +52,14 @@ int gen_transposed(bhmm_ctx *c, const WideModel &m)
     return BHMM_OK;
 }
 
-int gen_launch_forward(bhmm_ctx *c, const WideModel &m, const double *pobs)
+// rescue: the E-step's forward pass (k_gen_forward<.., RESCUE>)
+int gen_launch_forward(bhmm_ctx *c, const WideModel &m, const double *pobs, bool rescue = false)
 {
     size_t sm = gen_smem(c->n, 2, 2);
     const bool alds = gen_a_in_lds(c->n, sm);
     sm += alds ? gen_a_bytes(c->n) : 0;
-    auto *k = alds ? k_gen_forward<true> : k_gen_forward<false>;
+    auto *k = rescue ? (alds ? k_gen_forward<true, true> : k_gen_forward<false, true>)
+                     : (alds ? k_gen_forward<true> : k_gen_forward<false>);
     BHMM_HIP(launch(k, dim3(c->K), dim3(GEN_TPB), sm, c->stream, m, c->d_offsets.p, c->K, pobs, c->d_alpha_rm.p,
                     c->d_logLk.p));
     return BHMM_OK;
@@ -147,7 +149,7 @@ int gen_estep(bhmm_ctx *c, const double *A, const double *pi, const double *par0
     if ((rc = gen_pobs(c, m, &pobs)))
         return rc;
     BHMM_HIP(hipEventRecord(c->ev[1], c->stream));
-    if ((rc = gen_launch_forward(c, m, pobs)))
+    if ((rc = gen_launch_forward(c, m, pobs, true)))
         return rc;
     BHMM_HIP(hipEventRecord(c->ev[2], c->stream));
     if (c->kind == EMIT_DISC)

@@ -253,7 +253,11 @@ __device__ __forceinline__ double gen_block_sum(double v, double *red)
 }
 
 // _hidden.c:16-66.  alpha rows (total, n) row-major, logL per trajectory.
-template <bool ALDS>
+// RESCUE (the E-step; not the calls that hand the reference's own rows to the caller): a step whose sum is zero or
+// in the denormal range -- an emission row at the bottom of the double range, whose products with the predicted
+// vector round on the denormal grid or vanish -- is formed again with the row times 2^900 (exact), and the
+// exponent comes off the log-likelihood.  A sum that is zero then too is a probability of zero, as before.
+template <bool ALDS, bool RESCUE = false>
 __global__ __launch_bounds__(GEN_TPB) void k_gen_forward(const WideModel m, const int64_t *off, int K,
                                                           const double *pobs, double *alpha,
                                                           double *logL)
@@ -295,7 +299,21 @@ __global__ __launch_bounds__(GEN_TPB) void k_gen_forward(const WideModel m, cons
         // (the logarithm of the previous step's sum: in the shadow of the other wavefronts' products)
         if (tid == GEN_TPB - 1 && t > 0)
             ll += log(cprev);
-        const double c = gen_ordered_sum(ya, n, slot);
+        double c = gen_ordered_sum(ya, n, slot);
+        if constexpr (RESCUE) {
+            if (__builtin_expect(!(c >= 0x1p-959), 0)) { // (the same value in every thread)
+                for (int j = tid; j < n; j += GEN_TPB) {
+                    const double pj = ldexp(j == tid ? pmine : p[j], 900);
+                    ya[j] = (t == 0 ? m.pi[j] : gen_dot<ALDS>(Amat + j, n, xa, n)) * pj;
+                }
+                const double c2 = gen_ordered_sum(ya, n, slot);
+                if (c2 > 0.0) {
+                    c = c2;
+                    if (tid == GEN_TPB - 1)
+                        ll -= 900.0 * 0.693147180559945309417232121458;
+                }
+            }
+        }
         cprev = c;
         double *out = alpha + (t0 + t) * n;
         for (int j = tid; j < n; j += GEN_TPB) {
@@ -360,8 +378,22 @@ __global__ __launch_bounds__(GEN_TPB) void k_gen_backward(
             for (int i = tid; i < n; i += GEN_TPB)
                 cur[i] = gen_dot3<ALDS>(Atm + i, n, np, nb, n);
         }
-        const double c = gen_ordered_sum(cur, n, slot);
+        double c = gen_ordered_sum(cur, n, slot);
+        [[maybe_unused]] int resc = 0; // exponent put on the next row to keep this sum in range
         if constexpr (STATS) {
+            // (the E-step: as k_gen_forward<.., RESCUE> -- a sum that is zero or in the denormal range is formed
+            // again with the next row times 2^900; beta is normalised, the factor does not show)
+            if (t < T - 1 && __builtin_expect(!(c >= 0x1p-959), 0)) {
+                for (int i = tid; i < n; i += GEN_TPB) {
+                    double s2 = 0.0;
+                    const double *Ar = Atm + i;
+                    for (int j = 0; j < n; ++j)
+                        s2 += Ar[(int64_t)j * n] * (ldexp(np[j], 900) * nb[j]);
+                    cur[i] = s2;
+                }
+                c = gen_ordered_sum(cur, n, slot);
+                resc = 900;
+            }
             if (t < T - 1) {
                 // S_t = sum_i alpha_t[i] cur[i] (cur still unnormalised), then W_t from the row t+1
                 const double *a = alpha + (t0 + t) * n;
@@ -376,6 +408,7 @@ __global__ __launch_bounds__(GEN_TPB) void k_gen_backward(
                 if (c > 0.0) {
                     int ec;
                     (void)frexp(c, &ec);
+                    ec -= resc;
                     kx = -ec > 64 ? (-ec < 900 ? -ec : 900) : 0;
                 }
                 if (kx > 0) {

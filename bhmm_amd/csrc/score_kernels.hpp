@@ -55,6 +55,18 @@ __device__ __forceinline__ void score_emit(const Model<N> &m, const double *Bt, 
 #pragma unroll
         for (int j = 0; j < N; ++j)
             p[j] = Bt[(int64_t)o * BS + j];
+        // a column of B in the denormal range: times 2^900, exactly (its product with the vector would round on the
+        // denormal grid)
+        double mx = 0.0;
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+            mx = fmax(mx, p[j]);
+        if (__builtin_expect(mx < 0x1p-959 && mx > 0.0, 0)) {
+#pragma unroll
+            for (int j = 0; j < N; ++j)
+                p[j] = ldexp(p[j], 900);
+            pexp = -900;
+        }
     } else {
         double mx = 0.0;
 #pragma unroll
@@ -280,6 +292,16 @@ __global__ __launch_bounds__(32 * N) void k_score_pair(const Model<N> *__restric
             const double2 r = *reinterpret_cast<const double2 *>(Bt + (int64_t)o * BS + 2 * q);
             p[0] = r.x;
             p[1] = r.y;
+            double mx = fmax(p[0], p[1]); // (padded states: zero)
+            if constexpr (H >= 2)
+                mx = fmax(mx, grp_xor<1>(mx));
+            if constexpr (H >= 4)
+                mx = fmax(mx, grp_xor<2>(mx));
+            if (__builtin_expect(mx < 0x1p-959 && mx > 0.0, 0)) { // (group-uniform) as score_emit
+                p[0] = ldexp(p[0], 900);
+                p[1] = ldexp(p[1], 900);
+                pe = -900;
+            }
         } else {
             p[0] = real0 ? gauss_pdf<true>(o - mu[0], ea[0], eb[0], m.emg) : 0.0;
             p[1] = real1 ? gauss_pdf<true>(o - mu[1], ea[1], eb[1], m.emg) : 0.0;
@@ -456,15 +478,15 @@ __global__ __launch_bounds__(1024) void k_score_serial(int n, int M, int K, cons
             }
             pmx = fmax(pmx, p[r]);
         }
+        // a row in the denormal range, of any kind (entries of B, explicit pobs): times 2^900, exactly -- the
+        // product with alpha would round on the denormal grid.  An all-zero gaussian row is a row of ones
         int pe = 0;
-        if constexpr (KIND == EMIT_GAUSS) {
-            pmx = score_block_reduce(pmx, true, red);
-            if (pmx < 0x1p-959) {
+        pmx = score_block_reduce(pmx, true, red);
+        if (pmx < 0x1p-959 && (KIND == EMIT_GAUSS || pmx > 0.0)) {
 #pragma unroll
-                for (int r = 0; r < SCORE_SERIAL_R; ++r)
-                    p[r] = tid + r * bd < n ? (pmx == 0.0 ? 1.0 : ldexp(p[r], 900)) : 0.0;
-                pe = pmx == 0.0 ? 0 : -900;
-            }
+            for (int r = 0; r < SCORE_SERIAL_R; ++r)
+                p[r] = tid + r * bd < n ? (pmx == 0.0 ? 1.0 : ldexp(p[r], 900)) : 0.0;
+            pe = pmx == 0.0 ? 0 : -900;
         }
         double mx = 0.0;
 #pragma unroll

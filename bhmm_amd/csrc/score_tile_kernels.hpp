@@ -16,6 +16,9 @@
 //                  step goes to HBM.
 //                  A row that leaves the range of the refresh (a vector below 2^-900, an all-zero one, a sum
 //                  that is zero or not finite) counts in flags[3 model]: that model's numbers are not used.
+//                  The exponent is measured on the step before the one that takes it off, so up to four steps
+//                  lie between the last look and a segment's end; they are held to the same bound after the
+//                  loop: an exit sum, or an entry sum, below 2^-900 (WIDE_RANGE_MIN) counts there as well.
 //   k_score_tile_check  every derived entry vector against the predecessor's exit vector, componentwise
 //                  relative after normalisation (k_score_wide_check); per model the failures in
 //                  flags[3 model + 1] and the largest deviation, as the bits of a float, in flags[3 model + 2]
@@ -337,7 +340,10 @@ __global__ __launch_bounds__(SCORE_TILE_THREADS) void k_score_tile(const ScoreTi
         atomicAdd(&flags[SCORE_TILE_FLAGS * ms], 1u);
     __syncthreads();
     if (c_rec >= 0 && sl == 0) {
-        const bool bad = !(S_end > 0.0) || !(S_start > 0.0) || !(S_end < INFINITY) || !(S_start < INFINITY);
+        // (the steps after the last refresh are looked at here: a sum below the refresh's range may have lost bits to
+        // the denormal grid)
+        const bool bad = !(S_end >= WIDE_RANGE_MIN) || !(S_start >= WIDE_RANGE_MIN) || !(S_end < INFINITY) ||
+                         !(S_start < INFINITY);
         constexpr double LN2 = 0.693147180559945309417232121458;
         logLc[c_rec] = bad ? 0.0 : (log(S_end) - log(S_start)) + sEP[srow] * LN2;
         if (bad)

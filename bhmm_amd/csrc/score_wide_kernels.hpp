@@ -12,7 +12,10 @@
 //                  LAZY: the vector is carried up to a power of two that is refreshed every fourth step
 //                  (k_wide_fwd<.., LAZY>); a vector that leaves the range between two refreshes -- an all-zero
 //                  one and one that overflows included -- counts as a failure of the model (fails[model]),
-//                  never as a number.
+//                  never as a number.  The refresh looks at the steps before it; the one to three steps between
+//                  the last refresh and the segment's end (all of a segment of one to three steps) are held to
+//                  the same bound after the loop: an exit sum, or an entry sum, below 2^-900 (WIDE_RANGE_MIN) is
+//                  such a failure too -- a sum in the denormal range holds only a few bits.
 //                  Otherwise: normalised by its sum every step, a sum in the denormal range is rescued by
 //                  2^900, and a sum that is exactly zero makes the segment's log-normaliser -inf.
 //   k_score_wide_check  the forward half of k_wide_check per model: every derived entry vector against the
@@ -185,8 +188,12 @@ __global__ __launch_bounds__(64) void k_score_wide(const ScoreWideModel *__restr
         a_exit[rec * n + j] = a;
     constexpr double LN2 = 0.693147180559945309417232121458;
     if constexpr (LAZY) {
+        // the steps after the last refresh (all of them in a segment of one to three steps) are looked at here: an
+        // exit sum below the refresh's range may have lost bits to the denormal grid.  The entry sum is taken right
+        // after a refresh and is held to the same bound
         const double S_end = wgroup_sum<NP>(a);
-        trouble |= !(S_end > 0.0) || !(S_start > 0.0) || !(S_end < INFINITY) || !(S_start < INFINITY);
+        trouble |= !(S_end >= WIDE_RANGE_MIN) || !(S_start >= WIDE_RANGE_MIN) || !(S_end < INFINITY) ||
+                   !(S_start < INFINITY);
         if (j == 0) {
             logLc[rec] = trouble ? 0.0 : (log(S_end) - log(S_start)) + eP * LN2;
             if (trouble)

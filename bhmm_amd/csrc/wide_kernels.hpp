@@ -378,6 +378,9 @@ struct Segs {
 // removed in between).  A vector whose largest element falls below 2^-900 between two refreshes
 // raises flags[2]; the host then repeats the E-step with the per-step normalisation.
 #define WIDE_TROUBLE_EXP (-900)
+// the same bound for a sum taken between two refreshes (the score kernels' exit and entry sums)
+constexpr double WIDE_RANGE_MIN = 0x1p-900;
+static_assert(WIDE_TROUBLE_EXP == -900, "WIDE_RANGE_MIN is 2^WIDE_TROUBLE_EXP");
 // FULL: n == NP (no padded lanes; the row pitch is a constant)
 template <int NP, int KIND, bool LAZY = false, bool FULL = false>
 __global__ __launch_bounds__(64) void k_wide_fwd(const WideModel m, const int64_t *off, const Segs sg,
