@@ -376,7 +376,8 @@ struct Segs {
 // backward pass only uses alpha through scale-free ratios, and the log-likelihood of a segment
 // telescopes: log sum(alpha at the last step) - log sum(alpha at the entry) + ln 2 * (exponents
 // removed in between).  A vector whose largest element falls below 2^-900 between two refreshes
-// raises flags[2]; the host then repeats the E-step with the per-step normalisation.
+// raises flags[2], and so does a segment's exit or entry sum below 2^-900 (the steps after the last refresh of a
+// trajectory); the host then repeats the E-step with the per-step normalisation.
 #define WIDE_TROUBLE_EXP (-900)
 // the same bound for a sum taken between two refreshes (the score kernels' exit and entry sums)
 constexpr double WIDE_RANGE_MIN = 0x1p-900;
@@ -501,8 +502,12 @@ __global__ __launch_bounds__(64) void k_wide_fwd(const WideModel m, const int64_
     if (real)
         a_exit[(int64_t)s * n + j] = a;
     if constexpr (LAZY) {
+        // the refresh looks at the steps before it; the one to three steps between the last refresh and the end of a
+        // trajectory (all of a trajectory of one to three steps) are looked at here: an exit sum below the refresh's
+        // range may have lost bits to the denormal grid, and so have the alpha rows stored since (no rescue of rows in
+        // the denormal range in this form: wide_emit<.., RESCUE = !LAZY>).  The entry sum is taken right after a refresh
         const double S_end = wgroup_sum<NP>(a);
-        trouble |= !(S_end > 0.0) || !(S_start > 0.0);
+        trouble |= !(S_end >= WIDE_RANGE_MIN) || !(S_start >= WIDE_RANGE_MIN) || !(S_end < INFINITY);
         if (j == 0) {
             logL_seg[s] = (log(S_end) - log(S_start)) + (double)eP * 0.693147180559945309417232121458;
             if (trouble)
@@ -677,7 +682,9 @@ __global__ __launch_bounds__(64) void k_wide_bwd(const WideModel m, const int64_
         double gam;
         {
             double g = a * b, Sg = wgroup_sum<NP>(g);
-            if (!(Sg >= 0x1p-959) && Sg > 0.0) { // (as in the step below)
+            // (as in the step below.  The lazy form rescues here too: the alpha row is a segment's exit row, which
+            // k_wide_fwd<.., LAZY> holds to 2^-900 -- a sum this small is then beta's doing, and beta keeps its bits)
+            if (!(Sg >= 0x1p-959) && Sg > 0.0) {
                 g = a * ldexp(b, 900);
                 Sg = wgroup_sum<NP>(g);
             }
